@@ -15,8 +15,19 @@ running under a launcher.  For N>1 every rank maps its own 10 M distinct pairs p
 replicated, no data-path collective in the mapping itself) and the per-read records of every batch are gathered to rank 0
 over RCCL inside the timed region (the SAM-order gather of north_star; --no-gather switches it off).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) carrying `roofline` (dominant kernel, live HIP-event time vs
-algorithmic bytes) and `cpu_baseline` (the oracle timed on a bounded sample of the same reads on the host cores).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and prints the line (`value`, `ms_per_step`, the
+kernels' times in the timed region, the work counters).  `--full` adds everything that takes runs of its own: more runs of the same steps,
+the sustained pass, the secondary rates, one batch in flight, `roofline` (dominant kernel, live HIP-event time vs algorithmic bytes),
+`cpu_baseline` (the oracle timed on a bounded sample of the same reads on the host cores, with a parity check), accuracy, the
+command line end to end and, on one GPU with the default workload, the human-like leg.
+
+`--dump-outputs DIR` writes, after the timed steps, what the timed path returned in its last step for a fixed sample (the first
+DUMP_PAIRS pairs of every batch of the step), as the reference expansion of the compact records (host.expand_compact), in float64:
+  reads.npy      [reads, 9]   batch, read, score, sub_score, mis_num, mapq, n_rep, best, n_sj
+  reports.npy    [reports, 10] batch, read, aln_score, sj_type, flag, paired_idx, chr, bdir, pos, n_cigar   (in report order)
+  cigar.npy      [ops]        the CIGAR ops of those reports in report order (length << 4 | op)
+  junctions.npy  [tuples, 5]  batch, g1, g2, type, read_idx
+The inputs are a pure function of the arguments (seeded genome and batches), so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -97,10 +108,12 @@ def genome_spec(arg):
 
 
 PREP_S = {}                                       # rank 0: seconds spent making the synthetic genome and building its index in this run
+DUMP_PAIRS = 4096                                 # --dump-outputs: the first this many pairs of every batch of the last timed step
 
 
-def prepare_index(cache_dir, genome, rank, barrier, n_introns=0, repeat_scale=1.0, model="planted"):
-    """genome: a length in bp (one chromosome) or (names, lengths).  Rank 0 generates and indexes it once per box."""
+def prepare_index(cache_dir, genome, rank, barrier, n_introns=0, repeat_scale=1.0, model="planted", on_genome=None):
+    """genome: a length in bp (one chromosome) or (names, lengths).  Rank 0 generates and indexes it once per box.  on_genome(g), when
+    given, is called on rank 0 as soon as the genome exists, before its index is built (the caller's host work overlaps the build)."""
     import numpy as np
     import torch
     from dart_amd import synth, index_build
@@ -109,24 +122,30 @@ def prepare_index(cache_dir, genome, rank, barrier, n_introns=0, repeat_scale=1.
     prefix = os.path.join(cache_dir, "g%d" % total + ("c%d" % len(lengths) if len(lengths) > 1 else "") + ("_i%d" % n_introns if n_introns else "") +
                           ("_r%g" % repeat_scale if repeat_scale != 1.0 else "") + ("_%s" % model if model != "planted" else ""))
     done = prefix + ".done"
+    g = None
     if rank == 0 and not os.path.exists(done):
         os.makedirs(cache_dir, exist_ok=True)
         t = time.time()
         g = synth.make_genome(lengths, seed=20, repeat_scale=repeat_scale, n_introns=n_introns, names=names, model=model)
-        np.save(prefix + ".codes.npy", g.codes)
-        np.save(prefix + ".introns.npy", g.introns)
         PREP_S["genome_generated_s"] = round(time.time() - t, 1)
         log("[bench] genome %d bp generated in %.1f s" % (total, time.time() - t))
+        if on_genome is not None:
+            on_genome(g)
         t = time.time()
         index_build.build_index_from_genome(g, prefix, log=log)
         torch.cuda.empty_cache()
         PREP_S["index_build_s"] = round(time.time() - t, 1)      # di_build_files (libdartindex.so): the five files of this genome, written
         log("[bench] index built in %.1f s" % (time.time() - t))
+        t = time.time()
+        np.save(prefix + ".codes.npy", g.codes)                  # (for the next run on this box: the codes are in memory for this one)
+        np.save(prefix + ".introns.npy", g.introns)
         open(done, "w").write("ok")
+        PREP_S["genome_saved_s"] = round(time.time() - t, 1)
     barrier()
-    codes = np.load(prefix + ".codes.npy")
-    ipath = prefix + ".introns.npy"
-    g = synth.Genome(list(names), list(lengths), codes, np.load(ipath) if os.path.exists(ipath) else np.zeros((0, 3), np.int64))
+    if g is None:
+        codes = np.load(prefix + ".codes.npy")
+        ipath = prefix + ".introns.npy"
+        g = synth.Genome(list(names), list(lengths), codes, np.load(ipath) if os.path.exists(ipath) else np.zeros((0, 3), np.int64))
     return prefix, g
 
 
@@ -142,7 +161,7 @@ def self_launch(args, argv):
 
 
 def with_human_like_leg(args, argv):
-    """The default run on one GPU: this process stays off the GPU and runs two children one after the other, each alone on it -- the measurement
+    """The --full run on one GPU: this process stays off the GPU and runs two children one after the other, each alone on it -- the measurement
     itself (`--as-child`: everything this file did before round 4) and, if the time budget allows, the same timed region on the human-like genome
     (`--genome-model human`: about half of the genome in repeat classes, what a real human index looks like to the seeding stage).  A child that
     ran inside the first one's process found that process's sixteen hardware queues still mapped and lost 8 %.  Prints the first child's line
@@ -160,7 +179,7 @@ def with_human_like_leg(args, argv):
     else:
         try:
             t = time.time()
-            h = subprocess.run([sys.executable, me, "--as-child", "--genome-model", "human", "--no-secondary", "--no-cpu-baseline", "--sustained-s", "12", "--steps", str(args.steps), "--warmup", str(args.warmup),
+            h = subprocess.run([sys.executable, me, "--as-child", "--full", "--genome-model", "human", "--no-secondary", "--no-cpu-baseline", "--sustained-s", "12", "--steps", str(args.steps), "--warmup", str(args.warmup),
                                 "--pairs", str(args.pairs), "--batches", str(args.batches), "--inflight", str(args.inflight), "--mis", str(args.mis), "--cache", args.cache],
                                stdout=subprocess.PIPE, timeout=400)
             hl = json.loads(h.stdout.decode().strip().splitlines()[-1])
@@ -170,7 +189,7 @@ def with_human_like_leg(args, argv):
                 "kernels_ms": hl["kernels_ms"], "kernels_ms_one_batch_in_flight": hl["kernels_ms_one_batch_in_flight"], "sustained": hl.get("sustained"),
                 "roofline": {k: hl["roofline"].get(k) for k in ("kernel", "achieved", "peak", "unit", "frac", "traffic", "kernel_ms_standalone", "frac_of_random_line_ceiling", "seeding_mixed_ceiling", "fingerprint", "stages")},
                 "counters_per_launch": {k: hl["counters_per_launch"].get(k) for k in ("steps", "steps_executed", "occ_blocks_executed", "seeds", "candidates", "nw_calls", "reseed_calls", "general_path_units", "wave_chained_units")},
-                "what": "`bench.py --genome-model human --no-secondary --no-cpu-baseline` with this run's steps / warm-up / batches, a second child process after the first one has left the GPU "
+                "what": "`bench.py --full --genome-model human --no-secondary --no-cpu-baseline` with this run's steps / warm-up / batches, a second child process after the first one has left the GPU "
                         "(its own genome, index and batches: %.0f s)" % (time.time() - t)}
         except Exception as e:
             line["human_like"] = {"skipped": "the child run failed: " + repr(e)}
@@ -351,9 +370,10 @@ def run_cli(dart_exe, prefix, g, label, seed_pairs, args, cpu_pairs=0, gz_pairs=
 class Batch:
     """one distinct batch of pairs: ASCII and packed forms in page-locked host memory"""
 
-    def __init__(self, lib, g, pairs, rlen, seed, sub_rate, indel_frac, spliced, want_truth=False, rows=None):
+    def __init__(self, lib, g, pairs, rlen, seed, sub_rate, indel_frac, spliced, want_truth=False, rows=None, ascii=True):
         """rows = (a, b): only pairs [a, b) of the batch that `seed` generates (a rank's share of a global batch in --total-pairs mode;
-        the batch is a pure function of (seed, pairs), so the union over ranks is the same reads whatever the number of ranks)"""
+        the batch is a pure function of (seed, pairs), so the union over ranks is the same reads whatever the number of ranks).
+        ascii=False: the packed form only (a run that never hands the ASCII form to the library nor to the oracle)"""
         import numpy as np
         from dart_amd import synth, host
         r = synth.make_reads(g, pairs, rlen=rlen, seed=seed, sub_rate=sub_rate, indel_frac=indel_frac, n_frac=0.002, spliced_frac=spliced, return_truth=want_truth)
@@ -365,16 +385,17 @@ class Batch:
             if self.truth is not None:
                 self.truth = {k: v[rows[0]:rows[1]] for k, v in self.truth.items()}
         arr = host.interleave_pairs(m1, m2)
-        so, rl, flat = host.pack_reads(arr)
         words, nlist = host.pack_reads_2bit(arr)
-        self.n = len(rl); self.rlen = rlen; self.W2 = int(words.shape[1]); self.n_n = len(nlist)
-        self.so = host.PinnedArray(lib, (self.n,), np.uint32); self.so.a[:] = so
-        self.rl = host.PinnedArray(lib, (self.n,), np.uint16); self.rl.a[:] = rl
-        self.seq = host.PinnedArray(lib, (len(flat) + 64,), np.uint8); self.seq.a[:len(flat)] = flat
+        self.n = len(arr); self.rlen = rlen; self.W2 = int(words.shape[1]); self.n_n = len(nlist)
+        if ascii:
+            so, rl, flat = host.pack_reads(arr)
+            self.so = host.PinnedArray(lib, (self.n,), np.uint32); self.so.a[:] = so
+            self.rl = host.PinnedArray(lib, (self.n,), np.uint16); self.rl.a[:] = rl
+            self.seq = host.PinnedArray(lib, (len(flat) + 64,), np.uint8); self.seq.a[:len(flat)] = flat
+            self.bytes_ascii = len(flat) + 6 * self.n
         self.words = host.PinnedArray(lib, words.shape, np.uint32); self.words.a[:] = words
         self.nlist = host.PinnedArray(lib, (max(self.n_n, 1),), np.uint32); self.nlist.a[:self.n_n] = nlist
-        self.bases = int(rl.sum())
-        self.bytes_ascii = len(flat) + 6 * self.n
+        self.bases = self.n * rlen
         self.bytes_packed = words.nbytes + 4 * self.n_n
 
 
@@ -451,6 +472,27 @@ class Worker:
             return host.BatchResult(r, p, cg, self.o_s.a[:u[2]].copy())
         return host.BatchResult(self.o_r.a[:self.last_n].copy(), self.o_p.a[:u[0]].copy(), self.o_c.a[:u[1]].copy(), self.o_s.a[:u[2]].copy())
 
+    def snapshot(self, n_pairs, into):
+        """--dump-outputs: copies of what the last map() returned, as much as the sample of its first n_pairs pairs needs -- the sample's read
+        records; every report and every stored CIGAR op (compact: a report's ops start behind the whole first region when they lie in the second).
+        into = (report bytes, op words): buffers whose pages are already touched, so that the copy inside the timed region is a plain memcpy"""
+        import numpy as np
+        u = [int(x) for x in self.used]
+        k = min(self.last_n, 2 * n_pairs)
+        compact = self.last_records == "compact"
+        src_p = self.c_p[:u[0]] if compact else self.o_p.a[:u[0]]
+
+        def keep(a, buf):
+            if buf.nbytes < a.nbytes:                      # (the arrays grew inside the timed region)
+                return a.copy()
+            np.copyto(buf[:a.nbytes], a.view(np.uint8))    # (as bytes: a copy of records field by field is many times slower)
+            return buf[:a.nbytes].view(a.dtype)
+        p, cig = keep(src_p, into[0]), keep(self.o_c.a[:u[1]], into[1])
+        if compact:
+            r = self.c_r[:k].copy()
+            return "compact", self.last_rlen, r, p, cig, self.o_s.a[:int(r["n_sj"].sum())].copy()
+        return "full", self.last_rlen, self.o_r.a[:k].copy(), p, cig, self.o_s.a[:u[2]].copy()
+
     def out_bytes(self, n):
         u = [int(x) for x in self.used]
         return (12 * n + 16 * u[0] if self.last_records == "compact" else 36 * n + 40 * u[0]) + 4 * u[1] + 24 * u[2]
@@ -463,6 +505,53 @@ T_PHASE = []          # (name, wall clock) marks of the run's phases: rank 0 pri
 
 def phase(name):
     T_PHASE.append((name, time.time()))
+
+
+def sample_records(snap):
+    """a Worker.snapshot -> (reads, reports, CIGAR ops, junction tuples) of the sample in the full record types, the reports in read order and
+    their ops in report order: what the caller of the timed entry point has for those reads"""
+    import numpy as np
+    from dart_amd import host
+    kind, rlen, r, p, cig, sj = snap
+    nrep = int(r["n_rep"].sum())
+    if kind == "compact":
+        rep_ = p[:nrep]
+        plain = rep_["n_cigar"] == host.CIGAR_FULL_MATCH
+        stored = np.where(plain, 0, rep_["n_cigar"]).astype(np.int64)
+        second = (rep_["pad"] & 1) != 0
+        s1_all = int(np.where((p["n_cigar"] == host.CIGAR_FULL_MATCH) | ((p["pad"] & 1) != 0), 0, p["n_cigar"]).astype(np.int64).sum())   # the whole first region
+        s1, s2 = int(stored[~second].sum()), int(stored[second].sum())
+        reads, reports, ops = host.expand_compact(r, rep_, np.concatenate([cig[:s1], cig[s1_all:s1_all + s2]]), np.full(len(r), rlen, np.uint16))
+        return reads, reports, ops, sj
+    rows = np.concatenate([np.arange(o, o + n) for o, n in zip(r["rep_off"], r["n_rep"])]).astype(np.int64) if nrep else np.zeros(0, np.int64)
+    reports = p[rows]
+    ops = np.concatenate([cig[o:o + n] for o, n in zip(reports["cigar_off"], reports["n_cigar"])]) if len(reports) else np.zeros(0, np.uint32)
+    srows = np.concatenate([np.arange(o, o + n) for o, n in zip(r["sj_off"], r["n_sj"])]).astype(np.int64) if int(r["n_sj"].sum()) else np.zeros(0, np.int64)
+    return r, reports, ops, sj[srows]
+
+
+def dump_outputs(out_dir, captured):
+    """--dump-outputs: the sample of every batch of the last timed step as float64 arrays (the module's docstring lists the columns)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cols = {"reads": [], "reports": [], "cigar": [], "junctions": []}
+    captured = {b: v for b, v in captured.items() if len(v) == 6}          # (a batch that no timed step mapped still holds its empty buffers)
+    for b in sorted(captured):
+        reads, reports, ops, sj = sample_records(captured[b])
+        n = len(reads)
+        cols["reads"].append(np.column_stack([np.full(n, b), np.arange(n)] + [reads[f] for f in ("score", "sub_score", "mis_num", "mapq", "n_rep", "best", "n_sj")]))
+        owner = np.repeat(np.arange(n), reads["n_rep"].astype(np.int64))
+        cols["reports"].append(np.column_stack([np.full(len(reports), b), owner] + [reports[f] for f in ("aln_score", "sj_type", "flag", "paired_idx", "chr", "bdir", "pos", "n_cigar")]))
+        cols["cigar"].append(ops)
+        cols["junctions"].append(np.column_stack([np.full(len(sj), b)] + [sj[f] for f in ("g1", "g2", "type", "read_idx")]))
+    width = {"reads": 9, "reports": 10, "cigar": None, "junctions": 5}
+    total = 0
+    for name, parts in cols.items():
+        a = np.concatenate(parts).astype(np.float64) if parts else np.zeros((0, width[name]) if width[name] else 0, np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 << 20, "the dump is larger than 64 MB: %d bytes" % total
+    log("[bench] outputs of the last timed step (%d batches, first %d pairs each) written to %s: %.1f MB" % (len(captured), DUMP_PAIRS, out_dir, total / 1e6))
 
 
 def main():
@@ -526,7 +615,16 @@ def main():
     ap.add_argument("--inflight", type=int, default=int(os.environ.get("DART_BENCH_INFLIGHT", "12")),
                     help="batches in flight per GPU: contexts sharing one index, one host thread each (dg_clone)")
     ap.add_argument("--cache", default=os.environ.get("DART_BENCH_CACHE", "/tmp/dart_bench_cache"))
+    ap.add_argument("--full", action="store_true",
+                    help="also everything that takes runs of its own (repeats, sustained pass, secondary rates, one batch in flight, roofline, CPU baseline and "
+                         "parity sample, accuracy, command line end to end, human-like leg); a plain run measures the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step (a fixed sample: see the module's docstring) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        # the headline figure only: no pass after the timed region, no CPU or command-line legs, no second child
+        args.no_secondary = args.no_cpu_baseline = True
+        args.repeats, args.sustained_s, args.cli_pairs, args.human_like_budget = 0, 0.0, 0, 0.0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     T_PHASE.append(("start", time.time()))
@@ -542,7 +640,7 @@ def main():
         sys.exit(2)
 
     import threading
-    from concurrent.futures import ThreadPoolExecutor
+    from concurrent.futures import ThreadPoolExecutor, wait
     import numpy as np
     import torch
     from dart_amd import synth, host
@@ -565,22 +663,7 @@ def main():
         if dist is not None:
             dist.barrier()
 
-    label, gnames, glens = genome_spec(args.genome)
-    try:
-        prefix, g = prepare_index(args.cache, (gnames, glens), rank, barrier, args.introns, args.repeat_scale, args.genome_model)
-    except Exception as e:                         # e.g. not enough memory for the 6.2 G-symbol suffix sort: say so, use chr20
-        if world > 1 or len(glens) == 1:
-            raise
-        log("[bench] %s could not be indexed here (%r): falling back to the chr20-sized genome" % (label, e))
-        torch.cuda.empty_cache()
-        label, gnames, glens = genome_spec("chr20")
-        label = "FALLBACK (GRCh38-sized index build failed) " + label
-        prefix, g = prepare_index(args.cache, (gnames, glens), rank, barrier, args.introns, args.repeat_scale, args.genome_model)
-    phase("genome + index (rank 0 builds, the others wait)")
-    # ---- the step's distinct batches, in page-locked host memory (before the library context is created: the index builder has just released
-    #      > 100 GB of HBM, which the driver clears in the background; allocations that need those pages wait for it -- seconds of hipMalloc) ----
     lib = host._load_lib()
-    t = time.time()
     strong = args.total_pairs > 0
     if not strong:
         specs = [(1000 + 100 * rank + j, None) for j in range(max(1, args.batches))]
@@ -601,15 +684,37 @@ def main():
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             specs += [(0, (0, 0))] * (int(tt.item()) - n_local)
     nb = len(specs)
-    with ThreadPoolExecutor(max_workers=min(4, nb)) as ex:
-        batches = list(ex.map(lambda js: Batch(lib, g, args.pairs if js[1] is None else min(args.pairs, args.total_pairs - (js[0] - 1000) * args.pairs) if js[1][1] else 1,
-                                               args.rlen, js[0], args.sub_rate, args.indel_frac, args.spliced, want_truth=(js is specs[0]), rows=js[1]), specs))
-    n_reads = max(b.n for b in batches)
-    reads_per_step = 2 * args.total_pairs if strong else 2 * args.pairs * nb * world          # whole job, all ranks
-    if rank == 0:
-        log("[bench] %d distinct batches of %d pairs generated in %.1f s" % (nb, args.pairs, time.time() - t))
+    # ---- the step's distinct batches, in page-locked host memory, made by host threads while rank 0 builds the index and the library context
+    #      is created (the index builder has just released > 100 GB of HBM, which the driver clears in the background; the context's allocations
+    #      that need those pages wait for it -- seconds of hipMalloc that the batches' host work overlaps) ----
+    t_b = [0.0]
+    pool = ThreadPoolExecutor(max_workers=max(1, min(nb, host_cores())))
+    pending = []
 
-    phase("this rank's batches")
+    def start_batches(g_):
+        t_b[0] = time.time()
+        pending[:] = [pool.submit(Batch, lib, g_, args.pairs if js[1] is None else min(args.pairs, args.total_pairs - (js[0] - 1000) * args.pairs) if js[1][1] else 1,
+                                  args.rlen, js[0], args.sub_rate, args.indel_frac, args.spliced, want_truth=(js is specs[0]), rows=js[1],
+                                  ascii=args.full or args.input == "ascii") for js in specs]
+
+    label, gnames, glens = genome_spec(args.genome)
+    try:
+        prefix, g = prepare_index(args.cache, (gnames, glens), rank, barrier, args.introns, args.repeat_scale, args.genome_model, on_genome=start_batches)
+    except Exception as e:                         # e.g. not enough memory for the 6.2 G-symbol suffix sort: say so, use chr20
+        if world > 1 or len(glens) == 1:
+            raise
+        log("[bench] %s could not be indexed here (%r): falling back to the chr20-sized genome" % (label, e))
+        for f_ in pending:                         # (batches of the genome that was given up)
+            f_.cancel()
+        wait(pending)
+        pending[:] = []
+        torch.cuda.empty_cache()
+        label, gnames, glens = genome_spec("chr20")
+        label = "FALLBACK (GRCh38-sized index build failed) " + label
+        prefix, g = prepare_index(args.cache, (gnames, glens), rank, barrier, args.introns, args.repeat_scale, args.genome_model, on_genome=start_batches)
+    phase("genome + index (rank 0 builds, the others wait)")
+    if not pending:                                # (the genome came from the cache)
+        start_batches(g)
     ix = host.Index(prefix)
     params = host.default_params(paired=1, max_mismatch=args.mis, max_intron=args.max_intron)
     t = time.time()
@@ -619,6 +724,14 @@ def main():
     init_report = gpu.init_report()
     if rank == 0:
         log("[bench] dg_init_files %.2f s: %s" % (time.time() - t, gpu.init_report()))
+    phase("library start-up")
+    batches = [f_.result() for f_ in pending]
+    pool.shutdown()
+    n_reads = max(b.n for b in batches)
+    reads_per_step = 2 * args.total_pairs if strong else 2 * args.pairs * nb * world          # whole job, all ranks
+    if rank == 0:
+        log("[bench] %d distinct batches of %d pairs generated in %.1f s" % (nb, args.pairs, time.time() - t_b[0]))
+    phase("this rank's batches (made during the two phases before)")
 
     # `inflight` contexts share the index; each is driven by its own host thread, the way the reference runs ReadMapping in -t
     # threads.  Work item i = batch i % nb on context i % inflight; a step = nb items.
@@ -687,11 +800,12 @@ def main():
 
     stagger_s = float(os.environ.get("DART_BENCH_STAGGER_MS", "1.0")) * 1e-3
 
-    def run_items(n_items, mode, ws=workers, first_item=0, bl=None, static=False):
+    def run_items(n_items, mode, ws=workers, first_item=0, bl=None, static=False, capture=None):
         """n_items work items over the contexts ws, each driven by its own host thread.  A context takes the NEXT item when it is free (the reference's threads
         pull the next chunk under a lock, Mapping.cpp:598-603: GetNextChunk) -- rounds 1-4 dealt item i to context i mod n, and a long run then lasted as long as
         its slowest context (the contexts of a process do not progress at one rate: profiles/r05/f_sustained_*); static=True keeps the deal (every context exactly
-        its share: the passes that must leave a batch in every context).  The main thread takes the items in order: gathers (N > 1) happen in item order."""
+        its share: the passes that must leave a batch in every context).  The main thread takes the items in order: gathers (N > 1) happen in item order.
+        capture (a dict of Worker.snapshot buffers by batch): the context that mapped an item of the last len(bl) items replaces them by a snapshot."""
         bl_ = batches if bl is None else bl
         owner = [-1] * n_items                              # which context mapped item i
         cv = threading.Condition()
@@ -725,6 +839,9 @@ def main():
                         break
                     mine += 1
                     ws[k].map(bl_[(first_item + i) % len(bl_)], mode)
+                    if capture is not None and i >= n_items - len(bl_):
+                        b_ = (first_item + i) % len(bl_)
+                        capture[b_] = ws[k].snapshot(DUMP_PAIRS, capture[b_])
                     with cv:
                         owner[i] = k; done_flag[i] = 1
                         cv.notify_all()
@@ -761,10 +878,10 @@ def main():
         if errs:
             raise errs[0]
 
-    def timed(n_items, mode, ws=workers, bl=None):
+    def timed(n_items, mode, ws=workers, bl=None, capture=None):
         barrier(); torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run_items(n_items, mode, ws, 0, bl)
+        run_items(n_items, mode, ws, 0, bl, capture=capture)
         barrier(); torch.cuda.synchronize()
         el = time.perf_counter() - t0
         if dist is not None:
@@ -773,15 +890,24 @@ def main():
             el = float(tt.item())
         return el
 
-    phase("library start-up + first batch of every context")
+    phase("first batch of every context")
     run_items(args.warmup * nb, args.input)
     for w in workers:
         w.kern = {}; w.n_runs = 0
     phase("warm-up steps")
     if RATE_LOG is not None:
         del RATE_LOG[:]
-    elapsed = timed(args.steps * nb, args.input)
+    captured = None
+    if args.dump_outputs:
+        cap_p = max(int(w.caps[0]) for w in workers) * (host.REPORT_C.itemsize if args.records == "compact" else host.REPORT_OUT.itemsize)
+        cap_c = max(int(w.caps[1]) for w in workers) * 4
+        captured = {b_: (np.ones(cap_p, np.uint8), np.ones(cap_c, np.uint8)) for b_ in range(nb)}
+    elapsed = timed(args.steps * nb, args.input, capture=captured)
     phase("timed region")
+    if captured is not None and rank == 0:
+        dump_outputs(args.dump_outputs, captured)
+        captured = None
+        phase("outputs of the last step written")
     if RATE_LOG is not None and rank == 0:
         t_wall0 = time.time() - (time.perf_counter() - RATE_LOG[0][1]) if RATE_LOG else 0
         with open(os.environ["DART_BENCH_RATE_LOG"], "w") as f:
@@ -879,12 +1005,14 @@ def main():
         run_items(len(workers), "resident", static=True)   # (every context holds the batch it mapped last)
         secondary["value_device_resident"] = round(reads_per_step / nb * items / timed(items, "resident") / 1e6, 3)
     # the same item with ONE batch in flight, for per-kernel durations without other batches' kernels sharing the GPU
-    w0 = workers[0]; w0.kern = {}; w0.n_runs = 0
-    if args.no_secondary:
-        w0.map(batches[0], args.input)                     # (resident runs need an uploaded batch)
-        w0.kern = {}; w0.n_runs = 0
-    run_items(2, "resident", [w0])
-    iso = {k: v / 2 for k, v in w0.kern.items()}
+    iso = {}
+    if args.full:
+        w0 = workers[0]; w0.kern = {}; w0.n_runs = 0
+        if args.no_secondary:
+            w0.map(batches[0], args.input)                 # (resident runs need an uploaded batch)
+            w0.kern = {}; w0.n_runs = 0
+        run_items(2, "resident", [w0])
+        iso = {k: v / 2 for k, v in w0.kern.items()}
     do_gather = gather_timed
     barrier(); torch.cuda.synchronize()
 
@@ -933,110 +1061,112 @@ def main():
 
     value = reads_per_step * args.steps / elapsed / 1e6
 
-    # ---- roofline of the dominant kernel: algorithmic bytes (reference algorithm + layout) of one launch / its mean
-    #      HIP-event duration in the timed region ----
-    alg = {
-        "k_seed": 64 * counters["occ_blocks"] + batches[0].bases + 16 * n_reads,
-        "k_locate": 64 * counters["lf_steps"] + 8 * counters["sa_lookups"] + 8 * counters["seeds"],
-    }
     for d_ in (kern, iso):                                   # (the re-seeding kernels run on the second stream, beside k_report)
         if "k_reseed(overlapped)" in d_:
             d_["k_reseed"] = d_.pop("k_reseed(overlapped)")
-    alg["k_reseed"] = counters["reseed_window"] // 4 + 64 * counters["reseed_calls"]      # window bases at 2 bit/base, streamed once (B_ref)
-    stage_kernels = [k for k in ("k_seed", "k_locate", "k_pair", "k_report", "k_chain_heavy", "k_reseed") if k in kern]
-    per_read_B = (alg["k_seed"] + alg["k_locate"]) / n_reads
-    # PMC traffic: only from passes taken with THESE kernel sources on THIS workload (profiles/run_profile.sh stores the
-    # fingerprint of the bench line it profiled in profiles/traffic.json); anything else says nothing about this run
-    fingerprint = {"csrc_sha256": kernel_sources_sha256(),
-                   "workload": "genome=%s model=%s pairs=%d rlen=%d spliced=%g introns=%d repeat_scale=%g mis=%d sub=%g indel=%g" %
-                               (args.genome, args.genome_model, args.pairs, args.rlen, args.spliced, args.introns, args.repeat_scale, args.mis, args.sub_rate, args.indel_frac)}
-    tj = {}
-    for tname in ("traffic.json", "traffic_human.json", "traffic_spliced.json"):         # (the default workload's passes; the human-like genome's; the spliced 2x151 shape's)
-        tpath = os.path.join(ROOT, "profiles", tname)
-        if os.path.exists(tpath):
-            try:
-                cand = json.load(open(tpath))
-                if cand.get("_fingerprint") == fingerprint:
-                    tj = cand
-                    break
-            except Exception:
-                pass
-    # The dominant kernel of an HBM roofline: the one that moves the most bytes through the memory side (PMC; the seeding stage: half of a
-    # batch's traffic) -- without a matching PMC profile, the one that runs longest alone.  (The longest stand-alone stage alone is a coin
-    # flip by now: seeding and the general-path report are both ~1.0 ms.)  `stages` carries the same figures for every stage either way.
-    ms_of = lambda k: iso.get(k) or kern[k]
-    dom = max(stage_kernels, key=(lambda k: tj.get(k, 0)) if any(tj.get(k) for k in stage_kernels) else ms_of)
-    traffic = tj.get(dom)
-    stages = {k: {"ms_standalone": round(ms_of(k), 4), "ms_in_timed_region": round(kern[k], 4), "traffic": tj.get(k),
-                  "GBps": round(tj[k] / (ms_of(k) * 1e-3) / 1e9, 1) if tj.get(k) else None,
-                  "frac": round(tj[k] / (ms_of(k) * 1e-3) / 8e12, 5) if tj.get(k) else None,
-                  "frac_of_random_line_ceiling": round(tj[k] / (ms_of(k) * 1e-3) / 2.58e12, 4) if tj.get(k) else None} for k in stage_kernels}
-    dom_bytes = alg.get(dom)
-    if dom_bytes is None:      # pair / report kernels: their own input and output (seeds in, records out, read bases compared)
-        dom_bytes = 8 * counters["seeds"] + 90 * n_reads
-    own = {
-        # Occ blocks + 16-byte table entries + per located search one 8-byte SA entry and ~2 text windows of 20 bytes
-        # + the read's 2-bit/mask words in + 16-byte hits out
-        "k_seed": 64 * counters.get("occ_blocks_executed", 0) + 16 * counters.get("ktab_lookups", 0) + 48 * counters.get("direct_extensions", 0)
-                  + 56 * n_reads + 16 * counters["seeds"],
-        "k_locate": 64 * counters.get("lf_steps_executed", 0) + 8 * counters["sa_lookups"] + 8 * counters["seeds"],
-    }
-    own_bytes = int(own.get(dom, dom_bytes))
-    ms_alone = ms_of(dom)
-    # `achieved` is a HARDWARE statement: the bytes the dominant kernel really moves through the memory side (PMC FETCH_SIZE + WRITE_SIZE of one
-    # launch; without a matching profile: the bytes it requests, from the live counters -- a lower bound) over the launch's stand-alone
-    # duration, against 8 TB/s.  The rate on the REFERENCE algorithm's bytes stays beside it as `algorithmic_*`: the prefix
-    # table, the full SA and the direct text comparison remove most of those bytes, so that rate is a work-elimination factor, not a
-    # fraction of any hardware limit.
-    moved = traffic if traffic else own_bytes
-    achieved = moved / (ms_alone * 1e-3) / 1e9
-    roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
-                "frac": round(achieved / 8000.0, 5), "traffic": traffic,
-                "achieved_basis": ("PMC FETCH_SIZE + WRITE_SIZE bytes of one launch (profiles/traffic.json: same kernel sources, same workload)" if traffic else
-                                   "bytes the kernel requests per launch, from its live work counters (no PMC pass matches these kernel sources and this workload): a lower bound of the traffic")
-                                  + " / the launch's stand-alone HIP-event duration measured in this run",
-                "kernel_ms_standalone": round(ms_alone, 4), "kernel_ms_in_timed_region": round(kern[dom], 4),
-                "own_requested_bytes_per_launch": own_bytes,
-                # what the memory system allows for THIS access pattern, measured with known bytes (profiles/probes/fetch_calib.hip,
-                # profiles/r04/e_fetch_size_calibration_random_accesses.txt): random 64-byte accesses over the 3.1 GB Occ array run at 40.3 G lines/s
-                # = 2.58 TB/s from 4 waves per CU on (16-byte accesses, which round 2's probe used: 49 G/s); a random 128-byte access is ONE fabric
-                # request but runs at half that rate (21-22 G/s): the bytes, not the requests, are what the memory side limits.  The same probe
-                # calibrates the counter: FETCH_SIZE is exact for random accesses of up to 64 bytes (one 64-byte request each, also for 16 bytes)
-                # and reports half the bytes of 128-byte and wider ones (MI355X_MICROARCH.md's note on wide streams) -- the seeding kernels' accesses
-                # are 8 to 64 bytes wide, so their FETCH_SIZE needs no correction
-                "random_64B_line_ceiling_GBps": 2580.0,
-                "frac_of_random_line_ceiling": round(achieved / 2580.0, 4),
-                # ... per class of access (profiles/probes/footprint_sweep.sh, profiles/r04/y_random_line_rate_vs_footprint.txt): a random look-up made with ONE load
-                # instruction (16 bytes of the prefix table, 8 of the suffix array) runs at 46-49 G/s whatever the footprint (3 to 118 GB); a random 64-byte
-                # access is FOUR 16-byte loads, each translated on its own once the footprint is beyond the translation caches' reach: 39 G/s over the 3.1 GB
-                # Occ array (UTCL1 misses 31 %), 21 G/s over 8 GB, 19 G/s over 16-200 GB (99.5 %) -- ~76 G load instructions/s is what the translation path
-                # takes.  The seeding kernels make their wide accesses only in the 3.1 GB Occ array and the 0.8 GB text, so what the memory side allows them is
-                "seeding_mixed_ceiling": (lambda one, wide: (lambda ms_min: {
-                    "single_load_lookups": int(one), "occ_blocks_and_text_windows": int(wide), "single_load_rate_G_per_s": 46.0, "wide_rate_G_per_s": 39.3, "streamed_bytes": int(max(0, moved - 64 * (one + wide))),
-                    "ms_min": round(ms_min, 4), "frac_of_mixed_ceiling": round(ms_min / ms_alone, 4),
-                    "what": "single-load look-ups = prefix-table entries + suffix-array entries read by the seeding kernels, wide = Occ blocks + text windows of the direct comparisons "
-                            "(1.5 lines each), the rest of the launch's PMC bytes streamed at 8 TB/s; ms_min = single / 46 G/s + wide / 39.3 G/s + streamed / 8 TB/s"})(
-                        (one / 46.0e9 + wide / 39.3e9 + max(0, moved - 64 * (one + wide)) / 8e12) * 1e3))(
-                    counters.get("ktab_lookups", 0) + counters.get("seedq_slots_locate", 0), counters.get("occ_blocks_executed", 0) + 1.5 * counters.get("direct_extensions", 0)) if dom == "k_seed" else None,
-                "algorithmic_bytes_per_launch": int(dom_bytes),
-                "algorithmic_GBps_standalone": round(dom_bytes / (ms_alone * 1e-3) / 1e9, 1),
-                "algorithmic_GBps_in_timed_region": round(dom_bytes / (kern[dom] * 1e-3) / 1e9, 1),
-                "work_elimination": round(dom_bytes / moved, 2),
-                "fm_bytes_per_read": round(per_read_B, 1),
-                # SURVEY 8d's whole-job form: reads/s x algorithmic bytes per read (this GPU's share of `value`)
-                "whole_job_algorithmic_GBps_per_gpu": round(value / world * 1e6 * per_read_B / 1e9, 1),
-                "fingerprint": fingerprint,
-                "stages": stages,
-                "note": "one launch = one batch of %d reads.  achieved / frac = real bytes over the stand-alone duration (see achieved_basis); algorithmic_* = what the "
-                        "reference's algorithm and layout would fetch for the same reads (SURVEY 8d: 64 B per Occ block of bwt_2occ4, per LF step, 8 B per SA entry), "
-                        "kept as a work-elimination factor" % n_reads}
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel: algorithmic bytes (reference algorithm + layout) of one launch / its mean
+        #      HIP-event duration in the timed region ----
+        alg = {
+            "k_seed": 64 * counters["occ_blocks"] + batches[0].bases + 16 * n_reads,
+            "k_locate": 64 * counters["lf_steps"] + 8 * counters["sa_lookups"] + 8 * counters["seeds"],
+        }
+        alg["k_reseed"] = counters["reseed_window"] // 4 + 64 * counters["reseed_calls"]      # window bases at 2 bit/base, streamed once (B_ref)
+        stage_kernels = [k for k in ("k_seed", "k_locate", "k_pair", "k_report", "k_chain_heavy", "k_reseed") if k in kern]
+        per_read_B = (alg["k_seed"] + alg["k_locate"]) / n_reads
+        # PMC traffic: only from passes taken with THESE kernel sources on THIS workload (profiles/run_profile.sh stores the
+        # fingerprint of the bench line it profiled in profiles/traffic.json); anything else says nothing about this run
+        fingerprint = {"csrc_sha256": kernel_sources_sha256(),
+                       "workload": "genome=%s model=%s pairs=%d rlen=%d spliced=%g introns=%d repeat_scale=%g mis=%d sub=%g indel=%g" %
+                                   (args.genome, args.genome_model, args.pairs, args.rlen, args.spliced, args.introns, args.repeat_scale, args.mis, args.sub_rate, args.indel_frac)}
+        tj = {}
+        for tname in ("traffic.json", "traffic_human.json", "traffic_spliced.json"):         # (the default workload's passes; the human-like genome's; the spliced 2x151 shape's)
+            tpath = os.path.join(ROOT, "profiles", tname)
+            if os.path.exists(tpath):
+                try:
+                    cand = json.load(open(tpath))
+                    if cand.get("_fingerprint") == fingerprint:
+                        tj = cand
+                        break
+                except Exception:
+                    pass
+        # The dominant kernel of an HBM roofline: the one that moves the most bytes through the memory side (PMC; the seeding stage: half of a
+        # batch's traffic) -- without a matching PMC profile, the one that runs longest alone.  (The longest stand-alone stage alone is a coin
+        # flip by now: seeding and the general-path report are both ~1.0 ms.)  `stages` carries the same figures for every stage either way.
+        ms_of = lambda k: iso.get(k) or kern[k]
+        dom = max(stage_kernels, key=(lambda k: tj.get(k, 0)) if any(tj.get(k) for k in stage_kernels) else ms_of)
+        traffic = tj.get(dom)
+        stages = {k: {"ms_standalone": round(ms_of(k), 4), "ms_in_timed_region": round(kern[k], 4), "traffic": tj.get(k),
+                      "GBps": round(tj[k] / (ms_of(k) * 1e-3) / 1e9, 1) if tj.get(k) else None,
+                      "frac": round(tj[k] / (ms_of(k) * 1e-3) / 8e12, 5) if tj.get(k) else None,
+                      "frac_of_random_line_ceiling": round(tj[k] / (ms_of(k) * 1e-3) / 2.58e12, 4) if tj.get(k) else None} for k in stage_kernels}
+        dom_bytes = alg.get(dom)
+        if dom_bytes is None:      # pair / report kernels: their own input and output (seeds in, records out, read bases compared)
+            dom_bytes = 8 * counters["seeds"] + 90 * n_reads
+        own = {
+            # Occ blocks + 16-byte table entries + per located search one 8-byte SA entry and ~2 text windows of 20 bytes
+            # + the read's 2-bit/mask words in + 16-byte hits out
+            "k_seed": 64 * counters.get("occ_blocks_executed", 0) + 16 * counters.get("ktab_lookups", 0) + 48 * counters.get("direct_extensions", 0)
+                      + 56 * n_reads + 16 * counters["seeds"],
+            "k_locate": 64 * counters.get("lf_steps_executed", 0) + 8 * counters["sa_lookups"] + 8 * counters["seeds"],
+        }
+        own_bytes = int(own.get(dom, dom_bytes))
+        ms_alone = ms_of(dom)
+        # `achieved` is a HARDWARE statement: the bytes the dominant kernel really moves through the memory side (PMC FETCH_SIZE + WRITE_SIZE of one
+        # launch; without a matching profile: the bytes it requests, from the live counters -- a lower bound) over the launch's stand-alone
+        # duration, against 8 TB/s.  The rate on the REFERENCE algorithm's bytes stays beside it as `algorithmic_*`: the prefix
+        # table, the full SA and the direct text comparison remove most of those bytes, so that rate is a work-elimination factor, not a
+        # fraction of any hardware limit.
+        moved = traffic if traffic else own_bytes
+        achieved = moved / (ms_alone * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
+                    "frac": round(achieved / 8000.0, 5), "traffic": traffic,
+                    "achieved_basis": ("PMC FETCH_SIZE + WRITE_SIZE bytes of one launch (profiles/traffic.json: same kernel sources, same workload)" if traffic else
+                                       "bytes the kernel requests per launch, from its live work counters (no PMC pass matches these kernel sources and this workload): a lower bound of the traffic")
+                                      + " / the launch's stand-alone HIP-event duration measured in this run",
+                    "kernel_ms_standalone": round(ms_alone, 4), "kernel_ms_in_timed_region": round(kern[dom], 4),
+                    "own_requested_bytes_per_launch": own_bytes,
+                    # what the memory system allows for THIS access pattern, measured with known bytes (profiles/probes/fetch_calib.hip,
+                    # profiles/r04/e_fetch_size_calibration_random_accesses.txt): random 64-byte accesses over the 3.1 GB Occ array run at 40.3 G lines/s
+                    # = 2.58 TB/s from 4 waves per CU on (16-byte accesses, which round 2's probe used: 49 G/s); a random 128-byte access is ONE fabric
+                    # request but runs at half that rate (21-22 G/s): the bytes, not the requests, are what the memory side limits.  The same probe
+                    # calibrates the counter: FETCH_SIZE is exact for random accesses of up to 64 bytes (one 64-byte request each, also for 16 bytes)
+                    # and reports half the bytes of 128-byte and wider ones (MI355X_MICROARCH.md's note on wide streams) -- the seeding kernels' accesses
+                    # are 8 to 64 bytes wide, so their FETCH_SIZE needs no correction
+                    "random_64B_line_ceiling_GBps": 2580.0,
+                    "frac_of_random_line_ceiling": round(achieved / 2580.0, 4),
+                    # ... per class of access (profiles/probes/footprint_sweep.sh, profiles/r04/y_random_line_rate_vs_footprint.txt): a random look-up made with ONE load
+                    # instruction (16 bytes of the prefix table, 8 of the suffix array) runs at 46-49 G/s whatever the footprint (3 to 118 GB); a random 64-byte
+                    # access is FOUR 16-byte loads, each translated on its own once the footprint is beyond the translation caches' reach: 39 G/s over the 3.1 GB
+                    # Occ array (UTCL1 misses 31 %), 21 G/s over 8 GB, 19 G/s over 16-200 GB (99.5 %) -- ~76 G load instructions/s is what the translation path
+                    # takes.  The seeding kernels make their wide accesses only in the 3.1 GB Occ array and the 0.8 GB text, so what the memory side allows them is
+                    "seeding_mixed_ceiling": (lambda one, wide: (lambda ms_min: {
+                        "single_load_lookups": int(one), "occ_blocks_and_text_windows": int(wide), "single_load_rate_G_per_s": 46.0, "wide_rate_G_per_s": 39.3, "streamed_bytes": int(max(0, moved - 64 * (one + wide))),
+                        "ms_min": round(ms_min, 4), "frac_of_mixed_ceiling": round(ms_min / ms_alone, 4),
+                        "what": "single-load look-ups = prefix-table entries + suffix-array entries read by the seeding kernels, wide = Occ blocks + text windows of the direct comparisons "
+                                "(1.5 lines each), the rest of the launch's PMC bytes streamed at 8 TB/s; ms_min = single / 46 G/s + wide / 39.3 G/s + streamed / 8 TB/s"})(
+                            (one / 46.0e9 + wide / 39.3e9 + max(0, moved - 64 * (one + wide)) / 8e12) * 1e3))(
+                        counters.get("ktab_lookups", 0) + counters.get("seedq_slots_locate", 0), counters.get("occ_blocks_executed", 0) + 1.5 * counters.get("direct_extensions", 0)) if dom == "k_seed" else None,
+                    "algorithmic_bytes_per_launch": int(dom_bytes),
+                    "algorithmic_GBps_standalone": round(dom_bytes / (ms_alone * 1e-3) / 1e9, 1),
+                    "algorithmic_GBps_in_timed_region": round(dom_bytes / (kern[dom] * 1e-3) / 1e9, 1),
+                    "work_elimination": round(dom_bytes / moved, 2),
+                    "fm_bytes_per_read": round(per_read_B, 1),
+                    # SURVEY 8d's whole-job form: reads/s x algorithmic bytes per read (this GPU's share of `value`)
+                    "whole_job_algorithmic_GBps_per_gpu": round(value / world * 1e6 * per_read_B / 1e9, 1),
+                    "fingerprint": fingerprint,
+                    "stages": stages,
+                    "note": "one launch = one batch of %d reads.  achieved / frac = real bytes over the stand-alone duration (see achieved_basis); algorithmic_* = what the "
+                            "reference's algorithm and layout would fetch for the same reads (SURVEY 8d: 64 B per Occ block of bwt_2occ4, per LF step, 8 B per SA entry), "
+                            "kept as a work-elimination factor" % n_reads}
 
     # ---- CPU baseline: the oracle ("port") on a bounded sample of the same reads, all host cores ----
     cpu = None
     b0 = batches[0]
-    so = b0.so.a; rl = b0.rl.a; flat = b0.seq.a
     res0 = None
     if not args.no_cpu_baseline:
+        so = b0.so.a; rl = b0.rl.a; flat = b0.seq.a
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import oracle_py
         cores = host_cores()
@@ -1082,13 +1212,14 @@ def main():
     # accuracy beside parity (the reference's Evaluation/eva idea): of the plain fragments (no planted indel or
     # intron), how many reads' best alignment starts within 10 bp of where the read was taken from?  Outside every timed region.
     accuracy = None
-    try:
-        from dart_amd import evaluate
-        if res0 is None:
-            workers[0].map(b0, args.input); res0 = workers[0].result()
-        accuracy = evaluate.mapping_accuracy(res0, b0.truth, tolerance=10)
-    except Exception as e:
-        log("[bench] accuracy not computed:", repr(e))
+    if args.full:
+        try:
+            from dart_amd import evaluate
+            if res0 is None:
+                workers[0].map(b0, args.input); res0 = workers[0].result()
+            accuracy = evaluate.mapping_accuracy(res0, b0.truth, tolerance=10)
+        except Exception as e:
+            log("[bench] accuracy not computed:", repr(e))
 
     # ---- the drop-in product end to end (SURVEY 8d "plus end-to-end wall"): `dart -i IDX -f 1.fq -f2 2.fq -o out.sam` as a child process ----
     cli = cli_big = None
@@ -1146,6 +1277,9 @@ def main():
         "cpu_baseline": cpu,
         "accuracy": accuracy,
     }
+    if not args.full:
+        for k in ("kernels_ms_one_batch_in_flight", "roofline", "cpu_baseline", "accuracy"):
+            del line[k]
     if cli_big and cpu and "cpu_reference_object_code" in cli_big:
         # the reference's own object code, timed on THIS box (one thread), beside the port: the ratio replaces the builder's-container figure
         ro = cli_big["cpu_reference_object_code"]

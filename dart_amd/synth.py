@@ -14,6 +14,8 @@ bytes that the container used for its fixtures.
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 
 _ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
@@ -155,6 +157,35 @@ def _make_genome_human(rng, codes, total):
         codes[idx] = rows[keep]
 
 
+def _uniform_codes(rng, total: int) -> np.ndarray:
+    """rng.integers(0, 4, size=total, dtype=np.uint8), drawn by several threads.  numpy takes each such code from one byte of the
+    generator's output (Lemire's method never rejects for a range of 4: the code is the byte's top two bits, the bytes in little-endian
+    order of the 64-bit outputs), so chunks of the output stream can be drawn from copies of the generator advanced to their start; the
+    generator is left where the single call leaves it.  Anything else takes the single call."""
+    bg = rng.bit_generator
+    if total % 8 or total < (1 << 24) or type(bg) is not np.random.PCG64 or bg.state["has_uint32"] or np.little_endian is False:
+        return rng.integers(0, 4, size=total, dtype=np.uint8)
+    from concurrent.futures import ThreadPoolExecutor
+    n64 = total // 8
+    parts = max(1, min(16, os.cpu_count() or 1))
+    per = -(-n64 // parts)
+    start = bg.state
+    out = np.empty(total, np.uint8)
+
+    def chunk(i):
+        lo, hi = i * per, min(n64, (i + 1) * per)
+        if lo >= hi:
+            return
+        g = np.random.PCG64()
+        g.state = start
+        g.advance(lo)
+        np.right_shift(g.random_raw(hi - lo).view(np.uint8), 6, out=out[8 * lo:8 * hi])
+    with ThreadPoolExecutor(max_workers=parts) as ex:
+        list(ex.map(chunk, range(parts)))
+    bg.advance(n64)
+    return out
+
+
 def make_genome(lengths, seed=20, repeat_scale=1.0, n_introns=0, names=None, model="planted") -> Genome:
     """model "planted" (SURVEY 8d): i.i.d. genome + planted repeats. Repeat counts scaled by genome size
     relative to the chr20-sized config (64.4 Mbp): 30000 x 300 bp @10 %, 800 x 0.5-6 kb @5 %,
@@ -166,7 +197,7 @@ def make_genome(lengths, seed=20, repeat_scale=1.0, n_introns=0, names=None, mod
     total = sum(lengths)
     if names is None:
         names = ["chr%d" % (i + 1) for i in range(len(lengths))]
-    codes = rng.integers(0, 4, size=total, dtype=np.uint8)
+    codes = _uniform_codes(rng, total)
     if model == "human":
         _make_genome_human(rng, codes, total)
     elif model != "planted":

@@ -11,7 +11,7 @@ env = dict(os.environ)
 if os.environ.get("FORCE_BUCKETED") == "1":
     env["DART_SA_BUCKETED"] = "1"
 t = time.time()
-r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--genome", str(glen), "--steps", steps, "--warmup", "4", "--cpu-sample-pairs", "32000"],
+r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--genome", str(glen), "--steps", steps, "--warmup", "4", "--cpu-sample-pairs", "32000", "--full"],
                    env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
 open(os.path.join(ROOT, "gpurun_out", "bench_big_%d.err" % glen), "w").write(r.stderr.decode())
 print(r.stderr.decode()[-3000:])

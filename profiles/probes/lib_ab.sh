@@ -2,7 +2,7 @@
 # A/B of two builds of the library on one box, alternating: bash profiles/probes/lib_ab.sh <tag> <other.so> [bench args]
 TAG=${1:-x}; OTHER=$2; shift; shift
 OUT=gpurun_out/lib_ab_$TAG.txt
-ARGS="--no-cpu-baseline --steps 20 --warmup 3 $@"
+ARGS="--full --no-cpu-baseline --steps 20 --warmup 3 $@"
 pick='import sys, json
 d = json.loads(sys.stdin.read())
 k = d["kernels_ms_one_batch_in_flight"]; kf = d["kernels_ms"]

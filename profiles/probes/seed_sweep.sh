@@ -2,7 +2,7 @@
 # sweep of k_seed_qf's geometry on one box: bash profiles/probes/seed_sweep.sh <tag> "<name:ENV=..,ENV=..> ..." [bench args]
 TAG=${1:-x}; VARS=$2; shift; shift
 OUT=gpurun_out/seed_sweep_$TAG.txt
-ARGS="--no-cpu-baseline --no-secondary --steps 8 --warmup 3 $@"
+ARGS="--full --no-cpu-baseline --no-secondary --steps 8 --warmup 3 $@"
 pick='import sys, json
 d = json.loads(sys.stdin.read()); c = d["counters_per_launch"]
 print(sys.argv[1], "M reads/s", d["value"], "k_seed alone", d["kernels_ms_one_batch_in_flight"].get("k_seed"), "in flight", d["kernels_ms"].get("k_seed"),

@@ -2,7 +2,7 @@
 # one bench run per variant on one box: bash profiles/probes/variants.sh <tag> "<name:lib.so|-:ENV=..,ENV=..> ..." [bench args]
 TAG=${1:-x}; VARS=$2; shift; shift
 OUT=gpurun_out/variants_$TAG.txt
-ARGS="--no-cpu-baseline --no-secondary --steps 20 --warmup 3 $@"
+ARGS="--full --no-cpu-baseline --no-secondary --steps 20 --warmup 3 $@"
 pick='import sys, json
 d = json.loads(sys.stdin.read())
 print(sys.argv[1], "M reads/s", d["value"], d.get("value_repeats"))

@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd $ROOT
 python3 bench.py --steps 1 --warmup 0 --batches 1 --inflight 1 --no-cpu-baseline --no-secondary $EXTRA > /dev/null 2> $OUT/prep.err || true   # builds and caches the index outside the profiler
 # the default command (ten distinct batches per step, the default number in flight), fewer steps, minus the CPU leg
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary $EXTRA > $OUT/bench_trace.json 2> $OUT/bench_trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary $EXTRA > $OUT/bench_trace.json 2> $OUT/bench_trace.err
 echo "trace done"
 # counters: one batch in flight (the profiler serialises dispatches anyway), separate passes (PROFILE_PASSES="fetch tcc" runs a subset: a call on the GPU box is limited to 20 minutes)
 PMC="--steps 1 --warmup 0 --batches 2 --inflight 1 --no-cpu-baseline --no-secondary $EXTRA"

@@ -1,4 +1,4 @@
-"""CPU suite: the default `bench.py` run on one GPU is an orchestrator that stays off the GPU and runs two children (bench.with_human_like_leg): the measurement itself
+"""CPU suite: the `bench.py --full` run on one GPU is an orchestrator that stays off the GPU and runs two children (bench.with_human_like_leg): the measurement itself
 and, if the time budget allows, the human-like leg.  Whatever the second child does, the first one's JSON line is what the driver gets -- exactly one line."""
 import argparse, io, json, os, sys, types
 import common

@@ -1,15 +1,20 @@
 """CPU suite: the accuracy scorers (dart_amd/evaluate.py) -- hand-made known answers, the golden SAM /
-junction files of the spliced case against the generator's truth, and (where oracle/_ref exists) the reference's own
-eva / SJ_Eva programs run on the same files."""
-import os, re, subprocess
+junction files of the spliced case against the generator's truth, and the figures the reference's own eva / SJ_Eva / FluxEva
+programs print for the same files (recorded in tests/golden/oracle_vs_ref.json by tests/golden/make_oracle_vs_ref.py; where
+oracle/_ref exists the programs also run live)."""
+import json, os, re, subprocess
 import numpy as np
-import pytest
 import common, oracle_py
 from dart_amd import evaluate
 
 REF_EVA = os.path.join(oracle_py.ORACLE_DIR, "_ref", "eva")
 REF_SJ = os.path.join(oracle_py.ORACLE_DIR, "_ref", "SJ_Eva")
 REF_FLUX = os.path.join(oracle_py.ORACLE_DIR, "_ref", "FluxEva")
+LIVE_SCORERS = all(os.path.exists(p) for p in (REF_EVA, REF_SJ, REF_FLUX))
+
+
+def recorded_scorers():
+    return json.load(open(os.path.join(common.GOLDEN, "oracle_vs_ref.json")))["scorers"]
 
 
 def test_eva_known_answers():
@@ -52,29 +57,42 @@ def test_scorers_on_golden_case(workdir):
     assert j["predicted"] > 50 and j["precision"] > 0.9, j
 
 
-@pytest.mark.skipif(not (os.path.exists(REF_EVA) and os.path.exists(REF_SJ)), reason="oracle/_ref scorers not built (no /root/reference here)")
-def test_scorers_match_reference_programs(workdir):
+def _truth(g):
+    truth = []
+    ends = np.cumsum(g.lengths)
+    for s, ilen, _ in g.introns:
+        ci = int(np.searchsorted(ends, s, side="right"))
+        truth.append((g.names[ci], int(s - g.offsets[ci]) + 1, int(s - g.offsets[ci] + ilen)))
+    return truth
+
+
+def ref_eva_and_sj(workdir):
+    """the reference's eva and SJ_Eva on the spliced case's golden SAM / junctions: what they print, as numbers"""
     c, g, chroms, sam, junc = _spliced_case(workdir)
     d = os.path.join(workdir, "eva_ref"); os.makedirs(d, exist_ok=True)
     g.write_fasta(os.path.join(d, "hg38.fa"))             # the reference program opens this name in its working directory
     open(os.path.join(d, "out.sam"), "w").write(sam)
     out = subprocess.run([REF_EVA, "out.sam"], cwd=d, capture_output=True, text=True).stderr
     m = re.findall(r"sensitivity = (\d+) / (\d+) = ([0-9.]+), AvgSeqIdy = ([0-9.]+)", out)[-1]
-    r = evaluate.eva(sam.split("\n"), chroms)
-    assert (r["aligned"], r["records"]) == (int(m[0]), int(m[1]))
-    assert "%.3f" % (r["avg_identity"] + 0.0005) == m[3]    # the reference prints value + 0.0005 with three decimals
-    truth = []
-    ends = np.cumsum(g.lengths)
-    for s, ilen, _ in g.introns:
-        ci = int(np.searchsorted(ends, s, side="right"))
-        truth.append((g.names[ci], int(s - g.offsets[ci]) + 1, int(s - g.offsets[ci] + ilen)))
-    open(os.path.join(d, "junctions.txt"), "w").write("".join("%s\t%d\t%d\n" % t for t in truth))
+    open(os.path.join(d, "junctions.txt"), "w").write("".join("%s\t%d\t%d\n" % t for t in _truth(g)))
     open(os.path.join(d, "pred.tab"), "w").write(junc)
     out = subprocess.run([REF_SJ, "pred.tab"], cwd=d, capture_output=True, text=True).stdout
     acc = int(re.search(r"Acc = (\d+)", out).group(1)); n_rep = int(re.search(r"# of Reported SJ = (\d+)", out).group(1))
+    return {"eva": {"aligned": int(m[0]), "records": int(m[1]), "avg_identity": m[3]}, "sj_eva": {"acc": acc, "reported": n_rep}}
+
+
+def test_scorers_match_reference_programs(workdir):
+    c, g, chroms, sam, junc = _spliced_case(workdir)
+    want = recorded_scorers()
+    if LIVE_SCORERS:
+        live = ref_eva_and_sj(workdir)
+        assert live == {k: want[k] for k in ("eva", "sj_eva")}, live
+    r = evaluate.eva(sam.split("\n"), chroms)
+    assert (r["aligned"], r["records"]) == (want["eva"]["aligned"], want["eva"]["records"])
+    assert "%.3f" % (r["avg_identity"] + 0.0005) == want["eva"]["avg_identity"]    # the reference prints value + 0.0005 with three decimals
     pred = [tuple(l.split()[:3]) for l in junc.split("\n") if l.strip()]
-    j = evaluate.sj_eva(pred, truth)
-    assert (j["annotated"], j["predicted"]) == (acc, n_rep)
+    j = evaluate.sj_eva(pred, _truth(g))
+    assert (j["annotated"], j["predicted"]) == (want["sj_eva"]["acc"], want["sj_eva"]["reported"])
 
 
 def _flux_sam(workdir, n_keep=4000, seed=5):
@@ -118,16 +136,26 @@ def test_flux_eva_known_answers():
     assert (r["right"], r["scored"], r["records"], r["empty"], r["mapq0"]) == (2, 4, 6, 1, 1) and r["accuracy_percent"] == 50.0
 
 
-@pytest.mark.skipif(not os.path.exists(REF_FLUX), reason="oracle/_ref/FluxEva not built (no /root/reference here)")
-def test_flux_eva_matches_reference_program(workdir):
+FLUX_SEEDS = (5, 6)
+
+
+def ref_flux_eva(workdir, seed):
+    """the reference's FluxEva on _flux_sam(seed): what it prints, as numbers"""
     d = os.path.join(workdir, "flux_ref"); os.makedirs(d, exist_ok=True)
-    for seed in (5, 6):
+    open(os.path.join(d, "flux.sam"), "w").write(_flux_sam(workdir, seed=seed))
+    out = subprocess.run([REF_FLUX, "flux.sam"], cwd=d, capture_output=True, text=True).stdout
+    m = re.search(r"Acc = (\d+) / (\d+) = ([0-9.]+)\s*$", out.split("\r")[-1])
+    assert m, out
+    return {"right": int(m.group(1)), "scored": int(m.group(2)), "percent": m.group(3)}
+
+
+def test_flux_eva_matches_reference_program(workdir):
+    want = recorded_scorers()["flux_eva"]
+    for seed in FLUX_SEEDS:
+        if LIVE_SCORERS:
+            assert ref_flux_eva(workdir, seed) == want[str(seed)]
         sam = _flux_sam(workdir, seed=seed)
-        open(os.path.join(d, "flux.sam"), "w").write(sam)
-        out = subprocess.run([REF_FLUX, "flux.sam"], cwd=d, capture_output=True, text=True).stdout
-        m = re.search(r"Acc = (\d+) / (\d+) = ([0-9.]+)\s*$", out.split("\r")[-1])
-        assert m, out
         r = evaluate.flux_eva(sam.split("\n"))
-        assert (r["right"], r["scored"]) == (int(m.group(1)), int(m.group(2))), (r, out[-200:])
-        assert "%.2f" % r["accuracy_percent"] == m.group(3)
+        assert (r["right"], r["scored"]) == (want[str(seed)]["right"], want[str(seed)]["scored"]), r
+        assert "%.2f" % r["accuracy_percent"] == want[str(seed)]["percent"]
         assert r["right"] > 200 and r["scored"] - r["right"] > 100 and r["mapq0"] > 100 and r["empty"] > 0

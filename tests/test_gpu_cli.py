@@ -252,7 +252,7 @@ def test_bench_two_ranks_through_the_self_launcher(workdir):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "2", "--genome", "3000000", "--pairs", "20000", "--batches", "3", "--steps", "2", "--weak",
-                        "--warmup", "1", "--inflight", "2", "--cpu-sample-pairs", "4000", "--verify-gather"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--inflight", "2", "--cpu-sample-pairs", "4000", "--verify-gather", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.split("\n") if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -274,10 +274,55 @@ def test_bench_two_ranks_strong_scaling_one_job_sharded(workdir):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "2", "--genome", "3000000", "--pairs", "20000", "--total-pairs", "70001", "--steps", "2",
-                        "--warmup", "1", "--inflight", "2", "--no-cpu-baseline", "--verify-gather"], env=env, capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--inflight", "2", "--no-cpu-baseline", "--verify-gather", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.split("\n") if l.startswith("{")][0])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and "70001 pairs" in line["config"]["parallelism"]
     assert abs(line["value"] * 1e6 * line["ms_per_step"] * 1e-3 / (2 * 70001) - 1) < 1e-3  # value = the whole job's reads over the step time
     assert line["gather"]["verified_against_single_rank_mapping"] is True
     assert line["value_weak_scaling"] > 0 and line["phases_s"]["total"] > 0          # the weak-scaling rate beside it (every rank's own whole batches), and where the run's time went
+
+
+def test_bench_plain_run_dumps_the_last_steps_records(workdir):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (no --full): one JSON line with the headline fields and nothing that takes runs
+    of its own; DIR holds the records of the last timed step's sample (the first DUMP_PAIRS pairs of every batch) in float64, and batch 0's are the
+    oracle's records of the same reads"""
+    import json, subprocess, sys
+    import numpy as np
+    import bench
+    from dart_amd import host
+    cache, out = os.path.join(workdir, "bench1_cache"), os.path.join(workdir, "bench1_dump")
+    env = dict(os.environ, DART_BENCH_CACHE=cache)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(common.ROOT, "bench.py"), "--gpus", "1", "--genome", "3000000", "--pairs", "20000", "--batches", "3", "--steps", "3",
+                        "--warmup", "1", "--inflight", "2", "--dump-outputs", out], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.split("\n") if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert abs(line["value"] * 1e6 * line["ms_per_step"] * 1e-3 / (2 * 3 * 20000) - 1) < 1e-3
+    for k in ("roofline", "cpu_baseline", "accuracy", "human_like", "sustained", "value_ascii_input", "kernels_ms_one_batch_in_flight"):
+        assert k not in line, k
+    a = {n: np.load(os.path.join(out, n + ".npy")) for n in ("reads", "reports", "cigar", "junctions")}
+    assert all(v.dtype == np.float64 for v in a.values())
+    n = 2 * bench.DUMP_PAIRS
+    assert a["reads"].shape == (3 * n, 9) and sorted(set(a["reads"][:, 0])) == [0, 1, 2]
+    assert a["reports"].shape[0] == int(a["reads"][:, 6].sum()) and a["junctions"].shape[0] == int(a["reads"][:, 8].sum())
+    # batch 0 of every step: seed 1000, its first DUMP_PAIRS pairs, against the oracle
+    prefix, g = bench.prepare_index(cache, 3000000, 0, lambda: None)
+    m1, m2 = synth.make_reads(g, 20000, rlen=101, seed=1000, sub_rate=0.01, indel_frac=0.02, n_frac=0.002)
+    so, rl, flat = host.pack_reads(host.interleave_pairs(m1[:bench.DUMP_PAIRS], m2[:bench.DUMP_PAIRS]))
+    orc = oracle_py.Oracle(prefix)
+    reads, rep, cig, sj = orc.map_batch(orc.params(paired=1, max_mismatch=5), so, rl, flat)
+    orc.close()
+    rep, sj = rep[:int(reads["n_rep"].sum())], sj[:int(reads["n_sj"].sum())]
+    b0 = a["reads"][:, 0] == 0
+    assert np.array_equal(a["reads"][b0][:, 2:], np.column_stack([reads[f] for f in ("score", "sub_score", "mis_num", "mapq", "n_rep", "best", "n_sj")]).astype(np.float64))
+    p0 = a["reports"][:, 0] == 0
+    assert np.array_equal(a["reports"][p0][:, 2:], np.column_stack([rep[f] for f in ("aln_score", "sj_type", "flag", "paired_idx", "chr", "bdir", "pos", "n_cigar")]).astype(np.float64))
+    ops = np.concatenate([cig[o:o + k] for o, k in zip(rep["cigar_off"], rep["n_cigar"])]) if len(rep) else np.zeros(0)
+    assert np.array_equal(a["cigar"][:len(ops)], ops.astype(np.float64))
+    j0 = a["junctions"][:, 0] == 0
+    assert np.array_equal(a["junctions"][j0][:, 1:], np.column_stack([sj[f] for f in ("g1", "g2", "type", "read_idx")]).astype(np.float64))
