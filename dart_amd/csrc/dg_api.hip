@@ -42,7 +42,7 @@ template <typename T> struct DBuf {
 
 #define N_TIMERS 20
 #define N_TOPS 128              // small device counters of a batch (bump tops, tickets, list sizes, class histogram), zeroed per run
-enum { TOP_CIG = 0, TOP_SJ, TOP_JOBS, TOP_REPORT_MAIN, TOP_REPORT_JOBS, TOP_HEAVY_UNITS, TOP_SEED_NEXT, TOP_SEED_HEAVY,
+enum { TOP_CIG = 0, TOP_SJ, TOP_JOBS, TOP_REPORT_MAIN, TOP_REPORT_JOBS /* reserved, unused */, TOP_HEAVY_UNITS, TOP_SEED_NEXT, TOP_SEED_HEAVY,
        TOP_WORK = 16, TOP_TICKET_PAIR = 17, TOP_TICKET_EMIT = 18, TOP_RESEED_COUNT = 19 /* 19..21: items per ring size; 22: diagonals per chunk */, TOP_RESEED_TICKET = 23 /* 23..25 */, TOP_TICKET_SEED = 26, TOP_RS_POOL = 27, TOP_RS_OUT = 31,
        TOP_ORDER_INFO = 28 /* 28..30 */, TOP_CLASS_HIST = 32 /* 32..63 */, TOP_CLASS_FILL = 64 /* 64..95 */ };        // (explicit values: every index names its own word)
 
@@ -61,23 +61,17 @@ struct IndexShared {
     void *d_ktab = nullptr, *d_sa_dense = nullptr;
     std::string report, report_out;
     int device = 0;
-    // the re-seeding kernels' streams, shared by the contexts of this index (DG_S2_SHARED, make_ctx_objects)
-    hipStream_t s2[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    int n_s2 = -1;                            // -1 = not decided yet
-    std::atomic<int> n_ctx{0};
 };
 
 struct dg_ctx {
     int device = 0;
     IndexShared *shared_ix = nullptr; uint32_t ix_gen = 0;
     bool owns_index = true;       // false for dg_clone()d contexts: the index arrays belong to the parent
-    hipStream_t stream = nullptr, stream2 = nullptr;
-    bool owns_stream2 = true;
+    hipStream_t stream = nullptr;
     hipEvent_t ev_dl = nullptr, ev_dl_block = nullptr;      // this context's place in the device's copy stream (copy_stream below); _block: the host thread sleeps (DG_BLOCKING_SYNC)
     bool dl_on_copy_stream = false;
     int env_copy_stream = 1;                           // DG_COPY_STREAM: 0 = the downloads on the context's own stream, 1 = on the device's copy stream
-    hipEvent_t ev_prep = nullptr, ev_reseed0 = nullptr, ev_reseed1 = nullptr, ev_wait = nullptr;
-    float reseed_ms = 0;
+    hipEvent_t ev_wait = nullptr;
     char err[512] = "";
     DIndex ix{};
     DParams pr{};
@@ -118,10 +112,10 @@ struct dg_ctx {
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
-    int env_seed_waves = 4, env_bail_trips = 0 /* 0: 64 trips in k_seed_qf (a trip there is up to three dependent accesses), 128 in the other two */, env_both = 0, env_report_bpc = 8, env_no_fast = 0, env_seed_legacy = 0, env_seed_slots_lg = 0, env_seed_wgs = 0, env_blocking_sync = 0;
+    int env_seed_waves = 4, env_bail_trips = 0 /* 0: 64 trips in k_seed_qf (a trip there is up to three dependent accesses), 128 in the other two */, env_report_bpc = 8, env_no_fast = 0, env_seed_legacy = 0, env_seed_slots_lg = 0, env_seed_wgs = 0, env_blocking_sync = 0;
     int env_seed_phases = 0, env_seed_wg_waves = 4, env_seed_partial = 32, env_seed_multi = 4;   // DG_SEED_PHASES=1: round 2's barrier-phased queue kernel (k_seed_q) instead of the free-running one (k_seed_qf)
     bool seed_qf_used = false;     // the last run's seeding kernel was k_seed_qf (its own-work counters are derived from its slot counts)
-    int env_scan_mask = 7, env_one_stream = 1, env_packed_pair = 1, env_drain_bail = 0;
+    int env_scan_mask = 7;
     int env_chain_bpc = 8, env_seedh_bpc = 8, env_reseed_pct = 100;      // persistent one-wave workgroups per CU of k_chain_heavy / k_seed_heavy; k_reseed's grids in per cent (sweeps: DG_CHAIN_BPC, DG_SEEDH_BPC, DG_RESEED_PCT)
     int env_rs_chunk = RS_CHUNK_DIAGS, env_rs_inline = RS_ENT_INLINE, env_rs_pool = 0;      // test hooks (DG_RS_CHUNK, DG_RS_ENT_MAX, DG_RS_POOL_BLOCKS): diagonals per chunk of a shared re-seeding window, entries a chunk record holds inline, blocks of the entry pool
     int env_scan_budget = 0;      // DG_SCAN_POLL_BUDGET: poll budget of a look-back on the FIRST attempt of a batch (test hook: forces the DG_E_SCAN re-run path)
@@ -130,12 +124,12 @@ struct dg_ctx {
 static void read_env(dg_ctx *c)
 {
     auto geti = [](const char *k, int dflt) { const char *v = getenv(k); return v ? atoi(v) : dflt; };
-    c->env_seed_waves = geti("DG_SEED_WAVES", 4); c->env_bail_trips = geti("DG_SEED_BAIL_TRIPS", 0); c->env_both = geti("DG_SEED_BOTH", 0);
+    c->env_seed_waves = geti("DG_SEED_WAVES", 4); c->env_bail_trips = geti("DG_SEED_BAIL_TRIPS", 0);
     c->env_seed_legacy = geti("DG_SEED_LEGACY", 0); c->env_seed_slots_lg = geti("DG_SEED_SLOTS_LG", 0); c->env_seed_wgs = geti("DG_SEED_WGS", 0); c->env_blocking_sync = geti("DG_BLOCKING_SYNC", 0);
     c->env_report_bpc = geti("DG_REPORT_BPC", 8); c->env_no_fast = geti("DG_NO_FAST_PAIR", 0);
     c->env_scan_budget = geti("DG_SCAN_POLL_BUDGET", 0); c->env_scan_mask = geti("DG_SCAN_POLL_SCANS", 7);
     c->env_seed_phases = geti("DG_SEED_PHASES", 0); c->env_seed_wg_waves = geti("DG_SEED_WG_WAVES", 4); c->env_seed_partial = geti("DG_SEED_PARTIAL_MIN", 32);
-    c->env_copy_stream = geti("DG_COPY_STREAM", 1); c->env_one_stream = geti("DG_ONE_STREAM", 1); c->env_packed_pair = geti("DG_PACKED_PAIR", 1); c->env_drain_bail = geti("DG_SEED_DRAIN_BAIL", 0);
+    c->env_copy_stream = geti("DG_COPY_STREAM", 1);
     c->env_chain_bpc = std::max(1, geti("DG_CHAIN_BPC", 8)); c->env_seedh_bpc = std::max(1, geti("DG_SEEDH_BPC", 8)); c->env_reseed_pct = std::max(10, geti("DG_RESEED_PCT", 100));
     c->env_rs_chunk = geti("DG_RS_CHUNK", RS_CHUNK_DIAGS); c->env_rs_chunk = std::min(1 << 24, std::max(RS_SUPER, c->env_rs_chunk / RS_SUPER * RS_SUPER));      // (a multiple of the pac super-chunk)
     c->env_rs_inline = std::min(RS_ENT_INLINE, std::max(0, geti("DG_RS_ENT_MAX", RS_ENT_INLINE))); c->env_rs_pool = std::max(0, geti("DG_RS_POOL_BLOCKS", 0));
@@ -331,7 +325,7 @@ k_report(const DIndex ix, const DParams pr, int n_reads, int paired, const unsig
          const uint32_t *__restrict__ seq_off, const uint16_t *__restrict__ rlen, const uint32_t *__restrict__ seed_off,
          const DJob *__restrict__ jobs, DCand *__restrict__ cands,
          const uint32_t *__restrict__ rep_off, DSeed *__restrict__ work, const unsigned long long *__restrict__ items,
-         const uint32_t *__restrict__ n_jobitems_p, const uint32_t *__restrict__ n_items_p, int job_part, dg_report_out *__restrict__ reports, uint32_t *cigpool, uint32_t cigcap,
+         const uint32_t *__restrict__ n_items_p, dg_report_out *__restrict__ reports, uint32_t *cigpool, uint32_t cigcap,
          unsigned int *tops, unsigned char *ws, const WSLayout L, unsigned long long *ctr, int *err)
 {
     const unsigned long long t_wave0 = wall_clock64();
@@ -350,11 +344,10 @@ k_report(const DIndex ix, const DParams pr, int n_reads, int paired, const unsig
     cx.ix = &ix; cx.pr = &pr; cx.L = &L;
     cx.ws = ws + (size_t)lane * L.stride;
     cx.n_nw = cx.nw_cells = cx.n_reseed = cx.reseed_w = 0;
-    // items = [candidates that wait for k_reseed | all other live candidates of the listed reads, heaviest class first] (k_order_items); this launch takes
-    // one part, 64 items per ticket: lane = candidate.  (Rounds 1-4: lane = read, and the reads with dozens of candidates a wave each.)
-    const unsigned int n_jobitems = *n_jobitems_p;
-    const unsigned int lo = job_part ? 0u : n_jobitems, hi = job_part == 1 ? n_jobitems : *n_items_p;       // job_part 2: the whole list (k_reseed has run)
-    unsigned int *next = tops + (job_part == 1 ? 4 : 3);
+    // items = [candidates that waited for k_reseed | all other live candidates of the listed reads, heaviest class first] (k_order_items); this launch takes
+    // the whole list (k_reseed has run), 64 items per ticket: lane = candidate.  (Rounds 1-4: lane = read, and the reads with dozens of candidates a wave each.)
+    const unsigned int lo = 0u, hi = *n_items_p;
+    unsigned int *next = tops + TOP_REPORT_MAIN;
     while (true) {
         unsigned int ticket = 0;
         if ((threadIdx.x & 63) == 0) ticket = atomicAdd(next, 1u);
@@ -540,8 +533,6 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    if (c->stream2) (void)hipStreamSynchronize(c->stream2);
-    if (c->owns_index && c->shared_ix) for (hipStream_t &q : c->shared_ix->s2) if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); q = nullptr; }   // (clones go before their parent)
     if (c->owns_index && c->shared_ix) {          // the aids thread may still be allocating or building: it ends by itself (a failed upload tells it so)
         IndexShared *sh = c->shared_ix;
         { std::lock_guard<std::mutex> lk(sh->mu); if (!sh->upload_done) { sh->upload_done = true; sh->upload_ok = false; } }
@@ -562,13 +553,9 @@ extern "C" void dg_destroy(dg_ctx *c)
     c->reads_out.release(); c->reports.release(); c->cigpool.release(); c->cigfinal.release(); c->sjpool.release(); c->sjfinal.release();
     c->ws.release(); c->scan_state.release(); c->scan_trace.release(); c->reads_c.release(); c->reports_c.release(); c->cig_c.release();
     for (int i = 0; i <= N_TIMERS; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    if (c->ev_prep) (void)hipEventDestroy(c->ev_prep);
     if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
     if (c->ev_dl) (void)hipEventDestroy(c->ev_dl);
     if (c->ev_dl_block) (void)hipEventDestroy(c->ev_dl_block);
-    if (c->ev_reseed0) (void)hipEventDestroy(c->ev_reseed0);
-    if (c->ev_reseed1) (void)hipEventDestroy(c->ev_reseed1);
-    if (c->stream2 && c->owns_stream2) (void)hipStreamDestroy(c->stream2);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->owns_shared_caps) delete c->shared_caps;
     delete c;
@@ -579,44 +566,8 @@ static hipError_t make_ctx_objects(dg_ctx *c)
 {
     hipError_t e;
     for (int i = 0; i <= N_TIMERS; i++) c->ev[i] = nullptr;
-    // DG_CU_PARTS=P (measurement switch, profiles/r04/y_*): context k's two streams only get the compute units of part k % P (DG_CU_LAYOUT 0: P contiguous
-    // ranges of the mask's bits, 1: bit i belongs to part (i % 8) % P) -- fewer different kernels share a CU's instruction cache and LDS at a time
-    static std::atomic<int> n_made{0};
-#ifdef DG_EXPERIMENTS      /* measurement builds only (profiles/r04/x_modes_*): a stray environment variable must not take HBM away from a product run */
-    if (getenv("DG_EXP_CTX_PAD_KB")) {         // context k's allocations start behind a pad of (k + 1) x this many KB (never freed: an experiment)
-        void *pad = nullptr; static std::atomic<int> n_pad{0};
-        (void)hipMalloc(&pad, (size_t)(n_pad.fetch_add(1) + 1) * (size_t)atoll(getenv("DG_EXP_CTX_PAD_KB")) * 1024);
-    }
-#endif
-    const int parts = getenv("DG_CU_PARTS") ? atoi(getenv("DG_CU_PARTS")) : 0, layout = getenv("DG_CU_LAYOUT") ? atoi(getenv("DG_CU_LAYOUT")) : 0;
-    if (parts > 1) {
-        int n_cu = 0; (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, c->device);
-        const int part = n_made.fetch_add(1) % parts;
-        std::vector<uint32_t> mask((size_t)(n_cu + 31) / 32, 0u);
-        for (int i = 0; i < n_cu; i++) { const int pi = layout == 1 ? (i % 8) % parts : (int)((long long)i * parts / n_cu); if (pi == part) mask[(size_t)i / 32] |= 1u << (i % 32); }
-        if ((e = hipExtStreamCreateWithCUMask(&c->stream, (uint32_t)mask.size(), mask.data())) != hipSuccess || (e = hipExtStreamCreateWithCUMask(&c->stream2, (uint32_t)mask.size(), mask.data())) != hipSuccess) return e;
-    } else {
-        // A device's contexts share a few streams for their re-seeding kernels (four launches per batch) instead of owning one each: the runtime maps streams
-        // onto GPU_MAX_HW_QUEUES hardware queues, least-used first with ties broken by the queues' addresses -- with twelve contexts x two streams on sixteen
-        // queues, which contexts' MAIN streams ended up on one queue (and then ran their kernels one after the other) differed from process to process:
-        // 826 to 985 M reads/s for the same command (profiles/r04/x_modes_*).  Twelve main streams + DG_S2_SHARED (3) shared ones + the caller's own stream
-        // fit the sixteen queues without sharing.  0 = a private stream per context (rounds 2-3).
-        IndexShared *sh = c->shared_ix;
-        if ((e = hipStreamCreate(&c->stream)) != hipSuccess) return e;
-        const bool one_stream = !getenv("DG_ONE_STREAM") || atoi(getenv("DG_ONE_STREAM")) != 0;      // (the default since round 5: no second stream exists at all -- a stream that is never used still takes its place among the hardware queues)
-        if (sh && !one_stream) {
-            std::lock_guard<std::mutex> lk(sh->mu);
-            if (sh->n_s2 < 0) { const int n = getenv("DG_S2_SHARED") ? atoi(getenv("DG_S2_SHARED")) : 3; sh->n_s2 = n < 0 ? 0 : (n > 8 ? 8 : n); }
-            if (sh->n_s2 > 0) {
-                const int k = sh->n_ctx.fetch_add(1) % sh->n_s2;
-                if (!sh->s2[k] && (e = hipStreamCreate(&sh->s2[k])) != hipSuccess) return e;
-                c->stream2 = sh->s2[k]; c->owns_stream2 = false;
-            }
-        }
-        if (!one_stream && !c->stream2 && (e = hipStreamCreate(&c->stream2)) != hipSuccess) return e;
-    }
-    if ((e = hipEventCreate(&c->ev_prep)) != hipSuccess || (e = hipEventCreate(&c->ev_reseed0)) != hipSuccess || (e = hipEventCreate(&c->ev_reseed1)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&c->ev_wait, hipEventBlockingSync | hipEventDisableTiming)) != hipSuccess ||
+    if ((e = hipStreamCreate(&c->stream)) != hipSuccess) return e;
+    if ((e = hipEventCreateWithFlags(&c->ev_wait, hipEventBlockingSync | hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->ev_dl, hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&c->ev_dl_block, hipEventBlockingSync | hipEventDisableTiming)) != hipSuccess) return e;
     for (int i = 0; i <= N_TIMERS; i++) if ((e = hipEventCreate(&c->ev[i])) != hipSuccess) return e;
     if ((e = hipMalloc((void **)&c->d_ctr, CTR_STRIPES * CTR_STRIDE * 8)) != hipSuccess || (e = hipMalloc((void **)&c->d_tops, N_TOPS * 4)) != hipSuccess ||
@@ -818,19 +769,6 @@ static dg_ctx *init_index(const IndexMeta &m, UpSrc bwt, uint64_t bwt_off, UpSrc
     if (e != hipSuccess || ndev == 0) return bail(DG_ERR_NO_DEVICE, "no HIP device (libdartgpu has no CPU fallback)", e);
     if (device < 0 || device >= ndev) return bail(DG_ERR_NO_DEVICE, "device ordinal out of range", hipSuccess);
     if ((e = hipSetDevice(device)) != hipSuccess) return bail(DG_ERR_HIP, "hipSetDevice", e);
-#ifdef DG_EXPERIMENTS      /* measurement builds only: where the allocations land (profiles/r04/x_modes_*) */
-    if (getenv("DG_EXP_PREALLOC_GB")) {        // measurement switch (where the allocations land: profiles/r04/x_modes_*): take and give back this much memory first
-        void *dummy = nullptr;
-        if (hipMalloc(&dummy, (size_t)atoll(getenv("DG_EXP_PREALLOC_GB")) << 30) == hipSuccess) { (void)hipMemset(dummy, 0, 1 << 20); (void)hipDeviceSynchronize(); (void)hipFree(dummy); }
-    }
-    if (getenv("DG_EXP_HOLD_GB")) { void *hold = nullptr; (void)hipMalloc(&hold, (size_t)atoll(getenv("DG_EXP_HOLD_GB")) << 30); }      // (kept: shifts what follows)
-    if (getenv("DG_EXP_CHURN_GB")) {           // this much memory in 4 GB blocks, every other one given back first, then the rest: a free list in pieces
-        std::vector<void *> blk((size_t)atoll(getenv("DG_EXP_CHURN_GB")) / 4, nullptr);
-        for (auto &b : blk) (void)hipMalloc(&b, (size_t)4 << 30);
-        for (size_t i = 0; i < blk.size(); i += 2) (void)hipFree(blk[i]);
-        for (size_t i = 1; i < blk.size(); i += 2) (void)hipFree(blk[i]);
-    }
-#endif
     c = new dg_ctx();
     c->device = device;
     c->shared_caps = new dg_ctx::SharedCaps(); c->owns_shared_caps = true;
@@ -1072,25 +1010,6 @@ k_unpack_n(const uint32_t *__restrict__ nlist, uint32_t n_n, int W2, uint32_t n_
     atomicOr(&enc[(size_t)r * 2 * W2 + W2 + (pos >> 4)], bit);
 }
 
-// DG_PACKED_PAIR=0 (a measurement switch): the ASCII copy of the WHOLE packed batch, as rounds 2-3 made it, for k_pair<false>
-__global__ void __launch_bounds__(256)
-k_unpack_all(uint32_t n_words, int W2, const uint32_t *__restrict__ enc, unsigned char *__restrict__ seq)
-{
-    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_words) return;
-    const uint32_t r = t / (uint32_t)W2, ww = t - r * (uint32_t)W2;
-    const uint32_t w = enc[(size_t)r * 2 * W2 + ww], m = enc[(size_t)r * 2 * W2 + W2 + ww];
-    uint32_t out[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const uint32_t a = (w >> (24 - 8 * q)) & 0xFFu, b = (m >> (24 - 8 * q)) & 0xFFu;
-        const uint32_t sel = ((a * 0x40100401u) >> 6) & 0x03030303u, nb = ((b * 0x40100401u) >> 6) & 0x03030303u;
-        const uint32_t isn = ((nb | (nb >> 1)) & 0x01010101u) * 0xFFu;
-        out[q] = (__builtin_amdgcn_perm(0u, 0x54474341u, sel) & ~isn) | (0x4E4E4E4Eu & isn);
-    }
-    *(uint4 *)(seq + (size_t)r * 16 * W2 + 16 * ww) = make_uint4(out[0], out[1], out[2], out[3]);
-}
-
 static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uint16_t *rlen, int words_per_read, const uint32_t *words, const uint32_t *nlist, size_t n_n)
 {
     if (!c || n_reads < 0 || words_per_read < 1 || (n_reads > 0 && !words) || (n_n > 0 && !nlist)) return DG_ERR_ARG;
@@ -1114,7 +1033,6 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
         k_unpack_n<<<(unsigned)((n_n + 255) / 256), 256, 0, c->stream>>>(c->nlist_in.p, (uint32_t)n_n, W2, (uint32_t)(nw * 16), c->seq.p, c->enc.p, c->d_input_bad);
         HIPCHK(hipMemcpyAsync(&c->h_tail->input_bad, c->d_input_bad, 4, hipMemcpyDeviceToHost, c->stream));
     } else c->h_tail->input_bad = 0;
-    if (!c->env_packed_pair) k_unpack_all<<<(unsigned)((nw + 255) / 256), 256, 0, c->stream>>>((uint32_t)nw, W2, c->enc.p, c->seq.p);
     HIPCHK(hipGetLastError());
     return DG_OK;
 }
@@ -1183,7 +1101,7 @@ static hipError_t launch_seed(dg_ctx *c, int n, int H, hipEvent_t after_encode =
                                                                          // that to the other batches in flight (measured 5.4 vs 6.0 ms per step with four batches)
     if ((size_t)blocks * 64 > (size_t)n) blocks = (unsigned)((n + 63) / 64);
     const bool use_qf = !c->env_seed_legacy && !c->env_seed_phases && W <= 62 && c->pr.max_dup <= 30000;      // (k_seed_qf's slot state counts occurrences in 20 bits: 31 hits x max_dup)
-    const int bail_trips = c->env_bail_trips > 0 ? c->env_bail_trips : (use_qf ? 64 : 128), both_thr = c->env_both;
+    const int bail_trips = c->env_bail_trips > 0 ? c->env_bail_trips : (use_qf ? 64 : 128);
     unsigned int *tops = c->d_tops;
     // default: the queue kernel (dg_seedq.h).  DG_SEED_LEGACY=1 or reads too long for its LDS slots (> 496 bases): the lane-per-read kernel
     c->seed_qf_used = false;
@@ -1208,8 +1126,7 @@ static hipError_t launch_seed(dg_ctx *c, int n, int H, hipEvent_t after_encode =
         if (wgs > need) wgs = need;
         c->seed_qf_used = true;
         k_seed_qf<<<wgs, nw * 64, lds, c->stream>>>(c->ix, c->pr, c->enc.p, c->rlen.p, n, W, H, lg, c->hits.p, c->nhits.p, c->nseeds.p, tops + TOP_SEED_NEXT,
-                                                    c->seed_heavy.p, tops + TOP_SEED_HEAVY, c->d_ctr, bail_trips, c->env_seed_partial, c->env_seed_multi, c->d_err,
-                                                    c->env_drain_bail > 0 ? c->env_drain_bail : bail_trips);
+                                                    c->seed_heavy.p, tops + TOP_SEED_HEAVY, c->d_ctr, bail_trips, c->env_seed_partial, c->env_seed_multi, c->d_err, bail_trips);
     } else
     if (!c->env_seed_legacy && W <= 62) {
         int lg = c->env_seed_slots_lg >= 6 && c->env_seed_slots_lg <= 10 ? c->env_seed_slots_lg : 9;
@@ -1225,8 +1142,8 @@ static hipError_t launch_seed(dg_ctx *c, int n, int H, hipEvent_t after_encode =
         k_seed_q<<<wgs, SQ_THREADS, lds, c->stream>>>(c->ix, c->pr, c->enc.p, c->rlen.p, n, W, H, lg, c->hits.p, c->nhits.p, c->nseeds.p, tops + TOP_SEED_NEXT,
                                                       c->seed_heavy.p, tops + TOP_SEED_HEAVY, c->d_ctr, bail_trips, c->d_err);
     } else
-    if (W <= 78) k_seed<true><<<blocks, 64, ((size_t)2 * W * 64 + 64) * 4, c->stream>>>(c->ix, c->pr, c->enc.p, c->rlen.p, n, W, H, c->hits.p, c->nhits.p, c->nseeds.p, tops + TOP_SEED_NEXT, c->seed_heavy.p, tops + TOP_SEED_HEAVY, c->d_ctr, bail_trips, both_thr);
-    else k_seed<false><<<blocks, 64, 0, c->stream>>>(c->ix, c->pr, c->enc.p, c->rlen.p, n, W, H, c->hits.p, c->nhits.p, c->nseeds.p, tops + TOP_SEED_NEXT, c->seed_heavy.p, tops + TOP_SEED_HEAVY, c->d_ctr, bail_trips, both_thr);
+    if (W <= 78) k_seed<true><<<blocks, 64, ((size_t)2 * W * 64 + 64) * 4, c->stream>>>(c->ix, c->pr, c->enc.p, c->rlen.p, n, W, H, c->hits.p, c->nhits.p, c->nseeds.p, tops + TOP_SEED_NEXT, c->seed_heavy.p, tops + TOP_SEED_HEAVY, c->d_ctr, bail_trips);
+    else k_seed<false><<<blocks, 64, 0, c->stream>>>(c->ix, c->pr, c->enc.p, c->rlen.p, n, W, H, c->hits.p, c->nhits.p, c->nseeds.p, tops + TOP_SEED_NEXT, c->seed_heavy.p, tops + TOP_SEED_HEAVY, c->d_ctr, bail_trips);
     // the backward walk of every listed read, lane = read (dg_fm.h): from which start on all searches fail without being made
     if ((e = c->seed_heavy_sfail.ensure((size_t)n + 16)) != hipSuccess) return e;
     k_seed_heavy_walk<<<(unsigned)c->n_cu * 8u, 64, 0, c->stream>>>(c->ix, c->pr, c->enc.p, c->rlen.p, W, c->seed_heavy.p, tops + TOP_SEED_HEAVY, c->seed_heavy_sfail.p, c->d_ctr);
@@ -1392,15 +1309,13 @@ static int enqueue_run(dg_ctx *c)
         co = CompactOut{c->reads_c.p, c->reports_c.p, c->cig_c.p, &c->d_sizes->pad[1]};
     }
     const int W2p = (c->max_rlen + 15) / 16 > 0 ? (c->max_rlen + 15) / 16 : 1;
-    const bool packed_pair = c->enc_ready && c->env_packed_pair;
-    if (packed_pair)        // a packed batch: the characters follow from its words; only the general path's units get an ASCII copy (below)
-        k_pair<true><<<(unsigned)((n_units + PU_THREADS - 1) / PU_THREADS), PU_THREADS, 0, c->stream>>>(
+    const bool packed_pair = c->enc_ready;        // a packed batch: the characters follow from its words; only the general path's units get an ASCII copy (below)
+    auto launch_pair = [&](auto kernel) {
+        kernel<<<(unsigned)((n_units + PU_THREADS - 1) / PU_THREADS), PU_THREADS, 0, c->stream>>>(
             c->ix, c->pr, n_units, paired, try_fast, (c->want_full || !c->want_compact) ? 0 : 2, c->seq.p, c->seq_off.p, c->enc.p, W2p, c->rlen.p, c->seed_off.p, c->seeds.p, c->cands.p, c->ncand.p, c->rep_off.p,
             c->slow_units.p, c->reads_out.p, c->reports.p, c->cigfinal.p, (uint32_t)c->cap_rep, (uint32_t)c->cap_cig, ts_pair, c->d_sizes, tops + TOP_CIG, c->d_ctr, c->d_err, co);
-    else
-        k_pair<false><<<(unsigned)((n_units + PU_THREADS - 1) / PU_THREADS), PU_THREADS, 0, c->stream>>>(
-            c->ix, c->pr, n_units, paired, try_fast, (c->want_full || !c->want_compact) ? 0 : 2, c->seq.p, c->seq_off.p, c->enc.p, W2p, c->rlen.p, c->seed_off.p, c->seeds.p, c->cands.p, c->ncand.p, c->rep_off.p,
-            c->slow_units.p, c->reads_out.p, c->reports.p, c->cigfinal.p, (uint32_t)c->cap_rep, (uint32_t)c->cap_cig, ts_pair, c->d_sizes, tops + TOP_CIG, c->d_ctr, c->d_err, co);
+    };
+    if (packed_pair) launch_pair(k_pair<true>); else launch_pair(k_pair<false>);
     HIPCHK(hipGetLastError());
     TICK("k_pair");
 
@@ -1421,14 +1336,11 @@ static int enqueue_run(dg_ctx *c)
                                              packed_pair ? c->enc.p : nullptr, W2p, c->seq.p);      // (a packed batch: the listed reads get their ASCII copy here)
     HIPCHK(hipGetLastError());
     TICK("k_prep");
-    // Round 5: the re-seeding kernels run on the context's main stream, before the report kernel, which then takes ALL candidates in one launch.  Rounds 1-4
+    // The re-seeding kernels run on the context's only stream, before the report kernel, which then takes ALL candidates in one launch.  Rounds 1-4
     // gave a wave a whole window (up to 500 kb = ~1000 serial trips): the kernel was one long tail, so it ran on a second stream beside the report of the
     // candidates without jobs -- whose persistent waves held 113 of a CU's 160 KB of LDS and left k_reseed three waves per CU (cfg5: 3.8 s of wave time in
     // 5.4 ms).  With windows shared by several waves (dg_reseed.h) it is a balanced throughput kernel that wants the GPU for itself for a short time; a
     // context owns ONE stream (the sixteen hardware queues of a process hold twelve contexts, the caller's stream and -- on a node -- RCCL's).
-    // DG_ONE_STREAM=0: the second stream as before (k_report in two launches: candidates without jobs beside k_reseed, the others behind it).
-    if (!c->stream2) c->env_one_stream = 1;                       // (the context was made without a second stream)
-    const hipStream_t s2 = c->env_one_stream ? c->stream : c->stream2;
     const uint32_t jobcap = (uint32_t)c->jobs.cap;
     const RsPool rs_pool{c->job_pool.p, c->job_pool_next.p, tops + TOP_RS_POOL, c->env_rs_pool > 0 ? std::min<uint32_t>((uint32_t)c->env_rs_pool, rs_pool_cap) : rs_pool_cap};
     const int rs_gap_max = c->max_rlen - 32, rs_need = rs_gap_max >= 8 ? (rs_gap_max - 8) / 64 + 1 : 1;        // (see below)
@@ -1437,24 +1349,17 @@ static int enqueue_run(dg_ctx *c)
     k_order<<<slow_grid, 256, 0, c->stream>>>(paired, c->slow_units.p, c->d_sizes, c->seed_off.p, c->cands.p, c->ncand.p, tops + TOP_CLASS_HIST, tops + TOP_CLASS_FILL, c->items.p, tops + TOP_ORDER_INFO, rs_order, c->d_err);
     HIPCHK(hipGetLastError());
     TICK("order");
-    HIPCHK(hipEventRecord(c->ev_prep, c->stream));
-    if (!c->env_one_stream) HIPCHK(hipStreamWaitEvent(s2, c->ev_prep, 0));
-    HIPCHK(hipEventRecord(c->ev_reseed0, s2));
     // One launch per ring size the batch can need: a read gap lies between two seeds of >= 16 bases (bwt_search.cpp:165), so it is at most rlen - 32 long and
     // needs (gap - 16) / 64 + 1 bitmap words per diagonal -- one for reads of up to 103 bases (round 4 launched all three sizes for every batch), two up to 167.
     // (one stream for the ring sizes: side by side on streams of their own they cost the step 8 % with eight batches in flight, profiles/r02)
-    k_reseed<1><<<c->n_cu * 10 * c->env_reseed_pct / 100, 64, 0, s2>>>(c->ix, c->seq.p, c->seq_off.p, c->jobs.p, c->job_items.p, tops + TOP_RESEED_COUNT, tops + TOP_RESEED_COUNT + 3, tops + TOP_RESEED_TICKET, c->job_outs.p, rs_pool, c->env_rs_inline, c->d_ctr, c->d_err);
-    if (rs_need > 1) k_reseed<2><<<c->n_cu * 6 * c->env_reseed_pct / 100, 64, 0, s2>>>(c->ix, c->seq.p, c->seq_off.p, c->jobs.p, c->job_items.p + rs_list_cap, tops + TOP_RESEED_COUNT + 1, tops + TOP_RESEED_COUNT + 3, tops + TOP_RESEED_TICKET + 1, c->job_outs.p, rs_pool, c->env_rs_inline, c->d_ctr, c->d_err);
-    if (rs_need > 2) k_reseed<4><<<c->n_cu * 4 * c->env_reseed_pct / 100, 64, 0, s2>>>(c->ix, c->seq.p, c->seq_off.p, c->jobs.p, c->job_items.p + 2 * (size_t)rs_list_cap, tops + TOP_RESEED_COUNT + 2, tops + TOP_RESEED_COUNT + 3, tops + TOP_RESEED_TICKET + 2, c->job_outs.p, rs_pool, c->env_rs_inline, c->d_ctr, c->d_err);
+    k_reseed<1><<<c->n_cu * 10 * c->env_reseed_pct / 100, 64, 0, c->stream>>>(c->ix, c->seq.p, c->seq_off.p, c->jobs.p, c->job_items.p, tops + TOP_RESEED_COUNT, tops + TOP_RESEED_COUNT + 3, tops + TOP_RESEED_TICKET, c->job_outs.p, rs_pool, c->env_rs_inline, c->d_ctr, c->d_err);
+    if (rs_need > 1) k_reseed<2><<<c->n_cu * 6 * c->env_reseed_pct / 100, 64, 0, c->stream>>>(c->ix, c->seq.p, c->seq_off.p, c->jobs.p, c->job_items.p + rs_list_cap, tops + TOP_RESEED_COUNT + 1, tops + TOP_RESEED_COUNT + 3, tops + TOP_RESEED_TICKET + 1, c->job_outs.p, rs_pool, c->env_rs_inline, c->d_ctr, c->d_err);
+    if (rs_need > 2) k_reseed<4><<<c->n_cu * 4 * c->env_reseed_pct / 100, 64, 0, c->stream>>>(c->ix, c->seq.p, c->seq_off.p, c->jobs.p, c->job_items.p + 2 * (size_t)rs_list_cap, tops + TOP_RESEED_COUNT + 2, tops + TOP_RESEED_COUNT + 3, tops + TOP_RESEED_TICKET + 2, c->job_outs.p, rs_pool, c->env_rs_inline, c->d_ctr, c->d_err);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_reseed1, s2));
-    if (c->env_one_stream) TICK("k_reseed");
-    const uint32_t *n_jobitems_p = tops + TOP_ORDER_INFO;             // items of class 0 (they wait for k_reseed)
-    const uint32_t *n_items_p = tops + TOP_ORDER_INFO + 1;            // end of the list
-    // (two streams: one wave slot per CU is left free so that k_reseed's waves are resident beside the persistent report waves)
-    const int blocks_main = (!c->env_one_stream && blocks > c->n_cu * 4) ? blocks - c->n_cu : blocks;
-    k_report<2><<<blocks_main, 64, 0, c->stream>>>(c->ix, c->pr, n, paired, c->seq.p, c->seq_off.p, c->rlen.p, c->seed_off.p, c->jobs.p, c->cands.p,
-                                               c->rep_off.p, c->work.p, c->items.p, n_jobitems_p, n_items_p, c->env_one_stream ? 2 : 0, c->reports.p, c->cigpool.p,
+    TICK("k_reseed");
+    const uint32_t *n_items_p = tops + TOP_ORDER_INFO + 1;            // end of k_order's item list
+    k_report<2><<<blocks, 64, 0, c->stream>>>(c->ix, c->pr, n, paired, c->seq.p, c->seq_off.p, c->rlen.p, c->seed_off.p, c->jobs.p, c->cands.p,
+                                               c->rep_off.p, c->work.p, c->items.p, n_items_p, c->reports.p, c->cigpool.p,
                                                (uint32_t)cigcap, tops, c->ws.p, L, c->d_ctr, c->d_err);
     HIPCHK(hipGetLastError());
 #ifdef DG_PROFILE_CLASSES
@@ -1474,15 +1379,6 @@ static int enqueue_run(dg_ctx *c)
     }
 #endif
     TICK("k_report");
-    if (!c->env_one_stream) {
-    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_reseed1, 0));
-    // (the candidates that waited for k_reseed: a handful on DNA, a third of a spliced batch -- the full persistent grid; waves without work leave at once)
-    k_report<2><<<blocks_main, 64, 0, c->stream>>>(c->ix, c->pr, n, paired, c->seq.p, c->seq_off.p, c->rlen.p, c->seed_off.p, c->jobs.p, c->cands.p,
-                                               c->rep_off.p, c->work.p, c->items.p, n_jobitems_p, n_items_p, 1, c->reports.p, c->cigpool.p,
-                                               (uint32_t)cigcap, tops, c->ws.p, L, c->d_ctr, c->d_err);
-    HIPCHK(hipGetLastError());
-    TICK("k_report_jobs");
-    }
     k_finalize<<<slow_grid, 256, 0, c->stream>>>(c->ix, c->pr, paired, c->slow_units.p, c->d_sizes, c->seed_off.p, c->cands.p, c->ncand.p, c->rep_off.p, c->work.p,
                                                  c->reads_out.p, c->reports.p, c->sjpool.p, (uint32_t)sjcap, tops, c->d_err);
     k_emit_slow<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(paired, c->slow_units.p, c->d_sizes, c->reads_out.p, c->reports.p, c->cigpool.p, c->cigfinal.p,
@@ -1505,7 +1401,6 @@ static int finish_run(dg_ctx *c, size_t used[3])
     for (int attempt = 0; attempt < 6; attempt++) {
         c->runs_of_last_batch++;
         HIPCHK(wait_stream(c));
-        if (c->owns_stream2 && c->stream2) HIPCHK(hipStreamSynchronize(c->stream2));      // (a shared one holds other contexts' kernels too; this context's are behind ev_reseed1, which its main stream waited for)
         if (c->enc_ready && c->h_tail->input_bad) { snprintf(c->err, 512, "packed batch: the N list holds a position outside the batch"); c->enqueued = false; return DG_ERR_ARG; }
         const DSizes &sz = c->h_tail->sizes;
         const int derr = c->h_tail->err;
@@ -1544,7 +1439,6 @@ static int finish_run(dg_ctx *c, size_t used[3])
     }
     c->enqueued = false;
     for (int i = 0; i < c->n_t; i++) { float ms = 0; (void)hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]); c->tms[i] = ms; }
-    if (!c->env_one_stream && c->n_t < N_TIMERS) { float ms = 0; (void)hipEventElapsedTime(&ms, c->ev_reseed0, c->ev_reseed1); c->tname[c->n_t] = "k_reseed(overlapped)"; c->tms[c->n_t] = ms; c->n_t++; }
     static_assert(CTR_N <= CTR_STRIDE, "the work counters fill one stripe");
     for (int k = 0; k < CTR_N; k++) c->counters[k] = c->h_tail->ctr[k];
     if (c->seed_qf_used) {

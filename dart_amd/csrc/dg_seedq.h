@@ -533,7 +533,7 @@ k_seed_qf(const DIndex ix, const DParams pr, const uint32_t *__restrict__ enc, c
     const uint32_t w_magic = ((1u << 20) + (uint32_t)W - 1u) / (uint32_t)W;       // i / W == (i * w_magic) >> 20 for i < 64 W <= 2^12
     const SqEnv env = { ix, pr, st, rd, NSLOT, W2, K, H, bail_trips, direct, (direct && ix.sa_dense_intv == 1) ? multi : 0, hits, nhits, nseeds, heavy, n_heavy };
     // once the batch has no more reads to hand out, a workgroup only drains its slots: the launch then lasts as long as the longest chain of trips still
-    // ahead of one read, so reads give up for k_seed_heavy (a wave each) after fewer trips (DG_SEED_DRAIN_BAIL; = bail_trips: no difference)
+    // ahead of one read, so reads give up for k_seed_heavy (a wave each) after drain_bail trips (the host passes bail_trips: a lower threshold for the drain made no difference)
     SqEnv env_drain = env; env_drain.bail_trips = drain_bail;
     unsigned long long acc_steps = 0, acc_blocks = 0, acc_lf = 0;
     uint32_t max_trips = 0, wtrips = 0;

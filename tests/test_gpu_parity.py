@@ -270,10 +270,10 @@ def test_gpu_records_as_torch_tensor_for_rccl(ctxs):
     assert np.array_equal(back, res.reads)
 
 
-def test_gpu_cloned_contexts_run_concurrently(workdir, monkeypatch):
+def test_gpu_cloned_contexts_run_concurrently(workdir):
     """dg_clone: contexts sharing one index, one host thread each, different batches in flight at once (bench.py's
-    pipeline); every context's records equal the oracle's.  The contexts' re-seeding kernels (a sixth of these reads span an intron) run on streams the
-    contexts SHARE (DG_S2_SHARED, 3 by default; dg_api.hip make_ctx_objects): five contexts on three, on one, and on private streams (0)."""
+    pipeline); every context's records equal the oracle's.  Every context runs all its kernels, the re-seeding ones included (a sixth of these reads
+    span an intron), on its one stream.  Three passes, each with five fresh contexts: create, run, destroy, create again."""
     import threading
     g = synth.make_genome([1200000, 800000], seed=51, repeat_scale=40.0, n_introns=200)
     prefix = os.path.join(workdir, "clones")
@@ -285,9 +285,7 @@ def test_gpu_cloned_contexts_run_concurrently(workdir, monkeypatch):
         m1, m2 = synth.make_reads(g, 9000 + 2000 * j, rlen=101, seed=52 + j, spliced_frac=0.15, indel_frac=0.04, n_frac=0.01)
         batches.append(host.pack_reads(host.interleave_pairs(m1, m2)))
         want.append(orc.map_batch(orc.params(paired=1, max_mismatch=5), *batches[j], threads=16))
-    for shared in (None, "1", "0"):
-        if shared is None: monkeypatch.delenv("DG_S2_SHARED", raising=False)
-        else: monkeypatch.setenv("DG_S2_SHARED", shared)
+    for rnd in range(3):
         gpu = host.DartGPU(ix, host.default_params(paired=1, max_mismatch=5))
         ctx = [gpu] + [gpu.clone() for _ in range(n_ctx - 1)]
         out, errs = [None] * n_ctx, []
@@ -300,11 +298,10 @@ def test_gpu_cloned_contexts_run_concurrently(workdir, monkeypatch):
         th = [threading.Thread(target=work, args=(j,)) for j in range(n_ctx)]
         for t in th: t.start()
         for t in th: t.join()
-        assert not errs, (shared, errs)
+        assert not errs, (rnd, errs)
         for j in range(n_ctx):
             assert_same(out[j], want[j])
         gpu.close()
-    monkeypatch.delenv("DG_S2_SHARED", raising=False)
     orc.close()
 
 
@@ -399,27 +396,23 @@ def test_gpu_reseed_windows_shared_by_several_waves(workdir, monkeypatch):
     gpu.close(); orc.close()
 
 
-def test_gpu_second_stream_for_the_reseeding_kernels_still_gives_the_same_records(workdir, monkeypatch):
-    """DG_ONE_STREAM=0 (rounds 2-4's arrangement, kept as a switch): k_reseed on a second stream beside the report of the candidates without
-    re-seeding jobs, the others in a second k_report launch behind it.  Same records as the oracle's, and as the default's (one stream, k_reseed in
-    front of one k_report launch), on a batch where a third of the units have jobs."""
+def test_gpu_reseeding_runs_in_front_of_one_report_launch(workdir):
+    """A context has one stream: k_reseed runs on it in front of ONE k_report launch over all candidates (no second launch for the candidates that
+    waited for re-seeding).  Same records as the oracle's on a batch where a third of the units have re-seeding jobs."""
     g = synth.make_genome([3000000, 1500000], seed=71, repeat_scale=30.0, n_introns=800)
-    prefix = os.path.join(workdir, "two_streams")
+    prefix = os.path.join(workdir, "reseed_first")
     index_build.build_index_from_genome(g, prefix)
     ix = host.Index(prefix); orc = oracle_py.Oracle(prefix)
     m1, m2 = synth.make_reads(g, 30000, rlen=125, seed=72, sub_rate=0.01, indel_frac=0.03, n_frac=0.002, spliced_frac=0.4)
     so, rl, flat = host.pack_reads(host.interleave_pairs(m1, m2))
     want = orc.map_batch(orc.params(paired=1, max_mismatch=5, max_intron=200000), so, rl, flat, threads=16)
-    for one in ("0", "1"):
-        monkeypatch.setenv("DG_ONE_STREAM", one)
-        gpu = host.DartGPU(ix, host.default_params(paired=1, max_mismatch=5, max_intron=200000))       # (the switch is read when a context is created)
-        res = gpu.map_batch(so, rl, flat)
-        assert_same(res, want)
-        names = [n for n, _ in gpu.timings()]
-        assert ("k_report_jobs" in names) == (one == "0"), names
-        assert gpu.counters()["reseed_calls"] == orc.counters["n_reseed"] > 100
-        gpu.close()
-    orc.close()
+    gpu = host.DartGPU(ix, host.default_params(paired=1, max_mismatch=5, max_intron=200000))
+    res = gpu.map_batch(so, rl, flat)
+    assert_same(res, want)
+    names = [n for n, _ in gpu.timings()]
+    assert "k_report_jobs" not in names and "k_reseed" in names, names
+    assert gpu.counters()["reseed_calls"] == orc.counters["n_reseed"] > 100
+    gpu.close(); orc.close()
 
 
 def test_gpu_noisy_long_reads_wave_nw_paths(workdir):
