@@ -26,6 +26,41 @@
 
 static char g_init_error[512] = "";
 
+// A context drives one HIP stream and a host keeps a dozen contexts in flight (dg_clone); the HIP runtime maps every stream of a process
+// onto GPU_MAX_HW_QUEUES hardware queues (its default 4), and streams that share a queue run their kernels one after the other.  The
+// library needs DG_HW_QUEUES_NEED: twelve contexts + the device's copy stream + the caller's stream + two spare (DESIGN.md 6, round 5,
+// item 2).  A value that is missing, unparsable or LOWER than that is raised to it -- a launcher that presets the runtime's default of 4
+// must not squeeze twelve contexts onto four queues; a higher value stays (a host that asked for more keeps it).  The variable is read
+// when the HIP runtime initialises, so this reaches a host that loads the library before its first HIP call; one that touched HIP first
+// exports GPU_MAX_HW_QUEUES itself.  What was found and what was left is kept for dg_init_report and dg_clone.
+#define DG_HW_QUEUES_NEED 16
+static_assert(DG_HW_QUEUES_NEED <= 32, "more hardware queues than 32 are not asked for");
+static char g_hwq_found[24] = "unset";            // the variable's text at load time
+static int g_hwq_left = DG_HW_QUEUES_NEED;        // its value when the constructor returned
+__attribute__((constructor)) static void dg_default_hw_queues()
+{
+    const char *v = getenv("GPU_MAX_HW_QUEUES");
+    long have = 0;
+    if (v) {
+        size_t i = 0;
+        for (; v[i] && i + 1 < sizeof g_hwq_found; i++) g_hwq_found[i] = (v[i] > ' ' && v[i] < 127 && v[i] != ';' && v[i] != '=') ? v[i] : '?';
+        g_hwq_found[i] = 0;
+        if (!i) snprintf(g_hwq_found, sizeof g_hwq_found, "empty");
+        char *end = nullptr;
+        have = strtol(v, &end, 10);
+        if (end == v || *end) have = 0; else if (have > 1000000) have = 1000000;
+    }
+    if (have < DG_HW_QUEUES_NEED) {
+        char b[8];
+        snprintf(b, sizeof b, "%d", DG_HW_QUEUES_NEED);
+        setenv("GPU_MAX_HW_QUEUES", b, 1);
+        have = DG_HW_QUEUES_NEED;
+    }
+    g_hwq_left = (int)have;
+}
+static std::atomic<int> g_live_ctx[64];           // contexts alive per device (each owns one stream)
+static std::atomic<bool> g_hwq_warned{false};
+
 template <typename T> struct DBuf {
     T *p = nullptr; size_t cap = 0;
     hipError_t ensure(size_t n) {
@@ -556,7 +591,7 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
     if (c->ev_dl) (void)hipEventDestroy(c->ev_dl);
     if (c->ev_dl_block) (void)hipEventDestroy(c->ev_dl_block);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    if (c->stream) { (void)hipStreamDestroy(c->stream); g_live_ctx[c->device & 63].fetch_sub(1); }
     if (c->owns_shared_caps) delete c->shared_caps;
     delete c;
 }
@@ -567,6 +602,7 @@ static hipError_t make_ctx_objects(dg_ctx *c)
     hipError_t e;
     for (int i = 0; i <= N_TIMERS; i++) c->ev[i] = nullptr;
     if ((e = hipStreamCreate(&c->stream)) != hipSuccess) return e;
+    g_live_ctx[c->device & 63].fetch_add(1);
     if ((e = hipEventCreateWithFlags(&c->ev_wait, hipEventBlockingSync | hipEventDisableTiming)) != hipSuccess ||
         (e = hipEventCreateWithFlags(&c->ev_dl, hipEventDisableTiming)) != hipSuccess || (e = hipEventCreateWithFlags(&c->ev_dl_block, hipEventBlockingSync | hipEventDisableTiming)) != hipSuccess) return e;
     for (int i = 0; i <= N_TIMERS; i++) if ((e = hipEventCreate(&c->ev[i])) != hipSuccess) return e;
@@ -866,7 +902,9 @@ extern "C" const char *dg_init_report(const dg_ctx *c)
     if (!c || !c->shared_ix) return "";
     IndexShared *sh = c->shared_ix;
     std::lock_guard<std::mutex> lk(sh->mu);
-    sh->report_out = sh->report;           // (a copy the caller may keep reading while the aids thread appends)
+    char q[96];                            // (always the last two fields, whatever the aids thread has appended so far)
+    snprintf(q, sizeof q, "; hw_queues_env_found=%s hw_queues_env_set=%d", g_hwq_found, g_hwq_left);
+    sh->report_out = sh->report + q;       // (a copy the caller may keep reading while the aids thread appends)
     return sh->report_out.c_str();
 }
 
@@ -919,12 +957,7 @@ extern "C" dg_ctx *dg_init_files(const dg_index_files *f, const dg_params *p, in
 
 // A second context on the same device that shares the parent's index (no copy): its own streams, batch buffers
 // and counters, so that two batches can be in flight at once (one host thread per context).  The parent must
-// outlive its clones.
-// A context drives two HIP streams and a host keeps several contexts in flight (dg_clone); the runtime's default of 4 hardware
-// queues makes those streams wait for each other.  The variable is read when the HIP runtime initialises, so this only helps a
-// host that loads the library before its first HIP call; others export GPU_MAX_HW_QUEUES themselves.
-__attribute__((constructor)) static void dg_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
-
+// outlive its clones.  (The hardware queues the contexts' streams need: dg_default_hw_queues, at the top of this file.)
 extern "C" dg_ctx *dg_clone(dg_ctx *parent, int *status)
 {
     if (status) *status = DG_ERR_ARG;
@@ -940,6 +973,13 @@ extern "C" dg_ctx *dg_clone(dg_ctx *parent, int *status)
     if ((e = make_ctx_objects(c)) != hipSuccess) {
         snprintf(g_init_error, sizeof g_init_error, "dg_clone: %s", hipGetErrorString(e)); dg_destroy(c); if (status) *status = DG_ERR_HIP; return nullptr;
     }
+    // more streams than hardware queues: which contexts share one -- and run their kernels one behind the other -- then changes from process to
+    // process.  Said once per process, when it first happens.
+    const int live = g_live_ctx[c->device & 63].load();
+    if (live + 2 > g_hwq_left && !g_hwq_warned.exchange(true))
+        fprintf(stderr, "[libdartgpu] %d contexts on device %d + the copy stream + the caller's stream are more than the %d hardware queues of this process "
+                        "(GPU_MAX_HW_QUEUES was %s when the library loaded and %d when its constructor returned): contexts will share queues and wait for each other\n",
+                live, c->device, g_hwq_left, g_hwq_found, g_hwq_left);
     if (status) *status = DG_OK;
     return c;
 }

@@ -456,9 +456,22 @@ static void format_range(const Reads &R, int lo, int hi, int n_pair_mode, const 
     }
 }
 
+// The HIP runtime maps the streams of a process onto GPU_MAX_HW_QUEUES hardware queues (its default 4) and reads the variable when it
+// initialises.  The contexts in flight need a queue each (+ the copy stream, + this program's own, + two spare = 16: INTEGRATION.md 2): a
+// value that is missing, unparsable or lower is raised to that, a higher one stays.  libdartgpu's load-time constructor does the same;
+// a program that is linked against another build of the library still gets it from here.
+static const int HW_QUEUES_NEED = 16;          // (never above 32)
+static void ensure_hw_queues()
+{
+    const char *v = getenv("GPU_MAX_HW_QUEUES");
+    char *end = nullptr;
+    const long have = v ? strtol(v, &end, 10) : 0;
+    if (!v || end == v || *end || have < HW_QUEUES_NEED) setenv("GPU_MAX_HW_QUEUES", std::to_string(HW_QUEUES_NEED).c_str(), 1);
+}
+
 int main(int argc, char *argv[])
 {
-    setenv("GPU_MAX_HW_QUEUES", "16", 0);      // before the first HIP call: a hardware queue per stream of the contexts in flight
+    ensure_hw_queues();                        // before the first HIP call
     Options o;
     dg_params_default(&o.p);
     if (argc == 1 || strcmp(argv[1], "-h") == 0) { usage(argv[0], o); return 0; }

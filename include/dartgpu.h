@@ -84,7 +84,9 @@ dg_ctx     *dg_init(const dg_index_view *, const dg_params *, int device, int *s
  *   flags & DG_INIT_ASYNC_AIDS  allocated and built by a library thread (a quarter of the GPU's wave slots, lowest stream priority) while the
  *                               caller already maps batches: a context picks up each aid at its next batch.
  * dg_index_wait blocks until the aids are complete (DG_OK) or failed (the mapping still works without them; text in dg_last_error).
- * dg_init_report: one line of text with the start-up split in seconds (allocation, file -> HBM, each build kernel).              */
+ * dg_init_report: one line of text with the start-up split in seconds (allocation, file -> HBM, each build kernel); its last two
+ * fields, `hw_queues_env_found=<text or unset> hw_queues_env_set=<n>`, are GPU_MAX_HW_QUEUES as the library's load-time constructor
+ * found it and as it left it (see dg_clone).                                                                                     */
 typedef struct {
     const char *bwt_path, *sa_path, *pac_path;
     int64_t l_pac; int32_t n_chr; const int64_t *chr_off; const int64_t *chr_len;
@@ -98,7 +100,9 @@ int         dg_index_wait(dg_ctx *);
 const char *dg_init_report(const dg_ctx *);
 void        dg_destroy(dg_ctx *);
 /* a second context on the same device sharing the parent's index (no copy): its own stream -- one per context -- and batch buffers (keep contexts + 1, the
- * device's copy stream, + the host's own streams <= GPU_MAX_HW_QUEUES: INTEGRATION.md 2), so two
+ * device's copy stream, + the host's own streams <= GPU_MAX_HW_QUEUES: INTEGRATION.md 2.  The library raises that variable to 16 when it
+ * loads if it is unset, unparsable or lower, which takes effect in a process that has not initialised HIP yet; dg_clone writes one line
+ * to stderr, once per process, when a device's contexts + 2 first exceed the count the library left), so two
  * batches can be in flight at once, one host thread per context -- what the reference gets from running
  * ReadMapping in `-t` threads over one shared index (Mapping.cpp:760-790).  Destroy clones before the parent. */
 dg_ctx     *dg_clone(dg_ctx *parent, int *status);
