@@ -9,6 +9,7 @@
 #include "dg_pair.h"
 #include "dg_reseed.h"
 #include "dg_sort.h"
+#include "dg_samfmt.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -96,6 +97,8 @@ struct IndexShared {
     void *d_ktab = nullptr, *d_sa_dense = nullptr;
     std::string report, report_out;
     int device = 0;
+    // chromosome names for the SAM text (dg_set_chr_names): with the index, so every clone prints them
+    uint32_t *d_chr_name_off = nullptr; char *d_chr_names = nullptr; bool chr_names_set = false; uint64_t chr_names_gen = 0;
 };
 
 struct dg_ctx {
@@ -144,6 +147,12 @@ struct dg_ctx {
     uint64_t counters[CTR_N];
     uint64_t reruns_capacity = 0, reruns_scan = 0;      // since dg_init / dg_clone
     bool want_compact = true, packed_valid = false;     // compact records: written by this run's kernels too / present for the batch that ran last
+    // SAM text of the batch that ran last (dg_batch_format_sam): per-batch inputs, scan state, the text
+    DBuf<uint32_t> sam_hdr_off, sam_qual_off, sam_qlen; DBuf<char> sam_hdr, sam_qual, sam_text; DBuf<uint64_t> sam_read_off, sam_tile;
+    unsigned long long *d_sam_stat = nullptr, *h_sam_stat = nullptr;      // total bytes + the three counters: device / page-locked copy
+    hipEvent_t ev_sam[2] = {nullptr, nullptr};
+    bool batch_done = false, sam_valid = false; size_t sam_bytes = 0;
+    size_t env_sam_first_cap = 0;      // DG_SAM_TEXT_FIRST_CAP: test hook, the first size of the text buffer in bytes (forces the "text outgrew the guess" path)
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
@@ -168,6 +177,7 @@ static void read_env(dg_ctx *c)
     c->env_chain_bpc = std::max(1, geti("DG_CHAIN_BPC", 8)); c->env_seedh_bpc = std::max(1, geti("DG_SEEDH_BPC", 8)); c->env_reseed_pct = std::max(10, geti("DG_RESEED_PCT", 100));
     c->env_rs_chunk = geti("DG_RS_CHUNK", RS_CHUNK_DIAGS); c->env_rs_chunk = std::min(1 << 24, std::max(RS_SUPER, c->env_rs_chunk / RS_SUPER * RS_SUPER));      // (a multiple of the pac super-chunk)
     c->env_rs_inline = std::min(RS_ENT_INLINE, std::max(0, geti("DG_RS_ENT_MAX", RS_ENT_INLINE))); c->env_rs_pool = std::max(0, geti("DG_RS_POOL_BLOCKS", 0));
+    c->env_sam_first_cap = (size_t)std::max(0, geti("DG_SAM_TEXT_FIRST_CAP", 0));
     c->env_seed_multi = geti("DG_SEED_MULTI", 4); if (c->env_seed_multi < 0 || c->env_seed_multi > SQF_MULTI_MAX) c->env_seed_multi = SQF_MULTI_MAX;   // rows of an interval that are located and compared with the text at once (0: single rows only)
 }
 
@@ -575,6 +585,8 @@ extern "C" void dg_destroy(dg_ctx *c)
         if (sh->aids.joinable()) sh->aids.join();
         if (sh->d_ktab) (void)hipFree(sh->d_ktab);
         if (sh->d_sa_dense) (void)hipFree(sh->d_sa_dense);
+        if (sh->d_chr_name_off) (void)hipFree(sh->d_chr_name_off);
+        if (sh->d_chr_names) (void)hipFree(sh->d_chr_names);
         delete sh; c->shared_ix = nullptr;
     }
     void *ptrs[] = { c->d_bwt, c->d_sa, c->d_pac, c->d_lockey, c->d_locchr, c->d_chroff };
@@ -586,6 +598,10 @@ extern "C" void dg_destroy(dg_ctx *c)
     c->seed_off.release(); c->ncand.release(); c->rep_off.release(); c->tile_sums.release(); c->tile_read.release(); c->slow_units.release();
     c->seeds.release(); c->work.release(); c->cands.release(); c->jobs.release(); c->job_items.release(); c->job_outs.release(); c->job_pool.release(); c->job_pool_next.release(); c->items.release(); c->hist.release(); c->heavy.release(); c->seed_heavy.release(); c->seed_heavy_sfail.release(); c->chain_picks.release(); c->chain_todo.release();
     c->reads_out.release(); c->reports.release(); c->cigpool.release(); c->cigfinal.release(); c->sjpool.release(); c->sjfinal.release();
+    c->sam_hdr_off.release(); c->sam_qual_off.release(); c->sam_qlen.release(); c->sam_hdr.release(); c->sam_qual.release(); c->sam_text.release(); c->sam_read_off.release(); c->sam_tile.release();
+    if (c->d_sam_stat) (void)hipFree(c->d_sam_stat);
+    if (c->h_sam_stat) (void)hipHostFree(c->h_sam_stat);
+    for (hipEvent_t e : c->ev_sam) if (e) (void)hipEventDestroy(e);
     c->ws.release(); c->scan_state.release(); c->scan_trace.release(); c->reads_c.release(); c->reports_c.release(); c->cig_c.release();
     for (int i = 0; i <= N_TIMERS; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
@@ -998,7 +1014,7 @@ static int enqueue_upload(dg_ctx *c, int n_reads, const uint32_t *seq_off, const
         mx = rlen[i] > mx ? rlen[i] : mx;
     }
     if (mx > DG_MAX_RLEN) { snprintf(c->err, 512, "a read is longer than DG_MAX_RLEN (%d)", DG_MAX_RLEN); return DG_ERR_ARG; }
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64));     /* the kernels read up to 24 bytes at a read position in one go */
     HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     if (n_reads) {
@@ -1060,7 +1076,7 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
     if (mx > DG_MAX_RLEN || mx > 16 * W2 || (size_t)n_reads * 16 * W2 > 0xFFFFFFF0ull) { snprintf(c->err, 512, "packed batch: read length %d does not fit %d words (or exceeds DG_MAX_RLEN / 2^32 bases)", mx, W2); return DG_ERR_ARG; }
     if (n_reads && (mx + 15) / 16 != W2) { snprintf(c->err, 512, "packed batch: words_per_read must be ceil(longest read / 16) = %d", (mx + 15) / 16); return DG_ERR_ARG; }
     const size_t nw = (size_t)n_reads * W2, bytes = nw * 16;
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sam_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64)); HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     HIPCHK(c->enc.ensure(2 * nw + 16)); HIPCHK(c->packed_in.ensure(nw + 1)); HIPCHK(c->nlist_in.ensure(n_n + 1));
     c->enc_ready = true;
@@ -1506,12 +1522,14 @@ extern "C" int dg_batch_run(dg_ctx *c, size_t used[3])
     memset(c->counters, 0, sizeof c->counters);
     if (used) used[0] = used[1] = used[2] = 0;
     c->n_t = 0;
-    c->packed_valid = false; c->full_valid = false;
-    if (c->n_reads == 0) return DG_OK;
+    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sam_valid = false;
+    if (c->n_reads == 0) { c->batch_done = true; return DG_OK; }
     c->attempt_no = 0;
-    const int rc = enqueue_run(c);
+    int rc = enqueue_run(c);
     if (rc) return rc;
-    return finish_run(c, used);
+    rc = finish_run(c, used);
+    c->batch_done = rc == DG_OK;
+    return rc;
 }
 
 static int enqueue_download(dg_ctx *c, dg_read_out *ro, dg_report_out *po, uint32_t *cig, dg_sj_out *so, const size_t caps[3])
@@ -1689,6 +1707,151 @@ extern "C" int dg_batch_device_records_compact(dg_ctx *c, void *ptrs[4], size_t 
     if (!c->packed_valid) { snprintf(c->err, 512, "dg_batch_device_records_compact: the last batch has no compact records (use dg_map_batch_compact / dg_batch_download_compact)"); return DG_ERR_ARG; }
     ptrs[0] = c->reads_c.p; ptrs[1] = c->reports_c.p; ptrs[2] = c->cig_c.p; ptrs[3] = c->sjfinal.p;
     counts[0] = (size_t)c->n_reads; counts[1] = c->used[0]; counts[2] = (size_t)c->h_tail->sizes.pad[0]; counts[3] = c->used[2];
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// SAM text on the device (dg_samfmt.h): the records of the batch that ran last -> the bytes the reference prints for them
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_set_chr_names(dg_ctx *c, int n_chr, const uint32_t *name_off, const char *names)
+{
+    if (!c) return DG_ERR_ARG;
+    IndexShared *sh = c->shared_ix;
+    if (!sh || !name_off || n_chr != c->ix.n_chr) { snprintf(c->err, 512, "dg_set_chr_names: %d names for an index of %d chromosomes", n_chr, c->ix.n_chr); return DG_ERR_ARG; }
+    for (int i = 0; i < n_chr; i++) if (name_off[i + 1] < name_off[i]) { snprintf(c->err, 512, "dg_set_chr_names: name_off decreases at %d", i); return DG_ERR_ARG; }
+    if (name_off[n_chr] > name_off[0] && !names) { snprintf(c->err, 512, "dg_set_chr_names: names is NULL"); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(sh->mu);
+    std::vector<uint32_t> off((size_t)n_chr + 1);
+    for (int i = 0; i <= n_chr; i++) off[i] = name_off[i] - name_off[0];
+    uint32_t *d_off = nullptr; char *d_names = nullptr;
+    HIPCHK(hipMalloc((void **)&d_off, off.size() * 4));
+    if (hipMalloc((void **)&d_names, (size_t)off[n_chr] + 1) != hipSuccess) { (void)hipFree(d_off); return fail(c, DG_ERR_HIP, "hipMalloc (chromosome names)", hipErrorOutOfMemory); }
+    hipError_t e = hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && off[n_chr]) e = hipMemcpy(d_names, names + name_off[0], off[n_chr], hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d_off); (void)hipFree(d_names); return fail(c, DG_ERR_HIP, "hipMemcpy (chromosome names)", e); }
+    // A formatter of any context of this index reads the two pointers and enqueues its kernels under sh->mu (dg_batch_format_sam), so under the
+    // lock every kernel that may read the old arrays is already in a stream: the device is waited for, then they are freed.
+    if (sh->d_chr_name_off) { (void)hipDeviceSynchronize(); (void)hipFree(sh->d_chr_name_off); (void)hipFree(sh->d_chr_names); }
+    sh->d_chr_name_off = d_off; sh->d_chr_names = d_names; sh->chr_names_set = true; sh->chr_names_gen++;
+    return DG_OK;
+}
+
+static int sam_offsets_ok(dg_ctx *c, const char *what, const uint32_t *off, int n)
+{
+    for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { snprintf(c->err, 512, "dg_batch_format_sam: %s decreases at read %d", what, i); return DG_ERR_ARG; }
+    return DG_OK;
+}
+
+extern "C" int dg_batch_format_sam(dg_ctx *c, const dg_sam_text *in, uint32_t flags, size_t *n_bytes, uint64_t counters[3], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_bytes) *n_bytes = 0;
+    if (counters) counters[0] = counters[1] = counters[2] = 0;
+    if (device_ms) *device_ms = 0.f;
+    c->sam_valid = false; c->sam_bytes = 0;
+    if (!in) { snprintf(c->err, 512, "dg_batch_format_sam: the input is NULL"); return DG_ERR_ARG; }
+    if (!c->batch_done) { snprintf(c->err, 512, "dg_batch_format_sam: the context has no finished batch (upload and run one first)"); return DG_ERR_ARG; }
+    const int n = c->n_reads;
+    if (in->n_pair_mode < 0 || (in->n_pair_mode & 1) || in->n_pair_mode > n) { snprintf(c->err, 512, "dg_batch_format_sam: n_pair_mode %d must be even and at most the batch's %d reads", in->n_pair_mode, n); return DG_ERR_ARG; }
+    if (n == 0) { c->sam_valid = true; return DG_OK; }
+    if (c->enc_ready) { snprintf(c->err, 512, "dg_batch_format_sam: the batch was uploaded packed, and the pipeline keeps no ASCII copy of a packed batch: upload it as ASCII"); return DG_ERR_ARG; }
+    if (!c->full_valid) { snprintf(c->err, 512, "dg_batch_format_sam: the last batch has no full records (it was mapped through dg_map_batch_compact)"); return DG_ERR_ARG; }
+    IndexShared *sh = c->shared_ix;
+    if (!sh || !sh->chr_names_set) { snprintf(c->err, 512, "dg_batch_format_sam: the chromosome names are missing (dg_set_chr_names)"); return DG_ERR_ARG; }
+    if (!in->hdr_off || (in->qual && !in->qual_off)) { snprintf(c->err, 512, "dg_batch_format_sam: an offset array is NULL"); return DG_ERR_ARG; }
+    if (sam_offsets_ok(c, "hdr_off", in->hdr_off, n) || (in->qual && sam_offsets_ok(c, "qual_off", in->qual_off, n))) return DG_ERR_ARG;
+    const size_t hdr_bytes = (size_t)in->hdr_off[n] - in->hdr_off[0], qual_bytes = in->qual ? (size_t)in->qual_off[n] - in->qual_off[0] : 0;
+    if (hdr_bytes && !in->hdr) { snprintf(c->err, 512, "dg_batch_format_sam: hdr is NULL"); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_sam_stat) {
+        HIPCHK(hipMalloc((void **)&c->d_sam_stat, 4 * 8));
+        HIPCHK(hipHostMalloc((void **)&c->h_sam_stat, 4 * 8, hipHostMallocDefault));
+        for (hipEvent_t &e : c->ev_sam) HIPCHK(hipEventCreate(&e));
+    }
+    const uint32_t n_tiles = (uint32_t)((n + SAM_LEN_THREADS - 1) / SAM_LEN_THREADS);
+    HIPCHK(c->sam_hdr_off.ensure((size_t)n + 1)); HIPCHK(c->sam_hdr.ensure(hdr_bytes + 1)); HIPCHK(c->sam_qlen.ensure((size_t)n));
+    HIPCHK(c->sam_read_off.ensure((size_t)n)); HIPCHK(c->sam_tile.ensure(n_tiles));
+    if (in->qual) { HIPCHK(c->sam_qual_off.ensure((size_t)n + 1)); HIPCHK(c->sam_qual.ensure(qual_bytes + 1)); }
+    // the text's capacity is a guess the first time (one line per read); when it was too small k_sam_write alone runs again -- never the batch
+    size_t want = hdr_bytes + qual_bytes + c->seq_bytes + (size_t)n * 96;
+    want += want / 8;
+    if (c->env_sam_first_cap && !c->sam_text.p) want = c->env_sam_first_cap;
+    if (c->sam_text.cap < want) HIPCHK(c->sam_text.ensure(want));
+    // offsets are taken relative to their first entry on the device: the kernels add them to pointers moved back by it
+    HIPCHK(hipMemcpyAsync(c->sam_hdr_off.p, in->hdr_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (hdr_bytes) HIPCHK(hipMemcpyAsync(c->sam_hdr.p, in->hdr + in->hdr_off[0], hdr_bytes, hipMemcpyHostToDevice, c->stream));
+    if (in->qual) {
+        HIPCHK(hipMemcpyAsync(c->sam_qual_off.p, in->qual_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (qual_bytes) HIPCHK(hipMemcpyAsync(c->sam_qual.p, in->qual + in->qual_off[0], qual_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    SamBatch b;
+    b.ro = c->reads_out.p; b.po = c->reports.p; b.cig = c->cigfinal.p;
+    b.seq_off = c->seq_off.p; b.rlen = c->rlen.p; b.seq = c->seq.p;
+    b.hdr_off = c->sam_hdr_off.p; b.hdr = c->sam_hdr.p - in->hdr_off[0];
+    b.qual_off = in->qual ? c->sam_qual_off.p : nullptr; b.qual = in->qual ? c->sam_qual.p - in->qual_off[0] : nullptr;
+    b.chr_off = nullptr; b.chr = nullptr; b.qlen = nullptr;      // (the names: under the index's lock, below)
+    b.n_reads = n; b.n_pair_mode = in->n_pair_mode; b.unique_only = (flags & DG_SAM_UNIQUE_ONLY) ? 1 : 0; b.multi = c->pr.multi_hit ? 1 : 0;
+    SamBatch b2 = b; uint64_t names_gen = 0;
+    const unsigned grid = (unsigned)n;
+    {   // the chromosome names are read and the kernels that use them enqueued under the index's lock: dg_set_chr_names, which replaces the
+        // arrays under the same lock, waits for the device before it frees the old ones
+        std::lock_guard<std::mutex> lk(sh->mu);
+        b.chr_off = sh->d_chr_name_off; b.chr = sh->d_chr_names; names_gen = sh->chr_names_gen;
+        b2 = b; b2.qlen = c->sam_qlen.p;
+        HIPCHK(hipEventRecord(c->ev_sam[0], c->stream));
+        HIPCHK(hipMemsetAsync(c->d_sam_stat, 0, 4 * 8, c->stream));
+        k_sam_len<<<n_tiles, SAM_LEN_THREADS, 0, c->stream>>>(b, c->sam_read_off.p, c->sam_qlen.p, c->sam_tile.p, c->d_sam_stat);
+        k_sam_top<<<1, 256, 0, c->stream>>>(c->sam_tile.p, n_tiles, c->d_sam_stat);
+        k_sam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam_read_off.p, c->sam_tile.p, c->d_sam_stat, (unsigned long long)c->sam_text.cap, c->sam_text.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev_sam[1], c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(c->h_sam_stat, c->d_sam_stat, 4 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the one wait: for the size
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->ev_sam[0], c->ev_sam[1]);
+    const size_t total = (size_t)c->h_sam_stat[0];
+    if (total > c->sam_text.cap) {                                // the guess was too small (many lines per read): the lengths stand, the writer runs again
+        HIPCHK(c->sam_text.ensure(total));
+        {
+            std::lock_guard<std::mutex> lk(sh->mu);
+            if (names_gen != sh->chr_names_gen) { snprintf(c->err, 512, "dg_batch_format_sam: the chromosome names were replaced while the text was being formatted"); return DG_ERR_ARG; }
+            HIPCHK(hipEventRecord(c->ev_sam[0], c->stream));
+            k_sam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam_read_off.p, c->sam_tile.p, c->d_sam_stat, (unsigned long long)c->sam_text.cap, c->sam_text.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(c->ev_sam[1], c->stream));
+        }
+        HIPCHK(wait_stream(c));
+        float ms2 = 0.f;
+        (void)hipEventElapsedTime(&ms2, c->ev_sam[0], c->ev_sam[1]);
+        ms += ms2;
+    }
+    c->sam_bytes = total; c->sam_valid = true;
+    if (n_bytes) *n_bytes = total;
+    if (counters) { counters[0] = c->h_sam_stat[1]; counters[1] = c->h_sam_stat[2]; counters[2] = c->h_sam_stat[3]; }
+    if (device_ms) *device_ms = ms;
+    return DG_OK;
+}
+
+extern "C" int dg_batch_download_sam(dg_ctx *c, char *out, size_t cap)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->sam_valid) { snprintf(c->err, 512, "dg_batch_download_sam: no SAM text (dg_batch_format_sam first)"); return DG_ERR_ARG; }
+    if (cap < c->sam_bytes) { snprintf(c->err, 512, "dg_batch_download_sam: output capacity too small: %zu bytes of %zu", cap, c->sam_bytes); return DG_ERR_CAPACITY; }
+    if (c->sam_bytes == 0) return DG_OK;
+    if (!out) return DG_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(out, c->sam_text.p, c->sam_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_batch_device_sam(dg_ctx *c, void **ptr, size_t *n_bytes)
+{
+    if (!c || !ptr || !n_bytes) return DG_ERR_ARG;
+    if (!c->sam_valid) { snprintf(c->err, 512, "dg_batch_device_sam: no SAM text (dg_batch_format_sam first)"); return DG_ERR_ARG; }
+    *ptr = c->sam_bytes ? c->sam_text.p : nullptr; *n_bytes = c->sam_bytes;
     return DG_OK;
 }
 

@@ -400,6 +400,16 @@ static inline void put_cigar(std::string &out, const uint32_t *ops, uint32_t n)
     for (uint32_t i = 0; i < n; i++) { put_int(out, ops[i] >> 4); out += "MIDNS"[ops[i] & 15 ? (ops[i] & 15) : 0]; }
 }
 
+// which formatter ran and its seconds, for the DART_TIMING line of the parallel pipeline
+static std::string fast_format_text(const FastStats &f)
+{
+    char b[384];
+    if (g_device_sam) snprintf(b, sizeof b, "format=device %.3f s (sum over workers: gather names and qualities %.3f s, dg_batch_format_sam %.3f s of which kernels %.3f s, text download %.3f s; %zu batches, %.4f s per batch on its worker's path)",
+                               f.t_gather + f.t_dev_call + f.t_download, f.t_gather, f.t_dev_call, f.t_dev_kernels, f.t_download, f.n_batches, (f.t_gather + f.t_dev_call + f.t_download) / (double)std::max<size_t>(1, f.n_batches));
+    else snprintf(b, sizeof b, "format=host %.3f s", f.t_fmt);
+    return b;
+}
+
 // OutputPairedAlignments / OutputSingledAlignments (Mapping.cpp:208-369) for reads [lo,hi)
 static void format_range(const Reads &R, int lo, int hi, int n_pair_mode, const dg_read_out *ro, const dg_report_out *po,
                          const uint32_t *cig, const HostIndex &ix, const Options &o, bool fastq, std::string &out, Counters &ct)
@@ -645,6 +655,14 @@ int main(int argc, char *argv[])
             }
         }
     }
+    // DART_DEVICE_SAM=1: SAM text from the device's formatter (dg_batch_format_sam) instead of the host's; -bo keeps the host's (BAM is built from host text)
+    const bool device_sam = !o.bam && getenv("DART_DEVICE_SAM") && atoi(getenv("DART_DEVICE_SAM")) != 0;
+    g_device_sam = device_sam;
+    if (device_sam) {
+        std::vector<uint32_t> noff{0}; std::string nflat;
+        for (const std::string &nm : ix.names) { nflat += nm; noff.push_back((uint32_t)nflat.size()); }
+        for (dg_ctx *r : roots) if (dg_set_chr_names(r, (int)ix.names.size(), noff.data(), nflat.data())) { fprintf(stderr, "Error! %s\n", dg_last_error(r)); return 1; }
+    }
     const double t_init1 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     fprintf(stdout, "\nLoad the reference sequences...\n");
 
@@ -681,7 +699,7 @@ int main(int argc, char *argv[])
                                                  fileno(sam), &off, total, sjmap, t0, ferr, fst, pool, gi);
                 fseeko(sam, (off_t)off, SEEK_SET);
                 if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, assemble %.3f s (of which page-locked allocation %.3f s), map (sum over workers) %.3f s, format %.3f s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fst.t_asm, fst.t_alloc, fst.t_map, fst.t_fmt, fst.t_write);
+                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, assemble %.3f s (of which page-locked allocation %.3f s), map (sum over workers) %.3f s, %s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fst.t_asm, fst.t_alloc, fst.t_map, fast_format_text(fst).c_str(), fst.t_write);
                 gi->m1.close_now(); gi->m2.close_now();
                 continue;
             }
@@ -702,7 +720,7 @@ int main(int argc, char *argv[])
                                              fileno(sam), &off, total, sjmap, t0, ferr, fst, pool, lib == 0 ? &pre : nullptr);
             fseeko(sam, (off_t)off, SEEK_SET);
             if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, assemble %.3f s (of which page-locked allocation %.3f s), map (sum over workers) %.3f s, format %.3f s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fst.t_asm, fst.t_alloc, fst.t_map, fst.t_fmt, fst.t_write);
+            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, assemble %.3f s (of which page-locked allocation %.3f s), map (sum over workers) %.3f s, %s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fst.t_asm, fst.t_alloc, fst.t_map, fast_format_text(fst).c_str(), fst.t_write);
             if (s1.fp) fclose(s1.fp);
             if (s2.fp) fclose(s2.fp);
             continue;
@@ -711,7 +729,7 @@ int main(int argc, char *argv[])
         // Contexts = devices x DART_INFLIGHT (dg_clone: contexts of a device share its index), so the next batch is
         // parsed, and the previous one formatted and written, while the GPUs map.  Output order = input order.
         struct Batch { Reads rd; int odd = 0; std::unique_ptr<dg_read_out[]> ro; std::unique_ptr<dg_report_out[]> po; std::unique_ptr<uint32_t[]> cig; std::unique_ptr<dg_sj_out[]> sj;   // new T[n]: no zero fill
-                       size_t n_reads = 0; size_t used[3] = {0, 0, 0}; int rc = 0; std::string err; size_t seq = 0; std::vector<std::string> outs; std::vector<Counters> cts; };
+                       size_t n_reads = 0; size_t used[3] = {0, 0, 0}; int rc = 0; std::string err; size_t seq = 0; std::vector<std::string> outs; std::vector<Counters> cts; double t_dev = 0; };
         std::mutex mu; std::condition_variable cv_in, cv_out, cv_space;
         std::deque<std::unique_ptr<Batch>> inq; std::map<size_t, std::unique_ptr<Batch>> done;
         bool reader_done = false, failed = false; size_t in_flight = 0;
@@ -744,6 +762,22 @@ int main(int argc, char *argv[])
             reader_done = true; cv_in.notify_all(); cv_out.notify_all();
         });
 
+        // device formatter: the text of the reads [first, first + n) that c has just mapped, appended to the batch's (Reads holds names and qualities in the call's flat form)
+        auto device_text = [&](Batch &b, dg_ctx *c, int first, int n, int n_pair_mode) -> int {
+            const double t = now();
+            dg_sam_text in; in.hdr_off = b.rd.hoff.data() + first; in.hdr = b.rd.hdr.data(); in.qual_off = b.rd.qoff.data() + first; in.qual = fastq ? b.rd.qual.data() : nullptr; in.n_pair_mode = n_pair_mode;
+            size_t nb = 0; uint64_t ct[3] = {0, 0, 0};
+            int rc = dg_batch_format_sam(c, &in, o.unique ? DG_SAM_UNIQUE_ONLY : 0u, &nb, ct, nullptr);
+            if (!rc) {
+                std::string &out = b.outs[0];
+                const size_t at = out.size();
+                out.resize(at + nb);
+                rc = dg_batch_download_sam(c, &out[at], nb);
+                b.cts[0].unmapped += (long long)ct[0]; b.cts[0].unique += (long long)ct[1]; b.cts[0].paired += (long long)ct[2];
+            }
+            b.t_dev += now() - t;
+            return rc;
+        };
         auto map_one = [&](Batch &b, dg_ctx *c) {
             const int n = (int)b.rd.size(), n_even = n - b.odd;
             const std::vector<uint32_t> &off = b.rd.soff; std::vector<uint16_t> rl(n); const std::string &flat = b.rd.seq;   // the parsed bases are the device input
@@ -758,12 +792,15 @@ int main(int argc, char *argv[])
                 size_t used1[3] = {0, 0, 0}, used2[3] = {0, 0, 0};
                 dg_params p = o.p; p.paired = pair_end ? 1 : 0;
                 dg_set_params(c, &p);
+                if (device_sam) { b.outs.assign(1, std::string()); b.cts.assign(1, Counters()); b.t_dev = 0; }
                 int rc = n_even ? dg_map_batch(c, n_even, off.data(), rl.data(), flat.data(), b.ro.get(), b.po.get(), b.cig.get(), b.sj.get(), caps, used1) : 0;
+                if (rc == 0 && n_even && device_sam) rc = device_text(b, c, 0, n_even, pair_end ? n_even : 0);
                 if (rc == 0 && b.odd) {
                     p.paired = 0; dg_set_params(c, &p);
                     size_t caps2[3] = { caps[0] - used1[0], caps[1] - used1[1], caps[2] - used1[2] };
                     rc = dg_map_batch(c, b.odd, off.data() + n_even, rl.data() + n_even, flat.data(), b.ro.get() + n_even, b.po.get() + used1[0],
                                       b.cig.get() + used1[1], b.sj.get() + used1[2], caps2, used2);
+                    if (rc == 0 && device_sam) rc = device_text(b, c, n_even, b.odd, 0);      // (before the offsets below are rebased: the device holds the batch's own)
                     if (rc == DG_ERR_CAPACITY) for (int q = 0; q < 3; q++) used2[q] += used1[q];
                     else {
                         for (int k = n_even; k < n; k++) { b.ro[k].rep_off += (int32_t)used1[0]; b.ro[k].sj_off += (int32_t)used1[2]; }
@@ -805,9 +842,10 @@ int main(int argc, char *argv[])
                 }
                 double t = now();
                 map_one(*b, ctx[w]);
-                const double tm = now() - t; t = now();
-                if (!b->rc) format_one(*b);
-                const double tf = now() - t;
+                double tm = now() - t; t = now();
+                if (!b->rc && !device_sam) format_one(*b);
+                double tf = now() - t;
+                if (device_sam) { tm -= b->t_dev; tf = b->t_dev; b->rd = Reads(); }
                 std::lock_guard<std::mutex> lk(mu);
                 t_map += tm; t_fmt += tf;
                 if (b->rc) failed = true;
@@ -852,7 +890,7 @@ int main(int argc, char *argv[])
         pf1.finish(); pf2.finish();
         for (auto &w : workers) w.join();
         if (bad) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", bad_rc, bad_msg.c_str()); return 1; }
-        if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] read+parse %.3f s, map (sum over workers) %.3f s, format %.3f s, write %.3f s\n", t_read, t_map, t_fmt, t_write);
+        if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] read+parse %.3f s, map (sum over workers) %.3f s, format=%s %.3f s, write %.3f s\n", t_read, t_map, device_sam ? "device" : "host", t_fmt, t_write);
         if (s1.fp) fclose(s1.fp);
         if (s2.fp) fclose(s2.fp);
         s1.inf.reset(); s2.inf.reset();              // (the inflater threads end before their files are closed)

@@ -331,15 +331,23 @@ static void format_views(const RView *V, int lo, int hi, int n_pair_mode, const 
 static int hdr_beg_f(const char *s, int len) { for (int i = 1; i < len; i++) if (s[i] != '>' && s[i] != '@') return i; return len - 1; }
 static int hdr_end_f(const char *s, int len) { for (int i = 1; i < len; i++) if (s[i] == ' ' || s[i] == '/' || s[i] == '\t') return i; return len - 1; }
 
+static inline void rev_copy(char *d, const char *s, size_t l) { if (g_avx2) rev_copy_avx2(d, s, l); else for (size_t i = 0; i < l; i++) d[i] = s[l - 1 - i]; }
+
+// DART_DEVICE_SAM=1: the SAM text of a batch is formatted on the GPU (dg_batch_format_sam) right behind its mapping, on the same context, and
+// downloaded into the slot; format_views is not run.  Set by the host program before the first library.
+static bool g_device_sam = false;
+
 struct FastSlot {                       // one batch travelling through the stages
     size_t first = 0; int n = 0, odd = 0; size_t seqno = 0;
+    std::vector<uint32_t> hoff, qoff; char *names_quals = nullptr; size_t nq_cap = 0;      // device formatter: the batch's names and stored qualities, flat
+    char *text = nullptr; size_t text_cap = 0, text_n = 0; uint64_t dev_ct[3] = {0, 0, 0}; //                   its text and counters
     std::vector<RView> view; std::vector<uint32_t> soff; std::vector<uint16_t> rl;
     char *seq = nullptr; size_t seq_cap = 0, n_cap = 0;            // page-locked
     dg_read_out *ro = nullptr; dg_report_out *po = nullptr; uint32_t *cig = nullptr; dg_sj_out *sj = nullptr; size_t caps[3] = {0, 0, 0}, used[3] = {0, 0, 0};
     int rc = 0; std::string err;
 };
 
-struct FastStats { double t_index = 0, t_asm = 0, t_map = 0, t_fmt = 0, t_write = 0, t_alloc = 0; };
+struct FastStats { double t_index = 0, t_asm = 0, t_map = 0, t_fmt = 0, t_write = 0, t_alloc = 0, t_gather = 0, t_dev_call = 0, t_dev_kernels = 0, t_download = 0; size_t n_batches = 0; };
 
 // Batch arenas: ordinary memory by default -- page-locking costs ~1 s per GB, more than a short job saves; DART_PINNED=1 page-locks them
 // (then the copies to and from the GPU are plain DMA transfers: worth it for long runs with several contexts in flight)
@@ -369,7 +377,7 @@ struct SlotPool {
         if (g_pinned_slots) th = std::thread([this, batch_reads, bytes_per_read]() { const size_t z[3] = {0, 0, 0}; for (auto &s : slots) slot_reserve(s, batch_reads, batch_reads * bytes_per_read, z); });
     }
     void wait() { if (th.joinable()) th.join(); }
-    ~SlotPool() { wait(); for (auto &s : slots) { arena_free(s.seq); arena_free(s.ro); arena_free(s.po); arena_free(s.cig); arena_free(s.sj); } }
+    ~SlotPool() { wait(); for (auto &s : slots) { arena_free(s.seq); arena_free(s.ro); arena_free(s.po); arena_free(s.cig); arena_free(s.sj); arena_free(s.names_quals); arena_free(s.text); } }
 };
 
 // The mapped read files of a library and the positions of their records.  The host program starts this for its first library before it
@@ -582,7 +590,45 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                     break;
                 }
             }
-            { std::lock_guard<std::mutex> lk(mu); st.t_map += now() - tm; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
+            double t_gather = 0, t_call = 0, t_dl = 0; float dev_ms = 0.f;
+            if (!s->rc && g_device_sam) {
+                // the batch's names and qualities, flat, mate 2's qualities in stored order (reversed); then the text from the device
+                const double tg = now();
+                const int n = s->n;
+                s->hoff.resize((size_t)n + 1); s->qoff.resize((size_t)n + 1);
+                uint32_t ho = 0, qo = 0; bool fits = true;
+                for (int k = 0; k < n; k++) { s->hoff[k] = ho; s->qoff[k] = qo; const RView &v = s->view[k]; if ((uint64_t)ho + v.hl + qo + v.ql > 0xFFFFFF00ull) { fits = false; break; } ho += v.hl; qo += v.ql; }
+                s->hoff[n] = ho; s->qoff[n] = qo;
+                if (!fits) { s->rc = DG_ERR_ARG; s->err = "names and qualities of a batch exceed 32-bit offsets"; }
+                else {
+                    if ((size_t)ho + qo + 64 > s->nq_cap) { arena_free(s->names_quals); s->nq_cap = ((size_t)ho + qo) * 9 / 8 + 4096; s->names_quals = (char *)arena_alloc(s->nq_cap); }
+                    char *hb = s->names_quals, *qb = s->names_quals + ho;
+                    const int TG = std::max(1, T / 8);
+                    parallel_for(TG, [&](int tid) {
+                        const int lo = (int)((long long)n * tid / TG), hi = (int)((long long)n * (tid + 1) / TG);
+                        for (int k = lo; k < hi; k++) {
+                            const RView &v = s->view[k];
+                            memcpy(hb + s->hoff[k], v.h, v.hl);
+                            if (v.rc) rev_copy(qb + s->qoff[k], v.q, v.ql); else memcpy(qb + s->qoff[k], v.q, v.ql);
+                        }
+                    });
+                    t_gather = now() - tg;
+                    dg_sam_text in; in.hdr_off = s->hoff.data(); in.hdr = hb; in.qual_off = s->qoff.data(); in.qual = qb; in.n_pair_mode = (pair_end && !s->odd) ? n : 0;
+                    size_t nb = 0;
+                    const double tc = now();
+                    int rc = dg_batch_format_sam(ctx[w], &in, unique_only ? DG_SAM_UNIQUE_ONLY : 0u, &nb, s->dev_ct, &dev_ms);
+                    t_call = now() - tc;
+                    if (!rc) {
+                        const double td = now();
+                        if (nb > s->text_cap) { arena_free(s->text); s->text_cap = nb + nb / 8 + 4096; s->text = (char *)arena_alloc(s->text_cap); }
+                        rc = dg_batch_download_sam(ctx[w], s->text, s->text_cap);
+                        s->text_n = nb;
+                        t_dl = now() - td;
+                    }
+                    if (rc) { s->rc = rc; s->err = dg_last_error(ctx[w]); }
+                }
+            }
+            { std::lock_guard<std::mutex> lk(mu); st.t_map += now() - tm - t_gather - t_call - t_dl; st.t_gather += t_gather; st.t_dev_call += t_call; st.t_dev_kernels += dev_ms * 1e-3; st.t_download += t_dl; st.n_batches++; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
             cv.notify_all();
         }
         { std::lock_guard<std::mutex> lk(mu); mappers_left--; }
@@ -591,7 +637,8 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
 
     // format (this thread drives; T threads do the work) and write (its own thread, T threads again), batches in order; two sets of
     // text buffers, so batch b+1 is formatted while batch b is written
-    struct TextSet { std::vector<TextBuf> bufs; std::vector<Counters> cts; FastSlot *slot = nullptr; bool full = false; };
+    struct TextSet { std::vector<TextBuf> bufs; std::vector<Counters> cts; FastSlot *slot = nullptr; bool full = false;
+                     std::vector<std::pair<const char *, size_t>> pieces; };      // the text in file order: the formatter threads' buffers, or the slot's device text
     TextSet sets[2];
     for (auto &ts : sets) { ts.bufs.resize(TF); ts.cts.resize(TF); }
     bool fmt_done = false;
@@ -603,7 +650,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             const double tw = now();
             FastSlot *s = ts.slot;
             std::vector<size_t> offs(TF + 1, 0);
-            for (int k = 0; k < TF; k++) offs[k + 1] = offs[k] + ts.bufs[k].n;
+            for (int k = 0; k < TF; k++) offs[k + 1] = offs[k] + ts.pieces[k].second;
             const uint64_t base = *file_off;
             char *win = nullptr; size_t win_len = 0; const uint64_t a0 = base & ~(uint64_t)4095;
             if (use_mmap && offs[TF] && ftruncate(fd, (off_t)(base + offs[TF])) == 0) {      // copy into a shared mapping of the file's new part
@@ -616,10 +663,11 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             if (use_mmap && offs[TF] && !win) write_errno = errno ? errno : EIO;
             else parallel_for(TW, [&](int wt) {
                 for (int tid = wt; tid < TF; tid += TW) {
-                    if (win) { memcpy(win + (base - a0) + offs[tid], ts.bufs[tid].b, ts.bufs[tid].n); continue; }
+                    const char *piece = ts.pieces[tid].first; const size_t piece_n = ts.pieces[tid].second;
+                    if (win) { memcpy(win + (base - a0) + offs[tid], piece, piece_n); continue; }
                     size_t done = 0;
-                    while (done < ts.bufs[tid].n) {
-                        const ssize_t w = pwrite(fd, ts.bufs[tid].b + done, ts.bufs[tid].n - done, (off_t)(base + offs[tid] + done));
+                    while (done < piece_n) {
+                        const ssize_t w = pwrite(fd, piece + done, piece_n - done, (off_t)(base + offs[tid] + done));
                         if (w < 0 && errno == EINTR) continue;
                         if (w <= 0) { write_errno = w < 0 ? errno : ENOSPC; break; }
                         done += (size_t)w;
@@ -654,12 +702,20 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
         { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !ts.full || failed; }); if (failed) break; }
         const double tf = now();
         const int n = s->n, n_pair_mode = (pair_end && !s->odd) ? n : 0;
-        parallel_for(TF, [&](int tid) {
-            int lo = (int)((long long)n * tid / TF) & ~1, hi = tid == TF - 1 ? n : ((int)((long long)n * (tid + 1) / TF) & ~1);
-            ts.bufs[tid].n = 0; ts.cts[tid] = Counters();
-            format_views(s->view.data(), lo, hi, n_pair_mode, s->ro, s->po, s->cig, names, unique_only, multi, true, ts.bufs[tid], ts.cts[tid]);
-        });
-        st.t_fmt += now() - tf;
+        ts.pieces.assign(TF, std::make_pair((const char *)nullptr, (size_t)0));
+        if (g_device_sam) {                                   // formatted on the device behind the mapping: the text is in the slot
+            for (int tid = 0; tid < TF; tid++) ts.cts[tid] = Counters();
+            ts.pieces[0] = std::make_pair((const char *)s->text, s->text_n);
+            ts.cts[0].unmapped = (long long)s->dev_ct[0]; ts.cts[0].unique = (long long)s->dev_ct[1]; ts.cts[0].paired = (long long)s->dev_ct[2];
+        } else {
+            parallel_for(TF, [&](int tid) {
+                int lo = (int)((long long)n * tid / TF) & ~1, hi = tid == TF - 1 ? n : ((int)((long long)n * (tid + 1) / TF) & ~1);
+                ts.bufs[tid].n = 0; ts.cts[tid] = Counters();
+                format_views(s->view.data(), lo, hi, n_pair_mode, s->ro, s->po, s->cig, names, unique_only, multi, true, ts.bufs[tid], ts.cts[tid]);
+                ts.pieces[tid] = std::make_pair((const char *)ts.bufs[tid].b, ts.bufs[tid].n);
+            });
+            st.t_fmt += now() - tf;
+        }
         { std::lock_guard<std::mutex> lk(mu); ts.slot = s; ts.full = true; }
         cv.notify_all();
         next_out++; fill ^= 1;

@@ -88,6 +88,22 @@ class IndexFiles(C.Structure):
 INIT_ASYNC_AIDS = 1
 
 
+class SamText(C.Structure):
+    _fields_ = [("hdr_off", C.c_void_p), ("hdr", C.c_void_p), ("qual_off", C.c_void_p), ("qual", C.c_void_p), ("n_pair_mode", C.c_int32)]
+
+
+SAM_UNIQUE_ONLY = 1
+
+
+def flatten_strings(items):
+    """list of bytes / str -> (u32 offsets [n + 1], u8 array): the form dg_set_chr_names and dg_batch_format_sam take names and qualities in"""
+    bs = [x if isinstance(x, (bytes, bytearray)) else x.encode("latin1") for x in items]
+    off = np.zeros(len(bs) + 1, np.uint32)
+    if bs:
+        off[1:] = np.cumsum([len(x) for x in bs])
+    return off, np.frombuffer(b"".join(bs) + b"\0", np.uint8).copy()
+
+
 class Index:
     """The BWA-format index files as the reference loads them (bwt_index.cpp:15-35,102-121,229-251).  The headers and the chromosome
     table are read at once; the three big arrays only when something asks for them (dg_init's host-array view, tests): dg_init_files
@@ -215,6 +231,11 @@ def _load_lib():
     if hasattr(lib, "dg_batch_device_records_compact"):      # (absent from older builds of the library loaded through DARTGPU_LIB for A/B runs)
         lib.dg_batch_device_records_compact.argtypes = [vp, vp, vp]
     lib.dg_last_timings.argtypes = [vp, vp, vp, C.c_int]
+    if hasattr(lib, "dg_batch_format_sam"):                  # (likewise: the device's SAM formatter)
+        lib.dg_set_chr_names.argtypes = [vp, C.c_int, vp, vp]
+        lib.dg_batch_format_sam.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
+        lib.dg_batch_download_sam.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_batch_device_sam.argtypes = [vp, vp, vp]
     lib.dg_last_counters.argtypes = [vp, vp, C.c_int]
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
@@ -299,6 +320,46 @@ class DartGPU:
             self.ctx = self.lib.dg_init(C.byref(v), C.byref(self.params), device, C.byref(st))
         if not self.ctx:
             raise RuntimeError("dg_init failed (%d): %s" % (st.value, (self.lib.dg_last_error(None) or b"").decode()))
+        if hasattr(self.lib, "dg_set_chr_names"):            # (an older build loaded through DARTGPU_LIB has no formatter: format_sam then raises)
+            self.set_chr_names(index.names)
+
+    def set_chr_names(self, names):
+        """the chromosome names the device's SAM formatter prints (dg_set_chr_names): kept with the index, shared by clones"""
+        off, flat = flatten_strings(names)
+        self._chk(self.lib.dg_set_chr_names(self.ctx, len(names), off.ctypes.data, flat.ctypes.data), "dg_set_chr_names")
+
+    def format_sam(self, headers, quals, n_pair_mode: int, unique_only: bool = False):
+        """SAM text of the batch that ran last, formatted on the device (dg_batch_format_sam + dg_batch_download_sam) -> (bytes, counters);
+        headers / quals: one bytes or str per read, qualities in stored order (mate 2's reversed), quals None = FASTA ('*');
+        counters: dict unmapped / unique / paired; self.sam_device_ms holds the kernels' device time"""
+        if not hasattr(self.lib, "dg_batch_format_sam"):
+            raise RuntimeError("this build of libdartgpu.so has no dg_batch_format_sam")
+        ho, hb = flatten_strings(headers)
+        t = SamText()
+        t.hdr_off, t.hdr, t.n_pair_mode = ho.ctypes.data, hb.ctypes.data, int(n_pair_mode)
+        if quals is not None:
+            qo, qb = flatten_strings(quals)
+            t.qual_off, t.qual = qo.ctypes.data, qb.ctypes.data
+        nb = C.c_size_t(0); ct = (C.c_uint64 * 3)(); ms = C.c_float(0)
+        self._chk(self.lib.dg_batch_format_sam(self.ctx, C.byref(t), SAM_UNIQUE_ONLY if unique_only else 0, C.byref(nb), ct, C.byref(ms)), "dg_batch_format_sam")
+        self.sam_device_ms = float(ms.value)
+        out = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_batch_download_sam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_sam")
+        return out[:int(nb.value)].tobytes(), dict(unmapped=int(ct[0]), unique=int(ct[1]), paired=int(ct[2]))
+
+    def device_sam_tensor(self):
+        """torch uint8 view of the SAM text in HBM (dg_batch_device_sam), valid until the next upload or run (for RCCL collectives)"""
+        import torch
+        ptr = C.c_void_p(); nb = C.c_size_t(0)
+        self._chk(self.lib.dg_batch_device_sam(self.ctx, C.byref(ptr), C.byref(nb)), "dg_batch_device_sam")
+        if not nb.value:
+            return torch.empty(0, dtype=torch.uint8, device="cuda")
+
+        class _View:
+            pass
+        v = _View()
+        v.__cuda_array_interface__ = {"shape": (int(nb.value),), "typestr": "|u1", "data": (int(ptr.value), False), "version": 2}
+        return torch.as_tensor(v, device="cuda")
 
     def wait_index(self):
         self._chk(self.lib.dg_index_wait(self.ctx), "dg_index_wait")

@@ -188,6 +188,40 @@ int dg_batch_device_ptrs_compact(dg_ctx *, void *ptrs[2]);
  *   ptrs[3] dg_sj_out[counts[3]], grouped by read in read order (read_idx is the read's index inside the batch)                    */
 int dg_batch_device_records_compact(dg_ctx *, void *ptrs[4], size_t counts[4]);
 
+/* ---- SAM text on the device: the last batch's records -> the bytes OutputPairedAlignments / OutputSingledAlignments print (Mapping.cpp:208-369) ----
+ * The formatter reads what the batch left in HBM -- the full records and the reads' ASCII bases -- plus the names and qualities given here, and
+ * leaves ONE contiguous byte array in HBM: the lines of read 0, read 1, ... in read order, a read's lines in report order.  The bytes are those
+ * dart_amd/sam.py::format_records returns for the same records, whatever the launch geometry.
+ *   dg_set_chr_names   chromosome i's name = names[name_off[i] .. name_off[i+1]); kept with the index and shared by its clones; n_chr must be
+ *                      the index's, else DG_ERR_ARG.  Calling it again replaces the names for every context of the index: it waits for the
+ *                      device first, so a text already enqueued keeps the names it started with; a dg_batch_format_sam that is between its
+ *                      two launches of the writing kernel at that moment (the rare second launch) returns DG_ERR_ARG instead of mixing names.
+ *                      Set the names once, before the batches, as a host program does.
+ *   dg_sam_text        read i's name = hdr[hdr_off[i] .. hdr_off[i+1]) (any length), its quality = qual[qual_off[i] .. qual_off[i+1]) in STORED
+ *                      order (mate 2's reversed, as its bases are reverse-complemented) and printed as a C string (up to its first NUL byte);
+ *                      qual == NULL: FASTA input, the column is '*'.  Reads below n_pair_mode (even, <= n_reads) are mates 2i, 2i+1.
+ *   flags              DG_SAM_UNIQUE_ONLY = the reference's -unique; multi-hit output (-m) follows the context's params
+ *   counters           [0] unmapped reads, [1] reads with MAPQ 50, [2] reads in shown pairs -- the reference's statistics block
+ *   device_ms          device time of the formatter's kernels (may be NULL)
+ * dg_batch_format_sam enqueues on the context's stream behind the batch, grows its own device buffers, and waits once, for the size (when
+ * the text outgrew the buffer's first guess the writing kernel -- never the batch -- runs a second time).  DG_ERR_ARG, with a text in
+ * dg_last_error: no finished batch on the context; no full records (after dg_map_batch_compact); a batch uploaded PACKED (the pipeline keeps
+ * no ASCII copy of those reads, so N positions and the bases themselves are not there to print: upload as ASCII); no chromosome names;
+ * offsets that decrease; n_pair_mode odd or larger than the batch.  A batch of 0 reads gives 0 bytes.
+ * dg_batch_download_sam copies the text out (DG_ERR_CAPACITY, nothing written, when cap < n_bytes); dg_batch_device_sam gives the text in HBM,
+ * valid until the next upload or run on this context -- what a multi-GPU host hands to RCCL.
+ * dg_last_timings / dg_last_counters keep the batch's values.                                                                              */
+typedef struct {
+    const uint32_t *hdr_off; const char *hdr;
+    const uint32_t *qual_off; const char *qual;
+    int32_t n_pair_mode;
+} dg_sam_text;
+#define DG_SAM_UNIQUE_ONLY 1u
+int dg_set_chr_names(dg_ctx *, int n_chr, const uint32_t *name_off, const char *names);
+int dg_batch_format_sam(dg_ctx *, const dg_sam_text *in, uint32_t flags, size_t *n_bytes, uint64_t counters[3], float *device_ms);
+int dg_batch_download_sam(dg_ctx *, char *out, size_t cap);
+int dg_batch_device_sam(dg_ctx *, void **ptr, size_t *n_bytes);
+
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
 int dg_last_timings(dg_ctx *, const char **names, float *ms, int cap);
