@@ -10,6 +10,7 @@
 #include "dg_reseed.h"
 #include "dg_sort.h"
 #include "dg_samfmt.h"
+#include "dg_fastq.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -152,6 +153,12 @@ struct dg_ctx {
     unsigned long long *d_sam_stat = nullptr, *h_sam_stat = nullptr;      // total bytes + the three counters: device / page-locked copy
     hipEvent_t ev_sam[2] = {nullptr, nullptr};
     bool batch_done = false, sam_valid = false; size_t sam_bytes = 0;
+    // FASTQ text parsed on the device (dg_batch_upload_fastq, dg_fastq.h): the texts, their line starts, the scan state; the batch's names and stored
+    // qualities stay resident for dg_batch_format_sam_resident in buffers of their own (a dg_batch_format_sam with host arrays uses sam_*)
+    DBuf<unsigned char> fq_text; DBuf<uint32_t> fq_lines, fq_tile_cnt, fq_name_at, fq_name_len, fq_loc, fq_hdr_off, fq_qual_off; DBuf<unsigned long long> fq_tile_sum; DBuf<char> fq_hdr, fq_qual;
+    FqInfo *d_fq_info = nullptr, *h_fq_info = nullptr;                     // the sizes block: device / page-locked copy
+    hipEvent_t ev_fq[2] = {nullptr, nullptr};
+    bool fq_valid = false; size_t fq_hdr_bytes = 0, fq_qual_bytes = 0; float fq_ms = 0.f;      // the batch on the context came from dg_batch_upload_fastq
     size_t env_sam_first_cap = 0;      // DG_SAM_TEXT_FIRST_CAP: test hook, the first size of the text buffer in bytes (forces the "text outgrew the guess" path)
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
@@ -602,6 +609,11 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->d_sam_stat) (void)hipFree(c->d_sam_stat);
     if (c->h_sam_stat) (void)hipHostFree(c->h_sam_stat);
     for (hipEvent_t e : c->ev_sam) if (e) (void)hipEventDestroy(e);
+    c->fq_text.release(); c->fq_lines.release(); c->fq_tile_cnt.release(); c->fq_name_at.release(); c->fq_name_len.release(); c->fq_loc.release(); c->fq_hdr_off.release(); c->fq_qual_off.release();
+    c->fq_tile_sum.release(); c->fq_hdr.release(); c->fq_qual.release();
+    if (c->d_fq_info) (void)hipFree(c->d_fq_info);
+    if (c->h_fq_info) (void)hipHostFree(c->h_fq_info);
+    for (hipEvent_t e : c->ev_fq) if (e) (void)hipEventDestroy(e);
     c->ws.release(); c->scan_state.release(); c->scan_trace.release(); c->reads_c.release(); c->reports_c.release(); c->cig_c.release();
     for (int i = 0; i <= N_TIMERS; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
@@ -1014,7 +1026,7 @@ static int enqueue_upload(dg_ctx *c, int n_reads, const uint32_t *seq_off, const
         mx = rlen[i] > mx ? rlen[i] : mx;
     }
     if (mx > DG_MAX_RLEN) { snprintf(c->err, 512, "a read is longer than DG_MAX_RLEN (%d)", DG_MAX_RLEN); return DG_ERR_ARG; }
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->fq_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64));     /* the kernels read up to 24 bytes at a read position in one go */
     HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     if (n_reads) {
@@ -1076,7 +1088,7 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
     if (mx > DG_MAX_RLEN || mx > 16 * W2 || (size_t)n_reads * 16 * W2 > 0xFFFFFFF0ull) { snprintf(c->err, 512, "packed batch: read length %d does not fit %d words (or exceeds DG_MAX_RLEN / 2^32 bases)", mx, W2); return DG_ERR_ARG; }
     if (n_reads && (mx + 15) / 16 != W2) { snprintf(c->err, 512, "packed batch: words_per_read must be ceil(longest read / 16) = %d", (mx + 15) / 16); return DG_ERR_ARG; }
     const size_t nw = (size_t)n_reads * W2, bytes = nw * 16;
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sam_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->fq_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64)); HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     HIPCHK(c->enc.ensure(2 * nw + 16)); HIPCHK(c->packed_in.ensure(nw + 1)); HIPCHK(c->nlist_in.ensure(n_n + 1));
     c->enc_ready = true;
@@ -1098,6 +1110,121 @@ extern "C" int dg_batch_upload_packed(dg_ctx *c, int n_reads, int rlen_all, cons
     const int rc = enqueue_upload_packed(c, n_reads, rlen_all, rlen, words_per_read, words, nlist, n_n);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// batch input as FASTQ text (dg_fastq.h): the file bytes go up once, six kernels cut them into the batch -- bases, names, stored qualities -- in HBM
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_fastq_tile(void) { return FQ_TILE; }
+
+extern "C" int dg_batch_upload_fastq(dg_ctx *c, const dg_fastq_text *in, int *n_reads_out)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_reads_out) *n_reads_out = 0;
+    // whatever happens below, the context holds no batch until this call has succeeded
+    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->fq_valid = false;
+    c->fq_hdr_bytes = c->fq_qual_bytes = 0; c->fq_ms = 0.f;
+    if (!in) { snprintf(c->err, 512, "dg_batch_upload_fastq: the input is NULL"); return DG_ERR_ARG; }
+    const size_t n1 = in->text1 ? in->n1 : 0, n2 = in->text2 ? in->n2 : 0;
+    const bool two = in->text2 != nullptr && in->n2 > 0;
+    if ((in->n1 && !in->text1) || in->max_reads < 0) { snprintf(c->err, 512, "dg_batch_upload_fastq: text1 is NULL or max_reads is negative"); return DG_ERR_ARG; }
+    if (n1 >= 0xFFFFFF00ull || n2 >= 0xFFFFFF00ull) { snprintf(c->err, 512, "dg_batch_upload_fastq: a text must be smaller than 2^32 - 256 bytes"); return DG_ERR_ARG; }
+    if (n1 == 0 && !two) { c->fq_valid = true; return DG_OK; }       // no text: no reads
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->d_fq_info) {
+        HIPCHK(hipMalloc((void **)&c->d_fq_info, sizeof(FqInfo)));
+        HIPCHK(hipHostMalloc((void **)&c->h_fq_info, sizeof(FqInfo), hipHostMallocDefault));
+        for (hipEvent_t &e : c->ev_fq) HIPCHK(hipEventCreate(&e));
+    }
+    // capacities, all from the arguments (nothing is asked of the device before the one wait): a record has at least one byte per existing line, so a
+    // text of n bytes holds at most n + 1 line starts; the three outputs together are never larger than the texts
+    const size_t max_reads = (size_t)in->max_reads;
+    const size_t rec_cap[2] = { two ? (max_reads + 1) / 2 : max_reads, two ? max_reads / 2 : 0 };
+    const size_t nb[2] = { n1, n2 };
+    size_t line_cap[2], tiles[2];
+    for (int f = 0; f < 2; f++) { line_cap[f] = std::min(4 * rec_cap[f] + 1, nb[f] + 1); tiles[f] = (nb[f] + FQ_TILE - 1) / FQ_TILE; }
+    const size_t off2 = (n1 + 16 + 255) & ~(size_t)255, text_bytes = n1 + n2;
+    const size_t tile_stride = std::max(tiles[0], tiles[1]);
+    const size_t reads_bound = std::min(max_reads, (n1 + 4) / 4 + (n2 + 4) / 4);          // (records <= ceil(lines / 4), lines <= bytes + 1)
+    const size_t len_tiles = std::max<size_t>(1, (reads_bound + FQ_THREADS - 1) / FQ_THREADS);
+    HIPCHK(c->fq_text.ensure(off2 + n2 + 32)); HIPCHK(c->fq_lines.ensure(line_cap[0] + line_cap[1] + 2)); HIPCHK(c->fq_tile_cnt.ensure(2 * tile_stride + 1));
+    HIPCHK(c->fq_name_at.ensure(reads_bound + 1)); HIPCHK(c->fq_name_len.ensure(reads_bound + 1)); HIPCHK(c->fq_loc.ensure(3 * (reads_bound + 1))); HIPCHK(c->fq_tile_sum.ensure(3 * len_tiles));
+    HIPCHK(c->fq_hdr_off.ensure(reads_bound + 1)); HIPCHK(c->fq_qual_off.ensure(reads_bound + 1)); HIPCHK(c->fq_hdr.ensure(text_bytes + 1)); HIPCHK(c->fq_qual.ensure(text_bytes + 1));
+    HIPCHK(c->seq.ensure(text_bytes + 64)); HIPCHK(c->seq_off.ensure(reads_bound + 1)); HIPCHK(c->rlen.ensure(reads_bound + 1));
+    if (n1) HIPCHK(hipMemcpyAsync(c->fq_text.p, in->text1, n1, hipMemcpyHostToDevice, c->stream));
+    if (n2) HIPCHK(hipMemcpyAsync(c->fq_text.p + off2, in->text2, n2, hipMemcpyHostToDevice, c->stream));
+    FqText x;
+    x.t[0] = c->fq_text.p; x.t[1] = c->fq_text.p + off2; x.n[0] = (uint32_t)n1; x.n[1] = (uint32_t)n2;
+    x.line_start[0] = c->fq_lines.p; x.line_start[1] = c->fq_lines.p + line_cap[0] + 1; x.line_cap[0] = (uint32_t)line_cap[0]; x.line_cap[1] = (uint32_t)line_cap[1];
+    x.two = two ? 1 : 0;
+    const uint32_t stride = (uint32_t)(reads_bound + 1);
+    const dim3 text_grid((unsigned)std::max<size_t>(1, tile_stride), two ? 2u : 1u);
+    HIPCHK(hipEventRecord(c->ev_fq[0], c->stream));
+    k_fq_count<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)tile_stride);
+    k_fq_top<<<1, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)tile_stride, (uint32_t)max_reads, c->d_fq_info);
+    k_fq_lines<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)tile_stride, c->d_fq_info);
+    k_fq_len<<<(unsigned)len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->d_fq_info, c->rlen.p, c->fq_name_at.p, c->fq_name_len.p, c->fq_loc.p, stride, c->fq_tile_sum.p, (uint32_t)len_tiles);
+    k_fq_top3<<<1, FQ_THREADS, 0, c->stream>>>(c->fq_tile_sum.p, (uint32_t)len_tiles, c->d_fq_info);
+    if (reads_bound)
+        k_fq_write<<<(unsigned)reads_bound, 64, 0, c->stream>>>(x, c->d_fq_info, in->rc_odd_reads ? 1 : 0, c->rlen.p, c->fq_name_at.p, c->fq_name_len.p, c->fq_loc.p, stride, c->fq_tile_sum.p,
+                                                                 (uint32_t)len_tiles, c->seq_off.p, c->seq.p, c->fq_hdr_off.p, c->fq_hdr.p, c->fq_qual_off.p, c->fq_qual.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_fq[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_fq_info, c->d_fq_info, sizeof(FqInfo), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the one wait: for the sizes block
+    (void)hipEventElapsedTime(&c->fq_ms, c->ev_fq[0], c->ev_fq[1]);
+    const FqInfo &fi = *c->h_fq_info;
+    if (n_reads_out) *n_reads_out = (int)std::min<uint32_t>(fi.n_reads, 0x7FFFFFFFu);
+    switch (fi.status) {
+    case FQ_OK: break;
+    case FQ_E_COUNT:
+        snprintf(c->err, 512, "dg_batch_upload_fastq: text1 holds %u records and text2 %u: they must be equal, or text1 one more", (fi.n_lines[0] + 3) / 4, (fi.n_lines[1] + 3) / 4);
+        return DG_ERR_ARG;
+    case FQ_E_CAPACITY:
+        snprintf(c->err, 512, "dg_batch_upload_fastq: the texts hold %u reads, max_reads is %d", fi.n_reads, in->max_reads);
+        return DG_ERR_CAPACITY;
+    case FQ_E_EMPTY:
+        snprintf(c->err, 512, "dg_batch_upload_fastq: read %u is a record without bases", fi.bad_read);
+        return DG_ERR_ARG;
+    case FQ_E_LONG:
+        snprintf(c->err, 512, "dg_batch_upload_fastq: read %u is longer than DG_MAX_RLEN (%d)", fi.bad_read, DG_MAX_RLEN);
+        return DG_ERR_ARG;
+    default:
+        snprintf(c->err, 512, "dg_batch_upload_fastq: the bases, names or qualities of the batch exceed 32-bit offsets");
+        return DG_ERR_ARG;
+    }
+    c->n_reads = (int)fi.n_reads; c->max_rlen = (int)fi.max_rlen; c->seq_bytes = (size_t)fi.total[0];
+    c->fq_hdr_bytes = (size_t)fi.total[1]; c->fq_qual_bytes = (size_t)fi.total[2]; c->fq_valid = true;
+    return DG_OK;
+}
+
+extern "C" int dg_batch_fastq_device_ms(dg_ctx *c, float *ms)
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    *ms = c->fq_ms;
+    return DG_OK;
+}
+
+extern "C" int dg_batch_download_reads(dg_ctx *c, uint32_t *seq_off, uint16_t *rlen, char *seq, uint32_t *hdr_off, char *hdr, uint32_t *qual_off, char *qual,
+                                       const size_t caps[3], size_t used[3])
+{
+    if (!c || !caps || !used) return DG_ERR_ARG;
+    if (!c->fq_valid) { snprintf(c->err, 512, "dg_batch_download_reads: the context's last upload was not dg_batch_upload_fastq"); return DG_ERR_ARG; }
+    used[0] = c->seq_bytes; used[1] = c->fq_hdr_bytes; used[2] = c->fq_qual_bytes;
+    if (caps[0] < used[0] || caps[1] < used[1] || caps[2] < used[2]) { snprintf(c->err, 512, "dg_batch_download_reads: output capacity too small (need %zu %zu %zu)", used[0], used[1], used[2]); return DG_ERR_CAPACITY; }
+    const size_t n = (size_t)c->n_reads;
+    if (n == 0) { if (hdr_off) hdr_off[0] = 0; if (qual_off) qual_off[0] = 0; return DG_OK; }
+    if (!seq_off || !rlen || !hdr_off || !qual_off || (used[0] && !seq) || (used[1] && !hdr) || (used[2] && !qual)) return DG_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(seq_off, c->seq_off.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(rlen, c->rlen.p, n * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hdr_off, c->fq_hdr_off.p, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(qual_off, c->fq_qual_off.p, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    if (used[0]) HIPCHK(hipMemcpyAsync(seq, c->seq.p, used[0], hipMemcpyDeviceToHost, c->stream));
+    if (used[1]) HIPCHK(hipMemcpyAsync(hdr, c->fq_hdr.p, used[1], hipMemcpyDeviceToHost, c->stream));
+    if (used[2]) HIPCHK(hipMemcpyAsync(qual, c->fq_qual.p, used[2], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
     return DG_OK;
 }
 
@@ -1743,55 +1870,50 @@ static int sam_offsets_ok(dg_ctx *c, const char *what, const uint32_t *off, int 
     return DG_OK;
 }
 
-extern "C" int dg_batch_format_sam(dg_ctx *c, const dg_sam_text *in, uint32_t flags, size_t *n_bytes, uint64_t counters[3], float *device_ms)
+// what both entry points check before they look at names and qualities; *n = the batch's reads
+static int sam_batch_ready(dg_ctx *c, int n_pair_mode, size_t *n_bytes, uint64_t counters[3], float *device_ms)
 {
-    if (!c) return DG_ERR_ARG;
     if (n_bytes) *n_bytes = 0;
     if (counters) counters[0] = counters[1] = counters[2] = 0;
     if (device_ms) *device_ms = 0.f;
     c->sam_valid = false; c->sam_bytes = 0;
-    if (!in) { snprintf(c->err, 512, "dg_batch_format_sam: the input is NULL"); return DG_ERR_ARG; }
     if (!c->batch_done) { snprintf(c->err, 512, "dg_batch_format_sam: the context has no finished batch (upload and run one first)"); return DG_ERR_ARG; }
     const int n = c->n_reads;
-    if (in->n_pair_mode < 0 || (in->n_pair_mode & 1) || in->n_pair_mode > n) { snprintf(c->err, 512, "dg_batch_format_sam: n_pair_mode %d must be even and at most the batch's %d reads", in->n_pair_mode, n); return DG_ERR_ARG; }
-    if (n == 0) { c->sam_valid = true; return DG_OK; }
+    if (n_pair_mode < 0 || (n_pair_mode & 1) || n_pair_mode > n) { snprintf(c->err, 512, "dg_batch_format_sam: n_pair_mode %d must be even and at most the batch's %d reads", n_pair_mode, n); return DG_ERR_ARG; }
+    if (n == 0) return DG_OK;
     if (c->enc_ready) { snprintf(c->err, 512, "dg_batch_format_sam: the batch was uploaded packed, and the pipeline keeps no ASCII copy of a packed batch: upload it as ASCII"); return DG_ERR_ARG; }
     if (!c->full_valid) { snprintf(c->err, 512, "dg_batch_format_sam: the last batch has no full records (it was mapped through dg_map_batch_compact)"); return DG_ERR_ARG; }
     IndexShared *sh = c->shared_ix;
     if (!sh || !sh->chr_names_set) { snprintf(c->err, 512, "dg_batch_format_sam: the chromosome names are missing (dg_set_chr_names)"); return DG_ERR_ARG; }
-    if (!in->hdr_off || (in->qual && !in->qual_off)) { snprintf(c->err, 512, "dg_batch_format_sam: an offset array is NULL"); return DG_ERR_ARG; }
-    if (sam_offsets_ok(c, "hdr_off", in->hdr_off, n) || (in->qual && sam_offsets_ok(c, "qual_off", in->qual_off, n))) return DG_ERR_ARG;
-    const size_t hdr_bytes = (size_t)in->hdr_off[n] - in->hdr_off[0], qual_bytes = in->qual ? (size_t)in->qual_off[n] - in->qual_off[0] : 0;
-    if (hdr_bytes && !in->hdr) { snprintf(c->err, 512, "dg_batch_format_sam: hdr is NULL"); return DG_ERR_ARG; }
-    HIPCHK(hipSetDevice(c->device));
+    return DG_OK;
+}
+
+// The formatter behind its inputs: names and qualities are in HBM (hdr / qual already moved back by their first offset; qual == nullptr: FASTA), whoever put
+// them there -- dg_batch_format_sam's copies of the caller's arrays, enqueued just before, or the FASTQ upload.  Both entry points run these launches.
+static int sam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr, const uint32_t *qual_off, const char *qual, size_t hdr_bytes, size_t qual_bytes,
+                             int n_pair_mode, uint32_t flags, size_t *n_bytes, uint64_t counters[3], float *device_ms)
+{
+    const int n = c->n_reads;
+    IndexShared *sh = c->shared_ix;
     if (!c->d_sam_stat) {
         HIPCHK(hipMalloc((void **)&c->d_sam_stat, 4 * 8));
         HIPCHK(hipHostMalloc((void **)&c->h_sam_stat, 4 * 8, hipHostMallocDefault));
         for (hipEvent_t &e : c->ev_sam) HIPCHK(hipEventCreate(&e));
     }
     const uint32_t n_tiles = (uint32_t)((n + SAM_LEN_THREADS - 1) / SAM_LEN_THREADS);
-    HIPCHK(c->sam_hdr_off.ensure((size_t)n + 1)); HIPCHK(c->sam_hdr.ensure(hdr_bytes + 1)); HIPCHK(c->sam_qlen.ensure((size_t)n));
-    HIPCHK(c->sam_read_off.ensure((size_t)n)); HIPCHK(c->sam_tile.ensure(n_tiles));
-    if (in->qual) { HIPCHK(c->sam_qual_off.ensure((size_t)n + 1)); HIPCHK(c->sam_qual.ensure(qual_bytes + 1)); }
+    HIPCHK(c->sam_qlen.ensure((size_t)n)); HIPCHK(c->sam_read_off.ensure((size_t)n)); HIPCHK(c->sam_tile.ensure(n_tiles));
     // the text's capacity is a guess the first time (one line per read); when it was too small k_sam_write alone runs again -- never the batch
     size_t want = hdr_bytes + qual_bytes + c->seq_bytes + (size_t)n * 96;
     want += want / 8;
     if (c->env_sam_first_cap && !c->sam_text.p) want = c->env_sam_first_cap;
     if (c->sam_text.cap < want) HIPCHK(c->sam_text.ensure(want));
-    // offsets are taken relative to their first entry on the device: the kernels add them to pointers moved back by it
-    HIPCHK(hipMemcpyAsync(c->sam_hdr_off.p, in->hdr_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    if (hdr_bytes) HIPCHK(hipMemcpyAsync(c->sam_hdr.p, in->hdr + in->hdr_off[0], hdr_bytes, hipMemcpyHostToDevice, c->stream));
-    if (in->qual) {
-        HIPCHK(hipMemcpyAsync(c->sam_qual_off.p, in->qual_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        if (qual_bytes) HIPCHK(hipMemcpyAsync(c->sam_qual.p, in->qual + in->qual_off[0], qual_bytes, hipMemcpyHostToDevice, c->stream));
-    }
     SamBatch b;
     b.ro = c->reads_out.p; b.po = c->reports.p; b.cig = c->cigfinal.p;
     b.seq_off = c->seq_off.p; b.rlen = c->rlen.p; b.seq = c->seq.p;
-    b.hdr_off = c->sam_hdr_off.p; b.hdr = c->sam_hdr.p - in->hdr_off[0];
-    b.qual_off = in->qual ? c->sam_qual_off.p : nullptr; b.qual = in->qual ? c->sam_qual.p - in->qual_off[0] : nullptr;
+    b.hdr_off = hdr_off; b.hdr = hdr;
+    b.qual_off = qual ? qual_off : nullptr; b.qual = qual;
     b.chr_off = nullptr; b.chr = nullptr; b.qlen = nullptr;      // (the names: under the index's lock, below)
-    b.n_reads = n; b.n_pair_mode = in->n_pair_mode; b.unique_only = (flags & DG_SAM_UNIQUE_ONLY) ? 1 : 0; b.multi = c->pr.multi_hit ? 1 : 0;
+    b.n_reads = n; b.n_pair_mode = n_pair_mode; b.unique_only = (flags & DG_SAM_UNIQUE_ONLY) ? 1 : 0; b.multi = c->pr.multi_hit ? 1 : 0;
     SamBatch b2 = b; uint64_t names_gen = 0;
     const unsigned grid = (unsigned)n;
     {   // the chromosome names are read and the kernels that use them enqueued under the index's lock: dg_set_chr_names, which replaces the
@@ -1832,6 +1954,49 @@ extern "C" int dg_batch_format_sam(dg_ctx *c, const dg_sam_text *in, uint32_t fl
     if (counters) { counters[0] = c->h_sam_stat[1]; counters[1] = c->h_sam_stat[2]; counters[2] = c->h_sam_stat[3]; }
     if (device_ms) *device_ms = ms;
     return DG_OK;
+}
+
+extern "C" int dg_batch_format_sam(dg_ctx *c, const dg_sam_text *in, uint32_t flags, size_t *n_bytes, uint64_t counters[3], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!in) {
+        if (n_bytes) *n_bytes = 0;
+        if (counters) counters[0] = counters[1] = counters[2] = 0;
+        if (device_ms) *device_ms = 0.f;
+        c->sam_valid = false; c->sam_bytes = 0;
+        snprintf(c->err, 512, "dg_batch_format_sam: the input is NULL"); return DG_ERR_ARG;
+    }
+    const int rc = sam_batch_ready(c, in->n_pair_mode, n_bytes, counters, device_ms);
+    if (rc) return rc;
+    const int n = c->n_reads;
+    if (n == 0) { c->sam_valid = true; return DG_OK; }
+    if (!in->hdr_off || (in->qual && !in->qual_off)) { snprintf(c->err, 512, "dg_batch_format_sam: an offset array is NULL"); return DG_ERR_ARG; }
+    if (sam_offsets_ok(c, "hdr_off", in->hdr_off, n) || (in->qual && sam_offsets_ok(c, "qual_off", in->qual_off, n))) return DG_ERR_ARG;
+    const size_t hdr_bytes = (size_t)in->hdr_off[n] - in->hdr_off[0], qual_bytes = in->qual ? (size_t)in->qual_off[n] - in->qual_off[0] : 0;
+    if (hdr_bytes && !in->hdr) { snprintf(c->err, 512, "dg_batch_format_sam: hdr is NULL"); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->sam_hdr_off.ensure((size_t)n + 1)); HIPCHK(c->sam_hdr.ensure(hdr_bytes + 1));
+    if (in->qual) { HIPCHK(c->sam_qual_off.ensure((size_t)n + 1)); HIPCHK(c->sam_qual.ensure(qual_bytes + 1)); }
+    // offsets are taken relative to their first entry on the device: the kernels add them to pointers moved back by it
+    HIPCHK(hipMemcpyAsync(c->sam_hdr_off.p, in->hdr_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (hdr_bytes) HIPCHK(hipMemcpyAsync(c->sam_hdr.p, in->hdr + in->hdr_off[0], hdr_bytes, hipMemcpyHostToDevice, c->stream));
+    if (in->qual) {
+        HIPCHK(hipMemcpyAsync(c->sam_qual_off.p, in->qual_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (qual_bytes) HIPCHK(hipMemcpyAsync(c->sam_qual.p, in->qual + in->qual_off[0], qual_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    return sam_format_device(c, c->sam_hdr_off.p, c->sam_hdr.p - in->hdr_off[0], in->qual ? c->sam_qual_off.p : nullptr, in->qual ? c->sam_qual.p - in->qual_off[0] : nullptr,
+                             hdr_bytes, qual_bytes, in->n_pair_mode, flags, n_bytes, counters, device_ms);
+}
+
+extern "C" int dg_batch_format_sam_resident(dg_ctx *c, int n_pair_mode, uint32_t flags, size_t *n_bytes, uint64_t counters[3], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const int rc = sam_batch_ready(c, n_pair_mode, n_bytes, counters, device_ms);
+    if (rc) return rc;
+    if (!c->fq_valid) { snprintf(c->err, 512, "dg_batch_format_sam_resident: the context's last upload was not dg_batch_upload_fastq: no names and qualities in HBM"); return DG_ERR_ARG; }
+    if (c->n_reads == 0) { c->sam_valid = true; return DG_OK; }
+    HIPCHK(hipSetDevice(c->device));
+    return sam_format_device(c, c->fq_hdr_off.p, c->fq_hdr.p, c->fq_qual_off.p, c->fq_qual.p, c->fq_hdr_bytes, c->fq_qual_bytes, n_pair_mode, flags, n_bytes, counters, device_ms);
 }
 
 extern "C" int dg_batch_download_sam(dg_ctx *c, char *out, size_t cap)

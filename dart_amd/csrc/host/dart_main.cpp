@@ -404,9 +404,22 @@ static inline void put_cigar(std::string &out, const uint32_t *ops, uint32_t n)
 static std::string fast_format_text(const FastStats &f)
 {
     char b[384];
-    if (g_device_sam) snprintf(b, sizeof b, "format=device %.3f s (sum over workers: gather names and qualities %.3f s, dg_batch_format_sam %.3f s of which kernels %.3f s, text download %.3f s; %zu batches, %.4f s per batch on its worker's path)",
+    if (g_device_sam && f.fq_device) snprintf(b, sizeof b, "format=device %.3f s (sum over workers: names and qualities resident in HBM, dg_batch_format_sam_resident %.3f s of which kernels %.3f s, text download %.3f s; %zu batches, %.4f s per batch on its worker's path)",
+                                              f.t_dev_call + f.t_download, f.t_dev_call, f.t_dev_kernels, f.t_download, f.n_batches, (f.t_dev_call + f.t_download) / (double)std::max<size_t>(1, f.n_batches));
+    else if (g_device_sam) snprintf(b, sizeof b, "format=device %.3f s (sum over workers: gather names and qualities %.3f s, dg_batch_format_sam %.3f s of which kernels %.3f s, text download %.3f s; %zu batches, %.4f s per batch on its worker's path)",
                                f.t_gather + f.t_dev_call + f.t_download, f.t_gather, f.t_dev_call, f.t_dev_kernels, f.t_download, f.n_batches, (f.t_gather + f.t_dev_call + f.t_download) / (double)std::max<size_t>(1, f.n_batches));
     else snprintf(b, sizeof b, "format=host %.3f s", f.t_fmt);
+    return b;
+}
+
+// the assemble field of the same line: without DART_DEVICE_FASTQ it is what it always was; with the switch it names who cut the text into batches
+static std::string fast_assemble_text(const FastStats &f)
+{
+    char b[384];
+    if (!g_device_fastq) snprintf(b, sizeof b, "assemble %.3f s (of which page-locked allocation %.3f s)", f.t_asm, f.t_alloc);
+    else if (f.fq_device) snprintf(b, sizeof b, "assemble=device %.3f s (sum over workers: dg_batch_upload_fastq %.3f s of which kernels %.3f s; batch ranges and views on the host %.3f s, of which page-locked allocation %.3f s)",
+                                   f.t_fq_call, f.t_fq_call, f.t_fq_kernels, f.t_asm, f.t_alloc);
+    else snprintf(b, sizeof b, "assemble=host %.3f s (a record without bases: the host assembles; of which page-locked allocation %.3f s)", f.t_asm, f.t_alloc);
     return b;
 }
 
@@ -658,6 +671,8 @@ int main(int argc, char *argv[])
     // DART_DEVICE_SAM=1: SAM text from the device's formatter (dg_batch_format_sam) instead of the host's; -bo keeps the host's (BAM is built from host text)
     const bool device_sam = !o.bam && getenv("DART_DEVICE_SAM") && atoi(getenv("DART_DEVICE_SAM")) != 0;
     g_device_sam = device_sam;
+    // DART_DEVICE_FASTQ=1: the parallel pipeline hands its batches to the GPU as FASTQ text (dg_batch_upload_fastq); the streaming pipeline and -bo ignore it
+    g_device_fastq = !o.bam && getenv("DART_DEVICE_FASTQ") && atoi(getenv("DART_DEVICE_FASTQ")) != 0;
     if (device_sam) {
         std::vector<uint32_t> noff{0}; std::string nflat;
         for (const std::string &nm : ix.names) { nflat += nm; noff.push_back((uint32_t)nflat.size()); }
@@ -699,7 +714,7 @@ int main(int argc, char *argv[])
                                                  fileno(sam), &off, total, sjmap, t0, ferr, fst, pool, gi);
                 fseeko(sam, (off_t)off, SEEK_SET);
                 if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, assemble %.3f s (of which page-locked allocation %.3f s), map (sum over workers) %.3f s, %s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fst.t_asm, fst.t_alloc, fst.t_map, fast_format_text(fst).c_str(), fst.t_write);
+                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write);
                 gi->m1.close_now(); gi->m2.close_now();
                 continue;
             }
@@ -720,7 +735,7 @@ int main(int argc, char *argv[])
                                              fileno(sam), &off, total, sjmap, t0, ferr, fst, pool, lib == 0 ? &pre : nullptr);
             fseeko(sam, (off_t)off, SEEK_SET);
             if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, assemble %.3f s (of which page-locked allocation %.3f s), map (sum over workers) %.3f s, %s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fst.t_asm, fst.t_alloc, fst.t_map, fast_format_text(fst).c_str(), fst.t_write);
+            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write);
             if (s1.fp) fclose(s1.fp);
             if (s2.fp) fclose(s2.fp);
             continue;

@@ -336,6 +336,10 @@ static inline void rev_copy(char *d, const char *s, size_t l) { if (g_avx2) rev_
 // DART_DEVICE_SAM=1: the SAM text of a batch is formatted on the GPU (dg_batch_format_sam) right behind its mapping, on the same context, and
 // downloaded into the slot; format_views is not run.  Set by the host program before the first library.
 static bool g_device_sam = false;
+// DART_DEVICE_FASTQ=1: a batch goes to the GPU as the bytes of its records, straight from the mapped files (dg_batch_upload_fastq): no arena, no base copy on
+// the host; with DART_DEVICE_SAM=1 as well the text is formatted from the names and qualities that upload left in HBM (dg_batch_format_sam_resident) and
+// nothing is gathered.  The index pass below still decides the batches.  A library with a record without bases keeps the host's assembly.
+static bool g_device_fastq = false;
 
 struct FastSlot {                       // one batch travelling through the stages
     size_t first = 0; int n = 0, odd = 0; size_t seqno = 0;
@@ -344,10 +348,12 @@ struct FastSlot {                       // one batch travelling through the stag
     std::vector<RView> view; std::vector<uint32_t> soff; std::vector<uint16_t> rl;
     char *seq = nullptr; size_t seq_cap = 0, n_cap = 0;            // page-locked
     dg_read_out *ro = nullptr; dg_report_out *po = nullptr; uint32_t *cig = nullptr; dg_sj_out *sj = nullptr; size_t caps[3] = {0, 0, 0}, used[3] = {0, 0, 0};
+    const char *fq1 = nullptr, *fq2 = nullptr; size_t fq_n1 = 0, fq_n2 = 0; bool fq_device = false;      // device parser: the batch's byte range of each mapped file
     int rc = 0; std::string err;
 };
 
-struct FastStats { double t_index = 0, t_asm = 0, t_map = 0, t_fmt = 0, t_write = 0, t_alloc = 0, t_gather = 0, t_dev_call = 0, t_dev_kernels = 0, t_download = 0; size_t n_batches = 0; };
+struct FastStats { double t_index = 0, t_asm = 0, t_map = 0, t_fmt = 0, t_write = 0, t_alloc = 0, t_gather = 0, t_dev_call = 0, t_dev_kernels = 0, t_download = 0; size_t n_batches = 0;
+                   bool fq_device = false; double t_fq_call = 0, t_fq_kernels = 0; };      // the library's batches were parsed on the device: dg_batch_upload_fastq, sum over workers / its kernels
 
 // Batch arenas: ordinary memory by default -- page-locking costs ~1 s per GB, more than a short job saves; DART_PINNED=1 page-locks them
 // (then the copies to and from the GPU are plain DMA transfers: worth it for long runs with several contexts in flight)
@@ -508,6 +514,13 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
         mf = &m1; return r1[k];
     };
     if (batch_reads & 1) batch_reads++;
+    const bool fq_device = g_device_fastq && !explicit_order;      // (an entry without bases ends a chunk: the replayed order is not a byte range)
+    st.fq_device = fq_device;
+    // the bytes of records [a, b) of a mapped file
+    auto byte_range = [](const MappedFile &mf, const std::vector<FqRec> &v, size_t a, size_t b, const char *&p, size_t &n) {
+        const size_t lo = a < v.size() ? (size_t)v[a].off : mf.n, hi = b < v.size() ? (size_t)v[b].off : mf.n;
+        p = mf.p + lo; n = hi - lo;
+    };
     // slots + queues
     pool.wait();
     if (pool.slots.size() < ctx.size() + 2) pool.slots.resize(ctx.size() + 2);
@@ -530,7 +543,40 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             if (next < odd_from && end > odd_from) end = odd_from;
             if (next >= odd_from) { end = n_total; odd = (int)(end - next); }
             const int n = (int)(end - next);
-            s->first = next; s->n = n; s->odd = odd; s->seqno = seqno++; s->rc = 0;
+            s->first = next; s->n = n; s->odd = odd; s->seqno = seqno++; s->rc = 0; s->fq_device = fq_device;
+            if (fq_device) {
+                // the batch is a byte range of each file (next is even: batches and the start of an unpaired tail are); the host keeps views for its
+                // formatter only -- names, bases and qualities where they lie in the mapping, nothing copied
+                s->fq2 = nullptr; s->fq_n2 = 0;
+                if (f2) { byte_range(m1, r1, next / 2, (end + 1) / 2, s->fq1, s->fq_n1); byte_range(m2, r2, next / 2, end / 2, s->fq2, s->fq_n2); }
+                else byte_range(m1, r1, next, end, s->fq1, s->fq_n1);
+                if (s->fq_n1 >= 0xFFFFFF00ull || s->fq_n2 >= 0xFFFFFF00ull) { s->rc = DG_ERR_ARG; s->err = "a batch's FASTQ text exceeds 32-bit offsets: lower DART_BATCH"; }
+                else {
+                    { const double tl = now(); const size_t z[3] = {0, 0, 0}; slot_reserve(*s, (size_t)n, 0, z); st.t_alloc += now() - tl; }
+                    if (!g_device_sam) {
+                        s->view.resize(n);
+                        const int TA = std::max(1, T / 8);
+                        parallel_for(TA, [&](int tid) {
+                            const int lo = (int)((long long)n * tid / TA), hi = (int)((long long)n * (tid + 1) / TA);
+                            for (int k = lo; k < hi; k++) {
+                                const MappedFile *mf; const FqRec &r = rec_of(next + k, mf);
+                                const char *l0 = mf->p + r.off, *l1 = l0 + r.l0, *l3 = l1 + r.l1 + r.l2;
+                                const int p1 = hdr_beg_f(l0, (int)r.l0), p2 = hdr_end_f(l0, (int)r.l0);
+                                RView &v = s->view[k];
+                                v.h = l0 + p1; v.hl = p2 > p1 ? (uint32_t)(p2 - p1) : 0u;
+                                v.s = l1; v.sl = r.l1 - 1;
+                                v.q = l3; v.ql = std::min<uint32_t>(v.sl, r.l3);
+                                v.rc = pair_end && ((next + k) & 1);
+                            }
+                        });
+                    }
+                }
+                st.t_asm += now() - ta;
+                next = end;
+                { std::lock_guard<std::mutex> lk(mu); map_q.push_back(s); }
+                cv.notify_all();
+                continue;
+            }
             s->view.resize(n); s->soff.resize((size_t)n + 1); s->rl.resize(n);
             size_t bases = 0;
             bool too_long = false;
@@ -578,6 +624,30 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             FastSlot *s;
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !map_q.empty() || asm_done || failed; }); if (failed || map_q.empty()) break; s = map_q.front(); map_q.pop_front(); }
             const double tm = now();
+            double t_fq = 0; float fq_ms = 0.f;
+            if (!s->rc && s->fq_device) {
+                // upload the text (the device cuts it into the batch) -> run -> download
+                const int n = s->n;
+                dg_params p = base_params; p.paired = (pair_end && !s->odd) ? 1 : 0;
+                dg_set_params(ctx[w], &p);
+                dg_fastq_text ft; ft.text1 = s->fq1; ft.n1 = s->fq_n1; ft.text2 = s->fq2; ft.n2 = s->fq_n2; ft.rc_odd_reads = pair_end ? 1 : 0; ft.max_reads = n;
+                int got = 0;
+                const double tu = now();
+                int rc = dg_batch_upload_fastq(ctx[w], &ft, &got);
+                t_fq = now() - tu;
+                (void)dg_batch_fastq_device_ms(ctx[w], &fq_ms);
+                if (!rc && got != n) { s->rc = DG_ERR_INTERNAL; s->err = "the device parser found " + std::to_string(got) + " reads in a batch of " + std::to_string(n); }
+                else if (rc) { s->rc = rc; s->err = dg_last_error(ctx[w]); }
+                else {
+                    rc = dg_batch_run(ctx[w], s->used);
+                    if (!rc && (s->used[0] > s->caps[0] || s->used[1] > s->caps[1] || s->used[2] > s->caps[2])) {
+                        const size_t need[3] = { s->used[0] + s->used[0] / 8 + 1024, s->used[1] + s->used[1] / 8 + 1024, s->used[2] + s->used[2] / 8 + 1024 };
+                        slot_reserve(*s, (size_t)n, 0, need);
+                    }
+                    if (!rc) rc = dg_batch_download(ctx[w], s->ro, s->po, s->cig, s->sj, s->caps);
+                    s->rc = rc; if (rc) s->err = dg_last_error(ctx[w]);
+                }
+            } else
             if (!s->rc) {
                 const int n = s->n;
                 for (int attempt = 0; attempt < 2; attempt++) {
@@ -591,6 +661,21 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 }
             }
             double t_gather = 0, t_call = 0, t_dl = 0; float dev_ms = 0.f;
+            if (!s->rc && g_device_sam && s->fq_device) {
+                // names and qualities are in HBM already, in stored order: nothing to gather
+                size_t nb = 0;
+                const double tc = now();
+                int rc = dg_batch_format_sam_resident(ctx[w], (pair_end && !s->odd) ? s->n : 0, unique_only ? DG_SAM_UNIQUE_ONLY : 0u, &nb, s->dev_ct, &dev_ms);
+                t_call = now() - tc;
+                if (!rc) {
+                    const double td = now();
+                    if (nb > s->text_cap) { arena_free(s->text); s->text_cap = nb + nb / 8 + 4096; s->text = (char *)arena_alloc(s->text_cap); }
+                    rc = dg_batch_download_sam(ctx[w], s->text, s->text_cap);
+                    s->text_n = nb;
+                    t_dl = now() - td;
+                }
+                if (rc) { s->rc = rc; s->err = dg_last_error(ctx[w]); }
+            } else
             if (!s->rc && g_device_sam) {
                 // the batch's names and qualities, flat, mate 2's qualities in stored order (reversed); then the text from the device
                 const double tg = now();
@@ -628,7 +713,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                     if (rc) { s->rc = rc; s->err = dg_last_error(ctx[w]); }
                 }
             }
-            { std::lock_guard<std::mutex> lk(mu); st.t_map += now() - tm - t_gather - t_call - t_dl; st.t_gather += t_gather; st.t_dev_call += t_call; st.t_dev_kernels += dev_ms * 1e-3; st.t_download += t_dl; st.n_batches++; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
+            { std::lock_guard<std::mutex> lk(mu); st.t_map += now() - tm - t_gather - t_call - t_dl - t_fq; st.t_fq_call += t_fq; st.t_fq_kernels += fq_ms * 1e-3; st.t_gather += t_gather; st.t_dev_call += t_call; st.t_dev_kernels += dev_ms * 1e-3; st.t_download += t_dl; st.n_batches++; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
             cv.notify_all();
         }
         { std::lock_guard<std::mutex> lk(mu); mappers_left--; }

@@ -95,6 +95,10 @@ class SamText(C.Structure):
 SAM_UNIQUE_ONLY = 1
 
 
+class FastqText(C.Structure):
+    _fields_ = [("text1", C.c_void_p), ("n1", C.c_size_t), ("text2", C.c_void_p), ("n2", C.c_size_t), ("rc_odd_reads", C.c_int32), ("max_reads", C.c_int32)]
+
+
 def flatten_strings(items):
     """list of bytes / str -> (u32 offsets [n + 1], u8 array): the form dg_set_chr_names and dg_batch_format_sam take names and qualities in"""
     bs = [x if isinstance(x, (bytes, bytearray)) else x.encode("latin1") for x in items]
@@ -236,6 +240,12 @@ def _load_lib():
         lib.dg_batch_format_sam.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
         lib.dg_batch_download_sam.argtypes = [vp, vp, C.c_size_t]
         lib.dg_batch_device_sam.argtypes = [vp, vp, vp]
+    if hasattr(lib, "dg_batch_upload_fastq"):
+        lib.dg_batch_upload_fastq.argtypes = [vp, vp, vp]
+        lib.dg_batch_format_sam_resident.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, vp]
+        lib.dg_batch_download_reads.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        lib.dg_batch_fastq_device_ms.argtypes = [vp, vp]
+        lib.dg_fastq_tile.restype = C.c_int
     lib.dg_last_counters.argtypes = [vp, vp, C.c_int]
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
@@ -342,6 +352,59 @@ class DartGPU:
             t.qual_off, t.qual = qo.ctypes.data, qb.ctypes.data
         nb = C.c_size_t(0); ct = (C.c_uint64 * 3)(); ms = C.c_float(0)
         self._chk(self.lib.dg_batch_format_sam(self.ctx, C.byref(t), SAM_UNIQUE_ONLY if unique_only else 0, C.byref(nb), ct, C.byref(ms)), "dg_batch_format_sam")
+        self.sam_device_ms = float(ms.value)
+        out = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_batch_download_sam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_sam")
+        return out[:int(nb.value)].tobytes(), dict(unmapped=int(ct[0]), unique=int(ct[1]), paired=int(ct[2]))
+
+    def fastq_tile(self) -> int:
+        """bytes of FASTQ text one workgroup of the device parser's line kernels takes (dg_fastq_tile)"""
+        return int(self.lib.dg_fastq_tile())
+
+    def upload_fastq(self, text1, text2=None, rc_odd_reads: bool = False, max_reads: int | None = None) -> int:
+        """FASTQ bytes -> the batch in HBM (dg_batch_upload_fastq); two texts: reads alternate between them.  Returns the number of reads.
+        max_reads None: as many as the texts can hold.  self.fastq_device_ms holds the six kernels' device time."""
+        if not hasattr(self.lib, "dg_batch_upload_fastq"):
+            raise RuntimeError("this build of libdartgpu.so has no dg_batch_upload_fastq")
+        a = np.frombuffer(bytes(text1) + b"\0", np.uint8)
+        b = np.frombuffer(bytes(text2) + b"\0", np.uint8) if text2 is not None else None
+        t = FastqText()
+        t.text1, t.n1 = a.ctypes.data, len(a) - 1
+        if b is not None:
+            t.text2, t.n2 = b.ctypes.data, len(b) - 1
+        t.rc_odd_reads = int(bool(rc_odd_reads))
+        t.max_reads = int(max_reads) if max_reads is not None else min(0x7FFFFFFF, (len(a) + 3) // 4 + ((len(b) + 3) // 4 if b is not None else 0))
+        n = C.c_int(0)
+        rc = self.lib.dg_batch_upload_fastq(self.ctx, C.byref(t), C.byref(n))
+        self.fastq_need = int(n.value)               # (with DG_ERR_CAPACITY: the reads the texts hold)
+        self._chk(rc, "dg_batch_upload_fastq")
+        self._n = int(n.value)
+        ms = C.c_float(0)
+        self.lib.dg_batch_fastq_device_ms(self.ctx, C.byref(ms))
+        self.fastq_device_ms = float(ms.value)
+        return self._n
+
+    def download_reads(self):
+        """the batch a FASTQ upload parsed (dg_batch_download_reads) -> (seq_off u32 [n], rlen u16 [n], flat u8, names [n] bytes, stored qualities [n] bytes)"""
+        caps = (C.c_size_t * 3)(0, 0, 0); used = (C.c_size_t * 3)()
+        n = self._n
+        so = np.zeros(max(n, 1), np.uint32); rl = np.zeros(max(n, 1), np.uint16); ho = np.zeros(n + 1, np.uint32); qo = np.zeros(n + 1, np.uint32)
+        rc = self.lib.dg_batch_download_reads(self.ctx, so.ctypes.data, rl.ctypes.data, None, ho.ctypes.data, None, qo.ctypes.data, None, caps, used)
+        if rc not in (0, -4):
+            self._chk(rc, "dg_batch_download_reads")
+        flat = np.zeros(max(int(used[0]), 1), np.uint8); hb = np.zeros(max(int(used[1]), 1), np.uint8); qb = np.zeros(max(int(used[2]), 1), np.uint8)
+        caps = (C.c_size_t * 3)(int(used[0]), int(used[1]), int(used[2]))
+        self._chk(self.lib.dg_batch_download_reads(self.ctx, so.ctypes.data, rl.ctypes.data, flat.ctypes.data, ho.ctypes.data, hb.ctypes.data, qo.ctypes.data, qb.ctypes.data, caps, used),
+                  "dg_batch_download_reads")
+        hraw, qraw = hb.tobytes(), qb.tobytes()
+        names = [hraw[int(ho[k]):int(ho[k + 1])] for k in range(n)]
+        quals = [qraw[int(qo[k]):int(qo[k + 1])] for k in range(n)]
+        return so[:n], rl[:n], flat[:int(used[0])], names, quals
+
+    def format_sam_resident(self, n_pair_mode: int, unique_only: bool = False):
+        """format_sam with the names and qualities a FASTQ upload left in HBM (dg_batch_format_sam_resident) -> (bytes, counters)"""
+        nb = C.c_size_t(0); ct = (C.c_uint64 * 3)(); ms = C.c_float(0)
+        self._chk(self.lib.dg_batch_format_sam_resident(self.ctx, int(n_pair_mode), SAM_UNIQUE_ONLY if unique_only else 0, C.byref(nb), ct, C.byref(ms)), "dg_batch_format_sam_resident")
         self.sam_device_ms = float(ms.value)
         out = np.zeros(max(int(nb.value), 1), np.uint8)
         self._chk(self.lib.dg_batch_download_sam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_sam")

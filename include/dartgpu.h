@@ -222,6 +222,43 @@ int dg_batch_format_sam(dg_ctx *, const dg_sam_text *in, uint32_t flags, size_t 
 int dg_batch_download_sam(dg_ctx *, char *out, size_t cap);
 int dg_batch_device_sam(dg_ctx *, void **ptr, size_t *n_bytes);
 
+/* ---- FASTQ text on the device: the bytes of the read files -> the batch in HBM (replaces GetNextEntry / GetNextChunk, GetData.cpp:77-179) ----
+ * A record is four lines (a line ends with its '\n' or with the text); nothing about '@' or '+' is assumed.  Of a record:
+ *   name      IdentifyHeaderBegPos / IdentifyHeaderEndPos (GetData.cpp:55-75) over line 0: behind the leading '@' / '>' characters, up to the first
+ *             blank, '/' or tab; empty when the end does not lie behind the begin
+ *   read      line 1 without its last byte (GetData.cpp:95-101); a record whose read is empty or missing has no bases: DG_ERR_ARG, the text names it
+ *   quality   the first min(read length, length of line 3) bytes of line 3 (GetData.cpp:100-101)
+ *   odd reads with rc_odd_reads: kept reverse-complemented through comp_base (everything but ACGTacgt becomes N), the quality reversed
+ *             (GetData.cpp:157-166) -- the form dg_params::paired and dg_sam_text expect
+ * All other bytes pass through as they are ('\r', lower case, IUPAC codes, '-', NUL).
+ *   dg_batch_upload_fastq          texts are any readable host memory (a file mapping works; page-locked memory makes the copy a DMA transfer), each smaller
+ *                                  than 2^32 - 256 bytes.  Two texts (GetNextChunk's bSepLibrary, GetData.cpp:141,152): equal record counts, or text1 holds
+ *                                  one more, else DG_ERR_ARG.  The copies and six kernels are enqueued on the context's stream; the call waits once, for the
+ *                                  sizes.  It leaves the context as dg_batch_upload does (dg_batch_run, the downloads, dg_batch_device_* work unchanged)
+ *                                  and the names and stored qualities in HBM beside the bases.  More records than max_reads: DG_ERR_CAPACITY, *n_reads =
+ *                                  the need.  A read longer than DG_MAX_RLEN: DG_ERR_ARG.  An error leaves the context usable, without a batch.
+ *                                  No text at all: zero reads, DG_OK.
+ *   dg_batch_format_sam_resident   dg_batch_format_sam with the names and qualities the FASTQ upload left in HBM (the same launches); DG_ERR_ARG when the
+ *                                  context's last upload was not dg_batch_upload_fastq.  dg_batch_format_sam with host arrays still works on such a
+ *                                  batch and leaves the resident arrays alone.
+ *   dg_batch_download_reads        the parsed batch (GetNextChunk's ReadArr, GetData.cpp:134-179): seq_off / rlen [n_reads], hdr_off / qual_off
+ *                                  [n_reads + 1]; caps / used index: 0 = bases, 1 = name bytes, 2 = quality bytes; DG_ERR_CAPACITY: `used` holds the need
+ *   dg_batch_fastq_device_ms       device time of the last upload's six kernels (GetData.cpp:77-179 has no counterpart: a measurement)
+ *   dg_fastq_tile                  DG_FASTQ_TILE, the bytes of text one workgroup of the line kernels takes (tests place line ends on its seams)       */
+#define DG_FASTQ_TILE 16384
+typedef struct {
+    const char *text1; size_t n1;   /* whole records of file 1 (or of the only file) */
+    const char *text2; size_t n2;   /* NULL/0: one file. Else read 2i = record i of text1, 2i+1 = record i of text2 (GetNextChunk's order, GetData.cpp:141,152) */
+    int32_t rc_odd_reads;           /* odd reads are stored reverse-complemented, qualities reversed (GetData.cpp:157-166) */
+    int32_t max_reads;              /* capacity; more records -> DG_ERR_CAPACITY, *n_reads = the need */
+} dg_fastq_text;
+int dg_batch_upload_fastq(dg_ctx *, const dg_fastq_text *, int *n_reads);
+int dg_batch_format_sam_resident(dg_ctx *, int n_pair_mode, uint32_t flags, size_t *n_bytes, uint64_t counters[3], float *device_ms);
+int dg_batch_download_reads(dg_ctx *, uint32_t *seq_off, uint16_t *rlen, char *seq, uint32_t *hdr_off, char *hdr, uint32_t *qual_off, char *qual,
+                            const size_t caps[3] /* bases, name bytes, quality bytes */, size_t used[3]);
+int dg_batch_fastq_device_ms(dg_ctx *, float *ms);
+int dg_fastq_tile(void);
+
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
 int dg_last_timings(dg_ctx *, const char **names, float *ms, int cap);
