@@ -326,3 +326,32 @@ def test_bench_plain_run_dumps_the_last_steps_records(workdir):
     assert np.array_equal(a["cigar"][:len(ops)], ops.astype(np.float64))
     j0 = a["junctions"][:, 0] == 0
     assert np.array_equal(a["junctions"][j0][:, 1:], np.column_stack([sj[f] for f in ("g1", "g2", "type", "read_idx")]).astype(np.float64))
+
+
+@pytest.mark.parametrize("switches", [{}, {"DART_DEVICE_FASTQ": "1", "DART_DEVICE_SAM": "1"}], ids=["host text", "device fastq+sam"])
+@pytest.mark.parametrize("name", ["c5", "g5386"])
+def test_dart_index_then_map_on_a_small_genome(name, switches, workdir):
+    """what a first-time user does with a phage or a plasmid set: `dart index small.fa prefix`, then `dart -i prefix -f a.fq` (and -f2) on a genome of five
+    contigs of 33 to 1000 bases and on one of 5386 bases (tests/small_genome_inputs.py).  The five index files are the reference indexer's bytes, the
+    SAM and the junctions the oracle command line's and the ones the reference wrote (tests/golden/small_genomes.json)."""
+    import hashlib, json
+    import small_genome_inputs as sgi
+    oracle_py.build()
+    gold = json.load(open(os.path.join(common.GOLDEN, "small_genomes.json")))
+    d = os.path.join(workdir, "cli_small_%s_%d" % (name, len(switches)))
+    se, pe = sgi.write_inputs(name, d)
+    r = subprocess.run([DART, "index", "g.fa", "g"], cwd=d, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr + r.stdout
+    for ext, want in gold["genomes"][name]["index_sha256"].items():
+        assert common.sha(os.path.join(d, "g." + ext)) == want, (name, ext)
+    env = dict(os.environ, **switches)
+    for key, paired, flags in sgi.runs(name):
+        flags = (pe if paired else se) + flags
+        rg = subprocess.run([DART, "-i", "g"] + flags + ["-o", "gpu.sam", "-j", "gpu.j", "-t", "3"], cwd=d, stdout=subprocess.PIPE, check=True, env=env)
+        ro = subprocess.run([oracle_py.ORACLE_CLI, "-i", "g"] + flags + ["-o", "orc.sam", "-j", "orc.j"], cwd=d, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True)
+        a, b = open(os.path.join(d, "orc.sam")).read(), open(os.path.join(d, "gpu.sam")).read()
+        assert a == b, (key, common.first_diff(b, a))
+        junc = open(os.path.join(d, "gpu.j")).read()
+        assert open(os.path.join(d, "orc.j")).read() == junc, key
+        assert common.stats_block(rg.stdout) == common.stats_block(ro.stdout) == gold["runs"][key]["stats"] != "", (key, rg.stdout[-600:])
+        assert hashlib.sha256(b.encode()).hexdigest() == gold["runs"][key]["sam_sha256"] and hashlib.sha256(junc.encode()).hexdigest() == gold["runs"][key]["junctions_sha256"], key
