@@ -10,6 +10,8 @@
 #include "dg_reseed.h"
 #include "dg_sort.h"
 #include "dg_samfmt.h"
+#include "dg_bamfmt.h"
+#include "dg_bgzf.h"
 #include "dg_fastq.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -159,6 +161,14 @@ struct dg_ctx {
     FqInfo *d_fq_info = nullptr, *h_fq_info = nullptr;                     // the sizes block: device / page-locked copy
     hipEvent_t ev_fq[2] = {nullptr, nullptr};
     bool fq_valid = false; size_t fq_hdr_bytes = 0, fq_qual_bytes = 0; float fq_ms = 0.f;      // the batch on the context came from dg_batch_upload_fastq
+    // BAM of the batch that ran last (dg_batch_format_bam, dg_bamfmt.h / dg_bgzf.h): the uncompressed records, the blocks' slots, sizes and places, the
+    // contiguous stream; bgzf_in holds the bytes of a dg_bgzf_compress.  The records' inputs and scan state are the SAM formatter's buffers (sam_hdr*, sam_qual*,
+    // sam_qlen, sam_read_off, sam_tile: inputs and scratch of one call); the SAM text itself (sam_text) is left alone.
+    DBuf<unsigned char> bam_rec, bgzf_in, bgzf_slots, bgzf_out; DBuf<uint32_t> bgzf_size; DBuf<uint64_t> bgzf_off;
+    unsigned long long *d_bam_stat = nullptr, *h_bam_stat = nullptr;      // [0] raw bytes, [1..3] the SAM counters, [4] records, [5] refused, [6] stream bytes: device / page-locked copy
+    hipEvent_t ev_bam[2] = {nullptr, nullptr}; float bam_ms[2] = {0.f, 0.f};      // (both phases use the pair, one after the other) / device time of the record kernels, of the BGZF kernels
+    bool bam_valid = false; size_t bam_bytes = 0; unsigned char *bam_ptr = nullptr;
+    size_t env_bam_first_cap = 0;      // DG_BAM_FIRST_CAP: test hook, the first size of the record buffer in bytes
     size_t env_sam_first_cap = 0;      // DG_SAM_TEXT_FIRST_CAP: test hook, the first size of the text buffer in bytes (forces the "text outgrew the guess" path)
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
@@ -185,6 +195,7 @@ static void read_env(dg_ctx *c)
     c->env_rs_chunk = geti("DG_RS_CHUNK", RS_CHUNK_DIAGS); c->env_rs_chunk = std::min(1 << 24, std::max(RS_SUPER, c->env_rs_chunk / RS_SUPER * RS_SUPER));      // (a multiple of the pac super-chunk)
     c->env_rs_inline = std::min(RS_ENT_INLINE, std::max(0, geti("DG_RS_ENT_MAX", RS_ENT_INLINE))); c->env_rs_pool = std::max(0, geti("DG_RS_POOL_BLOCKS", 0));
     c->env_sam_first_cap = (size_t)std::max(0, geti("DG_SAM_TEXT_FIRST_CAP", 0));
+    c->env_bam_first_cap = (size_t)std::max(0, geti("DG_BAM_FIRST_CAP", 0));
     c->env_seed_multi = geti("DG_SEED_MULTI", 4); if (c->env_seed_multi < 0 || c->env_seed_multi > SQF_MULTI_MAX) c->env_seed_multi = SQF_MULTI_MAX;   // rows of an interval that are located and compared with the text at once (0: single rows only)
 }
 
@@ -609,6 +620,10 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->d_sam_stat) (void)hipFree(c->d_sam_stat);
     if (c->h_sam_stat) (void)hipHostFree(c->h_sam_stat);
     for (hipEvent_t e : c->ev_sam) if (e) (void)hipEventDestroy(e);
+    c->bam_rec.release(); c->bgzf_in.release(); c->bgzf_slots.release(); c->bgzf_out.release(); c->bgzf_size.release(); c->bgzf_off.release();
+    if (c->d_bam_stat) (void)hipFree(c->d_bam_stat);
+    if (c->h_bam_stat) (void)hipHostFree(c->h_bam_stat);
+    for (hipEvent_t e : c->ev_bam) if (e) (void)hipEventDestroy(e);
     c->fq_text.release(); c->fq_lines.release(); c->fq_tile_cnt.release(); c->fq_name_at.release(); c->fq_name_len.release(); c->fq_loc.release(); c->fq_hdr_off.release(); c->fq_qual_off.release();
     c->fq_tile_sum.release(); c->fq_hdr.release(); c->fq_qual.release();
     if (c->d_fq_info) (void)hipFree(c->d_fq_info);
@@ -1026,7 +1041,7 @@ static int enqueue_upload(dg_ctx *c, int n_reads, const uint32_t *seq_off, const
         mx = rlen[i] > mx ? rlen[i] : mx;
     }
     if (mx > DG_MAX_RLEN) { snprintf(c->err, 512, "a read is longer than DG_MAX_RLEN (%d)", DG_MAX_RLEN); return DG_ERR_ARG; }
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->fq_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64));     /* the kernels read up to 24 bytes at a read position in one go */
     HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     if (n_reads) {
@@ -1088,7 +1103,7 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
     if (mx > DG_MAX_RLEN || mx > 16 * W2 || (size_t)n_reads * 16 * W2 > 0xFFFFFFF0ull) { snprintf(c->err, 512, "packed batch: read length %d does not fit %d words (or exceeds DG_MAX_RLEN / 2^32 bases)", mx, W2); return DG_ERR_ARG; }
     if (n_reads && (mx + 15) / 16 != W2) { snprintf(c->err, 512, "packed batch: words_per_read must be ceil(longest read / 16) = %d", (mx + 15) / 16); return DG_ERR_ARG; }
     const size_t nw = (size_t)n_reads * W2, bytes = nw * 16;
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->fq_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64)); HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     HIPCHK(c->enc.ensure(2 * nw + 16)); HIPCHK(c->packed_in.ensure(nw + 1)); HIPCHK(c->nlist_in.ensure(n_n + 1));
     c->enc_ready = true;
@@ -1123,7 +1138,7 @@ extern "C" int dg_batch_upload_fastq(dg_ctx *c, const dg_fastq_text *in, int *n_
     if (!c) return DG_ERR_ARG;
     if (n_reads_out) *n_reads_out = 0;
     // whatever happens below, the context holds no batch until this call has succeeded
-    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->fq_valid = false;
+    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
     c->fq_hdr_bytes = c->fq_qual_bytes = 0; c->fq_ms = 0.f;
     if (!in) { snprintf(c->err, 512, "dg_batch_upload_fastq: the input is NULL"); return DG_ERR_ARG; }
     const size_t n1 = in->text1 ? in->n1 : 0, n2 = in->text2 ? in->n2 : 0;
@@ -1649,7 +1664,7 @@ extern "C" int dg_batch_run(dg_ctx *c, size_t used[3])
     memset(c->counters, 0, sizeof c->counters);
     if (used) used[0] = used[1] = used[2] = 0;
     c->n_t = 0;
-    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sam_valid = false;
+    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sam_valid = false; c->bam_valid = false;
     if (c->n_reads == 0) { c->batch_done = true; return DG_OK; }
     c->attempt_no = 0;
     int rc = enqueue_run(c);
@@ -1864,27 +1879,27 @@ extern "C" int dg_set_chr_names(dg_ctx *c, int n_chr, const uint32_t *name_off, 
     return DG_OK;
 }
 
-static int sam_offsets_ok(dg_ctx *c, const char *what, const uint32_t *off, int n)
+static int sam_offsets_ok(dg_ctx *c, const char *what, const uint32_t *off, int n, const char *fn = "dg_batch_format_sam")
 {
-    for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { snprintf(c->err, 512, "dg_batch_format_sam: %s decreases at read %d", what, i); return DG_ERR_ARG; }
+    for (int i = 0; i < n; i++) if (off[i + 1] < off[i]) { snprintf(c->err, 512, "%s: %s decreases at read %d", fn, what, i); return DG_ERR_ARG; }
     return DG_OK;
 }
 
-// what both entry points check before they look at names and qualities; *n = the batch's reads
-static int sam_batch_ready(dg_ctx *c, int n_pair_mode, size_t *n_bytes, uint64_t counters[3], float *device_ms)
+// what the entry points of both formatters check before they look at names and qualities (fn: the caller's name for the text; bam: the result that is reset)
+static int sam_batch_ready(dg_ctx *c, int n_pair_mode, size_t *n_bytes, uint64_t counters[3], float *device_ms, const char *fn = "dg_batch_format_sam", bool bam = false)
 {
     if (n_bytes) *n_bytes = 0;
     if (counters) counters[0] = counters[1] = counters[2] = 0;
     if (device_ms) *device_ms = 0.f;
-    c->sam_valid = false; c->sam_bytes = 0;
-    if (!c->batch_done) { snprintf(c->err, 512, "dg_batch_format_sam: the context has no finished batch (upload and run one first)"); return DG_ERR_ARG; }
+    if (bam) { c->bam_valid = false; c->bam_bytes = 0; } else { c->sam_valid = false; c->sam_bytes = 0; }
+    if (!c->batch_done) { snprintf(c->err, 512, "%s: the context has no finished batch (upload and run one first)", fn); return DG_ERR_ARG; }
     const int n = c->n_reads;
-    if (n_pair_mode < 0 || (n_pair_mode & 1) || n_pair_mode > n) { snprintf(c->err, 512, "dg_batch_format_sam: n_pair_mode %d must be even and at most the batch's %d reads", n_pair_mode, n); return DG_ERR_ARG; }
+    if (n_pair_mode < 0 || (n_pair_mode & 1) || n_pair_mode > n) { snprintf(c->err, 512, "%s: n_pair_mode %d must be even and at most the batch's %d reads", fn, n_pair_mode, n); return DG_ERR_ARG; }
     if (n == 0) return DG_OK;
-    if (c->enc_ready) { snprintf(c->err, 512, "dg_batch_format_sam: the batch was uploaded packed, and the pipeline keeps no ASCII copy of a packed batch: upload it as ASCII"); return DG_ERR_ARG; }
-    if (!c->full_valid) { snprintf(c->err, 512, "dg_batch_format_sam: the last batch has no full records (it was mapped through dg_map_batch_compact)"); return DG_ERR_ARG; }
+    if (c->enc_ready) { snprintf(c->err, 512, "%s: the batch was uploaded packed, and the pipeline keeps no ASCII copy of a packed batch: upload it as ASCII", fn); return DG_ERR_ARG; }
+    if (!c->full_valid) { snprintf(c->err, 512, "%s: the last batch has no full records (it was mapped through dg_map_batch_compact)", fn); return DG_ERR_ARG; }
     IndexShared *sh = c->shared_ix;
-    if (!sh || !sh->chr_names_set) { snprintf(c->err, 512, "dg_batch_format_sam: the chromosome names are missing (dg_set_chr_names)"); return DG_ERR_ARG; }
+    if (!sh || !sh->chr_names_set) { snprintf(c->err, 512, "%s: the chromosome names are missing (dg_set_chr_names)", fn); return DG_ERR_ARG; }
     return DG_OK;
 }
 
@@ -2017,6 +2032,214 @@ extern "C" int dg_batch_device_sam(dg_ctx *c, void **ptr, size_t *n_bytes)
     if (!c || !ptr || !n_bytes) return DG_ERR_ARG;
     if (!c->sam_valid) { snprintf(c->err, 512, "dg_batch_device_sam: no SAM text (dg_batch_format_sam first)"); return DG_ERR_ARG; }
     *ptr = c->sam_bytes ? c->sam_text.p : nullptr; *n_bytes = c->sam_bytes;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// BAM on the device (dg_bamfmt.h, dg_bgzf.h): the records of the batch that ran last -> uncompressed BAM records -> BGZF blocks
+// ------------------------------------------------------------------------------------------
+static int bam_state(dg_ctx *c)
+{
+    if (c->d_bam_stat) return DG_OK;
+    HIPCHK(hipMalloc((void **)&c->d_bam_stat, 8 * 8));
+    HIPCHK(hipHostMalloc((void **)&c->h_bam_stat, 8 * 8, hipHostMallocDefault));
+    for (hipEvent_t &e : c->ev_bam) HIPCHK(hipEventCreate(&e));
+    return DG_OK;
+}
+
+// n bytes in HBM (4-byte aligned, readable up to the next multiple of 4) -> BGZF blocks in c->bgzf_out: three launches and one wait, for the size
+static int bgzf_device(dg_ctx *c, const unsigned char *d_in, size_t n, size_t *n_out, float *ms)
+{
+    *n_out = 0; *ms = 0.f;
+    const size_t blocks = (n + BGZF_BLOCK - 1) / BGZF_BLOCK;
+    if (!blocks) return DG_OK;
+    if (blocks > 0x7fffffffull) { snprintf(c->err, 512, "BGZF: %zu bytes are more than one call takes", n); return DG_ERR_ARG; }
+    HIPCHK(c->bgzf_slots.ensure(blocks * BGZF_SLOT)); HIPCHK(c->bgzf_size.ensure(blocks)); HIPCHK(c->bgzf_off.ensure(blocks));
+    HIPCHK(c->bgzf_out.ensure(n + (size_t)BGZF_OVERHEAD * blocks));                 // the bound of the stored form: no block is larger
+    HIPCHK(hipEventRecord(c->ev_bam[0], c->stream));
+    k_bgzf_deflate<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bgzf_slots.p, c->bgzf_off.p, c->bgzf_size.p);
+    k_sam_top<<<1, 256, 0, c->stream>>>(c->bgzf_off.p, (uint32_t)blocks, c->d_bam_stat + 6);
+    k_bgzf_copy<<<(unsigned)blocks, 256, 0, c->stream>>>(c->bgzf_slots.p, c->bgzf_off.p, c->bgzf_size.p, c->bgzf_out.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_bam[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bam_stat + 6, c->d_bam_stat + 6, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    (void)hipEventElapsedTime(ms, c->ev_bam[0], c->ev_bam[1]);
+    *n_out = (size_t)c->h_bam_stat[6];
+    if (*n_out > n + (size_t)BGZF_OVERHEAD * blocks) { snprintf(c->err, 512, "BGZF: %zu bytes of blocks for %zu bytes", *n_out, n); return DG_ERR_INTERNAL; }
+    return DG_OK;
+}
+
+// The writer behind its inputs, as sam_format_device: names and qualities are in HBM.  Both entry points run these launches.
+static int bam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr, const uint32_t *qual_off, const char *qual, size_t hdr_bytes, size_t qual_bytes,
+                             int n_pair_mode, uint32_t flags, size_t *n_bytes, size_t *n_raw, uint64_t counters[5], float *device_ms)
+{
+    const int n = c->n_reads;
+    IndexShared *sh = c->shared_ix;
+    { const int rc = bam_state(c); if (rc) return rc; }
+    const uint32_t n_tiles = (uint32_t)((n + SAM_LEN_THREADS - 1) / SAM_LEN_THREADS);
+    HIPCHK(c->sam_qlen.ensure((size_t)n)); HIPCHK(c->sam_read_off.ensure((size_t)n)); HIPCHK(c->sam_tile.ensure(n_tiles));
+    // the capacity is a guess the first time (one record per read); when it was too small k_bam_write alone runs again -- never the batch
+    size_t want = hdr_bytes + qual_bytes + c->seq_bytes / 2 + (size_t)n * 64;
+    want += want / 8;
+    if (c->env_bam_first_cap && !c->bam_rec.p) want = c->env_bam_first_cap;
+    if (c->bam_rec.cap < want + 8) HIPCHK(c->bam_rec.ensure(want + 8));
+    SamBatch b;
+    b.ro = c->reads_out.p; b.po = c->reports.p; b.cig = c->cigfinal.p;
+    b.seq_off = c->seq_off.p; b.rlen = c->rlen.p; b.seq = c->seq.p;
+    b.hdr_off = hdr_off; b.hdr = hdr;
+    b.qual_off = qual ? qual_off : nullptr; b.qual = qual;
+    b.chr_off = nullptr; b.chr = nullptr; b.qlen = nullptr;
+    b.n_reads = n; b.n_pair_mode = n_pair_mode; b.unique_only = (flags & DG_SAM_UNIQUE_ONLY) ? 1 : 0; b.multi = c->pr.multi_hit ? 1 : 0;
+    SamBatch b2 = b;
+    const unsigned grid = (unsigned)n;
+    {   // k_bam_len takes its counters from the SAM formatter's length pass, which reads the chromosome names: enqueued under the index's lock, as there
+        std::lock_guard<std::mutex> lk(sh->mu);
+        b.chr_off = sh->d_chr_name_off; b.chr = sh->d_chr_names;
+        b2.qlen = c->sam_qlen.p;                                  // (the writer reads no names)
+        HIPCHK(hipEventRecord(c->ev_bam[0], c->stream));
+        HIPCHK(hipMemsetAsync(c->d_bam_stat, 0, 8 * 8, c->stream));
+        k_bam_len<<<n_tiles, SAM_LEN_THREADS, 0, c->stream>>>(b, c->sam_read_off.p, c->sam_qlen.p, c->sam_tile.p, c->d_bam_stat);
+        k_sam_top<<<1, 256, 0, c->stream>>>(c->sam_tile.p, n_tiles, c->d_bam_stat);
+        k_bam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam_read_off.p, c->sam_tile.p, c->d_bam_stat, (unsigned long long)(c->bam_rec.cap - 8), c->bam_rec.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev_bam[1], c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(c->h_bam_stat, c->d_bam_stat, 6 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the first wait: for the records' size
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->ev_bam[0], c->ev_bam[1]);
+    const size_t total = (size_t)c->h_bam_stat[0];
+    if (total > c->bam_rec.cap - 8) {                             // the guess was too small: the lengths stand, the writer runs again
+        HIPCHK(c->bam_rec.ensure(total + 8));
+        HIPCHK(hipEventRecord(c->ev_bam[0], c->stream));
+        k_bam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam_read_off.p, c->sam_tile.p, c->d_bam_stat, (unsigned long long)(c->bam_rec.cap - 8), c->bam_rec.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev_bam[1], c->stream));
+        HIPCHK(wait_stream(c));
+        float ms2 = 0.f;
+        (void)hipEventElapsedTime(&ms2, c->ev_bam[0], c->ev_bam[1]);
+        ms += ms2;
+    }
+    size_t out_bytes = total;
+    c->bam_ptr = c->bam_rec.p;
+    c->bam_ms[0] = ms; c->bam_ms[1] = 0.f;
+    if (!(flags & DG_BAM_RAW) && total) {
+        float ms_z = 0.f;
+        const int rc = bgzf_device(c, c->bam_rec.p, total, &out_bytes, &ms_z);      // the second wait: for the stream's size
+        if (rc) return rc;
+        ms += ms_z; c->bam_ms[1] = ms_z;
+        c->bam_ptr = c->bgzf_out.p;
+    }
+    c->bam_bytes = out_bytes; c->bam_valid = true;
+    if (n_bytes) *n_bytes = out_bytes;
+    if (n_raw) *n_raw = total;
+    if (counters) for (int i = 0; i < 5; i++) counters[i] = c->h_bam_stat[1 + i];
+    if (device_ms) *device_ms = ms;
+    return DG_OK;
+}
+
+static void bam_outputs_zero(size_t *n_raw, uint64_t counters[5]) { if (n_raw) *n_raw = 0; if (counters) counters[3] = counters[4] = 0; }
+
+extern "C" int dg_batch_format_bam(dg_ctx *c, const dg_sam_text *in, uint32_t flags, size_t *n_bytes, size_t *n_raw, uint64_t counters[5], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_batch_format_bam";
+    bam_outputs_zero(n_raw, counters);
+    if (!in) {
+        if (n_bytes) *n_bytes = 0;
+        if (counters) counters[0] = counters[1] = counters[2] = 0;
+        if (device_ms) *device_ms = 0.f;
+        c->bam_valid = false; c->bam_bytes = 0;
+        snprintf(c->err, 512, "%s: the input is NULL", fn); return DG_ERR_ARG;
+    }
+    const int rc = sam_batch_ready(c, in->n_pair_mode, n_bytes, counters, device_ms, fn, true);
+    if (rc) return rc;
+    const int n = c->n_reads;
+    if (n == 0) { c->bam_valid = true; c->bam_ptr = nullptr; return DG_OK; }
+    if (!in->hdr_off || (in->qual && !in->qual_off)) { snprintf(c->err, 512, "%s: an offset array is NULL", fn); return DG_ERR_ARG; }
+    if (sam_offsets_ok(c, "hdr_off", in->hdr_off, n, fn) || (in->qual && sam_offsets_ok(c, "qual_off", in->qual_off, n, fn))) return DG_ERR_ARG;
+    const size_t hdr_bytes = (size_t)in->hdr_off[n] - in->hdr_off[0], qual_bytes = in->qual ? (size_t)in->qual_off[n] - in->qual_off[0] : 0;
+    if (hdr_bytes && !in->hdr) { snprintf(c->err, 512, "%s: hdr is NULL", fn); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->sam_hdr_off.ensure((size_t)n + 1)); HIPCHK(c->sam_hdr.ensure(hdr_bytes + 1));
+    if (in->qual) { HIPCHK(c->sam_qual_off.ensure((size_t)n + 1)); HIPCHK(c->sam_qual.ensure(qual_bytes + 1)); }
+    HIPCHK(hipMemcpyAsync(c->sam_hdr_off.p, in->hdr_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (hdr_bytes) HIPCHK(hipMemcpyAsync(c->sam_hdr.p, in->hdr + in->hdr_off[0], hdr_bytes, hipMemcpyHostToDevice, c->stream));
+    if (in->qual) {
+        HIPCHK(hipMemcpyAsync(c->sam_qual_off.p, in->qual_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (qual_bytes) HIPCHK(hipMemcpyAsync(c->sam_qual.p, in->qual + in->qual_off[0], qual_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    return bam_format_device(c, c->sam_hdr_off.p, c->sam_hdr.p - in->hdr_off[0], in->qual ? c->sam_qual_off.p : nullptr, in->qual ? c->sam_qual.p - in->qual_off[0] : nullptr,
+                             hdr_bytes, qual_bytes, in->n_pair_mode, flags, n_bytes, n_raw, counters, device_ms);
+}
+
+extern "C" int dg_batch_format_bam_resident(dg_ctx *c, int n_pair_mode, uint32_t flags, size_t *n_bytes, size_t *n_raw, uint64_t counters[5], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    bam_outputs_zero(n_raw, counters);
+    const int rc = sam_batch_ready(c, n_pair_mode, n_bytes, counters, device_ms, "dg_batch_format_bam_resident", true);
+    if (rc) return rc;
+    if (!c->fq_valid) { snprintf(c->err, 512, "dg_batch_format_bam_resident: the context's last upload was not dg_batch_upload_fastq: no names and qualities in HBM"); return DG_ERR_ARG; }
+    if (c->n_reads == 0) { c->bam_valid = true; c->bam_ptr = nullptr; return DG_OK; }
+    HIPCHK(hipSetDevice(c->device));
+    return bam_format_device(c, c->fq_hdr_off.p, c->fq_hdr.p, c->fq_qual_off.p, c->fq_qual.p, c->fq_hdr_bytes, c->fq_qual_bytes, n_pair_mode, flags, n_bytes, n_raw, counters, device_ms);
+}
+
+extern "C" int dg_batch_download_bam(dg_ctx *c, void *out, size_t cap)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->bam_valid) { snprintf(c->err, 512, "dg_batch_download_bam: no BAM bytes (dg_batch_format_bam or dg_bgzf_compress first)"); return DG_ERR_ARG; }
+    if (cap < c->bam_bytes) { snprintf(c->err, 512, "dg_batch_download_bam: output capacity too small: %zu bytes of %zu", cap, c->bam_bytes); return DG_ERR_CAPACITY; }
+    if (c->bam_bytes == 0) return DG_OK;
+    if (!out) return DG_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(out, c->bam_ptr, c->bam_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_batch_device_bam(dg_ctx *c, void **ptr, size_t *n_bytes)
+{
+    if (!c || !ptr || !n_bytes) return DG_ERR_ARG;
+    if (!c->bam_valid) { snprintf(c->err, 512, "dg_batch_device_bam: no BAM bytes (dg_batch_format_bam or dg_bgzf_compress first)"); return DG_ERR_ARG; }
+    *ptr = c->bam_bytes ? c->bam_ptr : nullptr; *n_bytes = c->bam_bytes;
+    return DG_OK;
+}
+
+extern "C" int dg_bgzf_compress(dg_ctx *c, const void *host_bytes, size_t n, size_t *n_bytes, float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_bytes) *n_bytes = 0;
+    if (device_ms) *device_ms = 0.f;
+    c->bam_valid = false; c->bam_bytes = 0; c->bam_ptr = nullptr;
+    if (n == 0) { c->bam_valid = true; return DG_OK; }
+    if (!host_bytes) { snprintf(c->err, 512, "dg_bgzf_compress: the input is NULL"); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    { const int rc = bam_state(c); if (rc) return rc; }
+    HIPCHK(c->bgzf_in.ensure(n + 8));
+    HIPCHK(hipMemcpyAsync(c->bgzf_in.p, host_bytes, n, hipMemcpyHostToDevice, c->stream));
+    size_t out_bytes = 0; float ms = 0.f;
+    const int rc = bgzf_device(c, c->bgzf_in.p, n, &out_bytes, &ms);
+    if (rc) return rc;
+    c->bam_ptr = c->bgzf_out.p; c->bam_bytes = out_bytes; c->bam_valid = true;
+    c->bam_ms[0] = 0.f; c->bam_ms[1] = ms;
+    if (n_bytes) *n_bytes = out_bytes;
+    if (device_ms) *device_ms = ms;
+    return DG_OK;
+}
+
+extern "C" int dg_batch_bam_device_ms(dg_ctx *c, float ms[2])
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    ms[0] = c->bam_ms[0]; ms[1] = c->bam_ms[1];
+    return DG_OK;
+}
+
+extern "C" int dg_bgzf_granules(int out[2])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = (int)BGZF_STRIP; out[1] = (int)BGZF_SEG;
     return DG_OK;
 }
 

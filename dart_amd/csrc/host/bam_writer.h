@@ -103,6 +103,14 @@ public:
         for (size_t c = 0; c < n; c++) { append(recs[c].data(), recs[c].size()); n_records_ += good[c]; n_refused_ += refused[c]; }
         compress_full_blocks();
     }
+    // BGZF blocks of whole records that were compressed elsewhere (the device: dg_batch_format_bam): what is pending goes out first, then the bytes as they are
+    bool add_bgzf_blocks(const void *p, size_t n, long long records, long long refused)
+    {
+        flush_all();
+        if (n && fwrite(p, 1, n, f_) != n) bad_ = true;
+        n_records_ += records; n_refused_ += refused;
+        return !bad_;
+    }
     long long records() const { return n_records_; }
     long long refused() const { return n_refused_; }
 

@@ -404,9 +404,9 @@ static inline void put_cigar(std::string &out, const uint32_t *ops, uint32_t n)
 static std::string fast_format_text(const FastStats &f)
 {
     char b[384];
-    if (g_device_sam && f.fq_device) snprintf(b, sizeof b, "format=device %.3f s (sum over workers: names and qualities resident in HBM, dg_batch_format_sam_resident %.3f s of which kernels %.3f s, text download %.3f s; %zu batches, %.4f s per batch on its worker's path)",
+    if ((g_device_sam || g_device_bam) && f.fq_device) snprintf(b, sizeof b, "format=device %.3f s (sum over workers: names and qualities resident in HBM, dg_batch_format_sam_resident %.3f s of which kernels %.3f s, text download %.3f s; %zu batches, %.4f s per batch on its worker's path)",
                                               f.t_dev_call + f.t_download, f.t_dev_call, f.t_dev_kernels, f.t_download, f.n_batches, (f.t_dev_call + f.t_download) / (double)std::max<size_t>(1, f.n_batches));
-    else if (g_device_sam) snprintf(b, sizeof b, "format=device %.3f s (sum over workers: gather names and qualities %.3f s, dg_batch_format_sam %.3f s of which kernels %.3f s, text download %.3f s; %zu batches, %.4f s per batch on its worker's path)",
+    else if (g_device_sam || g_device_bam) snprintf(b, sizeof b, "format=device %.3f s (sum over workers: gather names and qualities %.3f s, dg_batch_format_sam %.3f s of which kernels %.3f s, text download %.3f s; %zu batches, %.4f s per batch on its worker's path)",
                                f.t_gather + f.t_dev_call + f.t_download, f.t_gather, f.t_dev_call, f.t_dev_kernels, f.t_download, f.n_batches, (f.t_gather + f.t_dev_call + f.t_download) / (double)std::max<size_t>(1, f.n_batches));
     else snprintf(b, sizeof b, "format=host %.3f s", f.t_fmt);
     return b;
@@ -551,6 +551,10 @@ int main(int argc, char *argv[])
     const double t_proc0 = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     size_t batch_reads = getenv("DART_BATCH") ? (size_t)atoll(getenv("DART_BATCH")) : 500000; batch_reads = std::max<size_t>(4000, batch_reads & ~(size_t)1);
     const int inflight_cfg = std::max(1, getenv("DART_INFLIGHT") ? atoi(getenv("DART_INFLIGHT")) : 2);
+    // DART_DEVICE_BAM=1 with -bo: plain-FASTQ libraries (and .gz ones inflated whole) take the parallel pipeline, and the BAM records and their BGZF blocks come
+    // from the device (dg_batch_format_bam); FASTA and streamed .gz keep the host writer whatever the switch says.  Without the switch -bo is what it always was.
+    const bool device_bam = o.bam && getenv("DART_DEVICE_BAM") && atoi(getenv("DART_DEVICE_BAM")) != 0;
+    const bool bam_streams = o.bam && !device_bam;         // -bo forces the streaming pipeline
     FastqIndex pre;                         // the first library's read files are mapped and indexed while the HIP runtime starts, the genome index loads and dg_init_files runs
     bool fast_first = false;
     // A library of .gz FASTQ files small enough to be inflated whole (libdeflate, ~3x zlib; DART_GZ_WHOLE_MAX_GB per file, default 8) goes through the
@@ -559,7 +563,7 @@ int main(int argc, char *argv[])
     const size_t gz_whole_max = (size_t)((getenv("DART_GZ_WHOLE_MAX_GB") ? atof(getenv("DART_GZ_WHOLE_MAX_GB")) : 8.0) * (double)(1ull << 30));
     auto is_gz = [](const std::string &fn) { return fn.substr(fn.find_last_of('.') + 1) == "gz"; };
     auto gz_whole_candidate = [&](size_t lib) -> bool {
-        if (o.bam || getenv("DART_STREAMING") || getenv("DART_GZ_STREAM") || !lib_deflate().ok() || gz_whole_max == 0) return false;
+        if (bam_streams || getenv("DART_STREAMING") || getenv("DART_GZ_STREAM") || !lib_deflate().ok() || gz_whole_max == 0) return false;
         const bool two = o.f1.size() == o.f2.size();
         struct stat st;
         const std::string *fns[2] = {&o.f1[lib], two ? &o.f2[lib] : nullptr};
@@ -573,7 +577,7 @@ int main(int argc, char *argv[])
     {
         const std::string &fn0 = o.f1[0];
         const bool two = o.f1.size() == o.f2.size();
-        if (!o.bam && !getenv("DART_STREAMING") && !is_gz(fn0) && check_read_format(fn0.c_str())) {
+        if (!bam_streams && !getenv("DART_STREAMING") && !is_gz(fn0) && check_read_format(fn0.c_str())) {
             fast_first = true;
             if (!two || !is_gz(o.f2[0])) pre.start(fn0.c_str(), two ? o.f2[0].c_str() : nullptr, o.threads);
         } else if (gz_whole_candidate(0)) {
@@ -615,7 +619,7 @@ int main(int argc, char *argv[])
         if (L.sep && !L.s2.fp && !L.s2.gz) return L.state = 1;
         if (L.s1.gz) gzbuffer(L.s1.gz, 1u << 20);
         if (L.s2.gz) gzbuffer(L.s2.gz, 1u << 20);
-        L.fast_host = L.fastq && !L.gz && !o.bam && !getenv("DART_STREAMING") && (!L.sep || o.f2[lib].substr(o.f2[lib].find_last_of('.') + 1) != "gz");
+        L.fast_host = L.fastq && !L.gz && !bam_streams && !getenv("DART_STREAMING") && (!L.sep || o.f2[lib].substr(o.f2[lib].find_last_of('.') + 1) != "gz");
         if (L.sep && !L.fast_host) { L.pf1.start(&L.s1, false); L.pf2.start(&L.s2, true); }      // (separate mate files: paired, mate 2 reverse-complemented)
         return L.state = 0;
     };
@@ -672,8 +676,9 @@ int main(int argc, char *argv[])
     const bool device_sam = !o.bam && getenv("DART_DEVICE_SAM") && atoi(getenv("DART_DEVICE_SAM")) != 0;
     g_device_sam = device_sam;
     // DART_DEVICE_FASTQ=1: the parallel pipeline hands its batches to the GPU as FASTQ text (dg_batch_upload_fastq); the streaming pipeline and -bo ignore it
-    g_device_fastq = !o.bam && getenv("DART_DEVICE_FASTQ") && atoi(getenv("DART_DEVICE_FASTQ")) != 0;
-    if (device_sam) {
+    g_device_fastq = !bam_streams && getenv("DART_DEVICE_FASTQ") && atoi(getenv("DART_DEVICE_FASTQ")) != 0;
+    g_device_bam = device_bam;
+    if (device_sam || device_bam) {
         std::vector<uint32_t> noff{0}; std::string nflat;
         for (const std::string &nm : ix.names) { nflat += nm; noff.push_back((uint32_t)nflat.size()); }
         for (dg_ctx *r : roots) if (dg_set_chr_names(r, (int)ix.names.size(), noff.data(), nflat.data())) { fprintf(stderr, "Error! %s\n", dg_last_error(r)); return 1; }
@@ -693,6 +698,11 @@ int main(int argc, char *argv[])
         fwrite(hdr_text.data(), 1, hdr_text.size(), sam);
     }
 
+    if (device_bam) g_bam_sink = [&bam](const char *p, size_t n, long long records, long long refused) { return bam.add_bgzf_blocks(p, n, records, refused); };
+    // the parallel pipeline's place in the output: the SAM file's descriptor and offset; with DART_DEVICE_BAM the blocks go through g_bam_sink instead
+    auto out_begin = [&](uint64_t &off) -> int { if (!sam) { off = 0; return -1; } fflush(sam); off = (uint64_t)ftello(sam); return fileno(sam); };
+    auto out_end = [&](uint64_t off) { if (sam) fseeko(sam, (off_t)off, SEEK_SET); };
+    const char *bam_note = !o.bam ? "" : ", bam=host";        // (the DART_TIMING lines: which BAM path a library took)
     Counters total;
     std::map<std::pair<int64_t, int64_t>, int> sjmap;
     time_t t0 = time(NULL);
@@ -707,14 +717,13 @@ int main(int argc, char *argv[])
             if (gi && gi->ok) {
                 const bool sep = o.f1.size() == o.f2.size();
                 if (sep) pair_end = true;
-                fflush(sam);
-                uint64_t off = (uint64_t)ftello(sam);
+                uint64_t off = 0; const int out_fd = out_begin(off);
                 std::string ferr; FastStats fst;
                 const int frc = run_fast_library(o.f1[lib].c_str(), sep ? o.f2[lib].c_str() : nullptr, pair_end, o.threads, batch_reads, ctx, o.p, ix.names, o.unique, o.multi, o.silent,
-                                                 fileno(sam), &off, total, sjmap, t0, ferr, fst, pool, gi);
-                fseeko(sam, (off_t)off, SEEK_SET);
+                                                 out_fd, &off, total, sjmap, t0, ferr, fst, pool, gi);
+                out_end(off);
                 if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write);
+                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, device_bam ? ", bam=device" : "");
                 gi->m1.close_now(); gi->m2.close_now();
                 continue;
             }
@@ -728,14 +737,13 @@ int main(int argc, char *argv[])
         const std::string &fn = o.f1[lib];
         if (sep) pair_end = true;
         if (fast_host) {
-            fflush(sam);
-            uint64_t off = (uint64_t)ftello(sam);
+            uint64_t off = 0; const int out_fd = out_begin(off);
             std::string ferr; FastStats fst;
             const int frc = run_fast_library(fn.c_str(), sep ? o.f2[lib].c_str() : nullptr, pair_end, o.threads, batch_reads, ctx, o.p, ix.names, o.unique, o.multi, o.silent,
-                                             fileno(sam), &off, total, sjmap, t0, ferr, fst, pool, lib == 0 ? &pre : nullptr);
-            fseeko(sam, (off_t)off, SEEK_SET);
+                                             out_fd, &off, total, sjmap, t0, ferr, fst, pool, lib == 0 ? &pre : nullptr);
+            out_end(off);
             if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write);
+            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, device_bam ? ", bam=device" : "");
             if (s1.fp) fclose(s1.fp);
             if (s2.fp) fclose(s2.fp);
             continue;
@@ -905,7 +913,7 @@ int main(int argc, char *argv[])
         pf1.finish(); pf2.finish();
         for (auto &w : workers) w.join();
         if (bad) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", bad_rc, bad_msg.c_str()); return 1; }
-        if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] read+parse %.3f s, map (sum over workers) %.3f s, format=%s %.3f s, write %.3f s\n", t_read, t_map, device_sam ? "device" : "host", t_fmt, t_write);
+        if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] read+parse %.3f s, map (sum over workers) %.3f s, format=%s %.3f s, write %.3f s%s\n", t_read, t_map, device_sam ? "device" : "host", t_fmt, t_write, bam_note);
         if (s1.fp) fclose(s1.fp);
         if (s2.fp) fclose(s2.fp);
         s1.inf.reset(); s2.inf.reset();              // (the inflater threads end before their files are closed)

@@ -15,6 +15,7 @@
 // reference's reader and of the streaming path in dart_main.cpp; tests/test_gpu_cli.py runs both paths against the oracle's
 // command line.
 #pragma once
+#include <functional>
 #include <atomic>
 #include <cerrno>
 #include <fcntl.h>
@@ -340,11 +341,15 @@ static bool g_device_sam = false;
 // the host; with DART_DEVICE_SAM=1 as well the text is formatted from the names and qualities that upload left in HBM (dg_batch_format_sam_resident) and
 // nothing is gathered.  The index pass below still decides the batches.  A library with a record without bases keeps the host's assembly.
 static bool g_device_fastq = false;
+// DART_DEVICE_BAM=1 with -bo: the batch's BAM records are written and compressed on the GPU (dg_batch_format_bam, or its resident form with DART_DEVICE_FASTQ=1)
+// behind its mapping; the slot holds whole BGZF blocks and the ordered writer hands them to g_bam_sink (BamWriter::add_bgzf_blocks) instead of writing text to fd.
+static bool g_device_bam = false;
+static std::function<bool(const char *blocks, size_t n, long long records, long long refused)> g_bam_sink;
 
 struct FastSlot {                       // one batch travelling through the stages
     size_t first = 0; int n = 0, odd = 0; size_t seqno = 0;
     std::vector<uint32_t> hoff, qoff; char *names_quals = nullptr; size_t nq_cap = 0;      // device formatter: the batch's names and stored qualities, flat
-    char *text = nullptr; size_t text_cap = 0, text_n = 0; uint64_t dev_ct[3] = {0, 0, 0}; //                   its text and counters
+    char *text = nullptr; size_t text_cap = 0, text_n = 0; uint64_t dev_ct[3] = {0, 0, 0}, bam_rr[2] = {0, 0}; //  its text (or BGZF blocks) and counters; BAM: records written, lines refused
     std::vector<RView> view; std::vector<uint32_t> soff; std::vector<uint16_t> rl;
     char *seq = nullptr; size_t seq_cap = 0, n_cap = 0;            // page-locked
     dg_read_out *ro = nullptr; dg_report_out *po = nullptr; uint32_t *cig = nullptr; dg_sj_out *sj = nullptr; size_t caps[3] = {0, 0, 0}, used[3] = {0, 0, 0};
@@ -553,7 +558,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 if (s->fq_n1 >= 0xFFFFFF00ull || s->fq_n2 >= 0xFFFFFF00ull) { s->rc = DG_ERR_ARG; s->err = "a batch's FASTQ text exceeds 32-bit offsets: lower DART_BATCH"; }
                 else {
                     { const double tl = now(); const size_t z[3] = {0, 0, 0}; slot_reserve(*s, (size_t)n, 0, z); st.t_alloc += now() - tl; }
-                    if (!g_device_sam) {
+                    if (!g_device_sam && !g_device_bam) {
                         s->view.resize(n);
                         const int TA = std::max(1, T / 8);
                         parallel_for(TA, [&](int tid) {
@@ -661,22 +666,34 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 }
             }
             double t_gather = 0, t_call = 0, t_dl = 0; float dev_ms = 0.f;
-            if (!s->rc && g_device_sam && s->fq_device) {
+            const bool dev_out = g_device_sam || g_device_bam;
+            // the device's formatter for this job: SAM text, or with DART_DEVICE_BAM the BGZF blocks of the BAM records (in == nullptr: the resident form)
+            auto dev_format = [&](const dg_sam_text *in, int npm, size_t *nb) -> int {
+                const uint32_t fl = unique_only ? DG_SAM_UNIQUE_ONLY : 0u;
+                if (!g_device_bam) return in ? dg_batch_format_sam(ctx[w], in, fl, nb, s->dev_ct, &dev_ms) : dg_batch_format_sam_resident(ctx[w], npm, fl, nb, s->dev_ct, &dev_ms);
+                uint64_t ct[5] = {0, 0, 0, 0, 0}; size_t raw = 0;
+                const int rc = in ? dg_batch_format_bam(ctx[w], in, fl, nb, &raw, ct, &dev_ms) : dg_batch_format_bam_resident(ctx[w], npm, fl, nb, &raw, ct, &dev_ms);
+                for (int i = 0; i < 3; i++) s->dev_ct[i] = ct[i];
+                s->bam_rr[0] = ct[3]; s->bam_rr[1] = ct[4];
+                return rc;
+            };
+            auto dev_download = [&]() -> int { return g_device_bam ? dg_batch_download_bam(ctx[w], s->text, s->text_cap) : dg_batch_download_sam(ctx[w], s->text, s->text_cap); };
+            if (!s->rc && dev_out && s->fq_device) {
                 // names and qualities are in HBM already, in stored order: nothing to gather
                 size_t nb = 0;
                 const double tc = now();
-                int rc = dg_batch_format_sam_resident(ctx[w], (pair_end && !s->odd) ? s->n : 0, unique_only ? DG_SAM_UNIQUE_ONLY : 0u, &nb, s->dev_ct, &dev_ms);
+                int rc = dev_format(nullptr, (pair_end && !s->odd) ? s->n : 0, &nb);
                 t_call = now() - tc;
                 if (!rc) {
                     const double td = now();
                     if (nb > s->text_cap) { arena_free(s->text); s->text_cap = nb + nb / 8 + 4096; s->text = (char *)arena_alloc(s->text_cap); }
-                    rc = dg_batch_download_sam(ctx[w], s->text, s->text_cap);
+                    rc = dev_download();
                     s->text_n = nb;
                     t_dl = now() - td;
                 }
                 if (rc) { s->rc = rc; s->err = dg_last_error(ctx[w]); }
             } else
-            if (!s->rc && g_device_sam) {
+            if (!s->rc && dev_out) {
                 // the batch's names and qualities, flat, mate 2's qualities in stored order (reversed); then the text from the device
                 const double tg = now();
                 const int n = s->n;
@@ -701,12 +718,12 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                     dg_sam_text in; in.hdr_off = s->hoff.data(); in.hdr = hb; in.qual_off = s->qoff.data(); in.qual = qb; in.n_pair_mode = (pair_end && !s->odd) ? n : 0;
                     size_t nb = 0;
                     const double tc = now();
-                    int rc = dg_batch_format_sam(ctx[w], &in, unique_only ? DG_SAM_UNIQUE_ONLY : 0u, &nb, s->dev_ct, &dev_ms);
+                    int rc = dev_format(&in, in.n_pair_mode, &nb);
                     t_call = now() - tc;
                     if (!rc) {
                         const double td = now();
                         if (nb > s->text_cap) { arena_free(s->text); s->text_cap = nb + nb / 8 + 4096; s->text = (char *)arena_alloc(s->text_cap); }
-                        rc = dg_batch_download_sam(ctx[w], s->text, s->text_cap);
+                        rc = dev_download();
                         s->text_n = nb;
                         t_dl = now() - td;
                     }
@@ -738,14 +755,15 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             for (int k = 0; k < TF; k++) offs[k + 1] = offs[k] + ts.pieces[k].second;
             const uint64_t base = *file_off;
             char *win = nullptr; size_t win_len = 0; const uint64_t a0 = base & ~(uint64_t)4095;
-            if (use_mmap && offs[TF] && ftruncate(fd, (off_t)(base + offs[TF])) == 0) {      // copy into a shared mapping of the file's new part
+            if (use_mmap && !g_device_bam && offs[TF] && ftruncate(fd, (off_t)(base + offs[TF])) == 0) {      // copy into a shared mapping of the file's new part
                 win_len = (size_t)(base + offs[TF] - a0);
                 void *m = mmap(nullptr, win_len, PROT_READ | PROT_WRITE, MAP_SHARED, fd, (off_t)a0);
                 win = m == MAP_FAILED ? nullptr : (char *)m;
             }
             const int TW = win ? std::max(1, TF / 4) : TWR;     // writes to one file serialise in the kernel: more threads only burn the CPU share
             std::atomic<int> write_errno{0};                 // a full disk must not end as a holed SAM file and exit code 0
-            if (use_mmap && offs[TF] && !win) write_errno = errno ? errno : EIO;
+            if (g_device_bam) { if (!g_bam_sink || !g_bam_sink(ts.pieces[0].first, ts.pieces[0].second, (long long)s->bam_rr[0], (long long)s->bam_rr[1])) write_errno = errno ? errno : EIO; }
+            else if (use_mmap && offs[TF] && !win) write_errno = errno ? errno : EIO;
             else parallel_for(TW, [&](int wt) {
                 for (int tid = wt; tid < TF; tid += TW) {
                     const char *piece = ts.pieces[tid].first; const size_t piece_n = ts.pieces[tid].second;
@@ -765,7 +783,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 cv.notify_all();
                 break;
             }
-            *file_off = base + offs[TF];
+            if (!g_device_bam) *file_off = base + offs[TF];
             for (int k = 0; k < TF; k++) { total.unique += ts.cts[k].unique; total.unmapped += ts.cts[k].unmapped; total.paired += ts.cts[k].paired; }
             total.total += s->n;
             for (size_t k = 0; k < s->used[2]; k++) sjmap[std::make_pair(s->sj[k].g1, s->sj[k].g2)]++;   // UpdateLocal/GlobalSJMap, Mapping.cpp:532-577
@@ -788,7 +806,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
         const double tf = now();
         const int n = s->n, n_pair_mode = (pair_end && !s->odd) ? n : 0;
         ts.pieces.assign(TF, std::make_pair((const char *)nullptr, (size_t)0));
-        if (g_device_sam) {                                   // formatted on the device behind the mapping: the text is in the slot
+        if (g_device_sam || g_device_bam) {                   // formatted on the device behind the mapping: the text (or the BGZF blocks) is in the slot
             for (int tid = 0; tid < TF; tid++) ts.cts[tid] = Counters();
             ts.pieces[0] = std::make_pair((const char *)s->text, s->text_n);
             ts.cts[0].unmapped = (long long)s->dev_ct[0]; ts.cts[0].unique = (long long)s->dev_ct[1]; ts.cts[0].paired = (long long)s->dev_ct[2];

@@ -93,6 +93,7 @@ class SamText(C.Structure):
 
 
 SAM_UNIQUE_ONLY = 1
+BAM_RAW = 2
 
 
 class FastqText(C.Structure):
@@ -246,6 +247,14 @@ def _load_lib():
         lib.dg_batch_download_reads.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.dg_batch_fastq_device_ms.argtypes = [vp, vp]
         lib.dg_fastq_tile.restype = C.c_int
+    if hasattr(lib, "dg_batch_format_bam"):                  # (likewise: BAM records and BGZF blocks on the device)
+        lib.dg_batch_format_bam.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp]
+        lib.dg_batch_format_bam_resident.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, vp, vp]
+        lib.dg_batch_download_bam.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_batch_device_bam.argtypes = [vp, vp, vp]
+        lib.dg_bgzf_compress.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        lib.dg_bgzf_granules.argtypes = [vp]
+        lib.dg_batch_bam_device_ms.argtypes = [vp, vp]
     lib.dg_last_counters.argtypes = [vp, vp, C.c_int]
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
@@ -415,6 +424,73 @@ class DartGPU:
         import torch
         ptr = C.c_void_p(); nb = C.c_size_t(0)
         self._chk(self.lib.dg_batch_device_sam(self.ctx, C.byref(ptr), C.byref(nb)), "dg_batch_device_sam")
+        if not nb.value:
+            return torch.empty(0, dtype=torch.uint8, device="cuda")
+
+        class _View:
+            pass
+        v = _View()
+        v.__cuda_array_interface__ = {"shape": (int(nb.value),), "typestr": "|u1", "data": (int(ptr.value), False), "version": 2}
+        return torch.as_tensor(v, device="cuda")
+
+    def _bam_result(self, nb, n_raw, ct, ms):
+        self.bam_device_ms = float(ms.value)
+        split = (C.c_float * 2)()
+        self.lib.dg_batch_bam_device_ms(self.ctx, split)
+        self.bam_device_ms_split = (float(split[0]), float(split[1]))      # record kernels, BGZF kernels
+        self.bam_raw_bytes = int(n_raw.value)
+        out = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_batch_download_bam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_bam")
+        return out[:int(nb.value)].tobytes(), dict(unmapped=int(ct[0]), unique=int(ct[1]), paired=int(ct[2]), records=int(ct[3]), refused=int(ct[4]))
+
+    def format_bam(self, headers, quals, n_pair_mode: int, unique_only: bool = False, raw: bool = False):
+        """BAM of the batch that ran last, made on the device (dg_batch_format_bam + dg_batch_download_bam) -> (bytes, counters): BGZF blocks without the
+        file's header and end-of-file block, or with raw=True the uncompressed records; arguments as format_sam; counters: format_sam's three, records
+        written and lines refused; self.bam_device_ms holds the kernels' device time, self.bam_raw_bytes the records' size"""
+        if not hasattr(self.lib, "dg_batch_format_bam"):
+            raise RuntimeError("this build of libdartgpu.so has no dg_batch_format_bam")
+        ho, hb = flatten_strings(headers)
+        t = SamText()
+        t.hdr_off, t.hdr, t.n_pair_mode = ho.ctypes.data, hb.ctypes.data, int(n_pair_mode)
+        if quals is not None:
+            qo, qb = flatten_strings(quals)
+            t.qual_off, t.qual = qo.ctypes.data, qb.ctypes.data
+        nb = C.c_size_t(0); n_raw = C.c_size_t(0); ct = (C.c_uint64 * 5)(); ms = C.c_float(0)
+        flags = (SAM_UNIQUE_ONLY if unique_only else 0) | (BAM_RAW if raw else 0)
+        self._chk(self.lib.dg_batch_format_bam(self.ctx, C.byref(t), flags, C.byref(nb), C.byref(n_raw), ct, C.byref(ms)), "dg_batch_format_bam")
+        return self._bam_result(nb, n_raw, ct, ms)
+
+    def format_bam_resident(self, n_pair_mode: int, unique_only: bool = False, raw: bool = False):
+        """format_bam with the names and qualities a FASTQ upload left in HBM (dg_batch_format_bam_resident) -> (bytes, counters)"""
+        nb = C.c_size_t(0); n_raw = C.c_size_t(0); ct = (C.c_uint64 * 5)(); ms = C.c_float(0)
+        flags = (SAM_UNIQUE_ONLY if unique_only else 0) | (BAM_RAW if raw else 0)
+        self._chk(self.lib.dg_batch_format_bam_resident(self.ctx, int(n_pair_mode), flags, C.byref(nb), C.byref(n_raw), ct, C.byref(ms)), "dg_batch_format_bam_resident")
+        return self._bam_result(nb, n_raw, ct, ms)
+
+    def bgzf_compress(self, data) -> bytes:
+        """any bytes -> BGZF blocks, compressed on the device (dg_bgzf_compress + dg_batch_download_bam); no end-of-file block; self.bam_device_ms holds the
+        kernels' device time"""
+        if not hasattr(self.lib, "dg_bgzf_compress"):
+            raise RuntimeError("this build of libdartgpu.so has no dg_bgzf_compress")
+        a = np.frombuffer(bytes(data) + b"\0", np.uint8)
+        nb = C.c_size_t(0); ms = C.c_float(0)
+        self._chk(self.lib.dg_bgzf_compress(self.ctx, a.ctypes.data, len(a) - 1, C.byref(nb), C.byref(ms)), "dg_bgzf_compress")
+        self.bam_device_ms = float(ms.value)
+        out = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_batch_download_bam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_bam")
+        return out[:int(nb.value)].tobytes()
+
+    def bgzf_granules(self):
+        """(strip, segment) of the device's deflate kernel in bytes (dg_bgzf_granules)"""
+        g = (C.c_int * 2)()
+        self._chk(self.lib.dg_bgzf_granules(g), "dg_bgzf_granules")
+        return int(g[0]), int(g[1])
+
+    def device_bam_tensor(self):
+        """torch uint8 view of the BAM bytes in HBM (dg_batch_device_bam), valid until the next upload or run"""
+        import torch
+        ptr = C.c_void_p(); nb = C.c_size_t(0)
+        self._chk(self.lib.dg_batch_device_bam(self.ctx, C.byref(ptr), C.byref(nb)), "dg_batch_device_bam")
         if not nb.value:
             return torch.empty(0, dtype=torch.uint8, device="cuda")
 

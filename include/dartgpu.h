@@ -259,6 +259,40 @@ int dg_batch_download_reads(dg_ctx *, uint32_t *seq_off, uint16_t *rlen, char *s
 int dg_batch_fastq_device_ms(dg_ctx *, float *ms);
 int dg_fastq_tile(void);
 
+/* ---- BAM on the device: the last batch's records -> uncompressed BAM records -> BGZF blocks, all in HBM (replaces sam_parse1 + sam_write1 of htslib on
+ * every SAM line, Mapping.cpp:41-48,655-662,739-755, and the host writer's deflate) ----
+ * A record is the bytes the host writer (dart_amd/csrc/host/bam_writer.h, BamWriter::sam_line_to_bam) makes of the SAM line dg_batch_format_sam prints for
+ * the same (read, report); the text is never built.  A line the writer refuses -- a name of 0 or more than 254 bytes, a printed quality whose length is not
+ * the read's, a CIGAR with an op code of 5 or more (the formatter prints it as '?') -- gives no bytes and is counted.  The blank-joined " XS:A:+" is lost, as in the reference's BAM.  Names hold no tab or newline.
+ *   dg_batch_format_bam           inputs, flags and errors as dg_batch_format_sam (no finished batch, compact-only records, a packed upload, no
+ *                                 chromosome names, decreasing offsets, a bad n_pair_mode: DG_ERR_ARG with a text; the batch stays usable).  The records lie
+ *                                 in read order in one array, the same whatever the launch geometry; the array is then cut into blocks of 0xff00 bytes
+ *                                 (the last may be shorter) and every block becomes one BGZF block: gzip / 'BC' header, one raw deflate block (LZ77 with
+ *                                 fixed Huffman codes, or stored when that is not smaller), CRC32, ISIZE.  The same input gives the same bytes on every run.
+ *                                 *n_bytes <= *n_raw + 31 * blocks.  No BAM header and no end-of-file block: the file's writer adds them (`dart -bo`:
+ *                                 BamWriter::open / close).  DG_BAM_RAW: stop at the records.  *n_raw = the records' bytes in both cases.
+ *                                 counters [0..2] as dg_batch_format_sam, [3] records written, [4] lines refused.  The call waits twice, for the two sizes;
+ *                                 when the records outgrew their buffer's first guess the writing kernel -- never the batch -- runs a second time.
+ *                                 A batch of 0 reads gives 0 bytes (0 blocks).  SAM and BAM of one batch may be formatted in either order.
+ *   dg_batch_format_bam_resident  the same with the names and qualities dg_batch_upload_fastq left in HBM; DG_ERR_ARG after any other upload
+ *   dg_batch_download_bam         copies the result out; DG_ERR_CAPACITY, nothing written, the text names the need, when cap is smaller
+ *   dg_batch_device_bam           the result in HBM, valid until the next upload or run on this context
+ *   dg_bgzf_compress              any n bytes of host memory -> BGZF blocks on the context's stream (n = 0: no block); needs no batch and no index aids;
+ *                                 leaves the result where dg_batch_download_bam / dg_batch_device_bam find it
+ *   dg_batch_bam_device_ms        device time of the last call's kernels: [0] the record kernels, [1] the BGZF kernels (0 when that phase did not run)
+ *   dg_bgzf_granules              [0] the strip, [1] the segment of the deflate kernel in bytes: matches are looked up in earlier strips (plus distance 1
+ *                                 and the same offset of the previous strip) and a lane's match ends with its segment (whole segments at the same distance are then joined, up to 258); tests place repeats on these seams
+ * dg_last_timings / dg_last_counters keep the batch's values.                                                                                          */
+#define DG_BAM_RAW 2u   /* leave the uncompressed records (no BGZF): what a caller with its own compressor, and the tests, take */
+int dg_batch_format_bam(dg_ctx *, const dg_sam_text *in, uint32_t flags, size_t *n_bytes, size_t *n_raw,
+                        uint64_t counters[5] /* SAM's three, [3] records written, [4] lines refused */, float *device_ms);
+int dg_batch_format_bam_resident(dg_ctx *, int n_pair_mode, uint32_t flags, size_t *n_bytes, size_t *n_raw, uint64_t counters[5], float *device_ms);
+int dg_batch_download_bam(dg_ctx *, void *out, size_t cap);
+int dg_batch_device_bam(dg_ctx *, void **ptr, size_t *n_bytes);
+int dg_bgzf_compress(dg_ctx *, const void *host_bytes, size_t n, size_t *n_bytes, float *device_ms);
+int dg_batch_bam_device_ms(dg_ctx *, float ms[2]);
+int dg_bgzf_granules(int out[2]);
+
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
 int dg_last_timings(dg_ctx *, const char **names, float *ms, int cap);
