@@ -13,6 +13,7 @@
 #include "dg_bamfmt.h"
 #include "dg_bgzf.h"
 #include "dg_fastq.h"
+#include "dg_sjtab.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -101,7 +102,7 @@ struct IndexShared {
     std::string report, report_out;
     int device = 0;
     // chromosome names for the SAM text (dg_set_chr_names): with the index, so every clone prints them
-    uint32_t *d_chr_name_off = nullptr; char *d_chr_names = nullptr; bool chr_names_set = false; uint64_t chr_names_gen = 0;
+    uint32_t *d_chr_name_off = nullptr; char *d_chr_names = nullptr; bool chr_names_set = false; uint64_t chr_names_gen = 0; uint32_t chr_name_max = 0;
 };
 
 struct dg_ctx {
@@ -168,6 +169,14 @@ struct dg_ctx {
     unsigned long long *d_bam_stat = nullptr, *h_bam_stat = nullptr;      // [0] raw bytes, [1..3] the SAM counters, [4] records, [5] refused, [6] stream bytes: device / page-locked copy
     hipEvent_t ev_bam[2] = {nullptr, nullptr}; float bam_ms[2] = {0.f, 0.f};      // (both phases use the pair, one after the other) / device time of the record kernels, of the BGZF kernels
     bool bam_valid = false; size_t bam_bytes = 0; unsigned char *bam_ptr = nullptr;
+    // the splice-junction table (dg_sjtab.h): resident across batches; the overflow lists of an insert pass and of the growth behind it; the sorter's buffers,
+    // the sorted entries and the text of the last dg_sj_finish
+    SjSlot *sj_tab = nullptr; size_t sj_slots = 0, sj_distinct = 0;
+    DBuf<dg_sj_entry> sj_ovf[2], sj_in, sj_entries; int sj_ovf_cur = 0;
+    DBuf<uint64_t> sj_keys[2], sj_line_off, sj_tile; DBuf<int64_t> sj_vals[2]; DBuf<uint32_t> sj_hist, sj_sums; DBuf<char> sj_text;
+    unsigned long long *d_sj_stat = nullptr, *h_sj_stat = nullptr;        // SJ_ST_* words: device / page-locked copy
+    hipEvent_t ev_sj[3] = {nullptr, nullptr, nullptr};                     // [0], [1]: device time of dg_sj_finish; [2]: the source stream's place for dg_sj_merge
+    bool sj_batch_counted = false, sj_fin_valid = false; size_t sj_fin_entries = 0, sj_fin_bytes = 0;
     size_t env_bam_first_cap = 0;      // DG_BAM_FIRST_CAP: test hook, the first size of the record buffer in bytes
     size_t env_sam_first_cap = 0;      // DG_SAM_TEXT_FIRST_CAP: test hook, the first size of the text buffer in bytes (forces the "text outgrew the guess" path)
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
@@ -624,6 +633,12 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->d_bam_stat) (void)hipFree(c->d_bam_stat);
     if (c->h_bam_stat) (void)hipHostFree(c->h_bam_stat);
     for (hipEvent_t e : c->ev_bam) if (e) (void)hipEventDestroy(e);
+    if (c->sj_tab) (void)hipFree(c->sj_tab);
+    c->sj_ovf[0].release(); c->sj_ovf[1].release(); c->sj_in.release(); c->sj_entries.release(); c->sj_keys[0].release(); c->sj_keys[1].release(); c->sj_vals[0].release(); c->sj_vals[1].release();
+    c->sj_line_off.release(); c->sj_tile.release(); c->sj_hist.release(); c->sj_sums.release(); c->sj_text.release();
+    if (c->d_sj_stat) (void)hipFree(c->d_sj_stat);
+    if (c->h_sj_stat) (void)hipHostFree(c->h_sj_stat);
+    for (hipEvent_t e : c->ev_sj) if (e) (void)hipEventDestroy(e);
     c->fq_text.release(); c->fq_lines.release(); c->fq_tile_cnt.release(); c->fq_name_at.release(); c->fq_name_len.release(); c->fq_loc.release(); c->fq_hdr_off.release(); c->fq_qual_off.release();
     c->fq_tile_sum.release(); c->fq_hdr.release(); c->fq_qual.release();
     if (c->d_fq_info) (void)hipFree(c->d_fq_info);
@@ -1041,7 +1056,7 @@ static int enqueue_upload(dg_ctx *c, int n_reads, const uint32_t *seq_off, const
         mx = rlen[i] > mx ? rlen[i] : mx;
     }
     if (mx > DG_MAX_RLEN) { snprintf(c->err, 512, "a read is longer than DG_MAX_RLEN (%d)", DG_MAX_RLEN); return DG_ERR_ARG; }
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64));     /* the kernels read up to 24 bytes at a read position in one go */
     HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     if (n_reads) {
@@ -1103,7 +1118,7 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
     if (mx > DG_MAX_RLEN || mx > 16 * W2 || (size_t)n_reads * 16 * W2 > 0xFFFFFFF0ull) { snprintf(c->err, 512, "packed batch: read length %d does not fit %d words (or exceeds DG_MAX_RLEN / 2^32 bases)", mx, W2); return DG_ERR_ARG; }
     if (n_reads && (mx + 15) / 16 != W2) { snprintf(c->err, 512, "packed batch: words_per_read must be ceil(longest read / 16) = %d", (mx + 15) / 16); return DG_ERR_ARG; }
     const size_t nw = (size_t)n_reads * W2, bytes = nw * 16;
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64)); HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     HIPCHK(c->enc.ensure(2 * nw + 16)); HIPCHK(c->packed_in.ensure(nw + 1)); HIPCHK(c->nlist_in.ensure(n_n + 1));
     c->enc_ready = true;
@@ -1138,7 +1153,7 @@ extern "C" int dg_batch_upload_fastq(dg_ctx *c, const dg_fastq_text *in, int *n_
     if (!c) return DG_ERR_ARG;
     if (n_reads_out) *n_reads_out = 0;
     // whatever happens below, the context holds no batch until this call has succeeded
-    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
+    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
     c->fq_hdr_bytes = c->fq_qual_bytes = 0; c->fq_ms = 0.f;
     if (!in) { snprintf(c->err, 512, "dg_batch_upload_fastq: the input is NULL"); return DG_ERR_ARG; }
     const size_t n1 = in->text1 ? in->n1 : 0, n2 = in->text2 ? in->n2 : 0;
@@ -1664,7 +1679,7 @@ extern "C" int dg_batch_run(dg_ctx *c, size_t used[3])
     memset(c->counters, 0, sizeof c->counters);
     if (used) used[0] = used[1] = used[2] = 0;
     c->n_t = 0;
-    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sam_valid = false; c->bam_valid = false;
+    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false;
     if (c->n_reads == 0) { c->batch_done = true; return DG_OK; }
     c->attempt_no = 0;
     int rc = enqueue_run(c);
@@ -1780,11 +1795,12 @@ extern "C" int dg_map_batch_compact(dg_ctx *c, int n_reads, const uint32_t *seq_
 static int ensure_full_records(dg_ctx *c)
 {
     if (c->full_valid || c->n_reads == 0) return DG_OK;
-    const bool keep = c->want_full;
+    const bool keep = c->want_full, counted = c->sj_batch_counted;
     c->want_full = true;
     size_t used[3];
     const int rc = dg_batch_run(c, used);
     c->want_full = keep;
+    c->sj_batch_counted = counted;      // (the same batch, mapped again: its tuples are in the junction table already if they were before)
     return rc;
 }
 
@@ -1876,6 +1892,8 @@ extern "C" int dg_set_chr_names(dg_ctx *c, int n_chr, const uint32_t *name_off, 
     // lock every kernel that may read the old arrays is already in a stream: the device is waited for, then they are freed.
     if (sh->d_chr_name_off) { (void)hipDeviceSynchronize(); (void)hipFree(sh->d_chr_name_off); (void)hipFree(sh->d_chr_names); }
     sh->d_chr_name_off = d_off; sh->d_chr_names = d_names; sh->chr_names_set = true; sh->chr_names_gen++;
+    sh->chr_name_max = 0;
+    for (int i = 0; i < n_chr; i++) sh->chr_name_max = std::max(sh->chr_name_max, off[i + 1] - off[i]);
     return DG_OK;
 }
 
@@ -2240,6 +2258,282 @@ extern "C" int dg_bgzf_granules(int out[2])
 {
     if (!out) return DG_ERR_ARG;
     out[0] = (int)BGZF_STRIP; out[1] = (int)BGZF_SEG;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the splice-junction table on the device (dg_sjtab.h): count per batch, sort and print at the end of the job
+// ------------------------------------------------------------------------------------------
+static int sj_state(dg_ctx *c)
+{
+    if (c->d_sj_stat) return DG_OK;
+    HIPCHK(hipMalloc((void **)&c->d_sj_stat, SJ_ST_WORDS * 8));
+    HIPCHK(hipMemset(c->d_sj_stat, 0, SJ_ST_WORDS * 8));
+    HIPCHK(hipHostMalloc((void **)&c->h_sj_stat, SJ_ST_WORDS * 8, hipHostMallocDefault));
+    memset(c->h_sj_stat, 0, SJ_ST_WORDS * 8);
+    for (hipEvent_t &e : c->ev_sj) HIPCHK(hipEventCreate(&e));
+    return DG_OK;
+}
+static size_t sj_round_slots(size_t slots)
+{
+    size_t s = SJ_MIN_SLOTS;
+    while (s < slots && s < ((size_t)1 << 40)) s <<= 1;
+    return s;
+}
+// an empty table of `slots` (a power of two) in place of the context's; the old one is handed back through *old (the caller frees it) or freed here
+static int sj_new_table(dg_ctx *c, size_t slots, SjSlot **old)
+{
+    SjSlot *t = nullptr;
+    HIPCHK(hipMalloc((void **)&t, slots * sizeof(SjSlot)));
+    const hipError_t e = hipMemsetAsync(t, 0, slots * sizeof(SjSlot), c->stream);
+    if (e != hipSuccess) { (void)hipFree(t); return fail(c, DG_ERR_HIP, "hipMemsetAsync (junction table)", e); }
+    if (old) *old = c->sj_tab;
+    else if (c->sj_tab) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->sj_tab); }
+    c->sj_tab = t; c->sj_slots = slots;
+    return DG_OK;
+}
+static int sj_ready(dg_ctx *c)
+{
+    HIPCHK(hipSetDevice(c->device));
+    { const int rc = sj_state(c); if (rc) return rc; }
+    c->sj_fin_valid = false;
+    if (!c->sj_tab) return sj_new_table(c, SJ_FIRST_SLOTS, nullptr);
+    return DG_OK;
+}
+static void sj_launch_insert(dg_ctx *c, const void *src, size_t n, int kind, DBuf<dg_sj_entry> &ovf)
+{
+    if (!n) return;
+    k_sj_insert<<<(unsigned)((n + SJ_THREADS - 1) / SJ_THREADS), SJ_THREADS, 0, c->stream>>>((const unsigned char *)src, (unsigned long long)n, kind, c->sj_tab,
+                                                                                          (unsigned long long)(c->sj_slots - 1), ovf.p, (unsigned long long)ovf.cap, c->d_sj_stat);
+}
+// Items in device memory (on this context's stream, or ordered before it) into the table: one insert pass, one wait; then, while an item found no slot or more
+// than half the slots hold a key, a table of twice the size takes the old slots with their counts and ONLY the items of the overflow list, so every item is
+// counted exactly once -- a pass is never run again whole.
+static int sj_insert(dg_ctx *c, const void *src, size_t n, int kind)
+{
+    if (n >= 0xFFFFFF00ull * SJ_THREADS) { snprintf(c->err, 512, "junction table: too many items in one call"); return DG_ERR_ARG; }
+    int cur = c->sj_ovf_cur;
+    HIPCHK(c->sj_ovf[cur].ensure(n));                             // the overflow list: a bump pointer with room for every item of the pass
+    HIPCHK(hipMemsetAsync(c->d_sj_stat + SJ_ST_OVERFLOW, 0, 8, c->stream));
+    sj_launch_insert(c, src, n, kind, c->sj_ovf[cur]);
+    HIPCHK(hipGetLastError());
+    for (int round = 0; ; round++) {
+        HIPCHK(hipMemcpyAsync(c->h_sj_stat, c->d_sj_stat, 3 * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(wait_stream(c));
+        const size_t n_ovf = (size_t)c->h_sj_stat[SJ_ST_OVERFLOW];
+        c->sj_distinct = (size_t)c->h_sj_stat[SJ_ST_DISTINCT];
+        if (n_ovf > c->sj_ovf[cur].cap) { snprintf(c->err, 512, "junction table: the overflow list outgrew its capacity (%zu of %zu)", n_ovf, c->sj_ovf[cur].cap); return DG_ERR_INTERNAL; }
+        if (n_ovf == 0 && c->sj_distinct <= c->sj_slots / 2) break;
+        if (round >= 40 || c->sj_slots >= ((size_t)1 << 40)) { snprintf(c->err, 512, "junction table: growth did not converge at %zu slots", c->sj_slots); return DG_ERR_INTERNAL; }
+        const int nxt = cur ^ 1;
+        const size_t old_slots = c->sj_slots, old_keys = c->sj_distinct;
+        HIPCHK(c->sj_ovf[nxt].ensure(old_keys + n_ovf));
+        SjSlot *old = nullptr;
+        { const int rc = sj_new_table(c, old_slots * 2, &old); if (rc) return rc; }
+        hipError_t e = hipMemsetAsync(c->d_sj_stat, 0, 2 * 8, c->stream);        // the overflow and the distinct counts: the new table counts its keys itself
+        if (e == hipSuccess) {
+            sj_launch_insert(c, old, old_slots, SJ_SRC_SLOTS, c->sj_ovf[nxt]);
+            sj_launch_insert(c, c->sj_ovf[cur].p, n_ovf, SJ_SRC_ENTRIES, c->sj_ovf[nxt]);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        (void)hipFree(old);
+        if (e != hipSuccess) return fail(c, DG_ERR_HIP, "junction table growth", e);
+        cur = nxt; c->sj_ovf_cur = cur;
+    }
+    return DG_OK;
+}
+// an insert pass may have met a coordinate the table cannot hold (INT64_MIN): said once the pass is over, the other items are counted
+static int sj_refused(dg_ctx *c, const char *fn)
+{
+    const size_t bad = (size_t)c->h_sj_stat[SJ_ST_REFUSED];
+    if (!bad) return DG_OK;
+    (void)hipMemsetAsync(c->d_sj_stat + SJ_ST_REFUSED, 0, 8, c->stream);
+    snprintf(c->err, 512, "%s: %zu tuples hold the coordinate INT64_MIN, which the table does not store; the others were counted", fn, bad);
+    return DG_ERR_RANGE;
+}
+
+extern "C" int dg_sj_granules(int out[2])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = SJ_THREADS; out[1] = SJ_MIN_SLOTS;
+    return DG_OK;
+}
+
+extern "C" int dg_sj_reserve(dg_ctx *c, size_t slots)
+{
+    if (!c) return DG_ERR_ARG;
+    if (c->sj_distinct) { snprintf(c->err, 512, "dg_sj_reserve: the table holds %zu keys (dg_sj_reset first)", c->sj_distinct); return DG_ERR_ARG; }
+    if (slots > ((size_t)1 << 36)) { snprintf(c->err, 512, "dg_sj_reserve: %zu slots are more than the table takes", slots); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    { const int rc = sj_state(c); if (rc) return rc; }
+    c->sj_fin_valid = false;
+    return sj_new_table(c, sj_round_slots(slots), nullptr);
+}
+
+extern "C" int dg_sj_reset(dg_ctx *c)
+{
+    if (!c) return DG_ERR_ARG;
+    { const int rc = sj_ready(c); if (rc) return rc; }
+    HIPCHK(hipMemsetAsync(c->sj_tab, 0, c->sj_slots * sizeof(SjSlot), c->stream));
+    HIPCHK(hipMemsetAsync(c->d_sj_stat, 0, SJ_ST_WORDS * 8, c->stream));
+    HIPCHK(wait_stream(c));
+    c->sj_distinct = 0;
+    return DG_OK;
+}
+
+extern "C" int dg_batch_accumulate_sj(dg_ctx *c, size_t *n_tuples)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_tuples) *n_tuples = 0;
+    if (!c->batch_done) { snprintf(c->err, 512, "dg_batch_accumulate_sj: the context has no finished batch (upload and run one first)"); return DG_ERR_ARG; }
+    if (c->sj_batch_counted) { snprintf(c->err, 512, "dg_batch_accumulate_sj: the tuples of this batch are in the table already (a batch is counted once)"); return DG_ERR_ARG; }
+    { const int rc = sj_ready(c); if (rc) return rc; }
+    const size_t n = c->n_reads ? c->used[2] : 0;
+    if (n) { const int rc = sj_insert(c, c->sjfinal.p, n, SJ_SRC_TUPLES); if (rc) return rc; }
+    c->sj_batch_counted = true;
+    if (n_tuples) *n_tuples = n;
+    return n ? sj_refused(c, "dg_batch_accumulate_sj") : DG_OK;
+}
+
+extern "C" int dg_sj_add(dg_ctx *c, const dg_sj_entry *entries, size_t n)
+{
+    if (!c || (n && !entries)) return DG_ERR_ARG;
+    for (size_t i = 0; i < n; i++)
+        if (entries[i].count && !sj_key_ok(entries[i].g1, entries[i].g2)) { snprintf(c->err, 512, "dg_sj_add: entry %zu holds the coordinate INT64_MIN, which the table does not store", i); return DG_ERR_ARG; }
+    { const int rc = sj_ready(c); if (rc) return rc; }
+    if (!n) return DG_OK;
+    HIPCHK(c->sj_in.ensure(n));
+    HIPCHK(hipMemcpyAsync(c->sj_in.p, entries, n * sizeof(dg_sj_entry), hipMemcpyHostToDevice, c->stream));
+    return sj_insert(c, c->sj_in.p, n, SJ_SRC_ENTRIES);
+}
+
+extern "C" int dg_sj_merge(dg_ctx *dst, dg_ctx *src)
+{
+    dg_ctx *c = dst;
+    if (!dst || !src) return DG_ERR_ARG;
+    if (dst == src || dst->device != src->device) { snprintf(c->err, 512, "dg_sj_merge: the two contexts must differ and be on one device"); return DG_ERR_ARG; }
+    { const int rc = sj_ready(dst); if (rc) return rc; }
+    src->sj_fin_valid = false;
+    if (!src->sj_tab || !src->sj_distinct) return DG_OK;
+    { const int rc = sj_state(src); if (rc) { snprintf(c->err, 512, "%s", src->err); return rc; } }
+    // behind everything the source's stream holds; the source's table is emptied on the destination's stream, which the call waits for
+    HIPCHK(hipEventRecord(src->ev_sj[2], src->stream));
+    HIPCHK(hipStreamWaitEvent(dst->stream, src->ev_sj[2], 0));
+    const int rc = sj_insert(dst, src->sj_tab, src->sj_slots, SJ_SRC_SLOTS);
+    if (rc) return rc;
+    HIPCHK(hipMemsetAsync(src->sj_tab, 0, src->sj_slots * sizeof(SjSlot), dst->stream));
+    HIPCHK(hipMemsetAsync(src->d_sj_stat, 0, SJ_ST_WORDS * 8, dst->stream));
+    HIPCHK(wait_stream(dst));
+    src->sj_distinct = 0;
+    return DG_OK;
+}
+
+// stable LSD radix sort (dg_sort.h) of n pairs by the low `bits` bits of the key, on the context's stream; which = the buffer that holds the input, and on
+// return the one that holds the result
+static int sj_sort(dg_ctx *c, uint32_t n, int bits, int &which)
+{
+    const uint32_t tiles = (n + RS_TILE - 1) / RS_TILE, m = 16u * tiles, scan_tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
+    HIPCHK(c->sj_hist.ensure((size_t)m + 1)); HIPCHK(c->sj_sums.ensure((size_t)scan_tiles + 1));
+    for (int shift = 0; shift < bits; shift += 4) {
+        const int o = which ^ 1;
+        k_rs_hist<<<tiles, 256, 0, c->stream>>>(c->sj_keys[which].p, n, shift, tiles, c->sj_hist.p);
+        k_scan_tiles<<<scan_tiles, 256, 0, c->stream>>>(c->sj_hist.p, c->sj_hist.p, c->sj_sums.p, m);
+        k_scan_top<<<1, 256, 0, c->stream>>>(c->sj_sums.p, scan_tiles, c->sj_hist.p + m, nullptr, 0, nullptr, 0);
+        k_scan_add<<<(m + 255) / 256, 256, 0, c->stream>>>(c->sj_hist.p, c->sj_sums.p, m);
+        k_rs_scatter<<<tiles, 256, 0, c->stream>>>(c->sj_keys[which].p, c->sj_vals[which].p, c->sj_keys[o].p, c->sj_vals[o].p, n, shift, tiles, c->sj_hist.p);
+        HIPCHK(hipGetLastError());
+        which = o;
+    }
+    return DG_OK;
+}
+
+extern "C" int dg_sj_finish(dg_ctx *c, uint32_t flags, size_t *n_entries, size_t *n_lines, size_t *n_bytes, float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_entries) *n_entries = 0;
+    if (n_lines) *n_lines = 0;
+    if (n_bytes) *n_bytes = 0;
+    if (device_ms) *device_ms = 0.f;
+    const bool text = !(flags & DG_SJ_ENTRIES_ONLY);
+    IndexShared *sh = c->shared_ix;
+    c->sj_fin_valid = false;
+    if (text && (!sh || !sh->chr_names_set)) { snprintf(c->err, 512, "dg_sj_finish: the chromosome names are missing (dg_set_chr_names), and DG_SJ_ENTRIES_ONLY is not set"); return DG_ERR_ARG; }
+    { const int rc = sj_ready(c); if (rc) return rc; }
+    c->sj_fin_entries = 0; c->sj_fin_bytes = 0;
+    if (!c->sj_distinct) { c->sj_fin_valid = true; return DG_OK; }
+    if (c->sj_distinct >= 0xFFFFF000ull) { snprintf(c->err, 512, "dg_sj_finish: %zu entries are more than the sorter takes", c->sj_distinct); return DG_ERR_ARG; }
+    const size_t cap = c->sj_distinct;
+    for (int k = 0; k < 2; k++) { HIPCHK(c->sj_keys[k].ensure(cap)); HIPCHK(c->sj_vals[k].ensure(cap)); }
+    HIPCHK(c->sj_entries.ensure(cap)); HIPCHK(c->sj_line_off.ensure(cap));
+    const uint32_t n_tiles = (uint32_t)((cap + SJ_THREADS - 1) / SJ_THREADS);
+    HIPCHK(c->sj_tile.ensure(n_tiles));
+    HIPCHK(hipEventRecord(c->ev_sj[0], c->stream));
+    HIPCHK(hipMemsetAsync(c->d_sj_stat + SJ_ST_ENTRIES, 0, (SJ_ST_WORDS - SJ_ST_ENTRIES) * 8, c->stream));
+    k_sj_compact<<<(unsigned)((c->sj_slots + SJ_THREADS - 1) / SJ_THREADS), SJ_THREADS, 0, c->stream>>>(c->sj_tab, (unsigned long long)c->sj_slots, (unsigned long long)cap, c->sj_keys[0].p, c->sj_vals[0].p, c->d_sj_stat);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_sj_stat, c->d_sj_stat, SJ_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the first wait: how many entries, and which digits their keys differ in
+    const size_t n = (size_t)c->h_sj_stat[SJ_ST_ENTRIES];
+    if (n != cap) { snprintf(c->err, 512, "dg_sj_finish: the table holds %zu filled slots, %zu keys were counted", n, cap); return DG_ERR_INTERNAL; }
+    const int bits1 = sj_key_bits(~c->h_sj_stat[SJ_ST_NMIN1], c->h_sj_stat[SJ_ST_MAX1]), bits2 = sj_key_bits(~c->h_sj_stat[SJ_ST_NMIN2], c->h_sj_stat[SJ_ST_MAX2]);
+    int which = 0;
+    { const int rc = sj_sort(c, (uint32_t)n, bits2, which); if (rc) return rc; }
+    k_sj_gather<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->sj_tab, c->sj_vals[which].p, (uint32_t)n, c->sj_keys[which].p);
+    { const int rc = sj_sort(c, (uint32_t)n, bits1, which); if (rc) return rc; }
+    SjPrint pr; pr.loc_key = c->ix.loc_key; pr.loc_chr = c->ix.loc_chr; pr.chr_off = c->ix.chr_off; pr.n2 = 2 * c->ix.n_chr; pr.name_off = nullptr; pr.names = nullptr;
+    size_t text_cap = 0;
+    {   // the chromosome names are read and the kernels that use them enqueued under the index's lock (as the SAM formatter does: dg_set_chr_names waits for the device before it frees them)
+        std::unique_lock<std::mutex> lk;
+        if (text) {
+            lk = std::unique_lock<std::mutex>(sh->mu);
+            pr.name_off = sh->d_chr_name_off; pr.names = sh->d_chr_names;
+            text_cap = n * ((size_t)sh->chr_name_max + 3 * 21 + 4);      // a name, three numbers of at most 20 characters and a sign, three tabs and the line end
+            HIPCHK(c->sj_text.ensure(text_cap));
+        }
+        k_sj_entries<<<n_tiles, SJ_THREADS, 0, c->stream>>>(c->sj_tab, c->sj_vals[which].p, (uint32_t)n, pr, c->sj_entries.p, c->sj_line_off.p, c->sj_tile.p, c->d_sj_stat);
+        if (text) {
+            k_sam_top<<<1, 256, 0, c->stream>>>(c->sj_tile.p, n_tiles, c->d_sj_stat + SJ_ST_BYTES);
+            k_sj_write<<<n_tiles, SJ_THREADS, 0, c->stream>>>(c->sj_entries.p, (uint32_t)n, pr, c->sj_line_off.p, c->sj_tile.p, c->d_sj_stat, (unsigned long long)c->sj_text.cap, c->sj_text.p);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev_sj[1], c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(c->h_sj_stat, c->d_sj_stat, SJ_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the second wait: lines and bytes
+    const size_t bytes = text ? (size_t)c->h_sj_stat[SJ_ST_BYTES] : 0;
+    if (bytes > c->sj_text.cap) { snprintf(c->err, 512, "dg_sj_finish: the text needs %zu bytes, the bound was %zu", bytes, c->sj_text.cap); return DG_ERR_INTERNAL; }
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->ev_sj[0], c->ev_sj[1]);
+    c->sj_fin_entries = n; c->sj_fin_bytes = bytes; c->sj_fin_valid = true;
+    if (n_entries) *n_entries = n;
+    if (n_lines) *n_lines = (size_t)c->h_sj_stat[SJ_ST_LINES];
+    if (n_bytes) *n_bytes = bytes;
+    if (device_ms) *device_ms = ms;
+    return DG_OK;
+}
+
+extern "C" int dg_sj_download(dg_ctx *c, dg_sj_entry *entries, size_t cap_entries, char *text, size_t cap_text)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->sj_fin_valid) { snprintf(c->err, 512, "dg_sj_download: no finished table (dg_sj_finish first)"); return DG_ERR_ARG; }
+    if ((entries && cap_entries < c->sj_fin_entries) || (text && cap_text < c->sj_fin_bytes)) {
+        snprintf(c->err, 512, "dg_sj_download: output capacity too small: %zu entries and %zu bytes of text are needed", c->sj_fin_entries, c->sj_fin_bytes);
+        return DG_ERR_CAPACITY;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (entries && c->sj_fin_entries) HIPCHK(hipMemcpyAsync(entries, c->sj_entries.p, c->sj_fin_entries * sizeof(dg_sj_entry), hipMemcpyDeviceToHost, c->stream));
+    if (text && c->sj_fin_bytes) HIPCHK(hipMemcpyAsync(text, c->sj_text.p, c->sj_fin_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_sj_device(dg_ctx *c, void **entries, void **text)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->sj_fin_valid) { snprintf(c->err, 512, "dg_sj_device: no finished table (dg_sj_finish first)"); return DG_ERR_ARG; }
+    if (entries) *entries = c->sj_fin_entries ? c->sj_entries.p : nullptr;
+    if (text) *text = c->sj_fin_bytes ? c->sj_text.p : nullptr;
     return DG_OK;
 }
 

@@ -678,7 +678,11 @@ int main(int argc, char *argv[])
     // DART_DEVICE_FASTQ=1: the parallel pipeline hands its batches to the GPU as FASTQ text (dg_batch_upload_fastq); the streaming pipeline and -bo ignore it
     g_device_fastq = !bam_streams && getenv("DART_DEVICE_FASTQ") && atoi(getenv("DART_DEVICE_FASTQ")) != 0;
     g_device_bam = device_bam;
-    if (device_sam || device_bam) {
+    // DART_DEVICE_SJ=1: the junction table is counted, sorted and printed on the device (dg_batch_accumulate_sj per batch, dg_sj_merge / dg_sj_finish at the end);
+    // works in both pipelines, with -o and -bo alike.  Without the switch the ordered writer fills a std::map, as always.
+    const bool device_sj = getenv("DART_DEVICE_SJ") && atoi(getenv("DART_DEVICE_SJ")) != 0;
+    g_device_sj = device_sj;
+    if (device_sam || device_bam || device_sj) {
         std::vector<uint32_t> noff{0}; std::string nflat;
         for (const std::string &nm : ix.names) { nflat += nm; noff.push_back((uint32_t)nflat.size()); }
         for (dg_ctx *r : roots) if (dg_set_chr_names(r, (int)ix.names.size(), noff.data(), nflat.data())) { fprintf(stderr, "Error! %s\n", dg_last_error(r)); return 1; }
@@ -810,25 +814,28 @@ int main(int argc, char *argv[])
             }
             b.ro.reset(new dg_read_out[n]); b.n_reads = (size_t)n;
             size_t caps[3] = { (size_t)n * 4 + 1024, (size_t)n * 16 + 4096, (size_t)n + 1024 };
+            bool sj_even_counted = false;      // DART_DEVICE_SJ: a batch runs in two parts (pairs, then an odd tail); the first part's tuples are counted once, also when the second part makes the batch run again
             for (int attempt = 0; attempt < 2; attempt++) {
-                b.po.reset(new dg_report_out[caps[0]]); b.cig.reset(new uint32_t[caps[1]]); b.sj.reset(new dg_sj_out[caps[2]]);
+                b.po.reset(new dg_report_out[caps[0]]); b.cig.reset(new uint32_t[caps[1]]); if (!device_sj) b.sj.reset(new dg_sj_out[caps[2]]);
                 size_t used1[3] = {0, 0, 0}, used2[3] = {0, 0, 0};
                 dg_params p = o.p; p.paired = pair_end ? 1 : 0;
                 dg_set_params(c, &p);
                 if (device_sam) { b.outs.assign(1, std::string()); b.cts.assign(1, Counters()); b.t_dev = 0; }
                 int rc = n_even ? dg_map_batch(c, n_even, off.data(), rl.data(), flat.data(), b.ro.get(), b.po.get(), b.cig.get(), b.sj.get(), caps, used1) : 0;
+                if (rc == 0 && n_even && device_sj && !sj_even_counted) { rc = sj_accumulate(c); sj_even_counted = rc == 0; }
                 if (rc == 0 && n_even && device_sam) rc = device_text(b, c, 0, n_even, pair_end ? n_even : 0);
                 if (rc == 0 && b.odd) {
                     p.paired = 0; dg_set_params(c, &p);
                     size_t caps2[3] = { caps[0] - used1[0], caps[1] - used1[1], caps[2] - used1[2] };
                     rc = dg_map_batch(c, b.odd, off.data() + n_even, rl.data() + n_even, flat.data(), b.ro.get() + n_even, b.po.get() + used1[0],
-                                      b.cig.get() + used1[1], b.sj.get() + used1[2], caps2, used2);
+                                      b.cig.get() + used1[1], device_sj ? nullptr : b.sj.get() + used1[2], caps2, used2);
+                    if (rc == 0 && device_sj) rc = sj_accumulate(c);
                     if (rc == 0 && device_sam) rc = device_text(b, c, n_even, b.odd, 0);      // (before the offsets below are rebased: the device holds the batch's own)
                     if (rc == DG_ERR_CAPACITY) for (int q = 0; q < 3; q++) used2[q] += used1[q];
                     else {
                         for (int k = n_even; k < n; k++) { b.ro[k].rep_off += (int32_t)used1[0]; b.ro[k].sj_off += (int32_t)used1[2]; }
                         for (size_t k = 0; k < used2[0]; k++) b.po[used1[0] + k].cigar_off += (uint32_t)used1[1];
-                        for (size_t k = 0; k < used2[2]; k++) b.sj[used1[2] + k].read_idx += n_even;
+                        if (!device_sj) for (size_t k = 0; k < used2[2]; k++) b.sj[used1[2] + k].read_idx += n_even;
                     }
                 }
                 if (rc == DG_ERR_CAPACITY && attempt == 0) {       // `used` holds the need: grow once and repeat
@@ -902,7 +909,11 @@ int main(int argc, char *argv[])
                 total.unique += b->cts[t2].unique; total.unmapped += b->cts[t2].unmapped; total.paired += b->cts[t2].paired;
             }
             total.total += (long long)n;
-            for (size_t k = 0; k < b->used[2]; k++) sjmap[std::make_pair(b->sj[k].g1, b->sj[k].g2)]++;   // UpdateLocal/GlobalSJMap, Mapping.cpp:532-577
+            if (!device_sj) {
+                const unsigned long long tj = sj_now_ns();
+                for (size_t k = 0; k < b->used[2]; k++) sjmap[std::make_pair(b->sj[k].g1, b->sj[k].g2)]++;   // UpdateLocal/GlobalSJMap, Mapping.cpp:532-577
+                g_sj_map_ns += sj_now_ns() - tj; g_sj_tuples += b->used[2];
+            }
             if (!o.silent) { fprintf(stdout, "\r%lld %s tags have been processed in %lld seconds...", total.total, pair_end ? "paired-end" : "singled-end", (long long)(time(NULL) - t0)); fflush(stdout); }
             t_write += now() - t;
             next_out++;
@@ -923,6 +934,25 @@ int main(int argc, char *argv[])
     if (!o.silent) fprintf(stdout, "\rAll the %lld %s reads have been processed in %lld seconds.\n", total.total, pair_end ? "paired-end" : "single-end", (long long)(time(NULL) - t0));
     if (o.bam) { if (!bam.close()) { fprintf(stderr, "Error while writing %s\n", o.out); return 1; } }
     else fclose(sam);
+    // DART_DEVICE_SJ: the clones' tables into their root's, further roots' into the first (downloaded entries, counted again there), then the table is sorted,
+    // mapped to chromosomes and printed on the device: the text is junctions.tab
+    std::string sj_text; size_t sj_entries = 0, sj_lines = 0; float sj_finish_ms = 0.f;
+    if (device_sj) {
+        auto sj_fail = [&](dg_ctx *c) { fprintf(stderr, "\nError! junction table: %s\n", dg_last_error(c)); return 1; };
+        for (size_t d = 0; d < roots.size(); d++)
+            for (int k = 1; k < inflight_cfg; k++) if (dg_sj_merge(roots[d], ctx[d * (size_t)inflight_cfg + k])) return sj_fail(roots[d]);
+        for (size_t d = 1; d < roots.size(); d++) {
+            size_t ne = 0;
+            if (dg_sj_finish(roots[d], DG_SJ_ENTRIES_ONLY, &ne, nullptr, nullptr, nullptr)) return sj_fail(roots[d]);
+            std::vector<dg_sj_entry> ent(ne ? ne : 1);
+            if (dg_sj_download(roots[d], ent.data(), ne, nullptr, 0)) return sj_fail(roots[d]);
+            if (dg_sj_add(roots[0], ent.data(), ne)) return sj_fail(roots[0]);
+        }
+        size_t nb = 0;
+        if (dg_sj_finish(roots[0], 0, &sj_entries, &sj_lines, &nb, &sj_finish_ms)) return sj_fail(roots[0]);
+        sj_text.resize(nb);
+        if (dg_sj_download(roots[0], nullptr, 0, nb ? &sj_text[0] : nullptr, nb)) return sj_fail(roots[0]);
+    }
     for (auto c : clones) dg_destroy(c);
     for (auto c : roots) dg_destroy(c);
 
@@ -939,7 +969,8 @@ int main(int argc, char *argv[])
         const int nc = (int)ix.names.size();
         std::vector<int64_t> key(2 * nc); std::vector<int> who(2 * nc);
         for (int i = 0; i < nc; i++) { key[i] = ix.off[i] + ix.len[i] - 1; who[i] = i; key[2 * nc - 1 - i] = 2 * ix.l_pac - ix.off[i] - 1; who[2 * nc - 1 - i] = i; }
-        for (auto &kv : sjmap) {
+        if (device_sj) { if (jf) fwrite(sj_text.data(), 1, sj_text.size(), jf); nj = (int)sj_lines; }
+        else for (auto &kv : sjmap) {
             const int lo = (int)(std::lower_bound(key.begin(), key.end(), kv.first.first) - key.begin());
             if (lo >= 2 * nc) continue;
             const int c = who[lo];
@@ -949,6 +980,10 @@ int main(int argc, char *argv[])
         if (jf) fclose(jf);
         fprintf(stdout, "\t# of splice junctions = %d (file: %s)\n", nj, o.sj);
         fprintf(stdout, "\tAlignment output: %s\n\n", o.out);
+    }
+    if (getenv("DART_TIMING")) {
+        if (device_sj) fprintf(stderr, "[dart sj] table=device tuples=%llu entries=%zu accumulate_ms=%.3f finish_ms=%.3f\n", (unsigned long long)g_sj_tuples.load(), sj_entries, g_sj_acc_ns.load() * 1e-6, (double)sj_finish_ms);
+        else fprintf(stderr, "[dart sj] table=host tuples=%llu entries=%zu map_s=%.6f\n", (unsigned long long)g_sj_tuples.load(), sjmap.size(), g_sj_map_ns.load() * 1e-9);
     }
     return 0;
 }

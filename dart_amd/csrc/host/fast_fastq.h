@@ -345,6 +345,21 @@ static bool g_device_fastq = false;
 // behind its mapping; the slot holds whole BGZF blocks and the ordered writer hands them to g_bam_sink (BamWriter::add_bgzf_blocks) instead of writing text to fd.
 static bool g_device_bam = false;
 static std::function<bool(const char *blocks, size_t n, long long records, long long refused)> g_bam_sink;
+// DART_DEVICE_SJ=1: every mapping thread counts its batch's junction tuples in its context's table on the GPU (dg_batch_accumulate_sj) right behind the mapping;
+// the tuples are not downloaded and the ordered writer's map loop does not run.  The host program merges the tables and prints junctions.tab from the device's
+// text at the end of the job.  The three figures below feed its `[dart sj]` line: tuples seen, time in the accumulate calls, time in the writer's map loop.
+static bool g_device_sj = false;
+static std::atomic<unsigned long long> g_sj_tuples{0}, g_sj_acc_ns{0}, g_sj_map_ns{0};
+static inline unsigned long long sj_now_ns() { return (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// the tuples of the batch that ctx has just mapped into its table
+static inline int sj_accumulate(dg_ctx *ctx)
+{
+    const unsigned long long t = sj_now_ns();
+    size_t n = 0;
+    const int rc = dg_batch_accumulate_sj(ctx, &n);
+    g_sj_acc_ns += sj_now_ns() - t; g_sj_tuples += n;
+    return rc;
+}
 
 struct FastSlot {                       // one batch travelling through the stages
     size_t first = 0; int n = 0, odd = 0; size_t seqno = 0;
@@ -649,7 +664,8 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                         const size_t need[3] = { s->used[0] + s->used[0] / 8 + 1024, s->used[1] + s->used[1] / 8 + 1024, s->used[2] + s->used[2] / 8 + 1024 };
                         slot_reserve(*s, (size_t)n, 0, need);
                     }
-                    if (!rc) rc = dg_batch_download(ctx[w], s->ro, s->po, s->cig, s->sj, s->caps);
+                    if (!rc && g_device_sj) rc = sj_accumulate(ctx[w]);
+                    if (!rc) rc = dg_batch_download(ctx[w], s->ro, s->po, s->cig, g_device_sj ? nullptr : s->sj, s->caps);
                     s->rc = rc; if (rc) s->err = dg_last_error(ctx[w]);
                 }
             } else
@@ -659,8 +675,9 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                     if (attempt) { const size_t need[3] = { s->used[0] * 2 + 1024, s->used[1] * 2 + 1024, s->used[2] * 2 + 1024 }; slot_reserve(*s, (size_t)n, 0, need); }
                     dg_params p = base_params; p.paired = (pair_end && !s->odd) ? 1 : 0;
                     dg_set_params(ctx[w], &p);
-                    const int rc = dg_map_batch(ctx[w], n, s->soff.data(), s->rl.data(), s->seq, s->ro, s->po, s->cig, s->sj, s->caps, s->used);
+                    int rc = dg_map_batch(ctx[w], n, s->soff.data(), s->rl.data(), s->seq, s->ro, s->po, s->cig, g_device_sj ? nullptr : s->sj, s->caps, s->used);
                     if (rc == DG_ERR_CAPACITY && attempt == 0) continue;      // `used` holds the need
+                    if (!rc && g_device_sj) rc = sj_accumulate(ctx[w]);       // (a batch that ran short of capacity is mapped again as a new batch and was not counted)
                     s->rc = rc; if (rc) s->err = dg_last_error(ctx[w]);
                     break;
                 }
@@ -786,7 +803,11 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             if (!g_device_bam) *file_off = base + offs[TF];
             for (int k = 0; k < TF; k++) { total.unique += ts.cts[k].unique; total.unmapped += ts.cts[k].unmapped; total.paired += ts.cts[k].paired; }
             total.total += s->n;
-            for (size_t k = 0; k < s->used[2]; k++) sjmap[std::make_pair(s->sj[k].g1, s->sj[k].g2)]++;   // UpdateLocal/GlobalSJMap, Mapping.cpp:532-577
+            if (!g_device_sj) {
+                const unsigned long long tj = sj_now_ns();
+                for (size_t k = 0; k < s->used[2]; k++) sjmap[std::make_pair(s->sj[k].g1, s->sj[k].g2)]++;   // UpdateLocal/GlobalSJMap, Mapping.cpp:532-577
+                g_sj_map_ns += sj_now_ns() - tj; g_sj_tuples += s->used[2];
+            }
             if (!silent) { fprintf(stdout, "\r%lld %s tags have been processed in %lld seconds...", total.total, pair_end ? "paired-end" : "singled-end", (long long)(time(NULL) - t0)); fflush(stdout); }
             st.t_write += now() - tw;
             { std::lock_guard<std::mutex> lk(mu); ts.full = false; free_q.push_back(s); }

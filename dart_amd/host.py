@@ -36,6 +36,9 @@ READ_C = np.dtype([("score", "<u2"), ("sub_score", "<u2"), ("mis_num", "<u2"), (
 REPORT_C = np.dtype([("pos", "<i4"), ("aln_score", "<u2"), ("flag", "<u2"), ("paired_idx", "<i2"), ("chr", "<u2"), ("n_cigar", "u1"),
                      ("sj_type", "i1"), ("bdir", "u1"), ("pad", "u1")])
 CIGAR_FULL_MATCH = 255
+SJ_ENTRY = np.dtype([("g1", "<i8"), ("g2", "<i8"), ("count", "<u4"), ("chr", "<u4")])      # dg_sj_entry
+SJ_ENTRIES_ONLY = 1
+SJ_NO_CHR = 0xFFFFFFFF
 assert READ_OUT.itemsize == 36 and REPORT_OUT.itemsize == 40 and SJ_OUT.itemsize == 24 and READ_C.itemsize == 12 and REPORT_C.itemsize == 16
 
 
@@ -255,6 +258,16 @@ def _load_lib():
         lib.dg_bgzf_compress.argtypes = [vp, vp, C.c_size_t, vp, vp]
         lib.dg_bgzf_granules.argtypes = [vp]
         lib.dg_batch_bam_device_ms.argtypes = [vp, vp]
+    if hasattr(lib, "dg_sj_finish"):                         # (likewise: the splice-junction table on the device)
+        lib.dg_sj_reserve.argtypes = [vp, C.c_size_t]
+        lib.dg_sj_reset.argtypes = [vp]
+        lib.dg_batch_accumulate_sj.argtypes = [vp, vp]
+        lib.dg_sj_add.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_sj_merge.argtypes = [vp, vp]
+        lib.dg_sj_finish.argtypes = [vp, C.c_uint32, vp, vp, vp, vp]
+        lib.dg_sj_download.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
+        lib.dg_sj_device.argtypes = [vp, vp, vp]
+        lib.dg_sj_granules.argtypes = [vp]
     lib.dg_last_counters.argtypes = [vp, vp, C.c_int]
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
@@ -499,6 +512,51 @@ class DartGPU:
         v = _View()
         v.__cuda_array_interface__ = {"shape": (int(nb.value),), "typestr": "|u1", "data": (int(ptr.value), False), "version": 2}
         return torch.as_tensor(v, device="cuda")
+
+    # ---- the splice-junction table on the device (dg_sj_*): counted per batch, sorted and printed at the end of the job ----
+    def sj_granules(self):
+        """(tuples one workgroup of the insert kernel takes, the smallest table in slots) (dg_sj_granules)"""
+        g = (C.c_int * 2)()
+        self._chk(self.lib.dg_sj_granules(g), "dg_sj_granules")
+        return int(g[0]), int(g[1])
+
+    def sj_reserve(self, slots: int):
+        self._chk(self.lib.dg_sj_reserve(self.ctx, int(slots)), "dg_sj_reserve")
+
+    def sj_reset(self):
+        self._chk(self.lib.dg_sj_reset(self.ctx), "dg_sj_reset")
+
+    def accumulate_sj(self) -> int:
+        """counts the junction tuples of the batch that ran last in the context's table (dg_batch_accumulate_sj) -> the number of tuples"""
+        n = C.c_size_t(0)
+        self._chk(self.lib.dg_batch_accumulate_sj(self.ctx, C.byref(n)), "dg_batch_accumulate_sj")
+        return int(n.value)
+
+    def sj_add(self, entries):
+        """counts host entries with their counts (dg_sj_add): an SJ_ENTRY array, or any sequence of (g1, g2, count)"""
+        if isinstance(entries, np.ndarray) and entries.dtype == SJ_ENTRY:
+            a = np.ascontiguousarray(entries)
+        else:
+            rows = list(entries)
+            a = np.zeros(len(rows), SJ_ENTRY)
+            for k, t in enumerate(rows):
+                a[k]["g1"], a[k]["g2"], a[k]["count"] = int(t[0]), int(t[1]), int(t[2]) if len(t) > 2 else 1
+        keep = a if len(a) else np.zeros(1, SJ_ENTRY)
+        self._chk(self.lib.dg_sj_add(self.ctx, keep.ctypes.data, len(a)), "dg_sj_add")
+
+    def sj_merge(self, src: "DartGPU"):
+        """folds src's table into this context's and leaves src's empty (dg_sj_merge)"""
+        self._chk(self.lib.dg_sj_merge(self.ctx, src.ctx), "dg_sj_merge")
+
+    def sj_finish(self, entries_only: bool = False):
+        """the table sorted, mapped to chromosomes and printed on the device (dg_sj_finish + dg_sj_download) -> (SJ_ENTRY array, the bytes of
+        junctions.tab); self.sj_lines = the reference's "# of splice junctions", self.sj_device_ms = the kernels' device time"""
+        ne = C.c_size_t(0); nl = C.c_size_t(0); nb = C.c_size_t(0); ms = C.c_float(0)
+        self._chk(self.lib.dg_sj_finish(self.ctx, SJ_ENTRIES_ONLY if entries_only else 0, C.byref(ne), C.byref(nl), C.byref(nb), C.byref(ms)), "dg_sj_finish")
+        self.sj_lines, self.sj_device_ms = int(nl.value), float(ms.value)
+        ent = np.zeros(max(int(ne.value), 1), SJ_ENTRY); text = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_sj_download(self.ctx, ent.ctypes.data, int(ne.value), text.ctypes.data, int(nb.value)), "dg_sj_download")
+        return ent[:int(ne.value)], text[:int(nb.value)].tobytes()
 
     def wait_index(self):
         self._chk(self.lib.dg_index_wait(self.ctx), "dg_index_wait")

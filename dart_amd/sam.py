@@ -6,6 +6,8 @@ used by the tests and bench.py to turn records into the reference's bytes.
 """
 from __future__ import annotations
 
+import bisect
+
 import numpy as np
 
 _COMP = {ord(a): b for a, b in zip("ACGTacgt", "TGCATGCA")}
@@ -118,3 +120,34 @@ def junction_table(sj, chr_names, chr_off, chr_len, l_pac: int) -> str:
         c = who[lo]
         out.append("%s\t%d\t%d\t%d\n" % (chr_names[c], g1 + 1 - int(chr_off[c]), g2 + 1 - int(chr_off[c]), keys[(g1, g2)]))
     return "".join(out)
+
+
+SJ_NO_CHR = 0xFFFFFFFF
+
+
+def junction_twin(tuples, chr_names, chr_off, chr_len, l_pac: int):
+    """The reference's junction table from (g1, g2) or (g1, g2, count) tuples in any order -- the twin of the device's table (dg_sj_finish):
+    -> (entries [(g1, g2, count, chr)] in ascending signed (g1, g2) order, chr = SJ_NO_CHR past the last boundary key, the bytes of junctions.tab,
+    the number of lines).  Counts add up per key (UpdateLocal/GlobalSJMap, Mapping.cpp:532-577) and are printed as the reference's int (%d);
+    a count of 0 adds nothing."""
+    keys = {}
+    for t in tuples:
+        g1, g2 = int(t[0]), int(t[1])
+        k = int(t[2]) if len(t) > 2 else 1
+        if k:
+            keys[(g1, g2)] = keys.get((g1, g2), 0) + k
+    n = len(chr_names)
+    loc = [int(chr_off[i]) + int(chr_len[i]) - 1 for i in range(n)] + [2 * int(l_pac) - int(chr_off[i]) - 1 for i in reversed(range(n))]
+    who = list(range(n)) + list(reversed(range(n)))
+    entries, out = [], []
+    for (g1, g2) in sorted(keys):
+        lo = bisect.bisect_left(loc, g1)
+        cnt = keys[(g1, g2)] & 0xFFFFFFFF
+        if lo >= 2 * n:
+            entries.append((g1, g2, cnt, SJ_NO_CHR))
+            continue
+        c = who[lo]
+        entries.append((g1, g2, cnt, c))
+        shown = cnt - (1 << 32) if cnt >= (1 << 31) else cnt
+        out.append("%s\t%d\t%d\t%d\n" % (chr_names[c], g1 + 1 - int(chr_off[c]), g2 + 1 - int(chr_off[c]), shown))
+    return entries, "".join(out).encode("latin1"), len(out)

@@ -293,6 +293,43 @@ int dg_bgzf_compress(dg_ctx *, const void *host_bytes, size_t n, size_t *n_bytes
 int dg_batch_bam_device_ms(dg_ctx *, float ms[2]);
 int dg_bgzf_granules(int out[2]);
 
+/* ---- the splice-junction table on the device: count, sort and print in HBM (replaces UpdateLocalSJMap / UpdateGlobalSJMap, Mapping.cpp:532-577, and
+ * OutputSpliceJunctions, Mapping.cpp:683-716) ----
+ * Every context owns a table (g1, g2) -> count that stays in HBM across batches: an open-addressing hash table keyed by the full 128 bits, grown by the
+ * library.  The same multiset of tuples gives the same entries and the same bytes whatever the order, the batch split, the contexts used or the growth history.
+ * Counts are exact up to 2^31 - 1, the reference's int (the table adds in 32 bits).  The one coordinate the table does not hold is INT64_MIN: dg_sj_add
+ * refuses such an entry (DG_ERR_ARG, nothing added).  Every failure leaves the context usable; dg_destroy frees the table.
+ *   dg_sj_reserve            the table's size in slots, rounded up to a power of two, at least dg_sj_granules [1]; DG_ERR_ARG when the table is not empty
+ *   dg_sj_reset              an empty table; the storage is kept
+ *   dg_batch_accumulate_sj   counts the tuples sjfinal[0 .. used[2]) of the last finished batch (after full or compact records alike): one launch on the
+ *                            context's stream behind the batch, one wait (for the overflow and distinct counts), growth when more than half the slots hold
+ *                            a key or a tuple found no slot.  *n_tuples (may be NULL) = used[2].  A batch is counted once: DG_ERR_ARG, with a text in
+ *                            dg_last_error, for a second call on the same batch and when the context has no finished batch
+ *   dg_sj_add                counts n host entries with their counts (chr is ignored, a count of 0 adds nothing): how a multi-device host folds in the
+ *                            table another device downloaded
+ *   dg_sj_merge              folds src's table into dst's and leaves src empty; both on one device, ordered behind both contexts' streams; DG_ERR_ARG for
+ *                            dst == src or different devices
+ *   dg_sj_finish             the entries in ascending signed (g1, g2) order, each with its chromosome (ChrLocMap.lower_bound(g1), Mapping.cpp:683-695), and
+ *                            the text "name \t g1+1-off \t g2+1-off \t count \n" of every entry that has one -- the bytes of junctions.tab.  *n_lines = the
+ *                            reference's "# of splice junctions".  DG_SJ_ENTRIES_ONLY: no text, *n_bytes = 0; without it the chromosome names must be set
+ *                            (DG_ERR_ARG).  The table stays intact: more batches may follow and dg_sj_finish may be called again.  *device_ms (may be NULL):
+ *                            device time of the kernels, a measurement.  An empty table: 0 entries, 0 lines, 0 bytes.
+ *   dg_sj_download           copies the entries and / or the text of the last dg_sj_finish out (either pointer may be NULL); DG_ERR_CAPACITY, nothing
+ *                            written, the text names the need, when a given buffer is too small
+ *   dg_sj_device             the same two arrays in HBM, valid until the next table call on the context
+ *   dg_sj_granules           [0] the tuples one workgroup of the insert kernel takes, [1] the smallest table in slots                                  */
+typedef struct { int64_t g1, g2; uint32_t count; uint32_t chr /* 0xFFFFFFFF: past the last boundary, no line */; } dg_sj_entry;   /* 24 bytes */
+#define DG_SJ_ENTRIES_ONLY 1u
+int dg_sj_reserve(dg_ctx *, size_t slots);
+int dg_sj_reset(dg_ctx *);
+int dg_batch_accumulate_sj(dg_ctx *, size_t *n_tuples);
+int dg_sj_add(dg_ctx *, const dg_sj_entry *, size_t n);
+int dg_sj_merge(dg_ctx *dst, dg_ctx *src);
+int dg_sj_finish(dg_ctx *, uint32_t flags, size_t *n_entries, size_t *n_lines, size_t *n_bytes, float *device_ms);
+int dg_sj_download(dg_ctx *, dg_sj_entry *entries, size_t cap_entries, char *text, size_t cap_text);
+int dg_sj_device(dg_ctx *, void **entries, void **text);
+int dg_sj_granules(int out[2]);
+
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
 int dg_last_timings(dg_ctx *, const char **names, float *ms, int cap);
