@@ -12,6 +12,7 @@
 #include "dg_samfmt.h"
 #include "dg_bamfmt.h"
 #include "dg_bgzf.h"
+#include "dg_bgzf_dyn.h"
 #include "dg_fastq.h"
 #include "dg_sjtab.h"
 #include <stdio.h>
@@ -2065,8 +2066,9 @@ static int bam_state(dg_ctx *c)
     return DG_OK;
 }
 
-// n bytes in HBM (4-byte aligned, readable up to the next multiple of 4) -> BGZF blocks in c->bgzf_out: three launches and one wait, for the size
-static int bgzf_device(dg_ctx *c, const unsigned char *d_in, size_t n, size_t *n_out, float *ms)
+// n bytes in HBM (4-byte aligned, readable up to the next multiple of 4) -> BGZF blocks in c->bgzf_out: three launches and one wait, for the size;
+// dynamic: Huffman codes per strip (k_bgzf_deflate_dyn) in place of the fixed code
+static int bgzf_device(dg_ctx *c, const unsigned char *d_in, size_t n, bool dynamic, size_t *n_out, float *ms, unsigned long long *d_phases = nullptr)
 {
     *n_out = 0; *ms = 0.f;
     const size_t blocks = (n + BGZF_BLOCK - 1) / BGZF_BLOCK;
@@ -2075,7 +2077,8 @@ static int bgzf_device(dg_ctx *c, const unsigned char *d_in, size_t n, size_t *n
     HIPCHK(c->bgzf_slots.ensure(blocks * BGZF_SLOT)); HIPCHK(c->bgzf_size.ensure(blocks)); HIPCHK(c->bgzf_off.ensure(blocks));
     HIPCHK(c->bgzf_out.ensure(n + (size_t)BGZF_OVERHEAD * blocks));                 // the bound of the stored form: no block is larger
     HIPCHK(hipEventRecord(c->ev_bam[0], c->stream));
-    k_bgzf_deflate<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bgzf_slots.p, c->bgzf_off.p, c->bgzf_size.p);
+    if (dynamic) k_bgzf_deflate_dyn<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bgzf_slots.p, c->bgzf_off.p, c->bgzf_size.p, d_phases);
+    else k_bgzf_deflate<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bgzf_slots.p, c->bgzf_off.p, c->bgzf_size.p);
     k_sam_top<<<1, 256, 0, c->stream>>>(c->bgzf_off.p, (uint32_t)blocks, c->d_bam_stat + 6);
     k_bgzf_copy<<<(unsigned)blocks, 256, 0, c->stream>>>(c->bgzf_slots.p, c->bgzf_off.p, c->bgzf_size.p, c->bgzf_out.p);
     HIPCHK(hipGetLastError());
@@ -2144,7 +2147,7 @@ static int bam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr
     c->bam_ms[0] = ms; c->bam_ms[1] = 0.f;
     if (!(flags & DG_BAM_RAW) && total) {
         float ms_z = 0.f;
-        const int rc = bgzf_device(c, c->bam_rec.p, total, &out_bytes, &ms_z);      // the second wait: for the stream's size
+        const int rc = bgzf_device(c, c->bam_rec.p, total, (flags & DG_BAM_DYNAMIC) != 0, &out_bytes, &ms_z);      // the second wait: for the stream's size
         if (rc) return rc;
         ms += ms_z; c->bam_ms[1] = ms_z;
         c->bam_ptr = c->bgzf_out.p;
@@ -2225,12 +2228,13 @@ extern "C" int dg_batch_device_bam(dg_ctx *c, void **ptr, size_t *n_bytes)
     return DG_OK;
 }
 
-extern "C" int dg_bgzf_compress(dg_ctx *c, const void *host_bytes, size_t n, size_t *n_bytes, float *device_ms)
+extern "C" int dg_bgzf_compress_flags(dg_ctx *c, const void *host_bytes, size_t n, uint32_t flags, size_t *n_bytes, float *device_ms)
 {
     if (!c) return DG_ERR_ARG;
     if (n_bytes) *n_bytes = 0;
     if (device_ms) *device_ms = 0.f;
     c->bam_valid = false; c->bam_bytes = 0; c->bam_ptr = nullptr;
+    if (flags & ~DG_BGZF_DYNAMIC) { snprintf(c->err, 512, "dg_bgzf_compress_flags: unknown flag bits 0x%x", flags & ~DG_BGZF_DYNAMIC); return DG_ERR_ARG; }
     if (n == 0) { c->bam_valid = true; return DG_OK; }
     if (!host_bytes) { snprintf(c->err, 512, "dg_bgzf_compress: the input is NULL"); return DG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
@@ -2238,13 +2242,18 @@ extern "C" int dg_bgzf_compress(dg_ctx *c, const void *host_bytes, size_t n, siz
     HIPCHK(c->bgzf_in.ensure(n + 8));
     HIPCHK(hipMemcpyAsync(c->bgzf_in.p, host_bytes, n, hipMemcpyHostToDevice, c->stream));
     size_t out_bytes = 0; float ms = 0.f;
-    const int rc = bgzf_device(c, c->bgzf_in.p, n, &out_bytes, &ms);
+    const int rc = bgzf_device(c, c->bgzf_in.p, n, (flags & DG_BGZF_DYNAMIC) != 0, &out_bytes, &ms);
     if (rc) return rc;
     c->bam_ptr = c->bgzf_out.p; c->bam_bytes = out_bytes; c->bam_valid = true;
     c->bam_ms[0] = 0.f; c->bam_ms[1] = ms;
     if (n_bytes) *n_bytes = out_bytes;
     if (device_ms) *device_ms = ms;
     return DG_OK;
+}
+
+extern "C" int dg_bgzf_compress(dg_ctx *c, const void *host_bytes, size_t n, size_t *n_bytes, float *device_ms)
+{
+    return dg_bgzf_compress_flags(c, host_bytes, n, 0u, n_bytes, device_ms);
 }
 
 extern "C" int dg_batch_bam_device_ms(dg_ctx *c, float ms[2])
@@ -2853,4 +2862,53 @@ extern "C" int dg_probe_nw(dg_ctx *c, int n, const uint32_t *a_off, const uint32
                            uint32_t *out_off, uint32_t *out_len, char *out_a, char *out_b, size_t cap)
 {
     return dg_probe_nw_mode(c, 0, n, a_off, b_off, a, b, out_off, out_len, out_a, out_b, cap);
+}
+
+// where the dynamic BGZF kernel's time goes: dg_bgzf_compress_flags(DG_BGZF_DYNAMIC) with the kernel's clock sums switched on
+extern "C" int dg_probe_bgzf_phases(dg_ctx *c, const void *host_bytes, size_t n, uint64_t cycles[8], size_t *n_bytes, float *device_ms)
+{
+    if (!c || !host_bytes || !n || !cycles) return DG_ERR_ARG;
+    static_assert(BGZF_PHASES == 8, "dartgpu.h says 8");
+    c->bam_valid = false; c->bam_bytes = 0; c->bam_ptr = nullptr;
+    HIPCHK(hipSetDevice(c->device));
+    { const int rc = bam_state(c); if (rc) return rc; }
+    DevTmp tmp;
+    unsigned long long *d_ph = nullptr;
+    HIPCHK(tmp.alloc((void **)&d_ph, BGZF_PHASES * 8));
+    HIPCHK(hipMemsetAsync(d_ph, 0, BGZF_PHASES * 8, c->stream));
+    HIPCHK(c->bgzf_in.ensure(n + 8));
+    HIPCHK(hipMemcpyAsync(c->bgzf_in.p, host_bytes, n, hipMemcpyHostToDevice, c->stream));
+    size_t out_bytes = 0; float ms = 0.f;
+    const int rc = bgzf_device(c, c->bgzf_in.p, n, true, &out_bytes, &ms, d_ph);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(cycles, d_ph, BGZF_PHASES * 8, hipMemcpyDeviceToHost));
+    c->bam_ptr = c->bgzf_out.p; c->bam_bytes = out_bytes; c->bam_valid = true;
+    c->bam_ms[0] = 0.f; c->bam_ms[1] = ms;
+    if (n_bytes) *n_bytes = out_bytes;
+    if (device_ms) *device_ms = ms;
+    return DG_OK;
+}
+
+// the length builder of the dynamic BGZF coder (dg_bgzf_dyn.h) on a caller's histogram: the one way to its length-limit repair with frequencies a
+// strip never has
+extern "C" int dg_probe_huff_lengths(dg_ctx *c, const uint32_t *freq, int n_sym, int limit, uint8_t *len_out)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!freq || !len_out || n_sym < 1 || n_sym > (int)BGZF_HUFF_MAX_SYM || limit < 1 || limit > 15) { snprintf(c->err, 512, "dg_probe_huff_lengths: 1 to %u symbols, a limit of 1 to 15", BGZF_HUFF_MAX_SYM); return DG_ERR_ARG; }
+    int used = 0;
+    for (int i = 0; i < n_sym; i++) {
+        if (freq[i] > BGZF_HUFF_FREQ_MAX) { snprintf(c->err, 512, "dg_probe_huff_lengths: frequency %d is above %u", i, BGZF_HUFF_FREQ_MAX); return DG_ERR_ARG; }
+        used += freq[i] != 0;
+    }
+    if (used > (1 << limit)) { snprintf(c->err, 512, "dg_probe_huff_lengths: %d used symbols have no code of at most %d bits", used, limit); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    DevTmp tmp;
+    uint32_t *d_freq = nullptr; unsigned char *d_len = nullptr;
+    HIPCHK(tmp.alloc((void **)&d_freq, (size_t)n_sym * 4)); HIPCHK(tmp.alloc((void **)&d_len, (size_t)n_sym));
+    HIPCHK(hipMemcpy(d_freq, freq, (size_t)n_sym * 4, hipMemcpyHostToDevice));
+    k_probe_huff<<<1, BGZF_THREADS, 0, c->stream>>>(d_freq, (uint32_t)n_sym, (uint32_t)limit, d_len);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(len_out, d_len, (size_t)n_sym, hipMemcpyDeviceToHost));
+    return DG_OK;
 }

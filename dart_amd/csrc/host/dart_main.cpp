@@ -554,6 +554,7 @@ int main(int argc, char *argv[])
     // DART_DEVICE_BAM=1 with -bo: plain-FASTQ libraries (and .gz ones inflated whole) take the parallel pipeline, and the BAM records and their BGZF blocks come
     // from the device (dg_batch_format_bam); FASTA and streamed .gz keep the host writer whatever the switch says.  Without the switch -bo is what it always was.
     const bool device_bam = o.bam && getenv("DART_DEVICE_BAM") && atoi(getenv("DART_DEVICE_BAM")) != 0;
+    const bool bgzf_dynamic = device_bam && getenv("DART_BGZF_DYNAMIC") && atoi(getenv("DART_BGZF_DYNAMIC")) != 0;      // (alone it does nothing)
     const bool bam_streams = o.bam && !device_bam;         // -bo forces the streaming pipeline
     FastqIndex pre;                         // the first library's read files are mapped and indexed while the HIP runtime starts, the genome index loads and dg_init_files runs
     bool fast_first = false;
@@ -678,6 +679,7 @@ int main(int argc, char *argv[])
     // DART_DEVICE_FASTQ=1: the parallel pipeline hands its batches to the GPU as FASTQ text (dg_batch_upload_fastq); the streaming pipeline and -bo ignore it
     g_device_fastq = !bam_streams && getenv("DART_DEVICE_FASTQ") && atoi(getenv("DART_DEVICE_FASTQ")) != 0;
     g_device_bam = device_bam;
+    g_bgzf_dynamic = bgzf_dynamic;
     // DART_DEVICE_SJ=1: the junction table is counted, sorted and printed on the device (dg_batch_accumulate_sj per batch, dg_sj_merge / dg_sj_finish at the end);
     // works in both pipelines, with -o and -bo alike.  Without the switch the ordered writer fills a std::map, as always.
     const bool device_sj = getenv("DART_DEVICE_SJ") && atoi(getenv("DART_DEVICE_SJ")) != 0;
@@ -727,7 +729,7 @@ int main(int argc, char *argv[])
                                                  out_fd, &off, total, sjmap, t0, ferr, fst, pool, gi);
                 out_end(off);
                 if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, device_bam ? ", bam=device" : "");
+                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "");
                 gi->m1.close_now(); gi->m2.close_now();
                 continue;
             }
@@ -747,7 +749,7 @@ int main(int argc, char *argv[])
                                              out_fd, &off, total, sjmap, t0, ferr, fst, pool, lib == 0 ? &pre : nullptr);
             out_end(off);
             if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, device_bam ? ", bam=device" : "");
+            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "");
             if (s1.fp) fclose(s1.fp);
             if (s2.fp) fclose(s2.fp);
             continue;

@@ -344,6 +344,8 @@ static bool g_device_fastq = false;
 // DART_DEVICE_BAM=1 with -bo: the batch's BAM records are written and compressed on the GPU (dg_batch_format_bam, or its resident form with DART_DEVICE_FASTQ=1)
 // behind its mapping; the slot holds whole BGZF blocks and the ordered writer hands them to g_bam_sink (BamWriter::add_bgzf_blocks) instead of writing text to fd.
 static bool g_device_bam = false;
+// DART_BGZF_DYNAMIC=1 beside DART_DEVICE_BAM=1: the blocks are coded with dynamic Huffman codes per strip (DG_BAM_DYNAMIC): a smaller file of the same records
+static bool g_bgzf_dynamic = false;
 static std::function<bool(const char *blocks, size_t n, long long records, long long refused)> g_bam_sink;
 // DART_DEVICE_SJ=1: every mapping thread counts its batch's junction tuples in its context's table on the GPU (dg_batch_accumulate_sj) right behind the mapping;
 // the tuples are not downloaded and the ordered writer's map loop does not run.  The host program merges the tables and prints junctions.tab from the device's
@@ -689,7 +691,8 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 const uint32_t fl = unique_only ? DG_SAM_UNIQUE_ONLY : 0u;
                 if (!g_device_bam) return in ? dg_batch_format_sam(ctx[w], in, fl, nb, s->dev_ct, &dev_ms) : dg_batch_format_sam_resident(ctx[w], npm, fl, nb, s->dev_ct, &dev_ms);
                 uint64_t ct[5] = {0, 0, 0, 0, 0}; size_t raw = 0;
-                const int rc = in ? dg_batch_format_bam(ctx[w], in, fl, nb, &raw, ct, &dev_ms) : dg_batch_format_bam_resident(ctx[w], npm, fl, nb, &raw, ct, &dev_ms);
+                const uint32_t bfl = fl | (g_bgzf_dynamic ? DG_BAM_DYNAMIC : 0u);
+                const int rc = in ? dg_batch_format_bam(ctx[w], in, bfl, nb, &raw, ct, &dev_ms) : dg_batch_format_bam_resident(ctx[w], npm, bfl, nb, &raw, ct, &dev_ms);
                 for (int i = 0; i < 3; i++) s->dev_ct[i] = ct[i];
                 s->bam_rr[0] = ct[3]; s->bam_rr[1] = ct[4];
                 return rc;

@@ -97,6 +97,8 @@ class SamText(C.Structure):
 
 SAM_UNIQUE_ONLY = 1
 BAM_RAW = 2
+BAM_DYNAMIC = 4            # DG_BAM_DYNAMIC: BGZF with dynamic Huffman codes per strip
+BGZF_DYNAMIC = 1           # DG_BGZF_DYNAMIC: the same for dg_bgzf_compress_flags
 
 
 class FastqText(C.Structure):
@@ -257,6 +259,10 @@ def _load_lib():
         lib.dg_batch_device_bam.argtypes = [vp, vp, vp]
         lib.dg_bgzf_compress.argtypes = [vp, vp, C.c_size_t, vp, vp]
         lib.dg_bgzf_granules.argtypes = [vp]
+    if hasattr(lib, "dg_bgzf_compress_flags"):
+        lib.dg_bgzf_compress_flags.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp]
+        lib.dg_probe_huff_lengths.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+        lib.dg_probe_bgzf_phases.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
         lib.dg_batch_bam_device_ms.argtypes = [vp, vp]
     if hasattr(lib, "dg_sj_finish"):                         # (likewise: the splice-junction table on the device)
         lib.dg_sj_reserve.argtypes = [vp, C.c_size_t]
@@ -456,10 +462,11 @@ class DartGPU:
         self._chk(self.lib.dg_batch_download_bam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_bam")
         return out[:int(nb.value)].tobytes(), dict(unmapped=int(ct[0]), unique=int(ct[1]), paired=int(ct[2]), records=int(ct[3]), refused=int(ct[4]))
 
-    def format_bam(self, headers, quals, n_pair_mode: int, unique_only: bool = False, raw: bool = False):
+    def format_bam(self, headers, quals, n_pair_mode: int, unique_only: bool = False, raw: bool = False, dynamic: bool = False):
         """BAM of the batch that ran last, made on the device (dg_batch_format_bam + dg_batch_download_bam) -> (bytes, counters): BGZF blocks without the
         file's header and end-of-file block, or with raw=True the uncompressed records; arguments as format_sam; counters: format_sam's three, records
-        written and lines refused; self.bam_device_ms holds the kernels' device time, self.bam_raw_bytes the records' size"""
+        written and lines refused; self.bam_device_ms holds the kernels' device time, self.bam_raw_bytes the records' size; dynamic=True: BGZF with
+        dynamic Huffman codes per strip (DG_BAM_DYNAMIC): a smaller stream of the same records"""
         if not hasattr(self.lib, "dg_batch_format_bam"):
             raise RuntimeError("this build of libdartgpu.so has no dg_batch_format_bam")
         ho, hb = flatten_strings(headers)
@@ -469,25 +476,30 @@ class DartGPU:
             qo, qb = flatten_strings(quals)
             t.qual_off, t.qual = qo.ctypes.data, qb.ctypes.data
         nb = C.c_size_t(0); n_raw = C.c_size_t(0); ct = (C.c_uint64 * 5)(); ms = C.c_float(0)
-        flags = (SAM_UNIQUE_ONLY if unique_only else 0) | (BAM_RAW if raw else 0)
+        flags = (SAM_UNIQUE_ONLY if unique_only else 0) | (BAM_RAW if raw else 0) | (BAM_DYNAMIC if dynamic else 0)
         self._chk(self.lib.dg_batch_format_bam(self.ctx, C.byref(t), flags, C.byref(nb), C.byref(n_raw), ct, C.byref(ms)), "dg_batch_format_bam")
         return self._bam_result(nb, n_raw, ct, ms)
 
-    def format_bam_resident(self, n_pair_mode: int, unique_only: bool = False, raw: bool = False):
+    def format_bam_resident(self, n_pair_mode: int, unique_only: bool = False, raw: bool = False, dynamic: bool = False):
         """format_bam with the names and qualities a FASTQ upload left in HBM (dg_batch_format_bam_resident) -> (bytes, counters)"""
         nb = C.c_size_t(0); n_raw = C.c_size_t(0); ct = (C.c_uint64 * 5)(); ms = C.c_float(0)
-        flags = (SAM_UNIQUE_ONLY if unique_only else 0) | (BAM_RAW if raw else 0)
+        flags = (SAM_UNIQUE_ONLY if unique_only else 0) | (BAM_RAW if raw else 0) | (BAM_DYNAMIC if dynamic else 0)
         self._chk(self.lib.dg_batch_format_bam_resident(self.ctx, int(n_pair_mode), flags, C.byref(nb), C.byref(n_raw), ct, C.byref(ms)), "dg_batch_format_bam_resident")
         return self._bam_result(nb, n_raw, ct, ms)
 
-    def bgzf_compress(self, data) -> bytes:
+    def bgzf_compress(self, data, dynamic: bool = False) -> bytes:
         """any bytes -> BGZF blocks, compressed on the device (dg_bgzf_compress + dg_batch_download_bam); no end-of-file block; self.bam_device_ms holds the
-        kernels' device time"""
+        kernels' device time; dynamic=True: dynamic Huffman codes per strip (dg_bgzf_compress_flags with DG_BGZF_DYNAMIC)"""
         if not hasattr(self.lib, "dg_bgzf_compress"):
             raise RuntimeError("this build of libdartgpu.so has no dg_bgzf_compress")
         a = np.frombuffer(bytes(data) + b"\0", np.uint8)
         nb = C.c_size_t(0); ms = C.c_float(0)
-        self._chk(self.lib.dg_bgzf_compress(self.ctx, a.ctypes.data, len(a) - 1, C.byref(nb), C.byref(ms)), "dg_bgzf_compress")
+        if dynamic:
+            if not hasattr(self.lib, "dg_bgzf_compress_flags"):
+                raise RuntimeError("this build of libdartgpu.so has no dg_bgzf_compress_flags")
+            self._chk(self.lib.dg_bgzf_compress_flags(self.ctx, a.ctypes.data, len(a) - 1, BGZF_DYNAMIC, C.byref(nb), C.byref(ms)), "dg_bgzf_compress_flags")
+        else:
+            self._chk(self.lib.dg_bgzf_compress(self.ctx, a.ctypes.data, len(a) - 1, C.byref(nb), C.byref(ms)), "dg_bgzf_compress")
         self.bam_device_ms = float(ms.value)
         out = np.zeros(max(int(nb.value), 1), np.uint8)
         self._chk(self.lib.dg_batch_download_bam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_bam")
@@ -746,6 +758,27 @@ class DartGPU:
             self._chk(rc, "dg_probe_seeds")
             u = int(used.value)
             return so, rp[:u], sl[:u], gp[:u]
+
+    BGZF_PHASES = ("parse", "sort", "lengths", "codes", "header", "emit", "insert", "rest")
+
+    def probe_bgzf_phases(self, data):
+        """the dynamic BGZF kernel's clocks per phase on `data` (dg_probe_bgzf_phases) -> ({phase: cycles summed over strips and blocks}, BGZF bytes)"""
+        a = np.ascontiguousarray(data, np.uint8) if isinstance(data, np.ndarray) else np.frombuffer(bytes(data), np.uint8)
+        cyc = (C.c_uint64 * 8)(); nb = C.c_size_t(0); ms = C.c_float(0)
+        self._chk(self.lib.dg_probe_bgzf_phases(self.ctx, a.ctypes.data, len(a), cyc, C.byref(nb), C.byref(ms)), "dg_probe_bgzf_phases")
+        self.bam_device_ms = float(ms.value)
+        out = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_batch_download_bam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_bam")
+        return dict(zip(self.BGZF_PHASES, (int(x) for x in cyc))), out[:int(nb.value)].tobytes()
+
+    def probe_huff_lengths(self, freq, limit: int):
+        """the code lengths the dynamic BGZF coder's builder gives a histogram, none above `limit`, computed on the device (dg_probe_huff_lengths)"""
+        if not hasattr(self.lib, "dg_probe_huff_lengths"):
+            raise RuntimeError("this build of libdartgpu.so has no dg_probe_huff_lengths")
+        f = np.ascontiguousarray(freq, np.uint32)
+        out = np.zeros(max(len(f), 1), np.uint8)
+        self._chk(self.lib.dg_probe_huff_lengths(self.ctx, f.ctypes.data, len(f), int(limit), out.ctypes.data), "dg_probe_huff_lengths")
+        return [int(x) for x in out[:len(f)]]
 
     def probe_nw(self, pairs, mode: int = 0):
         """nw_alignment of (a, b) byte pairs through form `mode` of the kernels (dg_probe_nw_mode)."""

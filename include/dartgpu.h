@@ -271,6 +271,9 @@ int dg_fastq_tile(void);
  *                                 fixed Huffman codes, or stored when that is not smaller), CRC32, ISIZE.  The same input gives the same bytes on every run.
  *                                 *n_bytes <= *n_raw + 31 * blocks.  No BAM header and no end-of-file block: the file's writer adds them (`dart -bo`:
  *                                 BamWriter::open / close).  DG_BAM_RAW: stop at the records.  *n_raw = the records' bytes in both cases.
+ *                                 DG_BAM_DYNAMIC: every strip of a block (dg_bgzf_granules [0] input bytes) becomes a deflate block of its own, coded with
+ *                                 the smaller of a dynamic Huffman code built from the strip's own tokens and the fixed code (dg_bgzf_dyn.h); the tokens, the
+ *                                 stored fallback and the bound on *n_bytes are the same, the stream is smaller.  Ignored together with DG_BAM_RAW.
  *                                 counters [0..2] as dg_batch_format_sam, [3] records written, [4] lines refused.  The call waits twice, for the two sizes;
  *                                 when the records outgrew their buffer's first guess the writing kernel -- never the batch -- runs a second time.
  *                                 A batch of 0 reads gives 0 bytes (0 blocks).  SAM and BAM of one batch may be formatted in either order.
@@ -279,17 +282,22 @@ int dg_fastq_tile(void);
  *   dg_batch_device_bam           the result in HBM, valid until the next upload or run on this context
  *   dg_bgzf_compress              any n bytes of host memory -> BGZF blocks on the context's stream (n = 0: no block); needs no batch and no index aids;
  *                                 leaves the result where dg_batch_download_bam / dg_batch_device_bam find it
+ *   dg_bgzf_compress_flags        the same with flags: 0 = dg_bgzf_compress, DG_BGZF_DYNAMIC = the coder of DG_BAM_DYNAMIC; any other bit: DG_ERR_ARG, nothing
+ *                                 is enqueued and the context stays usable
  *   dg_batch_bam_device_ms        device time of the last call's kernels: [0] the record kernels, [1] the BGZF kernels (0 when that phase did not run)
  *   dg_bgzf_granules              [0] the strip, [1] the segment of the deflate kernel in bytes: matches are looked up in earlier strips (plus distance 1
  *                                 and the same offset of the previous strip) and a lane's match ends with its segment (whole segments at the same distance are then joined, up to 258); tests place repeats on these seams
  * dg_last_timings / dg_last_counters keep the batch's values.                                                                                          */
 #define DG_BAM_RAW 2u   /* leave the uncompressed records (no BGZF): what a caller with its own compressor, and the tests, take */
+#define DG_BAM_DYNAMIC 4u   /* BGZF with dynamic Huffman codes per strip */
+#define DG_BGZF_DYNAMIC 1u  /* the same for dg_bgzf_compress_flags */
 int dg_batch_format_bam(dg_ctx *, const dg_sam_text *in, uint32_t flags, size_t *n_bytes, size_t *n_raw,
                         uint64_t counters[5] /* SAM's three, [3] records written, [4] lines refused */, float *device_ms);
 int dg_batch_format_bam_resident(dg_ctx *, int n_pair_mode, uint32_t flags, size_t *n_bytes, size_t *n_raw, uint64_t counters[5], float *device_ms);
 int dg_batch_download_bam(dg_ctx *, void *out, size_t cap);
 int dg_batch_device_bam(dg_ctx *, void **ptr, size_t *n_bytes);
 int dg_bgzf_compress(dg_ctx *, const void *host_bytes, size_t n, size_t *n_bytes, float *device_ms);
+int dg_bgzf_compress_flags(dg_ctx *, const void *host_bytes, size_t n, uint32_t flags, size_t *n_bytes, float *device_ms);
 int dg_batch_bam_device_ms(dg_ctx *, float ms[2]);
 int dg_bgzf_granules(int out[2]);
 
@@ -373,6 +381,15 @@ int dg_probe_nw(dg_ctx *, int n, const uint32_t *a_off, const uint32_t *b_off, c
  * kernels do (RefSequence, bwt_index.cpp:193-212): b must be ACGT, else DG_ERR_ARG.                                  */
 int dg_probe_nw_mode(dg_ctx *, int mode, int n, const uint32_t *a_off, const uint32_t *b_off, const char *a, const char *b,
                      uint32_t *out_off, uint32_t *out_len, char *out_a, char *out_b, size_t cap);
+/* Test hook: the code-length builder of the dynamic BGZF coder (DG_BAM_DYNAMIC) on a histogram of the caller's, in a one-workgroup kernel: len_out[i] =
+ * the length of symbol i's Huffman code, none above `limit` (1..15), 0 exactly where freq[i] is 0; one used symbol gets length 1.  The same integers as the
+ * host's build of dg_bgzf_dyn.h gives.  n_sym 1..320, every freq below 2^23, no more used symbols than 2^limit, else DG_ERR_ARG.  A strip's own
+ * histogram practically never needs the cut to 15 bits; this call reaches it. */
+int dg_probe_huff_lengths(dg_ctx *, const uint32_t *freq, int n_sym, int limit, uint8_t *len_out);
+/* Measuring hook: dg_bgzf_compress_flags(DG_BGZF_DYNAMIC) on n > 0 bytes with the kernel's clocks on: cycles[p] = lane 0's shader clocks between the barriers
+ * of phase p, summed over all strips and blocks: 0 parse + merge + histogram, 1 sort, 2 code lengths (serial), 3 canonical codes, 4 header + choice (serial),
+ * 5 scan + emit, 6 table inserts, 7 the rest (load, CRC, trailer).  The bytes are the unprobed call's and lie where dg_batch_download_bam finds them. */
+int dg_probe_bgzf_phases(dg_ctx *, const void *host_bytes, size_t n, uint64_t cycles[8], size_t *n_bytes, float *device_ms);
 
 #ifdef __cplusplus
 }
