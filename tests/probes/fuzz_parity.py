@@ -4,7 +4,7 @@ import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
-import common, oracle_py
+import common, oracle_py, read_structures as rs, read_structure_inputs as rsi
 from dart_amd import synth, index_build, host
 def run(rounds, seed0, workdir="/tmp/fuzz", log=print):
     """-> number of rounds that were identical; raises AssertionError at the first difference"""
@@ -46,6 +46,21 @@ def run(rounds, seed0, workdir="/tmp/fuzz", log=print):
                 common.assert_same(gpu.download_compact(), want)
                 common.assert_same(gpu.map_batch_compact(words, nlist, rlen), want)      # one call: compact records built inside the run
                 words_ok = " + packed/compact"
+            # one set of the named read structures synth.make_reads never makes (tests/read_structures.py), made on this round's genome: a batch of its own under the
+            # round's flags -- pairs when the round is paired, else every mate as a read of its own
+            classes = rs.make(g, seed0 + k, rlen=max(rlen, 101), n_per_class=12)
+            # (rs.make leaves out a class this genome cannot serve: only the two that need repeat families may be missing, and every class made is complete)
+            missing = [c for c in rs.class_names(max(rlen, 101)) if c not in classes]
+            assert set(missing) <= set(rs.NEEDS_REPEATS) and all(len(v) == 12 for v in classes.values()), (missing, {c: len(v) for c, v in classes.items() if len(v) != 12})
+            sreads = rs.as_reads(rs.all_pairs(classes)[0])
+            sso, srl, sflat = host.pack_reads(sreads)
+            swant = orc.map_batch(orc.params(paired=paired, **flags), sso, srl, sflat, threads=16)
+            common.assert_same(gpu.map_batch(sso, srl, sflat), swant)
+            swords, snlist, slongest, slens = rsi.padded_2bit(sreads)
+            common.assert_same(gpu.map_batch_packed(swords, snlist, slongest, slens), swant)
+            common.assert_same(gpu.download_compact(), swant)
+            common.assert_same(gpu.map_batch_compact(swords, snlist, slongest, slens), swant)
+            words_ok += " + %d reads of %d structure classes%s" % (len(sreads), len(classes), " (without %s)" % ", ".join(missing) if missing else "")
             log("round %d ok%s: genome %s rscale, %d x %s%d, %s, %s  (%.1f s)" % (k, words_ok, lens, n, "2x" if paired else "", rlen, kw, flags, time.time() - t))
         except AssertionError as e:
             raise AssertionError("round %d (seed %d) DIFFERS: genome %s, %d x %s%d, %s, %s: %s" % (k, seed0 + k, lens, n, "2x" if paired else "", rlen, kw, flags, str(e)[:300]))

@@ -73,6 +73,23 @@ def test_lane_code_writes_the_records_of_the_odd_character_reads(workdir):
     assert any(15 in (b >> 4, b & 15) for _, r in bdi.records_of(rec)[:200] for b in r[32 + r[8]:])      # a '-' or an N became code 15
 
 
+def test_lane_code_writes_the_records_of_the_read_structures(workdir):
+    """tests/read_structures.py's classes, paired, -mis 12 -m: several N in a CIGAR, long insertions, chains of one-base operations, improper and unpaired flags,
+    mates of 14 to 101 bases"""
+    import read_structures as rs, read_structure_inputs as rsi
+    c, classes, _ = rsi.read_set("rs101", workdir)
+    orc, ix = oracle_py.Oracle(c["prefix"]), host.Index(c["prefix"])
+    seqs = rs.as_reads(rs.all_pairs(classes)[0])
+    so, rl, flat = host.pack_reads(seqs)
+    p, _ = common.parse_flags(rsi.FIXTURE_FLAGS)
+    res = orc.map_batch(orc.params(paired=1, **p), so, rl, flat, threads=4)
+    headers = ["p%d" % (i // 2) for i in range(len(seqs))]
+    quals = ["I" * len(s) for s in seqs]
+    rec, seen = _check(workdir, "read_structures", res, so, rl, flat, headers, quals, ix.names, len(seqs), False, True, seqs)
+    _decodes_to(rec, ix.names, ix.chr_len, rsi.fixture_sam())
+    assert seen["refused"] == 0 and seen["odd"] > 0
+
+
 EDGE_RUNS = [(False, False, False), (True, False, False), (False, True, False), (True, True, True), (False, False, True)]
 
 

@@ -184,6 +184,23 @@ def test_device_bam_of_the_odd_character_reads(ctxs, workdir):
     _decodes_to(ix, z, gzip.open(os.path.join(common.GOLDEN, "odd_characters.mis12.sam.gz"), "rt").read())
 
 
+def test_device_bam_of_the_read_structures(ctxs, workdir):
+    """the classes of tests/read_structures.py, paired, -mis 12 -m (several N in a CIGAR, long insertions, chains of one-base operations, improper and unpaired flags,
+    mates of 14 to 101 bases): raw against the host writer, and the blocks decoded against the SAM the reference's object code wrote"""
+    import read_structures as rs, read_structure_inputs as rsi
+    c, ix, gpu = ctxs["pe101_spliced"]
+    _, classes, _ = rsi.read_set("rs101", workdir)
+    seqs = rs.as_reads(rs.all_pairs(classes)[0])
+    so, rl, flat = host.pack_reads(seqs)
+    p, _ = common.parse_flags(rsi.FIXTURE_FLAGS)
+    gpu.set_params(host.default_params(paired=1, **p))
+    gpu.map_batch(so, rl, flat)
+    headers = ["p%d" % (i // 2) for i in range(len(seqs))]; quals = ["I" * len(s) for s in seqs]
+    _device_vs_host_writer(gpu, ix, workdir, "gpu_read_structures", headers, quals, len(seqs))
+    z, _ = gpu.format_bam(headers, quals, len(seqs))
+    _decodes_to(ix, z, rsi.fixture_sam())
+
+
 def test_device_bam_edge_input_through_the_kernels(ctxs, workdir):
     """sdi.edge_reads (a 1-base and a 1000-base read, a 5000-byte name, a NUL inside a quality, a quality longer than its read, 6 pairs + a single tail) on
     records of a real mapping, in the four flag combinations, raw against the host writer"""

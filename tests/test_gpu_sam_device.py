@@ -66,6 +66,25 @@ def test_device_sam_of_the_odd_character_reads(ctxs):
     assert ct == dict(unmapped=st.unmapped, unique=st.unique, paired=st.paired)
 
 
+def test_device_sam_of_the_read_structures(ctxs, workdir):
+    """the classes of tests/read_structures.py, paired, -mis 12 -m: CIGARs with several N, insertions of up to 30 bases, chains of one-base operations, improper and
+    unpaired flags, mates of 14 to 101 bases -- against the SAM the reference's object code wrote for them"""
+    import read_structures as rs, read_structure_inputs as rsi
+    c, ix, gpu = ctxs["pe101_spliced"]
+    _, classes, _ = rsi.read_set("rs101", workdir)
+    seqs = rs.as_reads(rs.all_pairs(classes)[0])
+    so, rl, flat = host.pack_reads(seqs)
+    p, _ = common.parse_flags(rsi.FIXTURE_FLAGS)
+    gpu.set_params(host.default_params(paired=1, **p))
+    res = gpu.map_batch(so, rl, flat)
+    headers = ["p%d" % (i // 2) for i in range(len(seqs))]; quals = ["I" * len(s) for s in seqs]
+    text, ct = gpu.format_sam(headers, quals, len(seqs))
+    _same(text, sdi.body_of(rsi.fixture_sam()))
+    twin, st = sdi.twin_text(headers, seqs, quals, res.reads, res.reports, res.cigar, ix.names, len(seqs), multi=True)
+    _same(text, twin)
+    assert ct == dict(unmapped=st.unmapped, unique=st.unique, paired=st.paired)
+
+
 def test_device_sam_does_not_depend_on_how_the_batch_is_split(ctxs):
     c, ix, gpu = ctxs["pe101_spliced"]
     n = len(c["reads"])

@@ -22,7 +22,6 @@ def test_chain_stage_lane_code_on_host_against_reference_dumps(workdir):
     """dg_chain.h's per-lane code (sort, GenerateAlignmentCandidate, CheckPairedAlignmentCandidates, RemoveUnMated...,
     RemoveRedundantCandidates) compiled for the host and fed the seeds of the REFERENCE's stage dumps (S1/S2 lines): the
     candidates must be the reference's C1/C2 lines -- score, PosDiff, mate index, seed count -- for every read of every case."""
-    import gzip
     src = os.path.join(common.ROOT, "tests", "native", "chain_checks.hip")
     exe = os.path.join(workdir, "chain_checks")
     subprocess.run(["hipcc", "-O2", "--offload-arch=gfx950", "-std=c++17", "-w", "-o", exe, src], check=True)
@@ -30,29 +29,47 @@ def test_chain_stage_lane_code_on_host_against_reference_dumps(workdir):
     for name, spec in sorted(common.MANIFEST["cases"].items()):
         run0 = common.MANIFEST["manifest"][name]["runs"][0]
         p, _ = common.parse_flags(run0["flags"])
-        lengths = spec["lengths"]
         paired = 1 if spec["paired"] else 0
-        inp = ["H %d %d %d %d %d" % (len(lengths), sum(lengths), p.get("max_gaps", 5), p.get("max_intron", 500000), paired)]
-        o = 0
-        for l in lengths:
-            inp.append("%d %d" % (o, l)); o += l
-        want, unit = [], {}
-        for line in gzip.open(os.path.join(common.GOLDEN, run0["base"] + ".stages.gz"), "rt"):
-            f = line.split()
-            if f[0] in ("S1", "S2"):
-                toks = [t.split(":") for t in f[3:]]
-                unit[f[0]] = "%d %d " % (spec["rlen"], len(toks)) + " ".join("%s %s %s" % (t[0], t[1], t[2]) for t in toks)
-                if (f[0] == "S2") or not paired:
-                    inp.append("U " + unit["S1"] + (" " + unit["S2"] if paired else ""))
-                    unit = {}
-            elif f[0] in ("C1", "C2"):
-                want.append(" ".join([f[0]] + f[2:]))
-        out = subprocess.run([exe], input="\n".join(inp) + "\n", check=True, capture_output=True, text=True).stdout.strip().split("\n")
-        assert len(out) == len(want) and len(want) > 100, (name, len(out), len(want))
-        for got, w in zip(out, want):
-            assert got == w, (name, got, w)
-        total += len(want)
+        n = _chain_check(exe, name, spec["lengths"], p, paired, os.path.join(common.GOLDEN, run0["base"] + ".stages.gz"), lambda k: spec["rlen"])
+        assert n > 100, (name, n)
+        total += n
     assert total > 1000
+    # the read structures synth.make_reads never makes (tests/read_structures.py): reads of several lengths, seeds of chimeras, of reads across the text's seams, of
+    # noise between short stretches of text
+    import read_structures as rs, read_structure_inputs as rsi
+    c, classes, _ = rsi.read_set("rs101", workdir)
+    reads = rs.as_reads(rs.all_pairs(classes)[0])
+    p, _ = common.parse_flags(rsi.FIXTURE_FLAGS)
+    n = _chain_check(exe, "read structures", c["spec"]["lengths"], p, 1, rsi.BASE + ".stages.gz", lambda k: len(reads[k]))
+    assert n == len(reads)
+
+
+def _chain_check(exe, name, lengths, p, paired, dump, rlen_of, check=None):
+    """one stage dump through the program: the seeds of its S lines in, its C lines expected -> number of C lines compared.  rlen_of(k): length of the k-th read"""
+    import gzip
+    inp = ["H %d %d %d %d %d" % (len(lengths), sum(lengths), p.get("max_gaps", 5), p.get("max_intron", 500000), paired)]
+    o = 0
+    for l in lengths:
+        inp.append("%d %d" % (o, l)); o += l
+    want, unit, k = [], {}, 0
+    for line in gzip.open(dump, "rt"):
+        f = line.split()
+        if f[0] in ("S1", "S2"):
+            toks = [t.split(":") for t in f[3:]]
+            unit[f[0]] = "%d %d " % (rlen_of(k), len(toks)) + " ".join("%s %s %s" % (t[0], t[1], t[2]) for t in toks)
+            k += 1
+            if (f[0] == "S2") or not paired:
+                inp.append("U " + unit["S1"] + (" " + unit["S2"] if paired else ""))
+                unit = {}
+        elif f[0] in ("C1", "C2"):
+            want.append(" ".join([f[0]] + f[2:]))
+    r = subprocess.run([exe], input="\n".join(inp) + "\n", capture_output=True, text=True)
+    assert r.returncode == 0 and (check is None or check(r)), (name, r.stderr[-3000:])
+    out = r.stdout.strip().split("\n")
+    assert len(out) == len(want), (name, len(out), len(want))
+    for got, w in zip(out, want):
+        assert got == w, (name, got, w)
+    return len(want)
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
@@ -117,6 +134,8 @@ def test_pair_kernel_unit_code_on_host_against_oracle(workdir):
         p, _ = common.parse_flags(flags)
         runs.append((prefix, p, 1, arr))
     runs.append((prefix, common.parse_flags(["-mis", "4"])[0], 0, m1))
+    n_generator = len(runs)
+    runs += _read_structure_runs(workdir)           # (what synth.make_reads never makes: tests/read_structures.py, paired and every mate as a read of its own)
     fast = total = multi = packed = 0
     for k, (pf, p, paired, reads_arr) in enumerate(runs):
         path = os.path.join(workdir, "pairchk_%d.bin" % k)
@@ -128,8 +147,74 @@ def test_pair_kernel_unit_code_on_host_against_oracle(workdir):
         f = out.stdout.split()
         total += int(f[1].rstrip(":")); fast += int(f[4].rstrip(",")); multi += int(f[f.index("reports") + 1].rstrip(";"))
         packed += int(f[f.index("words") + 1].rstrip(";"))
+        if k + 1 == n_generator:
+            assert total > 20000 and fast > 0.5 * total and multi > 200 and packed > 0.5 * total, (total, fast, multi, packed)      # (the generator's runs alone, as before)
+            total0, fast0 = total, fast
+        elif k >= n_generator:
+            assert int(f[4].rstrip(",")) > 0, (k, p, out.stdout)
+    # the read structures' runs: only a unit finished here has its records compared.  Every second read of these sets is a plain mate, an exact copy of the text (or one with
+    # 1 % substitutions), which the unit code finishes itself when each mate is a unit of its own: half of the single-end runs' units, which are two thirds of all units
+    print("read structures: %d of %d units finished by the unit code" % (fast - fast0, total - total0))
+    assert total - total0 > 30000 and fast - fast0 >= (total - total0) // 3, (total - total0, fast - fast0)
     # (packed: units whose reads hold A/C/G/T/N only were run a second time from 2-bit + mask words -- what k_pair does for a packed batch -- and gave the same state)
     assert total > 20000 and fast > 0.5 * total and multi > 200 and packed > 0.5 * total, (total, fast, multi, packed)
+
+
+def _read_structure_runs(workdir):
+    """-> [(index prefix, flags, paired, reads)]: both committed read sets under the three flag sets, paired and single-end"""
+    import read_structures as rs, read_structure_inputs as rsi
+    runs = []
+    for name in rsi.SETS:
+        c, classes, _ = rsi.read_set(name, workdir)
+        reads = rs.as_reads(rs.all_pairs(classes)[0])
+        for flags in rsi.SET_FLAGS[name]:
+            for paired in (1, 0):
+                runs.append((c["prefix"], common.parse_flags(flags)[0], paired, reads))
+    return runs
+
+
+def _sanitized(workdir, name):
+    exe = os.path.join(workdir, name + "_san")
+    if not os.path.exists(exe):
+        subprocess.run(["hipcc", "-O1", "-g", "--offload-arch=gfx950", "-std=c++17", "-w", "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
+                        "-o", exe, os.path.join(common.ROOT, "tests", "native", name + ".hip")], check=True)
+    return exe
+
+
+def _clean(r):
+    return r.returncode == 0 and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+@pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")
+def test_pair_and_chain_lane_code_under_sanitizers_on_read_structures(workdir):
+    """pair_checks.hip and chain_checks.hip once more as stand-alone programs with the host side under AddressSanitizer and UndefinedBehaviorSanitizer, on the read sets of
+    tests/read_structures.py: an index out of an array in dg_pair.h's or dg_chain.h's lane code shows here, before the same code runs on a device.  (-mis 12 -m, paired,
+    and -mis 30 with every mate as its own read: the flag sets with the most candidates and the most segment pairs per read; the 250-base set also at -mis 100, paired,
+    under which its long insertions pass the mismatch limit.)"""
+    import read_structures as rs, read_structure_inputs as rsi
+    exe = _sanitized(workdir, "pair_checks")
+    units = finished = 0
+    for name in rsi.SETS:
+        c, classes, _ = rsi.read_set(name, workdir)
+        reads = rs.as_reads(rs.all_pairs(classes)[0])
+        for flags, paired in ((["-mis", "12", "-m"], 1), (["-mis", "30"], 0)) + (((rsi.WIDE_FLAGS, 1),) if rsi.WIDE_FLAGS in rsi.SET_FLAGS[name] else ()):
+            path = os.path.join(workdir, "pairchk_san_%s_%s_%d.bin" % (name, flags[1], paired))
+            orc = oracle_py.Oracle(c["prefix"])
+            _pair_check_file(path, c["prefix"], common.parse_flags(flags)[0], paired, reads, orc)
+            orc.close()
+            r = subprocess.run([exe, path], capture_output=True, text=True)
+            assert _clean(r) and r.stdout.strip().endswith("bad=0"), (name, flags, r.stdout[-500:] + r.stderr[-3000:])
+            f = r.stdout.split()
+            assert int(f[4].rstrip(",")) > 0, (name, flags, r.stdout)
+            units += int(f[1].rstrip(":")); finished += int(f[4].rstrip(","))
+    # (only a unit finished here is compared: the plain mates of the single-end runs at the least, half of their units, which are more than half of all units)
+    print("sanitized: %d of %d units finished by the unit code" % (finished, units))
+    assert units > 4000 and finished >= units // 4, (units, finished)
+    exe = _sanitized(workdir, "chain_checks")
+    c, classes, _ = rsi.read_set("rs101", workdir)
+    reads = rs.as_reads(rs.all_pairs(classes)[0])
+    n = _chain_check(exe, "read structures, sanitized", c["spec"]["lengths"], common.parse_flags(rsi.FIXTURE_FLAGS)[0], 1, rsi.BASE + ".stages.gz", lambda k: len(reads[k]), check=_clean)
+    assert n == len(reads)
 
 
 @pytest.mark.skipif(shutil.which("hipcc") is None, reason="hipcc not on PATH")

@@ -158,3 +158,40 @@ def test_oracle_cli_matches_reference_on_reads_with_odd_characters(workdir):
     got = open(os.path.join(d, "orc.sam")).read()
     assert got == want, common.first_diff(got, want)
     assert open(os.path.join(d, "orc.j")).read() == open(os.path.join(common.GOLDEN, "odd_characters.mis12.junctions.tab")).read()
+
+
+def test_oracle_cli_matches_reference_on_read_structures(workdir):
+    """The classes of tests/read_structures.py (several junctions in a read, short overhangs, long indels, noise, tandem gains and losses, chimeras, reads across the text's
+    seams, pairs that are not two facing mates), paired: the oracle's command line against what the reference's object code wrote for the same reads
+    (tests/golden/read_structures.*, made by tests/golden/make_read_structures.py) -- statistics block and digests of every run, the SAM and junction files of the
+    -mis 12 -m run line by line; where the reference's object code is at hand it also runs beside the oracle."""
+    import hashlib, subprocess
+    import read_structures as rs, read_structure_inputs as rsi
+    oracle_py.build()
+    gold = rsi.gold()
+    live = os.path.exists(oracle_py.REF_HARNESS)
+    for name in rsi.SETS:
+        c, classes, _ = rsi.read_set(name, workdir)
+        meta = gold["sets"][name]
+        assert {k: len(v) for k, v in classes.items()} == meta["classes"] and rs.digest(classes) == meta["reads_sha256"], "the read generator drifted from the golden inputs"
+        d = os.path.join(workdir, "read_structures_" + name); os.makedirs(d, exist_ok=True)
+        rs.write_fastq(os.path.join(d, "a.fq"), os.path.join(d, "b.fq"), rs.all_pairs(classes)[0])
+        for flags in rsi.REF_FLAGS[name]:
+            r = subprocess.run([oracle_py.ORACLE_CLI, "-i", c["prefix"], "-f", "a.fq", "-f2", "b.fq"] + list(flags) + ["-o", "orc.sam", "-j", "orc.j", "-t", "4"], cwd=d,
+                               stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, check=True)
+            sam, junc = open(os.path.join(d, "orc.sam")).read(), open(os.path.join(d, "orc.j")).read()
+            if live:
+                rr = subprocess.run([oracle_py.REF_HARNESS, "map", "-i", c["prefix"], "-f", "a.fq", "-f2", "b.fq"] + list(flags) + ["-o", "ref.sam", "-j", "ref.j"], cwd=d,
+                                    stdout=subprocess.PIPE, check=True, env=rsi.REF_ENV)
+                want = open(os.path.join(d, "ref.sam")).read()
+                assert sam == want, (name, flags, common.first_diff(sam, want))
+                assert junc == open(os.path.join(d, "ref.j")).read(), (name, flags)
+                assert common.stats_block(r.stdout) == common.stats_block(rr.stdout) != ""
+            if name == "rs101" and list(flags) == rsi.FIXTURE_FLAGS:
+                want = rsi.fixture_sam()
+                assert sam == want, common.first_diff(sam, want)
+                assert junc == rsi.fixture_junctions()
+            rec = gold["runs"][rsi.run_key(name, flags)]
+            assert common.stats_block(r.stdout) == rec["stats"] != "", (name, flags)
+            assert hashlib.sha256(sam.encode()).hexdigest() == rec["sam_sha256"], (name, flags)
+            assert hashlib.sha256(junc.encode()).hexdigest() == rec["junctions_sha256"], (name, flags)

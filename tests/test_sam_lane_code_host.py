@@ -60,6 +60,21 @@ def test_lane_code_prints_the_reference_sam_of_the_odd_character_reads(workdir):
     _check(workdir, "odd", res, so, rl, flat, headers, quals, ix.names, 0, False, False, want_body=want, seqs=seqs)
 
 
+def test_lane_code_prints_the_reference_sam_of_the_read_structures(workdir):
+    """tests/read_structures.py's classes, paired, -mis 12 -m: several N in a CIGAR, long insertions, chains of one-base operations, improper and unpaired flags,
+    mates of 14 to 101 bases"""
+    import read_structures as rs, read_structure_inputs as rsi
+    c, classes, _ = rsi.read_set("rs101", workdir)
+    orc, ix = oracle_py.Oracle(c["prefix"]), host.Index(c["prefix"])
+    seqs = rs.as_reads(rs.all_pairs(classes)[0])
+    so, rl, flat = host.pack_reads(seqs)
+    p, _ = common.parse_flags(rsi.FIXTURE_FLAGS)
+    res = orc.map_batch(orc.params(paired=1, **p), so, rl, flat, threads=4)
+    headers = ["p%d" % (i // 2) for i in range(len(seqs))]
+    quals = ["I" * len(s) for s in seqs]
+    _check(workdir, "read_structures", res, so, rl, flat, headers, quals, ix.names, len(seqs), False, True, want_body=sdi.body_of(rsi.fixture_sam()), seqs=seqs)
+
+
 def _edge_records():
     """hand-made records for the edge batch (6 pairs + a single tail): several reports per read, both strands, a negative POS and negative distances,
     an unmapped mate, a low MAPQ for -unique, a long CIGAR that outgrows the writer's staging area"""
