@@ -14,6 +14,7 @@
 #include "dg_bgzf.h"
 #include "dg_bgzf_dyn.h"
 #include "dg_fastq.h"
+#include "dg_inflate.h"
 #include "dg_sjtab.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -163,6 +164,15 @@ struct dg_ctx {
     FqInfo *d_fq_info = nullptr, *h_fq_info = nullptr;                     // the sizes block: device / page-locked copy
     hipEvent_t ev_fq[2] = {nullptr, nullptr};
     bool fq_valid = false; size_t fq_hdr_bytes = 0, fq_qual_bytes = 0; float fq_ms = 0.f;      // the batch on the context came from dg_batch_upload_fastq
+    // BGZF inflated on the device (dg_bgzf_inflate, dg_batch_upload_fastq_bgzf; dg_inflate.h): the compressed bytes, the member table, a status word per member,
+    // the first failing member; inf_out holds the bytes of a dg_bgzf_inflate (the FASTQ path inflates straight into fq_text).  fq_tail: what the last
+    // dg_batch_upload_fastq_bgzf left behind the last whole record of each text.
+    DBuf<unsigned char> inf_in, inf_out, fq_tail; DBuf<InfBlock> inf_tab; DBuf<uint32_t> inf_status;
+    unsigned long long *d_inf_verdict = nullptr, *h_inf_verdict = nullptr;
+    hipEvent_t ev_inf[2] = {nullptr, nullptr};
+    bool inf_valid = false; size_t inf_bytes = 0;
+    bool fq_tail_valid = false; size_t fq_tail_n[2] = {0, 0}, fq_tail_off2 = 0;
+    bool no_batch = false;         // the last upload was a DG_FQ_CHECK_ONLY: there is nothing to run
     // BAM of the batch that ran last (dg_batch_format_bam, dg_bamfmt.h / dg_bgzf.h): the uncompressed records, the blocks' slots, sizes and places, the
     // contiguous stream; bgzf_in holds the bytes of a dg_bgzf_compress.  The records' inputs and scan state are the SAM formatter's buffers (sam_hdr*, sam_qual*,
     // sam_qlen, sam_read_off, sam_tile: inputs and scratch of one call); the SAM text itself (sam_text) is left alone.
@@ -645,6 +655,10 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->d_fq_info) (void)hipFree(c->d_fq_info);
     if (c->h_fq_info) (void)hipHostFree(c->h_fq_info);
     for (hipEvent_t e : c->ev_fq) if (e) (void)hipEventDestroy(e);
+    c->inf_in.release(); c->inf_out.release(); c->fq_tail.release(); c->inf_tab.release(); c->inf_status.release();
+    if (c->d_inf_verdict) (void)hipFree(c->d_inf_verdict);
+    if (c->h_inf_verdict) (void)hipHostFree(c->h_inf_verdict);
+    for (hipEvent_t e : c->ev_inf) if (e) (void)hipEventDestroy(e);
     c->ws.release(); c->scan_state.release(); c->scan_trace.release(); c->reads_c.release(); c->reports_c.release(); c->cig_c.release();
     for (int i = 0; i <= N_TIMERS; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
     if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
@@ -1058,6 +1072,7 @@ static int enqueue_upload(dg_ctx *c, int n_reads, const uint32_t *seq_off, const
     }
     if (mx > DG_MAX_RLEN) { snprintf(c->err, 512, "a read is longer than DG_MAX_RLEN (%d)", DG_MAX_RLEN); return DG_ERR_ARG; }
     c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
+    c->no_batch = false; c->inf_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64));     /* the kernels read up to 24 bytes at a read position in one go */
     HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     if (n_reads) {
@@ -1120,6 +1135,7 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
     if (n_reads && (mx + 15) / 16 != W2) { snprintf(c->err, 512, "packed batch: words_per_read must be ceil(longest read / 16) = %d", (mx + 15) / 16); return DG_ERR_ARG; }
     const size_t nw = (size_t)n_reads * W2, bytes = nw * 16;
     c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
+    c->no_batch = false; c->inf_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64)); HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     HIPCHK(c->enc.ensure(2 * nw + 16)); HIPCHK(c->packed_in.ensure(nw + 1)); HIPCHK(c->nlist_in.ensure(n_n + 1));
     c->enc_ready = true;
@@ -1149,13 +1165,103 @@ extern "C" int dg_batch_upload_packed(dg_ctx *c, int n_reads, int rlen_all, cons
 // ------------------------------------------------------------------------------------------
 extern "C" int dg_fastq_tile(void) { return FQ_TILE; }
 
+// The parser behind its input: the texts lie in c->fq_text, text 1 at 0 and text 2 at off2.  fq_reserve sizes every buffer from the arguments (nothing is asked
+// of the device before the one wait), fq_enqueue launches the kernels, fq_finish waits for the sizes block and says what it holds.
+struct FqPlan { size_t n[2], off2, line_cap[2], tile_stride, reads_bound, len_tiles, max_reads, text_bytes; bool two; };
+
+static int fq_reserve(dg_ctx *c, FqPlan &p)
+{
+    if (!c->d_fq_info) {
+        HIPCHK(hipMalloc((void **)&c->d_fq_info, sizeof(FqInfo)));
+        HIPCHK(hipHostMalloc((void **)&c->h_fq_info, sizeof(FqInfo), hipHostMallocDefault));
+        for (hipEvent_t &e : c->ev_fq) HIPCHK(hipEventCreate(&e));
+    }
+    // a record has at least one byte per existing line, so a text of n bytes holds at most n + 1 line starts; the three outputs together are never larger
+    // than the texts
+    const size_t max_reads = p.max_reads, n1 = p.n[0], n2 = p.n[1];
+    const size_t rec_cap[2] = { p.two ? (max_reads + 1) / 2 : max_reads, p.two ? max_reads / 2 : 0 };
+    size_t tiles[2];
+    for (int f = 0; f < 2; f++) { p.line_cap[f] = std::min(4 * rec_cap[f] + 1, p.n[f] + 1); tiles[f] = (p.n[f] + FQ_TILE - 1) / FQ_TILE; }
+    p.off2 = (n1 + 16 + 255) & ~(size_t)255; p.text_bytes = n1 + n2;
+    p.tile_stride = std::max(tiles[0], tiles[1]);
+    p.reads_bound = std::min(max_reads, (n1 + 4) / 4 + (n2 + 4) / 4);          // (records <= ceil(lines / 4), lines <= bytes + 1)
+    p.len_tiles = std::max<size_t>(1, (p.reads_bound + FQ_THREADS - 1) / FQ_THREADS);
+    const size_t reads_bound = p.reads_bound, text_bytes = p.text_bytes;
+    HIPCHK(c->fq_text.ensure(p.off2 + n2 + 32)); HIPCHK(c->fq_lines.ensure(p.line_cap[0] + p.line_cap[1] + 2)); HIPCHK(c->fq_tile_cnt.ensure(2 * p.tile_stride + 1));
+    HIPCHK(c->fq_name_at.ensure(reads_bound + 1)); HIPCHK(c->fq_name_len.ensure(reads_bound + 1)); HIPCHK(c->fq_loc.ensure(3 * (reads_bound + 1))); HIPCHK(c->fq_tile_sum.ensure(3 * p.len_tiles));
+    HIPCHK(c->fq_hdr_off.ensure(reads_bound + 1)); HIPCHK(c->fq_qual_off.ensure(reads_bound + 1)); HIPCHK(c->fq_hdr.ensure(text_bytes + 1)); HIPCHK(c->fq_qual.ensure(text_bytes + 1));
+    HIPCHK(c->seq.ensure(text_bytes + 64)); HIPCHK(c->seq_off.ensure(reads_bound + 1)); HIPCHK(c->rlen.ensure(reads_bound + 1));
+    return DG_OK;
+}
+
+// whole: the texts are pieces of files (whole records only; the tails and the count of unlike records are taken too); write: the batch is written
+static int fq_enqueue(dg_ctx *c, const FqPlan &p, int rc_odd_reads, bool whole, bool pieces, bool write)
+{
+    FqText x;
+    x.t[0] = c->fq_text.p; x.t[1] = c->fq_text.p + p.off2; x.n[0] = (uint32_t)p.n[0]; x.n[1] = (uint32_t)p.n[1];
+    x.line_start[0] = c->fq_lines.p; x.line_start[1] = c->fq_lines.p + p.line_cap[0] + 1; x.line_cap[0] = (uint32_t)p.line_cap[0]; x.line_cap[1] = (uint32_t)p.line_cap[1];
+    x.two = p.two ? 1 : 0;
+    const uint32_t stride = (uint32_t)(p.reads_bound + 1);
+    const dim3 text_grid((unsigned)std::max<size_t>(1, p.tile_stride), p.two ? 2u : 1u);
+    k_fq_count<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)p.tile_stride);
+    k_fq_top<<<1, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)p.tile_stride, (uint32_t)p.max_reads, c->d_fq_info, whole ? 1 : 0);
+    k_fq_lines<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)p.tile_stride, c->d_fq_info);
+    if (whole) k_fq_tail<<<dim3(64, p.two ? 2u : 1u), FQ_THREADS, 0, c->stream>>>(x, c->d_fq_info, c->fq_tail.p, (uint32_t)c->fq_tail_off2);
+    if (pieces && p.reads_bound) k_fq_unlike<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->d_fq_info);
+    k_fq_len<<<(unsigned)p.len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->d_fq_info, c->rlen.p, c->fq_name_at.p, c->fq_name_len.p, c->fq_loc.p, stride, c->fq_tile_sum.p, (uint32_t)p.len_tiles);
+    k_fq_top3<<<1, FQ_THREADS, 0, c->stream>>>(c->fq_tile_sum.p, (uint32_t)p.len_tiles, c->d_fq_info);
+    if (p.reads_bound && write)
+        k_fq_write<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->d_fq_info, rc_odd_reads ? 1 : 0, c->rlen.p, c->fq_name_at.p, c->fq_name_len.p, c->fq_loc.p, stride, c->fq_tile_sum.p,
+                                                                   (uint32_t)p.len_tiles, c->seq_off.p, c->seq.p, c->fq_hdr_off.p, c->fq_hdr.p, c->fq_qual_off.p, c->fq_qual.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_fq[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_fq_info, c->d_fq_info, sizeof(FqInfo), hipMemcpyDeviceToHost, c->stream));
+    return DG_OK;
+}
+
+// behind the wait: the sizes block's verdict; keep: the context holds the batch from here on
+static int fq_finish(dg_ctx *c, const char *fn, int max_reads, int *n_reads_out, bool keep)
+{
+    (void)hipEventElapsedTime(&c->fq_ms, c->ev_fq[0], c->ev_fq[1]);
+    const FqInfo &fi = *c->h_fq_info;
+    if (n_reads_out) *n_reads_out = (int)std::min<uint32_t>(fi.n_reads, 0x7FFFFFFFu);
+    switch (fi.status) {
+    case FQ_OK: break;
+    case FQ_E_COUNT:
+        snprintf(c->err, 512, "%s: text1 holds %u records and text2 %u: they must be equal, or text1 one more", fn, (fi.n_lines[0] + 3) / 4, (fi.n_lines[1] + 3) / 4);
+        return DG_ERR_ARG;
+    case FQ_E_CAPACITY:
+        snprintf(c->err, 512, "%s: the texts hold %u reads, max_reads is %d", fn, fi.n_reads, max_reads);
+        return DG_ERR_CAPACITY;
+    case FQ_E_EMPTY:
+        snprintf(c->err, 512, "%s: read %u is a record without bases", fn, fi.bad_read);
+        return DG_ERR_ARG;
+    case FQ_E_LONG:
+        snprintf(c->err, 512, "%s: read %u is longer than DG_MAX_RLEN (%d)", fn, fi.bad_read, DG_MAX_RLEN);
+        return DG_ERR_ARG;
+    default:
+        snprintf(c->err, 512, "%s: the bases, names or qualities of the batch exceed 32-bit offsets", fn);
+        return DG_ERR_ARG;
+    }
+    if (!keep) return DG_OK;
+    c->n_reads = (int)fi.n_reads; c->max_rlen = (int)fi.max_rlen; c->seq_bytes = (size_t)fi.total[0];
+    c->fq_hdr_bytes = (size_t)fi.total[1]; c->fq_qual_bytes = (size_t)fi.total[2]; c->fq_valid = true;
+    return DG_OK;
+}
+
+// whatever happens in an upload of FASTQ text, the context holds no batch until the call has succeeded
+static void fq_forget_batch(dg_ctx *c)
+{
+    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
+    c->fq_hdr_bytes = c->fq_qual_bytes = 0; c->fq_ms = 0.f;
+    c->no_batch = false; c->inf_valid = false; c->fq_tail_valid = false; c->fq_tail_n[0] = c->fq_tail_n[1] = 0;
+}
+
 extern "C" int dg_batch_upload_fastq(dg_ctx *c, const dg_fastq_text *in, int *n_reads_out)
 {
     if (!c) return DG_ERR_ARG;
     if (n_reads_out) *n_reads_out = 0;
-    // whatever happens below, the context holds no batch until this call has succeeded
-    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
-    c->fq_hdr_bytes = c->fq_qual_bytes = 0; c->fq_ms = 0.f;
+    fq_forget_batch(c);
     if (!in) { snprintf(c->err, 512, "dg_batch_upload_fastq: the input is NULL"); return DG_ERR_ARG; }
     const size_t n1 = in->text1 ? in->n1 : 0, n2 = in->text2 ? in->n2 : 0;
     const bool two = in->text2 != nullptr && in->n2 > 0;
@@ -1163,70 +1269,180 @@ extern "C" int dg_batch_upload_fastq(dg_ctx *c, const dg_fastq_text *in, int *n_
     if (n1 >= 0xFFFFFF00ull || n2 >= 0xFFFFFF00ull) { snprintf(c->err, 512, "dg_batch_upload_fastq: a text must be smaller than 2^32 - 256 bytes"); return DG_ERR_ARG; }
     if (n1 == 0 && !two) { c->fq_valid = true; return DG_OK; }       // no text: no reads
     HIPCHK(hipSetDevice(c->device));
-    if (!c->d_fq_info) {
-        HIPCHK(hipMalloc((void **)&c->d_fq_info, sizeof(FqInfo)));
-        HIPCHK(hipHostMalloc((void **)&c->h_fq_info, sizeof(FqInfo), hipHostMallocDefault));
-        for (hipEvent_t &e : c->ev_fq) HIPCHK(hipEventCreate(&e));
-    }
-    // capacities, all from the arguments (nothing is asked of the device before the one wait): a record has at least one byte per existing line, so a
-    // text of n bytes holds at most n + 1 line starts; the three outputs together are never larger than the texts
-    const size_t max_reads = (size_t)in->max_reads;
-    const size_t rec_cap[2] = { two ? (max_reads + 1) / 2 : max_reads, two ? max_reads / 2 : 0 };
-    const size_t nb[2] = { n1, n2 };
-    size_t line_cap[2], tiles[2];
-    for (int f = 0; f < 2; f++) { line_cap[f] = std::min(4 * rec_cap[f] + 1, nb[f] + 1); tiles[f] = (nb[f] + FQ_TILE - 1) / FQ_TILE; }
-    const size_t off2 = (n1 + 16 + 255) & ~(size_t)255, text_bytes = n1 + n2;
-    const size_t tile_stride = std::max(tiles[0], tiles[1]);
-    const size_t reads_bound = std::min(max_reads, (n1 + 4) / 4 + (n2 + 4) / 4);          // (records <= ceil(lines / 4), lines <= bytes + 1)
-    const size_t len_tiles = std::max<size_t>(1, (reads_bound + FQ_THREADS - 1) / FQ_THREADS);
-    HIPCHK(c->fq_text.ensure(off2 + n2 + 32)); HIPCHK(c->fq_lines.ensure(line_cap[0] + line_cap[1] + 2)); HIPCHK(c->fq_tile_cnt.ensure(2 * tile_stride + 1));
-    HIPCHK(c->fq_name_at.ensure(reads_bound + 1)); HIPCHK(c->fq_name_len.ensure(reads_bound + 1)); HIPCHK(c->fq_loc.ensure(3 * (reads_bound + 1))); HIPCHK(c->fq_tile_sum.ensure(3 * len_tiles));
-    HIPCHK(c->fq_hdr_off.ensure(reads_bound + 1)); HIPCHK(c->fq_qual_off.ensure(reads_bound + 1)); HIPCHK(c->fq_hdr.ensure(text_bytes + 1)); HIPCHK(c->fq_qual.ensure(text_bytes + 1));
-    HIPCHK(c->seq.ensure(text_bytes + 64)); HIPCHK(c->seq_off.ensure(reads_bound + 1)); HIPCHK(c->rlen.ensure(reads_bound + 1));
+    FqPlan p;
+    p.n[0] = n1; p.n[1] = n2; p.two = two; p.max_reads = (size_t)in->max_reads;
+    { const int rc = fq_reserve(c, p); if (rc) return rc; }
     if (n1) HIPCHK(hipMemcpyAsync(c->fq_text.p, in->text1, n1, hipMemcpyHostToDevice, c->stream));
-    if (n2) HIPCHK(hipMemcpyAsync(c->fq_text.p + off2, in->text2, n2, hipMemcpyHostToDevice, c->stream));
-    FqText x;
-    x.t[0] = c->fq_text.p; x.t[1] = c->fq_text.p + off2; x.n[0] = (uint32_t)n1; x.n[1] = (uint32_t)n2;
-    x.line_start[0] = c->fq_lines.p; x.line_start[1] = c->fq_lines.p + line_cap[0] + 1; x.line_cap[0] = (uint32_t)line_cap[0]; x.line_cap[1] = (uint32_t)line_cap[1];
-    x.two = two ? 1 : 0;
-    const uint32_t stride = (uint32_t)(reads_bound + 1);
-    const dim3 text_grid((unsigned)std::max<size_t>(1, tile_stride), two ? 2u : 1u);
+    if (n2) HIPCHK(hipMemcpyAsync(c->fq_text.p + p.off2, in->text2, n2, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipEventRecord(c->ev_fq[0], c->stream));
-    k_fq_count<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)tile_stride);
-    k_fq_top<<<1, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)tile_stride, (uint32_t)max_reads, c->d_fq_info);
-    k_fq_lines<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)tile_stride, c->d_fq_info);
-    k_fq_len<<<(unsigned)len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->d_fq_info, c->rlen.p, c->fq_name_at.p, c->fq_name_len.p, c->fq_loc.p, stride, c->fq_tile_sum.p, (uint32_t)len_tiles);
-    k_fq_top3<<<1, FQ_THREADS, 0, c->stream>>>(c->fq_tile_sum.p, (uint32_t)len_tiles, c->d_fq_info);
-    if (reads_bound)
-        k_fq_write<<<(unsigned)reads_bound, 64, 0, c->stream>>>(x, c->d_fq_info, in->rc_odd_reads ? 1 : 0, c->rlen.p, c->fq_name_at.p, c->fq_name_len.p, c->fq_loc.p, stride, c->fq_tile_sum.p,
-                                                                 (uint32_t)len_tiles, c->seq_off.p, c->seq.p, c->fq_hdr_off.p, c->fq_hdr.p, c->fq_qual_off.p, c->fq_qual.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_fq[1], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_fq_info, c->d_fq_info, sizeof(FqInfo), hipMemcpyDeviceToHost, c->stream));
+    { const int rc = fq_enqueue(c, p, in->rc_odd_reads, false, false, true); if (rc) return rc; }
     HIPCHK(wait_stream(c));                                       // the one wait: for the sizes block
-    (void)hipEventElapsedTime(&c->fq_ms, c->ev_fq[0], c->ev_fq[1]);
-    const FqInfo &fi = *c->h_fq_info;
-    if (n_reads_out) *n_reads_out = (int)std::min<uint32_t>(fi.n_reads, 0x7FFFFFFFu);
-    switch (fi.status) {
-    case FQ_OK: break;
-    case FQ_E_COUNT:
-        snprintf(c->err, 512, "dg_batch_upload_fastq: text1 holds %u records and text2 %u: they must be equal, or text1 one more", (fi.n_lines[0] + 3) / 4, (fi.n_lines[1] + 3) / 4);
-        return DG_ERR_ARG;
-    case FQ_E_CAPACITY:
-        snprintf(c->err, 512, "dg_batch_upload_fastq: the texts hold %u reads, max_reads is %d", fi.n_reads, in->max_reads);
-        return DG_ERR_CAPACITY;
-    case FQ_E_EMPTY:
-        snprintf(c->err, 512, "dg_batch_upload_fastq: read %u is a record without bases", fi.bad_read);
-        return DG_ERR_ARG;
-    case FQ_E_LONG:
-        snprintf(c->err, 512, "dg_batch_upload_fastq: read %u is longer than DG_MAX_RLEN (%d)", fi.bad_read, DG_MAX_RLEN);
-        return DG_ERR_ARG;
-    default:
-        snprintf(c->err, 512, "dg_batch_upload_fastq: the bases, names or qualities of the batch exceed 32-bit offsets");
+    return fq_finish(c, "dg_batch_upload_fastq", in->max_reads, n_reads_out, true);
+}
+
+// ------------------------------------------------------------------------------------------
+// BGZF inflated on the device (dg_inflate.h): whole blocks in host memory -> their bytes in HBM; and in front of the FASTQ parser
+// ------------------------------------------------------------------------------------------
+static int inf_state(dg_ctx *c)
+{
+    if (c->d_inf_verdict) return DG_OK;
+    HIPCHK(hipMalloc((void **)&c->d_inf_verdict, 8));
+    HIPCHK(hipHostMalloc((void **)&c->h_inf_verdict, 8, hipHostMallocDefault));
+    for (hipEvent_t &e : c->ev_inf) HIPCHK(hipEventCreate(&e));
+    return DG_OK;
+}
+
+// the compressed bytes of up to two inputs (the second at in_off2 of inf_in) and the table go up; the kernel writes at d_out + the members' out_off
+static int inf_enqueue_copies(dg_ctx *c, const std::vector<InfBlock> &tab, const void *src1, size_t n1, const void *src2, size_t n2, size_t in_off2)
+{
+    HIPCHK(c->inf_in.ensure(std::max(n1, in_off2 + n2) + 8)); HIPCHK(c->inf_tab.ensure(tab.size() + 1)); HIPCHK(c->inf_status.ensure(tab.size() + 1));
+    if (n1) HIPCHK(hipMemcpyAsync(c->inf_in.p, src1, n1, hipMemcpyHostToDevice, c->stream));
+    if (n2) HIPCHK(hipMemcpyAsync(c->inf_in.p + in_off2, src2, n2, hipMemcpyHostToDevice, c->stream));
+    if (!tab.empty()) HIPCHK(hipMemcpyAsync(c->inf_tab.p, tab.data(), tab.size() * sizeof(InfBlock), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_inf_verdict, 0xff, 8, c->stream));
+    return DG_OK;
+}
+static int inf_enqueue_kernel(dg_ctx *c, size_t n_blocks, unsigned char *d_out)
+{
+    if (n_blocks) k_bgzf_inflate<<<(unsigned)((n_blocks + INF_WAVES - 1) / INF_WAVES), 64 * INF_WAVES, 0, c->stream>>>(c->inf_in.p, c->inf_tab.p, (uint32_t)n_blocks, d_out, c->inf_status.p, c->d_inf_verdict);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->h_inf_verdict, c->d_inf_verdict, 8, hipMemcpyDeviceToHost, c->stream));
+    return DG_OK;
+}
+
+extern "C" int dg_inflate_granules(int out[2])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = INF_WAVES; out[1] = (int)INF_ROUND;
+    return DG_OK;
+}
+
+extern "C" int dg_bgzf_inflate(dg_ctx *c, const void *host_bytes, size_t n, size_t *n_out, size_t *n_blocks, float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_out) *n_out = 0;
+    if (n_blocks) *n_blocks = 0;
+    if (device_ms) *device_ms = 0.f;
+    c->inf_valid = false; c->inf_bytes = 0;
+    if (n == 0) { c->inf_valid = true; return DG_OK; }
+    if (!host_bytes) { snprintf(c->err, 512, "dg_bgzf_inflate: the input is NULL"); return DG_ERR_ARG; }
+    std::vector<InfBlock> tab;
+    size_t total = 0, bad = 0;
+    if (const char *why = inf_walk_members((const unsigned char *)host_bytes, n, 0, 0, tab, &total, &bad)) { snprintf(c->err, 512, "dg_bgzf_inflate: block %zu: %s", bad, why); return DG_ERR_ARG; }
+    if (tab.size() > 0x7fffffffull) { snprintf(c->err, 512, "dg_bgzf_inflate: %zu blocks are more than one call takes", tab.size()); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    { const int rc = inf_state(c); if (rc) return rc; }
+    HIPCHK(c->inf_out.ensure(total + 32));
+    { const int rc = inf_enqueue_copies(c, tab, host_bytes, n, nullptr, 0, 0); if (rc) return rc; }
+    HIPCHK(hipEventRecord(c->ev_inf[0], c->stream));
+    { const int rc = inf_enqueue_kernel(c, tab.size(), c->inf_out.p); if (rc) return rc; }
+    HIPCHK(hipEventRecord(c->ev_inf[1], c->stream));
+    HIPCHK(wait_stream(c));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->ev_inf[0], c->ev_inf[1]);
+    if (device_ms) *device_ms = ms;
+    if (n_blocks) *n_blocks = tab.size();
+    const unsigned long long v = *c->h_inf_verdict;
+    if (v != ~0ull) { snprintf(c->err, 512, "dg_bgzf_inflate: block %llu: %s", v >> 8, inf_rule((uint32_t)(v & 0xffu))); return DG_ERR_ARG; }
+    c->inf_valid = true; c->inf_bytes = total;
+    if (n_out) *n_out = total;
+    return DG_OK;
+}
+
+extern "C" int dg_inflate_download(dg_ctx *c, void *out, size_t cap)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->inf_valid) { snprintf(c->err, 512, "dg_inflate_download: no inflated bytes (dg_bgzf_inflate first)"); return DG_ERR_ARG; }
+    if (cap < c->inf_bytes) { snprintf(c->err, 512, "dg_inflate_download: output capacity too small: %zu bytes of %zu", cap, c->inf_bytes); return DG_ERR_CAPACITY; }
+    if (c->inf_bytes == 0) return DG_OK;
+    if (!out) return DG_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(out, c->inf_out.p, c->inf_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_inflate_device(dg_ctx *c, void **ptr, size_t *n_out)
+{
+    if (!c || !ptr || !n_out) return DG_ERR_ARG;
+    if (!c->inf_valid) { snprintf(c->err, 512, "dg_inflate_device: no inflated bytes (dg_bgzf_inflate first)"); return DG_ERR_ARG; }
+    *ptr = c->inf_bytes ? c->inf_out.p : nullptr; *n_out = c->inf_bytes;
+    return DG_OK;
+}
+
+extern "C" int dg_batch_upload_fastq_bgzf(dg_ctx *c, const dg_fastq_bgzf *in, uint32_t flags, int *n_reads_out, size_t tail[2], uint64_t *n_unlike)
+{
+    static const char *fn = "dg_batch_upload_fastq_bgzf";
+    if (!c) return DG_ERR_ARG;
+    if (n_reads_out) *n_reads_out = 0;
+    if (tail) tail[0] = tail[1] = 0;
+    if (n_unlike) *n_unlike = 0;
+    fq_forget_batch(c);
+    if (!in) { snprintf(c->err, 512, "%s: the input is NULL", fn); return DG_ERR_ARG; }
+    if (flags & ~DG_FQ_CHECK_ONLY) { snprintf(c->err, 512, "%s: unknown flag bits 0x%x", fn, flags & ~DG_FQ_CHECK_ONLY); return DG_ERR_ARG; }
+    const bool check_only = (flags & DG_FQ_CHECK_ONLY) != 0, two = in->blocks2 != nullptr || in->head2 != nullptr, last = in->last != 0;
+    if ((in->n_head1 && !in->head1) || (in->n_blocks1 && !in->blocks1) || (in->n_head2 && !in->head2) || (in->n_blocks2 && !in->blocks2) || in->max_reads < 0) {
+        snprintf(c->err, 512, "%s: a length without its pointer, or max_reads is negative", fn); return DG_ERR_ARG;
+    }
+    // the members of both inputs, before anything is enqueued: text f = head f ++ its blocks' bytes, in fq_text at 0 / off2
+    const size_t nh[2] = { in->head1 ? in->n_head1 : 0, in->head2 ? in->n_head2 : 0 }, nb[2] = { in->blocks1 ? in->n_blocks1 : 0, two && in->blocks2 ? in->n_blocks2 : 0 };
+    const unsigned char *src[2] = { (const unsigned char *)in->blocks1, (const unsigned char *)in->blocks2 };
+    const size_t in_off2 = (nb[0] + 255) & ~(size_t)255;
+    std::vector<InfBlock> tab;
+    size_t n_inf[2] = {0, 0}, first2 = 0;
+    for (int f = 0; f < (two ? 2 : 1); f++) {
+        size_t bad = 0;
+        if (f) first2 = tab.size();
+        if (const char *why = inf_walk_members(src[f], nb[f], f ? in_off2 : 0, nh[f], tab, &n_inf[f], &bad)) { snprintf(c->err, 512, "%s: text %d block %zu: %s", fn, f + 1, bad, why); return DG_ERR_ARG; }
+        if (nh[f] + n_inf[f] >= 0xFFFFFF00ull) { snprintf(c->err, 512, "%s: a text must be smaller than 2^32 - 256 bytes", fn); return DG_ERR_ARG; }
+    }
+    if (!two) first2 = tab.size();
+    if (tab.size() > 0x7fffffffull) { snprintf(c->err, 512, "%s: %zu blocks are more than one call takes", fn, tab.size()); return DG_ERR_ARG; }
+    FqPlan p;
+    p.n[0] = nh[0] + n_inf[0]; p.n[1] = nh[1] + n_inf[1]; p.two = two; p.max_reads = (size_t)in->max_reads;
+    if (p.n[0] == 0 && p.n[1] == 0) { c->fq_valid = !check_only; c->no_batch = check_only; c->fq_tail_valid = true; return DG_OK; }       // no text: no reads, no tails
+    HIPCHK(hipSetDevice(c->device));
+    { const int rc = inf_state(c); if (rc) return rc; }
+    { const int rc = fq_reserve(c, p); if (rc) return rc; }
+    for (size_t k = first2; k < tab.size(); k++) tab[k].out_off += p.off2;
+    c->fq_tail_off2 = (p.n[0] + 255) & ~(size_t)255;
+    HIPCHK(c->fq_tail.ensure(c->fq_tail_off2 + p.n[1] + 16));
+    { const int rc = inf_enqueue_copies(c, tab, src[0], nb[0], src[1], nb[1], in_off2); if (rc) return rc; }
+    if (nh[0]) HIPCHK(hipMemcpyAsync(c->fq_text.p, in->head1, nh[0], hipMemcpyHostToDevice, c->stream));
+    if (nh[1]) HIPCHK(hipMemcpyAsync(c->fq_text.p + p.off2, in->head2, nh[1], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev_fq[0], c->stream));
+    { const int rc = inf_enqueue_kernel(c, tab.size(), c->fq_text.p); if (rc) return rc; }
+    { const int rc = fq_enqueue(c, p, in->rc_odd_reads, !last, true, !check_only); if (rc) return rc; }
+    HIPCHK(wait_stream(c));                                       // the one wait: for the first failing block and the sizes block
+    const unsigned long long v = *c->h_inf_verdict;
+    if (v != ~0ull) {                                             // (the parser ran over bytes that mean nothing: its verdict is not looked at)
+        const size_t k = (size_t)(v >> 8);
+        snprintf(c->err, 512, "%s: text %d block %zu: %s", fn, k >= first2 ? 2 : 1, k >= first2 ? k - first2 : k, inf_rule((uint32_t)(v & 0xffu)));
         return DG_ERR_ARG;
     }
-    c->n_reads = (int)fi.n_reads; c->max_rlen = (int)fi.max_rlen; c->seq_bytes = (size_t)fi.total[0];
-    c->fq_hdr_bytes = (size_t)fi.total[1]; c->fq_qual_bytes = (size_t)fi.total[2]; c->fq_valid = true;
+    const FqInfo &fi = *c->h_fq_info;
+    if (n_unlike) *n_unlike = fi.n_unlike;
+    const int rc = fq_finish(c, fn, in->max_reads, n_reads_out, !check_only);
+    if (fi.status == FQ_OK || fi.status == FQ_E_EMPTY || fi.status == FQ_E_LONG || fi.status == FQ_E_OFFSETS) {      // the lines were found: the tails are known
+        c->fq_tail_n[0] = p.n[0] - fi.tail_at[0]; c->fq_tail_n[1] = two ? p.n[1] - fi.tail_at[1] : 0;
+        c->fq_tail_valid = true;
+        if (tail) { tail[0] = c->fq_tail_n[0]; tail[1] = c->fq_tail_n[1]; }
+    }
+    if (rc == DG_OK && check_only) c->no_batch = true;
+    return rc;
+}
+
+extern "C" int dg_batch_download_fastq_tail(dg_ctx *c, char *tail1, size_t cap1, char *tail2, size_t cap2)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->fq_tail_valid) { snprintf(c->err, 512, "dg_batch_download_fastq_tail: no tails (dg_batch_upload_fastq_bgzf first)"); return DG_ERR_ARG; }
+    if (cap1 < c->fq_tail_n[0] || cap2 < c->fq_tail_n[1]) { snprintf(c->err, 512, "dg_batch_download_fastq_tail: output capacity too small (need %zu %zu)", c->fq_tail_n[0], c->fq_tail_n[1]); return DG_ERR_CAPACITY; }
+    if ((c->fq_tail_n[0] && !tail1) || (c->fq_tail_n[1] && !tail2)) return DG_ERR_ARG;
+    if (!c->fq_tail_n[0] && !c->fq_tail_n[1]) return DG_OK;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->fq_tail_n[0]) HIPCHK(hipMemcpyAsync(tail1, c->fq_tail.p, c->fq_tail_n[0], hipMemcpyDeviceToHost, c->stream));
+    if (c->fq_tail_n[1]) HIPCHK(hipMemcpyAsync(tail2, c->fq_tail.p + c->fq_tail_off2, c->fq_tail_n[1], hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
     return DG_OK;
 }
 
@@ -1675,7 +1891,9 @@ static int finish_run(dg_ctx *c, size_t used[3])
 extern "C" int dg_batch_run(dg_ctx *c, size_t used[3])
 {
     if (!c) return DG_ERR_ARG;
+    if (c->no_batch) { snprintf(c->err, 512, "dg_batch_run: the context holds no batch (its last upload was a DG_FQ_CHECK_ONLY)"); return DG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
+    c->inf_valid = false;
     c->used[0] = c->used[1] = c->used[2] = 0;
     memset(c->counters, 0, sizeof c->counters);
     if (used) used[0] = used[1] = used[2] = 0;

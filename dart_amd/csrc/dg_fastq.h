@@ -9,6 +9,11 @@
 //                exclusive scans of its 256 x 3 lengths and their sums
 //   k_fq_top3    one workgroup: exclusive scans of the workgroup sums (64 bit), the totals, the status
 //   k_fq_write   wave = read: bases (reverse-complemented for a stored mate 2), name and quality (reversed for a stored mate 2) lane beside lane
+// A text that is a piece of a file (dg_batch_upload_fastq_bgzf without `last`: the blocks of a compressed file do not end where records end) is taken in
+// whole records -- four lines, each ended by its newline; two texts give the same number of records, the smaller of the two counts -- by k_fq_top's `whole`
+// mode; what lies behind the last record taken is the text's tail:
+//   k_fq_tail    where each text's tail begins, and its bytes into a buffer of their own (the next call's head)
+//   k_fq_unlike  wave = read: counts the records the reference's gz reader (gzgets into 1024 bytes) and its plain reader would read differently
 // Plain scans in launches (no look-back: an upload never runs twice).  Every byte's place follows from the scanned lengths alone, so the batch is the
 // same whatever the grid.
 #ifndef DG_FASTQ_H
@@ -76,6 +81,15 @@ FQ_HD int64_t fq_read_count(bool two, uint64_t rec1, uint64_t rec2)
     if (rec1 == rec2 + 1) return (int64_t)(2 * rec2 + 1);
     return -1;
 }
+// whole records only: a text with `nl` newlines holds nl / 4 of them; two texts give the smaller count each
+FQ_HD uint64_t fq_whole_records(bool two, uint64_t nl1, uint64_t nl2) { const uint64_t a = nl1 / 4, b = nl2 / 4; return !two ? a : a < b ? a : b; }
+// Would the reference's gz reader (gzGetNextEntry, GetData.cpp:181-210: gzgets into 1024 bytes, strlen) read this record as its plain reader does?  The rules
+// of the host program's gz_reader_sees_the_same on the four line lengths (newlines included, 0 = the line does not exist); a NUL in the record is the caller's.
+FQ_HD bool fq_gz_reader_same(const char *text, uint64_t off, uint32_t l0, uint32_t l1, uint32_t l2, uint32_t l3)
+{
+    if (!(l0 >= 2u && l1 >= 2u && l2 >= 1u && l3 >= 1u && l0 < 1024u && l1 < 1024u && l2 < 1024u && l3 < 1024u && text[off] == '@')) return false;
+    return fq_hdr_end(text + off, (int64_t)l0) - fq_hdr_beg(text + off, (int64_t)l0) > 0;       // the name must not be empty (GetData.cpp:194)
+}
 FQ_HD bool fq_stored_rc(uint32_t k, int rc_odd_reads) { return rc_odd_reads && (k & 1u); }
 // byte i of the stored read / the stored quality (GetData.cpp:157-166: an odd read of a pair is kept reverse-complemented, its quality reversed)
 FQ_HD char fq_stored_base(const char *line1, uint32_t rlen, uint32_t i, bool rc) { return rc ? fq_comp_base(line1[rlen - 1u - i]) : line1[i]; }
@@ -90,6 +104,7 @@ struct FqInfo {
     unsigned long long total[3];           // bases, name bytes, quality bytes
     uint32_t n_nl[2], n_lines[2];          // per text: newlines; lines (a last line without '\n' counts)
     uint32_t n_reads, max_rlen, status, bad_read, bad_long, pad;
+    uint32_t tail_at[2], n_unlike, pad2;   // whole-record mode: where each text's tail begins; records the reference's gz reader would read differently
 };
 struct FqText {
     const unsigned char *t[2]; uint32_t n[2];      // the texts in HBM (16-byte aligned, readable up to the next multiple of 16) and their lengths
@@ -137,8 +152,9 @@ k_fq_count(const FqText x, uint32_t *__restrict__ tile_cnt, uint32_t tile_stride
 }
 
 // tile_cnt becomes its exclusive scan; info: lines per text, the number of reads, FQ_E_COUNT / FQ_E_CAPACITY
+// whole: the texts are pieces of files: whole records only, the same number from each text; n_lines becomes the lines of the records taken
 __global__ void __launch_bounds__(FQ_THREADS)
-k_fq_top(const FqText x, uint32_t *__restrict__ tile_cnt, uint32_t tile_stride, uint32_t max_reads, FqInfo *__restrict__ info)
+k_fq_top(const FqText x, uint32_t *__restrict__ tile_cnt, uint32_t tile_stride, uint32_t max_reads, FqInfo *__restrict__ info, int whole)
 {
     __shared__ uint32_t s_w[FQ_THREADS / 64];
     __shared__ uint32_t s_lines[2];
@@ -162,7 +178,11 @@ k_fq_top(const FqText x, uint32_t *__restrict__ tile_cnt, uint32_t tile_stride, 
     __syncthreads();
     if (threadIdx.x == 0) {
         if (!x.two) { info->n_nl[1] = 0; info->n_lines[1] = 0; s_lines[1] = 0; }
-        const uint64_t rec1 = ((uint64_t)s_lines[0] + 3) / 4, rec2 = ((uint64_t)s_lines[1] + 3) / 4;
+        uint64_t rec1 = ((uint64_t)s_lines[0] + 3) / 4, rec2 = ((uint64_t)s_lines[1] + 3) / 4;
+        if (whole) {
+            rec1 = fq_whole_records(x.two != 0, info->n_nl[0], info->n_nl[1]); rec2 = x.two ? rec1 : 0;
+            info->n_lines[0] = (uint32_t)(4 * rec1); info->n_lines[1] = (uint32_t)(4 * rec2);
+        }
         const int64_t n = fq_read_count(x.two != 0, rec1, rec2);
         uint32_t status = FQ_OK;
         if (n < 0) status = FQ_E_COUNT;
@@ -170,6 +190,7 @@ k_fq_top(const FqText x, uint32_t *__restrict__ tile_cnt, uint32_t tile_stride, 
         info->n_reads = n < 0 ? 0u : (uint32_t)(n > 0xFFFFFFFFll ? 0xFFFFFFFFll : n);
         info->status = status; info->max_rlen = 0; info->bad_read = 0xFFFFFFFFu; info->bad_long = 0xFFFFFFFFu; info->pad = 0;
         info->total[0] = info->total[1] = info->total[2] = 0;
+        info->tail_at[0] = x.n[0]; info->tail_at[1] = x.two ? x.n[1] : 0u; info->n_unlike = 0; info->pad2 = 0;
     }
 }
 
@@ -208,6 +229,39 @@ __device__ __forceinline__ uint32_t fq_dev_line(const FqText &x, const FqInfo *i
     start = x.line_start[f][i];
     const uint32_t end = i < info->n_nl[f] ? x.line_start[f][i + 1] : x.n[f];
     return end - start;
+}
+
+// whole-record mode, behind k_fq_lines: text f's tail begins behind the last line taken; its bytes go to tail (text 2's at tail_off2)
+__global__ void __launch_bounds__(FQ_THREADS)
+k_fq_tail(const FqText x, FqInfo *info, unsigned char *__restrict__ tail, uint32_t tail_off2)
+{
+    if (info->status != FQ_OK) return;
+    const int f = (int)blockIdx.y;
+    if (f && !x.two) return;
+    const uint32_t taken = info->n_lines[f];
+    const uint32_t at = taken ? x.line_start[f][taken] : 0u;          // (taken <= the text's newlines: the entry exists, and taken < line_cap)
+    if (blockIdx.x == 0 && threadIdx.x == 0) info->tail_at[f] = at;
+    unsigned char *dst = tail + (f ? tail_off2 : 0u);
+    for (uint64_t i = (uint64_t)at + blockIdx.x * FQ_THREADS + threadIdx.x; i < x.n[f]; i += (uint64_t)gridDim.x * FQ_THREADS) dst[i - at] = x.t[f][i];
+}
+
+// One wave per read, behind k_fq_lines: the record's four lines against fq_gz_reader_same, its bytes against NUL
+__global__ void __launch_bounds__(64)
+k_fq_unlike(const FqText x, FqInfo *info)
+{
+    if (info->status != FQ_OK) return;
+    const uint32_t k = blockIdx.x, lane = threadIdx.x;
+    if (k >= info->n_reads) return;
+    int f; uint32_t rec;
+    fq_read_place(k, x.two != 0, f, rec);
+    uint32_t s0, s1, s2, s3;
+    const uint32_t l0 = fq_dev_line(x, info, f, 4ull * rec, s0), l1 = fq_dev_line(x, info, f, 4ull * rec + 1, s1);
+    const uint32_t l2 = fq_dev_line(x, info, f, 4ull * rec + 2, s2), l3 = fq_dev_line(x, info, f, 4ull * rec + 3, s3);
+    const char *t = (const char *)x.t[f];
+    bool nul = false;
+    for (uint32_t i = lane; i < l0 + l1 + l2 + l3; i += 64) nul |= t[s0 + i] == 0;      // (the lines of a record lie one behind the other)
+    const bool bad = __any(nul) || !fq_gz_reader_same(t, s0, l0, l1, l2, l3);
+    if (lane == 0 && bad) atomicAdd(&info->n_unlike, 1u);
 }
 
 // loc / tile_sum hold three rows (bases, name bytes, quality bytes) of `stride` / n_tiles entries

@@ -574,11 +574,33 @@ int main(int argc, char *argv[])
         }
         return true;
     };
-    bool gz_first = false;
+    // DART_DEVICE_GZ=1 beside DART_DEVICE_FASTQ=1 and a device formatter (DART_DEVICE_SAM=1, or DART_DEVICE_BAM=1 with -bo: the host never holds the names and
+    // qualities): a library whose files are all FASTQ .gz with a BGZF block in front is inflated on the device too (GzDevPlan, fast_fastq.h).  Anything else
+    // -- also a library its check pass turns down -- runs as without the switch.
+    auto env_on = [](const char *k) { return getenv(k) && atoi(getenv(k)) != 0; };
+    const bool device_gz = env_on("DART_DEVICE_GZ") && env_on("DART_DEVICE_FASTQ") && !bam_streams && !getenv("DART_STREAMING") && (device_bam || (!o.bam && env_on("DART_DEVICE_SAM")));
+    auto starts_with_bgzf = [](const std::string &fn) -> bool {
+        unsigned char h[18 + 256]; FILE *f = fopen(fn.c_str(), "rb");
+        if (!f) return false;
+        const size_t got = fread(h, 1, sizeof h, f); fclose(f);
+        if (got < 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || h[3] != 4) return false;
+        const size_t xlen = (size_t)h[10] | (size_t)h[11] << 8;
+        for (size_t x = 12; x + 4 <= 12 + xlen && x + 4 <= got;) { const size_t slen = (size_t)h[x + 2] | (size_t)h[x + 3] << 8; if (h[x] == 'B' && h[x + 1] == 'C' && slen == 2) return true; x += 4 + slen; }
+        return false;
+    };
+    auto gz_device_candidate = [&](size_t lib) -> bool {
+        if (!device_gz) return false;
+        const bool two = o.f1.size() == o.f2.size();
+        const std::string *fns[2] = {&o.f1[lib], two ? &o.f2[lib] : nullptr};
+        for (const std::string *fn : fns) if (fn && (!is_gz(*fn) || !starts_with_bgzf(*fn) || !check_read_format(fn->c_str()))) return false;
+        return true;
+    };
+    bool gz_first = false, gz_device_first = false;
     {
         const std::string &fn0 = o.f1[0];
         const bool two = o.f1.size() == o.f2.size();
-        if (!bam_streams && !getenv("DART_STREAMING") && !is_gz(fn0) && check_read_format(fn0.c_str())) {
+        if (gz_device_candidate(0)) fast_first = gz_device_first = true;      // (its files are mapped when its turn comes: nothing to start here)
+        else if (!bam_streams && !getenv("DART_STREAMING") && !is_gz(fn0) && check_read_format(fn0.c_str())) {
             fast_first = true;
             if (!two || !is_gz(o.f2[0])) pre.start(fn0.c_str(), two ? o.f2[0].c_str() : nullptr, o.threads);
         } else if (gz_whole_candidate(0)) {
@@ -715,11 +737,26 @@ int main(int argc, char *argv[])
     if (o.silent) fprintf(stdout, "Start read mapping...\n");
     bool pair_end = o.pair_end;
     for (size_t lib = 0; lib < o.f1.size(); lib++) {
+        if (gz_device_candidate(lib)) {   // BGZF FASTQ inflated on the device: the plan's check pass decides
+            const bool sep = o.f1.size() == o.f2.size();
+            GzDevPlan plan;
+            if (plan.make(o.f1[lib].c_str(), sep ? o.f2[lib].c_str() : nullptr, pair_end || sep, batch_reads, ctx[0])) {
+                if (sep) pair_end = true;
+                uint64_t off = 0; const int out_fd = out_begin(off);
+                std::string ferr; FastStats fst;
+                const int frc = run_fast_library(o.f1[lib].c_str(), sep ? o.f2[lib].c_str() : nullptr, pair_end, o.threads, batch_reads, ctx, o.p, ix.names, o.unique, o.multi, o.silent,
+                                                 out_fd, &off, total, sjmap, t0, ferr, fst, pool, nullptr, &plan);
+                out_end(off);
+                if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
+                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), gz=device (check pass over every block %.3f s; %zu chunks, waits for the tail chain %.3f s summed over workers), %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_gz_check, plan.chunks.size(), fst.t_gz_tail, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "");
+                continue;
+            }
+        }
         {   // .gz FASTQ inflated whole: the parallel pipeline on the inflated text (library 0's files have been inflating since before the GPU was touched)
             std::unique_ptr<FastqIndex> own_gz;
             FastqIndex *gi = nullptr;
             if (lib == 0 && gz_first) { pre.wait(); gi = &pre; }
-            else if (lib > 0 && gz_whole_candidate(lib)) { own_gz.reset(new FastqIndex()); own_gz->run(o.f1[lib].c_str(), o.f1.size() == o.f2.size() ? o.f2[lib].c_str() : nullptr, o.threads, true, gz_whole_max); gi = own_gz.get(); }
+            else if ((lib > 0 || gz_device_first) && gz_whole_candidate(lib)) { own_gz.reset(new FastqIndex()); own_gz->run(o.f1[lib].c_str(), o.f1.size() == o.f2.size() ? o.f2[lib].c_str() : nullptr, o.threads, true, gz_whole_max); gi = own_gz.get(); }
             if (gi && gi->ok) {
                 const bool sep = o.f1.size() == o.f2.size();
                 if (sep) pair_end = true;

@@ -371,10 +371,12 @@ struct FastSlot {                       // one batch travelling through the stag
     char *seq = nullptr; size_t seq_cap = 0, n_cap = 0;            // page-locked
     dg_read_out *ro = nullptr; dg_report_out *po = nullptr; uint32_t *cig = nullptr; dg_sj_out *sj = nullptr; size_t caps[3] = {0, 0, 0}, used[3] = {0, 0, 0};
     const char *fq1 = nullptr, *fq2 = nullptr; size_t fq_n1 = 0, fq_n2 = 0; bool fq_device = false;      // device parser: the batch's byte range of each mapped file
+    int gz_chunk = -1;                  // DART_DEVICE_GZ: the ranges are whole BGZF blocks of the compressed files, chunk gz_chunk of the library's plan
     int rc = 0; std::string err;
 };
 
 struct FastStats { double t_index = 0, t_asm = 0, t_map = 0, t_fmt = 0, t_write = 0, t_alloc = 0, t_gather = 0, t_dev_call = 0, t_dev_kernels = 0, t_download = 0; size_t n_batches = 0;
+                   bool gz_device = false; double t_gz_check = 0, t_gz_tail = 0;      // the library's .gz files were inflated on the device: the check pass / waiting for and downloading the tails
                    bool fq_device = false; double t_fq_call = 0, t_fq_kernels = 0; };      // the library's batches were parsed on the device: dg_batch_upload_fastq, sum over workers / its kernels
 
 // Batch arenas: ordinary memory by default -- page-locking costs ~1 s per GB, more than a short job saves; DART_PINNED=1 page-locks them
@@ -460,12 +462,98 @@ struct FastqIndex {
     ~FastqIndex() { wait(); }
 };
 
+// DART_DEVICE_GZ=1: a library of BGZF-compressed FASTQ files goes to the GPU as it lies on the disk (dg_batch_upload_fastq_bgzf): the files are mapped,
+// cut into chunks of whole blocks (by the blocks' ISIZE, to about a batch of reads), and every chunk is inflated and parsed in HBM.  Blocks do not end where
+// records end: what lies behind a chunk's last whole record (its tail) is downloaded and goes in front of the next chunk, so the uploads are ordered.
+// The plan is made by a first pass over all chunks with DG_FQ_CHECK_ONLY: it finds a corrupt block, and a record the reference's gz reader would read in its
+// own way, before a byte of output exists -- such a library takes the host's path -- and it leaves every chunk's number of reads.
+struct GzDevPlan {
+    struct Member { size_t off; uint32_t bsize, isize; };
+    struct Chunk { size_t a1, b1, a2, b2; int n_reads; bool last; };
+    MappedFile m1, m2; bool two = false;
+    std::vector<Chunk> chunks; size_t total_reads = 0; double t_check = 0;
+    // the mapping pass: whose turn it is to upload, and the tails the turn before left
+    std::mutex mu; std::condition_variable cv; size_t turn = 0; std::vector<char> tail1, tail2;
+
+    // the members of a mapped file; false: not BGZF all the way (the library's own walk will say the same)
+    static bool members(const MappedFile &mf, std::vector<Member> &out) {
+        const unsigned char *p = (const unsigned char *)mf.p;
+        for (size_t at = 0; at < mf.n;) {
+            if (mf.n - at < 12 || p[at] != 0x1f || p[at + 1] != 0x8b || p[at + 2] != 8 || p[at + 3] != 4) return false;
+            const size_t xlen = (size_t)p[at + 10] | (size_t)p[at + 11] << 8;
+            if (mf.n - at - 12 < xlen) return false;
+            size_t bsize = 0;
+            for (size_t x = at + 12, xe = at + 12 + xlen; x + 4 <= xe;) {
+                const size_t slen = (size_t)p[x + 2] | (size_t)p[x + 3] << 8;
+                if (xe - x - 4 < slen) break;
+                if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2) { bsize = ((size_t)p[x + 4] | (size_t)p[x + 5] << 8) + 1; break; }
+                x += 4 + slen;
+            }
+            if (!bsize || bsize > mf.n - at || bsize < 12 + xlen + 8) return false;
+            uint32_t isize; memcpy(&isize, p + at + bsize - 4, 4);
+            if (isize > 65536) return false;
+            out.push_back(Member{at, (uint32_t)bsize, isize});
+            at += bsize;
+        }
+        return true;
+    }
+    // one chunk through the library; the tails replace the heads
+    static int upload(dg_ctx *c, const GzDevPlan &P, const Chunk &k, std::vector<char> &h1, std::vector<char> &h2, bool pair_end, int max_reads, uint32_t flags, int *n, uint64_t *unlike) {
+        dg_fastq_bgzf in;
+        in.head1 = h1.data(); in.n_head1 = h1.size(); in.blocks1 = P.m1.p + k.a1; in.n_blocks1 = k.b1 - k.a1;
+        in.head2 = P.two ? h2.data() : nullptr; in.n_head2 = P.two ? h2.size() : 0; in.blocks2 = P.two ? P.m2.p + k.a2 : nullptr; in.n_blocks2 = P.two ? k.b2 - k.a2 : 0;
+        in.rc_odd_reads = pair_end ? 1 : 0; in.max_reads = max_reads; in.last = k.last ? 1 : 0;
+        size_t tail[2] = {0, 0};
+        int rc = dg_batch_upload_fastq_bgzf(c, &in, flags, n, tail, unlike);
+        if (rc) return rc;
+        std::vector<char> t1(tail[0] + 1), t2(tail[1] + 1);
+        rc = dg_batch_download_fastq_tail(c, t1.data(), tail[0], t2.data(), tail[1]);
+        if (rc) return rc;
+        t1.resize(tail[0]); t2.resize(tail[1]); h1.swap(t1); h2.swap(t2);
+        return 0;
+    }
+    // false: the library is not one for this path (the caller takes the host's, silently)
+    bool make(const char *f1, const char *f2, bool pair_end, size_t batch_reads, dg_ctx *c) {
+        const double t = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+        two = f2 != nullptr;
+        if (pair_end && !two) return false;                   // (interlaced pairs: a chunk would have to end on an even record)
+        if (!m1.open(f1) || (two && !m2.open(f2))) return false;
+        std::vector<Member> M1, M2;
+        if (!members(m1, M1) || (two && !members(m2, M2)) || M1.empty() || (two && M2.empty())) return false;
+        const size_t target = std::max<size_t>(1, two ? batch_reads / 2 : batch_reads);      // records of each text per chunk
+        double bpr1 = 125, bpr2 = 125;                        // bytes per record: a first guess, then what the last chunk had
+        std::vector<char> h1, h2;
+        for (size_t i1 = 0, i2 = 0; i1 < M1.size() || i2 < M2.size();) {
+            size_t j1 = i1, j2 = i2, sum1 = 0, sum2 = 0;
+            while (j1 < M1.size() && (double)sum1 < (double)target * bpr1) sum1 += M1[j1++].isize;
+            while (j2 < M2.size() && (double)sum2 < (double)target * bpr2) sum2 += M2[j2++].isize;
+            if (h1.size() + sum1 >= 0xFFFFFF00ull || h2.size() + sum2 >= 0xFFFFFF00ull) return false;
+            Chunk k;
+            k.a1 = i1 < M1.size() ? M1[i1].off : m1.n; k.b1 = j1 < M1.size() ? M1[j1].off : m1.n;
+            k.a2 = i2 < M2.size() ? M2[i2].off : m2.n; k.b2 = j2 < M2.size() ? M2[j2].off : m2.n;
+            k.last = j1 == M1.size() && j2 == M2.size(); k.n_reads = 0;
+            const size_t in1 = h1.size() + sum1, in2 = h2.size() + sum2;
+            uint64_t unlike = 0;
+            const size_t room = (in1 + in2) / 4 + 2;
+            if (upload(c, *this, k, h1, h2, pair_end, (int)std::min<size_t>(room, 0x7FFFFFFF), DG_FQ_CHECK_ONLY, &k.n_reads, &unlike) != 0 || unlike) return false;
+            if (pair_end && (k.n_reads & 1)) return false;    // (an unpaired tail is the host's business)
+            const size_t rec = two ? (size_t)(k.n_reads + 1) / 2 : (size_t)k.n_reads;
+            if (rec) { bpr1 = std::max(16.0, (double)(in1 - h1.size()) / (double)rec); if (two && k.n_reads > 1) bpr2 = std::max(16.0, (double)(in2 - h2.size()) / (double)(k.n_reads / 2)); }
+            chunks.push_back(k); total_reads += (size_t)k.n_reads;
+            i1 = j1; i2 = j2;
+        }
+        t_check = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t;
+        return !chunks.empty();
+    }
+};
+
 // Maps one library of plain FASTQ files.  f2 == nullptr: one file (single-end, or interlaced pairs when pair_end).
+// gzp: the library is BGZF-compressed and gzp holds its plan (DART_DEVICE_GZ): the batches are the plan's chunks, inflated and parsed on the device.
 // Returns 0, or the failing dg status (message in err).  SAM text goes to fd at *file_off (advanced).
 static int run_fast_library(const char *f1, const char *f2, bool pair_end, int threads, size_t batch_reads, const std::vector<dg_ctx *> &ctx, const dg_params &base_params,
                             const std::vector<std::string> &names, bool unique_only, bool multi, bool silent, int fd, uint64_t *file_off,
                             Counters &total, std::map<std::pair<int64_t, int64_t>, int> &sjmap, time_t t0, std::string &err, FastStats &st, SlotPool &pool,
-                            FastqIndex *pre = nullptr)
+                            FastqIndex *pre = nullptr, GzDevPlan *gzp = nullptr)
 {
     auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const int T = std::max(1, threads);
@@ -478,9 +566,12 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
     const char *wm = getenv("DART_WRITE");
     const bool use_mmap = wm && strcmp(wm, "mmap") == 0;          // default pwrite (measured on tmpfs: 5.1 GB/s against 3.2 GB/s through a shared mapping)
     FastqIndex own;                                   // (unless the caller has indexed this library already, beside dg_init)
-    if (pre) pre->wait();
-    if (!pre || pre->f1 != f1 || pre->f2 != (f2 ? f2 : "")) { pre = &own; own.run(f1, f2, T); }
-    if (!pre->ok) { err = "cannot map the read files"; return DG_ERR_ARG; }
+    if (gzp) pre = &own;                              // (no record index: the host never sees the text)
+    else {
+        if (pre) pre->wait();
+        if (!pre || pre->f1 != f1 || pre->f2 != (f2 ? f2 : "")) { pre = &own; own.run(f1, f2, T); }
+        if (!pre->ok) { err = "cannot map the read files"; return DG_ERR_ARG; }
+    }
     MappedFile &m1 = pre->m1, &m2 = pre->m2;
     std::vector<FqRec> &r1 = pre->r1, &r2 = pre->r2;
     const bool e1 = pre->e1, e2 = pre->e2;
@@ -535,8 +626,9 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
         if (f2) { mf = (k & 1) ? &m2 : &m1; return (k & 1) ? r2[k >> 1] : r1[k >> 1]; }
         mf = &m1; return r1[k];
     };
+    if (gzp) { n_total = gzp->total_reads; odd_from = n_total; st.gz_device = true; st.t_gz_check += gzp->t_check; }
     if (batch_reads & 1) batch_reads++;
-    const bool fq_device = g_device_fastq && !explicit_order;      // (an entry without bases ends a chunk: the replayed order is not a byte range)
+    const bool fq_device = gzp || (g_device_fastq && !explicit_order);      // (an entry without bases ends a chunk: the replayed order is not a byte range)
     st.fq_device = fq_device;
     // the bytes of records [a, b) of a mapped file
     auto byte_range = [](const MappedFile &mf, const std::vector<FqRec> &v, size_t a, size_t b, const char *&p, size_t &n) {
@@ -555,7 +647,19 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
 
     std::thread assembler([&]() {
         size_t next = 0, seqno = 0;
-        while (next < n_total) {
+        for (size_t ci = 0; gzp && ci < gzp->chunks.size(); ci++) {      // DART_DEVICE_GZ: a batch is a chunk of the plan
+            FastSlot *s;
+            { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !free_q.empty() || failed; }); if (failed) break; s = free_q.front(); free_q.pop_front(); }
+            const double ta = now();
+            const int n = gzp->chunks[ci].n_reads;
+            s->first = next; s->n = n; s->odd = 0; s->seqno = seqno++; s->rc = 0; s->fq_device = true; s->gz_chunk = (int)ci;
+            { const double tl = now(); const size_t z[3] = {0, 0, 0}; slot_reserve(*s, (size_t)n, 0, z); st.t_alloc += now() - tl; }
+            st.t_asm += now() - ta;
+            next += (size_t)n;
+            { std::lock_guard<std::mutex> lk(mu); map_q.push_back(s); }
+            cv.notify_all();
+        }
+        while (!gzp && next < n_total) {
             FastSlot *s;
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !free_q.empty() || failed; }); if (failed) break; s = free_q.front(); free_q.pop_front(); }
             const double ta = now();
@@ -565,7 +669,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             if (next < odd_from && end > odd_from) end = odd_from;
             if (next >= odd_from) { end = n_total; odd = (int)(end - next); }
             const int n = (int)(end - next);
-            s->first = next; s->n = n; s->odd = odd; s->seqno = seqno++; s->rc = 0; s->fq_device = fq_device;
+            s->first = next; s->n = n; s->odd = odd; s->seqno = seqno++; s->rc = 0; s->fq_device = fq_device; s->gz_chunk = -1;
             if (fq_device) {
                 // the batch is a byte range of each file (next is even: batches and the start of an unpaired tail are); the host keeps views for its
                 // formatter only -- names, bases and qualities where they lie in the mapping, nothing copied
@@ -646,7 +750,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             FastSlot *s;
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !map_q.empty() || asm_done || failed; }); if (failed || map_q.empty()) break; s = map_q.front(); map_q.pop_front(); }
             const double tm = now();
-            double t_fq = 0; float fq_ms = 0.f;
+            double t_fq = 0, t_gz_wait = 0; float fq_ms = 0.f;
             if (!s->rc && s->fq_device) {
                 // upload the text (the device cuts it into the batch) -> run -> download
                 const int n = s->n;
@@ -654,8 +758,18 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 dg_set_params(ctx[w], &p);
                 dg_fastq_text ft; ft.text1 = s->fq1; ft.n1 = s->fq_n1; ft.text2 = s->fq2; ft.n2 = s->fq_n2; ft.rc_odd_reads = pair_end ? 1 : 0; ft.max_reads = n;
                 int got = 0;
-                const double tu = now();
-                int rc = dg_batch_upload_fastq(ctx[w], &ft, &got);
+                double tu = now();
+                int rc;
+                if (s->gz_chunk >= 0) {
+                    // the uploads take turns: this chunk's heads are the tails of the one before
+                    std::unique_lock<std::mutex> lk(gzp->mu);
+                    gzp->cv.wait(lk, [&]() { return gzp->turn == (size_t)s->gz_chunk; });
+                    t_gz_wait = now() - tu; tu = now();
+                    uint64_t unlike = 0;
+                    rc = GzDevPlan::upload(ctx[w], *gzp, gzp->chunks[s->gz_chunk], gzp->tail1, gzp->tail2, pair_end, n, 0u, &got, &unlike);
+                    gzp->turn++;
+                    lk.unlock(); gzp->cv.notify_all();
+                } else rc = dg_batch_upload_fastq(ctx[w], &ft, &got);
                 t_fq = now() - tu;
                 (void)dg_batch_fastq_device_ms(ctx[w], &fq_ms);
                 if (!rc && got != n) { s->rc = DG_ERR_INTERNAL; s->err = "the device parser found " + std::to_string(got) + " reads in a batch of " + std::to_string(n); }
@@ -750,7 +864,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                     if (rc) { s->rc = rc; s->err = dg_last_error(ctx[w]); }
                 }
             }
-            { std::lock_guard<std::mutex> lk(mu); st.t_map += now() - tm - t_gather - t_call - t_dl - t_fq; st.t_fq_call += t_fq; st.t_fq_kernels += fq_ms * 1e-3; st.t_gather += t_gather; st.t_dev_call += t_call; st.t_dev_kernels += dev_ms * 1e-3; st.t_download += t_dl; st.n_batches++; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
+            { std::lock_guard<std::mutex> lk(mu); st.t_map += now() - tm - t_gather - t_call - t_dl - t_fq - t_gz_wait; st.t_gz_tail += t_gz_wait; st.t_fq_call += t_fq; st.t_fq_kernels += fq_ms * 1e-3; st.t_gather += t_gather; st.t_dev_call += t_call; st.t_dev_kernels += dev_ms * 1e-3; st.t_download += t_dl; st.n_batches++; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
             cv.notify_all();
         }
         { std::lock_guard<std::mutex> lk(mu); mappers_left--; }

@@ -105,6 +105,15 @@ class FastqText(C.Structure):
     _fields_ = [("text1", C.c_void_p), ("n1", C.c_size_t), ("text2", C.c_void_p), ("n2", C.c_size_t), ("rc_odd_reads", C.c_int32), ("max_reads", C.c_int32)]
 
 
+class FastqBgzf(C.Structure):
+    _fields_ = [("head1", C.c_void_p), ("n_head1", C.c_size_t), ("blocks1", C.c_void_p), ("n_blocks1", C.c_size_t),
+                ("head2", C.c_void_p), ("n_head2", C.c_size_t), ("blocks2", C.c_void_p), ("n_blocks2", C.c_size_t),
+                ("rc_odd_reads", C.c_int32), ("max_reads", C.c_int32), ("last", C.c_int32)]
+
+
+FQ_CHECK_ONLY = 1           # DG_FQ_CHECK_ONLY: inflate, count and check; no batch is written
+
+
 def flatten_strings(items):
     """list of bytes / str -> (u32 offsets [n + 1], u8 array): the form dg_set_chr_names and dg_batch_format_sam take names and qualities in"""
     bs = [x if isinstance(x, (bytes, bytearray)) else x.encode("latin1") for x in items]
@@ -264,6 +273,13 @@ def _load_lib():
         lib.dg_probe_huff_lengths.argtypes = [vp, vp, C.c_int, C.c_int, vp]
         lib.dg_probe_bgzf_phases.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
         lib.dg_batch_bam_device_ms.argtypes = [vp, vp]
+    if hasattr(lib, "dg_bgzf_inflate"):                      # (likewise: BGZF inflated on the device, in front of the FASTQ parser)
+        lib.dg_bgzf_inflate.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+        lib.dg_inflate_download.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_inflate_device.argtypes = [vp, vp, vp]
+        lib.dg_batch_upload_fastq_bgzf.argtypes = [vp, vp, C.c_uint32, vp, vp, vp]
+        lib.dg_batch_download_fastq_tail.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
+        lib.dg_inflate_granules.argtypes = [vp]
     if hasattr(lib, "dg_sj_finish"):                         # (likewise: the splice-junction table on the device)
         lib.dg_sj_reserve.argtypes = [vp, C.c_size_t]
         lib.dg_sj_reset.argtypes = [vp]
@@ -509,6 +525,56 @@ class DartGPU:
         """(strip, segment) of the device's deflate kernel in bytes (dg_bgzf_granules)"""
         g = (C.c_int * 2)()
         self._chk(self.lib.dg_bgzf_granules(g), "dg_bgzf_granules")
+        return int(g[0]), int(g[1])
+
+    def bgzf_inflate(self, data) -> bytes:
+        """whole BGZF blocks -> their bytes, inflated on the device (dg_bgzf_inflate + dg_inflate_download); self.inflate_device_ms holds the kernel's device
+        time, self.inflate_blocks the number of blocks"""
+        if not hasattr(self.lib, "dg_bgzf_inflate"):
+            raise RuntimeError("this build of libdartgpu.so has no dg_bgzf_inflate")
+        a = np.frombuffer(bytes(data) + b"\0", np.uint8)
+        nb = C.c_size_t(0); nk = C.c_size_t(0); ms = C.c_float(0)
+        self._chk(self.lib.dg_bgzf_inflate(self.ctx, a.ctypes.data, len(a) - 1, C.byref(nb), C.byref(nk), C.byref(ms)), "dg_bgzf_inflate")
+        self.inflate_device_ms = float(ms.value); self.inflate_blocks = int(nk.value)
+        out = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_inflate_download(self.ctx, out.ctypes.data, int(nb.value)), "dg_inflate_download")
+        return out[:int(nb.value)].tobytes()
+
+    def upload_fastq_bgzf(self, head1, blocks1, head2=None, blocks2=None, rc_odd_reads: bool = False, max_reads: int | None = None, last: bool = False,
+                          check_only: bool = False):
+        """FASTQ text as head bytes + BGZF blocks per text -> the batch in HBM (dg_batch_upload_fastq_bgzf) -> (n_reads, tail1, tail2, n_unlike): whole records
+        only unless last; the tails are what lies behind the last record taken (the next call's heads).  head2 and blocks2 None: one text.  check_only: the
+        same counts, no batch.  max_reads None: as many as the texts can hold."""
+        if not hasattr(self.lib, "dg_batch_upload_fastq_bgzf"):
+            raise RuntimeError("this build of libdartgpu.so has no dg_batch_upload_fastq_bgzf")
+        two = head2 is not None or blocks2 is not None
+        bufs = [np.frombuffer(bytes(x if x is not None else b"") + b"\0", np.uint8) for x in (head1, blocks1, head2, blocks2)]
+        t = FastqBgzf()
+        t.head1, t.n_head1, t.blocks1, t.n_blocks1 = bufs[0].ctypes.data, len(bufs[0]) - 1, bufs[1].ctypes.data, len(bufs[1]) - 1
+        if two:
+            t.head2, t.n_head2, t.blocks2, t.n_blocks2 = bufs[2].ctypes.data, len(bufs[2]) - 1, bufs[3].ctypes.data, len(bufs[3]) - 1
+        t.rc_odd_reads, t.last = int(bool(rc_odd_reads)), int(bool(last))
+        # (a record has at least four bytes; a block inflates to at most 65536 bytes and is at least 28)
+        room = sum(len(bufs[i]) + (len(bufs[i + 1]) // 28 + 1) * 65536 for i in (0, 2))
+        t.max_reads = int(max_reads) if max_reads is not None else min(0x7FFFFFFF, room // 4 + 2)
+        n = C.c_int(0); tail = (C.c_size_t * 2)(); nu = C.c_uint64(0)
+        rc = self.lib.dg_batch_upload_fastq_bgzf(self.ctx, C.byref(t), FQ_CHECK_ONLY if check_only else 0, C.byref(n), tail, C.byref(nu))
+        self.fastq_need = int(n.value)
+        self._chk(rc, "dg_batch_upload_fastq_bgzf")
+        self._n = 0 if check_only else int(n.value)
+        ms = C.c_float(0)
+        self.lib.dg_batch_fastq_device_ms(self.ctx, C.byref(ms))
+        self.fastq_device_ms = float(ms.value)
+        t1 = np.zeros(max(int(tail[0]), 1), np.uint8); t2 = np.zeros(max(int(tail[1]), 1), np.uint8)
+        self._chk(self.lib.dg_batch_download_fastq_tail(self.ctx, t1.ctypes.data, int(tail[0]), t2.ctypes.data, int(tail[1])), "dg_batch_download_fastq_tail")
+        return int(n.value), t1[:int(tail[0])].tobytes(), (t2[:int(tail[1])].tobytes() if two else None), int(nu.value)
+
+    def inflate_granules(self):
+        """(blocks per workgroup, tokens decoded per write-out round) of the device's inflate kernel (dg_inflate_granules)"""
+        if not hasattr(self.lib, "dg_inflate_granules"):
+            raise RuntimeError("this build of libdartgpu.so has no dg_inflate_granules")
+        g = (C.c_int * 2)()
+        self._chk(self.lib.dg_inflate_granules(g), "dg_inflate_granules")
         return int(g[0]), int(g[1])
 
     def device_bam_tensor(self):

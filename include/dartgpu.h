@@ -301,6 +301,50 @@ int dg_bgzf_compress_flags(dg_ctx *, const void *host_bytes, size_t n, uint32_t 
 int dg_batch_bam_device_ms(dg_ctx *, float ms[2]);
 int dg_bgzf_granules(int out[2]);
 
+/* ---- BGZF inflated on the device: compressed read files -> a batch in HBM (replaces the gz branch of the reference's reader, GetData.cpp:181-247, for files
+ * whose gzip members are BGZF blocks: what bgzip and htslib write, and dg_bgzf_compress) ----
+ * A member: magic 1f 8b 08, FLG exactly FEXTRA, a 'BC' subfield (anywhere in the extra field) with the member's size, one raw deflate stream, CRC32 and ISIZE
+ * (at most 65536; a member of 0 bytes -- the end-of-file marker -- may stand anywhere).  The call hops over the headers on the host; another FLG, no 'BC'
+ * subfield, a size that points past the input, an ISIZE above 65536 or trailing bytes that are no member give DG_ERR_ARG, the text names the block's index,
+ * and nothing is enqueued.  One wave inflates one member (dg_inflate.h): RFC 1951 complete, accepting and refusing what zlib's inflate does; then the length
+ * against ISIZE and the CRC32.  A block that fails gives DG_ERR_ARG; the text names the block and the first rule it broke.  A malformed block is never read or
+ * written outside its own bytes.  A plain single-member gzip file is one serial bit stream: not taken here (FLG / 'BC': DG_ERR_ARG), it stays on the host.
+ * Every failure leaves the context usable.
+ *   dg_bgzf_inflate               whole blocks in host memory -> their bytes in HBM; needs no batch and no index aids; n = 0: 0 bytes, 0 blocks
+ *   dg_inflate_download           copies them out; DG_ERR_CAPACITY, nothing written, when cap is smaller than *n_out was
+ *   dg_inflate_device             the bytes in HBM, valid until the next upload, run or inflate on this context
+ *   dg_batch_upload_fastq_bgzf    dg_batch_upload_fastq for texts that are pieces of compressed files: text f = head f (plain bytes: the tail the previous
+ *                                 call gave back) followed by the bytes of blocks f, each text smaller than 2^32 - 256 bytes.  Blocks do not end where
+ *                                 records end, so without `last` only whole records are taken -- four lines, each ended by '\n'; two texts give the same
+ *                                 number of records, the smaller of the two counts -- and what lies behind the last record taken is the text's tail:
+ *                                 tail[f] (may be NULL) = its size.  With `last` the rules of dg_batch_upload_fastq hold (a line may end with the text,
+ *                                 text 1 may hold one more record) and both tails are empty.  Which reads are odd (rc_odd_reads) is counted from the
+ *                                 call's first read: pairs interlaced in ONE text need calls that take an even number of records, which this call does
+ *                                 not promise.  *n_unlike (may be NULL) counts the records taken that the
+ *                                 reference's gz reader (gzgets into 1024 bytes) and its plain reader would read differently: a line of 1024 bytes or
+ *                                 more, a NUL in the record, a header line that does not start with '@' or names nothing, a record without bases or
+ *                                 with fewer than four lines; the batch is built all the same, the count is what the caller acts on.  Errors as
+ *                                 dg_batch_upload_fastq (DG_ERR_CAPACITY: *n_reads = the need), a failing block as above with "text 1" / "text 2".
+ *                                 Afterwards the context is as after dg_batch_upload_fastq; dg_batch_fastq_device_ms includes the inflate.  The call
+ *                                 waits once.  DG_FQ_CHECK_ONLY: the same verdicts, counts and tails, but no batch is written and the context is left
+ *                                 without one (dg_batch_run: DG_ERR_ARG) until the next upload.
+ *   dg_batch_download_fastq_tail  the tails of the last dg_batch_upload_fastq_bgzf (the next call's heads); DG_ERR_CAPACITY, nothing written, when a cap
+ *                                 is smaller than its tail
+ *   dg_inflate_granules           [0] blocks per workgroup, [1] tokens decoded per write-out round of the inflate kernel: tests place seams on them      */
+typedef struct {
+    const char *head1; size_t n_head1; const void *blocks1; size_t n_blocks1;   /* text 1 = head1 ++ inflate(blocks1) */
+    const char *head2; size_t n_head2; const void *blocks2; size_t n_blocks2;   /* blocks2 == NULL && head2 == NULL: one text */
+    int32_t rc_odd_reads, max_reads;
+    int32_t last;                                                                /* the files end here */
+} dg_fastq_bgzf;
+#define DG_FQ_CHECK_ONLY 1u   /* inflate, count and check; no batch is written and the context is left without one */
+int dg_bgzf_inflate(dg_ctx *, const void *host_bytes, size_t n, size_t *n_out, size_t *n_blocks, float *device_ms);
+int dg_inflate_download(dg_ctx *, void *out, size_t cap);
+int dg_inflate_device(dg_ctx *, void **ptr, size_t *n_out);
+int dg_batch_upload_fastq_bgzf(dg_ctx *, const dg_fastq_bgzf *, uint32_t flags, int *n_reads, size_t tail[2], uint64_t *n_unlike);
+int dg_batch_download_fastq_tail(dg_ctx *, char *tail1, size_t cap1, char *tail2, size_t cap2);
+int dg_inflate_granules(int out[2]);
+
 /* ---- the splice-junction table on the device: count, sort and print in HBM (replaces UpdateLocalSJMap / UpdateGlobalSJMap, Mapping.cpp:532-577, and
  * OutputSpliceJunctions, Mapping.cpp:683-716) ----
  * Every context owns a table (g1, g2) -> count that stays in HBM across batches: an open-addressing hash table keyed by the full 128 bits, grown by the
