@@ -16,6 +16,7 @@
 #include "dg_fastq.h"
 #include "dg_inflate.h"
 #include "dg_sjtab.h"
+#include "dg_bamsort.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -188,6 +189,17 @@ struct dg_ctx {
     unsigned long long *d_sj_stat = nullptr, *h_sj_stat = nullptr;        // SJ_ST_* words: device / page-locked copy
     hipEvent_t ev_sj[3] = {nullptr, nullptr, nullptr};                     // [0], [1]: device time of dg_sj_finish; [2]: the source stream's place for dg_sj_merge
     bool sj_batch_counted = false, sj_fin_valid = false; size_t sj_fin_entries = 0, sj_fin_bytes = 0;
+    // the coordinate-sorted BAM store (dg_bamsort.h): resident across batches: the records' bytes, one key and one offset per record, and the list of segments
+    // (one per accumulate / add call); the sorter's buffers and the sorted array of the last dg_bam_sort_finish
+    unsigned char *bs_rec = nullptr; uint64_t *bs_key = nullptr; int64_t *bs_off = nullptr;
+    size_t bs_rec_cap = 0, bs_rec_used = 0, bs_key_cap = 0, bs_off_cap = 0, bs_n = 0, bs_growths = 0;
+    std::vector<BsSeg> bs_segs;
+    DBuf<uint32_t> bs_cnt_off, bs_tile_cnt, bs_hist, bs_sums; DBuf<uint64_t> bs_k[2], bs_tile; DBuf<int64_t> bs_v[2]; DBuf<unsigned char> bs_sorted;
+    unsigned long long *d_bs_stat = nullptr, *h_bs_stat = nullptr;        // [0] bytes of the sorted array, [1] (low word) records counted by k_bs_count: device / page-locked copy
+    hipEvent_t ev_bs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // [0..4]: the phases of dg_bam_sort_finish; [5]: the source stream's place for dg_bam_sort_merge
+    bool bam_rec_valid = false, bam_rec_stored = false; size_t bam_rec_bytes = 0, bam_rec_records = 0;      // bam_rec and the formatter's offsets hold the current batch's records / they are in the store
+    bool bs_fin_valid = false; size_t bs_fin_bytes = 0, bs_fin_records = 0; float bs_ms[4] = {0.f, 0.f, 0.f, 0.f}, bs_acc_ms = 0.f; int bs_passes = 0;
+    size_t env_bamsort_first_cap = 0;  // DG_BAMSORT_FIRST_CAP: test hook, the first size of the store in bytes (forces growth)
     size_t env_bam_first_cap = 0;      // DG_BAM_FIRST_CAP: test hook, the first size of the record buffer in bytes
     size_t env_sam_first_cap = 0;      // DG_SAM_TEXT_FIRST_CAP: test hook, the first size of the text buffer in bytes (forces the "text outgrew the guess" path)
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
@@ -216,6 +228,7 @@ static void read_env(dg_ctx *c)
     c->env_rs_inline = std::min(RS_ENT_INLINE, std::max(0, geti("DG_RS_ENT_MAX", RS_ENT_INLINE))); c->env_rs_pool = std::max(0, geti("DG_RS_POOL_BLOCKS", 0));
     c->env_sam_first_cap = (size_t)std::max(0, geti("DG_SAM_TEXT_FIRST_CAP", 0));
     c->env_bam_first_cap = (size_t)std::max(0, geti("DG_BAM_FIRST_CAP", 0));
+    c->env_bamsort_first_cap = (size_t)std::max(0, geti("DG_BAMSORT_FIRST_CAP", 0));
     c->env_seed_multi = geti("DG_SEED_MULTI", 4); if (c->env_seed_multi < 0 || c->env_seed_multi > SQF_MULTI_MAX) c->env_seed_multi = SQF_MULTI_MAX;   // rows of an interval that are located and compared with the text at once (0: single rows only)
 }
 
@@ -650,6 +663,14 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->d_sj_stat) (void)hipFree(c->d_sj_stat);
     if (c->h_sj_stat) (void)hipHostFree(c->h_sj_stat);
     for (hipEvent_t e : c->ev_sj) if (e) (void)hipEventDestroy(e);
+    if (c->bs_rec) (void)hipFree(c->bs_rec);
+    if (c->bs_key) (void)hipFree(c->bs_key);
+    if (c->bs_off) (void)hipFree(c->bs_off);
+    c->bs_cnt_off.release(); c->bs_tile_cnt.release(); c->bs_hist.release(); c->bs_sums.release(); c->bs_k[0].release(); c->bs_k[1].release(); c->bs_v[0].release(); c->bs_v[1].release();
+    c->bs_tile.release(); c->bs_sorted.release();
+    if (c->d_bs_stat) (void)hipFree(c->d_bs_stat);
+    if (c->h_bs_stat) (void)hipHostFree(c->h_bs_stat);
+    for (hipEvent_t e : c->ev_bs) if (e) (void)hipEventDestroy(e);
     c->fq_text.release(); c->fq_lines.release(); c->fq_tile_cnt.release(); c->fq_name_at.release(); c->fq_name_len.release(); c->fq_loc.release(); c->fq_hdr_off.release(); c->fq_qual_off.release();
     c->fq_tile_sum.release(); c->fq_hdr.release(); c->fq_qual.release();
     if (c->d_fq_info) (void)hipFree(c->d_fq_info);
@@ -1071,7 +1092,7 @@ static int enqueue_upload(dg_ctx *c, int n_reads, const uint32_t *seq_off, const
         mx = rlen[i] > mx ? rlen[i] : mx;
     }
     if (mx > DG_MAX_RLEN) { snprintf(c->err, 512, "a read is longer than DG_MAX_RLEN (%d)", DG_MAX_RLEN); return DG_ERR_ARG; }
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
     c->no_batch = false; c->inf_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64));     /* the kernels read up to 24 bytes at a read position in one go */
     HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
@@ -1134,7 +1155,7 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
     if (mx > DG_MAX_RLEN || mx > 16 * W2 || (size_t)n_reads * 16 * W2 > 0xFFFFFFF0ull) { snprintf(c->err, 512, "packed batch: read length %d does not fit %d words (or exceeds DG_MAX_RLEN / 2^32 bases)", mx, W2); return DG_ERR_ARG; }
     if (n_reads && (mx + 15) / 16 != W2) { snprintf(c->err, 512, "packed batch: words_per_read must be ceil(longest read / 16) = %d", (mx + 15) / 16); return DG_ERR_ARG; }
     const size_t nw = (size_t)n_reads * W2, bytes = nw * 16;
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
     c->no_batch = false; c->inf_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64)); HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     HIPCHK(c->enc.ensure(2 * nw + 16)); HIPCHK(c->packed_in.ensure(nw + 1)); HIPCHK(c->nlist_in.ensure(n_n + 1));
@@ -1252,7 +1273,7 @@ static int fq_finish(dg_ctx *c, const char *fn, int max_reads, int *n_reads_out,
 // whatever happens in an upload of FASTQ text, the context holds no batch until the call has succeeded
 static void fq_forget_batch(dg_ctx *c)
 {
-    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->fq_valid = false;
+    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
     c->fq_hdr_bytes = c->fq_qual_bytes = 0; c->fq_ms = 0.f;
     c->no_batch = false; c->inf_valid = false; c->fq_tail_valid = false; c->fq_tail_n[0] = c->fq_tail_n[1] = 0;
 }
@@ -1898,7 +1919,7 @@ extern "C" int dg_batch_run(dg_ctx *c, size_t used[3])
     memset(c->counters, 0, sizeof c->counters);
     if (used) used[0] = used[1] = used[2] = 0;
     c->n_t = 0;
-    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false;
+    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false;
     if (c->n_reads == 0) { c->batch_done = true; return DG_OK; }
     c->attempt_no = 0;
     int rc = enqueue_run(c);
@@ -2014,12 +2035,13 @@ extern "C" int dg_map_batch_compact(dg_ctx *c, int n_reads, const uint32_t *seq_
 static int ensure_full_records(dg_ctx *c)
 {
     if (c->full_valid || c->n_reads == 0) return DG_OK;
-    const bool keep = c->want_full, counted = c->sj_batch_counted;
+    const bool keep = c->want_full, counted = c->sj_batch_counted, stored = c->bam_rec_stored;
     c->want_full = true;
     size_t used[3];
     const int rc = dg_batch_run(c, used);
     c->want_full = keep;
     c->sj_batch_counted = counted;      // (the same batch, mapped again: its tuples are in the junction table already if they were before)
+    c->bam_rec_stored = stored;         // (and its BAM records in the sorted store)
     return rc;
 }
 
@@ -2129,6 +2151,7 @@ static int sam_batch_ready(dg_ctx *c, int n_pair_mode, size_t *n_bytes, uint64_t
     if (counters) counters[0] = counters[1] = counters[2] = 0;
     if (device_ms) *device_ms = 0.f;
     if (bam) { c->bam_valid = false; c->bam_bytes = 0; } else { c->sam_valid = false; c->sam_bytes = 0; }
+    c->bam_rec_valid = false;           // (both formatters write the per-read offsets dg_batch_accumulate_bam walks)
     if (!c->batch_done) { snprintf(c->err, 512, "%s: the context has no finished batch (upload and run one first)", fn); return DG_ERR_ARG; }
     const int n = c->n_reads;
     if (n_pair_mode < 0 || (n_pair_mode & 1) || n_pair_mode > n) { snprintf(c->err, 512, "%s: n_pair_mode %d must be even and at most the batch's %d reads", fn, n_pair_mode, n); return DG_ERR_ARG; }
@@ -2371,6 +2394,7 @@ static int bam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr
         c->bam_ptr = c->bgzf_out.p;
     }
     c->bam_bytes = out_bytes; c->bam_valid = true;
+    c->bam_rec_valid = true; c->bam_rec_bytes = total; c->bam_rec_records = (size_t)c->h_bam_stat[4];
     if (n_bytes) *n_bytes = out_bytes;
     if (n_raw) *n_raw = total;
     if (counters) for (int i = 0; i < 5; i++) counters[i] = c->h_bam_stat[1 + i];
@@ -2395,7 +2419,7 @@ extern "C" int dg_batch_format_bam(dg_ctx *c, const dg_sam_text *in, uint32_t fl
     const int rc = sam_batch_ready(c, in->n_pair_mode, n_bytes, counters, device_ms, fn, true);
     if (rc) return rc;
     const int n = c->n_reads;
-    if (n == 0) { c->bam_valid = true; c->bam_ptr = nullptr; return DG_OK; }
+    if (n == 0) { c->bam_valid = true; c->bam_ptr = nullptr; c->bam_rec_valid = true; c->bam_rec_bytes = c->bam_rec_records = 0; return DG_OK; }
     if (!in->hdr_off || (in->qual && !in->qual_off)) { snprintf(c->err, 512, "%s: an offset array is NULL", fn); return DG_ERR_ARG; }
     if (sam_offsets_ok(c, "hdr_off", in->hdr_off, n, fn) || (in->qual && sam_offsets_ok(c, "qual_off", in->qual_off, n, fn))) return DG_ERR_ARG;
     const size_t hdr_bytes = (size_t)in->hdr_off[n] - in->hdr_off[0], qual_bytes = in->qual ? (size_t)in->qual_off[n] - in->qual_off[0] : 0;
@@ -2420,7 +2444,7 @@ extern "C" int dg_batch_format_bam_resident(dg_ctx *c, int n_pair_mode, uint32_t
     const int rc = sam_batch_ready(c, n_pair_mode, n_bytes, counters, device_ms, "dg_batch_format_bam_resident", true);
     if (rc) return rc;
     if (!c->fq_valid) { snprintf(c->err, 512, "dg_batch_format_bam_resident: the context's last upload was not dg_batch_upload_fastq: no names and qualities in HBM"); return DG_ERR_ARG; }
-    if (c->n_reads == 0) { c->bam_valid = true; c->bam_ptr = nullptr; return DG_OK; }
+    if (c->n_reads == 0) { c->bam_valid = true; c->bam_ptr = nullptr; c->bam_rec_valid = true; c->bam_rec_bytes = c->bam_rec_records = 0; return DG_OK; }
     HIPCHK(hipSetDevice(c->device));
     return bam_format_device(c, c->fq_hdr_off.p, c->fq_hdr.p, c->fq_qual_off.p, c->fq_qual.p, c->fq_hdr_bytes, c->fq_qual_bytes, n_pair_mode, flags, n_bytes, n_raw, counters, device_ms);
 }
@@ -2656,23 +2680,33 @@ extern "C" int dg_sj_merge(dg_ctx *dst, dg_ctx *src)
     return DG_OK;
 }
 
-// stable LSD radix sort (dg_sort.h) of n pairs by the low `bits` bits of the key, on the context's stream; which = the buffer that holds the input, and on
-// return the one that holds the result
-static int sj_sort(dg_ctx *c, uint32_t n, int bits, int &which)
+// The passes of the stable LSD radix sort (dg_sort.h) of n pairs by the low `bits` bits of the key, enqueued on the context's stream: the driver of the junction
+// table's sorts and of the sorted BAM store's.  keys / vals: two buffers each; which: in = the pair that holds the input, out = the one that holds the result.
+// hist holds 16 x tiles + 1 words, sums one per SCAN_TILE of them + 1: the caller's scratch.
+static int rs_sort_passes(dg_ctx *c, uint64_t *const keys[2], int64_t *const vals[2], uint32_t *hist, uint32_t *sums, uint32_t n, int bits, int &which)
 {
     const uint32_t tiles = (n + RS_TILE - 1) / RS_TILE, m = 16u * tiles, scan_tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
-    HIPCHK(c->sj_hist.ensure((size_t)m + 1)); HIPCHK(c->sj_sums.ensure((size_t)scan_tiles + 1));
     for (int shift = 0; shift < bits; shift += 4) {
         const int o = which ^ 1;
-        k_rs_hist<<<tiles, 256, 0, c->stream>>>(c->sj_keys[which].p, n, shift, tiles, c->sj_hist.p);
-        k_scan_tiles<<<scan_tiles, 256, 0, c->stream>>>(c->sj_hist.p, c->sj_hist.p, c->sj_sums.p, m);
-        k_scan_top<<<1, 256, 0, c->stream>>>(c->sj_sums.p, scan_tiles, c->sj_hist.p + m, nullptr, 0, nullptr, 0);
-        k_scan_add<<<(m + 255) / 256, 256, 0, c->stream>>>(c->sj_hist.p, c->sj_sums.p, m);
-        k_rs_scatter<<<tiles, 256, 0, c->stream>>>(c->sj_keys[which].p, c->sj_vals[which].p, c->sj_keys[o].p, c->sj_vals[o].p, n, shift, tiles, c->sj_hist.p);
+        k_rs_hist<<<tiles, 256, 0, c->stream>>>(keys[which], n, shift, tiles, hist);
+        k_scan_tiles<<<scan_tiles, 256, 0, c->stream>>>(hist, hist, sums, m);
+        k_scan_top<<<1, 256, 0, c->stream>>>(sums, scan_tiles, hist + m, nullptr, 0, nullptr, 0);
+        k_scan_add<<<(m + 255) / 256, 256, 0, c->stream>>>(hist, sums, m);
+        k_rs_scatter<<<tiles, 256, 0, c->stream>>>(keys[which], vals[which], keys[o], vals[o], n, shift, tiles, hist);
         HIPCHK(hipGetLastError());
         which = o;
     }
     return DG_OK;
+}
+static size_t rs_hist_words(uint32_t n) { return 16 * (size_t)((n + RS_TILE - 1) / RS_TILE) + 1; }
+static size_t rs_sums_words(uint32_t n) { return (rs_hist_words(n) - 1 + SCAN_TILE - 1) / SCAN_TILE + 1; }
+
+// the junction table's sort: n pairs in sj_keys / sj_vals [which]
+static int sj_sort(dg_ctx *c, uint32_t n, int bits, int &which)
+{
+    HIPCHK(c->sj_hist.ensure(rs_hist_words(n))); HIPCHK(c->sj_sums.ensure(rs_sums_words(n)));
+    uint64_t *const keys[2] = {c->sj_keys[0].p, c->sj_keys[1].p}; int64_t *const vals[2] = {c->sj_vals[0].p, c->sj_vals[1].p};
+    return rs_sort_passes(c, keys, vals, c->sj_hist.p, c->sj_sums.p, n, bits, which);
 }
 
 extern "C" int dg_sj_finish(dg_ctx *c, uint32_t flags, size_t *n_entries, size_t *n_lines, size_t *n_bytes, float *device_ms)
@@ -2761,6 +2795,295 @@ extern "C" int dg_sj_device(dg_ctx *c, void **entries, void **text)
     if (!c->sj_fin_valid) { snprintf(c->err, 512, "dg_sj_device: no finished table (dg_sj_finish first)"); return DG_ERR_ARG; }
     if (entries) *entries = c->sj_fin_entries ? c->sj_entries.p : nullptr;
     if (text) *text = c->sj_fin_bytes ? c->sj_text.p : nullptr;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// coordinate-sorted BAM on the device (dg_bamsort.h): the records of every batch stay in HBM, one sort and one gather at the end of the job
+// ------------------------------------------------------------------------------------------
+static int bs_state(dg_ctx *c)
+{
+    if (c->d_bs_stat) return DG_OK;
+    HIPCHK(hipMalloc((void **)&c->d_bs_stat, 4 * 8));
+    HIPCHK(hipMemset(c->d_bs_stat, 0, 4 * 8));
+    HIPCHK(hipHostMalloc((void **)&c->h_bs_stat, 4 * 8, hipHostMallocDefault));
+    memset(c->h_bs_stat, 0, 4 * 8);
+    for (hipEvent_t &e : c->ev_bs) HIPCHK(hipEventCreate(&e));
+    return DG_OK;
+}
+static int bs_ready(dg_ctx *c)
+{
+    HIPCHK(hipSetDevice(c->device));
+    { const int rc = bs_state(c); if (rc) return rc; }
+    return bam_state(c);
+}
+// One array of the store with room for `need` elements (`pad` more are allocated and never counted).  DBuf::ensure frees what it holds; here the first `used`
+// elements are kept: allocate, copy device to device on the context's stream, wait, free.  hipMalloc fails: DG_ERR_CAPACITY, the array stays as it was.
+template <typename T>
+static int bs_grow(dg_ctx *c, T *&p, size_t &cap, size_t used, size_t need, size_t first, size_t pad, const char *fn, const char *what)
+{
+    if (need <= cap) return DG_OK;
+    const size_t want = std::max(need, cap ? cap * 2 : first);
+    T *q = nullptr;
+    if (hipMalloc((void **)&q, (want + pad) * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        snprintf(c->err, 512, "%s: the store cannot grow: its %s need %zu bytes of device memory (%zu are held)", fn, what, (want + pad) * sizeof(T), cap ? (cap + pad) * sizeof(T) : (size_t)0);
+        return DG_ERR_CAPACITY;
+    }
+    hipError_t e = hipSuccess;
+    if (p && used) e = hipMemcpyAsync(q, p, used * sizeof(T), hipMemcpyDeviceToDevice, c->stream);
+    if (e == hipSuccess && p) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { (void)hipFree(q); return fail(c, DG_ERR_HIP, "growing the sorted-BAM store", e); }
+    if (p) (void)hipFree(p);
+    p = q; cap = want;
+    return DG_OK;
+}
+// room for n_rec more records of `bytes` bytes
+static int bs_reserve(dg_ctx *c, size_t n_rec, size_t bytes, const char *fn)
+{
+    if (c->bs_n + n_rec >= 0xFFFFF000ull) { snprintf(c->err, 512, "%s: %zu records are more than the sorter takes", fn, c->bs_n + n_rec); return DG_ERR_ARG; }
+    const size_t hook = c->env_bamsort_first_cap;
+    const size_t first_bytes = hook ? std::max<size_t>(hook, BS_MIN_BYTES) : (size_t)1 << 24, first_recs = hook ? std::max<size_t>(hook / 64, 16) : (size_t)1 << 16;
+    const bool grows = (c->bs_rec && c->bs_rec_used + bytes > c->bs_rec_cap) || (c->bs_key && c->bs_n + n_rec > c->bs_key_cap);      // an array is replaced by a larger one
+    int rc = bs_grow(c, c->bs_rec, c->bs_rec_cap, c->bs_rec_used, c->bs_rec_used + bytes, first_bytes, 8, fn, "records");
+    if (!rc) rc = bs_grow(c, c->bs_key, c->bs_key_cap, c->bs_n, c->bs_n + n_rec, first_recs, 0, fn, "keys");
+    if (!rc) rc = bs_grow(c, c->bs_off, c->bs_off_cap, c->bs_n, c->bs_n + n_rec, first_recs, 0, fn, "offsets");
+    if (!rc && grows) c->bs_growths++;
+    return rc;
+}
+static void bs_commit(dg_ctx *c, uint32_t ordinal, size_t n_rec, size_t bytes)
+{
+    c->bs_segs.push_back(BsSeg{ordinal, (uint64_t)c->bs_n, (uint64_t)n_rec});
+    c->bs_n += n_rec; c->bs_rec_used += bytes;
+}
+#define BS_ENSURE(buf, n, what) do { if ((buf).ensure(n) != hipSuccess) { (void)hipGetLastError(); \
+    snprintf(c->err, 512, "%s: not enough device memory: %s need %zu bytes", fn, what, (size_t)(n) * sizeof(*(buf).p)); return DG_ERR_CAPACITY; } } while (0)
+
+extern "C" int dg_bam_sort_granules(int out[3])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = BS_THREADS; out[1] = RS_TILE; out[2] = BS_MIN_BYTES;
+    return DG_OK;
+}
+
+// test hook (not in the public header): [0] records, [1] bytes, [2] segments, [3] the calls in which the store grew (an array replaced by a larger one)
+extern "C" int dg_bam_sort_info(dg_ctx *c, size_t out[4])
+{
+    if (!c || !out) return DG_ERR_ARG;
+    out[0] = c->bs_n; out[1] = c->bs_rec_used; out[2] = c->bs_segs.size(); out[3] = c->bs_growths;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_sort_reset(dg_ctx *c)
+{
+    if (!c) return DG_ERR_ARG;
+    { const int rc = bs_ready(c); if (rc) return rc; }
+    HIPCHK(wait_stream(c));
+    c->bs_n = 0; c->bs_rec_used = 0; c->bs_segs.clear(); c->bs_fin_valid = false;
+    return DG_OK;
+}
+
+extern "C" int dg_batch_accumulate_bam(dg_ctx *c, uint32_t ordinal, size_t *n_records, size_t *n_bytes)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_batch_accumulate_bam";
+    if (n_records) *n_records = 0;
+    if (n_bytes) *n_bytes = 0;
+    if (!c->bam_rec_valid) { snprintf(c->err, 512, "%s: the records of the current batch are not there (dg_batch_format_bam on a finished batch first, and no dg_batch_format_sam behind it)", fn); return DG_ERR_ARG; }
+    if (c->bam_rec_stored) { snprintf(c->err, 512, "%s: the records of this batch are in the store already (a batch is added once)", fn); return DG_ERR_ARG; }
+    { const int rc = bs_ready(c); if (rc) return rc; }
+    const size_t n_rec = c->bam_rec_records, bytes = c->bam_rec_bytes;
+    if (!n_rec) { c->bam_rec_stored = true; return DG_OK; }
+    { const int rc = bs_reserve(c, n_rec, bytes, fn); if (rc) return rc; }
+    c->bs_fin_valid = false;
+    const int n = c->n_reads;
+    const uint32_t n_tiles = (uint32_t)((n + BS_THREADS - 1) / BS_THREADS);
+    BS_ENSURE(c->bs_cnt_off, (size_t)n, "the per-read counts"); BS_ENSURE(c->bs_tile_cnt, (size_t)n_tiles + 1, "the per-workgroup counts");
+    HIPCHK(hipEventRecord(c->ev_bs[0], c->stream));
+    k_bs_count<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bam_rec.p, c->sam_read_off.p, c->sam_tile.p, n, (unsigned long long)bytes, c->bs_cnt_off.p, c->bs_tile_cnt.p);
+    k_scan_top<<<1, 256, 0, c->stream>>>(c->bs_tile_cnt.p, n_tiles, (uint32_t *)(c->d_bs_stat + 1), nullptr, 0, nullptr, 0);
+    k_bs_emit<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bam_rec.p, c->sam_read_off.p, c->sam_tile.p, n, (unsigned long long)bytes, c->bs_cnt_off.p, c->bs_tile_cnt.p, c->ix.n_chr,
+                                                     (unsigned long long)c->bs_n, (unsigned long long)(c->bs_n + n_rec), (unsigned long long)c->bs_rec_used, c->bs_key, c->bs_off);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(c->bs_rec + c->bs_rec_used, c->bam_rec.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev_bs[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bs_stat + 1, c->d_bs_stat + 1, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the one wait: the walk must find the records the formatter counted
+    (void)hipEventElapsedTime(&c->bs_acc_ms, c->ev_bs[0], c->ev_bs[1]);
+    const size_t found = (size_t)(uint32_t)c->h_bs_stat[1];
+    if (found != n_rec) { snprintf(c->err, 512, "%s: the walk over the batch's records found %zu, the formatter wrote %zu; nothing was added", fn, found, n_rec); return DG_ERR_INTERNAL; }
+    bs_commit(c, ordinal, n_rec, bytes);
+    c->bam_rec_stored = true;
+    if (n_records) *n_records = n_rec;
+    if (n_bytes) *n_bytes = bytes;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_sort_add(dg_ctx *c, const void *records, size_t n, uint32_t ordinal, size_t *n_records)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_sort_add";
+    if (n_records) *n_records = 0;
+    if (n && !records) { snprintf(c->err, 512, "%s: the input is NULL", fn); return DG_ERR_ARG; }
+    { const int rc = bs_ready(c); if (rc) return rc; }
+    if (!n) return DG_OK;
+    const unsigned char *p = (const unsigned char *)records;
+    const int n_chr = c->ix.n_chr;
+    const uint64_t base = c->bs_rec_used;
+    std::vector<uint64_t> keys; std::vector<int64_t> offs;
+    size_t bad = 0; int why = BS_REC_OK;
+    const size_t n_rec = bs_walk_checked(p, n, n_chr, &bad, &why, [&](size_t, size_t at) { keys.push_back(bs_key(p + at, n_chr)); offs.push_back((int64_t)(base + at)); });
+    if (why) { snprintf(c->err, 512, "%s: record %zu: %s; nothing was added", fn, bad, bs_rec_why(why)); return DG_ERR_ARG; }
+    { const int rc = bs_reserve(c, n_rec, n, fn); if (rc) return rc; }
+    c->bs_fin_valid = false;
+    HIPCHK(hipMemcpyAsync(c->bs_rec + c->bs_rec_used, p, n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bs_key + c->bs_n, keys.data(), n_rec * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bs_off + c->bs_n, offs.data(), n_rec * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(wait_stream(c));
+    bs_commit(c, ordinal, n_rec, n);
+    if (n_records) *n_records = n_rec;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_sort_merge(dg_ctx *dst, dg_ctx *src)
+{
+    dg_ctx *c = dst;
+    if (!dst || !src) return DG_ERR_ARG;
+    const char *fn = "dg_bam_sort_merge";
+    if (dst == src || dst->device != src->device) { snprintf(c->err, 512, "%s: the two contexts must differ and be on one device", fn); return DG_ERR_ARG; }
+    { const int rc = bs_ready(dst); if (rc) return rc; }
+    if (!src->bs_n) { src->bs_fin_valid = false; return DG_OK; }
+    { const int rc = bs_state(src); if (rc) { snprintf(c->err, 512, "%s", src->err); return rc; } }
+    const size_t n_rec = src->bs_n, bytes = src->bs_rec_used;
+    { const int rc = bs_reserve(dst, n_rec, bytes, fn); if (rc) return rc; }
+    dst->bs_fin_valid = false; src->bs_fin_valid = false;
+    // behind everything the source's stream holds; the call waits for the destination's stream, so the source's storage is free again when it returns
+    HIPCHK(hipEventRecord(src->ev_bs[5], src->stream));
+    HIPCHK(hipStreamWaitEvent(dst->stream, src->ev_bs[5], 0));
+    HIPCHK(hipMemcpyAsync(dst->bs_rec + dst->bs_rec_used, src->bs_rec, bytes, hipMemcpyDeviceToDevice, dst->stream));
+    HIPCHK(hipMemcpyAsync(dst->bs_key + dst->bs_n, src->bs_key, n_rec * 8, hipMemcpyDeviceToDevice, dst->stream));
+    k_bs_shift<<<(unsigned)((n_rec + 255) / 256), 256, 0, dst->stream>>>(src->bs_off, dst->bs_off + dst->bs_n, (unsigned long long)n_rec, (long long)dst->bs_rec_used);
+    HIPCHK(hipGetLastError());
+    HIPCHK(wait_stream(dst));
+    for (const BsSeg &s : src->bs_segs) dst->bs_segs.push_back(BsSeg{s.ordinal, s.start + (uint64_t)dst->bs_n, s.count});      // behind dst's own: among equal ordinals dst's come first
+    dst->bs_n += n_rec; dst->bs_rec_used += bytes;
+    src->bs_n = 0; src->bs_rec_used = 0; src->bs_segs.clear();
+    return DG_OK;
+}
+
+// the store's sort (rs_sort_passes): n pairs in bs_k / bs_v [which]
+static int bs_sort(dg_ctx *c, uint32_t n, int bits, int &which)
+{
+    const char *fn = "dg_bam_sort_finish";
+    BS_ENSURE(c->bs_hist, rs_hist_words(n), "the sorter's histograms"); BS_ENSURE(c->bs_sums, rs_sums_words(n), "the sorter's sums");
+    uint64_t *const keys[2] = {c->bs_k[0].p, c->bs_k[1].p}; int64_t *const vals[2] = {c->bs_v[0].p, c->bs_v[1].p};
+    return rs_sort_passes(c, keys, vals, c->bs_hist.p, c->bs_sums.p, n, bits, which);
+}
+
+extern "C" int dg_bam_sort_finish(dg_ctx *c, size_t *n_records, size_t *n_raw, float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_sort_finish";
+    if (n_records) *n_records = 0;
+    if (n_raw) *n_raw = 0;
+    if (device_ms) *device_ms = 0.f;
+    c->bs_fin_valid = false; c->bs_fin_bytes = 0; c->bs_fin_records = 0; c->bs_passes = 0;
+    for (float &m : c->bs_ms) m = 0.f;
+    { const int rc = bs_ready(c); if (rc) return rc; }
+    if (!c->bs_n) { c->bs_fin_valid = true; return DG_OK; }
+    const size_t n = c->bs_n, bytes = c->bs_rec_used;
+    const uint32_t n_tiles = (uint32_t)((n + BS_THREADS - 1) / BS_THREADS);
+    for (int k = 0; k < 2; k++) { BS_ENSURE(c->bs_k[k], n, "the sorter's keys"); BS_ENSURE(c->bs_v[k], n, "the sorter's values"); }
+    BS_ENSURE(c->bs_tile, (size_t)n_tiles, "the per-workgroup sums"); BS_ENSURE(c->bs_sorted, bytes + 8, "the sorted records");
+    // step one: the segments in ordinal order (neighbours in the store that stay neighbours go in one copy)
+    std::vector<uint32_t> order(c->bs_segs.size());
+    bs_order_segments(c->bs_segs.data(), c->bs_segs.size(), order.data());
+    HIPCHK(hipEventRecord(c->ev_bs[0], c->stream));
+    size_t at = 0;
+    for (size_t i = 0; i < order.size();) {
+        const uint64_t start = c->bs_segs[order[i]].start;
+        uint64_t count = c->bs_segs[order[i]].count;
+        for (i++; i < order.size() && c->bs_segs[order[i]].start == start + count; i++) count += c->bs_segs[order[i]].count;
+        if (!count) continue;
+        HIPCHK(hipMemcpyAsync(c->bs_k[0].p + at, c->bs_key + start, count * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bs_v[0].p + at, c->bs_off + start, count * 8, hipMemcpyDeviceToDevice, c->stream));
+        at += count;
+    }
+    if (at != n) { snprintf(c->err, 512, "%s: the segments hold %zu records, the store %zu", fn, at, n); return DG_ERR_INTERNAL; }
+    HIPCHK(hipEventRecord(c->ev_bs[1], c->stream));
+    // step two: one stable sort; the values are the records' offsets in the store
+    int which = 0;
+    const int bits = bs_key_bits(c->ix.n_chr);
+    { const int rc = bs_sort(c, (uint32_t)n, bits, which); if (rc) return rc; }
+    c->bs_passes = (bits + 3) / 4;
+    HIPCHK(hipEventRecord(c->ev_bs[2], c->stream));
+    // step three: lengths in sorted order, their scan (the places go where the sorter's other key buffer was), the gather
+    uint64_t *dst_off = c->bs_k[which ^ 1].p;
+    k_bs_len<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bs_rec, c->bs_v[which].p, (uint32_t)n, dst_off, c->bs_tile.p);
+    k_sam_top<<<1, 256, 0, c->stream>>>(c->bs_tile.p, n_tiles, c->d_bs_stat);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_bs[3], c->stream));
+    k_bs_gather<<<(unsigned)((n + BS_GATHER_WAVES - 1) / BS_GATHER_WAVES), 64 * BS_GATHER_WAVES, 0, c->stream>>>(c->bs_rec, c->bs_v[which].p, dst_off, c->bs_tile.p, (uint32_t)n,
+                                                                                                             (unsigned long long)bytes, c->bs_sorted.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_bs[4], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bs_stat, c->d_bs_stat, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    if ((size_t)c->h_bs_stat[0] != bytes) { snprintf(c->err, 512, "%s: the sorted records' lengths add up to %zu bytes, the store holds %zu", fn, (size_t)c->h_bs_stat[0], bytes); return DG_ERR_INTERNAL; }
+    float total = 0.f;
+    for (int k = 0; k < 4; k++) { (void)hipEventElapsedTime(&c->bs_ms[k], c->ev_bs[k], c->ev_bs[k + 1]); total += c->bs_ms[k]; }
+    c->bs_fin_valid = true; c->bs_fin_bytes = bytes; c->bs_fin_records = n;
+    if (n_records) *n_records = n;
+    if (n_raw) *n_raw = bytes;
+    if (device_ms) *device_ms = total;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_sort_device_ms(dg_ctx *c, float ms[5], int *n_passes)
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    for (int k = 0; k < 4; k++) ms[k] = c->bs_ms[k];
+    ms[4] = c->bs_acc_ms;
+    if (n_passes) *n_passes = c->bs_passes;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_sort_device(dg_ctx *c, void **ptr, size_t *n_raw)
+{
+    if (!c || !ptr || !n_raw) return DG_ERR_ARG;
+    if (!c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_sort_device: no sorted array (dg_bam_sort_finish first)"); return DG_ERR_ARG; }
+    *ptr = c->bs_fin_bytes ? c->bs_sorted.p : nullptr; *n_raw = c->bs_fin_bytes;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_sort_compress(dg_ctx *c, size_t raw_off, size_t raw_len, uint32_t flags, size_t *n_bytes, float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_sort_compress";
+    if (n_bytes) *n_bytes = 0;
+    if (device_ms) *device_ms = 0.f;
+    c->bam_valid = false; c->bam_bytes = 0; c->bam_ptr = nullptr;
+    if (!c->bs_fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
+    if (flags != 0u && flags != DG_BGZF_DYNAMIC && flags != DG_BAM_RAW) { snprintf(c->err, 512, "%s: flags 0x%x are none of 0, DG_BGZF_DYNAMIC, DG_BAM_RAW", fn, flags); return DG_ERR_ARG; }
+    const size_t total = c->bs_fin_bytes;
+    if (raw_off % BGZF_BLOCK || raw_off > total || raw_len > total - raw_off || (raw_len % BGZF_BLOCK && raw_off + raw_len != total)) {
+        snprintf(c->err, 512, "%s: the range %zu + %zu of %zu bytes must begin at a multiple of %u, and end at one or at the array's end", fn, raw_off, raw_len, total, BGZF_BLOCK);
+        return DG_ERR_ARG;
+    }
+    if (!raw_len) { c->bam_valid = true; return DG_OK; }
+    { const int rc = bs_ready(c); if (rc) return rc; }
+    unsigned char *in = c->bs_sorted.p + raw_off;
+    size_t out_bytes = raw_len; float ms = 0.f;
+    c->bam_ptr = in;
+    if (flags != DG_BAM_RAW) {
+        const int rc = bgzf_device(c, in, raw_len, flags == DG_BGZF_DYNAMIC, &out_bytes, &ms);
+        if (rc) return rc;
+        c->bam_ptr = c->bgzf_out.p;
+    }
+    c->bam_bytes = out_bytes; c->bam_valid = true;
+    c->bam_ms[0] = 0.f; c->bam_ms[1] = ms;
+    if (n_bytes) *n_bytes = out_bytes;
+    if (device_ms) *device_ms = ms;
     return DG_OK;
 }
 

@@ -556,6 +556,15 @@ int main(int argc, char *argv[])
     const bool device_bam = o.bam && getenv("DART_DEVICE_BAM") && atoi(getenv("DART_DEVICE_BAM")) != 0;
     const bool bgzf_dynamic = device_bam && getenv("DART_BGZF_DYNAMIC") && atoi(getenv("DART_BGZF_DYNAMIC")) != 0;      // (alone it does nothing)
     const bool bam_streams = o.bam && !device_bam;         // -bo forces the streaming pipeline
+    // DART_SORT_BAM=1 beside -bo and DART_DEVICE_BAM=1: the records of every batch stay in HBM (dg_batch_accumulate_bam) and the file is written once, at the end,
+    // in coordinate order (dg_bam_sort_finish / dg_bam_sort_compress).  A user who asked for a sorted file never silently gets an unsorted one: whatever is
+    // missing ends the run before any output exists.
+    const bool sort_bam = getenv("DART_SORT_BAM") && atoi(getenv("DART_SORT_BAM")) != 0;
+    if (sort_bam && !device_bam) {
+        fprintf(stderr, "Error! DART_SORT_BAM=1 needs -bo and DART_DEVICE_BAM=1: %s missing\n", !o.bam ? (getenv("DART_DEVICE_BAM") && atoi(getenv("DART_DEVICE_BAM")) ? "-bo is" : "both are") : "DART_DEVICE_BAM=1 is");
+        return 1;
+    }
+    const char *bam_dev_note = sort_bam ? (bgzf_dynamic ? ", bam=device+sorted+dyn" : ", bam=device+sorted") : bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "";
     FastqIndex pre;                         // the first library's read files are mapped and indexed while the HIP runtime starts, the genome index loads and dg_init_files runs
     bool fast_first = false;
     // A library of .gz FASTQ files small enough to be inflated whole (libdeflate, ~3x zlib; DART_GZ_WHOLE_MAX_GB per file, default 8) goes through the
@@ -617,6 +626,7 @@ int main(int argc, char *argv[])
     // that the multi-device pool (several roots, one ordered writer: Mapping.cpp:644-664) runs where only one GPU exists
     const int same_device_times = getenv("DART_SAME_DEVICE_TIMES") ? std::max(1, std::min(8, atoi(getenv("DART_SAME_DEVICE_TIMES")))) : 0;
     if (same_device_times) n_gpu = same_device_times;
+    if (sort_bam && n_gpu > 1) { fprintf(stderr, "DART_SORT_BAM=1: the sorted store lives on one device; 1 of %d devices is used\n", n_gpu); n_gpu = 1; }
     SlotPool pool;                          // batch slots of the parallel FASTQ pipeline (page-locked in the background with DART_PINNED=1)
     if (fast_first) pool.start((size_t)n_gpu * inflight_cfg + 2, batch_reads, 160);
     // The read files of a library.  Plain FASTQ goes through the parallel host pipeline (fast_fastq.h); FASTA, .gz, -bo and DART_STREAMING=1 through the
@@ -702,6 +712,7 @@ int main(int argc, char *argv[])
     g_device_fastq = !bam_streams && getenv("DART_DEVICE_FASTQ") && atoi(getenv("DART_DEVICE_FASTQ")) != 0;
     g_device_bam = device_bam;
     g_bgzf_dynamic = bgzf_dynamic;
+    g_sort_bam = sort_bam;
     // DART_DEVICE_SJ=1: the junction table is counted, sorted and printed on the device (dg_batch_accumulate_sj per batch, dg_sj_merge / dg_sj_finish at the end);
     // works in both pipelines, with -o and -bo alike.  Without the switch the ordered writer fills a std::map, as always.
     const bool device_sj = getenv("DART_DEVICE_SJ") && atoi(getenv("DART_DEVICE_SJ")) != 0;
@@ -715,6 +726,7 @@ int main(int argc, char *argv[])
     fprintf(stdout, "\nLoad the reference sequences...\n");
 
     std::string hdr_text = std::string("@PG\tID:Dart\tPN:Dart\tVN:") + VersionStr + "\n";      // Mapping.cpp:741-751
+    if (sort_bam) hdr_text = "@HD\tVN:1.6\tSO:coordinate\n" + hdr_text;
     for (size_t i = 0; i < ix.names.size(); i++) hdr_text += "@SQ\tSN:" + ix.names[i] + "\tLN:" + std::to_string((long long)ix.len[i]) + "\n";
     FILE *sam = nullptr;
     BamWriter bam;
@@ -730,6 +742,13 @@ int main(int argc, char *argv[])
     // the parallel pipeline's place in the output: the SAM file's descriptor and offset; with DART_DEVICE_BAM the blocks go through g_bam_sink instead
     auto out_begin = [&](uint64_t &off) -> int { if (!sam) { off = 0; return -1; } fflush(sam); off = (uint64_t)ftello(sam); return fileno(sam); };
     auto out_end = [&](uint64_t off) { if (sam) fseeko(sam, (off_t)off, SEEK_SET); };
+    // a library that failed: under DART_SORT_BAM no partial file is left, and a store that could not grow says which switch asked for the memory
+    auto lib_failed = [&](int frc, const std::string &ferr) -> int {
+        if (sort_bam) { (void)bam.close(); remove(o.out); }
+        if (sort_bam && frc == DG_ERR_CAPACITY) fprintf(stderr, "\nError! DART_SORT_BAM=1: the records do not fit in device memory: %s\n", ferr.c_str());
+        else fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str());
+        return 1;
+    };
     const char *bam_note = !o.bam ? "" : ", bam=host";        // (the DART_TIMING lines: which BAM path a library took)
     Counters total;
     std::map<std::pair<int64_t, int64_t>, int> sjmap;
@@ -747,8 +766,9 @@ int main(int argc, char *argv[])
                 const int frc = run_fast_library(o.f1[lib].c_str(), sep ? o.f2[lib].c_str() : nullptr, pair_end, o.threads, batch_reads, ctx, o.p, ix.names, o.unique, o.multi, o.silent,
                                                  out_fd, &off, total, sjmap, t0, ferr, fst, pool, nullptr, &plan);
                 out_end(off);
-                if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), gz=device (check pass over every block %.3f s; %zu chunks, waits for the tail chain %.3f s summed over workers), %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_gz_check, plan.chunks.size(), fst.t_gz_tail, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "");
+                if (frc) return lib_failed(frc, ferr);
+                g_sort_ordinal_base += fst.n_batches;
+                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), gz=device (check pass over every block %.3f s; %zu chunks, waits for the tail chain %.3f s summed over workers), %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_gz_check, plan.chunks.size(), fst.t_gz_tail, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, bam_dev_note);
                 continue;
             }
         }
@@ -765,19 +785,25 @@ int main(int argc, char *argv[])
                 const int frc = run_fast_library(o.f1[lib].c_str(), sep ? o.f2[lib].c_str() : nullptr, pair_end, o.threads, batch_reads, ctx, o.p, ix.names, o.unique, o.multi, o.silent,
                                                  out_fd, &off, total, sjmap, t0, ferr, fst, pool, gi);
                 out_end(off);
-                if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "");
+                if (frc) return lib_failed(frc, ferr);
+                g_sort_ordinal_base += fst.n_batches;
+                if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), inflate (libdeflate, whole files) + index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, bam_dev_note);
                 gi->m1.close_now(); gi->m2.close_now();
                 continue;
             }
         }
         const int orc = open_lib(lib);              // (library 0 was opened before the index went to the GPU: its files are being inflated and parsed since)
-        if (orc == 2) return 1;
+        if (orc == 2) { if (sort_bam) { (void)bam.close(); remove(o.out); } return 1; }      // (under DART_SORT_BAM no failed run leaves a file)
         if (orc == 1) continue;
         LibIO &L = *libs[lib];
         Source &s1 = L.s1, &s2 = L.s2; Prefetch &pf1 = L.pf1, &pf2 = L.pf2;
         const bool sep = L.sep, gz = L.gz, fastq = L.fastq, fast_host = L.fast_host;
         const std::string &fn = o.f1[lib];
+        if (sort_bam && !fast_host) {
+            fprintf(stderr, "\nError! DART_SORT_BAM=1: %s takes the streaming pipeline (FASTA, a streamed .gz, DART_STREAMING), which has no sorted output\n", fn.c_str());
+            (void)bam.close(); remove(o.out);
+            return 1;
+        }
         if (sep) pair_end = true;
         if (fast_host) {
             uint64_t off = 0; const int out_fd = out_begin(off);
@@ -785,8 +811,9 @@ int main(int argc, char *argv[])
             const int frc = run_fast_library(fn.c_str(), sep ? o.f2[lib].c_str() : nullptr, pair_end, o.threads, batch_reads, ctx, o.p, ix.names, o.unique, o.multi, o.silent,
                                              out_fd, &off, total, sjmap, t0, ferr, fst, pool, lib == 0 ? &pre : nullptr);
             out_end(off);
-            if (frc) { fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str()); return 1; }
-            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "");
+            if (frc) return lib_failed(frc, ferr);
+            g_sort_ordinal_base += fst.n_batches;
+            if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing] start-up %.3f s (%s), index %.3f s, %s, map (sum over workers) %.3f s, %s, write %.3f s%s\n", t_init1 - t_proc0, dg_init_report(roots[0]), fst.t_index, fast_assemble_text(fst).c_str(), fst.t_map, fast_format_text(fst).c_str(), fst.t_write, bam_dev_note);
             if (s1.fp) fclose(s1.fp);
             if (s2.fp) fclose(s2.fp);
             continue;
@@ -971,7 +998,47 @@ int main(int argc, char *argv[])
         if (s2.gz) gzclose(s2.gz);
     }
     if (!o.silent) fprintf(stdout, "\rAll the %lld %s reads have been processed in %lld seconds.\n", total.total, pair_end ? "paired-end" : "single-end", (long long)(time(NULL) - t0));
-    if (o.bam) { if (!bam.close()) { fprintf(stderr, "Error while writing %s\n", o.out); return 1; } }
+    // DART_SORT_BAM: the clones' stores into their root's, one sort, and the sorted array out in pieces of whole BGZF blocks: compress -> download -> write
+    if (sort_bam) {
+        auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        auto sort_fail = [&](dg_ctx *c, int rc) {
+            (void)bam.close(); remove(o.out);
+            if (rc == DG_ERR_CAPACITY) fprintf(stderr, "\nError! DART_SORT_BAM=1: the records do not fit in device memory: %s\n", dg_last_error(c));
+            else fprintf(stderr, "\nError! DART_SORT_BAM=1: %s\n", dg_last_error(c));
+            return 1;
+        };
+        const double ts0 = now_s();
+        int rc = 0;
+        for (int k = 1; k < inflight_cfg; k++) if ((rc = dg_bam_sort_merge(roots[0], ctx[(size_t)k]))) return sort_fail(roots[0], rc);
+        size_t n_sorted = 0, n_raw = 0; float fin_ms = 0.f;
+        if ((rc = dg_bam_sort_finish(roots[0], &n_sorted, &n_raw, &fin_ms))) return sort_fail(roots[0], rc);
+        const double ts1 = now_s();
+        const size_t block = 0xff00;
+        const double piece_mb = getenv("DART_SORT_PIECE_MB") ? atof(getenv("DART_SORT_PIECE_MB")) : 256.0;
+        // whole blocks, at least one, at most the array (whatever the variable holds -- a huge or unparsable value included): the file is the same whatever the piece
+        const size_t all_blocks = std::max<size_t>(1, (n_raw + block - 1) / block);
+        const double want_blocks = piece_mb > 0.0 ? piece_mb * 1048576.0 / (double)block : 0.0;      // (a NaN compares false)
+        const size_t piece = (want_blocks >= (double)all_blocks ? all_blocks : std::max<size_t>(1, (size_t)want_blocks)) * block;
+        const size_t cap = std::min(piece, n_raw) + 31 * (std::min(piece, n_raw) / block + 1);
+        char *buf = (char *)dg_host_alloc(cap ? cap : 1);
+        const bool pinned = buf != nullptr;
+        if (!buf) buf = (char *)malloc(cap ? cap : 1);
+        if (!buf) { (void)bam.close(); remove(o.out); fprintf(stderr, "\nError! DART_SORT_BAM=1: no host memory for a piece of %zu bytes\n", cap); return 1; }
+        float z_ms = 0.f; size_t n_pieces = 0, n_out = 0;
+        bool wrote = true;
+        for (size_t off = 0; off < n_raw && !rc && wrote; off += piece, n_pieces++) {
+            size_t nb = 0; float ms = 0.f;
+            rc = dg_bam_sort_compress(roots[0], off, std::min(piece, n_raw - off), bgzf_dynamic ? DG_BGZF_DYNAMIC : 0u, &nb, &ms);
+            if (!rc) rc = dg_batch_download_bam(roots[0], buf, cap);
+            if (!rc) { wrote = bam.add_bgzf_blocks(buf, nb, 0, 0); z_ms += ms; n_out += nb; }
+        }
+        if (pinned) dg_host_free(buf); else free(buf);
+        if (rc) return sort_fail(roots[0], rc);
+        if (!wrote) { (void)bam.close(); remove(o.out); fprintf(stderr, "Error while writing %s\n", o.out); return 1; }
+        if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing]%s: %zu records, %zu raw bytes; accumulate (sum over workers) %.3f s; merge + finish %.3f s (kernels %.3f s); compress + download + write %.3f s (BGZF kernels %.3f s, %zu pieces of %zu bytes, %zu bytes out)\n",
+                                           bam_dev_note + 1, n_sorted, n_raw, g_sort_acc_ns.load() * 1e-9, ts1 - ts0, fin_ms * 1e-3, now_s() - ts1, z_ms * 1e-3, n_pieces, piece, n_out);
+    }
+    if (o.bam) { if (!bam.close()) { if (sort_bam) remove(o.out); fprintf(stderr, "Error while writing %s\n", o.out); return 1; } }
     else fclose(sam);
     // DART_DEVICE_SJ: the clones' tables into their root's, further roots' into the first (downloaded entries, counted again there), then the table is sorted,
     // mapped to chromosomes and printed on the device: the text is junctions.tab

@@ -347,6 +347,12 @@ static bool g_device_bam = false;
 // DART_BGZF_DYNAMIC=1 beside DART_DEVICE_BAM=1: the blocks are coded with dynamic Huffman codes per strip (DG_BAM_DYNAMIC): a smaller file of the same records
 static bool g_bgzf_dynamic = false;
 static std::function<bool(const char *blocks, size_t n, long long records, long long refused)> g_bam_sink;
+// DART_SORT_BAM=1 beside DART_DEVICE_BAM=1: a batch's records are left uncompressed (DG_BAM_RAW) and appended to its context's store in HBM
+// (dg_batch_accumulate_bam) under the batch's index counted across libraries; nothing is downloaded, the ordered writer only sums the counters.  The host
+// program merges the stores, sorts and writes the file at the end of the job.
+static bool g_sort_bam = false;
+static size_t g_sort_ordinal_base = 0;      // batches of the libraries before the current one
+static std::atomic<unsigned long long> g_sort_acc_ns{0};
 // DART_DEVICE_SJ=1: every mapping thread counts its batch's junction tuples in its context's table on the GPU (dg_batch_accumulate_sj) right behind the mapping;
 // the tuples are not downloaded and the ordered writer's map loop does not run.  The host program merges the tables and prints junctions.tab from the device's
 // text at the end of the job.  The three figures below feed its `[dart sj]` line: tuples seen, time in the accumulate calls, time in the writer's map loop.
@@ -805,13 +811,19 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 const uint32_t fl = unique_only ? DG_SAM_UNIQUE_ONLY : 0u;
                 if (!g_device_bam) return in ? dg_batch_format_sam(ctx[w], in, fl, nb, s->dev_ct, &dev_ms) : dg_batch_format_sam_resident(ctx[w], npm, fl, nb, s->dev_ct, &dev_ms);
                 uint64_t ct[5] = {0, 0, 0, 0, 0}; size_t raw = 0;
-                const uint32_t bfl = fl | (g_bgzf_dynamic ? DG_BAM_DYNAMIC : 0u);
-                const int rc = in ? dg_batch_format_bam(ctx[w], in, bfl, nb, &raw, ct, &dev_ms) : dg_batch_format_bam_resident(ctx[w], npm, bfl, nb, &raw, ct, &dev_ms);
+                const uint32_t bfl = fl | (g_sort_bam ? DG_BAM_RAW : g_bgzf_dynamic ? DG_BAM_DYNAMIC : 0u);
+                int rc = in ? dg_batch_format_bam(ctx[w], in, bfl, nb, &raw, ct, &dev_ms) : dg_batch_format_bam_resident(ctx[w], npm, bfl, nb, &raw, ct, &dev_ms);
                 for (int i = 0; i < 3; i++) s->dev_ct[i] = ct[i];
                 s->bam_rr[0] = ct[3]; s->bam_rr[1] = ct[4];
+                if (!rc && g_sort_bam) {
+                    const unsigned long long t = sj_now_ns();
+                    rc = dg_batch_accumulate_bam(ctx[w], (uint32_t)(g_sort_ordinal_base + s->seqno), nullptr, nullptr);
+                    g_sort_acc_ns += sj_now_ns() - t;
+                    *nb = 0;                                  // the records stay in HBM: the slot carries the counters alone
+                }
                 return rc;
             };
-            auto dev_download = [&]() -> int { return g_device_bam ? dg_batch_download_bam(ctx[w], s->text, s->text_cap) : dg_batch_download_sam(ctx[w], s->text, s->text_cap); };
+            auto dev_download = [&]() -> int { return g_sort_bam ? 0 : g_device_bam ? dg_batch_download_bam(ctx[w], s->text, s->text_cap) : dg_batch_download_sam(ctx[w], s->text, s->text_cap); };
             if (!s->rc && dev_out && s->fq_device) {
                 // names and qualities are in HBM already, in stored order: nothing to gather
                 size_t nb = 0;

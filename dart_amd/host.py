@@ -290,6 +290,17 @@ def _load_lib():
         lib.dg_sj_download.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
         lib.dg_sj_device.argtypes = [vp, vp, vp]
         lib.dg_sj_granules.argtypes = [vp]
+    if hasattr(lib, "dg_bam_sort_finish"):                   # (likewise: coordinate-sorted BAM on the device)
+        lib.dg_batch_accumulate_bam.argtypes = [vp, C.c_uint32, vp, vp]
+        lib.dg_bam_sort_add.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp]
+        lib.dg_bam_sort_merge.argtypes = [vp, vp]
+        lib.dg_bam_sort_reset.argtypes = [vp]
+        lib.dg_bam_sort_finish.argtypes = [vp, vp, vp, vp]
+        lib.dg_bam_sort_device_ms.argtypes = [vp, vp, vp]
+        lib.dg_bam_sort_device.argtypes = [vp, vp, vp]
+        lib.dg_bam_sort_compress.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_uint32, vp, vp]
+        lib.dg_bam_sort_granules.argtypes = [vp]
+        lib.dg_bam_sort_info.argtypes = [vp, vp]                # (a test hook, not in include/dartgpu.h)
     lib.dg_last_counters.argtypes = [vp, vp, C.c_int]
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
@@ -635,6 +646,65 @@ class DartGPU:
         ent = np.zeros(max(int(ne.value), 1), SJ_ENTRY); text = np.zeros(max(int(nb.value), 1), np.uint8)
         self._chk(self.lib.dg_sj_download(self.ctx, ent.ctypes.data, int(ne.value), text.ctypes.data, int(nb.value)), "dg_sj_download")
         return ent[:int(ne.value)], text[:int(nb.value)].tobytes()
+
+    # ---- coordinate-sorted BAM on the device (dg_bam_sort_*): every batch's records stay in HBM, one sort at the end of the job ----
+    def bam_sort_granules(self):
+        """(reads per workgroup of the two key kernels, pairs per tile of the sorter, the store's smallest size in bytes) (dg_bam_sort_granules)"""
+        g = (C.c_int * 3)()
+        self._chk(self.lib.dg_bam_sort_granules(g), "dg_bam_sort_granules")
+        return int(g[0]), int(g[1]), int(g[2])
+
+    def bam_sort_info(self):
+        """the store: dict(records, bytes, segments, growths = the calls in which it grew) (dg_bam_sort_info, a test hook)"""
+        o = (C.c_size_t * 4)()
+        self._chk(self.lib.dg_bam_sort_info(self.ctx, o), "dg_bam_sort_info")
+        return dict(records=int(o[0]), bytes=int(o[1]), segments=int(o[2]), growths=int(o[3]))
+
+    def accumulate_bam(self, ordinal: int) -> int:
+        """appends the uncompressed records the last format_bam left for the current batch to the context's store under this ordinal
+        (dg_batch_accumulate_bam) -> the number of records; self.bam_sort_added_bytes holds their bytes"""
+        n = C.c_size_t(0); nb = C.c_size_t(0)
+        self._chk(self.lib.dg_batch_accumulate_bam(self.ctx, int(ordinal), C.byref(n), C.byref(nb)), "dg_batch_accumulate_bam")
+        self.bam_sort_added_bytes = int(nb.value)
+        split = (C.c_float * 5)()
+        self.lib.dg_bam_sort_device_ms(self.ctx, split, None)
+        self.bam_sort_accumulate_ms = float(split[4])        # device time of the key kernels and the copy
+        return int(n.value)
+
+    def bam_sort_add(self, data, ordinal: int) -> int:
+        """appends whole uncompressed BAM records from host memory (dg_bam_sort_add) -> the number of records"""
+        a = np.frombuffer(bytes(data) + b"\0", np.uint8)
+        n = C.c_size_t(0)
+        self._chk(self.lib.dg_bam_sort_add(self.ctx, a.ctypes.data, len(a) - 1, int(ordinal), C.byref(n)), "dg_bam_sort_add")
+        return int(n.value)
+
+    def bam_sort_merge(self, src: "DartGPU"):
+        """appends src's store to this context's and leaves src's empty (dg_bam_sort_merge)"""
+        self._chk(self.lib.dg_bam_sort_merge(self.ctx, src.ctx), "dg_bam_sort_merge")
+
+    def bam_sort_reset(self):
+        self._chk(self.lib.dg_bam_sort_reset(self.ctx), "dg_bam_sort_reset")
+
+    def bam_sort_finish(self):
+        """sorts the store's records into one contiguous array in HBM (dg_bam_sort_finish) -> (records, raw bytes); self.bam_sort_device_ms holds the
+        device time, self.bam_sort_device_ms_split (segment ordering, sort, lengths + scan, gather), self.bam_sort_passes the sorter's passes"""
+        n = C.c_size_t(0); nb = C.c_size_t(0); ms = C.c_float(0)
+        self._chk(self.lib.dg_bam_sort_finish(self.ctx, C.byref(n), C.byref(nb), C.byref(ms)), "dg_bam_sort_finish")
+        split = (C.c_float * 5)(); passes = C.c_int(0)
+        self.lib.dg_bam_sort_device_ms(self.ctx, split, C.byref(passes))
+        self.bam_sort_device_ms, self.bam_sort_device_ms_split, self.bam_sort_passes = float(ms.value), tuple(float(x) for x in split[:4]), int(passes.value)
+        return int(n.value), int(nb.value)
+
+    def bam_sort_compress(self, off: int, length: int, raw: bool = False, dynamic: bool = False) -> bytes:
+        """one range of the sorted array as BGZF blocks, or with raw=True as it is (dg_bam_sort_compress + dg_batch_download_bam); off must be a multiple
+        of 0xff00, length such a multiple or reach the array's end; self.bam_device_ms holds the BGZF kernels' device time"""
+        nb = C.c_size_t(0); ms = C.c_float(0)
+        flags = BAM_RAW if raw else (BGZF_DYNAMIC if dynamic else 0)
+        self._chk(self.lib.dg_bam_sort_compress(self.ctx, int(off), int(length), flags, C.byref(nb), C.byref(ms)), "dg_bam_sort_compress")
+        self.bam_device_ms = float(ms.value)
+        out = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_batch_download_bam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_bam")
+        return out[:int(nb.value)].tobytes()
 
     def wait_index(self):
         self._chk(self.lib.dg_index_wait(self.ctx), "dg_index_wait")

@@ -382,6 +382,50 @@ int dg_sj_download(dg_ctx *, dg_sj_entry *entries, size_t cap_entries, char *tex
 int dg_sj_device(dg_ctx *, void **entries, void **text);
 int dg_sj_granules(int out[2]);
 
+/* ---- coordinate-sorted BAM on the device: the records of every batch stay in HBM, one sort at the end (the reference has no such output: an opt-in
+ * extension; it replaces the `samtools sort` a user runs behind `dart -bo`) ----
+ * Every context owns a store: the bytes of whole uncompressed BAM records, and per record one 64-bit key and its offset.  The order is defined by a record's
+ * own bytes -- refID at byte 4, pos at byte 8, flag at byte 18, little endian, read byte by byte (records are not aligned):
+ *     tid' = refID when 0 <= refID < n_chr, else n_chr (unplaced records come last)
+ *     key  = tid' << 33 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1)
+ * ascending key; equal keys keep their input order: ascending ordinal (the caller's number of the batch), then the record's place in its batch; segments with
+ * equal ordinals in the order of their calls.  This is the comparison `samtools sort` makes by default (tid as unsigned, pos, reverse strand, stable); no
+ * samtools exists where this library is built and tested, so the definition here -- not a run of samtools -- is what the tests pin.
+ * The same records under the same ordinals give the same bytes whatever the batch split, the order of the calls, the contexts used or the growth history.
+ * Every failure leaves the context and the store usable, with a text in dg_last_error; dg_destroy frees the store.  Memory: the store holds the raw bytes
+ * and 16 bytes per record; dg_bam_sort_finish adds the sorted array (the raw bytes again) and 32 bytes per record.  The store grows by doubling and keeps
+ * its content (allocate, copy on the context's stream, free); when hipMalloc fails: DG_ERR_CAPACITY, the text names the need, the store stays as it was.
+ *   dg_batch_accumulate_bam  appends the uncompressed records the last dg_batch_format_bam[_resident] left for the current batch (with or without
+ *                            DG_BAM_RAW): a count pass over the reads (0 to several records each), a scan, an emit pass and a device copy on the context's
+ *                            stream, one wait.  DG_ERR_ARG: no records of the current batch are there (no dg_batch_format_bam since the upload / run, or a
+ *                            dg_batch_format_sam behind it, which reuses the per-read offsets; dg_bgzf_compress does not count); a second call on the same
+ *                            batch.  A batch of 0 records adds nothing.  *n_records / *n_bytes (may be NULL): what was added.
+ *   dg_bam_sort_add          whole uncompressed records from host memory: how a multi-device host folds in another device's records.  The host walks them
+ *                            once and checks block_size >= 32 + l_read_name + 4 * n_cigar_op + (l_seq + 1) / 2 + l_seq, l_read_name >= 1, refID < n_chr,
+ *                            pos >= -1, and that the sizes add up to exactly n; else DG_ERR_ARG, the text names the first bad record, nothing is added.
+ *   dg_bam_sort_merge        appends src's store to dst's (its segments behind dst's own) and leaves src empty; both on one device, ordered behind both
+ *                            contexts' streams; DG_ERR_ARG for dst == src or different devices
+ *   dg_bam_sort_reset        an empty store; the storage is kept
+ *   dg_bam_sort_finish       the segments in ordinal order, one stable radix sort over 33 + bits(n_chr) key bits, the records' lengths in sorted order, a
+ *                            scan, and a gather into one contiguous array.  The store stays intact: more batches may follow and the call may be repeated.
+ *                            An empty store: 0 records, 0 bytes.  The array is valid until the next store call on the context.  *device_ms (may be NULL):
+ *                            device time, a measurement; dg_bam_sort_device_ms splits it: [0] segment ordering, [1] the sort (*n_passes passes), [2] lengths
+ *                            and scan, [3] the gather, and [4] the key kernels and the copy of the last dg_batch_accumulate_bam.  dg_bam_sort_device: the array in HBM.
+ *   dg_bam_sort_compress     one range of the sorted array -> BGZF blocks (flags 0, or DG_BGZF_DYNAMIC), or the bytes as they are (DG_BAM_RAW); the result
+ *                            lies where dg_batch_download_bam / dg_batch_device_bam find it.  raw_off must be a multiple of 0xff00 and raw_len such a multiple
+ *                            or reach the array's end (else DG_ERR_ARG): so the concatenated output is the same bytes whatever piece size the caller picks,
+ *                            and an array of 20 GB never needs 20 GB of block slots at once.
+ *   dg_bam_sort_granules     [0] reads per workgroup of the two key kernels, [1] pairs per tile of the sorter, [2] the store's smallest size in bytes    */
+int dg_batch_accumulate_bam(dg_ctx *, uint32_t ordinal, size_t *n_records, size_t *n_bytes);
+int dg_bam_sort_add(dg_ctx *, const void *records, size_t n, uint32_t ordinal, size_t *n_records);
+int dg_bam_sort_merge(dg_ctx *dst, dg_ctx *src);
+int dg_bam_sort_reset(dg_ctx *);
+int dg_bam_sort_finish(dg_ctx *, size_t *n_records, size_t *n_raw, float *device_ms);
+int dg_bam_sort_device_ms(dg_ctx *, float ms[5], int *n_passes);
+int dg_bam_sort_device(dg_ctx *, void **ptr, size_t *n_raw);
+int dg_bam_sort_compress(dg_ctx *, size_t raw_off, size_t raw_len, uint32_t flags, size_t *n_bytes, float *device_ms);
+int dg_bam_sort_granules(int out[3]);
+
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
 int dg_last_timings(dg_ctx *, const char **names, float *ms, int cap);
