@@ -880,6 +880,25 @@ static void aids_thread(IndexShared *sh, int sa_file_intv, uint64_t n_sa, bool a
     sh->cv.notify_all();
 }
 
+// The second strand of the text, once per index: pac arrives as the forward half (PREFIX.pac, or the caller's array) and leaves dg_init* as all 2L symbols,
+// so that no kernel computes a reverse complement per access (d_pac_both, dg_common.h).  Thread = output byte, from the byte that holds symbol L on; that
+// byte is composed of forward symbols and the first reverse ones when L is no multiple of 4.
+__global__ void __launch_bounds__(256)
+k_pac_both(uint8_t *pac, int64_t L, int64_t first_byte, int64_t n_bytes)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n_bytes) pac[first_byte + i] = d_pac_both_byte(pac, L, first_byte + i);
+}
+static size_t pac_both_bytes(int64_t L) { return (size_t)((2 * L + 3) / 4); }
+static hipError_t pac_fill_second_half(uint8_t *d_pac, int64_t L, hipStream_t s)
+{
+    const int64_t first = L / 4, n = (int64_t)pac_both_bytes(L) - first;
+    if (n <= 0) return hipSuccess;
+    k_pac_both<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(d_pac, L, first, n);
+    hipError_t e = hipGetLastError();
+    return e != hipSuccess ? e : hipStreamSynchronize(s);
+}
+
 struct IndexMeta { uint64_t bwt_words, primary, L2[5], seq_len, n_sa; int sa_intv; int64_t l_pac; int n_chr; const int64_t *chr_off, *chr_len; uint64_t expected_reads; };
 
 // everything of dg_init / dg_init_files behind the argument checks: contexts objects, index arrays, the upload, the aids
@@ -911,7 +930,7 @@ static dg_ctx *init_index(const IndexMeta &m, UpSrc bwt, uint64_t bwt_off, UpSrc
 
     // ---- index arrays: the .bwt blocks at a 64-byte aligned base (+ two blocks of padding so the last, possibly partial, block can be
     //      fetched whole), sampled SA, pac, chromosome keys
-    const size_t bwt_bytes = (size_t)m.bwt_words * 4, sa_bytes = (size_t)m.n_sa * 8, pac_bytes = (size_t)(m.l_pac / 4 + 1);
+    const size_t bwt_bytes = (size_t)m.bwt_words * 4, sa_bytes = (size_t)m.n_sa * 8, pac_bytes = std::max(pac_both_bytes(m.l_pac), (size_t)(m.l_pac / 4 + 1));   // both strands: 2 bits x 2L
     const uint64_t n_blocks = (m.seq_len + 127) / 128;
     if (bwt_bytes > (n_blocks + 1) * 64) return bail(DG_ERR_ARG, "the .bwt data is larger than its header's text length allows", hipSuccess);
     if ((e = hipMalloc(&c->d_bwt, (n_blocks + 2) * 64)) != hipSuccess || (e = hipMemsetAsync(c->d_bwt, 0, (n_blocks + 2) * 64, c->stream)) != hipSuccess) return bail(DG_ERR_HIP, "hipMalloc bwt", e);
@@ -942,6 +961,7 @@ static dg_ctx *init_index(const IndexMeta &m, UpSrc bwt, uint64_t bwt_off, UpSrc
     c->ix.primary = m.primary; for (int i = 0; i < 5; i++) c->ix.L2[i] = m.L2[i]; c->ix.seq_len = m.seq_len;
     c->ix.l_pac = m.l_pac; c->ix.n_chr = m.n_chr; c->ix.sa_intv = m.sa_intv;
     c->ix.ktab = nullptr; c->ix.ktab_k = 0; c->ix.sa_dense = nullptr; c->ix.sa_dense_intv = 0; c->ix.sa_dense_shift = 0;
+    c->ix.pac_both = 1;                    // (the second half is filled below, before the first kernel that reads pac can start)
     IndexShared *sh = c->shared_ix;
     sh->ix = c->ix; c->ix_gen = sh->gen.load();
     const double t_alloc = now_s();
@@ -958,15 +978,17 @@ static dg_ctx *init_index(const IndexMeta &m, UpSrc bwt, uint64_t bwt_off, UpSrc
     n_threads = (int)std::min<size_t>((size_t)n_threads, std::max<size_t>(1, chunks.size()));
     std::string what;
     e = upload_chunks(device, chunks, chunk, n_threads, what);
+    const double t_fwd = now_s();
+    if (e == hipSuccess && (e = pac_fill_second_half((uint8_t *)c->d_pac, m.l_pac, c->stream)) != hipSuccess) what = "k_pac_both (the second strand of pac)";
+    const double t_both = now_s() - t_fwd;
     { std::lock_guard<std::mutex> lk(sh->mu); sh->upload_done = true; sh->upload_ok = e == hipSuccess; }
     sh->cv.notify_all();
     if (e != hipSuccess) return bail(what.find("shorter") != std::string::npos ? DG_ERR_ARG : DG_ERR_HIP, what.c_str(), what.find("shorter") != std::string::npos ? hipSuccess : e);
-    const double t_up = now_s();
     {
         std::lock_guard<std::mutex> lk(sh->mu);
-        char b[320];
-        snprintf(b, sizeof b, "context %.3f s, index arrays (hipMalloc + fill) %.3f s, %s -> HBM + Occ re-layout %.3f s (%.2f GB, %d reader threads)",
-                 t_ctx - t_start, t_alloc - t_ctx, bwt.mem ? "host arrays" : "index files", t_up - t_alloc, (bwt_bytes + sa_count * 8 + pac_copy) / 1e9, n_threads);
+        char b[400];
+        snprintf(b, sizeof b, "context %.3f s, index arrays (hipMalloc + fill) %.3f s, %s -> HBM + Occ re-layout %.3f s (%.2f GB, %d reader threads), second strand of pac (k_pac_both) %.4f s",
+                 t_ctx - t_start, t_alloc - t_ctx, bwt.mem ? "host arrays" : "index files", t_fwd - t_alloc, (bwt_bytes + sa_count * 8 + pac_copy) / 1e9, n_threads, t_both);
         sh->report = std::string(b) + sh->report;
     }
     if (!(flags & DG_INIT_ASYNC_AIDS)) {
@@ -3363,13 +3385,14 @@ extern "C" int dg_probe_nw_mode(dg_ctx *c, int mode, int n, const uint32_t *a_of
     if (tot > cap) return DG_ERR_CAPACITY;
     const size_t la = a_off[n], lb = b_off[n];
     std::vector<uint8_t> pac;
-    if (mode >= 2) {                                   // the genome side as a forward-strand pac (2 bit/base, first base on top)
-        pac.assign(lb / 4 + 1 + 64, 0);
+    if (mode >= 2) {                                   // the genome side as a pac (2 bit/base, first base on top): forward strand, then -- as every pac a kernel sees -- its reverse complement
+        pac.assign(pac_both_bytes((int64_t)lb) + 4096, 0);
         for (size_t k = 0; k < lb; k++) {
             const uint8_t code = d_nt4((unsigned char)b[k]);
             if (code > 3) { snprintf(c->err, 512, "dg_probe_nw_mode %d: the genome side must be ACGT (RefSequence holds nothing else)", mode); return DG_ERR_ARG; }
             pac[k >> 2] |= (uint8_t)(code << ((~k & 3) << 1));
         }
+        for (size_t q = lb / 4; q < pac_both_bytes((int64_t)lb); q++) pac[q] = d_pac_both_byte(pac.data(), (int64_t)lb, (int64_t)q);
     }
     const WSLayout L = make_ws_layout(mx);
     DevTmp tmp;
@@ -3388,14 +3411,36 @@ extern "C" int dg_probe_nw_mode(dg_ctx *c, int mode, int n, const uint32_t *a_of
     else {
         HIPCHK(tmp.alloc((void **)&d_pac, pac.size()));
         HIPCHK(hipMemcpy(d_pac, pac.data(), pac.size(), hipMemcpyHostToDevice));
-        DIndex fx = c->ix;                              // a text that is just the b strings, forward strand only
-        fx.pac = d_pac; fx.l_pac = (int64_t)lb;
+        DIndex fx = c->ix;                              // a text that is just the b strings
+        fx.pac = d_pac; fx.l_pac = (int64_t)lb; fx.pac_both = 1;
         k_probe_nw_wave<<<nblk, 64, 0, c->stream>>>(n, mode == 3 ? 1 : 0, d_aoff, d_boff, d_a, d_ooff, d_olen, d_oa, d_ob, d_ws, L, fx, c->pr);
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(c->stream));
     HIPCHK(hipMemcpy(out_len, d_olen, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out_a, d_oa, tot, hipMemcpyDeviceToHost)); HIPCHK(hipMemcpy(out_b, d_ob, tot, hipMemcpyDeviceToHost));
+    return DG_OK;
+}
+
+// RefSequence[g0, g0 + n) as the kernels see it: d_refchar per position (0 outside [0, 2L))
+__global__ void __launch_bounds__(256)
+k_probe_refseq(const DIndex ix, int64_t g0, int64_t n, char *out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = d_refchar(ix, g0 + i);
+}
+extern "C" int dg_probe_refseq(dg_ctx *c, int64_t g0, int64_t n, char *out)
+{
+    if (!c || !out || n < 0 || n > ((int64_t)1 << 30)) return DG_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    if (n == 0) return DG_OK;
+    DevTmp tmp;
+    char *d_out = nullptr;
+    HIPCHK(tmp.alloc((void **)&d_out, (size_t)n));
+    k_probe_refseq<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->ix, g0, n, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpy(out, d_out, (size_t)n, hipMemcpyDeviceToHost));
     return DG_OK;
 }
 

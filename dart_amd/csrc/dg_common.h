@@ -85,7 +85,41 @@ struct DIndex {
     int32_t  n_chr, sa_intv;
     int32_t  ktab_k, sa_dense_intv;
     int32_t  sa_dense_shift;      // log2(sa_dense_intv): a 64-bit division by a run-time value is ~150 instructions per lane
+    int32_t  pac_both;            // 1 = pac holds all 2L symbols of the text (forward strand, then its reverse complement: k_pac_both), 0 = the forward half only
 };
+static_assert(sizeof(DIndex) == 8 * 8 + 7 * 8 + 8 + 6 * 4, "pac_both sits in what was padding: the kernels' scalar registers hold the same words as before");
+
+// Which form of pac the code reads.  Every DIndex a kernel is launched with holds both strands (dg_init* build the second half before they return,
+// the probes that bring a text of their own do the same), so device code does not ask: the forward-only forms are not compiled into any kernel.
+// Host-compiled code (the host checks under tests/native) looks at the flag; a zeroed DIndex keeps the forward-only forms, which stay the reference form.
+__host__ __device__ __forceinline__ bool d_pac_both(const DIndex &ix)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    (void)ix; return true;
+#else
+    return ix.pac_both != 0;
+#endif
+}
+
+// One byte of the both-strand pac: symbols 4b .. 4b+3 of T[0, 2L), T[t] = fwd[t] below L and 3 - fwd[2L-1-t] from L on, 0 behind the text; first symbol
+// in the top bits.  Reads forward symbols only (bytes up to L/4, and of byte L/4 only the bits of symbols below L, which a concurrent writer of that
+// byte leaves as they are), so the array can be completed in place.
+__host__ __device__ __forceinline__ uint8_t d_pac_both_byte(const uint8_t *pac, int64_t L, int64_t b)
+{
+    uint32_t out = 0;
+    for (int k = 0; k < 4; k++) {
+        const int64_t t = 4 * b + k;
+        uint32_t c = 0;
+        if (t < 2 * L) {
+            const bool rev = t >= L;
+            const int64_t f = rev ? 2 * L - 1 - t : t;
+            c = (pac[f >> 2] >> ((~f & 3) << 1)) & 3u;
+            if (rev) c = 3u - c;
+        }
+        out |= c << ((3 - k) << 1);
+    }
+    return (uint8_t)out;
+}
 
 struct DParams {
     int32_t max_gaps, max_dup, max_intron, min_intron, max_mismatch, multi_hit, all_sj, paired;
@@ -126,11 +160,12 @@ __host__ __device__ __forceinline__ uint8_t d_nt4(unsigned char c)   // nst_nt4_
     return (uint8_t)(acgt ? code : (c == '-' ? 5u : 4u));
 }
 
-// RefSequence[g] (bwt_index.cpp:193-212,252) computed from the forward 2-bit pac; 0 outside [0,2L)
+// RefSequence[g] (bwt_index.cpp:193-212,252) from the 2-bit pac (both strands stored, or computed from the forward half); 0 outside [0,2L)
 __host__ __device__ __forceinline__ char d_refchar(const DIndex &ix, int64_t g)
 {
     const int64_t L = ix.l_pac;
     if (g < 0 || g >= 2 * L) return 0;
+    if (d_pac_both(ix)) return (char)(0x54474341u >> (8u * ((ix.pac[g >> 2] >> ((~g & 3) << 1)) & 3u)));
     const bool rev = g >= L;
     const int64_t f = rev ? 2 * L - 1 - g : g;
     const uint32_t c = (ix.pac[f >> 2] >> ((~f & 3) << 1)) & 3u;
@@ -145,13 +180,13 @@ __host__ __device__ __forceinline__ uint64_t d_ref8(const DIndex &ix, int64_t g0
 {
     const int64_t L = ix.l_pac;
     uint64_t out = 0;
-    if (g0 >= 0 && g0 + 8 <= L) {                              // forward strand: 8 bases = 16 bits out of 3 pac bytes
+    if (g0 >= 0 && g0 + 8 <= (d_pac_both(ix) ? 2 * L : L)) {   // 8 bases = 16 bits out of 3 pac bytes (forward-only form: the forward strand)
         const uint32_t w = __builtin_bswap32(*(const uint32_a1 *)(ix.pac + (g0 >> 2))) << ((g0 & 3) << 1);
 #pragma unroll
         for (int k = 0; k < 8; k++) out |= (uint64_t)((0x54474341u >> (8u * ((w >> (30 - 2 * k)) & 3u))) & 0xFFu) << (8 * k);
         return out;
     }
-    if (g0 >= L && g0 + 8 <= 2 * L) {                          // reverse strand: Ref[g0+k] = comp(fwd[f0-k])
+    if (!d_pac_both(ix) && g0 >= L && g0 + 8 <= 2 * L) {       // reverse strand from the forward half: Ref[g0+k] = comp(fwd[f0-k])
         const int64_t f0 = 2 * L - 1 - g0, lo = f0 - 7;        // fwd[lo..f0]
         const uint32_t w = __builtin_bswap32(*(const uint32_a1 *)(ix.pac + (lo >> 2))) << ((lo & 3) << 1);   // fwd[lo+q] at bits 31-2q
 #pragma unroll
@@ -160,6 +195,66 @@ __host__ __device__ __forceinline__ uint64_t d_ref8(const DIndex &ix, int64_t g0
     }
     for (int k = 0; k < 8; k++) out |= (uint64_t)(unsigned char)d_refchar(ix, g0 + k) << (8 * k);
     return out;
+}
+
+// ---- 64 text symbols T[t .. t+64) for the seeding stage's comparisons with a read: four words of 16 symbols, first symbol in the top bits (the read's
+// format), and nv = how many of the 64 exist (symbols behind the text are 0).  In two steps, because the seeding kernels issue their loads from one place:
+// d_text64_at says which five 32-bit words of pac to load, d_text64_words turns them into the window; d_text64 is both at once.
+// pac with both strands: every window is read as stored; one that runs past the end of the text reads the zeroed pad behind it with nv clamped, and one
+// that begins outside the text has nv = 0 (and reads the pad).  The pad is 4096 bytes, a window 24.
+// pac with the forward half only (host-compiled code with pac_both == 0): a window inside the reverse half is the mirrored forward window, its 2-bit groups
+// reversed and complemented; one that straddles the strand boundary or an end of the text is put together symbol by symbol (`slow`: nothing to load).
+struct Text64 { uint32_t T0, T1, T2, T3; int nv; };
+struct Text64At { int64_t word; uint32_t sh; int nv; bool mirror, slow; };
+__host__ __device__ __forceinline__ uint32_t d_fsl(uint32_t lo, uint32_t hi, uint32_t sh)      // the top word of (hi:lo) << sh, sh < 32
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __funnelshift_l(lo, hi, sh);
+#else
+    return sh ? (hi << sh) | (lo >> (32u - sh)) : hi;
+#endif
+}
+__host__ __device__ __forceinline__ uint32_t d_rev2(uint32_t x)      // reverse the order of the 16 2-bit groups
+{
+    const uint32_t y = __builtin_bitreverse32(x);
+    return ((y & 0x55555555u) << 1) | ((y >> 1) & 0x55555555u);
+}
+__host__ __device__ __forceinline__ Text64At d_text64_at(const DIndex &ix, int64_t t)
+{
+    const int64_t L = ix.l_pac, left = t >= 0 ? 2 * L - t : 0;
+    Text64At a;
+    a.nv = left >= 64 ? 64 : (left > 0 ? (int)left : 0); a.mirror = false; a.slow = false;
+    int64_t f0 = a.nv ? t : 2 * L;
+    if (!d_pac_both(ix)) {
+        if (t >= 0 && t + 64 <= L) f0 = t;
+        else if (t >= L && t + 64 <= 2 * L) { f0 = 2 * L - 1 - t - 63; a.mirror = true; }
+        else { f0 = 0; a.slow = true; }
+    }
+    a.word = f0 >> 4; a.sh = (uint32_t)((f0 & 15) << 1);
+    return a;
+}
+// r0 .. r4: the words pac32[a.word .. a.word + 5) as loaded (not for a.slow)
+__host__ __device__ __forceinline__ Text64 d_text64_words(const DIndex &ix, const Text64At &a, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t r4)
+{
+    const uint32_t d0 = __builtin_bswap32(r0), d1 = __builtin_bswap32(r1), d2 = __builtin_bswap32(r2), d3 = __builtin_bswap32(r3), d4 = __builtin_bswap32(r4);
+    const uint32_t t0 = d_fsl(d1, d0, a.sh), t1 = d_fsl(d2, d1, a.sh), t2 = d_fsl(d3, d2, a.sh), t3 = d_fsl(d4, d3, a.sh);
+    Text64 x;
+    x.nv = a.nv;
+    if (!d_pac_both(ix) && a.mirror) { x.T0 = ~d_rev2(t3); x.T1 = ~d_rev2(t2); x.T2 = ~d_rev2(t1); x.T3 = ~d_rev2(t0); }   // T[t+j] = 3 - fwd[2L-1-t-j]
+    else { x.T0 = t0; x.T1 = t1; x.T2 = t2; x.T3 = t3; }
+    return x;
+}
+__host__ __device__ inline Text64 d_text64(const DIndex &ix, int64_t t)
+{
+    const Text64At a = d_text64_at(ix, t);
+    if (!d_pac_both(ix) && a.slow) {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+        for (int j = 0; j < a.nv; j++) w[j >> 4] |= (uint32_t)d_nt4((unsigned char)d_refchar(ix, t + j)) << (30 - 2 * (j & 15));
+        Text64 x; x.T0 = w[0]; x.T1 = w[1]; x.T2 = w[2]; x.T3 = w[3]; x.nv = a.nv;
+        return x;
+    }
+    const uint32_t *pw = (const uint32_t *)ix.pac + a.word;
+    return d_text64_words(ix, a, pw[0], pw[1], pw[2], pw[3], pw[4]);
 }
 
 // RefSequence[g0 .. g0+n) into dst, eight bases per pac fetch (a per-base d_refchar is a dependent load each, and on a

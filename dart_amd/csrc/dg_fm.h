@@ -276,22 +276,6 @@ k_build_ktab(const DIndex ix, int K, uint64_t *__restrict__ tab)
 // ---------------------------------------------------------------------------------------------
 #define SEED_REFILL 8
 
-// slow path of the text comparison (strand boundary, end of the text): up to 16 symbols T[t..t+16) in the
-// read's format (first symbol in the top bits); *nv = how many exist.  T = forward strand + reverse
-// complement, read from the forward pac.
-__device__ __forceinline__ uint32_t d_text16_slow(const DIndex &ix, int64_t t, int &nv)
-{
-    uint32_t y = 0;
-    nv = 0;
-    for (int j = 0; j < 16; j++) {
-        const char ch = d_refchar(ix, t + j);
-        if (ch == 0) break;
-        y |= (uint32_t)d_nt4((unsigned char)ch) << (30 - 2 * j);
-        nv = j + 1;
-    }
-    return y;
-}
-
 // One BWT_Search (bwt_search.cpp:139-182) in flight, advanced one memory access per trip:
 // mode 1 = FM steps, 3 = locating the unique row (LF steps), 2 = comparing with the text, 0 = done.
 struct Search {
@@ -316,11 +300,6 @@ __device__ __forceinline__ uint32_t d_win16(F &f, int q)
 }
 template <class F>
 __device__ __forceinline__ uint32_t d_at(F &f, int q) { return (f(q >> 4) >> (30 - ((q & 15) << 1))) & 3u; }
-__device__ __forceinline__ uint32_t d_rev2(uint32_t x)      // reverse the order of the 16 2-bit groups
-{
-    const uint32_t y = __brev(x);
-    return ((y & 0x55555555u) << 1) | ((y >> 1) & 0x55555555u);
-}
 
 __device__ __forceinline__ void d_search_end(const DParams &pr, Search &s)   // bwt_search.cpp:173-179
 {
@@ -340,7 +319,7 @@ typedef uint4 __attribute__((aligned(4))) uint4_a4;
 typedef uint2 __attribute__((aligned(4))) uint2_a4;
 struct TripAddr { const uint4 *pa, *pb; const uint4_a4 *p16; const uint2_a4 *p8; };     // nullptr = not needed
 struct TripData { OccBlock a, b; uint4 s16; uint2 s8; uint64_t kk, ll; uint32_t aux; };
-enum { T_NONE = 0, T_TABLE, T_SINGLE, T_STEP, T_STOP, T_LF, T_LF_PRIMARY, T_SA, T_CMP, T_CMP_SLOW };
+enum { T_NONE = 0, T_TABLE, T_SINGLE, T_STEP, T_STOP, T_LF, T_LF_PRIMARY, T_SA, T_CMP };
 
 __device__ __forceinline__ void d_trip_load(const TripAddr &ta, TripData &t)
 {
@@ -414,21 +393,16 @@ __device__ __forceinline__ void d_trip_issue(const DIndex &ix, RM &rm, int len, 
             ta.p8 = (const uint2_a4 *)(ix.sa_dense + (s.lk >> ix.sa_dense_shift));
             t.aux = T_SA;
         }
-    } else if ((MODES & TM_CMP) && mode == 2) {    // 64 text symbols = five pac words
-        const int64_t tt = s.tpos + (s.p - s.start), L = ix.l_pac;
-        const uint32_t *pw = (const uint32_t *)ix.pac;
-        int64_t f0 = -1;                           // first forward-strand symbol of the window
-        if (tt >= 0 && tt + 64 <= L) { f0 = tt; t.ll = 0; }
-        else if (tt >= L && tt + 64 <= 2 * L) { f0 = 2 * L - 1 - tt - 63; t.ll = 1; }
-        if (f0 >= 0) {
-            ta.p16 = (const uint4_a4 *)(pw + (f0 >> 4)); ta.p8 = (const uint2_a4 *)(pw + (f0 >> 4) + 4);
-            t.kk = (uint64_t)((f0 & 15) << 1); t.aux = T_CMP;
-        } else t.aux = T_CMP_SLOW;
+    } else if ((MODES & TM_CMP) && mode == 2) {    // 64 text symbols = five pac words, on either strand as stored (d_text64_at)
+        const Text64At at = d_text64_at(ix, s.tpos + (s.p - s.start));
+        const uint32_t *pw = (const uint32_t *)ix.pac + at.word;
+        ta.p16 = (const uint4_a4 *)pw; ta.p8 = (const uint2_a4 *)(pw + 4);
+        t.kk = (uint64_t)at.sh; t.ll = (uint64_t)at.nv; t.aux = T_CMP;
     }
 }
 
 // modes 1,3,2: consume the loads; when the search finishes, mode becomes 0 and hit_len/located hold the result.
-// MODES: the modes the trip can have been issued in (step: T_STOP / T_STEP, locate: T_LF / T_LF_PRIMARY / T_SA, compare: T_CMP / T_CMP_SLOW); only
+// MODES: the modes the trip can have been issued in (step: T_STOP / T_STEP, locate: T_LF / T_LF_PRIMARY / T_SA, compare: T_CMP); only
 // their code is instantiated -- with a run-time `aux` alone every instance carried all of it (the per-base slow text comparison included)
 template <int MODES = TM_ALL, class RB, class RM>
 __device__ __forceinline__ void d_trip_finish(const DIndex &ix, const DParams &pr, RB &rb, RM &rm, int len, Search &s, SeedCtr &c, const TripData &t)
@@ -447,16 +421,13 @@ __device__ __forceinline__ void d_trip_finish(const DIndex &ix, const DParams &p
         s.tpos = (int64_t)(s.lsteps + (e & 0xFFFFFFFFFFull) - 1);
         s.lk = e;                                  // keeps the memoised reference LF count (bits 40..)
         s.mode = 2; c.n_direct++;
-    } else if ((MODES & TM_CMP) && (t.aux == T_CMP || t.aux == T_CMP_SLOW)) {      // the interval is one text position: compare up to 64 bases
-        int nv = 64, chunk = 64;
-        uint32_t T0, T1 = 0, T2 = 0, T3 = 0;
-        if (t.aux == T_CMP) {
-            const uint32_t d0 = __builtin_bswap32(t.s16.x), d1 = __builtin_bswap32(t.s16.y), d2 = __builtin_bswap32(t.s16.z),
-                           d3 = __builtin_bswap32(t.s16.w), d4 = __builtin_bswap32(t.s8.x), o = (uint32_t)t.kk;
-            const uint32_t s0 = __funnelshift_l(d1, d0, o), s1 = __funnelshift_l(d2, d1, o), s2 = __funnelshift_l(d3, d2, o), s3 = __funnelshift_l(d4, d3, o);
-            if (t.ll) { T0 = ~d_rev2(s3); T1 = ~d_rev2(s2); T2 = ~d_rev2(s1); T3 = ~d_rev2(s0); }   // T[t+j] = 3 - fwd[2L-1-t-j]
-            else { T0 = s0; T1 = s1; T2 = s2; T3 = s3; }
-        } else { T0 = d_text16_slow(ix, s.tpos + (s.p - s.start), nv); chunk = 16; }
+    } else if ((MODES & TM_CMP) && t.aux == T_CMP) {      // the interval is one text position: compare up to 64 bases
+        // (a window that runs past the end of the text has nv < 64: its last comparison ends the search there, as the reference's failing step does)
+        constexpr int chunk = 64;
+        Text64At at; at.word = 0; at.sh = (uint32_t)t.kk; at.nv = (int)t.ll; at.mirror = false; at.slow = false;
+        const Text64 x = d_text64_words(ix, at, t.s16.x, t.s16.y, t.s16.z, t.s16.w, t.s8.x);
+        const int nv = x.nv;
+        const uint32_t T0 = x.T0, T1 = x.T1, T2 = x.T2, T3 = x.T3;
         const int w = s.p >> 4;
         const uint32_t o = (uint32_t)((s.p & 15) << 1);
         const uint32_t b0 = rb(w), b1 = rb(w + 1), b2 = rb(w + 2), b3 = rb(w + 3), b4 = rb(w + 4);

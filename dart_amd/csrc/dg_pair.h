@@ -267,13 +267,13 @@ struct ReadWords {
         return v;
     }
     // the same count in the 2-bit domain: a packed batch's reads are A/C/G/T/N by contract (never a '-'), RefSequence is A/C/G/T (pac), so characters differ
-    // exactly where the codes differ or the read's base is masked -- no character is ever built.  Windows that are not wholly inside one strand of the
-    // text (d_ref8's per-character path: 0 outside) take the character form.
+    // exactly where the codes differ or the read's base is masked -- no character is ever built.  Windows that leave the text (d_ref8's per-character
+    // path: 0 outside) take the character form; so do, where pac holds the forward half only, windows that straddle the strand boundary.
     __host__ __device__ __forceinline__ int mismatches8(const DIndex &ix, int i, int e, int64_t g, bool &dash) const {
         const int64_t L = ix.l_pac;
         uint32_t g16;                              // eight genome codes, base k at bits 15-2k .. 14-2k
-        if (g >= 0 && g + 8 <= L) g16 = (__builtin_bswap32(*(const uint32_a1 *)(ix.pac + (g >> 2))) << ((g & 3) << 1)) >> 16;
-        else if (g >= L && g + 8 <= 2 * L) {
+        if (g >= 0 && g + 8 <= (d_pac_both(ix) ? 2 * L : L)) g16 = (__builtin_bswap32(*(const uint32_a1 *)(ix.pac + (g >> 2))) << ((g & 3) << 1)) >> 16;
+        else if (!d_pac_both(ix) && g >= L && g + 8 <= 2 * L) {                                                    // (forward-only form: the reverse half from its mirror)
             const int64_t lo = 2 * L - 1 - g - 7;                                                                  // fwd[lo .. lo+7], Ref[g+k] = 3 - fwd[lo+7-k]
             const uint32_t w = (__builtin_bswap32(*(const uint32_a1 *)(ix.pac + (lo >> 2))) << ((lo & 3) << 1)) >> 16;   // fwd[lo+q] at bits 15-2q .. 14-2q
             uint32_t r = ((w & 0x3333u) << 2) | ((w >> 2) & 0x3333u); r = ((r & 0x0F0Fu) << 4) | ((r >> 4) & 0x0F0Fu); r = ((r & 0x00FFu) << 8) | (r >> 8);   // 2-bit groups reversed
@@ -502,13 +502,12 @@ __host__ __device__ inline uint32_t d_unit_emit_read(bool first, const DRead &rd
 // ---------------------------------------------------------------------------------------------
 #include "dg_scan.h"
 
-// the pac word a gap comparison that starts behind seed k will read first (ReadWords::mismatches8 / d_ref8: the same address on either strand); 0 for windows
-// at the edges of the text, which take the per-character path
+// the pac word a gap comparison that starts behind seed k will read first (ReadWords::mismatches8 / d_ref8); 0 for windows that leave the text, which
+// take the per-character path
 __device__ __forceinline__ uint32_t d_pac_touch(const DIndex &ix, SKey k)
 {
     const int64_t L = ix.l_pac, g = sk_gpos(k) + sk_rlen(k);
-    if (g >= 0 && g + 8 <= L) return *(const uint32_a1 *)(ix.pac + (g >> 2));
-    if (g >= L && g + 8 <= 2 * L) return *(const uint32_a1 *)(ix.pac + ((2 * L - 1 - g - 7) >> 2));
+    if (g >= 0 && g + 8 <= 2 * L) return *(const uint32_a1 *)(ix.pac + (g >> 2));
     return 0u;
 }
 

@@ -325,16 +325,17 @@ __host__ __device__ inline bool d_check_seq_fragment(const DIndex &ix, int64_t L
 }
 
 // RefSequence[g0 .. g0 + n) as 2-bit codes (A C G T = 0 1 2 3), n <= 28, first base in the top bits -- when the bases, and the eight pac bytes the fetch
-// reads, lie inside one strand half; *ok says so.  One 8-byte fetch instead of n dependent d_refchar loads.
+// reads, lie inside the text (where pac holds the forward half only: inside one strand half); *ok says so.  One 8-byte fetch instead of n dependent
+// d_refchar loads.
 __host__ __device__ __forceinline__ uint64_t d_ref_codes(const DIndex &ix, int64_t g0, int n, bool *ok)
 {
     typedef uint64_t __attribute__((aligned(1))) uint64_a1;
     const int64_t L = ix.l_pac;
-    if (g0 >= 0 && g0 + 32 <= L) {
+    if (g0 >= 0 && (d_pac_both(ix) ? g0 + n <= 2 * L : g0 + 32 <= L)) {      // (both strands stored: the fetch may run into the zeroed pad behind the text)
         *ok = true;
         return __builtin_bswap64(*(const uint64_a1 *)(ix.pac + (g0 >> 2))) << ((g0 & 3) << 1);
     }
-    if (g0 >= L + 32 - n && g0 + n <= 2 * L) {            // RefSequence[g0 + j] = complement of forward base f0 - j
+    if (!d_pac_both(ix) && g0 >= L + 32 - n && g0 + n <= 2 * L) {            // RefSequence[g0 + j] = complement of forward base f0 - j
         const int64_t lo = 2 * L - 1 - g0 - (n - 1);      // the window's last base is forward base lo: 0 <= lo, lo + 32 <= L
         const uint64_t x = __builtin_bswap64(*(const uint64_a1 *)(ix.pac + (lo >> 2))) << ((lo & 3) << 1);       // forward base lo + k at bits 63-2k, 62-2k
         uint64_t y = __builtin_bitreverse64(x);                                                                  // ... at bits 2k, 2k+1 (swapped inside the pair)

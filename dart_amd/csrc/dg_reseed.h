@@ -14,8 +14,8 @@
 // Algorithm (order-equivalent to the reference's sort/join/sort, see dg_report.h d_reseed for the
 // serial form): the read-gap 8-mers sit sorted in LDS behind a 64 Kbit presence filter; every lane
 // extracts the 8-mer of its window position straight from the 2-bit pac (one unaligned 24-bit
-// fetch; reverse-strand windows are read from the forward pac and reverse-complemented in
-// registers), and hits set bit rPos of diagonal (g - rPos) in an LDS ring of diagonals.  A diagonal
+// fetch; pac stores both strands, so a reverse-strand window is read like a forward one),
+// and hits set bit rPos of diagonal (g - rPos) in an LDS ring of diagonals.  A diagonal
 // is complete once the window front has moved past it by the gap length; complete diagonals are
 // summarised 64 at a time (count, first, last rPos) and folded in increasing order into the
 // running (s, max_len) state of GenerateLongestSimplePairsFromFragmentPair -- bit-identical,
@@ -163,22 +163,12 @@ k_prep(const DParams pr, int paired, const uint32_t *__restrict__ slow_units, co
 __device__ __forceinline__ uint32_t d_window_kmer(const DIndex &ix, int64_t t)
 {
     const int64_t L = ix.l_pac;
-    if (t >= 0 && t + 7 < L) {
+    if (t >= 0 && t + 7 < 2 * L) {                       // (pac holds both strands)
         const uint8_t *p = ix.pac + (t >> 2);
         const uint32_t v = ((uint32_t)p[0] << 16) | ((uint32_t)p[1] << 8) | (uint32_t)p[2];
         return (v >> (8 - 2 * (int)(t & 3))) & 0xFFFFu;
     }
-    if (t >= L && t + 7 < 2 * L) {                      // reverse half: complement of the mirrored forward 8-mer
-        const int64_t u = 2 * L - 1 - t - 7;
-        const uint8_t *p = ix.pac + (u >> 2);
-        const uint32_t v = ((uint32_t)p[0] << 16) | ((uint32_t)p[1] << 8) | (uint32_t)p[2];
-        uint32_t x = (v >> (8 - 2 * (int)(u & 3))) & 0xFFFFu;
-        x = ((x & 0x3333u) << 2) | ((x >> 2) & 0x3333u);
-        x = ((x & 0x0F0Fu) << 4) | ((x >> 4) & 0x0F0Fu);
-        x = ((x << 8) | (x >> 8)) & 0xFFFFu;
-        return x ^ 0xFFFFu;
-    }
-    uint32_t wid = 0;                                    // straddles the strand boundary or the end
+    uint32_t wid = 0;                                    // leaves the text
     for (int i = 0; i < 8; i++) wid = (wid << 2) + d_nt4((unsigned char)d_refchar(ix, t + i));
     return wid;
 }
@@ -413,8 +403,8 @@ struct RsLds {
 
 // The window positions whose hits fall on the diagonals [d_lo, d_hi) are streamed once: positions [g_lo, g_hi], g_lo a multiple of RS_SUPER.  EMIT = false: the
 // whole window by this wave, folded as it goes (st); EMIT = true: one chunk, entries to em.  Per trip a wave looks at RS_CHUNK window positions, RS_PPL
-// consecutive ones per lane: the lane's 15 bases come from two dwords of the staged pac bytes (reverse half: bit-reversed and complemented once, not per
-// 8-mer), every 8-mer is one bit-field extract, the bitmap says which of them can be in the read gap at all (0.3 % are), and those go through the table --
+// consecutive ones per lane: the lane's 15 bases come from two dwords of the staged pac bytes (either strand as stored),
+// every 8-mer is one bit-field extract, the bitmap says which of them can be in the read gap at all (0.3 % are), and those go through the table --
 // one or two LDS reads -- to their entries of km[].  Returns the trips made.
 template <int WORDS, bool EMIT>
 __device__ __forceinline__ unsigned int d_rs_scan(const DIndex &ix, RsLds<WORDS> &S, const DJob &job, const int nk, const int span, const int g_lo, const int g_hi,
@@ -423,17 +413,13 @@ __device__ __forceinline__ unsigned int d_rs_scan(const DIndex &ix, RsLds<WORDS>
     const int64_t L = ix.l_pac;
     const int glen = job.glen;
     unsigned int n_trips = 0;
-    // window entirely inside one strand half -> k-mers come from coalesced pac dwords staged in LDS
-    const bool fwd = job.Lb >= 0 && job.Lb + glen <= L;
-    const bool rev = job.Lb >= L && job.Lb + glen <= 2 * L;
+    // window entirely inside the text -> k-mers come from coalesced pac dwords staged in LDS (pac holds both strands, so either half is read as stored)
+    const bool fwd = job.Lb >= 0 && job.Lb + glen <= 2 * L;
     auto super_base = [&](int gs) -> int64_t {                  // first pac byte (16-aligned) of the super-chunk that starts at window position gs
-        if (fwd) return (int64_t)(((job.Lb + gs) >> 2) & ~(int64_t)15);
-        int64_t ulo = 2 * L - 1 - (job.Lb + gs + RS_SUPER - 1) - 7;
-        if (ulo < 0) ulo = 0;
-        return (int64_t)((ulo >> 2) & ~(int64_t)15);
+        return (int64_t)(((job.Lb + gs) >> 2) & ~(int64_t)15);
     };
     uint4 pre = make_uint4(0, 0, 0, 0), pre_t = make_uint4(0, 0, 0, 0);
-    if (fwd || rev) {
+    if (fwd) {
         const uint4 *src = (const uint4 *)(ix.pac + super_base(g_lo));
         pre = src[lane]; if (lane < 4) pre_t = src[64 + lane];
     }
@@ -443,7 +429,7 @@ __device__ __forceinline__ unsigned int d_rs_scan(const DIndex &ix, RsLds<WORDS>
         d_rs_finalize<WORDS, EMIT>(S.ring, &S.dirty, st, em, pool, (int64_t)g0 - span, false, lane);
         const int p0 = g0 + RS_PPL * lane;
         uint32_t y = 0;                 // the lane's RS_PPL + 7 window bases (and one more), first base in the top bits
-        if (fwd || rev) {
+        if (fwd) {
             if (g0 % RS_SUPER == 0) {                              // (uniform) a new super-chunk: the fetch issued one super-chunk ago has arrived
                 B0 = super_base(g0);
                 RS_WAVE_SYNC();
@@ -454,22 +440,11 @@ __device__ __forceinline__ unsigned int d_rs_scan(const DIndex &ix, RsLds<WORDS>
                 }
                 RS_WAVE_SYNC();
             }
-            // first forward base this lane needs, relative to base 4*B0 of the staged bytes
-            int fb, o_rev = 0;
-            if (fwd) fb = (int)(job.Lb + p0 - 4 * B0);
-            else { const int64_t f64 = 2 * L - 1 - (job.Lb + p0 + RS_PPL - 1) - 7 - 4 * B0; fb = (int)f64; if (f64 < 0) { o_rev = f64 < -64 ? 64 : (int)-f64; fb = 0; } }
+            const int fb = (int)(job.Lb + p0 - 4 * B0);                           // first base this lane needs, relative to base 4*B0 of the staged bytes
             const int m = fb >> 4, o = fb & 15;                                   // dword index, base offset inside it
             const uint32_t w0 = __builtin_bswap32(S.pacbuf[m]), w1 = __builtin_bswap32(S.pacbuf[m + 1]);
-            uint32_t f = o ? ((w0 << (2 * o)) | (w1 >> (32 - 2 * o))) : w0;       // 16 forward bases from fb on
-            if (fwd) y = f;
-            else {
-                // window base k is the complement of forward base 14 - k: the 2-bit groups reversed, one group up, complemented
-                if (o_rev) f = o_rev > 15 ? 0u : f >> (2 * o_rev);   // window start clipped at forward base 0 (never a valid position)
-                uint32_t r = __builtin_bitreverse32(f);
-                r = ((r & 0x55555555u) << 1) | ((r >> 1) & 0x55555555u);
-                y = ~r << 2;
-            }
-        } else {                                                    // straddles the strand boundary or the end of the text
+            y = o ? ((w0 << (2 * o)) | (w1 >> (32 - 2 * o))) : w0;                // 16 bases from fb on
+        } else {                                                    // leaves the text
             for (int i = 0; i < RS_PPL + 7; i++)
                 if (p0 + i < glen) y |= (uint32_t)(d_nt4((unsigned char)d_refchar(ix, job.Lb + p0 + i)) & 3u) << (30 - 2 * i);
         }

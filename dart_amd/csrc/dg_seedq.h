@@ -383,19 +383,14 @@ __device__ __forceinline__ int sqf_trip(const SqEnv &e, const bool act, const ui
 #pragma unroll
         for (int i = 0; i < SQF_MULTI_MAX; i++) if (go && !have_pos && (uint32_t)i < nx) sa[i] = sap[i];
         SQF_TW(dl, 3);
-        const int64_t L = ix.l_pac;
         const uint32_t *pw = (const uint32_t *)ix.pac;
-        uint4 s16[SQF_MULTI_MAX]; uint2 s8[SQF_MULTI_MAX]; uint32_t sh[SQF_MULTI_MAX]; int kind[SQF_MULTI_MAX];      // kind: 0 none, 1 forward, 2 reverse, 3 slow
+        uint4 s16[SQF_MULTI_MAX]; uint2 s8[SQF_MULTI_MAX]; uint32_t sh[SQF_MULTI_MAX]; int tnv[SQF_MULTI_MAX];      // the rows' windows: five pac words each, on either strand as stored (d_text64_at)
 #pragma unroll
         for (int i = 0; i < SQF_MULTI_MAX; i++) {
-            s16[i] = make_uint4(0u, 0u, 0u, 0u); s8[i] = make_uint2(0u, 0u); sh[i] = 0u; kind[i] = 0;
+            s16[i] = make_uint4(0u, 0u, 0u, 0u); s8[i] = make_uint2(0u, 0u); sh[i] = 0u; tnv[i] = 0;
             if (go && (uint32_t)i < nx) {
-                const int64_t tt = (int64_t)(d_u64(sa[i].x, sa[i].y & 0xFFu) - 1ull) + (s.p - s.start);
-                int64_t f0 = -1;
-                if (tt >= 0 && tt + 64 <= L) { f0 = tt; kind[i] = 1; }
-                else if (tt >= L && tt + 64 <= 2 * L) { f0 = 2 * L - 1 - tt - 63; kind[i] = 2; }
-                else kind[i] = 3;
-                if (f0 >= 0) { s16[i] = *(const uint4_a4 *)(pw + (f0 >> 4)); s8[i] = *(const uint2_a4 *)(pw + (f0 >> 4) + 4); sh[i] = (uint32_t)((f0 & 15) << 1); }
+                const Text64At at = d_text64_at(ix, (int64_t)(d_u64(sa[i].x, sa[i].y & 0xFFu) - 1ull) + (s.p - s.start));
+                s16[i] = *(const uint4_a4 *)(pw + at.word); s8[i] = *(const uint2_a4 *)(pw + at.word + 4); sh[i] = at.sh; tnv[i] = at.nv;
             }
         }
         SQF_TW(dl, 5);
@@ -406,25 +401,17 @@ __device__ __forceinline__ int sqf_trip(const SqEnv &e, const bool act, const ui
             const uint32_t m0 = rm(w), m1 = rm(w + 1), m2 = rm(w + 2), m3 = rm(w + 3), m4 = rm(w + 4);
             const uint32_t R0 = __funnelshift_l(b1, b0, o), R1 = __funnelshift_l(b2, b1, o), R2 = __funnelshift_l(b3, b2, o), R3 = __funnelshift_l(b4, b3, o);
             const uint32_t N0 = __funnelshift_l(m1, m0, o), N1 = __funnelshift_l(m2, m1, o), N2 = __funnelshift_l(m3, m2, o), N3 = __funnelshift_l(m4, m3, o);
-            bool slow = false;
-#pragma unroll
-            for (int i = 0; i < SQF_MULTI_MAX; i++) slow = slow || kind[i] == 3;
-            const int chunk = slow ? 16 : 64;                                          // a row near a strand boundary or the end of the text: everybody compares 16 symbols
+            constexpr int chunk = 64;                                                  // (a row whose window runs past the end of the text has nv < 64 and ends there)
             const int in_read = len - s.p < chunk ? len - s.p : chunk;                 // bases left in the read
             int jj[SQF_MULTI_MAX];
 #pragma unroll
             for (int i = 0; i < SQF_MULTI_MAX; i++) {
                 jj[i] = -1;
                 if ((uint32_t)i < nx) {
-                    int nv = 64;
-                    uint32_t T0, T1 = 0, T2 = 0, T3 = 0;
-                    if (kind[i] != 3) {
-                        const uint32_t d0 = __builtin_bswap32(s16[i].x), d1 = __builtin_bswap32(s16[i].y), d2 = __builtin_bswap32(s16[i].z),
-                                       d3 = __builtin_bswap32(s16[i].w), d4 = __builtin_bswap32(s8[i].x);
-                        const uint32_t t0 = __funnelshift_l(d1, d0, sh[i]), t1 = __funnelshift_l(d2, d1, sh[i]), t2 = __funnelshift_l(d3, d2, sh[i]), t3 = __funnelshift_l(d4, d3, sh[i]);
-                        if (kind[i] == 2) { T0 = ~d_rev2(t3); T1 = ~d_rev2(t2); T2 = ~d_rev2(t1); T3 = ~d_rev2(t0); }   // T[t+j] = 3 - fwd[2L-1-t-j]
-                        else { T0 = t0; T1 = t1; T2 = t2; T3 = t3; }
-                    } else T0 = d_text16_slow(ix, (int64_t)(d_u64(sa[i].x, sa[i].y & 0xFFu) - 1ull) + (s.p - s.start), nv);
+                    Text64At at; at.word = 0; at.sh = sh[i]; at.nv = tnv[i]; at.mirror = false; at.slow = false;
+                    const Text64 x = d_text64_words(ix, at, s16[i].x, s16[i].y, s16[i].z, s16[i].w, s8[i].x);
+                    const int nv = x.nv;
+                    const uint32_t T0 = x.T0, T1 = x.T1, T2 = x.T2, T3 = x.T3;
                     const int lim = in_read < nv ? in_read : nv;
                     auto tail = [&](int k) -> uint32_t { const int rem = lim - 16 * k; return rem >= 16 ? 0u : (rem <= 0 ? 0xFFFFFFFFu : 0xFFFFFFFFu >> (2 * rem)); };
                     const uint32_t e0 = (R0 ^ T0) | N0 | tail(0), e1 = (R1 ^ T1) | N1 | tail(1), e2 = (R2 ^ T2) | N2 | tail(2), e3 = (R3 ^ T3) | N3 | tail(3);

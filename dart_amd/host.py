@@ -305,6 +305,7 @@ def _load_lib():
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
     lib.dg_probe_nw_mode.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
+    lib.dg_probe_refseq.argtypes = [vp, C.c_int64, C.c_int64, vp]
     return lib
 
 
@@ -915,6 +916,12 @@ class DartGPU:
         out = np.zeros(max(len(f), 1), np.uint8)
         self._chk(self.lib.dg_probe_huff_lengths(self.ctx, f.ctypes.data, len(f), int(limit), out.ctypes.data), "dg_probe_huff_lengths")
         return [int(x) for x in out[:len(f)]]
+
+    def probe_refseq(self, g0: int, n: int) -> bytes:
+        """RefSequence[g0, g0 + n) as the kernels read it from the device's text (dg_probe_refseq); 0 bytes outside [0, 2L)"""
+        out = np.zeros(max(int(n), 1), np.uint8)
+        self._chk(self.lib.dg_probe_refseq(self.ctx, int(g0), int(n), out.ctypes.data), "dg_probe_refseq")
+        return out[:int(n)].tobytes()
 
     def probe_nw(self, pairs, mode: int = 0):
         """nw_alignment of (a, b) byte pairs through form `mode` of the kernels (dg_probe_nw_mode)."""

@@ -469,6 +469,9 @@ int dg_probe_nw(dg_ctx *, int n, const uint32_t *a_off, const uint32_t *b_off, c
  * kernels do (RefSequence, bwt_index.cpp:193-212): b must be ACGT, else DG_ERR_ARG.                                  */
 int dg_probe_nw_mode(dg_ctx *, int mode, int n, const uint32_t *a_off, const uint32_t *b_off, const char *a, const char *b,
                      uint32_t *out_off, uint32_t *out_len, char *out_a, char *out_b, size_t cap);
+/* RefSequence[g0, g0 + n) (bwt_index.cpp:193-212) as the kernels read it from the device's 2-bit text, which holds the forward strand and -- built once at
+ * start-up -- its reverse complement: out[i] = 'A' 'C' 'G' 'T', or 0 where g0 + i is outside [0, 2 l_pac).  n up to 2^30. */
+int dg_probe_refseq(dg_ctx *, int64_t g0, int64_t n, char *out);
 /* Test hook: the code-length builder of the dynamic BGZF coder (DG_BAM_DYNAMIC) on a histogram of the caller's, in a one-workgroup kernel: len_out[i] =
  * the length of symbol i's Huffman code, none above `limit` (1..15), 0 exactly where freq[i] is 0; one used symbol gets length 1.  The same integers as the
  * host's build of dg_bgzf_dyn.h gives.  n_sym 1..320, every freq below 2^23, no more used symbols than 2^limit, else DG_ERR_ARG.  A strip's own
