@@ -17,6 +17,7 @@
 #include "dg_inflate.h"
 #include "dg_sjtab.h"
 #include "dg_bamsort.h"
+#include "dg_bamidx.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -199,6 +200,15 @@ struct dg_ctx {
     hipEvent_t ev_bs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // [0..4]: the phases of dg_bam_sort_finish; [5]: the source stream's place for dg_bam_sort_merge
     bool bam_rec_valid = false, bam_rec_stored = false; size_t bam_rec_bytes = 0, bam_rec_records = 0;      // bam_rec and the formatter's offsets hold the current batch's records / they are in the store
     bool bs_fin_valid = false; size_t bs_fin_bytes = 0, bs_fin_records = 0; float bs_ms[4] = {0.f, 0.f, 0.f, 0.f}, bs_acc_ms = 0.f; int bs_passes = 0;
+    // the BAM index of the sorted array (dg_bamidx.h): the compressed size of every block as the last dg_bam_sort_compress left it (bi_covered: which blocks have one),
+    // the per-record, per-chunk and per-reference arrays of dg_bam_index_finish, and the index itself
+    DBuf<uint32_t> bi_sizes, bi_sizes_in, bi_span, bi_tile_cnt, bi_chead, bi_mhead, bi_mbin, bi_binq, bi_ref_q, bi_ref_b, bi_hist, bi_sums;
+    DBuf<uint64_t> bi_coff, bi_key, bi_voff, bi_ck[2], bi_excl, bi_ctile, bi_ref_at, bi_lin_at; DBuf<int64_t> bi_cv[2];
+    DBuf<unsigned long long> bi_ref, bi_lin; DBuf<unsigned char> bi_flag, bi_out;
+    std::vector<unsigned char> bi_covered; std::vector<unsigned long long> h_bi_ref; std::vector<uint64_t> h_bi_lin_at;
+    unsigned long long *d_bi_stat = nullptr, *h_bi_stat = nullptr;        // BI_ST_* words: device / page-locked copy
+    hipEvent_t ev_bi[4] = {nullptr, nullptr, nullptr, nullptr};          // the kernels before and behind the mid-way wait
+    bool bi_valid = false; size_t bi_bytes = 0; int bs_fin_which = 0;     // bs_fin_which: bs_k[bs_fin_which ^ 1] holds the sorted records' places inside their tiles
     size_t env_bamsort_first_cap = 0;  // DG_BAMSORT_FIRST_CAP: test hook, the first size of the store in bytes (forces growth)
     size_t env_bam_first_cap = 0;      // DG_BAM_FIRST_CAP: test hook, the first size of the record buffer in bytes
     size_t env_sam_first_cap = 0;      // DG_SAM_TEXT_FIRST_CAP: test hook, the first size of the text buffer in bytes (forces the "text outgrew the guess" path)
@@ -668,6 +678,12 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->bs_off) (void)hipFree(c->bs_off);
     c->bs_cnt_off.release(); c->bs_tile_cnt.release(); c->bs_hist.release(); c->bs_sums.release(); c->bs_k[0].release(); c->bs_k[1].release(); c->bs_v[0].release(); c->bs_v[1].release();
     c->bs_tile.release(); c->bs_sorted.release();
+    for (DBuf<uint32_t> *b : {&c->bi_sizes, &c->bi_sizes_in, &c->bi_span, &c->bi_tile_cnt, &c->bi_chead, &c->bi_mhead, &c->bi_mbin, &c->bi_binq, &c->bi_ref_q, &c->bi_ref_b, &c->bi_hist, &c->bi_sums}) b->release();
+    for (DBuf<uint64_t> *b : {&c->bi_coff, &c->bi_key, &c->bi_voff, &c->bi_ck[0], &c->bi_ck[1], &c->bi_excl, &c->bi_ctile, &c->bi_ref_at, &c->bi_lin_at}) b->release();
+    c->bi_cv[0].release(); c->bi_cv[1].release(); c->bi_ref.release(); c->bi_lin.release(); c->bi_flag.release(); c->bi_out.release();
+    if (c->d_bi_stat) (void)hipFree(c->d_bi_stat);
+    if (c->h_bi_stat) (void)hipHostFree(c->h_bi_stat);
+    for (hipEvent_t e : c->ev_bi) if (e) (void)hipEventDestroy(e);
     if (c->d_bs_stat) (void)hipFree(c->d_bs_stat);
     if (c->h_bs_stat) (void)hipHostFree(c->h_bs_stat);
     for (hipEvent_t e : c->ev_bs) if (e) (void)hipEventDestroy(e);
@@ -3010,6 +3026,7 @@ extern "C" int dg_bam_sort_finish(dg_ctx *c, size_t *n_records, size_t *n_raw, f
     if (n_raw) *n_raw = 0;
     if (device_ms) *device_ms = 0.f;
     c->bs_fin_valid = false; c->bs_fin_bytes = 0; c->bs_fin_records = 0; c->bs_passes = 0;
+    c->bi_valid = false; c->bi_covered.clear();             // (no block of the new array has been compressed)
     for (float &m : c->bs_ms) m = 0.f;
     { const int rc = bs_ready(c); if (rc) return rc; }
     if (!c->bs_n) { c->bs_fin_valid = true; return DG_OK; }
@@ -3054,7 +3071,7 @@ extern "C" int dg_bam_sort_finish(dg_ctx *c, size_t *n_records, size_t *n_raw, f
     if ((size_t)c->h_bs_stat[0] != bytes) { snprintf(c->err, 512, "%s: the sorted records' lengths add up to %zu bytes, the store holds %zu", fn, (size_t)c->h_bs_stat[0], bytes); return DG_ERR_INTERNAL; }
     float total = 0.f;
     for (int k = 0; k < 4; k++) { (void)hipEventElapsedTime(&c->bs_ms[k], c->ev_bs[k], c->ev_bs[k + 1]); total += c->bs_ms[k]; }
-    c->bs_fin_valid = true; c->bs_fin_bytes = bytes; c->bs_fin_records = n;
+    c->bs_fin_valid = true; c->bs_fin_bytes = bytes; c->bs_fin_records = n; c->bs_fin_which = which;
     if (n_records) *n_records = n;
     if (n_raw) *n_raw = bytes;
     if (device_ms) *device_ms = total;
@@ -3101,11 +3118,181 @@ extern "C" int dg_bam_sort_compress(dg_ctx *c, size_t raw_off, size_t raw_len, u
         const int rc = bgzf_device(c, in, raw_len, flags == DG_BGZF_DYNAMIC, &out_bytes, &ms);
         if (rc) return rc;
         c->bam_ptr = c->bgzf_out.p;
+        // the blocks' compressed sizes, kept for dg_bam_index_finish: device to device, at the piece's block offset
+        const size_t all_blocks = (total + BGZF_BLOCK - 1) / BGZF_BLOCK, b0 = raw_off / BGZF_BLOCK, nb = (raw_len + BGZF_BLOCK - 1) / BGZF_BLOCK;
+        // (no memory for that array: the compression stands, the blocks stay uncovered, and dg_bam_index_finish without block_sizes says which block it misses)
+        if (c->bi_sizes.cap < all_blocks) { c->bi_covered.clear(); if (c->bi_sizes.ensure(all_blocks) != hipSuccess) (void)hipGetLastError(); }
+        if (c->bi_sizes.cap >= all_blocks) {
+            if (c->bi_covered.size() != all_blocks) c->bi_covered.assign(all_blocks, 0);
+            HIPCHK(hipMemcpyAsync(c->bi_sizes.p + b0, c->bgzf_size.p, nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+            std::fill(c->bi_covered.begin() + (long)b0, c->bi_covered.begin() + (long)(b0 + nb), (unsigned char)1);
+        }
     }
     c->bam_bytes = out_bytes; c->bam_valid = true;
     c->bam_ms[0] = 0.f; c->bam_ms[1] = ms;
     if (n_bytes) *n_bytes = out_bytes;
     if (device_ms) *device_ms = ms;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the BAM index of the sorted array (dg_bamidx.h): built in HBM from the sorted records, their places and the blocks' compressed sizes
+// ------------------------------------------------------------------------------------------
+static int bi_state(dg_ctx *c)
+{
+    if (c->d_bi_stat) return DG_OK;
+    HIPCHK(hipMalloc((void **)&c->d_bi_stat, BI_ST_WORDS * 8));
+    HIPCHK(hipHostMalloc((void **)&c->h_bi_stat, BI_ST_WORDS * 8, hipHostMallocDefault));
+    memset(c->h_bi_stat, 0, BI_ST_WORDS * 8);
+    for (hipEvent_t &e : c->ev_bi) HIPCHK(hipEventCreate(&e));
+    return DG_OK;
+}
+
+extern "C" int dg_bam_index_granules(int out[2])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = BI_THREADS; out[1] = RS_TILE;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_index_finish(dg_ctx *c, uint64_t first_block_offset, const uint32_t *block_sizes, size_t n_blocks_given, size_t *n_bytes, uint64_t stats[6], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_index_finish";
+    if (n_bytes) *n_bytes = 0;
+    if (device_ms) *device_ms = 0.f;
+    if (stats) for (int k = 0; k < 6; k++) stats[k] = 0;
+    c->bi_valid = false; c->bi_bytes = 0;
+    if (!c->bs_fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
+    { const int rc = bs_ready(c); if (rc) return rc; }
+    { const int rc = bi_state(c); if (rc) return rc; }
+    const size_t n = c->bs_fin_records, n_raw = c->bs_fin_bytes, n_blocks = (n_raw + BGZF_BLOCK - 1) / BGZF_BLOCK;
+    const int n_chr = c->ix.n_chr;
+    if (n_chr < 1 || n_blocks > 0xFFFFFFF0ull) { snprintf(c->err, 512, "%s: %d chromosomes, %zu blocks", fn, n_chr, n_blocks); return DG_ERR_ARG; }
+    if (first_block_offset >> 48) { snprintf(c->err, 512, "%s: the first block's file offset %llu does not fit a virtual offset's 48 bits", fn, (unsigned long long)first_block_offset); return DG_ERR_RANGE; }
+    // the blocks' sizes: the caller's, or what the last dg_bam_sort_compress of every block left
+    const uint32_t *sizes = nullptr;
+    if (block_sizes) {
+        if (n_blocks_given != n_blocks) { snprintf(c->err, 512, "%s: n_blocks is %zu, the sorted array of %zu bytes has %zu blocks of %u bytes", fn, n_blocks_given, n_raw, n_blocks, BGZF_BLOCK); return DG_ERR_ARG; }
+        for (size_t k = 0; k < n_blocks; k++) if (!block_sizes[k]) { snprintf(c->err, 512, "%s: block %zu has the compressed size 0", fn, k); return DG_ERR_ARG; }
+        BS_ENSURE(c->bi_sizes_in, n_blocks + 1, "the blocks' compressed sizes");
+        if (n_blocks) HIPCHK(hipMemcpyAsync(c->bi_sizes_in.p, block_sizes, n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        sizes = c->bi_sizes_in.p;
+    } else {
+        for (size_t k = 0; k < n_blocks; k++) if (k >= c->bi_covered.size() || !c->bi_covered[k]) {
+            snprintf(c->err, 512, "%s: block %zu of the sorted array has not been compressed since dg_bam_sort_finish (dg_bam_sort_compress without DG_BAM_RAW), and no block_sizes are given", fn, k);
+            return DG_ERR_ARG;
+        }
+        sizes = c->bi_sizes.p;
+    }
+    const uint32_t tiles = (uint32_t)((n + BI_THREADS - 1) / BI_THREADS);
+    BS_ENSURE(c->bi_coff, n_blocks + 1, "the blocks' file offsets");
+    BS_ENSURE(c->bi_key, n + 1, "the records' bins"); BS_ENSURE(c->bi_voff, n + 1, "the records' virtual offsets"); BS_ENSURE(c->bi_span, n + 1, "the records' windows");
+    BS_ENSURE(c->bi_tile_cnt, (size_t)tiles + 1, "the per-workgroup chunk counts");
+    BS_ENSURE(c->bi_ref, (size_t)BI_REF_PLANES * n_chr, "the per-reference values");
+    BS_ENSURE(c->bi_ref_q, (size_t)n_chr + 1, "the per-reference chunk counts"); BS_ENSURE(c->bi_ref_b, (size_t)n_chr + 1, "the per-reference bin counts");
+    BS_ENSURE(c->bi_ref_at, (size_t)n_chr + 1, "the per-reference byte offsets"); BS_ENSURE(c->bi_lin_at, (size_t)n_chr + 1, "the per-reference window offsets");
+    c->h_bi_ref.resize((size_t)BI_REF_PLANES * n_chr); c->h_bi_lin_at.resize((size_t)n_chr + 1);
+    const uint64_t *dst_off = c->bs_k[c->bs_fin_which ^ 1].p;
+    HIPCHK(hipMemsetAsync(c->d_bi_stat, 0, BI_ST_WORDS * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_bi_stat + BI_ST_BAD, 0xff, 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->bi_ref.p, 0, (size_t)BI_REF_PLANES * n_chr * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->bi_ref.p + 3 * (size_t)n_chr, 0xff, (size_t)n_chr * 8, c->stream));
+    HIPCHK(hipEventRecord(c->ev_bi[0], c->stream));
+    k_bi_coff<<<1, BI_THREADS, 0, c->stream>>>(sizes, (uint32_t)n_blocks, (unsigned long long)first_block_offset, c->bi_coff.p, c->d_bi_stat);
+    if (n) {
+        k_bi_rec<<<tiles, BI_THREADS, 0, c->stream>>>(c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, c->bi_coff.p, (uint32_t)n_blocks, n_chr,
+                                                      c->bi_key.p, c->bi_voff.p, c->bi_span.p, c->bi_ref.p, c->d_bi_stat);
+        k_bi_heads<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi_key.p, (uint32_t)n, c->bi_tile_cnt.p);
+        k_scan_top<<<1, 256, 0, c->stream>>>(c->bi_tile_cnt.p, tiles, (uint32_t *)(c->d_bi_stat + BI_ST_CHUNKS), nullptr, 0, nullptr, 0);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_bi[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bi_stat, c->d_bi_stat, BI_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bi_ref.data(), c->bi_ref.p, (size_t)BI_REF_PLANES * n_chr * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the first wait: the per-reference sizes (and the chunk count, and what was out of range)
+    if (c->h_bi_stat[BI_ST_COFF_END] >> 48) { snprintf(c->err, 512, "%s: the file offset %llu behind the last block does not fit a virtual offset's 48 bits", fn, c->h_bi_stat[BI_ST_COFF_END]); return DG_ERR_RANGE; }
+    if (c->h_bi_stat[BI_ST_BAD] != BI_NONE) {
+        snprintf(c->err, 512, "%s: record %llu of the sorted array ends behind position 2^29: a BAI cannot hold it, such a reference needs a CSI index; no index was built", fn, c->h_bi_stat[BI_ST_BAD]);
+        return DG_ERR_RANGE;
+    }
+    const size_t n_chunks = (size_t)(uint32_t)c->h_bi_stat[BI_ST_CHUNKS];
+    size_t n_placed = 0, n_lin = 0;
+    for (int t = 0; t < n_chr; t++) {
+        c->h_bi_lin_at[(size_t)t] = n_lin;
+        n_lin += (size_t)c->h_bi_ref[(size_t)t];
+        n_placed += (size_t)(c->h_bi_ref[(size_t)n_chr + t] + c->h_bi_ref[2 * (size_t)n_chr + t]);
+    }
+    c->h_bi_lin_at[(size_t)n_chr] = n_lin;
+    if (n_placed > n || n_chunks > n_placed) { snprintf(c->err, 512, "%s: %zu placed records and %zu chunks of %zu records", fn, n_placed, n_chunks, n); return DG_ERR_INTERNAL; }
+    const size_t cap = (size_t)bi_bytes_bound((uint64_t)n_chr, n_chunks, n_lin);
+    const uint32_t ctiles = (uint32_t)((n_chunks + BI_THREADS - 1) / BI_THREADS);
+    BS_ENSURE(c->bi_lin, n_lin + 1, "the linear index"); BS_ENSURE(c->bi_out, cap, "the index");
+    for (int k = 0; k < 2; k++) { BS_ENSURE(c->bi_ck[k], n_chunks + 1, "the chunks' keys"); BS_ENSURE(c->bi_cv[k], n_chunks + 1, "the chunks' numbers"); }
+    BS_ENSURE(c->bi_chead, n_chunks + 1, "the chunks' first records"); BS_ENSURE(c->bi_mhead, n_chunks + 1, "the merged chunks"); BS_ENSURE(c->bi_mbin, n_chunks + 1, "the merged chunks' bins");
+    BS_ENSURE(c->bi_binq, n_chunks + 1, "the bins' first chunks"); BS_ENSURE(c->bi_flag, n_chunks + 1, "the chunks' flags"); BS_ENSURE(c->bi_excl, n_chunks + 1, "the chunks' places");
+    BS_ENSURE(c->bi_ctile, (size_t)ctiles + 1, "the per-workgroup sums");
+    BS_ENSURE(c->bi_hist, rs_hist_words((uint32_t)n_chunks), "the sorter's histograms"); BS_ENSURE(c->bi_sums, rs_sums_words((uint32_t)n_chunks), "the sorter's sums");
+    HIPCHK(hipMemcpyAsync(c->bi_lin_at.p, c->h_bi_lin_at.data(), ((size_t)n_chr + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev_bi[2], c->stream));
+    HIPCHK(hipMemsetAsync(c->bi_out.p, 0, cap, c->stream));
+    if (n_lin) {
+        HIPCHK(hipMemsetAsync(c->bi_lin.p, 0xff, n_lin * 8, c->stream));
+        k_bi_lin<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi_key.p, c->bi_span.p, c->bi_voff.p, (uint32_t)n, n_chr, c->bi_lin_at.p, c->bi_lin.p);
+    }
+    int which = 0;
+    if (n_chunks) {
+        k_bi_chunks<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi_key.p, (uint32_t)n, c->bi_tile_cnt.p, (uint32_t)n_chunks, (uint32_t)n_placed, c->bi_ck[0].p, c->bi_cv[0].p, c->bi_chead.p);
+        uint64_t *const keys[2] = {c->bi_ck[0].p, c->bi_ck[1].p}; int64_t *const vals[2] = {c->bi_cv[0].p, c->bi_cv[1].p};
+        { const int rc = rs_sort_passes(c, keys, vals, c->bi_hist.p, c->bi_sums.p, (uint32_t)n_chunks, bi_key_bits(n_chr), which); if (rc) return rc; }
+        k_bi_merge_scan<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi_ck[which].p, c->bi_cv[which].p, c->bi_chead.p, c->bi_voff.p, (uint32_t)n_chunks, c->bi_flag.p, c->bi_excl.p, c->bi_ctile.p);
+        k_sam_top<<<1, 256, 0, c->stream>>>(c->bi_ctile.p, ctiles, c->d_bi_stat + BI_ST_MERGED);
+        k_bi_merge_emit<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi_ck[which].p, c->bi_flag.p, c->bi_excl.p, c->bi_ctile.p, (uint32_t)n_chunks, n_chr, c->d_bi_stat, c->bi_mhead.p, c->bi_mbin.p,
+                                                               c->bi_binq.p, c->bi_ref_q.p, c->bi_ref_b.p);
+    } else {
+        HIPCHK(hipMemsetAsync(c->bi_ref_q.p, 0, ((size_t)n_chr + 1) * 4, c->stream));
+        HIPCHK(hipMemsetAsync(c->bi_ref_b.p, 0, ((size_t)n_chr + 1) * 4, c->stream));
+    }
+    k_bi_refs<<<1, BI_THREADS, 0, c->stream>>>(n_chr, c->bi_ref.p, c->bi_ref_q.p, c->bi_ref_b.p, (unsigned long long)(n - n_placed), c->bi_ref_at.p, c->bi_out.p, (unsigned long long)cap, c->d_bi_stat);
+    if (n_chunks)
+        k_bi_write_chunks<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi_ck[which].p, c->bi_cv[which].p, c->bi_chead.p, c->bi_voff.p, (uint32_t)n_chunks, c->d_bi_stat, c->bi_mhead.p, c->bi_mbin.p,
+                                                                 c->bi_binq.p, c->bi_ref_q.p, c->bi_ref_b.p, c->bi_ref_at.p, n_chr, c->bi_out.p, (unsigned long long)cap);
+    k_bi_write_refs<<<(unsigned)n_chr, BI_THREADS, 0, c->stream>>>(n_chr, c->bi_ref.p, c->bi_ref_q.p, c->bi_ref_b.p, c->bi_ref_at.p, c->bi_voff.p, (uint32_t)n, c->bi_lin_at.p, c->bi_lin.p,
+                                                                   c->bi_out.p, (unsigned long long)cap);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_bi[3], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_bi_stat, c->d_bi_stat, BI_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the second wait: the index's size
+    const size_t total = (size_t)c->h_bi_stat[BI_ST_BYTES], n_merged = (size_t)(uint32_t)c->h_bi_stat[BI_ST_MERGED], n_bins = (size_t)(c->h_bi_stat[BI_ST_MERGED] >> 32);
+    if (total > cap || total < 16 + 8 * (size_t)n_chr || n_merged > n_chunks || n_bins > n_merged) {
+        snprintf(c->err, 512, "%s: an index of %zu bytes (%zu chunks, %zu bins) where at most %zu bytes and %zu chunks can be", fn, total, n_merged, n_bins, cap, n_chunks);
+        return DG_ERR_INTERNAL;
+    }
+    float a = 0.f, b = 0.f;
+    (void)hipEventElapsedTime(&a, c->ev_bi[0], c->ev_bi[1]); (void)hipEventElapsedTime(&b, c->ev_bi[2], c->ev_bi[3]);
+    c->bi_valid = true; c->bi_bytes = total;
+    if (n_bytes) *n_bytes = total;
+    if (device_ms) *device_ms = a + b;
+    if (stats) { stats[0] = n_placed; stats[1] = n - n_placed; stats[2] = n_bins; stats[3] = n_chunks; stats[4] = n_merged; stats[5] = n_lin; }
+    return DG_OK;
+}
+
+extern "C" int dg_bam_index_download(dg_ctx *c, void *out, size_t cap)
+{
+    if (!c || (!out && cap)) return DG_ERR_ARG;
+    if (!c->bi_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_index_download: no index (dg_bam_index_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if (cap < c->bi_bytes) { snprintf(c->err, 512, "dg_bam_index_download: the index has %zu bytes, the buffer %zu", c->bi_bytes, cap); return DG_ERR_CAPACITY; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(out, c->bi_out.p, c->bi_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_bam_index_device(dg_ctx *c, void **ptr, size_t *n_bytes)
+{
+    if (!c || !ptr || !n_bytes) return DG_ERR_ARG;
+    if (!c->bi_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_index_device: no index (dg_bam_index_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    *ptr = c->bi_out.p; *n_bytes = c->bi_bytes;
     return DG_OK;
 }
 

@@ -45,6 +45,7 @@ public:
         }
         append(h.data(), h.size());
         flush_all();                                           // (bam_hdr_write ends with bgzf_flush: the header never shares a block with records)
+        header_bytes_ = written_;                              // (counted, never sought: the output may be a pipe)
         return !bad_;
     }
     // whole SAM lines ("...\n"), header lines ('@') skipped
@@ -108,9 +109,12 @@ public:
     {
         flush_all();
         if (n && fwrite(p, 1, n, f_) != n) bad_ = true;
+        written_ += n;
         n_records_ += records; n_refused_ += refused;
         return !bad_;
     }
+    // the file offset behind the header's blocks: where the first block of records begins (what a BAM index counts its virtual offsets from)
+    uint64_t first_block_offset() const { return header_bytes_; }
     long long records() const { return n_records_; }
     long long refused() const { return n_refused_; }
 
@@ -225,6 +229,7 @@ private:
     int threads_ = 1;
     bool bad_ = false;
     long long n_records_ = 0, n_refused_ = 0;
+    uint64_t header_bytes_ = 0, written_ = 0;                  // bytes of blocks handed to the file so far; what the header's blocks took
     std::unordered_map<std::string, int32_t> tid_;
     std::vector<uint8_t> pending_;
     mutable std::vector<uint8_t> rec_;
@@ -275,7 +280,7 @@ private:
         auto work = [&](int t) { for (size_t b = (size_t)t; b < nb; b += (size_t)T) { const size_t o = b * BLOCK, l = std::min(BLOCK, n_bytes - o); ok[b] = compress_block(pending_.data() + o, l, outb[b]); } };
         if (T <= 1) work(0);
         else { std::vector<std::thread> th; for (int t = 0; t < T; t++) th.emplace_back(work, t); for (auto &x : th) x.join(); }
-        for (size_t b = 0; b < nb; b++) { if (!ok[b] || fwrite(outb[b].data(), 1, outb[b].size(), f_) != outb[b].size()) bad_ = true; }
+        for (size_t b = 0; b < nb; b++) { if (!ok[b] || fwrite(outb[b].data(), 1, outb[b].size(), f_) != outb[b].size()) bad_ = true; written_ += outb[b].size(); }
         pending_.erase(pending_.begin(), pending_.begin() + (long)n_bytes);
     }
     void compress_full_blocks() { const size_t full = pending_.size() / BLOCK * BLOCK; if (full) compress_range(full); }

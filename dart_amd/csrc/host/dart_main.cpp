@@ -58,6 +58,7 @@ static void usage(const char *prog, const Options &o)   // ShowProgramUsage, mai
     fprintf(stdout, "         -max_dup INT  maximal number of repetitive fragments (between 100-10000) [%d]\n", o.p.max_dup);
     fprintf(stdout, "         -o            alignment filename in SAM format\n");
     fprintf(stdout, "         -bo           alignment filename in BAM format\n");
+    fprintf(stdout, "                       (DART_DEVICE_BAM=1 DART_SORT_BAM=1: coordinate-sorted on the device; DART_BAM_INDEX=1 beside them: its .bai too)\n");
     fprintf(stdout, "         -j            splice junction output filename [junctions.tab]\n");
     fprintf(stdout, "         -m            output multiple alignments [false]\n");
     fprintf(stdout, "         -all_sj       detect all splice junction regardless of mapq score [false]\n");
@@ -564,6 +565,14 @@ int main(int argc, char *argv[])
         fprintf(stderr, "Error! DART_SORT_BAM=1 needs -bo and DART_DEVICE_BAM=1: %s missing\n", !o.bam ? (getenv("DART_DEVICE_BAM") && atoi(getenv("DART_DEVICE_BAM")) ? "-bo is" : "both are") : "DART_DEVICE_BAM=1 is");
         return 1;
     }
+    // DART_BAM_INDEX=1 beside DART_SORT_BAM=1: the sorted file's index <out>.bai, built on the device from the sorted records and the blocks' sizes
+    // (dg_bam_index_finish) in place of the `samtools index` behind the sort.  Without the sort there is nothing to index: no output is begun.
+    const bool bam_index = getenv("DART_BAM_INDEX") && atoi(getenv("DART_BAM_INDEX")) != 0;
+    if (bam_index && !sort_bam) {
+        fprintf(stderr, "Error! DART_BAM_INDEX=1 needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n");
+        return 1;
+    }
+    const std::string bai_path = bam_index ? std::string(o.out) + ".bai" : std::string();
     const char *bam_dev_note = sort_bam ? (bgzf_dynamic ? ", bam=device+sorted+dyn" : ", bam=device+sorted") : bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "";
     FastqIndex pre;                         // the first library's read files are mapped and indexed while the HIP runtime starts, the genome index loads and dg_init_files runs
     bool fast_first = false;
@@ -744,7 +753,7 @@ int main(int argc, char *argv[])
     auto out_end = [&](uint64_t off) { if (sam) fseeko(sam, (off_t)off, SEEK_SET); };
     // a library that failed: under DART_SORT_BAM no partial file is left, and a store that could not grow says which switch asked for the memory
     auto lib_failed = [&](int frc, const std::string &ferr) -> int {
-        if (sort_bam) { (void)bam.close(); remove(o.out); }
+        if (sort_bam) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); }
         if (sort_bam && frc == DG_ERR_CAPACITY) fprintf(stderr, "\nError! DART_SORT_BAM=1: the records do not fit in device memory: %s\n", ferr.c_str());
         else fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str());
         return 1;
@@ -793,7 +802,7 @@ int main(int argc, char *argv[])
             }
         }
         const int orc = open_lib(lib);              // (library 0 was opened before the index went to the GPU: its files are being inflated and parsed since)
-        if (orc == 2) { if (sort_bam) { (void)bam.close(); remove(o.out); } return 1; }      // (under DART_SORT_BAM no failed run leaves a file)
+        if (orc == 2) { if (sort_bam) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); } return 1; }      // (under DART_SORT_BAM no failed run leaves a file)
         if (orc == 1) continue;
         LibIO &L = *libs[lib];
         Source &s1 = L.s1, &s2 = L.s2; Prefetch &pf1 = L.pf1, &pf2 = L.pf2;
@@ -801,7 +810,7 @@ int main(int argc, char *argv[])
         const std::string &fn = o.f1[lib];
         if (sort_bam && !fast_host) {
             fprintf(stderr, "\nError! DART_SORT_BAM=1: %s takes the streaming pipeline (FASTA, a streamed .gz, DART_STREAMING), which has no sorted output\n", fn.c_str());
-            (void)bam.close(); remove(o.out);
+            (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str());
             return 1;
         }
         if (sep) pair_end = true;
@@ -1003,6 +1012,7 @@ int main(int argc, char *argv[])
         auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         auto sort_fail = [&](dg_ctx *c, int rc) {
             (void)bam.close(); remove(o.out);
+            if (bam_index) remove(bai_path.c_str());
             if (rc == DG_ERR_CAPACITY) fprintf(stderr, "\nError! DART_SORT_BAM=1: the records do not fit in device memory: %s\n", dg_last_error(c));
             else fprintf(stderr, "\nError! DART_SORT_BAM=1: %s\n", dg_last_error(c));
             return 1;
@@ -1023,7 +1033,7 @@ int main(int argc, char *argv[])
         char *buf = (char *)dg_host_alloc(cap ? cap : 1);
         const bool pinned = buf != nullptr;
         if (!buf) buf = (char *)malloc(cap ? cap : 1);
-        if (!buf) { (void)bam.close(); remove(o.out); fprintf(stderr, "\nError! DART_SORT_BAM=1: no host memory for a piece of %zu bytes\n", cap); return 1; }
+        if (!buf) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); fprintf(stderr, "\nError! DART_SORT_BAM=1: no host memory for a piece of %zu bytes\n", cap); return 1; }
         float z_ms = 0.f; size_t n_pieces = 0, n_out = 0;
         bool wrote = true;
         for (size_t off = 0; off < n_raw && !rc && wrote; off += piece, n_pieces++) {
@@ -1034,11 +1044,27 @@ int main(int argc, char *argv[])
         }
         if (pinned) dg_host_free(buf); else free(buf);
         if (rc) return sort_fail(roots[0], rc);
-        if (!wrote) { (void)bam.close(); remove(o.out); fprintf(stderr, "Error while writing %s\n", o.out); return 1; }
-        if (getenv("DART_TIMING")) fprintf(stderr, "[dart timing]%s: %zu records, %zu raw bytes; accumulate (sum over workers) %.3f s; merge + finish %.3f s (kernels %.3f s); compress + download + write %.3f s (BGZF kernels %.3f s, %zu pieces of %zu bytes, %zu bytes out)\n",
-                                           bam_dev_note + 1, n_sorted, n_raw, g_sort_acc_ns.load() * 1e-9, ts1 - ts0, fin_ms * 1e-3, now_s() - ts1, z_ms * 1e-3, n_pieces, piece, n_out);
+        if (!wrote) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); fprintf(stderr, "Error while writing %s\n", o.out); return 1; }
+        const double ts2 = now_s();
+        // DART_BAM_INDEX: the blocks' sizes are those the pieces above left in HBM; the records' blocks begin behind the header's
+        size_t bai_bytes = 0; float bai_ms = 0.f;
+        if (bam_index) {
+            auto index_fail = [&](dg_ctx *c) { (void)bam.close(); remove(o.out); remove(bai_path.c_str()); fprintf(stderr, "\nError! DART_BAM_INDEX=1: %s\n", dg_last_error(c)); return 1; };
+            if (dg_bam_index_finish(roots[0], bam.first_block_offset(), nullptr, 0, &bai_bytes, nullptr, &bai_ms)) return index_fail(roots[0]);
+            std::vector<char> bai(bai_bytes ? bai_bytes : 1);
+            if (dg_bam_index_download(roots[0], bai.data(), bai_bytes)) return index_fail(roots[0]);
+            FILE *bf = fopen(bai_path.c_str(), "wb");
+            const bool ok = bf && fwrite(bai.data(), 1, bai_bytes, bf) == bai_bytes;
+            if (!(bf && fclose(bf) == 0 && ok)) { (void)bam.close(); remove(o.out); remove(bai_path.c_str()); fprintf(stderr, "Error while writing %s\n", bai_path.c_str()); return 1; }
+        }
+        if (getenv("DART_TIMING")) {
+            char idx_note[128] = "";
+            if (bam_index) snprintf(idx_note, sizeof idx_note, "; index %.3f s (kernels %.3f s, %zu bytes)", now_s() - ts2, bai_ms * 1e-3, bai_bytes);
+            fprintf(stderr, "[dart timing]%s: %zu records, %zu raw bytes; accumulate (sum over workers) %.3f s; merge + finish %.3f s (kernels %.3f s); compress + download + write %.3f s (BGZF kernels %.3f s, %zu pieces of %zu bytes, %zu bytes out)%s\n",
+                    bam_dev_note + 1, n_sorted, n_raw, g_sort_acc_ns.load() * 1e-9, ts1 - ts0, fin_ms * 1e-3, ts2 - ts1, z_ms * 1e-3, n_pieces, piece, n_out, idx_note);
+        }
     }
-    if (o.bam) { if (!bam.close()) { if (sort_bam) remove(o.out); fprintf(stderr, "Error while writing %s\n", o.out); return 1; } }
+    if (o.bam) { if (!bam.close()) { if (sort_bam) remove(o.out); if (bam_index) remove(bai_path.c_str()); fprintf(stderr, "Error while writing %s\n", o.out); return 1; } }
     else fclose(sam);
     // DART_DEVICE_SJ: the clones' tables into their root's, further roots' into the first (downloaded entries, counted again there), then the table is sorted,
     // mapped to chromosomes and printed on the device: the text is junctions.tab

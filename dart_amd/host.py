@@ -301,6 +301,11 @@ def _load_lib():
         lib.dg_bam_sort_compress.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_uint32, vp, vp]
         lib.dg_bam_sort_granules.argtypes = [vp]
         lib.dg_bam_sort_info.argtypes = [vp, vp]                # (a test hook, not in include/dartgpu.h)
+    if hasattr(lib, "dg_bam_index_finish"):                  # (likewise: the BAM index of the sorted array)
+        lib.dg_bam_index_finish.argtypes = [vp, C.c_uint64, vp, C.c_size_t, vp, vp, vp]
+        lib.dg_bam_index_download.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_bam_index_device.argtypes = [vp, vp, vp]
+        lib.dg_bam_index_granules.argtypes = [vp]
     lib.dg_last_counters.argtypes = [vp, vp, C.c_int]
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
@@ -705,6 +710,29 @@ class DartGPU:
         self.bam_device_ms = float(ms.value)
         out = np.zeros(max(int(nb.value), 1), np.uint8)
         self._chk(self.lib.dg_batch_download_bam(self.ctx, out.ctypes.data, int(nb.value)), "dg_batch_download_bam")
+        return out[:int(nb.value)].tobytes()
+
+    # ---- the BAM index of the sorted array (dg_bam_index_*): the .bai, built in HBM behind bam_sort_finish ----
+    def bam_index_granules(self):
+        """(records per workgroup of the per-record kernel, chunks per tile of the sorter) (dg_bam_index_granules)"""
+        g = (C.c_int * 2)()
+        self._chk(self.lib.dg_bam_index_granules(g), "dg_bam_index_granules")
+        return int(g[0]), int(g[1])
+
+    def bam_index_finish(self, first_block_offset: int, block_sizes=None) -> bytes:
+        """the .bai of the sorted array (dg_bam_index_finish + dg_bam_index_download); block_sizes=None: the compressed sizes the last bam_sort_compress of
+        every block left, else one size per block of 0xff00 raw bytes.  self.bam_index_stats = (placed records, n_no_coor, bins, chunks before the merge,
+        chunks after it, linear-index entries), self.bam_index_device_ms = the kernels' device time"""
+        nb = C.c_size_t(0); ms = C.c_float(0); st = (C.c_uint64 * 6)()
+        sizes, n = None, 0
+        if block_sizes is not None:
+            sizes = np.ascontiguousarray(np.asarray(block_sizes, np.uint32).reshape(-1)); n = len(sizes)
+            sizes = np.concatenate([sizes, np.zeros(1, np.uint32)])          # (never an empty buffer)
+        self._chk(self.lib.dg_bam_index_finish(self.ctx, int(first_block_offset), sizes.ctypes.data if sizes is not None else None, n, C.byref(nb), st, C.byref(ms)),
+                  "dg_bam_index_finish")
+        self.bam_index_stats, self.bam_index_device_ms = tuple(int(x) for x in st), float(ms.value)
+        out = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_bam_index_download(self.ctx, out.ctypes.data, int(nb.value)), "dg_bam_index_download")
         return out[:int(nb.value)].tobytes()
 
     def wait_index(self):

@@ -414,7 +414,9 @@ int dg_sj_granules(int out[2]);
  *   dg_bam_sort_compress     one range of the sorted array -> BGZF blocks (flags 0, or DG_BGZF_DYNAMIC), or the bytes as they are (DG_BAM_RAW); the result
  *                            lies where dg_batch_download_bam / dg_batch_device_bam find it.  raw_off must be a multiple of 0xff00 and raw_len such a multiple
  *                            or reach the array's end (else DG_ERR_ARG): so the concatenated output is the same bytes whatever piece size the caller picks,
- *                            and an array of 20 GB never needs 20 GB of block slots at once.
+ *                            and an array of 20 GB never needs 20 GB of block slots at once.  A compressing call also keeps its blocks' compressed sizes
+ *                            in HBM for dg_bam_index_finish (4 bytes per block of the array); should that small array not be had, the call succeeds all
+ *                            the same and dg_bam_index_finish without block_sizes names the block it misses.
  *   dg_bam_sort_granules     [0] reads per workgroup of the two key kernels, [1] pairs per tile of the sorter, [2] the store's smallest size in bytes    */
 int dg_batch_accumulate_bam(dg_ctx *, uint32_t ordinal, size_t *n_records, size_t *n_bytes);
 int dg_bam_sort_add(dg_ctx *, const void *records, size_t n, uint32_t ordinal, size_t *n_records);
@@ -425,6 +427,60 @@ int dg_bam_sort_device_ms(dg_ctx *, float ms[5], int *n_passes);
 int dg_bam_sort_device(dg_ctx *, void **ptr, size_t *n_raw);
 int dg_bam_sort_compress(dg_ctx *, size_t raw_off, size_t raw_len, uint32_t flags, size_t *n_bytes, float *device_ms);
 int dg_bam_sort_granules(int out[3]);
+
+/* ---- the BAM index (.bai) of the sorted array, built in HBM next to the sort (the reference has no such output: an opt-in extension; it replaces the
+ * `samtools index` a user runs behind `samtools sort`) ----
+ * THE DEFINITION.  The index is the BAI of SAM specification 5.2, built the way htslib's hts_idx_push / hts_idx_finish build it for a BAM read record by
+ * record, with two deliberate differences (1, 2 below).  No samtools or htslib binary exists where this library is built and tested: the definition here --
+ * not a run of samtools -- is what the tests pin.
+ * Per sorted record, fields read byte by byte (block_size at byte 0): refID int32 at byte 4, pos int32 at byte 8, l_read_name u8 at byte 12, n_cigar_op u16 at
+ * byte 16, flag u16 at byte 18; the CIGAR ops are u32 little endian (len << 4 | op) from byte 36 + l_read_name.
+ *     placed   0 <= refID < n_chr; all other records come last in the sorted array and are only counted, in n_no_coor
+ *     mapped   flag & 4 is clear
+ *     rlen     the sum of len over ops 0, 2, 3, 7, 8 (M, D, N, =, X) when the record is mapped and n_cigar_op > 0, else 0
+ *     end_raw = pos + (rlen ? rlen : 1); beg = max(pos, 0); end = max(end_raw, beg + 1) -- the clamp applies to every placed record (htslib clamps only
+ *              mapped ones; the formatter never writes a placed record with pos = -1, so the difference is reachable only through dg_bam_sort_add)
+ *     bin      reg2bin(beg, end), recomputed, not read from the record's bin field -- exactly as htslib does
+ *     end > 2^29 on a placed record: DG_ERR_RANGE; the text names the record's index and says that such a reference needs a CSI index; no index is left
+ *              behind, the sorted array and the store stay as they were
+ * Virtual offsets: B = 0xff00; coff[k] = first_block_offset + the compressed sizes of blocks 0 .. k-1; coff[n_blocks] = the file offset behind the last data
+ * block.  For a position r of the sorted array voff(r) = coff[r / B] << 16 | r % B for r < n_raw, and voff(n_raw) = coff[n_blocks] << 16: what bgzf_tell returns
+ * after reading up to r (a position at a block's end reads as the start of the next block).  Every coff must stay below 2^48, else DG_ERR_RANGE.
+ * Chunks, as hts_idx_push makes them: walking the placed records in file order, a chunk is a maximal run of consecutive records with the same (refID, bin),
+ * from voff of its first record's start to voff of the start of the record behind the run (behind the last placed record: the first unplaced record's start, or
+ * voff(n_raw)).  Per reference the bins are written in ASCENDING BIN NUMBER (difference 1: htslib writes them in hash-table order; the specification allows any
+ * order).  Inside a bin the chunks lie in file order; neighbours are merged when prev.end >> 16 >= next.beg >> 16, keeping the earlier begin and the later end
+ * (compress_binning's last loop).  htslib's other compression step, moving a bin that spans less than 64 KiB of file to its parent, is NOT done (difference 2:
+ * the index is larger and equally valid).
+ * The pseudo-bin 37450 is written only for a reference that has records, last: two chunks, (voff of the reference's first record's start, voff of its last
+ * record's end) and (n_mapped, n_unmapped).  A reference without records has n_bin = 0 and n_intv = 0.
+ * The linear index: n_intv = max over the reference's mapped records of ((end - 1) >> 14) + 1; window w holds the smallest voff(start) over the mapped records
+ * with beg >> 14 <= w <= (end - 1) >> 14.  Placed unmapped records are binned and counted but do not touch it.  Empty windows are filled as update_loff fills
+ * them: leading ones get the reference's first record's start (the pseudo-bin's first value), a later one its predecessor's value.
+ * The bytes, little endian: "BAI\1", int32 n_ref = n_chr; per reference int32 n_bin (counting the pseudo-bin), per bin {u32 bin, int32 n_chunk, n_chunk x
+ * {u64 beg, u64 end}}, int32 n_intv, n_intv x u64; finally u64 n_no_coor.  An empty store gives 8 + 8 * n_chr + 8 bytes.
+ * The same records and the same block sizes give the same bytes, whatever the grid, the batch split, the contexts used, the store's growth history or the
+ * piece size of dg_bam_sort_compress.  The chromosome names are not needed.
+ *   dg_bam_index_finish    needs the sorted array of dg_bam_sort_finish with no store call behind it, else DG_ERR_ARG (the text names dg_bam_sort_finish).
+ *                          first_block_offset: the file offset of the first block of records (behind the header's blocks).  block_sizes == NULL: the sizes
+ *                          dg_bam_sort_compress recorded -- every compressing call (flags 0 or DG_BGZF_DYNAMIC, not DG_BAM_RAW) keeps its blocks' compressed
+ *                          sizes in HBM (one u32 per block of the sorted array, copied device to device) and marks the blocks covered; dg_bam_sort_finish and
+ *                          every store call clear the marks; a block not compressed since the last finish gives DG_ERR_ARG, the text names the first such
+ *                          block.  The sizes are those of the LAST compress of each block: writing those very bytes to the file is the caller's duty.
+ *                          block_sizes != NULL (a caller with its own compressor, and the tests): n_blocks must be ceil(n_raw / 0xff00) and every size at
+ *                          least 1, else DG_ERR_ARG.  stats (may be NULL): [0] placed records, [1] n_no_coor, [2] bins written, without the pseudo-bins,
+ *                          [3] chunks before the merge, [4] chunks after it, [5] linear-index entries.  *device_ms (may be NULL): device time of the
+ *                          kernels, a measurement.  The call enqueues on the context's stream and waits twice: for the per-reference sizes, and for the
+ *                          index's size.  Memory: 20 bytes per record, about 60 per chunk, 8 per window, and the index; a failed allocation gives
+ *                          DG_ERR_CAPACITY, the text names the need.  Every failure leaves the context, the store and the sorted array usable; the
+ *                          sorted array stays valid and the call may be repeated, for instance with other sizes.  dg_destroy frees the buffers.
+ *   dg_bam_index_download  copies the index out; DG_ERR_CAPACITY, nothing written, when cap is smaller
+ *   dg_bam_index_device    the index in HBM, valid until the next store or index call on the context
+ *   dg_bam_index_granules  [0] records per workgroup of the per-record kernel, [1] the sorter's tile (chunks)                                              */
+int dg_bam_index_finish(dg_ctx *, uint64_t first_block_offset, const uint32_t *block_sizes, size_t n_blocks, size_t *n_bytes, uint64_t stats[6], float *device_ms);
+int dg_bam_index_download(dg_ctx *, void *out, size_t cap);
+int dg_bam_index_device(dg_ctx *, void **ptr, size_t *n_bytes);
+int dg_bam_index_granules(int out[2]);
 
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
