@@ -18,6 +18,7 @@
 #include "dg_sjtab.h"
 #include "dg_bamsort.h"
 #include "dg_bamidx.h"
+#include "dg_coverage.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -209,6 +210,13 @@ struct dg_ctx {
     unsigned long long *d_bi_stat = nullptr, *h_bi_stat = nullptr;        // BI_ST_* words: device / page-locked copy
     hipEvent_t ev_bi[4] = {nullptr, nullptr, nullptr, nullptr};          // the kernels before and behind the mid-way wait
     bool bi_valid = false; size_t bi_bytes = 0; int bs_fin_which = 0;     // bs_fin_which: bs_k[bs_fin_which ^ 1] holds the sorted records' places inside their tiles
+    // the coverage track of the sorted array (dg_coverage.h): buffers of its own (the sorter's hold the records' places, which the index needs): per record the
+    // block offsets, per event the sorter's pairs, the scanned deltas and the marks, per breakpoint its key and depth, per entry its breakpoint, record and line
+    DBuf<uint32_t> cv_blk_off, cv_incl, cv_dep_tile, cv_tile_prev, cv_mark, cv_bp_depth, cv_ent_bp, cv_line_off, cv_hist, cv_sums;
+    DBuf<uint64_t> cv_blk_tile, cv_k[2], cv_tile_last, cv_cnt_tile, cv_bp_key, cv_line_tile, cv_part; DBuf<int64_t> cv_v[2]; DBuf<dg_cov_entry> cv_entries; DBuf<char> cv_text;
+    unsigned long long *d_cv_stat = nullptr, *h_cv_stat = nullptr;        // CV_ST_* words: device / page-locked copy
+    hipEvent_t ev_cv[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // around the kernels between the waits
+    bool cv_valid = false; size_t cv_n_entries = 0, cv_bytes = 0; float cv_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f}; int cv_passes = 0;
     size_t env_bamsort_first_cap = 0;  // DG_BAMSORT_FIRST_CAP: test hook, the first size of the store in bytes (forces growth)
     size_t env_bam_first_cap = 0;      // DG_BAM_FIRST_CAP: test hook, the first size of the record buffer in bytes
     size_t env_sam_first_cap = 0;      // DG_SAM_TEXT_FIRST_CAP: test hook, the first size of the text buffer in bytes (forces the "text outgrew the guess" path)
@@ -684,6 +692,12 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->d_bi_stat) (void)hipFree(c->d_bi_stat);
     if (c->h_bi_stat) (void)hipHostFree(c->h_bi_stat);
     for (hipEvent_t e : c->ev_bi) if (e) (void)hipEventDestroy(e);
+    for (DBuf<uint32_t> *b : {&c->cv_blk_off, &c->cv_incl, &c->cv_dep_tile, &c->cv_tile_prev, &c->cv_mark, &c->cv_bp_depth, &c->cv_ent_bp, &c->cv_line_off, &c->cv_hist, &c->cv_sums}) b->release();
+    for (DBuf<uint64_t> *b : {&c->cv_blk_tile, &c->cv_k[0], &c->cv_k[1], &c->cv_tile_last, &c->cv_cnt_tile, &c->cv_bp_key, &c->cv_line_tile, &c->cv_part}) b->release();
+    c->cv_v[0].release(); c->cv_v[1].release(); c->cv_entries.release(); c->cv_text.release();
+    if (c->d_cv_stat) (void)hipFree(c->d_cv_stat);
+    if (c->h_cv_stat) (void)hipHostFree(c->h_cv_stat);
+    for (hipEvent_t e : c->ev_cv) if (e) (void)hipEventDestroy(e);
     if (c->d_bs_stat) (void)hipFree(c->d_bs_stat);
     if (c->h_bs_stat) (void)hipHostFree(c->h_bs_stat);
     for (hipEvent_t e : c->ev_bs) if (e) (void)hipEventDestroy(e);
@@ -3027,6 +3041,7 @@ extern "C" int dg_bam_sort_finish(dg_ctx *c, size_t *n_records, size_t *n_raw, f
     if (device_ms) *device_ms = 0.f;
     c->bs_fin_valid = false; c->bs_fin_bytes = 0; c->bs_fin_records = 0; c->bs_passes = 0;
     c->bi_valid = false; c->bi_covered.clear();             // (no block of the new array has been compressed)
+    c->cv_valid = false;
     for (float &m : c->bs_ms) m = 0.f;
     { const int rc = bs_ready(c); if (rc) return rc; }
     if (!c->bs_n) { c->bs_fin_valid = true; return DG_OK; }
@@ -3293,6 +3308,182 @@ extern "C" int dg_bam_index_device(dg_ctx *c, void **ptr, size_t *n_bytes)
     if (!c || !ptr || !n_bytes) return DG_ERR_ARG;
     if (!c->bi_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_index_device: no index (dg_bam_index_finish first, and no store call behind it)"); return DG_ERR_ARG; }
     *ptr = c->bi_out.p; *n_bytes = c->bi_bytes;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the coverage track of the sorted array (dg_coverage.h): built in HBM from the sorted records and their places, in buffers of its own
+// ------------------------------------------------------------------------------------------
+static int cv_state(dg_ctx *c)
+{
+    if (c->d_cv_stat) return DG_OK;
+    HIPCHK(hipMalloc((void **)&c->d_cv_stat, CV_ST_WORDS * 8));
+    HIPCHK(hipHostMalloc((void **)&c->h_cv_stat, CV_ST_WORDS * 8, hipHostMallocDefault));
+    memset(c->h_cv_stat, 0, CV_ST_WORDS * 8);
+    for (hipEvent_t &e : c->ev_cv) HIPCHK(hipEventCreate(&e));
+    return DG_OK;
+}
+
+extern "C" int dg_bam_coverage_granules(int out[2])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = CV_THREADS; out[1] = RS_TILE;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_coverage_finish(dg_ctx *c, uint32_t flags, uint32_t exclude_flags, uint32_t min_mapq, size_t *n_entries, size_t *n_bytes, uint64_t stats[7], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_coverage_finish";
+    if (n_entries) *n_entries = 0;
+    if (n_bytes) *n_bytes = 0;
+    if (device_ms) *device_ms = 0.f;
+    if (stats) for (int k = 0; k < 7; k++) stats[k] = 0;
+    c->cv_valid = false; c->cv_n_entries = 0; c->cv_bytes = 0; c->cv_passes = 0;
+    for (float &m : c->cv_ms) m = 0.f;
+    if (!c->bs_fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
+    if (flags & ~(DG_COV_ENTRIES_ONLY | DG_COV_STRAND_PLUS | DG_COV_STRAND_MINUS)) { snprintf(c->err, 512, "%s: flags 0x%x hold a bit that is none of DG_COV_ENTRIES_ONLY, DG_COV_STRAND_PLUS, DG_COV_STRAND_MINUS", fn, flags); return DG_ERR_ARG; }
+    const bool text = !(flags & DG_COV_ENTRIES_ONLY);
+    IndexShared *sh = c->shared_ix;
+    if (text && (!sh || !sh->chr_names_set)) { snprintf(c->err, 512, "%s: the chromosome names are missing (dg_set_chr_names), and DG_COV_ENTRIES_ONLY is not set", fn); return DG_ERR_ARG; }
+    { const int rc = bs_ready(c); if (rc) return rc; }
+    { const int rc = cv_state(c); if (rc) return rc; }
+    const size_t n = c->bs_fin_records, n_raw = c->bs_fin_bytes;
+    const int n_chr = c->ix.n_chr;
+    if (n_chr < 1) { snprintf(c->err, 512, "%s: %d chromosomes", fn, n_chr); return DG_ERR_ARG; }
+    if (!n) { c->cv_valid = true; return DG_OK; }
+    const CvFilter f{flags, exclude_flags, min_mapq};
+    const uint32_t tiles = (uint32_t)((n + CV_THREADS - 1) / CV_THREADS);
+    BS_ENSURE(c->cv_blk_off, n, "the records' block offsets"); BS_ENSURE(c->cv_blk_tile, (size_t)tiles + 1, "the per-workgroup block counts");
+    BS_ENSURE(c->cv_part, (size_t)CV_PLANES * tiles, "the per-workgroup values");
+    const uint64_t *dst_off = c->bs_k[c->bs_fin_which ^ 1].p;
+    HIPCHK(hipMemsetAsync(c->d_cv_stat, 0, CV_ST_WORDS * 8, c->stream));
+    HIPCHK(hipEventRecord(c->ev_cv[0], c->stream));
+    k_cv_count<<<tiles, CV_THREADS, 0, c->stream>>>(c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, n_chr, f, c->cv_blk_off.p, c->cv_blk_tile.p, c->cv_part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv_blk_tile.p, tiles, c->d_cv_stat + CV_ST_BLOCKS, c->cv_part.p, 5, 2, c->d_cv_stat + CV_ST_COUNTED);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_cv[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_cv_stat, c->d_cv_stat, CV_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the first wait: how many events, which digits their keys differ in, and what was out of range
+    if (c->h_cv_stat[CV_ST_NBAD]) {
+        snprintf(c->err, 512, "%s: record %llu of the sorted array has a block that ends behind position 2^32 - 1: an entry cannot hold it; no track was built", fn, ~c->h_cv_stat[CV_ST_NBAD]);
+        return DG_ERR_RANGE;
+    }
+    const unsigned long long n_blocks = c->h_cv_stat[CV_ST_BLOCKS], n_counted = c->h_cv_stat[CV_ST_COUNTED], aligned = c->h_cv_stat[CV_ST_ALIGNED];
+    if (2 * n_blocks >= 0xFFFFF000ull) { snprintf(c->err, 512, "%s: %llu events (two per block) are more than the sorter takes (2^32 - 1, less a tile)", fn, 2 * n_blocks); return DG_ERR_CAPACITY; }
+    float a = 0.f;
+    (void)hipEventElapsedTime(&a, c->ev_cv[0], c->ev_cv[1]);
+    c->cv_ms[0] = a;
+    auto done = [&](size_t ne, size_t nb, unsigned long long n_bp, unsigned long long covered, unsigned long long deepest) {
+        float total = 0.f;
+        for (float m : c->cv_ms) total += m;
+        c->cv_valid = true; c->cv_n_entries = ne; c->cv_bytes = nb;
+        if (n_entries) *n_entries = ne;
+        if (n_bytes) *n_bytes = nb;
+        if (device_ms) *device_ms = total;
+        if (stats) { stats[0] = n_counted; stats[1] = n_blocks; stats[2] = n_bp; stats[3] = ne; stats[4] = covered; stats[5] = aligned; stats[6] = deepest; }
+        return DG_OK;
+    };
+    if (!n_blocks) return done(0, 0, 0, 0, 0);
+    const uint32_t n_ev = (uint32_t)(2 * n_blocks), etiles = (n_ev + CV_THREADS - 1) / CV_THREADS;
+    for (int k = 0; k < 2; k++) { BS_ENSURE(c->cv_k[k], (size_t)n_ev, "the events' keys"); BS_ENSURE(c->cv_v[k], (size_t)n_ev, "the events' deltas"); }
+    BS_ENSURE(c->cv_hist, rs_hist_words(n_ev), "the sorter's histograms"); BS_ENSURE(c->cv_sums, rs_sums_words(n_ev), "the sorter's sums");
+    BS_ENSURE(c->cv_incl, (size_t)n_ev, "the scanned deltas"); BS_ENSURE(c->cv_mark, (size_t)n_ev, "the events' marks");
+    BS_ENSURE(c->cv_dep_tile, (size_t)etiles + 1, "the per-workgroup depth sums"); BS_ENSURE(c->cv_tile_last, (size_t)etiles + 1, "the per-workgroup last tails");
+    BS_ENSURE(c->cv_tile_prev, (size_t)etiles + 1, "the per-workgroup previous tails"); BS_ENSURE(c->cv_cnt_tile, (size_t)etiles + 1, "the per-workgroup breakpoint counts");
+    BS_ENSURE(c->cv_part, (size_t)etiles, "the per-workgroup values");
+    const int bits = std::min(cv_key_bits(~c->h_cv_stat[CV_ST_NMIN], c->h_cv_stat[CV_ST_MAX]), cv_key_bits_max(n_chr));
+    int which = 0;
+    HIPCHK(hipEventRecord(c->ev_cv[2], c->stream));
+    k_cv_emit<<<tiles, CV_THREADS, 0, c->stream>>>(c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, n_chr, f, c->cv_blk_off.p, c->cv_blk_tile.p, n_blocks, c->cv_k[0].p, c->cv_v[0].p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_cv[3], c->stream));
+    {
+        uint64_t *const keys[2] = {c->cv_k[0].p, c->cv_k[1].p}; int64_t *const vals[2] = {c->cv_v[0].p, c->cv_v[1].p};
+        const int rc = rs_sort_passes(c, keys, vals, c->cv_hist.p, c->cv_sums.p, n_ev, bits, which);
+        if (rc) return rc;
+        c->cv_passes = (bits + 3) / 4;
+    }
+    HIPCHK(hipEventRecord(c->ev_cv[4], c->stream));
+    const uint64_t *skey = c->cv_k[which].p;
+    k_cv_depth<<<etiles, CV_THREADS, 0, c->stream>>>(c->cv_v[which].p, n_ev, c->cv_incl.p, c->cv_dep_tile.p);
+    k_scan_top<<<1, 256, 0, c->stream>>>(c->cv_dep_tile.p, etiles, (uint32_t *)(c->d_cv_stat + CV_ST_DEPTH_END), nullptr, 0, nullptr, 0);
+    k_cv_tails<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv_incl.p, c->cv_dep_tile.p, n_ev, c->cv_tile_last.p);
+    k_cv_tails_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv_tile_last.p, etiles, c->cv_tile_prev.p);
+    k_cv_flag<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv_incl.p, c->cv_dep_tile.p, c->cv_tile_prev.p, n_ev, c->cv_mark.p, c->cv_cnt_tile.p, c->cv_part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv_cnt_tile.p, etiles, c->d_cv_stat + CV_ST_MARKS, c->cv_part.p, 1, 0, c->d_cv_stat + CV_ST_MAX_DEPTH);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_cv[5], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_cv_stat, c->d_cv_stat, CV_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the second wait: how many breakpoints and entries
+    const size_t n_bp = (size_t)(uint32_t)c->h_cv_stat[CV_ST_MARKS], n_ent = (size_t)(c->h_cv_stat[CV_ST_MARKS] >> 32);
+    if ((uint32_t)c->h_cv_stat[CV_ST_DEPTH_END] != 0u || n_bp < 2 || n_ent < 1 || n_ent >= n_bp || n_bp > n_ev) {
+        snprintf(c->err, 512, "%s: %u events leave the depth %u behind the last, %zu breakpoints and %zu entries", fn, n_ev, (uint32_t)c->h_cv_stat[CV_ST_DEPTH_END], n_bp, n_ent);
+        return DG_ERR_INTERNAL;
+    }
+    const uint32_t ntiles = (uint32_t)((n_ent + CV_THREADS - 1) / CV_THREADS);
+    BS_ENSURE(c->cv_bp_key, n_bp, "the breakpoints' keys"); BS_ENSURE(c->cv_bp_depth, n_bp, "the breakpoints' depths"); BS_ENSURE(c->cv_ent_bp, n_ent, "the entries' breakpoints");
+    BS_ENSURE(c->cv_entries, n_ent, "the entries"); BS_ENSURE(c->cv_line_off, n_ent, "the lines' offsets"); BS_ENSURE(c->cv_line_tile, (size_t)ntiles + 1, "the per-workgroup line sums");
+    BS_ENSURE(c->cv_part, 2 * (size_t)ntiles, "the per-workgroup values");
+    {   // the chromosome names are read and the kernels that use them enqueued under the index's lock (as the SAM formatter does: dg_set_chr_names waits for the device before it frees them)
+        std::unique_lock<std::mutex> lk;
+        const uint32_t *name_off = nullptr; const char *names = nullptr;
+        if (text) {
+            lk = std::unique_lock<std::mutex>(sh->mu);
+            name_off = sh->d_chr_name_off; names = sh->d_chr_names;
+            BS_ENSURE(c->cv_text, (size_t)(n_ent * cv_line_bound(sh->chr_name_max)), "the text");
+        }
+        HIPCHK(hipEventRecord(c->ev_cv[6], c->stream));
+        k_cv_compact<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv_incl.p, c->cv_dep_tile.p, c->cv_mark.p, c->cv_cnt_tile.p, n_ev, (uint32_t)n_bp, (uint32_t)n_ent, c->cv_bp_key.p, c->cv_bp_depth.p, c->cv_ent_bp.p);
+        HIPCHK(hipEventRecord(c->ev_cv[7], c->stream));
+        k_cv_entries<<<ntiles, CV_THREADS, 0, c->stream>>>(c->cv_bp_key.p, c->cv_bp_depth.p, c->cv_ent_bp.p, (uint32_t)n_bp, (uint32_t)n_ent, n_chr, name_off, c->cv_entries.p, c->cv_line_off.p, c->cv_line_tile.p, c->cv_part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv_line_tile.p, ntiles, c->d_cv_stat + CV_ST_BYTES, c->cv_part.p, 2, 2, c->d_cv_stat + CV_ST_COVERED);
+        if (text)
+            k_cv_write<<<ntiles, CV_THREADS, 0, c->stream>>>(c->cv_entries.p, (uint32_t)n_ent, n_chr, name_off, names, c->cv_line_off.p, c->cv_line_tile.p, c->d_cv_stat, (unsigned long long)c->cv_text.cap, c->cv_text.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->ev_cv[8], c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(c->h_cv_stat, c->d_cv_stat, CV_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the third wait: the text's size, the covered bases
+    const size_t bytes = text ? (size_t)c->h_cv_stat[CV_ST_BYTES] : 0;
+    if (bytes > c->cv_text.cap) { snprintf(c->err, 512, "%s: the text needs %zu bytes, the bound was %zu", fn, bytes, c->cv_text.cap); return DG_ERR_INTERNAL; }
+    if (c->h_cv_stat[CV_ST_AREA] != aligned) { snprintf(c->err, 512, "%s: the entries hold %llu aligned bases, the blocks %llu", fn, c->h_cv_stat[CV_ST_AREA], aligned); return DG_ERR_INTERNAL; }
+    float e = 0.f, s = 0.f, d1 = 0.f, d2 = 0.f, w = 0.f;
+    (void)hipEventElapsedTime(&e, c->ev_cv[2], c->ev_cv[3]); (void)hipEventElapsedTime(&s, c->ev_cv[3], c->ev_cv[4]); (void)hipEventElapsedTime(&d1, c->ev_cv[4], c->ev_cv[5]);
+    (void)hipEventElapsedTime(&d2, c->ev_cv[6], c->ev_cv[7]); (void)hipEventElapsedTime(&w, c->ev_cv[7], c->ev_cv[8]);
+    c->cv_ms[1] = e; c->cv_ms[2] = s; c->cv_ms[3] = d1 + d2; c->cv_ms[4] = w;
+    return done(n_ent, bytes, n_bp, c->h_cv_stat[CV_ST_COVERED], c->h_cv_stat[CV_ST_MAX_DEPTH]);
+}
+
+extern "C" int dg_bam_coverage_download(dg_ctx *c, dg_cov_entry *entries, size_t cap_entries, char *text, size_t cap_text)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->cv_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_coverage_download: no track (dg_bam_coverage_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if ((entries && cap_entries < c->cv_n_entries) || (text && cap_text < c->cv_bytes)) {
+        snprintf(c->err, 512, "dg_bam_coverage_download: output capacity too small: %zu entries and %zu bytes of text are needed", c->cv_n_entries, c->cv_bytes);
+        return DG_ERR_CAPACITY;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (entries && c->cv_n_entries) HIPCHK(hipMemcpyAsync(entries, c->cv_entries.p, c->cv_n_entries * sizeof(dg_cov_entry), hipMemcpyDeviceToHost, c->stream));
+    if (text && c->cv_bytes) HIPCHK(hipMemcpyAsync(text, c->cv_text.p, c->cv_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_bam_coverage_device(dg_ctx *c, void **entries, void **text)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->cv_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_coverage_device: no track (dg_bam_coverage_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if (entries) *entries = c->cv_n_entries ? c->cv_entries.p : nullptr;
+    if (text) *text = c->cv_bytes ? c->cv_text.p : nullptr;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_coverage_device_ms(dg_ctx *c, float ms[5], int *n_passes)
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    for (int k = 0; k < 5; k++) ms[k] = c->cv_ms[k];
+    if (n_passes) *n_passes = c->cv_passes;
     return DG_OK;
 }
 

@@ -58,7 +58,7 @@ static void usage(const char *prog, const Options &o)   // ShowProgramUsage, mai
     fprintf(stdout, "         -max_dup INT  maximal number of repetitive fragments (between 100-10000) [%d]\n", o.p.max_dup);
     fprintf(stdout, "         -o            alignment filename in SAM format\n");
     fprintf(stdout, "         -bo           alignment filename in BAM format\n");
-    fprintf(stdout, "                       (DART_DEVICE_BAM=1 DART_SORT_BAM=1: coordinate-sorted on the device; DART_BAM_INDEX=1 beside them: its .bai too)\n");
+    fprintf(stdout, "                       (DART_DEVICE_BAM=1 DART_SORT_BAM=1: coordinate-sorted on the device; DART_BAM_INDEX=1 beside them: its .bai too; DART_COVERAGE=1 or 2: its bedGraph, or one per strand)\n");
     fprintf(stdout, "         -j            splice junction output filename [junctions.tab]\n");
     fprintf(stdout, "         -m            output multiple alignments [false]\n");
     fprintf(stdout, "         -all_sj       detect all splice junction regardless of mapq score [false]\n");
@@ -573,6 +573,24 @@ int main(int argc, char *argv[])
         return 1;
     }
     const std::string bai_path = bam_index ? std::string(o.out) + ".bai" : std::string();
+    // DART_COVERAGE=1 beside DART_SORT_BAM=1: the sorted file's coverage track <out>.bedgraph, built on the device from the sorted records (dg_bam_coverage_finish)
+    // in place of a `bedtools genomecov -bg -split` over the file; DART_COVERAGE=2: <out>.plus.bedgraph and <out>.minus.bedgraph.  DART_COVERAGE_EXCLUDE (default
+    // 0x704) and DART_COVERAGE_MIN_MAPQ (default 0) are the filter.  Without the sort there is nothing to cover: no output is begun.
+    const int coverage = getenv("DART_COVERAGE") ? atoi(getenv("DART_COVERAGE")) : 0;
+    if (coverage != 0 && coverage != 1 && coverage != 2) {
+        fprintf(stderr, "Error! DART_COVERAGE=%d is neither 1 (one track) nor 2 (one track per strand)\n", coverage);
+        return 1;
+    }
+    if (coverage && !sort_bam) {
+        fprintf(stderr, "Error! DART_COVERAGE=%d needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n", coverage);
+        return 1;
+    }
+    const uint32_t cov_exclude = getenv("DART_COVERAGE_EXCLUDE") ? (uint32_t)strtoul(getenv("DART_COVERAGE_EXCLUDE"), nullptr, 0) : 0x704u;
+    const uint32_t cov_min_mapq = getenv("DART_COVERAGE_MIN_MAPQ") ? (uint32_t)strtoul(getenv("DART_COVERAGE_MIN_MAPQ"), nullptr, 0) : 0u;
+    std::vector<std::pair<std::string, uint32_t>> cov_tracks;      // path, strand flags
+    if (coverage == 1) cov_tracks.emplace_back(std::string(o.out) + ".bedgraph", 0u);
+    if (coverage == 2) { cov_tracks.emplace_back(std::string(o.out) + ".plus.bedgraph", DG_COV_STRAND_PLUS); cov_tracks.emplace_back(std::string(o.out) + ".minus.bedgraph", DG_COV_STRAND_MINUS); }
+    auto drop_tracks = [&]() { for (const auto &t : cov_tracks) remove(t.first.c_str()); };      // (no failed run leaves a track, a stale one included)
     const char *bam_dev_note = sort_bam ? (bgzf_dynamic ? ", bam=device+sorted+dyn" : ", bam=device+sorted") : bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "";
     FastqIndex pre;                         // the first library's read files are mapped and indexed while the HIP runtime starts, the genome index loads and dg_init_files runs
     bool fast_first = false;
@@ -753,7 +771,7 @@ int main(int argc, char *argv[])
     auto out_end = [&](uint64_t off) { if (sam) fseeko(sam, (off_t)off, SEEK_SET); };
     // a library that failed: under DART_SORT_BAM no partial file is left, and a store that could not grow says which switch asked for the memory
     auto lib_failed = [&](int frc, const std::string &ferr) -> int {
-        if (sort_bam) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); }
+        if (sort_bam) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); drop_tracks(); }
         if (sort_bam && frc == DG_ERR_CAPACITY) fprintf(stderr, "\nError! DART_SORT_BAM=1: the records do not fit in device memory: %s\n", ferr.c_str());
         else fprintf(stderr, "\nError! GPU mapping failed (%d): %s\n", frc, ferr.c_str());
         return 1;
@@ -802,7 +820,7 @@ int main(int argc, char *argv[])
             }
         }
         const int orc = open_lib(lib);              // (library 0 was opened before the index went to the GPU: its files are being inflated and parsed since)
-        if (orc == 2) { if (sort_bam) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); } return 1; }      // (under DART_SORT_BAM no failed run leaves a file)
+        if (orc == 2) { if (sort_bam) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); drop_tracks(); } return 1; }      // (under DART_SORT_BAM no failed run leaves a file)
         if (orc == 1) continue;
         LibIO &L = *libs[lib];
         Source &s1 = L.s1, &s2 = L.s2; Prefetch &pf1 = L.pf1, &pf2 = L.pf2;
@@ -810,7 +828,7 @@ int main(int argc, char *argv[])
         const std::string &fn = o.f1[lib];
         if (sort_bam && !fast_host) {
             fprintf(stderr, "\nError! DART_SORT_BAM=1: %s takes the streaming pipeline (FASTA, a streamed .gz, DART_STREAMING), which has no sorted output\n", fn.c_str());
-            (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str());
+            (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); drop_tracks();
             return 1;
         }
         if (sep) pair_end = true;
@@ -1012,7 +1030,7 @@ int main(int argc, char *argv[])
         auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         auto sort_fail = [&](dg_ctx *c, int rc) {
             (void)bam.close(); remove(o.out);
-            if (bam_index) remove(bai_path.c_str());
+            if (bam_index) remove(bai_path.c_str()); drop_tracks();
             if (rc == DG_ERR_CAPACITY) fprintf(stderr, "\nError! DART_SORT_BAM=1: the records do not fit in device memory: %s\n", dg_last_error(c));
             else fprintf(stderr, "\nError! DART_SORT_BAM=1: %s\n", dg_last_error(c));
             return 1;
@@ -1033,7 +1051,7 @@ int main(int argc, char *argv[])
         char *buf = (char *)dg_host_alloc(cap ? cap : 1);
         const bool pinned = buf != nullptr;
         if (!buf) buf = (char *)malloc(cap ? cap : 1);
-        if (!buf) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); fprintf(stderr, "\nError! DART_SORT_BAM=1: no host memory for a piece of %zu bytes\n", cap); return 1; }
+        if (!buf) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); drop_tracks(); fprintf(stderr, "\nError! DART_SORT_BAM=1: no host memory for a piece of %zu bytes\n", cap); return 1; }
         float z_ms = 0.f; size_t n_pieces = 0, n_out = 0;
         bool wrote = true;
         for (size_t off = 0; off < n_raw && !rc && wrote; off += piece, n_pieces++) {
@@ -1044,18 +1062,18 @@ int main(int argc, char *argv[])
         }
         if (pinned) dg_host_free(buf); else free(buf);
         if (rc) return sort_fail(roots[0], rc);
-        if (!wrote) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); fprintf(stderr, "Error while writing %s\n", o.out); return 1; }
+        if (!wrote) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); drop_tracks(); fprintf(stderr, "Error while writing %s\n", o.out); return 1; }
         const double ts2 = now_s();
         // DART_BAM_INDEX: the blocks' sizes are those the pieces above left in HBM; the records' blocks begin behind the header's
         size_t bai_bytes = 0; float bai_ms = 0.f;
         if (bam_index) {
-            auto index_fail = [&](dg_ctx *c) { (void)bam.close(); remove(o.out); remove(bai_path.c_str()); fprintf(stderr, "\nError! DART_BAM_INDEX=1: %s\n", dg_last_error(c)); return 1; };
+            auto index_fail = [&](dg_ctx *c) { (void)bam.close(); remove(o.out); remove(bai_path.c_str()); drop_tracks(); fprintf(stderr, "\nError! DART_BAM_INDEX=1: %s\n", dg_last_error(c)); return 1; };
             if (dg_bam_index_finish(roots[0], bam.first_block_offset(), nullptr, 0, &bai_bytes, nullptr, &bai_ms)) return index_fail(roots[0]);
             std::vector<char> bai(bai_bytes ? bai_bytes : 1);
             if (dg_bam_index_download(roots[0], bai.data(), bai_bytes)) return index_fail(roots[0]);
             FILE *bf = fopen(bai_path.c_str(), "wb");
             const bool ok = bf && fwrite(bai.data(), 1, bai_bytes, bf) == bai_bytes;
-            if (!(bf && fclose(bf) == 0 && ok)) { (void)bam.close(); remove(o.out); remove(bai_path.c_str()); fprintf(stderr, "Error while writing %s\n", bai_path.c_str()); return 1; }
+            if (!(bf && fclose(bf) == 0 && ok)) { (void)bam.close(); remove(o.out); remove(bai_path.c_str()); drop_tracks(); fprintf(stderr, "Error while writing %s\n", bai_path.c_str()); return 1; }
         }
         if (getenv("DART_TIMING")) {
             char idx_note[128] = "";
@@ -1064,8 +1082,28 @@ int main(int argc, char *argv[])
                     bam_dev_note + 1, n_sorted, n_raw, g_sort_acc_ns.load() * 1e-9, ts1 - ts0, fin_ms * 1e-3, ts2 - ts1, z_ms * 1e-3, n_pieces, piece, n_out, idx_note);
         }
     }
-    if (o.bam) { if (!bam.close()) { if (sort_bam) remove(o.out); if (bam_index) remove(bai_path.c_str()); fprintf(stderr, "Error while writing %s\n", o.out); return 1; } }
+    if (o.bam) { if (!bam.close()) { if (sort_bam) remove(o.out); if (bam_index) remove(bai_path.c_str()); drop_tracks(); fprintf(stderr, "Error while writing %s\n", o.out); return 1; } }
     else fclose(sam);
+    // DART_COVERAGE: the sorted array still lies in HBM; the BAM and its index are complete and closed, and a failure here leaves them as they are
+    if (coverage) {
+        auto now_s = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        const double tc0 = now_s();
+        size_t cov_entries = 0, cov_bytes = 0; float cov_ms = 0.f;
+        for (const auto &t : cov_tracks) {
+            size_t ne = 0, nb = 0; float ms = 0.f;
+            int rc = dg_bam_coverage_finish(roots[0], t.second, cov_exclude, cov_min_mapq, &ne, &nb, nullptr, &ms);
+            std::vector<char> text(nb ? nb : 1);
+            if (!rc) rc = dg_bam_coverage_download(roots[0], nullptr, 0, text.data(), nb);
+            if (rc) { drop_tracks(); fprintf(stderr, "\nError! DART_COVERAGE=%d: %s\n", coverage, dg_last_error(roots[0])); return 1; }
+            FILE *cf = fopen(t.first.c_str(), "wb");
+            const bool ok = cf && fwrite(text.data(), 1, nb, cf) == nb;
+            if (!(cf && fclose(cf) == 0 && ok)) { drop_tracks(); fprintf(stderr, "Error while writing %s\n", t.first.c_str()); return 1; }
+            cov_entries += ne; cov_bytes += nb; cov_ms += ms;
+        }
+        if (getenv("DART_TIMING"))
+            fprintf(stderr, "[dart timing] coverage: %zu tracks, %zu entries, %zu bytes; %.3f s (kernels %.3f s; exclude 0x%x, min mapq %u)\n", cov_tracks.size(), cov_entries, cov_bytes, now_s() - tc0,
+                    cov_ms * 1e-3, cov_exclude, cov_min_mapq);
+    }
     // DART_DEVICE_SJ: the clones' tables into their root's, further roots' into the first (downloaded entries, counted again there), then the table is sorted,
     // mapped to chromosomes and printed on the device: the text is junctions.tab
     std::string sj_text; size_t sj_entries = 0, sj_lines = 0; float sj_finish_ms = 0.f;

@@ -38,6 +38,8 @@ REPORT_C = np.dtype([("pos", "<i4"), ("aln_score", "<u2"), ("flag", "<u2"), ("pa
 CIGAR_FULL_MATCH = 255
 SJ_ENTRY = np.dtype([("g1", "<i8"), ("g2", "<i8"), ("count", "<u4"), ("chr", "<u4")])      # dg_sj_entry
 SJ_ENTRIES_ONLY = 1
+COV_ENTRY = np.dtype([("chr", "<u4"), ("start", "<u4"), ("end", "<u4"), ("depth", "<u4")])      # dg_cov_entry
+COV_ENTRIES_ONLY, COV_STRAND_PLUS, COV_STRAND_MINUS = 1, 2, 4
 SJ_NO_CHR = 0xFFFFFFFF
 assert READ_OUT.itemsize == 36 and REPORT_OUT.itemsize == 40 and SJ_OUT.itemsize == 24 and READ_C.itemsize == 12 and REPORT_C.itemsize == 16
 
@@ -306,6 +308,12 @@ def _load_lib():
         lib.dg_bam_index_download.argtypes = [vp, vp, C.c_size_t]
         lib.dg_bam_index_device.argtypes = [vp, vp, vp]
         lib.dg_bam_index_granules.argtypes = [vp]
+    if hasattr(lib, "dg_bam_coverage_finish"):               # (likewise: the coverage track of the sorted array)
+        lib.dg_bam_coverage_finish.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+        lib.dg_bam_coverage_download.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
+        lib.dg_bam_coverage_device.argtypes = [vp, vp, vp]
+        lib.dg_bam_coverage_device_ms.argtypes = [vp, vp, vp]
+        lib.dg_bam_coverage_granules.argtypes = [vp]
     lib.dg_last_counters.argtypes = [vp, vp, C.c_int]
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
@@ -734,6 +742,29 @@ class DartGPU:
         out = np.zeros(max(int(nb.value), 1), np.uint8)
         self._chk(self.lib.dg_bam_index_download(self.ctx, out.ctypes.data, int(nb.value)), "dg_bam_index_download")
         return out[:int(nb.value)].tobytes()
+
+    # ---- the coverage track of the sorted array (dg_bam_coverage_*): the bedGraph, built in HBM behind bam_sort_finish ----
+    def bam_coverage_granules(self):
+        """(records / events / entries per workgroup, events per tile of the sorter) (dg_bam_coverage_granules)"""
+        g = (C.c_int * 2)()
+        self._chk(self.lib.dg_bam_coverage_granules(g), "dg_bam_coverage_granules")
+        return int(g[0]), int(g[1])
+
+    def bam_coverage_finish(self, exclude: int = 0x704, min_mapq: int = 0, strand=None, entries_only: bool = False):
+        """the coverage track of the sorted array (dg_bam_coverage_finish + dg_bam_coverage_download) -> (COV_ENTRY array, the bedGraph's bytes); strand: None,
+        "+" or "-" (a second mate counts for the opposite strand).  self.bam_coverage_stats = (records counted, blocks, breakpoints, entries, covered bases,
+        aligned bases, largest depth), self.bam_coverage_device_ms = the kernels' device time, self.bam_coverage_device_ms_split = (counting walk, emitting
+        walk, event sort, scans and compaction, entries and text), self.bam_coverage_passes = the sorter's passes"""
+        flags = (COV_ENTRIES_ONLY if entries_only else 0) | {None: 0, "+": COV_STRAND_PLUS, "-": COV_STRAND_MINUS}[strand]
+        ne = C.c_size_t(0); nb = C.c_size_t(0); ms = C.c_float(0); st = (C.c_uint64 * 7)()
+        self._chk(self.lib.dg_bam_coverage_finish(self.ctx, flags, int(exclude), int(min_mapq), C.byref(ne), C.byref(nb), st, C.byref(ms)), "dg_bam_coverage_finish")
+        self.bam_coverage_stats, self.bam_coverage_device_ms = tuple(int(x) for x in st), float(ms.value)
+        split = (C.c_float * 5)(); passes = C.c_int(0)
+        self._chk(self.lib.dg_bam_coverage_device_ms(self.ctx, split, C.byref(passes)), "dg_bam_coverage_device_ms")
+        self.bam_coverage_device_ms_split, self.bam_coverage_passes = tuple(float(x) for x in split), int(passes.value)
+        ent = np.zeros(max(int(ne.value), 1), COV_ENTRY); text = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_bam_coverage_download(self.ctx, ent.ctypes.data, int(ne.value), text.ctypes.data, int(nb.value)), "dg_bam_coverage_download")
+        return ent[:int(ne.value)], text[:int(nb.value)].tobytes()
 
     def wait_index(self):
         self._chk(self.lib.dg_index_wait(self.ctx), "dg_index_wait")

@@ -482,6 +482,56 @@ int dg_bam_index_download(dg_ctx *, void *out, size_t cap);
 int dg_bam_index_device(dg_ctx *, void **ptr, size_t *n_bytes);
 int dg_bam_index_granules(int out[2]);
 
+/* ---- the coverage track of the sorted array, built on the device (dart_amd/csrc/dg_coverage.h): the bedGraph a genome browser shows, as a by-product beside
+ * the sort.  The reference has no such output: an opt-in extension (what `bedtools genomecov -bg -split` or `samtools depth` would compute from the file).
+ * THE DEFINITION -- modelled on `bedtools genomecov -bg -split` (blocks, 0-based half-open intervals, zero depth not printed) with the default filter of
+ * `samtools depth` (FLAG 0x704 skipped); no such tool exists where this library is built and tested, so this text, not a run of one, is what the tests pin.
+ * Input: the sorted array of dg_bam_sort_finish with no store call behind it.  The call neither needs nor disturbs dg_bam_sort_compress or
+ * dg_bam_index_finish and may come before, between or after them.
+ * Per record, fields read byte by byte: refID int32 at byte 4, pos int32 at 8, l_read_name u8 at 12, mapq u8 at 13, n_cigar_op u16 at 16, flag u16 at 18, the
+ * CIGAR ops (u32 little endian, len << 4 | op) from byte 36 + l_read_name.  No read ever passes the record's block_size or the array's end.
+ *     counted  all of: 0 <= refID < n_chr; pos >= 0; flag & 4 clear; n_cigar_op > 0; (flag & exclude_flags) == 0; mapq >= min_mapq; the strand selection, if
+ *              any, passes; the CIGAR lies inside the record (36 + l_read_name + 4 n_cigar_op <= 4 + block_size; dg_bam_sort_add refuses any other record)
+ *     strand   s = (flag >> 4 & 1) ^ (flag >> 7 & 1): a second mate counts for the opposite strand.  DG_COV_STRAND_PLUS keeps s == 0, DG_COV_STRAND_MINUS
+ *              s == 1; both set, or neither: every record
+ *     blocks   walk with p = pos: op 0, 7, 8 (M, =, X) of length L > 0 is a block [p, p + L), then p += L; op 2, 3 (D, N) is p += L and no block; every other
+ *              op changes nothing.  Mates that overlap both count.
+ *     range    a block end above 2^32 - 1 on a counted record: DG_ERR_RANGE, the text names the record's index; no track is left behind
+ *     Positions are not clamped to the chromosome's length (the BAI does not clamp either; the formatter never writes such a record).
+ * Depth: every block gives two events, (refID, start, +1) and (refID, end, -1), ordered by refID << 32 | position.  The deltas of equal keys are summed; keys
+ * whose sum is 0 are dropped (a read ending where another begins is no breakpoint); the running sum over what remains is the depth from that position to the
+ * next.  Every block opens and closes on one reference, so the running sum is 0 at each reference's end.
+ * Entries: one dg_cov_entry for every breakpoint with depth > 0, end = the next breakpoint's position; ascending (chr, start); neighbours that touch always
+ * differ in depth; a chromosome without coverage has none.  Text: per entry "name\tstart\tend\tdepth\n", decimal, no header line, names of dg_set_chr_names.
+ * The result is a function of the record set: the same records give the same bytes whatever their order, the grid, the batch split, the ordinals, the
+ * contexts used or the store's growth history.
+ *   dg_bam_coverage_finish    flags: DG_COV_ENTRIES_ONLY (no text; the chromosome names are not needed), DG_COV_STRAND_PLUS, DG_COV_STRAND_MINUS; any other
+ *                             bit, or no valid sorted array (the text names dg_bam_sort_finish), or text without chromosome names: DG_ERR_ARG.
+ *                             exclude_flags: samtools depth's default is 0x704; min_mapq: 0 counts every record.  stats (may be NULL): [0] records counted,
+ *                             [1] blocks, [2] breakpoints, [3] entries, [4] covered bases, the sum of end - start, [5] aligned bases, the sum of the blocks'
+ *                             lengths (the call checks that it equals the sum of depth x (end - start)), [6] the largest depth.  *device_ms (may be NULL):
+ *                             device time of the kernels, a measurement.  More events than the sorter takes (2^32 - 1, less a tile): DG_ERR_CAPACITY, the count in the text.  The call
+ *                             enqueues on the context's stream and waits three times: for the number of events, for the numbers of breakpoints and entries,
+ *                             and for the text's size.  It uses buffers of its own, never the sorter's (they hold the records' places, which the index
+ *                             needs): 4 bytes per record, 40 per event (two per block) and the sorter's histograms, 12 per breakpoint, 24 per entry and its line; a failed
+ *                             allocation gives DG_ERR_CAPACITY, the text names the need.  An empty store gives 0 entries and 0 bytes.  Every failure leaves
+ *                             the context, the store, the sorted array, the recorded block sizes and a finished index usable; the call may be repeated with
+ *                             other filters.  dg_destroy frees the buffers.
+ *   dg_bam_coverage_download  copies entries and / or text out (either pointer may be NULL); DG_ERR_CAPACITY, nothing written, when a capacity is too small
+ *   dg_bam_coverage_device    entries and text in HBM (NULL when there are none), valid until the next store or coverage call on the context
+ *   dg_bam_coverage_device_ms the last finish's device time by stage: [0] the counting walk, [1] the emitting walk, [2] the event sort, [3] the depth and
+ *                             breakpoint scans with the compaction, [4] entries and text; *n_passes (may be NULL): the sorter's passes
+ *   dg_bam_coverage_granules  [0] records / events / entries per workgroup, [1] the sorter's tile (events)                                                  */
+#define DG_COV_ENTRIES_ONLY 1u
+#define DG_COV_STRAND_PLUS  2u
+#define DG_COV_STRAND_MINUS 4u
+typedef struct { uint32_t chr, start, end, depth; } dg_cov_entry;     /* 16 bytes */
+int dg_bam_coverage_finish(dg_ctx *, uint32_t flags, uint32_t exclude_flags, uint32_t min_mapq, size_t *n_entries, size_t *n_bytes, uint64_t stats[7], float *device_ms);
+int dg_bam_coverage_download(dg_ctx *, dg_cov_entry *entries, size_t cap_entries, char *text, size_t cap_text);
+int dg_bam_coverage_device(dg_ctx *, void **entries, void **text);
+int dg_bam_coverage_device_ms(dg_ctx *, float ms[5], int *n_passes);
+int dg_bam_coverage_granules(int out[2]);
+
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
 int dg_last_timings(dg_ctx *, const char **names, float *ms, int cap);
