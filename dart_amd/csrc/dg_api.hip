@@ -19,6 +19,7 @@
 #include "dg_bamsort.h"
 #include "dg_bamidx.h"
 #include "dg_coverage.h"
+#include "dg_genecount.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -108,6 +109,8 @@ struct IndexShared {
     int device = 0;
     // chromosome names for the SAM text (dg_set_chr_names): with the index, so every clone prints them
     uint32_t *d_chr_name_off = nullptr; char *d_chr_names = nullptr; bool chr_names_set = false; uint64_t chr_names_gen = 0; uint32_t chr_name_max = 0;
+    // the gene annotation's segment table (dg_gene_set_annotation, dg_genecount.h): with the index, so every clone counts with it; gc_gen: 0 = none
+    uint32_t *d_gc_chr_first = nullptr, *d_gc_seg_start = nullptr, *d_gc_seg_lab = nullptr; uint32_t gc_n_genes = 0; size_t gc_n_seg = 0; uint64_t gc_gen = 0;
 };
 
 struct dg_ctx {
@@ -217,6 +220,11 @@ struct dg_ctx {
     unsigned long long *d_cv_stat = nullptr, *h_cv_stat = nullptr;        // CV_ST_* words: device / page-locked copy
     hipEvent_t ev_cv[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // around the kernels between the waits
     bool cv_valid = false; size_t cv_n_entries = 0, cv_bytes = 0; float cv_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f}; int cv_passes = 0;
+    // the gene table (dg_genecount.h): resident across batches, (4 + n_genes) x 3 words, counted under annotation generation gc_gen; the per-workgroup lines of
+    // the N_* rows; host counts and host records on their way in
+    unsigned long long *gc_counts = nullptr; size_t gc_rows = 0; uint64_t gc_gen = 0; bool gc_nonempty = false, gc_batch_counted = false, gc_timed = false;
+    DBuf<unsigned long long> gc_wg, gc_in; DBuf<dg_read_out> gc_in_reads; DBuf<dg_report_out> gc_in_rep; DBuf<uint32_t> gc_in_cig;
+    hipEvent_t ev_gc[3] = {nullptr, nullptr, nullptr};                     // [0], [1]: device time of the last count; [2]: the source stream's place for dg_gene_merge
     size_t env_bamsort_first_cap = 0;  // DG_BAMSORT_FIRST_CAP: test hook, the first size of the store in bytes (forces growth)
     size_t env_bam_first_cap = 0;      // DG_BAM_FIRST_CAP: test hook, the first size of the record buffer in bytes
     size_t env_sam_first_cap = 0;      // DG_SAM_TEXT_FIRST_CAP: test hook, the first size of the text buffer in bytes (forces the "text outgrew the guess" path)
@@ -656,6 +664,7 @@ extern "C" void dg_destroy(dg_ctx *c)
         if (sh->d_sa_dense) (void)hipFree(sh->d_sa_dense);
         if (sh->d_chr_name_off) (void)hipFree(sh->d_chr_name_off);
         if (sh->d_chr_names) (void)hipFree(sh->d_chr_names);
+        for (void *p : {(void *)sh->d_gc_chr_first, (void *)sh->d_gc_seg_start, (void *)sh->d_gc_seg_lab}) if (p) (void)hipFree(p);
         delete sh; c->shared_ix = nullptr;
     }
     void *ptrs[] = { c->d_bwt, c->d_sa, c->d_pac, c->d_lockey, c->d_locchr, c->d_chroff };
@@ -698,6 +707,9 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->d_cv_stat) (void)hipFree(c->d_cv_stat);
     if (c->h_cv_stat) (void)hipHostFree(c->h_cv_stat);
     for (hipEvent_t e : c->ev_cv) if (e) (void)hipEventDestroy(e);
+    if (c->gc_counts) (void)hipFree(c->gc_counts);
+    c->gc_wg.release(); c->gc_in.release(); c->gc_in_reads.release(); c->gc_in_rep.release(); c->gc_in_cig.release();
+    for (hipEvent_t e : c->ev_gc) if (e) (void)hipEventDestroy(e);
     if (c->d_bs_stat) (void)hipFree(c->d_bs_stat);
     if (c->h_bs_stat) (void)hipHostFree(c->h_bs_stat);
     for (hipEvent_t e : c->ev_bs) if (e) (void)hipEventDestroy(e);
@@ -1144,7 +1156,7 @@ static int enqueue_upload(dg_ctx *c, int n_reads, const uint32_t *seq_off, const
         mx = rlen[i] > mx ? rlen[i] : mx;
     }
     if (mx > DG_MAX_RLEN) { snprintf(c->err, 512, "a read is longer than DG_MAX_RLEN (%d)", DG_MAX_RLEN); return DG_ERR_ARG; }
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->gc_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
     c->no_batch = false; c->inf_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64));     /* the kernels read up to 24 bytes at a read position in one go */
     HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
@@ -1207,7 +1219,7 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
     if (mx > DG_MAX_RLEN || mx > 16 * W2 || (size_t)n_reads * 16 * W2 > 0xFFFFFFF0ull) { snprintf(c->err, 512, "packed batch: read length %d does not fit %d words (or exceeds DG_MAX_RLEN / 2^32 bases)", mx, W2); return DG_ERR_ARG; }
     if (n_reads && (mx + 15) / 16 != W2) { snprintf(c->err, 512, "packed batch: words_per_read must be ceil(longest read / 16) = %d", (mx + 15) / 16); return DG_ERR_ARG; }
     const size_t nw = (size_t)n_reads * W2, bytes = nw * 16;
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->gc_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
     c->no_batch = false; c->inf_valid = false;
     HIPCHK(c->seq.ensure(bytes + 64)); HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     HIPCHK(c->enc.ensure(2 * nw + 16)); HIPCHK(c->packed_in.ensure(nw + 1)); HIPCHK(c->nlist_in.ensure(n_n + 1));
@@ -1325,7 +1337,7 @@ static int fq_finish(dg_ctx *c, const char *fn, int max_reads, int *n_reads_out,
 // whatever happens in an upload of FASTQ text, the context holds no batch until the call has succeeded
 static void fq_forget_batch(dg_ctx *c)
 {
-    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
+    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->gc_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
     c->fq_hdr_bytes = c->fq_qual_bytes = 0; c->fq_ms = 0.f;
     c->no_batch = false; c->inf_valid = false; c->fq_tail_valid = false; c->fq_tail_n[0] = c->fq_tail_n[1] = 0;
 }
@@ -1971,7 +1983,7 @@ extern "C" int dg_batch_run(dg_ctx *c, size_t used[3])
     memset(c->counters, 0, sizeof c->counters);
     if (used) used[0] = used[1] = used[2] = 0;
     c->n_t = 0;
-    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sj_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false;
+    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sj_batch_counted = false; c->gc_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false;
     if (c->n_reads == 0) { c->batch_done = true; return DG_OK; }
     c->attempt_no = 0;
     int rc = enqueue_run(c);
@@ -2087,13 +2099,14 @@ extern "C" int dg_map_batch_compact(dg_ctx *c, int n_reads, const uint32_t *seq_
 static int ensure_full_records(dg_ctx *c)
 {
     if (c->full_valid || c->n_reads == 0) return DG_OK;
-    const bool keep = c->want_full, counted = c->sj_batch_counted, stored = c->bam_rec_stored;
+    const bool keep = c->want_full, counted = c->sj_batch_counted, stored = c->bam_rec_stored, genes = c->gc_batch_counted;
     c->want_full = true;
     size_t used[3];
     const int rc = dg_batch_run(c, used);
     c->want_full = keep;
     c->sj_batch_counted = counted;      // (the same batch, mapped again: its tuples are in the junction table already if they were before)
     c->bam_rec_stored = stored;         // (and its BAM records in the sorted store)
+    c->gc_batch_counted = genes;        // (and its units in the gene table)
     return rc;
 }
 
@@ -3308,6 +3321,219 @@ extern "C" int dg_bam_index_device(dg_ctx *c, void **ptr, size_t *n_bytes)
     if (!c || !ptr || !n_bytes) return DG_ERR_ARG;
     if (!c->bi_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_index_device: no index (dg_bam_index_finish first, and no store call behind it)"); return DG_ERR_ARG; }
     *ptr = c->bi_out.p; *n_bytes = c->bi_bytes;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// gene-level read counts (dg_genecount.h): the annotation's segment table lives with the index, a table of counts with every context
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_gene_granules(int out[2])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = GC_THREADS; out[1] = GC_WAVE;
+    return DG_OK;
+}
+
+extern "C" int dg_gene_set_annotation(dg_ctx *c, const dg_gene_annot *a, size_t *n_segments)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_segments) *n_segments = 0;
+    IndexShared *sh = c->shared_ix;
+    if (!sh || !a) { snprintf(c->err, 512, "dg_gene_set_annotation: no annotation (or a context without an index)"); return DG_ERR_ARG; }
+    std::vector<uint32_t> chr_first, seg_start, seg_lab;
+    char why[400];
+    if (!gc_flatten(c->ix.n_chr, a->n_genes, a->n_exons, a->exons, chr_first, seg_start, seg_lab, why, sizeof why)) { snprintf(c->err, 512, "dg_gene_set_annotation: %s", why); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(sh->mu);
+    uint32_t *d[3] = {nullptr, nullptr, nullptr};
+    const std::vector<uint32_t> *src[3] = {&chr_first, &seg_start, &seg_lab};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 3 && e == hipSuccess; k++) {
+        e = hipMalloc((void **)&d[k], (src[k]->size() + 1) * 4);
+        if (e == hipSuccess && !src[k]->empty()) e = hipMemcpy(d[k], src[k]->data(), src[k]->size() * 4, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { for (uint32_t *p : d) if (p) (void)hipFree(p); return fail(c, DG_ERR_HIP, "the gene annotation's segment table", e); }
+    // A count of any context of this index reads the three pointers and enqueues its kernels under sh->mu, so under the lock every kernel that may read the
+    // old table is already in a stream: the device is waited for, then it is freed (as dg_set_chr_names does).
+    if (sh->gc_gen) { (void)hipDeviceSynchronize(); (void)hipFree(sh->d_gc_chr_first); (void)hipFree(sh->d_gc_seg_start); (void)hipFree(sh->d_gc_seg_lab); }
+    sh->d_gc_chr_first = d[0]; sh->d_gc_seg_start = d[1]; sh->d_gc_seg_lab = d[2];
+    sh->gc_n_genes = a->n_genes; sh->gc_n_seg = seg_start.size(); sh->gc_gen++;
+    if (n_segments) *n_segments = seg_start.size();
+    return DG_OK;
+}
+
+// the context's table for the current annotation: made on first use; an empty one of another generation is replaced, a filled one is the caller's to reset
+static int gc_ready(dg_ctx *c, const char *fn, bool fresh = false)
+{
+    IndexShared *sh = c->shared_ix;
+    uint64_t gen = 0; size_t rows = 0;
+    if (sh) { std::lock_guard<std::mutex> lk(sh->mu); gen = sh->gc_gen; rows = 4 + (size_t)sh->gc_n_genes; }
+    if (!gen) { snprintf(c->err, 512, "%s: no gene annotation (dg_gene_set_annotation first)", fn); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    if (!c->ev_gc[0]) for (hipEvent_t &e : c->ev_gc) HIPCHK(hipEventCreate(&e));
+    if (c->gc_counts && c->gc_gen == gen && !fresh) return DG_OK;
+    if (c->gc_counts && c->gc_gen != gen && c->gc_nonempty && !fresh) {
+        snprintf(c->err, 512, "%s: the table holds counts of annotation generation %llu, the annotation is generation %llu now (dg_gene_reset first)", fn, (unsigned long long)c->gc_gen, (unsigned long long)gen);
+        return DG_ERR_ARG;
+    }
+    if (!c->gc_counts || c->gc_rows != rows) {
+        unsigned long long *t = nullptr;
+        HIPCHK(hipMalloc((void **)&t, rows * 3 * 8));
+        if (c->gc_counts) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->gc_counts); }
+        c->gc_counts = t; c->gc_rows = rows;
+    }
+    HIPCHK(hipMemsetAsync(c->gc_counts, 0, c->gc_rows * 3 * 8, c->stream));
+    c->gc_gen = gen; c->gc_nonempty = false;
+    return DG_OK;
+}
+
+// k_gc_count and k_gc_top over the records b holds in HBM, behind whatever the stream holds
+static int gc_count_device(dg_ctx *c, GcBatch b, const char *fn)
+{
+    IndexShared *sh = c->shared_ix;
+    const unsigned long long n_units = gc_units(b.n_reads, b.n_pair_mode);
+    const unsigned long long n_wg = (n_units + GC_THREADS - 1) / GC_THREADS;
+    if (!n_units) return DG_OK;
+    if (n_wg > 0x7FFFFFFFull) { snprintf(c->err, 512, "%s: %llu units are more than one call takes", fn, n_units); return DG_ERR_ARG; }
+    HIPCHK(c->gc_wg.ensure((size_t)n_wg * 12));
+    std::lock_guard<std::mutex> lk(sh->mu);          // (dg_gene_set_annotation replaces the table under the same lock and waits for the device before it frees the old one)
+    if (sh->gc_gen != c->gc_gen) { snprintf(c->err, 512, "%s: the annotation was replaced while the call was being prepared", fn); return DG_ERR_ARG; }
+    const GcTable t{sh->d_gc_chr_first, sh->d_gc_seg_start, sh->d_gc_seg_lab, c->ix.n_chr};
+    HIPCHK(hipEventRecord(c->ev_gc[0], c->stream));
+    k_gc_count<<<(unsigned)n_wg, GC_THREADS, 0, c->stream>>>(b, t, n_units, c->gc_counts, (unsigned long long)c->gc_rows, c->gc_wg.p);
+    k_gc_top<<<1, 256, 0, c->stream>>>(c->gc_wg.p, n_wg, c->gc_counts);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_gc[1], c->stream));
+    c->gc_timed = true; c->gc_nonempty = true;
+    return DG_OK;
+}
+
+static int gc_pair_mode_ok(dg_ctx *c, const char *fn, int n_pair_mode, int n)
+{
+    if (n_pair_mode < 0 || (n_pair_mode & 1) || n_pair_mode > n) { snprintf(c->err, 512, "%s: n_pair_mode %d must be even and at most the batch's %d reads", fn, n_pair_mode, n); return DG_ERR_ARG; }
+    return DG_OK;
+}
+
+extern "C" int dg_batch_accumulate_genes(dg_ctx *c, int n_pair_mode, uint32_t min_mapq, size_t *n_units)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_batch_accumulate_genes";
+    if (n_units) *n_units = 0;
+    { IndexShared *sh = c->shared_ix; uint64_t gen = 0; if (sh) { std::lock_guard<std::mutex> lk(sh->mu); gen = sh->gc_gen; }
+      if (!gen) { snprintf(c->err, 512, "%s: no gene annotation (dg_gene_set_annotation first)", fn); return DG_ERR_ARG; } }
+    if (!c->batch_done) { snprintf(c->err, 512, "%s: the context has no finished batch (upload and run one first)", fn); return DG_ERR_ARG; }
+    { const int rc = gc_pair_mode_ok(c, fn, n_pair_mode, c->n_reads); if (rc) return rc; }
+    if (c->n_reads && !c->full_valid) { snprintf(c->err, 512, "%s: the last batch has no full records (it was mapped through dg_map_batch_compact)", fn); return DG_ERR_ARG; }
+    if (c->gc_batch_counted) { snprintf(c->err, 512, "%s: the units of this batch are in the table already (a batch is counted once)", fn); return DG_ERR_ARG; }
+    { const int rc = gc_ready(c, fn); if (rc) return rc; }
+    if (c->n_reads) {
+        const GcBatch b{c->reads_out.p, c->reports.p, c->cigfinal.p, (unsigned long long)c->used[0], (unsigned long long)c->used[1], c->n_reads, n_pair_mode, min_mapq};
+        const int rc = gc_count_device(c, b, fn);
+        if (rc) return rc;
+    }
+    c->gc_batch_counted = true;
+    if (n_units) *n_units = (size_t)gc_units(c->n_reads, n_pair_mode);
+    return DG_OK;
+}
+
+extern "C" int dg_gene_count_records(dg_ctx *c, int n_reads, int n_pair_mode, uint32_t min_mapq, const dg_read_out *reads, const dg_report_out *reports, size_t n_reports,
+                                     const uint32_t *cigar, size_t n_ops, size_t *n_units)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_gene_count_records";
+    if (n_units) *n_units = 0;
+    if (n_reads < 0 || (n_reads && !reads) || (n_reports && !reports) || (n_ops && !cigar)) { snprintf(c->err, 512, "%s: %d reads, %zu reports and %zu CIGAR ops need their arrays", fn, n_reads, n_reports, n_ops); return DG_ERR_ARG; }
+    { const int rc = gc_pair_mode_ok(c, fn, n_pair_mode, n_reads); if (rc) return rc; }
+    const long long bad = gc_first_bad_read(reads, n_reads, reports, n_reports, n_ops);
+    if (bad >= 0) { snprintf(c->err, 512, "%s: read %lld points outside the arrays (%zu reports, %zu CIGAR ops), or its best report is none of its own", fn, bad, n_reports, n_ops); return DG_ERR_ARG; }
+    { const int rc = gc_ready(c, fn); if (rc) return rc; }
+    if (!n_reads) return DG_OK;
+    HIPCHK(c->gc_in_reads.ensure((size_t)n_reads)); HIPCHK(c->gc_in_rep.ensure(n_reports + 1)); HIPCHK(c->gc_in_cig.ensure(n_ops + 1));
+    HIPCHK(hipMemcpyAsync(c->gc_in_reads.p, reads, (size_t)n_reads * sizeof(dg_read_out), hipMemcpyHostToDevice, c->stream));
+    if (n_reports) HIPCHK(hipMemcpyAsync(c->gc_in_rep.p, reports, n_reports * sizeof(dg_report_out), hipMemcpyHostToDevice, c->stream));
+    if (n_ops) HIPCHK(hipMemcpyAsync(c->gc_in_cig.p, cigar, n_ops * 4, hipMemcpyHostToDevice, c->stream));
+    const GcBatch b{c->gc_in_reads.p, c->gc_in_rep.p, c->gc_in_cig.p, (unsigned long long)n_reports, (unsigned long long)n_ops, n_reads, n_pair_mode, min_mapq};
+    { const int rc = gc_count_device(c, b, fn); if (rc) return rc; }
+    HIPCHK(wait_stream(c));                          // (the caller's arrays are free again, and the staging buffers may take the next call's)
+    if (n_units) *n_units = (size_t)gc_units(n_reads, n_pair_mode);
+    return DG_OK;
+}
+
+extern "C" int dg_gene_add(dg_ctx *c, const uint64_t *counts, size_t n_rows)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_gene_add";
+    { const int rc = gc_ready(c, fn); if (rc) return rc; }
+    if (!counts || n_rows != c->gc_rows) { snprintf(c->err, 512, "%s: %zu rows, the table has %zu (4 + the annotation's genes)", fn, n_rows, c->gc_rows); return DG_ERR_ARG; }
+    const size_t n = n_rows * 3;
+    HIPCHK(c->gc_in.ensure(n));
+    HIPCHK(hipMemcpyAsync(c->gc_in.p, counts, n * 8, hipMemcpyHostToDevice, c->stream));
+    k_gc_add<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->gc_counts, c->gc_in.p, (unsigned long long)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(wait_stream(c));
+    c->gc_nonempty = true;
+    return DG_OK;
+}
+
+extern "C" int dg_gene_merge(dg_ctx *dst, dg_ctx *src)
+{
+    dg_ctx *c = dst;
+    if (!dst || !src) return DG_ERR_ARG;
+    const char *fn = "dg_gene_merge";
+    if (dst == src || dst->device != src->device) { snprintf(c->err, 512, "%s: the two contexts must differ and be on one device", fn); return DG_ERR_ARG; }
+    if (!src->gc_counts || !src->gc_nonempty) return DG_OK;
+    { const int rc = gc_ready(dst, fn); if (rc) return rc; }
+    if (dst->gc_gen != src->gc_gen || dst->gc_rows != src->gc_rows) {
+        snprintf(c->err, 512, "%s: the tables were counted under different annotation generations (%llu and %llu)", fn, (unsigned long long)dst->gc_gen, (unsigned long long)src->gc_gen);
+        return DG_ERR_ARG;
+    }
+    // behind everything the source's stream holds; the source's table is emptied on the destination's stream, which the call waits for
+    HIPCHK(hipEventRecord(src->ev_gc[2], src->stream));
+    HIPCHK(hipStreamWaitEvent(dst->stream, src->ev_gc[2], 0));
+    const size_t n = dst->gc_rows * 3;
+    k_gc_add<<<(unsigned)((n + 255) / 256), 256, 0, dst->stream>>>(dst->gc_counts, src->gc_counts, (unsigned long long)n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(src->gc_counts, 0, n * 8, dst->stream));
+    HIPCHK(wait_stream(dst));
+    dst->gc_nonempty = true; src->gc_nonempty = false;
+    return DG_OK;
+}
+
+extern "C" int dg_gene_reset(dg_ctx *c)
+{
+    if (!c) return DG_ERR_ARG;
+    { const int rc = gc_ready(c, "dg_gene_reset", true); if (rc) return rc; }
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_gene_download(dg_ctx *c, uint64_t *counts, size_t cap_rows)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_gene_download";
+    if (!c->gc_counts) { const int rc = gc_ready(c, fn); if (rc) return rc; }
+    if (!counts || cap_rows < c->gc_rows) { snprintf(c->err, 512, "%s: output capacity too small: %zu rows are needed", fn, c->gc_rows); return DG_ERR_CAPACITY; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(counts, c->gc_counts, c->gc_rows * 3 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_gene_device(dg_ctx *c, void **counts)
+{
+    if (!c || !counts) return DG_ERR_ARG;
+    if (!c->gc_counts) { const int rc = gc_ready(c, "dg_gene_device"); if (rc) return rc; }
+    *counts = c->gc_counts;
+    return DG_OK;
+}
+
+extern "C" int dg_gene_device_ms(dg_ctx *c, float *ms)
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    *ms = 0.f;
+    if (!c->gc_timed) return DG_OK;
+    HIPCHK(hipEventSynchronize(c->ev_gc[1]));
+    HIPCHK(hipEventElapsedTime(ms, c->ev_gc[0], c->ev_gc[1]));
     return DG_OK;
 }
 

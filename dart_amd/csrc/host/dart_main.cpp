@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "fast_fastq.h"
+#include "gtf.h"
 #include "bam_writer.h"
 #include "index_cmd.h"
 
@@ -691,6 +692,23 @@ int main(int argc, char *argv[])
     fprintf(stdout, "Load the genome index files...");
     if (!load_ann(o.index, ix)) { fprintf(stderr, "\n\nError! Index files are corrupt!\n"); return 0; }
 
+    // DART_GENE_COUNTS=<annotation.gtf>: reads per gene, counted on the device batch by batch (dg_batch_accumulate_genes) from the records in HBM, written as
+    // <out>.genes.tab (STAR's ReadsPerGene.out.tab layout) after the alignments are complete.  Both pipelines, -o and -bo, beside every other switch.
+    // DART_GENE_FEATURE (default exon) picks the GTF lines, DART_GENE_MIN_MAPQ (default 4, the -unique rule mapq > 3) the units that count as unique.
+    // A GTF that cannot be used ends the run here, before a context exists and before any output is begun; no failed run leaves a table, a stale one included.
+    const char *gene_gtf = getenv("DART_GENE_COUNTS") && getenv("DART_GENE_COUNTS")[0] ? getenv("DART_GENE_COUNTS") : nullptr;
+    const std::string genes_path = gene_gtf ? std::string(o.out) + ".genes.tab" : std::string();
+    GtfAnnotation gtf;
+    if (gene_gtf) {
+        remove(genes_path.c_str());
+        const char *feature = getenv("DART_GENE_FEATURE") && getenv("DART_GENE_FEATURE")[0] ? getenv("DART_GENE_FEATURE") : "exon";
+        const std::string gerr = gtf_parse(gene_gtf, ix.names, feature, gtf);
+        if (!gerr.empty()) { fprintf(stderr, "\nError! DART_GENE_COUNTS=%s: %s\n", gene_gtf, gerr.c_str()); return 1; }
+        if (gtf.skipped_seq || gtf.skipped_strand)
+            fprintf(stderr, "DART_GENE_COUNTS: skipped %zu '%s' lines on sequences the index lacks and %zu with a strand other than + or -\n", gtf.skipped_seq, feature, gtf.skipped_strand);
+        g_gene_min_mapq = getenv("DART_GENE_MIN_MAPQ") ? (uint32_t)strtoul(getenv("DART_GENE_MIN_MAPQ"), nullptr, 0) : 4u;
+    }
+
     // The contexts: one root per device (the index files go to its HBM inside dg_init_files, main.cpp:231-235 / bwt_index.cpp:147-159), clones
     // for the batches in flight.  The look-up aids are built in the background while the first batches are mapped (DART_SYNC_AIDS=1: before).
     std::vector<dg_ctx *> ctx, roots, clones;
@@ -731,6 +749,16 @@ int main(int argc, char *argv[])
                 ctx.push_back(cl); clones.push_back(cl);
             }
         }
+    }
+    if (gene_gtf) {      // the annotation goes to every root; its clones count with it
+        dg_gene_annot ann; ann.n_genes = (uint32_t)gtf.genes.size(); ann.pad = 0; ann.n_exons = gtf.exons.size(); ann.exons = gtf.exons.data();
+        for (dg_ctx *r : roots) if (dg_gene_set_annotation(r, &ann, nullptr)) {
+            fprintf(stderr, "Error! DART_GENE_COUNTS=%s: %s\n", gene_gtf, dg_last_error(r));
+            for (auto c : clones) dg_destroy(c);
+            for (auto c : roots) dg_destroy(c);
+            return 1;
+        }
+        g_gene_counts = true;
     }
     // DART_DEVICE_SAM=1: SAM text from the device's formatter (dg_batch_format_sam) instead of the host's; -bo keeps the host's (BAM is built from host text)
     const bool device_sam = !o.bam && getenv("DART_DEVICE_SAM") && atoi(getenv("DART_DEVICE_SAM")) != 0;
@@ -907,6 +935,7 @@ int main(int argc, char *argv[])
             }
             b.ro.reset(new dg_read_out[n]); b.n_reads = (size_t)n;
             size_t caps[3] = { (size_t)n * 4 + 1024, (size_t)n * 16 + 4096, (size_t)n + 1024 };
+            bool gene_even_counted = false;    // DART_GENE_COUNTS: likewise, the first part's units
             bool sj_even_counted = false;      // DART_DEVICE_SJ: a batch runs in two parts (pairs, then an odd tail); the first part's tuples are counted once, also when the second part makes the batch run again
             for (int attempt = 0; attempt < 2; attempt++) {
                 b.po.reset(new dg_report_out[caps[0]]); b.cig.reset(new uint32_t[caps[1]]); if (!device_sj) b.sj.reset(new dg_sj_out[caps[2]]);
@@ -916,6 +945,7 @@ int main(int argc, char *argv[])
                 if (device_sam) { b.outs.assign(1, std::string()); b.cts.assign(1, Counters()); b.t_dev = 0; }
                 int rc = n_even ? dg_map_batch(c, n_even, off.data(), rl.data(), flat.data(), b.ro.get(), b.po.get(), b.cig.get(), b.sj.get(), caps, used1) : 0;
                 if (rc == 0 && n_even && device_sj && !sj_even_counted) { rc = sj_accumulate(c); sj_even_counted = rc == 0; }
+                if (rc == 0 && n_even && g_gene_counts && !gene_even_counted) { rc = gene_accumulate(c, pair_end ? n_even : 0); gene_even_counted = rc == 0; }
                 if (rc == 0 && n_even && device_sam) rc = device_text(b, c, 0, n_even, pair_end ? n_even : 0);
                 if (rc == 0 && b.odd) {
                     p.paired = 0; dg_set_params(c, &p);
@@ -923,6 +953,7 @@ int main(int argc, char *argv[])
                     rc = dg_map_batch(c, b.odd, off.data() + n_even, rl.data() + n_even, flat.data(), b.ro.get() + n_even, b.po.get() + used1[0],
                                       b.cig.get() + used1[1], device_sj ? nullptr : b.sj.get() + used1[2], caps2, used2);
                     if (rc == 0 && device_sj) rc = sj_accumulate(c);
+                    if (rc == 0 && g_gene_counts) rc = gene_accumulate(c, 0);
                     if (rc == 0 && device_sam) rc = device_text(b, c, n_even, b.odd, 0);      // (before the offsets below are rebased: the device holds the batch's own)
                     if (rc == DG_ERR_CAPACITY) for (int q = 0; q < 3; q++) used2[q] += used1[q];
                     else {
@@ -1123,6 +1154,32 @@ int main(int argc, char *argv[])
         sj_text.resize(nb);
         if (dg_sj_download(roots[0], nullptr, 0, nb ? &sj_text[0] : nullptr, nb)) return sj_fail(roots[0]);
     }
+    // DART_GENE_COUNTS: the clones' tables into their root's (dg_gene_merge), further roots' into the first (downloaded, folded in with dg_gene_add); the host
+    // prints the table
+    unsigned long long gene_counted = 0;
+    if (g_gene_counts) {
+        auto gene_fail = [&](dg_ctx *c) { fprintf(stderr, "\nError! gene counts: %s\n", dg_last_error(c)); return 1; };
+        const size_t n_rows = 4 + gtf.genes.size();
+        std::vector<uint64_t> tab(n_rows * 3, 0);
+        for (size_t d = 0; d < roots.size(); d++)
+            for (int k = 1; k < inflight_cfg; k++) if (dg_gene_merge(roots[d], ctx[d * (size_t)inflight_cfg + k])) return gene_fail(roots[d]);
+        for (size_t d = 1; d < roots.size(); d++) {
+            if (dg_gene_download(roots[d], tab.data(), n_rows)) return gene_fail(roots[d]);
+            if (dg_gene_add(roots[0], tab.data(), n_rows)) return gene_fail(roots[0]);
+        }
+        if (dg_gene_download(roots[0], tab.data(), n_rows)) return gene_fail(roots[0]);
+        std::string text;
+        static const char *const head[4] = {"N_unmapped", "N_multimapping", "N_noFeature", "N_ambiguous"};
+        for (size_t r = 0; r < n_rows; r++) {
+            text += r < 4 ? std::string(head[r]) : gtf.genes[r - 4];
+            for (int col = 0; col < 3; col++) { text += '\t'; text += std::to_string((unsigned long long)tab[3 * r + col]); }
+            text += '\n';
+            if (r >= 4) gene_counted += tab[3 * r];
+        }
+        FILE *gf = fopen(genes_path.c_str(), "wb");
+        const bool ok = gf && fwrite(text.data(), 1, text.size(), gf) == text.size();
+        if (!(gf && fclose(gf) == 0 && ok)) { remove(genes_path.c_str()); fprintf(stderr, "Error while writing %s\n", genes_path.c_str()); return 1; }
+    }
     for (auto c : clones) dg_destroy(c);
     for (auto c : roots) dg_destroy(c);
 
@@ -1151,6 +1208,8 @@ int main(int argc, char *argv[])
         fprintf(stdout, "\t# of splice junctions = %d (file: %s)\n", nj, o.sj);
         fprintf(stdout, "\tAlignment output: %s\n\n", o.out);
     }
+    if (getenv("DART_TIMING") && g_gene_counts)
+        fprintf(stderr, "[dart genes] table=device units=%llu counted=%llu genes=%zu acc_ms=%.3f min_mapq=%u\n", (unsigned long long)g_gene_units.load(), gene_counted, gtf.genes.size(), g_gene_acc_ns.load() * 1e-6, g_gene_min_mapq);
     if (getenv("DART_TIMING")) {
         if (device_sj) fprintf(stderr, "[dart sj] table=device tuples=%llu entries=%zu accumulate_ms=%.3f finish_ms=%.3f\n", (unsigned long long)g_sj_tuples.load(), sj_entries, g_sj_acc_ns.load() * 1e-6, (double)sj_finish_ms);
         else fprintf(stderr, "[dart sj] table=host tuples=%llu entries=%zu map_s=%.6f\n", (unsigned long long)g_sj_tuples.load(), sjmap.size(), g_sj_map_ns.load() * 1e-9);

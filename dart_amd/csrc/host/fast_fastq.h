@@ -369,6 +369,21 @@ static inline int sj_accumulate(dg_ctx *ctx)
     return rc;
 }
 
+// DART_GENE_COUNTS=<annotation.gtf>: every mapping thread counts its batch's units per gene in its context's table on the GPU (dg_batch_accumulate_genes) right
+// behind the mapping, where sj_accumulate sits: mates are still neighbours there.  The host program merges the tables and prints <out>.genes.tab at the end
+// of the job.  The figures feed its `[dart genes]` line: units counted, time in the accumulate calls.
+static bool g_gene_counts = false;
+static uint32_t g_gene_min_mapq = 4;
+static std::atomic<unsigned long long> g_gene_units{0}, g_gene_acc_ns{0};
+static inline int gene_accumulate(dg_ctx *ctx, int n_pair_mode)
+{
+    const unsigned long long t = sj_now_ns();
+    size_t n = 0;
+    const int rc = dg_batch_accumulate_genes(ctx, n_pair_mode, g_gene_min_mapq, &n);
+    g_gene_acc_ns += sj_now_ns() - t; g_gene_units += n;
+    return rc;
+}
+
 struct FastSlot {                       // one batch travelling through the stages
     size_t first = 0; int n = 0, odd = 0; size_t seqno = 0;
     std::vector<uint32_t> hoff, qoff; char *names_quals = nullptr; size_t nq_cap = 0;      // device formatter: the batch's names and stored qualities, flat
@@ -787,6 +802,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                         slot_reserve(*s, (size_t)n, 0, need);
                     }
                     if (!rc && g_device_sj) rc = sj_accumulate(ctx[w]);
+                    if (!rc && g_gene_counts) rc = gene_accumulate(ctx[w], (pair_end && !s->odd) ? n : 0);
                     if (!rc) rc = dg_batch_download(ctx[w], s->ro, s->po, s->cig, g_device_sj ? nullptr : s->sj, s->caps);
                     s->rc = rc; if (rc) s->err = dg_last_error(ctx[w]);
                 }
@@ -800,6 +816,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                     int rc = dg_map_batch(ctx[w], n, s->soff.data(), s->rl.data(), s->seq, s->ro, s->po, s->cig, g_device_sj ? nullptr : s->sj, s->caps, s->used);
                     if (rc == DG_ERR_CAPACITY && attempt == 0) continue;      // `used` holds the need
                     if (!rc && g_device_sj) rc = sj_accumulate(ctx[w]);       // (a batch that ran short of capacity is mapped again as a new batch and was not counted)
+                    if (!rc && g_gene_counts) rc = gene_accumulate(ctx[w], (pair_end && !s->odd) ? n : 0);
                     s->rc = rc; if (rc) s->err = dg_last_error(ctx[w]);
                     break;
                 }

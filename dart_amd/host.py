@@ -41,6 +41,12 @@ SJ_ENTRIES_ONLY = 1
 COV_ENTRY = np.dtype([("chr", "<u4"), ("start", "<u4"), ("end", "<u4"), ("depth", "<u4")])      # dg_cov_entry
 COV_ENTRIES_ONLY, COV_STRAND_PLUS, COV_STRAND_MINUS = 1, 2, 4
 SJ_NO_CHR = 0xFFFFFFFF
+GENE_EXON = np.dtype([("chr", "<i4"), ("start", "<u4"), ("end", "<u4"), ("strand", "<u4"), ("gene", "<u4")])      # dg_gene_exon
+GENE_NONE, GENE_AMBIG = 0xFFFFFFFF, 0xFFFFFFFE
+
+
+class GeneAnnot(C.Structure):
+    _fields_ = [("n_genes", C.c_uint32), ("pad", C.c_uint32), ("n_exons", C.c_size_t), ("exons", C.c_void_p)]
 assert READ_OUT.itemsize == 36 and REPORT_OUT.itemsize == 40 and SJ_OUT.itemsize == 24 and READ_C.itemsize == 12 and REPORT_C.itemsize == 16
 
 
@@ -314,6 +320,17 @@ def _load_lib():
         lib.dg_bam_coverage_device.argtypes = [vp, vp, vp]
         lib.dg_bam_coverage_device_ms.argtypes = [vp, vp, vp]
         lib.dg_bam_coverage_granules.argtypes = [vp]
+    if hasattr(lib, "dg_gene_set_annotation"):               # (likewise: gene-level read counts)
+        lib.dg_gene_set_annotation.argtypes = [vp, vp, vp]
+        lib.dg_batch_accumulate_genes.argtypes = [vp, C.c_int, C.c_uint32, vp]
+        lib.dg_gene_count_records.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, vp, vp, C.c_size_t, vp, C.c_size_t, vp]
+        lib.dg_gene_add.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_gene_merge.argtypes = [vp, vp]
+        lib.dg_gene_reset.argtypes = [vp]
+        lib.dg_gene_download.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_gene_device.argtypes = [vp, vp]
+        lib.dg_gene_device_ms.argtypes = [vp, vp]
+        lib.dg_gene_granules.argtypes = [vp]
     lib.dg_last_counters.argtypes = [vp, vp, C.c_int]
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
@@ -660,6 +677,66 @@ class DartGPU:
         ent = np.zeros(max(int(ne.value), 1), SJ_ENTRY); text = np.zeros(max(int(nb.value), 1), np.uint8)
         self._chk(self.lib.dg_sj_download(self.ctx, ent.ctypes.data, int(ne.value), text.ctypes.data, int(nb.value)), "dg_sj_download")
         return ent[:int(ne.value)], text[:int(nb.value)].tobytes()
+
+    # ---- gene-level read counts on the device (dg_gene_*): counted per batch from the records in HBM, merged at the end of the job ----
+    def gene_granules(self):
+        """(units per workgroup of the counting kernel, the wave width its combining uses) (dg_gene_granules)"""
+        g = (C.c_int * 2)()
+        self._chk(self.lib.dg_gene_granules(g), "dg_gene_granules")
+        return int(g[0]), int(g[1])
+
+    def gene_set_annotation(self, n_genes: int, exons) -> int:
+        """flattens and uploads the annotation, kept with the index and shared by clones (dg_gene_set_annotation) -> the number of segments;
+        exons: a GENE_EXON array, or any sequence of (chr, start, end, strand, gene) with 0-based half-open coordinates"""
+        if isinstance(exons, np.ndarray) and exons.dtype == GENE_EXON:
+            a = np.ascontiguousarray(exons)
+        else:
+            rows = list(exons)
+            a = np.zeros(len(rows), GENE_EXON)
+            for k, t in enumerate(rows):
+                a[k] = tuple(int(x) for x in t)
+        keep = a if len(a) else np.zeros(1, GENE_EXON)
+        ann = GeneAnnot(int(n_genes), 0, len(a), keep.ctypes.data)
+        n = C.c_size_t(0)
+        self._chk(self.lib.dg_gene_set_annotation(self.ctx, C.byref(ann), C.byref(n)), "dg_gene_set_annotation")
+        self.gene_rows = 4 + int(n_genes)
+        return int(n.value)
+
+    def accumulate_genes(self, n_pair_mode: int, min_mapq: int = 4) -> int:
+        """counts the units of the batch that ran last in the context's table (dg_batch_accumulate_genes) -> the number of units"""
+        n = C.c_size_t(0)
+        self._chk(self.lib.dg_batch_accumulate_genes(self.ctx, int(n_pair_mode), int(min_mapq), C.byref(n)), "dg_batch_accumulate_genes")
+        return int(n.value)
+
+    def gene_count_records(self, reads, reports, cigar, n_pair_mode: int, min_mapq: int = 4) -> int:
+        """counts host records (READ_OUT, REPORT_OUT, CIGAR words) through the same kernel (dg_gene_count_records) -> the number of units"""
+        rd = np.ascontiguousarray(reads, READ_OUT); rp = np.ascontiguousarray(reports, REPORT_OUT); cg = np.ascontiguousarray(cigar, np.uint32)
+        n = C.c_size_t(0)
+        self._chk(self.lib.dg_gene_count_records(self.ctx, len(rd), int(n_pair_mode), int(min_mapq), rd.ctypes.data if len(rd) else None, rp.ctypes.data if len(rp) else None, len(rp),
+                                                 cg.ctypes.data if len(cg) else None, len(cg), C.byref(n)), "dg_gene_count_records")
+        return int(n.value)
+
+    def gene_add(self, counts):
+        """host counts folded in (dg_gene_add): uint64 [4 + n_genes, 3]"""
+        a = np.ascontiguousarray(counts, np.uint64)
+        self._chk(self.lib.dg_gene_add(self.ctx, a.ctypes.data, a.shape[0]), "dg_gene_add")
+
+    def gene_merge(self, src: "DartGPU"):
+        """adds src's table to this context's and leaves src's empty (dg_gene_merge)"""
+        self._chk(self.lib.dg_gene_merge(self.ctx, src.ctx), "dg_gene_merge")
+
+    def gene_reset(self):
+        self._chk(self.lib.dg_gene_reset(self.ctx), "dg_gene_reset")
+
+    def gene_counts(self, n_rows: int | None = None) -> np.ndarray:
+        """the context's table (dg_gene_download) -> uint64 [4 + n_genes, 3]; n_rows: of a table counted under an annotation this object did not set (a clone's)"""
+        rows = int(n_rows if n_rows is not None else getattr(self, "gene_rows", None) or self._parent.gene_rows)
+        out = np.zeros((rows, 3), np.uint64)
+        self._chk(self.lib.dg_gene_download(self.ctx, out.ctypes.data, rows), "dg_gene_download")
+        ms = C.c_float(0)
+        self._chk(self.lib.dg_gene_device_ms(self.ctx, C.byref(ms)), "dg_gene_device_ms")
+        self.gene_device_ms = float(ms.value)
+        return out
 
     # ---- coordinate-sorted BAM on the device (dg_bam_sort_*): every batch's records stay in HBM, one sort at the end of the job ----
     def bam_sort_granules(self):

@@ -151,3 +151,16 @@ def junction_twin(tuples, chr_names, chr_off, chr_len, l_pac: int):
         shown = cnt - (1 << 32) if cnt >= (1 << 31) else cnt
         out.append("%s\t%d\t%d\t%d\n" % (chr_names[c], g1 + 1 - int(chr_off[c]), g2 + 1 - int(chr_off[c]), shown))
     return entries, "".join(out).encode("latin1"), len(out)
+
+
+GENE_ROWS = ("N_unmapped", "N_multimapping", "N_noFeature", "N_ambiguous")
+
+
+def gene_table(names, counts) -> bytes:
+    """The bytes of <out>.genes.tab from the device's gene table (dg_gene_download): STAR's ReadsPerGene.out.tab layout -- the four N_* lines, then one line
+    per gene in the caller's order; columns: unstranded, forward (htseq-count -s yes), reverse.  counts: [4 + len(names)][3]."""
+    assert len(counts) == 4 + len(names)
+    out = []
+    for name, row in zip(list(GENE_ROWS) + [n.decode("latin1") if isinstance(n, bytes) else n for n in names], counts):
+        out.append("%s\t%d\t%d\t%d\n" % (name, int(row[0]), int(row[1]), int(row[2])))
+    return "".join(out).encode("latin1")

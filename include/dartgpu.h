@@ -532,6 +532,68 @@ int dg_bam_coverage_device(dg_ctx *, void **entries, void **text);
 int dg_bam_coverage_device_ms(dg_ctx *, float ms[5], int *n_passes);
 int dg_bam_coverage_granules(int out[2]);
 
+/* ---- gene-level read counts on the device (dart_amd/csrc/dg_genecount.h): a ReadsPerGene table per job ----
+ * Counted per batch, from the records the batch left in HBM (mates 2i and 2i + 1 are still neighbours), in a per-context table that stays in HBM across
+ * batches and is merged at the end of the job, as the junction table is.  Modelled on `htseq-count --mode union` with the layout of STAR's ReadsPerGene.out.tab;
+ * neither tool is run anywhere, so this text is the definition (tests/genecount_inputs.py is its sequential twin):
+ * Annotation: n_genes >= 1 genes and n_exons >= 0 exons (chr, start, end, strand, gene): 0 <= chr < n_chr; start < end <= 2^32 - 1, 0-based half-open on the
+ *   chromosome; strand 0 (+) or 1 (-); 0 <= gene < n_genes.  Anything else is DG_ERR_ARG, the text names the first bad exon.  Exons may arrive in any order, may
+ *   overlap and may repeat.  A gene covers a base on a strand when one of its exons does.  For every base there are three gene sets: `any` (every covering gene),
+ *   `plus` (covering genes whose exon strand is +), `minus` (those whose exon strand is -).  Each set gives a label: NONE (0xFFFFFFFF) for the empty set, the
+ *   gene's index for exactly one gene, AMBIG (0xFFFFFFFE) for two or more.  The library flattens the annotation once, on the host, into a segment table per
+ *   chromosome: ascending breakpoints, per segment the three labels, neighbouring segments with three equal labels merged, the segment behind a chromosome's
+ *   last exon NONE.  The table is uploaded once and kept with the index, shared by its clones, as the chromosome names are.  (Gene names are the caller's: the
+ *   library prints nothing.)
+ * A read's alignment: read k is aligned when reads[k].score > 0 and it has a report j >= best that the SAM formatter would show (aln_score > 0 in pair mode,
+ *   aln_score == score otherwise); its alignment is the first such report, the first SAM line the read prints.
+ * A read's strand: s = (flag >> 4 & 1) ^ (flag >> 7 & 1) of that report (the coverage track's rule: a second mate counts for the opposite strand).
+ * A read's blocks: p = pos - 1 (pos is 1-based); op 0, 7 or 8 of length L > 0 is a block [p, p + L), then p += L; op 2 or 3 moves p and makes no block; every
+ *   other op changes nothing.  A read with pos < 1 or chr outside [0, n_chr) has no blocks.
+ * A unit: reads 2i, 2i + 1 form one unit for 2i + 1 < n_pair_mode (even, at most n_reads, the meaning it has for dg_batch_format_sam); every read from
+ *   n_pair_mode on is a unit of its own.
+ * A unit's outcome, decided in this order: 1. no read of the unit is aligned: N_unmapped.  2. an aligned read of the unit has mapq < min_mapq: N_multimapping
+ *   (DART's MAPQ takes the values 0, 1, 2, 3 and 50; `dart` passes 4, the -unique rule mapq > 3).  3. otherwise, for each of three columns, the labels of every
+ *   segment that every block of every aligned read of the unit touches are combined; a block on a chromosome without segments, or outside them, contributes NONE.
+ *   Column 0 (unstranded) reads `any`; column 1 (forward, htseq-count -s yes) reads `plus` when the read's s == 0 and `minus` otherwise; column 2 (reverse) reads
+ *   the opposite label; each read uses its own s.  Combine: NONE + x = x, g + g = g, g + h = AMBIG for g != h, AMBIG + x = AMBIG.  Result g: the unit counts
+ *   once for gene g in that column (two mates in one gene count once); NONE: N_noFeature of that column; AMBIG: N_ambiguous of that column.  A unit in case 1 or
+ *   2 adds to all three columns of its row.
+ * Counts: uint64_t counts[4 + n_genes][3]; rows 0-3 are N_unmapped, N_multimapping, N_noFeature, N_ambiguous, row 4 + g is gene g.  Every column sums to the
+ *   number of units counted.  The table is a function of the multiset of units: not of their order, the batch split, the grid, the contexts used or the merges.
+ * Text (the host's, STAR's layout): "N_unmapped\t%llu\t%llu\t%llu\n" .. "N_ambiguous..", then "name\tc0\tc1\tc2\n" per gene in the caller's gene order.
+ * Every failure leaves the context and its table usable, with a text in dg_last_error; dg_destroy frees everything.
+ *   dg_gene_set_annotation     flattens, uploads and keeps the table with the index (every clone counts with it); *n_segments (may be NULL): its size.  A second
+ *                              call replaces it after waiting for the device, as dg_set_chr_names does.  Each call gives the annotation a new generation number;
+ *                              a context's table remembers the generation it was counted under
+ *   dg_batch_accumulate_genes  counts the batch that ran last, in one launch sequence on the context's stream behind the batch; *n_units (may be NULL): its
+ *                              units.  DG_ERR_ARG with a text: no annotation; no finished batch; no full records (the batch went through dg_map_batch_compact);
+ *                              n_pair_mode odd or above the batch; a second call on the same batch; a table that holds counts of an older annotation generation
+ *                              (dg_gene_reset first).  A batch of 0 reads adds nothing.  Packed and FASTQ uploads work: no bases are needed
+ *   dg_gene_count_records      the same record layout from host memory through the same kernel (a multi-device host; crafted alignments).  The host walks the
+ *                              records once: rep_off + n_rep > n_reports, best outside [0, n_rep) on a read with score > 0, or cigar_off + n_cigar > n_ops gives
+ *                              DG_ERR_ARG naming the first bad read, and nothing is counted
+ *   dg_gene_add                host counts folded in; n_rows must be 4 + n_genes
+ *   dg_gene_merge              adds src's table to dst's and leaves src's empty; one device, ordered behind both streams; DG_ERR_ARG for dst == src, different
+ *                              devices or different generations
+ *   dg_gene_reset              an empty table of the current annotation's shape and generation
+ *   dg_gene_download           copies the table out, (4 + n_genes) x 3 words; DG_ERR_CAPACITY, nothing written, when cap_rows is too small (the text names the need)
+ *   dg_gene_device             the table in HBM, valid until the next gene call on the context
+ *   dg_gene_device_ms          device time of the last accumulate / count_records, a measurement
+ *   dg_gene_granules           [0] units per workgroup, [1] the wave width the combining uses                                                        */
+typedef struct { int32_t chr; uint32_t start, end, strand, gene; } dg_gene_exon;      /* 20 bytes */
+typedef struct { uint32_t n_genes; uint32_t pad; size_t n_exons; const dg_gene_exon *exons; } dg_gene_annot;
+int dg_gene_set_annotation(dg_ctx *, const dg_gene_annot *, size_t *n_segments);
+int dg_batch_accumulate_genes(dg_ctx *, int n_pair_mode, uint32_t min_mapq, size_t *n_units);
+int dg_gene_count_records(dg_ctx *, int n_reads, int n_pair_mode, uint32_t min_mapq, const dg_read_out *reads, const dg_report_out *reports, size_t n_reports,
+                          const uint32_t *cigar, size_t n_ops, size_t *n_units);
+int dg_gene_add(dg_ctx *, const uint64_t *counts, size_t n_rows);
+int dg_gene_merge(dg_ctx *dst, dg_ctx *src);
+int dg_gene_reset(dg_ctx *);
+int dg_gene_download(dg_ctx *, uint64_t *counts, size_t cap_rows);
+int dg_gene_device(dg_ctx *, void **counts);
+int dg_gene_device_ms(dg_ctx *, float *ms);
+int dg_gene_granules(int out[2]);
+
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
 int dg_last_timings(dg_ctx *, const char **names, float *ms, int cap);
