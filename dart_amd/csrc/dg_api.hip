@@ -19,6 +19,7 @@
 #include "dg_bamsort.h"
 #include "dg_bamidx.h"
 #include "dg_coverage.h"
+#include "dg_markdup.h"
 #include "dg_genecount.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -220,6 +221,14 @@ struct dg_ctx {
     unsigned long long *d_cv_stat = nullptr, *h_cv_stat = nullptr;        // CV_ST_* words: device / page-locked copy
     hipEvent_t ev_cv[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // around the kernels between the waits
     bool cv_valid = false; size_t cv_n_entries = 0, cv_bytes = 0; float cv_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f}; int cv_passes = 0;
+    // duplicate marking of the sorted array (dg_markdup.h): buffers of its own: per record the end key, the name's hash, the score, the partner and two
+    // offsets; the sorter's pairs of buffers for candidates (then pairs) and for ends; the per-workgroup sums and values
+    DBuf<uint64_t> md_E, md_h, md_tile, md_junk, md_part, md_tile_last, md_k[2], md_ek[2]; DBuf<int64_t> md_v[2], md_ev[2];
+    DBuf<uint32_t> md_score, md_mate, md_cand_off, md_cnt_off, md_tile_prev, md_hist, md_sums;
+    unsigned long long *d_md_stat = nullptr, *h_md_stat = nullptr;        // MD_ST_* words: device / page-locked copy
+    hipEvent_t ev_md[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    float md_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; int md_passes = 0;
+    int env_markdup_hash_bits = MD_HASH_BITS;   // DG_MARKDUP_HASH_BITS: test hook, the bits of a name's hash that are kept (makes collisions and crowded runs reachable)
     // the gene table (dg_genecount.h): resident across batches, (4 + n_genes) x 3 words, counted under annotation generation gc_gen; the per-workgroup lines of
     // the N_* rows; host counts and host records on their way in
     unsigned long long *gc_counts = nullptr; size_t gc_rows = 0; uint64_t gc_gen = 0; bool gc_nonempty = false, gc_batch_counted = false, gc_timed = false;
@@ -255,6 +264,7 @@ static void read_env(dg_ctx *c)
     c->env_sam_first_cap = (size_t)std::max(0, geti("DG_SAM_TEXT_FIRST_CAP", 0));
     c->env_bam_first_cap = (size_t)std::max(0, geti("DG_BAM_FIRST_CAP", 0));
     c->env_bamsort_first_cap = (size_t)std::max(0, geti("DG_BAMSORT_FIRST_CAP", 0));
+    c->env_markdup_hash_bits = geti("DG_MARKDUP_HASH_BITS", MD_HASH_BITS); if (c->env_markdup_hash_bits < 1 || c->env_markdup_hash_bits > MD_HASH_BITS) c->env_markdup_hash_bits = MD_HASH_BITS;
     c->env_seed_multi = geti("DG_SEED_MULTI", 4); if (c->env_seed_multi < 0 || c->env_seed_multi > SQF_MULTI_MAX) c->env_seed_multi = SQF_MULTI_MAX;   // rows of an interval that are located and compared with the text at once (0: single rows only)
 }
 
@@ -707,6 +717,12 @@ extern "C" void dg_destroy(dg_ctx *c)
     if (c->d_cv_stat) (void)hipFree(c->d_cv_stat);
     if (c->h_cv_stat) (void)hipHostFree(c->h_cv_stat);
     for (hipEvent_t e : c->ev_cv) if (e) (void)hipEventDestroy(e);
+    for (DBuf<uint64_t> *b : {&c->md_E, &c->md_h, &c->md_tile, &c->md_junk, &c->md_part, &c->md_tile_last, &c->md_k[0], &c->md_k[1], &c->md_ek[0], &c->md_ek[1]}) b->release();
+    for (DBuf<uint32_t> *b : {&c->md_score, &c->md_mate, &c->md_cand_off, &c->md_cnt_off, &c->md_tile_prev, &c->md_hist, &c->md_sums}) b->release();
+    c->md_v[0].release(); c->md_v[1].release(); c->md_ev[0].release(); c->md_ev[1].release();
+    if (c->d_md_stat) (void)hipFree(c->d_md_stat);
+    if (c->h_md_stat) (void)hipHostFree(c->h_md_stat);
+    for (hipEvent_t e : c->ev_md) if (e) (void)hipEventDestroy(e);
     if (c->gc_counts) (void)hipFree(c->gc_counts);
     c->gc_wg.release(); c->gc_in.release(); c->gc_in_reads.release(); c->gc_in_rep.release(); c->gc_in_cig.release();
     for (hipEvent_t e : c->ev_gc) if (e) (void)hipEventDestroy(e);
@@ -3710,6 +3726,158 @@ extern "C" int dg_bam_coverage_device_ms(dg_ctx *c, float ms[5], int *n_passes)
     if (!c || !ms) return DG_ERR_ARG;
     for (int k = 0; k < 5; k++) ms[k] = c->cv_ms[k];
     if (n_passes) *n_passes = c->cv_passes;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// duplicate marking of the sorted array (dg_markdup.h): flag 0x400 written in place, in HBM, before dg_bam_sort_compress
+// ------------------------------------------------------------------------------------------
+static int md_state(dg_ctx *c)
+{
+    if (c->d_md_stat) return DG_OK;
+    HIPCHK(hipMalloc((void **)&c->d_md_stat, MD_ST_WORDS * 8));
+    HIPCHK(hipHostMalloc((void **)&c->h_md_stat, MD_ST_WORDS * 8, hipHostMallocDefault));
+    memset(c->h_md_stat, 0, MD_ST_WORDS * 8);
+    for (hipEvent_t &e : c->ev_md) HIPCHK(hipEventCreate(&e));
+    return DG_OK;
+}
+
+extern "C" int dg_bam_markdup_granules(int out[3])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = MD_THREADS; out[1] = RS_TILE; out[2] = MD_CROWD;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_markdup_finish(dg_ctx *c, uint32_t flags, uint64_t stats[8], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_markdup_finish";
+    if (device_ms) *device_ms = 0.f;
+    if (stats) for (int k = 0; k < 8; k++) stats[k] = 0;
+    c->md_passes = 0;
+    for (float &m : c->md_ms) m = 0.f;
+    if (!c->bs_fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
+    if (flags & ~DG_MD_COUNT_ONLY) { snprintf(c->err, 512, "%s: flags 0x%x hold a bit that is not DG_MD_COUNT_ONLY", fn, flags); return DG_ERR_ARG; }
+    const int write = (flags & DG_MD_COUNT_ONLY) ? 0 : 1;
+    { const int rc = bs_ready(c); if (rc) return rc; }
+    { const int rc = md_state(c); if (rc) return rc; }
+    const size_t n = c->bs_fin_records, n_raw = c->bs_fin_bytes;
+    const int n_chr = c->ix.n_chr, hash_bits = c->env_markdup_hash_bits;
+    if (n_chr < 1) { snprintf(c->err, 512, "%s: %d chromosomes", fn, n_chr); return DG_ERR_ARG; }
+    if (!n) return DG_OK;
+    const uint32_t tiles = (uint32_t)((n + MD_THREADS - 1) / MD_THREADS);
+    BS_ENSURE(c->md_E, n, "the records' end keys"); BS_ENSURE(c->md_h, n, "the names' hashes"); BS_ENSURE(c->md_score, n, "the records' scores"); BS_ENSURE(c->md_mate, n, "the records' partners");
+    BS_ENSURE(c->md_cand_off, n, "the candidates' offsets"); BS_ENSURE(c->md_cnt_off, n, "the pairs' and ends' offsets");
+    BS_ENSURE(c->md_tile, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(c->md_junk, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(c->md_part, 2 * (size_t)tiles, "the per-workgroup values");
+    BS_ENSURE(c->md_tile_last, (size_t)tiles + 1, "the per-workgroup last heads"); BS_ENSURE(c->md_tile_prev, (size_t)tiles + 2, "the per-workgroup previous heads");
+    const uint64_t *dst_off = c->bs_k[c->bs_fin_which ^ 1].p;
+    HIPCHK(hipMemsetAsync(c->d_md_stat, 0, MD_ST_WORDS * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->md_junk.p, 0, ((size_t)tiles + 1) * 8, c->stream));
+    HIPCHK(hipEventRecord(c->ev_md[0], c->stream));
+    k_md_rec<<<tiles, MD_THREADS, 0, c->stream>>>(c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, n_chr, hash_bits, c->md_E.p, c->md_h.p, c->md_score.p, c->md_mate.p,
+                                                  c->md_cand_off.p, c->md_tile.p, c->md_part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_tile.p, tiles, c->d_md_stat + MD_ST_CAND, c->md_part.p, 2, 1, c->d_md_stat + MD_ST_EXAMINED);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_md[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_md_stat, c->d_md_stat, MD_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the first wait: how many candidates, and what was out of range
+    if (c->h_md_stat[MD_ST_NBAD]) {
+        snprintf(c->err, 512, "%s: record %llu of the sorted array has an unclipped 5' end outside [-2^31, 3 * 2^31): an end key cannot hold it; nothing was written", fn, ~c->h_md_stat[MD_ST_NBAD]);
+        return DG_ERR_RANGE;
+    }
+    const size_t n_cand = (size_t)c->h_md_stat[MD_ST_CAND], n_examined = (size_t)c->h_md_stat[MD_ST_EXAMINED];
+    if (n_cand > n || n_examined > n) { snprintf(c->err, 512, "%s: %zu candidates and %zu examined records of %zu", fn, n_cand, n_examined, n); return DG_ERR_INTERNAL; }
+    const uint32_t ctiles = (uint32_t)((n_cand + MD_THREADS - 1) / MD_THREADS);
+    int which = 0;
+    if (n_cand) {
+        for (int k = 0; k < 2; k++) { BS_ENSURE(c->md_k[k], n_cand, "the sorter's keys"); BS_ENSURE(c->md_v[k], n_cand, "the sorter's values"); }
+        BS_ENSURE(c->md_hist, rs_hist_words((uint32_t)n), "the sorter's histograms"); BS_ENSURE(c->md_sums, rs_sums_words((uint32_t)n), "the sorter's sums");
+    }
+    uint64_t *const keys[2] = {c->md_k[0].p, c->md_k[1].p}; int64_t *const vals[2] = {c->md_v[0].p, c->md_v[1].p};
+    HIPCHK(hipEventRecord(c->ev_md[2], c->stream));
+    if (n_cand) {
+        k_md_compact<<<tiles, MD_THREADS, 0, c->stream>>>(c->md_cand_off.p, c->md_tile.p, c->md_h.p, (uint32_t)n, (uint32_t)n_cand, keys[0], vals[0]);
+        { const int rc = rs_sort_passes(c, keys, vals, c->md_hist.p, c->md_sums.p, (uint32_t)n_cand, hash_bits, which); if (rc) return rc; }
+        c->md_passes += (hash_bits + 3) / 4;
+        k_md_mate<<<ctiles, MD_THREADS, 0, c->stream>>>(keys[which], vals[which], (uint32_t)n_cand, (uint32_t)n, c->bs_sorted.p, dst_off, c->bs_tile.p, c->md_mate.p, c->md_part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_junk.p, ctiles, c->d_md_stat + MD_ST_JUNK, c->md_part.p, 1, 1, c->d_md_stat + MD_ST_CROWDED);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(c->ev_md[3], c->stream));
+    k_md_count<<<tiles, MD_THREADS, 0, c->stream>>>(c->md_mate.p, (uint32_t)n, c->md_cnt_off.p, c->md_tile.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_tile.p, tiles, c->d_md_stat + MD_ST_COUNTS, nullptr, 0, 0, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_md[4], c->stream));
+    HIPCHK(hipMemcpyAsync(c->h_md_stat, c->d_md_stat, MD_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the second wait: how many pairs and ends
+    const size_t n_pairs = (size_t)(c->h_md_stat[MD_ST_COUNTS] >> 32), n_ends = (size_t)(uint32_t)c->h_md_stat[MD_ST_COUNTS], n_crowded = (size_t)c->h_md_stat[MD_ST_CROWDED];
+    if (2 * n_pairs > n_cand || n_ends != n_examined) { snprintf(c->err, 512, "%s: %zu pairs of %zu candidates, %zu ends of %zu examined records", fn, n_pairs, n_cand, n_ends, n_examined); return DG_ERR_INTERNAL; }
+    const uint32_t ptiles = (uint32_t)((n_pairs + MD_THREADS - 1) / MD_THREADS), etiles = (uint32_t)((n_ends + MD_THREADS - 1) / MD_THREADS);
+    if (n_ends) {
+        for (int k = 0; k < 2; k++) { BS_ENSURE(c->md_ek[k], n_ends, "the ends' keys"); BS_ENSURE(c->md_ev[k], n_ends, "the ends' values"); }
+        BS_ENSURE(c->md_hist, rs_hist_words((uint32_t)n), "the sorter's histograms"); BS_ENSURE(c->md_sums, rs_sums_words((uint32_t)n), "the sorter's sums");
+    }
+    uint64_t *const ekeys[2] = {c->md_ek[0].p, c->md_ek[1].p}; int64_t *const evals[2] = {c->md_ev[0].p, c->md_ev[1].p};
+    const int e_bits = md_e_bits(n_chr);
+    int pw = 0, ew = 0;
+    HIPCHK(hipEventRecord(c->ev_md[5], c->stream));
+    if (n_ends) k_md_emit<<<tiles, MD_THREADS, 0, c->stream>>>(c->md_mate.p, c->md_score.p, c->md_cnt_off.p, c->md_tile.p, (uint32_t)n, (uint32_t)n_pairs, (uint32_t)n_ends, keys[0], vals[0], ekeys[0], evals[0]);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_md[6], c->stream));
+    if (n_pairs) {
+        { const int rc = rs_sort_passes(c, keys, vals, c->md_hist.p, c->md_sums.p, (uint32_t)n_pairs, MD_SCORE_BITS, pw); if (rc) return rc; }
+        k_md_rekey<<<ptiles, MD_THREADS, 0, c->stream>>>(keys[pw], vals[pw], (uint32_t)n_pairs, 0, c->md_E.p, c->md_mate.p, (uint32_t)n);
+        { const int rc = rs_sort_passes(c, keys, vals, c->md_hist.p, c->md_sums.p, (uint32_t)n_pairs, e_bits, pw); if (rc) return rc; }
+        k_md_rekey<<<ptiles, MD_THREADS, 0, c->stream>>>(keys[pw], vals[pw], (uint32_t)n_pairs, 1, c->md_E.p, c->md_mate.p, (uint32_t)n);
+        { const int rc = rs_sort_passes(c, keys, vals, c->md_hist.p, c->md_sums.p, (uint32_t)n_pairs, e_bits, pw); if (rc) return rc; }
+        c->md_passes += (MD_SCORE_BITS + 3) / 4 + 2 * ((e_bits + 3) / 4);
+    }
+    HIPCHK(hipEventRecord(c->ev_md[7], c->stream));
+    if (n_ends) {
+        { const int rc = rs_sort_passes(c, ekeys, evals, c->md_hist.p, c->md_sums.p, (uint32_t)n_ends, MD_SCORE_BITS, ew); if (rc) return rc; }
+        k_md_rekey<<<etiles, MD_THREADS, 0, c->stream>>>(ekeys[ew], evals[ew], (uint32_t)n_ends, 2, c->md_E.p, c->md_mate.p, (uint32_t)n);
+        { const int rc = rs_sort_passes(c, ekeys, evals, c->md_hist.p, c->md_sums.p, (uint32_t)n_ends, e_bits, ew); if (rc) return rc; }
+        c->md_passes += (MD_SCORE_BITS + 3) / 4 + (e_bits + 3) / 4;
+    }
+    HIPCHK(hipEventRecord(c->ev_md[8], c->stream));
+    if (n_pairs) {
+        k_md_heads<<<ptiles, MD_THREADS, 0, c->stream>>>(keys[pw], vals[pw], (uint32_t)n_pairs, c->md_E.p, c->md_mate.p, c->md_tile_last.p);
+        k_cv_tails_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_tile_last.p, ptiles, c->md_tile_prev.p);
+        k_md_flag_pairs<<<ptiles, MD_THREADS, 0, c->stream>>>(keys[pw], vals[pw], (uint32_t)n_pairs, c->md_E.p, c->md_mate.p, c->md_tile_prev.p, c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n,
+                                                               (unsigned long long)n_raw, write, c->md_part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_junk.p, ptiles, c->d_md_stat + MD_ST_JUNK, c->md_part.p, 2, 1, c->d_md_stat + MD_ST_DUP_PAIRS);
+    }
+    if (n_ends) {
+        k_md_flag_ends<<<etiles, MD_THREADS, 0, c->stream>>>(ekeys[ew], evals[ew], (uint32_t)n_ends, c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, write, c->md_part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_junk.p, etiles, c->d_md_stat + MD_ST_JUNK, c->md_part.p, 1, 1, c->d_md_stat + MD_ST_DUP_FRAGS);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->ev_md[9], c->stream));
+    if (write && n_ends) {                                        // bytes of the array changed: as behind dg_bam_sort_finish, no block of it has been compressed, and no track covers it
+        c->bi_valid = false; c->bi_covered.clear(); c->cv_valid = false;
+    }
+    HIPCHK(hipMemcpyAsync(c->h_md_stat, c->d_md_stat, MD_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));                                       // the third wait: the counts
+    float t[9];
+    for (int k = 0; k < 9; k++) { t[k] = 0.f; (void)hipEventElapsedTime(&t[k], c->ev_md[k], c->ev_md[k + 1]); }
+    c->md_ms[0] = t[0]; c->md_ms[1] = t[2]; c->md_ms[2] = t[6]; c->md_ms[3] = t[7]; c->md_ms[4] = t[8]; c->md_ms[5] = t[3] + t[5];
+    float total = 0.f;
+    for (float m : c->md_ms) total += m;
+    if (device_ms) *device_ms = total;
+    const uint64_t dup_pairs = c->h_md_stat[MD_ST_DUP_PAIRS], dup_frags = c->h_md_stat[MD_ST_DUP_FRAGS];
+    if (stats) {
+        stats[0] = n_examined; stats[1] = n_pairs; stats[2] = n_examined - 2 * n_pairs; stats[3] = dup_pairs; stats[4] = dup_frags; stats[5] = n_crowded;
+        stats[6] = 2 * dup_pairs + dup_frags; stats[7] = c->h_md_stat[MD_ST_FAMILY];
+    }
+    return DG_OK;
+}
+
+extern "C" int dg_bam_markdup_device_ms(dg_ctx *c, float ms[6], int *n_passes)
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    for (int k = 0; k < 6; k++) ms[k] = c->md_ms[k];
+    if (n_passes) *n_passes = c->md_passes;
     return DG_OK;
 }
 

@@ -59,7 +59,7 @@ static void usage(const char *prog, const Options &o)   // ShowProgramUsage, mai
     fprintf(stdout, "         -max_dup INT  maximal number of repetitive fragments (between 100-10000) [%d]\n", o.p.max_dup);
     fprintf(stdout, "         -o            alignment filename in SAM format\n");
     fprintf(stdout, "         -bo           alignment filename in BAM format\n");
-    fprintf(stdout, "                       (DART_DEVICE_BAM=1 DART_SORT_BAM=1: coordinate-sorted on the device; DART_BAM_INDEX=1 beside them: its .bai too; DART_COVERAGE=1 or 2: its bedGraph, or one per strand)\n");
+    fprintf(stdout, "                       (DART_DEVICE_BAM=1 DART_SORT_BAM=1: coordinate-sorted on the device; DART_BAM_INDEX=1 beside them: its .bai too; DART_COVERAGE=1 or 2: its bedGraph, or one per strand; DART_MARK_DUPLICATES=1: flag 0x400 set on the device)\n");
     fprintf(stdout, "         -j            splice junction output filename [junctions.tab]\n");
     fprintf(stdout, "         -m            output multiple alignments [false]\n");
     fprintf(stdout, "         -all_sj       detect all splice junction regardless of mapq score [false]\n");
@@ -591,7 +591,16 @@ int main(int argc, char *argv[])
     std::vector<std::pair<std::string, uint32_t>> cov_tracks;      // path, strand flags
     if (coverage == 1) cov_tracks.emplace_back(std::string(o.out) + ".bedgraph", 0u);
     if (coverage == 2) { cov_tracks.emplace_back(std::string(o.out) + ".plus.bedgraph", DG_COV_STRAND_PLUS); cov_tracks.emplace_back(std::string(o.out) + ".minus.bedgraph", DG_COV_STRAND_MINUS); }
-    auto drop_tracks = [&]() { for (const auto &t : cov_tracks) remove(t.first.c_str()); };      // (no failed run leaves a track, a stale one included)
+    // DART_MARK_DUPLICATES=1 beside DART_SORT_BAM=1: flag 0x400 is written into the sorted records on the device (dg_bam_markdup_finish) before the first piece
+    // is compressed, in place of a `samtools markdup` over the file; the index and the tracks see the marked records; <out>.markdup.txt holds the counts.
+    // Without the sort there is nothing to mark: no output is begun.
+    const bool mark_dups = getenv("DART_MARK_DUPLICATES") && atoi(getenv("DART_MARK_DUPLICATES")) != 0;
+    if (mark_dups && !sort_bam) {
+        fprintf(stderr, "Error! DART_MARK_DUPLICATES=1 needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n");
+        return 1;
+    }
+    const std::string md_path = mark_dups ? std::string(o.out) + ".markdup.txt" : std::string();
+    auto drop_tracks = [&]() { for (const auto &t : cov_tracks) remove(t.first.c_str()); if (mark_dups) remove(md_path.c_str()); };      // (no failed run leaves a track or the duplicates' counts, stale ones included)
     const char *bam_dev_note = sort_bam ? (bgzf_dynamic ? ", bam=device+sorted+dyn" : ", bam=device+sorted") : bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "";
     FastqIndex pre;                         // the first library's read files are mapped and indexed while the HIP runtime starts, the genome index loads and dg_init_files runs
     bool fast_first = false;
@@ -1071,6 +1080,22 @@ int main(int argc, char *argv[])
         for (int k = 1; k < inflight_cfg; k++) if ((rc = dg_bam_sort_merge(roots[0], ctx[(size_t)k]))) return sort_fail(roots[0], rc);
         size_t n_sorted = 0, n_raw = 0; float fin_ms = 0.f;
         if ((rc = dg_bam_sort_finish(roots[0], &n_sorted, &n_raw, &fin_ms))) return sort_fail(roots[0], rc);
+        // DART_MARK_DUPLICATES: the verdicts go into the sorted records before any piece is compressed
+        uint64_t md_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; float md_ms = 0.f; double t_md = 0.0;
+        if (mark_dups) {
+            const double tm0 = now_s();
+            if ((rc = dg_bam_markdup_finish(roots[0], 0u, md_stats, &md_ms))) {
+                (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); drop_tracks();
+                fprintf(stderr, "\nError! DART_MARK_DUPLICATES=1: %s\n", dg_last_error(roots[0]));
+                return 1;
+            }
+            static const char *const md_names[8] = {"examined_records", "pairs", "fragments", "duplicate_pairs", "duplicate_fragments", "candidates_in_crowded_runs", "records_marked_duplicate", "largest_family"};
+            FILE *mf = fopen(md_path.c_str(), "wb");
+            bool ok = mf != nullptr;
+            for (int k = 0; k < 8 && ok; k++) ok = fprintf(mf, "%s\t%llu\n", md_names[k], (unsigned long long)md_stats[k]) > 0;
+            if (!(mf && fclose(mf) == 0 && ok)) { (void)bam.close(); remove(o.out); if (bam_index) remove(bai_path.c_str()); drop_tracks(); fprintf(stderr, "Error while writing %s\n", md_path.c_str()); return 1; }
+            t_md = now_s() - tm0;
+        }
         const double ts1 = now_s();
         const size_t block = 0xff00;
         const double piece_mb = getenv("DART_SORT_PIECE_MB") ? atof(getenv("DART_SORT_PIECE_MB")) : 256.0;
@@ -1110,7 +1135,11 @@ int main(int argc, char *argv[])
             char idx_note[128] = "";
             if (bam_index) snprintf(idx_note, sizeof idx_note, "; index %.3f s (kernels %.3f s, %zu bytes)", now_s() - ts2, bai_ms * 1e-3, bai_bytes);
             fprintf(stderr, "[dart timing]%s: %zu records, %zu raw bytes; accumulate (sum over workers) %.3f s; merge + finish %.3f s (kernels %.3f s); compress + download + write %.3f s (BGZF kernels %.3f s, %zu pieces of %zu bytes, %zu bytes out)%s\n",
-                    bam_dev_note + 1, n_sorted, n_raw, g_sort_acc_ns.load() * 1e-9, ts1 - ts0, fin_ms * 1e-3, ts2 - ts1, z_ms * 1e-3, n_pieces, piece, n_out, idx_note);
+                    bam_dev_note + 1, n_sorted, n_raw, g_sort_acc_ns.load() * 1e-9, ts1 - ts0 - t_md, fin_ms * 1e-3, ts2 - ts1, z_ms * 1e-3, n_pieces, piece, n_out, idx_note);
+            if (mark_dups)
+                fprintf(stderr, "[dart timing] markdup: %llu examined records, %llu pairs, %llu fragments; %llu records marked (%llu pairs, %llu fragments); %.3f s (kernels %.3f s)\n",
+                        (unsigned long long)md_stats[0], (unsigned long long)md_stats[1], (unsigned long long)md_stats[2], (unsigned long long)md_stats[6], (unsigned long long)md_stats[3],
+                        (unsigned long long)md_stats[4], t_md, md_ms * 1e-3);
         }
     }
     if (o.bam) { if (!bam.close()) { if (sort_bam) remove(o.out); if (bam_index) remove(bai_path.c_str()); drop_tracks(); fprintf(stderr, "Error while writing %s\n", o.out); return 1; } }

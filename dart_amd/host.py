@@ -40,6 +40,7 @@ SJ_ENTRY = np.dtype([("g1", "<i8"), ("g2", "<i8"), ("count", "<u4"), ("chr", "<u
 SJ_ENTRIES_ONLY = 1
 COV_ENTRY = np.dtype([("chr", "<u4"), ("start", "<u4"), ("end", "<u4"), ("depth", "<u4")])      # dg_cov_entry
 COV_ENTRIES_ONLY, COV_STRAND_PLUS, COV_STRAND_MINUS = 1, 2, 4
+MD_COUNT_ONLY = 1                                                                                 # DG_MD_COUNT_ONLY
 SJ_NO_CHR = 0xFFFFFFFF
 GENE_EXON = np.dtype([("chr", "<i4"), ("start", "<u4"), ("end", "<u4"), ("strand", "<u4"), ("gene", "<u4")])      # dg_gene_exon
 GENE_NONE, GENE_AMBIG = 0xFFFFFFFF, 0xFFFFFFFE
@@ -320,6 +321,10 @@ def _load_lib():
         lib.dg_bam_coverage_device.argtypes = [vp, vp, vp]
         lib.dg_bam_coverage_device_ms.argtypes = [vp, vp, vp]
         lib.dg_bam_coverage_granules.argtypes = [vp]
+    if hasattr(lib, "dg_bam_markdup_finish"):                # (likewise: duplicate marking of the sorted array)
+        lib.dg_bam_markdup_finish.argtypes = [vp, C.c_uint32, vp, vp]
+        lib.dg_bam_markdup_device_ms.argtypes = [vp, vp, vp]
+        lib.dg_bam_markdup_granules.argtypes = [vp]
     if hasattr(lib, "dg_gene_set_annotation"):               # (likewise: gene-level read counts)
         lib.dg_gene_set_annotation.argtypes = [vp, vp, vp]
         lib.dg_batch_accumulate_genes.argtypes = [vp, C.c_int, C.c_uint32, vp]
@@ -842,6 +847,27 @@ class DartGPU:
         ent = np.zeros(max(int(ne.value), 1), COV_ENTRY); text = np.zeros(max(int(nb.value), 1), np.uint8)
         self._chk(self.lib.dg_bam_coverage_download(self.ctx, ent.ctypes.data, int(ne.value), text.ctypes.data, int(nb.value)), "dg_bam_coverage_download")
         return ent[:int(ne.value)], text[:int(nb.value)].tobytes()
+
+    # ---- duplicate marking of the sorted array (dg_bam_markdup_*): flag 0x400 written in HBM behind bam_sort_finish, before bam_sort_compress ----
+    def bam_markdup_granules(self):
+        """(records / candidates / pairs / ends per workgroup, items per tile of the sorter, the largest run of equal name hashes that is not crowded)
+        (dg_bam_markdup_granules)"""
+        g = (C.c_int * 3)()
+        self._chk(self.lib.dg_bam_markdup_granules(g), "dg_bam_markdup_granules")
+        return int(g[0]), int(g[1]), int(g[2])
+
+    def bam_markdup_finish(self, count_only: bool = False):
+        """marks the duplicates of the sorted array in place (dg_bam_markdup_finish; count_only: decides and counts, writes no flag) -> the stats, also kept as
+        self.bam_markdup_stats = (examined records, pairs, fragments, duplicate pairs, duplicate fragments, candidates in crowded runs, records that leave
+        with 0x400, the largest family); self.bam_markdup_device_ms = the kernels' device time, self.bam_markdup_device_ms_split = (record pass, mate sort and
+        search, pair sorts, end sorts, family scan and flag writes, counting and emitting), self.bam_markdup_passes = the sorter's passes"""
+        ms = C.c_float(0); st = (C.c_uint64 * 8)()
+        self._chk(self.lib.dg_bam_markdup_finish(self.ctx, MD_COUNT_ONLY if count_only else 0, st, C.byref(ms)), "dg_bam_markdup_finish")
+        self.bam_markdup_stats, self.bam_markdup_device_ms = tuple(int(x) for x in st), float(ms.value)
+        split = (C.c_float * 6)(); passes = C.c_int(0)
+        self._chk(self.lib.dg_bam_markdup_device_ms(self.ctx, split, C.byref(passes)), "dg_bam_markdup_device_ms")
+        self.bam_markdup_device_ms_split, self.bam_markdup_passes = tuple(float(x) for x in split), int(passes.value)
+        return self.bam_markdup_stats
 
     def wait_index(self):
         self._chk(self.lib.dg_index_wait(self.ctx), "dg_index_wait")

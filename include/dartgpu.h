@@ -532,6 +532,54 @@ int dg_bam_coverage_device(dg_ctx *, void **entries, void **text);
 int dg_bam_coverage_device_ms(dg_ctx *, float ms[5], int *n_passes);
 int dg_bam_coverage_granules(int out[2]);
 
+/* ---- duplicate marking of the sorted array, on the device (dart_amd/csrc/dg_markdup.h): flag 0x400 written into the records in HBM, before
+ * dg_bam_sort_compress, so that the file, the .bai and the coverage track (default filter 0x704) all see it.  The reference has no such output: an opt-in
+ * extension (what `samtools markdup` or Picard MarkDuplicates would compute from the file).
+ * THE DEFINITION -- modelled on Picard's rules (unclipped 5' ends, sum of base qualities, a fragment loses to any pair that shares its end); no such tool
+ * exists where this library is built and tested, so this text, not a run of one, is what the tests pin (tests/markdup_inputs.py is its sequential twin).
+ * Per record, fields read byte by byte, little endian: refID int32 at byte 4, pos int32 at 8, l_read_name u8 at 12, n_cigar_op u16 at 16, flag u16 at 18,
+ * l_seq u32 at 20; then from byte 36 the name, the CIGAR ops (u32, len << 4 | op), (l_seq + 1) / 2 bytes of bases and l_seq quality bytes.
+ *     examined   all of: 0 <= refID < n_chr; pos >= 0; flag & 4 clear; flag & 0x900 clear; n_cigar_op > 0; name, CIGAR, bases and qualities inside the record
+ *                and the array (36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <= 4 + block_size).  Every other record plays no part and leaves
+ *                with its bytes unchanged.
+ *     0x400      the input's bit plays no part: an examined record leaves with the verdict, set or cleared.  The call is idempotent.
+ *     end key    s = flag >> 4 & 1; rlen = the sum of M, D, N, =, X; lead / trail = the sum of the S and H ops in front of the first / behind the last op
+ *                that is neither (clips alone: lead = their sum, trail = 0); u5 = s ? pos + rlen - 1 + trail : pos - lead in 64-bit arithmetic.
+ *                u5 + 2^31 outside [0, 2^33): DG_ERR_RANGE, the text names the record's index in the sorted array, nothing is written.
+ *                E = refID << 34 | (u5 + 2^31) << 1 | s
+ *     score      the sum of the quality bytes q with 15 <= q <= 93, saturated at 2^20 - 1 (0xff counts as 0)
+ *     candidate  an examined record with flag & 1 set, flag & 8 clear, and exactly one of 0x40 and 0x80 set
+ *     hash       h = FNV-1a 64 over the l_read_name - 1 name bytes, folded as (h ^ h >> 48), masked to hash_bits bits: 48, or DG_MARKDUP_HASH_BITS = 1..48
+ *                from the environment of dg_init (read where DG_BAMSORT_FIRST_CAP is read; a test hook that makes collisions and crowds reachable)
+ *     runs       the candidates, ordered stably by h, fall into runs of equal h.  A run of more than 64 is crowded: all its members are fragments.  Else the
+ *                candidates of a run with the same name bytes form a group; a group of exactly two, one with 0x40 and one with 0x80, is a pair; members of
+ *                any other group are fragments.  A fragment is an examined record that is in no pair.
+ *     pairs      lo = min(Ea, Eb), hi = max(Ea, Eb), score = the sum of the members', rep = the smaller of their indices in the sorted array.  Among pairs
+ *                with equal (lo, hi) the largest score survives, on equal scores the smallest rep; both records of every other pair get 0x400.
+ *     fragments  a fragment with end key E is a duplicate when any pair has lo == E or hi == E, or another fragment with the same E has a larger score, or
+ *                an equal score and a smaller index.
+ * Optical duplicates, UMIs and the propagation to secondary or supplementary records are not done.
+ *   dg_bam_markdup_finish     works in place on the array of the last dg_bam_sort_finish.  flags: DG_MD_COUNT_ONLY decides and counts but writes no flag; any
+ *                             other bit, or no valid sorted array (none finished, or a store call behind the finish; the text names dg_bam_sort_finish):
+ *                             DG_ERR_ARG.  stats (may be NULL): [0] examined records, [1] pairs, [2] fragments, [3] duplicate pairs, [4] duplicate fragments,
+ *                             [5] candidates in crowded runs, [6] records that leave with 0x400 = 2 [3] + [4], [7] the largest family: pairs sharing one
+ *                             (lo, hi).  An empty array gives zeros.  A call that writes also forgets which blocks dg_bam_sort_compress has compressed and
+ *                             any finished index or track, exactly as dg_bam_sort_finish does: dg_bam_index_finish without sizes then refuses blocks
+ *                             compressed before the marking.  The store itself is untouched: a later dg_bam_sort_finish gives the unmarked array again.
+ *                             The call enqueues on the context's stream and waits three times: for the number of candidates (and a record out of range),
+ *                             for the numbers of pairs and ends, and for the counts.  Buffers of its own: 32 bytes per record, 32 per candidate (the
+ *                             sorter's two key and two value buffers, which the pairs use after the mate search), 32 per end (one per fragment, two per
+ *                             pair: at most one per record) and the sorter's histograms; a failed allocation gives DG_ERR_CAPACITY.  Every failure leaves
+ *                             the context and the array usable, the array's bytes unchanged.  dg_destroy frees the buffers.
+ *   dg_bam_markdup_device_ms  the last finish's device time by stage: [0] the record pass, [1] the mate sort and search, [2] the pair sorts, [3] the end
+ *                             sorts, [4] the family scan and the flag writes, [5] counting and emitting pairs and ends; *n_passes (may be NULL): the
+ *                             sorter's passes, all sorts together
+ *   dg_bam_markdup_granules   [0] records / candidates / pairs / ends per workgroup, [1] the sorter's tile, [2] the largest run that is not crowded        */
+#define DG_MD_COUNT_ONLY 1u    /* decide and count, write no flag */
+int dg_bam_markdup_finish(dg_ctx *, uint32_t flags, uint64_t stats[8], float *device_ms);
+int dg_bam_markdup_device_ms(dg_ctx *, float ms[6], int *n_passes);
+int dg_bam_markdup_granules(int out[3]);
+
 /* ---- gene-level read counts on the device (dart_amd/csrc/dg_genecount.h): a ReadsPerGene table per job ----
  * Counted per batch, from the records the batch left in HBM (mates 2i and 2i + 1 are still neighbours), in a per-context table that stays in HBM across
  * batches and is merged at the end of the job, as the junction table is.  Modelled on `htseq-count --mode union` with the layout of STAR's ReadsPerGene.out.tab;
