@@ -73,19 +73,7 @@ __attribute__((constructor)) static void dg_default_hw_queues()
 static std::atomic<int> g_live_ctx[64];           // contexts alive per device (each owns one stream)
 static std::atomic<bool> g_hwq_warned{false};
 
-template <typename T> struct DBuf {
-    T *p = nullptr; size_t cap = 0;
-    hipError_t ensure(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr; cap = 0;
-        size_t want = n + n / 8 + 64;
-        hipError_t e = hipMalloc((void **)&p, want * sizeof(T));
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
+#include "api_ctx.h"
 
 #define N_TIMERS 20
 #define N_TOPS 128              // small device counters of a batch (bump tops, tickets, list sizes, class histogram), zeroed per run
@@ -156,87 +144,14 @@ struct dg_ctx {
     size_t used[3] = {0, 0, 0};
     bool enqueued = false;
     // timings
-    hipEvent_t ev[N_TIMERS + 1]; const char *tname[N_TIMERS]; int n_t = 0; float tms[N_TIMERS];
+    hipEvent_t ev[N_TIMERS + 1] = {}; const char *tname[N_TIMERS]; int n_t = 0; float tms[N_TIMERS];
     uint64_t counters[CTR_N];
     uint64_t reruns_capacity = 0, reruns_scan = 0;      // since dg_init / dg_clone
     bool want_compact = true, packed_valid = false;     // compact records: written by this run's kernels too / present for the batch that ran last
-    // SAM text of the batch that ran last (dg_batch_format_sam): per-batch inputs, scan state, the text
-    DBuf<uint32_t> sam_hdr_off, sam_qual_off, sam_qlen; DBuf<char> sam_hdr, sam_qual, sam_text; DBuf<uint64_t> sam_read_off, sam_tile;
-    unsigned long long *d_sam_stat = nullptr, *h_sam_stat = nullptr;      // total bytes + the three counters: device / page-locked copy
-    hipEvent_t ev_sam[2] = {nullptr, nullptr};
-    bool batch_done = false, sam_valid = false; size_t sam_bytes = 0;
-    // FASTQ text parsed on the device (dg_batch_upload_fastq, dg_fastq.h): the texts, their line starts, the scan state; the batch's names and stored
-    // qualities stay resident for dg_batch_format_sam_resident in buffers of their own (a dg_batch_format_sam with host arrays uses sam_*)
-    DBuf<unsigned char> fq_text; DBuf<uint32_t> fq_lines, fq_tile_cnt, fq_name_at, fq_name_len, fq_loc, fq_hdr_off, fq_qual_off; DBuf<unsigned long long> fq_tile_sum; DBuf<char> fq_hdr, fq_qual;
-    FqInfo *d_fq_info = nullptr, *h_fq_info = nullptr;                     // the sizes block: device / page-locked copy
-    hipEvent_t ev_fq[2] = {nullptr, nullptr};
-    bool fq_valid = false; size_t fq_hdr_bytes = 0, fq_qual_bytes = 0; float fq_ms = 0.f;      // the batch on the context came from dg_batch_upload_fastq
-    // BGZF inflated on the device (dg_bgzf_inflate, dg_batch_upload_fastq_bgzf; dg_inflate.h): the compressed bytes, the member table, a status word per member,
-    // the first failing member; inf_out holds the bytes of a dg_bgzf_inflate (the FASTQ path inflates straight into fq_text).  fq_tail: what the last
-    // dg_batch_upload_fastq_bgzf left behind the last whole record of each text.
-    DBuf<unsigned char> inf_in, inf_out, fq_tail; DBuf<InfBlock> inf_tab; DBuf<uint32_t> inf_status;
-    unsigned long long *d_inf_verdict = nullptr, *h_inf_verdict = nullptr;
-    hipEvent_t ev_inf[2] = {nullptr, nullptr};
-    bool inf_valid = false; size_t inf_bytes = 0;
-    bool fq_tail_valid = false; size_t fq_tail_n[2] = {0, 0}, fq_tail_off2 = 0;
+    bool batch_done = false;       // the batch on the context has been run and waited for
     bool no_batch = false;         // the last upload was a DG_FQ_CHECK_ONLY: there is nothing to run
-    // BAM of the batch that ran last (dg_batch_format_bam, dg_bamfmt.h / dg_bgzf.h): the uncompressed records, the blocks' slots, sizes and places, the
-    // contiguous stream; bgzf_in holds the bytes of a dg_bgzf_compress.  The records' inputs and scan state are the SAM formatter's buffers (sam_hdr*, sam_qual*,
-    // sam_qlen, sam_read_off, sam_tile: inputs and scratch of one call); the SAM text itself (sam_text) is left alone.
-    DBuf<unsigned char> bam_rec, bgzf_in, bgzf_slots, bgzf_out; DBuf<uint32_t> bgzf_size; DBuf<uint64_t> bgzf_off;
-    unsigned long long *d_bam_stat = nullptr, *h_bam_stat = nullptr;      // [0] raw bytes, [1..3] the SAM counters, [4] records, [5] refused, [6] stream bytes: device / page-locked copy
-    hipEvent_t ev_bam[2] = {nullptr, nullptr}; float bam_ms[2] = {0.f, 0.f};      // (both phases use the pair, one after the other) / device time of the record kernels, of the BGZF kernels
-    bool bam_valid = false; size_t bam_bytes = 0; unsigned char *bam_ptr = nullptr;
-    // the splice-junction table (dg_sjtab.h): resident across batches; the overflow lists of an insert pass and of the growth behind it; the sorter's buffers,
-    // the sorted entries and the text of the last dg_sj_finish
-    SjSlot *sj_tab = nullptr; size_t sj_slots = 0, sj_distinct = 0;
-    DBuf<dg_sj_entry> sj_ovf[2], sj_in, sj_entries; int sj_ovf_cur = 0;
-    DBuf<uint64_t> sj_keys[2], sj_line_off, sj_tile; DBuf<int64_t> sj_vals[2]; DBuf<uint32_t> sj_hist, sj_sums; DBuf<char> sj_text;
-    unsigned long long *d_sj_stat = nullptr, *h_sj_stat = nullptr;        // SJ_ST_* words: device / page-locked copy
-    hipEvent_t ev_sj[3] = {nullptr, nullptr, nullptr};                     // [0], [1]: device time of dg_sj_finish; [2]: the source stream's place for dg_sj_merge
-    bool sj_batch_counted = false, sj_fin_valid = false; size_t sj_fin_entries = 0, sj_fin_bytes = 0;
-    // the coordinate-sorted BAM store (dg_bamsort.h): resident across batches: the records' bytes, one key and one offset per record, and the list of segments
-    // (one per accumulate / add call); the sorter's buffers and the sorted array of the last dg_bam_sort_finish
-    unsigned char *bs_rec = nullptr; uint64_t *bs_key = nullptr; int64_t *bs_off = nullptr;
-    size_t bs_rec_cap = 0, bs_rec_used = 0, bs_key_cap = 0, bs_off_cap = 0, bs_n = 0, bs_growths = 0;
-    std::vector<BsSeg> bs_segs;
-    DBuf<uint32_t> bs_cnt_off, bs_tile_cnt, bs_hist, bs_sums; DBuf<uint64_t> bs_k[2], bs_tile; DBuf<int64_t> bs_v[2]; DBuf<unsigned char> bs_sorted;
-    unsigned long long *d_bs_stat = nullptr, *h_bs_stat = nullptr;        // [0] bytes of the sorted array, [1] (low word) records counted by k_bs_count: device / page-locked copy
-    hipEvent_t ev_bs[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // [0..4]: the phases of dg_bam_sort_finish; [5]: the source stream's place for dg_bam_sort_merge
-    bool bam_rec_valid = false, bam_rec_stored = false; size_t bam_rec_bytes = 0, bam_rec_records = 0;      // bam_rec and the formatter's offsets hold the current batch's records / they are in the store
-    bool bs_fin_valid = false; size_t bs_fin_bytes = 0, bs_fin_records = 0; float bs_ms[4] = {0.f, 0.f, 0.f, 0.f}, bs_acc_ms = 0.f; int bs_passes = 0;
-    // the BAM index of the sorted array (dg_bamidx.h): the compressed size of every block as the last dg_bam_sort_compress left it (bi_covered: which blocks have one),
-    // the per-record, per-chunk and per-reference arrays of dg_bam_index_finish, and the index itself
-    DBuf<uint32_t> bi_sizes, bi_sizes_in, bi_span, bi_tile_cnt, bi_chead, bi_mhead, bi_mbin, bi_binq, bi_ref_q, bi_ref_b, bi_hist, bi_sums;
-    DBuf<uint64_t> bi_coff, bi_key, bi_voff, bi_ck[2], bi_excl, bi_ctile, bi_ref_at, bi_lin_at; DBuf<int64_t> bi_cv[2];
-    DBuf<unsigned long long> bi_ref, bi_lin; DBuf<unsigned char> bi_flag, bi_out;
-    std::vector<unsigned char> bi_covered; std::vector<unsigned long long> h_bi_ref; std::vector<uint64_t> h_bi_lin_at;
-    unsigned long long *d_bi_stat = nullptr, *h_bi_stat = nullptr;        // BI_ST_* words: device / page-locked copy
-    hipEvent_t ev_bi[4] = {nullptr, nullptr, nullptr, nullptr};          // the kernels before and behind the mid-way wait
-    bool bi_valid = false; size_t bi_bytes = 0; int bs_fin_which = 0;     // bs_fin_which: bs_k[bs_fin_which ^ 1] holds the sorted records' places inside their tiles
-    // the coverage track of the sorted array (dg_coverage.h): buffers of its own (the sorter's hold the records' places, which the index needs): per record the
-    // block offsets, per event the sorter's pairs, the scanned deltas and the marks, per breakpoint its key and depth, per entry its breakpoint, record and line
-    DBuf<uint32_t> cv_blk_off, cv_incl, cv_dep_tile, cv_tile_prev, cv_mark, cv_bp_depth, cv_ent_bp, cv_line_off, cv_hist, cv_sums;
-    DBuf<uint64_t> cv_blk_tile, cv_k[2], cv_tile_last, cv_cnt_tile, cv_bp_key, cv_line_tile, cv_part; DBuf<int64_t> cv_v[2]; DBuf<dg_cov_entry> cv_entries; DBuf<char> cv_text;
-    unsigned long long *d_cv_stat = nullptr, *h_cv_stat = nullptr;        // CV_ST_* words: device / page-locked copy
-    hipEvent_t ev_cv[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // around the kernels between the waits
-    bool cv_valid = false; size_t cv_n_entries = 0, cv_bytes = 0; float cv_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f}; int cv_passes = 0;
-    // duplicate marking of the sorted array (dg_markdup.h): buffers of its own: per record the end key, the name's hash, the score, the partner and two
-    // offsets; the sorter's pairs of buffers for candidates (then pairs) and for ends; the per-workgroup sums and values
-    DBuf<uint64_t> md_E, md_h, md_tile, md_junk, md_part, md_tile_last, md_k[2], md_ek[2]; DBuf<int64_t> md_v[2], md_ev[2];
-    DBuf<uint32_t> md_score, md_mate, md_cand_off, md_cnt_off, md_tile_prev, md_hist, md_sums;
-    unsigned long long *d_md_stat = nullptr, *h_md_stat = nullptr;        // MD_ST_* words: device / page-locked copy
-    hipEvent_t ev_md[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    float md_ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; int md_passes = 0;
-    int env_markdup_hash_bits = MD_HASH_BITS;   // DG_MARKDUP_HASH_BITS: test hook, the bits of a name's hash that are kept (makes collisions and crowded runs reachable)
-    // the gene table (dg_genecount.h): resident across batches, (4 + n_genes) x 3 words, counted under annotation generation gc_gen; the per-workgroup lines of
-    // the N_* rows; host counts and host records on their way in
-    unsigned long long *gc_counts = nullptr; size_t gc_rows = 0; uint64_t gc_gen = 0; bool gc_nonempty = false, gc_batch_counted = false, gc_timed = false;
-    DBuf<unsigned long long> gc_wg, gc_in; DBuf<dg_read_out> gc_in_reads; DBuf<dg_report_out> gc_in_rep; DBuf<uint32_t> gc_in_cig;
-    hipEvent_t ev_gc[3] = {nullptr, nullptr, nullptr};                     // [0], [1]: device time of the last count; [2]: the source stream's place for dg_gene_merge
-    size_t env_bamsort_first_cap = 0;  // DG_BAMSORT_FIRST_CAP: test hook, the first size of the store in bytes (forces growth)
-    size_t env_bam_first_cap = 0;      // DG_BAM_FIRST_CAP: test hook, the first size of the record buffer in bytes
-    size_t env_sam_first_cap = 0;      // DG_SAM_TEXT_FIRST_CAP: test hook, the first size of the text buffer in bytes (forces the "text outgrew the guess" path)
+    // the library stages' state, one struct each (api_ctx.h); every stage's section of this file drives its own
+    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; GcState gc;
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
@@ -247,6 +162,14 @@ struct dg_ctx {
     int env_chain_bpc = 8, env_seedh_bpc = 8, env_reseed_pct = 100;      // persistent one-wave workgroups per CU of k_chain_heavy / k_seed_heavy; k_reseed's grids in per cent (sweeps: DG_CHAIN_BPC, DG_SEEDH_BPC, DG_RESEED_PCT)
     int env_rs_chunk = RS_CHUNK_DIAGS, env_rs_inline = RS_ENT_INLINE, env_rs_pool = 0;      // test hooks (DG_RS_CHUNK, DG_RS_ENT_MAX, DG_RS_POOL_BLOCKS): diagonals per chunk of a shared re-seeding window, entries a chunk record holds inline, blocks of the entry pool
     int env_scan_budget = 0;      // DG_SCAN_POLL_BUDGET: poll budget of a look-back on the FIRST attempt of a batch (test hook: forces the DG_E_SCAN re-run path)
+    // what make_ctx_objects made by hand; every DBuf and every stage above frees itself.  Only dg_destroy deletes a context (device current, stream waited for).
+    ~dg_ctx() {
+        for (void *p : {(void *)d_ctr, (void *)d_tops, (void *)d_err, (void *)d_sizes, (void *)d_input_bad}) if (p) (void)hipFree(p);
+        if (h_tail) (void)hipHostFree(h_tail);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_wait, ev_dl, ev_dl_block}) if (e) (void)hipEventDestroy(e);
+        if (owns_shared_caps) delete shared_caps;
+    }
 };
 
 static void read_env(dg_ctx *c)
@@ -261,10 +184,10 @@ static void read_env(dg_ctx *c)
     c->env_chain_bpc = std::max(1, geti("DG_CHAIN_BPC", 8)); c->env_seedh_bpc = std::max(1, geti("DG_SEEDH_BPC", 8)); c->env_reseed_pct = std::max(10, geti("DG_RESEED_PCT", 100));
     c->env_rs_chunk = geti("DG_RS_CHUNK", RS_CHUNK_DIAGS); c->env_rs_chunk = std::min(1 << 24, std::max(RS_SUPER, c->env_rs_chunk / RS_SUPER * RS_SUPER));      // (a multiple of the pac super-chunk)
     c->env_rs_inline = std::min(RS_ENT_INLINE, std::max(0, geti("DG_RS_ENT_MAX", RS_ENT_INLINE))); c->env_rs_pool = std::max(0, geti("DG_RS_POOL_BLOCKS", 0));
-    c->env_sam_first_cap = (size_t)std::max(0, geti("DG_SAM_TEXT_FIRST_CAP", 0));
-    c->env_bam_first_cap = (size_t)std::max(0, geti("DG_BAM_FIRST_CAP", 0));
-    c->env_bamsort_first_cap = (size_t)std::max(0, geti("DG_BAMSORT_FIRST_CAP", 0));
-    c->env_markdup_hash_bits = geti("DG_MARKDUP_HASH_BITS", MD_HASH_BITS); if (c->env_markdup_hash_bits < 1 || c->env_markdup_hash_bits > MD_HASH_BITS) c->env_markdup_hash_bits = MD_HASH_BITS;
+    c->sam.first_cap = (size_t)std::max(0, geti("DG_SAM_TEXT_FIRST_CAP", 0));
+    c->bam.first_cap = (size_t)std::max(0, geti("DG_BAM_FIRST_CAP", 0));
+    c->bs.first_cap = (size_t)std::max(0, geti("DG_BAMSORT_FIRST_CAP", 0));
+    c->md.hash_bits = geti("DG_MARKDUP_HASH_BITS", MD_HASH_BITS); if (c->md.hash_bits < 1 || c->md.hash_bits > MD_HASH_BITS) c->md.hash_bits = MD_HASH_BITS;
     c->env_seed_multi = geti("DG_SEED_MULTI", 4); if (c->env_seed_multi < 0 || c->env_seed_multi > SQF_MULTI_MAX) c->env_seed_multi = SQF_MULTI_MAX;   // rows of an interval that are located and compared with the text at once (0: single rows only)
 }
 
@@ -679,80 +602,14 @@ extern "C" void dg_destroy(dg_ctx *c)
     }
     void *ptrs[] = { c->d_bwt, c->d_sa, c->d_pac, c->d_lockey, c->d_locchr, c->d_chroff };
     if (c->owns_index) for (void *p : ptrs) if (p) (void)hipFree(p);
-    void *own[] = { c->d_ctr, c->d_tops, c->d_err, c->d_sizes, c->d_input_bad };
-    for (void *p : own) if (p) (void)hipFree(p);
-    if (c->h_tail) (void)hipHostFree(c->h_tail);
-    c->seq.release(); c->seq_off.release(); c->rlen.release(); c->enc.release(); c->packed_in.release(); c->nlist_in.release(); c->hits.release(); c->nhits.release(); c->nseeds.release();
-    c->seed_off.release(); c->ncand.release(); c->rep_off.release(); c->tile_sums.release(); c->tile_read.release(); c->slow_units.release();
-    c->seeds.release(); c->work.release(); c->cands.release(); c->jobs.release(); c->job_items.release(); c->job_outs.release(); c->job_pool.release(); c->job_pool_next.release(); c->items.release(); c->hist.release(); c->heavy.release(); c->seed_heavy.release(); c->seed_heavy_sfail.release(); c->chain_picks.release(); c->chain_todo.release();
-    c->reads_out.release(); c->reports.release(); c->cigpool.release(); c->cigfinal.release(); c->sjpool.release(); c->sjfinal.release();
-    c->sam_hdr_off.release(); c->sam_qual_off.release(); c->sam_qlen.release(); c->sam_hdr.release(); c->sam_qual.release(); c->sam_text.release(); c->sam_read_off.release(); c->sam_tile.release();
-    if (c->d_sam_stat) (void)hipFree(c->d_sam_stat);
-    if (c->h_sam_stat) (void)hipHostFree(c->h_sam_stat);
-    for (hipEvent_t e : c->ev_sam) if (e) (void)hipEventDestroy(e);
-    c->bam_rec.release(); c->bgzf_in.release(); c->bgzf_slots.release(); c->bgzf_out.release(); c->bgzf_size.release(); c->bgzf_off.release();
-    if (c->d_bam_stat) (void)hipFree(c->d_bam_stat);
-    if (c->h_bam_stat) (void)hipHostFree(c->h_bam_stat);
-    for (hipEvent_t e : c->ev_bam) if (e) (void)hipEventDestroy(e);
-    if (c->sj_tab) (void)hipFree(c->sj_tab);
-    c->sj_ovf[0].release(); c->sj_ovf[1].release(); c->sj_in.release(); c->sj_entries.release(); c->sj_keys[0].release(); c->sj_keys[1].release(); c->sj_vals[0].release(); c->sj_vals[1].release();
-    c->sj_line_off.release(); c->sj_tile.release(); c->sj_hist.release(); c->sj_sums.release(); c->sj_text.release();
-    if (c->d_sj_stat) (void)hipFree(c->d_sj_stat);
-    if (c->h_sj_stat) (void)hipHostFree(c->h_sj_stat);
-    for (hipEvent_t e : c->ev_sj) if (e) (void)hipEventDestroy(e);
-    if (c->bs_rec) (void)hipFree(c->bs_rec);
-    if (c->bs_key) (void)hipFree(c->bs_key);
-    if (c->bs_off) (void)hipFree(c->bs_off);
-    c->bs_cnt_off.release(); c->bs_tile_cnt.release(); c->bs_hist.release(); c->bs_sums.release(); c->bs_k[0].release(); c->bs_k[1].release(); c->bs_v[0].release(); c->bs_v[1].release();
-    c->bs_tile.release(); c->bs_sorted.release();
-    for (DBuf<uint32_t> *b : {&c->bi_sizes, &c->bi_sizes_in, &c->bi_span, &c->bi_tile_cnt, &c->bi_chead, &c->bi_mhead, &c->bi_mbin, &c->bi_binq, &c->bi_ref_q, &c->bi_ref_b, &c->bi_hist, &c->bi_sums}) b->release();
-    for (DBuf<uint64_t> *b : {&c->bi_coff, &c->bi_key, &c->bi_voff, &c->bi_ck[0], &c->bi_ck[1], &c->bi_excl, &c->bi_ctile, &c->bi_ref_at, &c->bi_lin_at}) b->release();
-    c->bi_cv[0].release(); c->bi_cv[1].release(); c->bi_ref.release(); c->bi_lin.release(); c->bi_flag.release(); c->bi_out.release();
-    if (c->d_bi_stat) (void)hipFree(c->d_bi_stat);
-    if (c->h_bi_stat) (void)hipHostFree(c->h_bi_stat);
-    for (hipEvent_t e : c->ev_bi) if (e) (void)hipEventDestroy(e);
-    for (DBuf<uint32_t> *b : {&c->cv_blk_off, &c->cv_incl, &c->cv_dep_tile, &c->cv_tile_prev, &c->cv_mark, &c->cv_bp_depth, &c->cv_ent_bp, &c->cv_line_off, &c->cv_hist, &c->cv_sums}) b->release();
-    for (DBuf<uint64_t> *b : {&c->cv_blk_tile, &c->cv_k[0], &c->cv_k[1], &c->cv_tile_last, &c->cv_cnt_tile, &c->cv_bp_key, &c->cv_line_tile, &c->cv_part}) b->release();
-    c->cv_v[0].release(); c->cv_v[1].release(); c->cv_entries.release(); c->cv_text.release();
-    if (c->d_cv_stat) (void)hipFree(c->d_cv_stat);
-    if (c->h_cv_stat) (void)hipHostFree(c->h_cv_stat);
-    for (hipEvent_t e : c->ev_cv) if (e) (void)hipEventDestroy(e);
-    for (DBuf<uint64_t> *b : {&c->md_E, &c->md_h, &c->md_tile, &c->md_junk, &c->md_part, &c->md_tile_last, &c->md_k[0], &c->md_k[1], &c->md_ek[0], &c->md_ek[1]}) b->release();
-    for (DBuf<uint32_t> *b : {&c->md_score, &c->md_mate, &c->md_cand_off, &c->md_cnt_off, &c->md_tile_prev, &c->md_hist, &c->md_sums}) b->release();
-    c->md_v[0].release(); c->md_v[1].release(); c->md_ev[0].release(); c->md_ev[1].release();
-    if (c->d_md_stat) (void)hipFree(c->d_md_stat);
-    if (c->h_md_stat) (void)hipHostFree(c->h_md_stat);
-    for (hipEvent_t e : c->ev_md) if (e) (void)hipEventDestroy(e);
-    if (c->gc_counts) (void)hipFree(c->gc_counts);
-    c->gc_wg.release(); c->gc_in.release(); c->gc_in_reads.release(); c->gc_in_rep.release(); c->gc_in_cig.release();
-    for (hipEvent_t e : c->ev_gc) if (e) (void)hipEventDestroy(e);
-    if (c->d_bs_stat) (void)hipFree(c->d_bs_stat);
-    if (c->h_bs_stat) (void)hipHostFree(c->h_bs_stat);
-    for (hipEvent_t e : c->ev_bs) if (e) (void)hipEventDestroy(e);
-    c->fq_text.release(); c->fq_lines.release(); c->fq_tile_cnt.release(); c->fq_name_at.release(); c->fq_name_len.release(); c->fq_loc.release(); c->fq_hdr_off.release(); c->fq_qual_off.release();
-    c->fq_tile_sum.release(); c->fq_hdr.release(); c->fq_qual.release();
-    if (c->d_fq_info) (void)hipFree(c->d_fq_info);
-    if (c->h_fq_info) (void)hipHostFree(c->h_fq_info);
-    for (hipEvent_t e : c->ev_fq) if (e) (void)hipEventDestroy(e);
-    c->inf_in.release(); c->inf_out.release(); c->fq_tail.release(); c->inf_tab.release(); c->inf_status.release();
-    if (c->d_inf_verdict) (void)hipFree(c->d_inf_verdict);
-    if (c->h_inf_verdict) (void)hipHostFree(c->h_inf_verdict);
-    for (hipEvent_t e : c->ev_inf) if (e) (void)hipEventDestroy(e);
-    c->ws.release(); c->scan_state.release(); c->scan_trace.release(); c->reads_c.release(); c->reports_c.release(); c->cig_c.release();
-    for (int i = 0; i <= N_TIMERS; i++) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
-    if (c->ev_wait) (void)hipEventDestroy(c->ev_wait);
-    if (c->ev_dl) (void)hipEventDestroy(c->ev_dl);
-    if (c->ev_dl_block) (void)hipEventDestroy(c->ev_dl_block);
     if (c->stream) { (void)hipStreamDestroy(c->stream); g_live_ctx[c->device & 63].fetch_sub(1); }
-    if (c->owns_shared_caps) delete c->shared_caps;
-    delete c;
+    delete c;                      // everything else the context owns frees itself (api_ctx.h): the device is current, the stream has been waited for
 }
 
 // per-context objects that dg_init and dg_clone both need
 static hipError_t make_ctx_objects(dg_ctx *c)
 {
     hipError_t e;
-    for (int i = 0; i <= N_TIMERS; i++) c->ev[i] = nullptr;
     if ((e = hipStreamCreate(&c->stream)) != hipSuccess) return e;
     g_live_ctx[c->device & 63].fetch_add(1);
     if ((e = hipEventCreateWithFlags(&c->ev_wait, hipEventBlockingSync | hipEventDisableTiming)) != hipSuccess ||
@@ -1172,8 +1029,8 @@ static int enqueue_upload(dg_ctx *c, int n_reads, const uint32_t *seq_off, const
         mx = rlen[i] > mx ? rlen[i] : mx;
     }
     if (mx > DG_MAX_RLEN) { snprintf(c->err, 512, "a read is longer than DG_MAX_RLEN (%d)", DG_MAX_RLEN); return DG_ERR_ARG; }
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->gc_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
-    c->no_batch = false; c->inf_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
+    c->no_batch = false; c->inf.valid = false;
     HIPCHK(c->seq.ensure(bytes + 64));     /* the kernels read up to 24 bytes at a read position in one go */
     HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     if (n_reads) {
@@ -1235,8 +1092,8 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
     if (mx > DG_MAX_RLEN || mx > 16 * W2 || (size_t)n_reads * 16 * W2 > 0xFFFFFFF0ull) { snprintf(c->err, 512, "packed batch: read length %d does not fit %d words (or exceeds DG_MAX_RLEN / 2^32 bases)", mx, W2); return DG_ERR_ARG; }
     if (n_reads && (mx + 15) / 16 != W2) { snprintf(c->err, 512, "packed batch: words_per_read must be ceil(longest read / 16) = %d", (mx + 15) / 16); return DG_ERR_ARG; }
     const size_t nw = (size_t)n_reads * W2, bytes = nw * 16;
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->gc_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
-    c->no_batch = false; c->inf_valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
+    c->no_batch = false; c->inf.valid = false;
     HIPCHK(c->seq.ensure(bytes + 64)); HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     HIPCHK(c->enc.ensure(2 * nw + 16)); HIPCHK(c->packed_in.ensure(nw + 1)); HIPCHK(c->nlist_in.ensure(n_n + 1));
     c->enc_ready = true;
@@ -1266,17 +1123,13 @@ extern "C" int dg_batch_upload_packed(dg_ctx *c, int n_reads, int rlen_all, cons
 // ------------------------------------------------------------------------------------------
 extern "C" int dg_fastq_tile(void) { return FQ_TILE; }
 
-// The parser behind its input: the texts lie in c->fq_text, text 1 at 0 and text 2 at off2.  fq_reserve sizes every buffer from the arguments (nothing is asked
+// The parser behind its input: the texts lie in c->fq.text, text 1 at 0 and text 2 at off2.  fq_reserve sizes every buffer from the arguments (nothing is asked
 // of the device before the one wait), fq_enqueue launches the kernels, fq_finish waits for the sizes block and says what it holds.
 struct FqPlan { size_t n[2], off2, line_cap[2], tile_stride, reads_bound, len_tiles, max_reads, text_bytes; bool two; };
 
 static int fq_reserve(dg_ctx *c, FqPlan &p)
 {
-    if (!c->d_fq_info) {
-        HIPCHK(hipMalloc((void **)&c->d_fq_info, sizeof(FqInfo)));
-        HIPCHK(hipHostMalloc((void **)&c->h_fq_info, sizeof(FqInfo), hipHostMallocDefault));
-        for (hipEvent_t &e : c->ev_fq) HIPCHK(hipEventCreate(&e));
-    }
+    HIPCHK(c->fq.ready());
     // a record has at least one byte per existing line, so a text of n bytes holds at most n + 1 line starts; the three outputs together are never larger
     // than the texts
     const size_t max_reads = p.max_reads, n1 = p.n[0], n2 = p.n[1];
@@ -1288,9 +1141,9 @@ static int fq_reserve(dg_ctx *c, FqPlan &p)
     p.reads_bound = std::min(max_reads, (n1 + 4) / 4 + (n2 + 4) / 4);          // (records <= ceil(lines / 4), lines <= bytes + 1)
     p.len_tiles = std::max<size_t>(1, (p.reads_bound + FQ_THREADS - 1) / FQ_THREADS);
     const size_t reads_bound = p.reads_bound, text_bytes = p.text_bytes;
-    HIPCHK(c->fq_text.ensure(p.off2 + n2 + 32)); HIPCHK(c->fq_lines.ensure(p.line_cap[0] + p.line_cap[1] + 2)); HIPCHK(c->fq_tile_cnt.ensure(2 * p.tile_stride + 1));
-    HIPCHK(c->fq_name_at.ensure(reads_bound + 1)); HIPCHK(c->fq_name_len.ensure(reads_bound + 1)); HIPCHK(c->fq_loc.ensure(3 * (reads_bound + 1))); HIPCHK(c->fq_tile_sum.ensure(3 * p.len_tiles));
-    HIPCHK(c->fq_hdr_off.ensure(reads_bound + 1)); HIPCHK(c->fq_qual_off.ensure(reads_bound + 1)); HIPCHK(c->fq_hdr.ensure(text_bytes + 1)); HIPCHK(c->fq_qual.ensure(text_bytes + 1));
+    HIPCHK(c->fq.text.ensure(p.off2 + n2 + 32)); HIPCHK(c->fq.lines.ensure(p.line_cap[0] + p.line_cap[1] + 2)); HIPCHK(c->fq.tile_cnt.ensure(2 * p.tile_stride + 1));
+    HIPCHK(c->fq.name_at.ensure(reads_bound + 1)); HIPCHK(c->fq.name_len.ensure(reads_bound + 1)); HIPCHK(c->fq.loc.ensure(3 * (reads_bound + 1))); HIPCHK(c->fq.tile_sum.ensure(3 * p.len_tiles));
+    HIPCHK(c->fq.hdr_off.ensure(reads_bound + 1)); HIPCHK(c->fq.qual_off.ensure(reads_bound + 1)); HIPCHK(c->fq.hdr.ensure(text_bytes + 1)); HIPCHK(c->fq.qual.ensure(text_bytes + 1));
     HIPCHK(c->seq.ensure(text_bytes + 64)); HIPCHK(c->seq_off.ensure(reads_bound + 1)); HIPCHK(c->rlen.ensure(reads_bound + 1));
     return DG_OK;
 }
@@ -1299,32 +1152,32 @@ static int fq_reserve(dg_ctx *c, FqPlan &p)
 static int fq_enqueue(dg_ctx *c, const FqPlan &p, int rc_odd_reads, bool whole, bool pieces, bool write)
 {
     FqText x;
-    x.t[0] = c->fq_text.p; x.t[1] = c->fq_text.p + p.off2; x.n[0] = (uint32_t)p.n[0]; x.n[1] = (uint32_t)p.n[1];
-    x.line_start[0] = c->fq_lines.p; x.line_start[1] = c->fq_lines.p + p.line_cap[0] + 1; x.line_cap[0] = (uint32_t)p.line_cap[0]; x.line_cap[1] = (uint32_t)p.line_cap[1];
+    x.t[0] = c->fq.text.p; x.t[1] = c->fq.text.p + p.off2; x.n[0] = (uint32_t)p.n[0]; x.n[1] = (uint32_t)p.n[1];
+    x.line_start[0] = c->fq.lines.p; x.line_start[1] = c->fq.lines.p + p.line_cap[0] + 1; x.line_cap[0] = (uint32_t)p.line_cap[0]; x.line_cap[1] = (uint32_t)p.line_cap[1];
     x.two = p.two ? 1 : 0;
     const uint32_t stride = (uint32_t)(p.reads_bound + 1);
     const dim3 text_grid((unsigned)std::max<size_t>(1, p.tile_stride), p.two ? 2u : 1u);
-    k_fq_count<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)p.tile_stride);
-    k_fq_top<<<1, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)p.tile_stride, (uint32_t)p.max_reads, c->d_fq_info, whole ? 1 : 0);
-    k_fq_lines<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq_tile_cnt.p, (uint32_t)p.tile_stride, c->d_fq_info);
-    if (whole) k_fq_tail<<<dim3(64, p.two ? 2u : 1u), FQ_THREADS, 0, c->stream>>>(x, c->d_fq_info, c->fq_tail.p, (uint32_t)c->fq_tail_off2);
-    if (pieces && p.reads_bound) k_fq_unlike<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->d_fq_info);
-    k_fq_len<<<(unsigned)p.len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->d_fq_info, c->rlen.p, c->fq_name_at.p, c->fq_name_len.p, c->fq_loc.p, stride, c->fq_tile_sum.p, (uint32_t)p.len_tiles);
-    k_fq_top3<<<1, FQ_THREADS, 0, c->stream>>>(c->fq_tile_sum.p, (uint32_t)p.len_tiles, c->d_fq_info);
+    k_fq_count<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq.tile_cnt.p, (uint32_t)p.tile_stride);
+    k_fq_top<<<1, FQ_THREADS, 0, c->stream>>>(x, c->fq.tile_cnt.p, (uint32_t)p.tile_stride, (uint32_t)p.max_reads, c->fq.info.d, whole ? 1 : 0);
+    k_fq_lines<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq.tile_cnt.p, (uint32_t)p.tile_stride, c->fq.info.d);
+    if (whole) k_fq_tail<<<dim3(64, p.two ? 2u : 1u), FQ_THREADS, 0, c->stream>>>(x, c->fq.info.d, c->fq.tail.p, (uint32_t)c->fq.tail_off2);
+    if (pieces && p.reads_bound) k_fq_unlike<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d);
+    k_fq_len<<<(unsigned)p.len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->fq.info.d, c->rlen.p, c->fq.name_at.p, c->fq.name_len.p, c->fq.loc.p, stride, c->fq.tile_sum.p, (uint32_t)p.len_tiles);
+    k_fq_top3<<<1, FQ_THREADS, 0, c->stream>>>(c->fq.tile_sum.p, (uint32_t)p.len_tiles, c->fq.info.d);
     if (p.reads_bound && write)
-        k_fq_write<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->d_fq_info, rc_odd_reads ? 1 : 0, c->rlen.p, c->fq_name_at.p, c->fq_name_len.p, c->fq_loc.p, stride, c->fq_tile_sum.p,
-                                                                   (uint32_t)p.len_tiles, c->seq_off.p, c->seq.p, c->fq_hdr_off.p, c->fq_hdr.p, c->fq_qual_off.p, c->fq_qual.p);
+        k_fq_write<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d, rc_odd_reads ? 1 : 0, c->rlen.p, c->fq.name_at.p, c->fq.name_len.p, c->fq.loc.p, stride, c->fq.tile_sum.p,
+                                                                   (uint32_t)p.len_tiles, c->seq_off.p, c->seq.p, c->fq.hdr_off.p, c->fq.hdr.p, c->fq.qual_off.p, c->fq.qual.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_fq[1], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_fq_info, c->d_fq_info, sizeof(FqInfo), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->fq.ev[1], c->stream));
+    HIPCHK(c->fq.info.fetch(c->stream));
     return DG_OK;
 }
 
 // behind the wait: the sizes block's verdict; keep: the context holds the batch from here on
 static int fq_finish(dg_ctx *c, const char *fn, int max_reads, int *n_reads_out, bool keep)
 {
-    (void)hipEventElapsedTime(&c->fq_ms, c->ev_fq[0], c->ev_fq[1]);
-    const FqInfo &fi = *c->h_fq_info;
+    c->fq.ms = c->fq.ev.ms(0, 1);
+    const FqInfo &fi = *c->fq.info.h;
     if (n_reads_out) *n_reads_out = (int)std::min<uint32_t>(fi.n_reads, 0x7FFFFFFFu);
     switch (fi.status) {
     case FQ_OK: break;
@@ -1346,16 +1199,16 @@ static int fq_finish(dg_ctx *c, const char *fn, int max_reads, int *n_reads_out,
     }
     if (!keep) return DG_OK;
     c->n_reads = (int)fi.n_reads; c->max_rlen = (int)fi.max_rlen; c->seq_bytes = (size_t)fi.total[0];
-    c->fq_hdr_bytes = (size_t)fi.total[1]; c->fq_qual_bytes = (size_t)fi.total[2]; c->fq_valid = true;
+    c->fq.hdr_bytes = (size_t)fi.total[1]; c->fq.qual_bytes = (size_t)fi.total[2]; c->fq.valid = true;
     return DG_OK;
 }
 
 // whatever happens in an upload of FASTQ text, the context holds no batch until the call has succeeded
 static void fq_forget_batch(dg_ctx *c)
 {
-    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj_batch_counted = false; c->gc_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false; c->fq_valid = false;
-    c->fq_hdr_bytes = c->fq_qual_bytes = 0; c->fq_ms = 0.f;
-    c->no_batch = false; c->inf_valid = false; c->fq_tail_valid = false; c->fq_tail_n[0] = c->fq_tail_n[1] = 0;
+    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
+    c->fq.hdr_bytes = c->fq.qual_bytes = 0; c->fq.ms = 0.f;
+    c->no_batch = false; c->inf.valid = false; c->fq.tail_valid = false; c->fq.tail_n[0] = c->fq.tail_n[1] = 0;
 }
 
 extern "C" int dg_batch_upload_fastq(dg_ctx *c, const dg_fastq_text *in, int *n_reads_out)
@@ -1368,14 +1221,14 @@ extern "C" int dg_batch_upload_fastq(dg_ctx *c, const dg_fastq_text *in, int *n_
     const bool two = in->text2 != nullptr && in->n2 > 0;
     if ((in->n1 && !in->text1) || in->max_reads < 0) { snprintf(c->err, 512, "dg_batch_upload_fastq: text1 is NULL or max_reads is negative"); return DG_ERR_ARG; }
     if (n1 >= 0xFFFFFF00ull || n2 >= 0xFFFFFF00ull) { snprintf(c->err, 512, "dg_batch_upload_fastq: a text must be smaller than 2^32 - 256 bytes"); return DG_ERR_ARG; }
-    if (n1 == 0 && !two) { c->fq_valid = true; return DG_OK; }       // no text: no reads
+    if (n1 == 0 && !two) { c->fq.valid = true; return DG_OK; }       // no text: no reads
     HIPCHK(hipSetDevice(c->device));
     FqPlan p;
     p.n[0] = n1; p.n[1] = n2; p.two = two; p.max_reads = (size_t)in->max_reads;
     { const int rc = fq_reserve(c, p); if (rc) return rc; }
-    if (n1) HIPCHK(hipMemcpyAsync(c->fq_text.p, in->text1, n1, hipMemcpyHostToDevice, c->stream));
-    if (n2) HIPCHK(hipMemcpyAsync(c->fq_text.p + p.off2, in->text2, n2, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev_fq[0], c->stream));
+    if (n1) HIPCHK(hipMemcpyAsync(c->fq.text.p, in->text1, n1, hipMemcpyHostToDevice, c->stream));
+    if (n2) HIPCHK(hipMemcpyAsync(c->fq.text.p + p.off2, in->text2, n2, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->fq.ev[0], c->stream));
     { const int rc = fq_enqueue(c, p, in->rc_odd_reads, false, false, true); if (rc) return rc; }
     HIPCHK(wait_stream(c));                                       // the one wait: for the sizes block
     return fq_finish(c, "dg_batch_upload_fastq", in->max_reads, n_reads_out, true);
@@ -1384,30 +1237,21 @@ extern "C" int dg_batch_upload_fastq(dg_ctx *c, const dg_fastq_text *in, int *n_
 // ------------------------------------------------------------------------------------------
 // BGZF inflated on the device (dg_inflate.h): whole blocks in host memory -> their bytes in HBM; and in front of the FASTQ parser
 // ------------------------------------------------------------------------------------------
-static int inf_state(dg_ctx *c)
-{
-    if (c->d_inf_verdict) return DG_OK;
-    HIPCHK(hipMalloc((void **)&c->d_inf_verdict, 8));
-    HIPCHK(hipHostMalloc((void **)&c->h_inf_verdict, 8, hipHostMallocDefault));
-    for (hipEvent_t &e : c->ev_inf) HIPCHK(hipEventCreate(&e));
-    return DG_OK;
-}
-
-// the compressed bytes of up to two inputs (the second at in_off2 of inf_in) and the table go up; the kernel writes at d_out + the members' out_off
+// the compressed bytes of up to two inputs (the second at in_off2 of inf.in) and the table go up; the kernel writes at d_out + the members' out_off
 static int inf_enqueue_copies(dg_ctx *c, const std::vector<InfBlock> &tab, const void *src1, size_t n1, const void *src2, size_t n2, size_t in_off2)
 {
-    HIPCHK(c->inf_in.ensure(std::max(n1, in_off2 + n2) + 8)); HIPCHK(c->inf_tab.ensure(tab.size() + 1)); HIPCHK(c->inf_status.ensure(tab.size() + 1));
-    if (n1) HIPCHK(hipMemcpyAsync(c->inf_in.p, src1, n1, hipMemcpyHostToDevice, c->stream));
-    if (n2) HIPCHK(hipMemcpyAsync(c->inf_in.p + in_off2, src2, n2, hipMemcpyHostToDevice, c->stream));
-    if (!tab.empty()) HIPCHK(hipMemcpyAsync(c->inf_tab.p, tab.data(), tab.size() * sizeof(InfBlock), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_inf_verdict, 0xff, 8, c->stream));
+    HIPCHK(c->inf.in.ensure(std::max(n1, in_off2 + n2) + 8)); HIPCHK(c->inf.tab.ensure(tab.size() + 1)); HIPCHK(c->inf.status.ensure(tab.size() + 1));
+    if (n1) HIPCHK(hipMemcpyAsync(c->inf.in.p, src1, n1, hipMemcpyHostToDevice, c->stream));
+    if (n2) HIPCHK(hipMemcpyAsync(c->inf.in.p + in_off2, src2, n2, hipMemcpyHostToDevice, c->stream));
+    if (!tab.empty()) HIPCHK(hipMemcpyAsync(c->inf.tab.p, tab.data(), tab.size() * sizeof(InfBlock), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemsetAsync(c->inf.verdict.d, 0xff, 8, c->stream));
     return DG_OK;
 }
 static int inf_enqueue_kernel(dg_ctx *c, size_t n_blocks, unsigned char *d_out)
 {
-    if (n_blocks) k_bgzf_inflate<<<(unsigned)((n_blocks + INF_WAVES - 1) / INF_WAVES), 64 * INF_WAVES, 0, c->stream>>>(c->inf_in.p, c->inf_tab.p, (uint32_t)n_blocks, d_out, c->inf_status.p, c->d_inf_verdict);
+    if (n_blocks) k_bgzf_inflate<<<(unsigned)((n_blocks + INF_WAVES - 1) / INF_WAVES), 64 * INF_WAVES, 0, c->stream>>>(c->inf.in.p, c->inf.tab.p, (uint32_t)n_blocks, d_out, c->inf.status.p, c->inf.verdict.d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_inf_verdict, c->d_inf_verdict, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c->inf.verdict.fetch(c->stream));
     return DG_OK;
 }
 
@@ -1424,28 +1268,27 @@ extern "C" int dg_bgzf_inflate(dg_ctx *c, const void *host_bytes, size_t n, size
     if (n_out) *n_out = 0;
     if (n_blocks) *n_blocks = 0;
     if (device_ms) *device_ms = 0.f;
-    c->inf_valid = false; c->inf_bytes = 0;
-    if (n == 0) { c->inf_valid = true; return DG_OK; }
+    c->inf.valid = false; c->inf.bytes = 0;
+    if (n == 0) { c->inf.valid = true; return DG_OK; }
     if (!host_bytes) { snprintf(c->err, 512, "dg_bgzf_inflate: the input is NULL"); return DG_ERR_ARG; }
     std::vector<InfBlock> tab;
     size_t total = 0, bad = 0;
     if (const char *why = inf_walk_members((const unsigned char *)host_bytes, n, 0, 0, tab, &total, &bad)) { snprintf(c->err, 512, "dg_bgzf_inflate: block %zu: %s", bad, why); return DG_ERR_ARG; }
     if (tab.size() > 0x7fffffffull) { snprintf(c->err, 512, "dg_bgzf_inflate: %zu blocks are more than one call takes", tab.size()); return DG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    { const int rc = inf_state(c); if (rc) return rc; }
-    HIPCHK(c->inf_out.ensure(total + 32));
+    HIPCHK(c->inf.ready());
+    HIPCHK(c->inf.out.ensure(total + 32));
     { const int rc = inf_enqueue_copies(c, tab, host_bytes, n, nullptr, 0, 0); if (rc) return rc; }
-    HIPCHK(hipEventRecord(c->ev_inf[0], c->stream));
-    { const int rc = inf_enqueue_kernel(c, tab.size(), c->inf_out.p); if (rc) return rc; }
-    HIPCHK(hipEventRecord(c->ev_inf[1], c->stream));
+    HIPCHK(hipEventRecord(c->inf.ev[0], c->stream));
+    { const int rc = inf_enqueue_kernel(c, tab.size(), c->inf.out.p); if (rc) return rc; }
+    HIPCHK(hipEventRecord(c->inf.ev[1], c->stream));
     HIPCHK(wait_stream(c));
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->ev_inf[0], c->ev_inf[1]);
+    const float ms = c->inf.ev.ms(0, 1);
     if (device_ms) *device_ms = ms;
     if (n_blocks) *n_blocks = tab.size();
-    const unsigned long long v = *c->h_inf_verdict;
+    const unsigned long long v = *c->inf.verdict.h;
     if (v != ~0ull) { snprintf(c->err, 512, "dg_bgzf_inflate: block %llu: %s", v >> 8, inf_rule((uint32_t)(v & 0xffu))); return DG_ERR_ARG; }
-    c->inf_valid = true; c->inf_bytes = total;
+    c->inf.valid = true; c->inf.bytes = total;
     if (n_out) *n_out = total;
     return DG_OK;
 }
@@ -1453,12 +1296,12 @@ extern "C" int dg_bgzf_inflate(dg_ctx *c, const void *host_bytes, size_t n, size
 extern "C" int dg_inflate_download(dg_ctx *c, void *out, size_t cap)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->inf_valid) { snprintf(c->err, 512, "dg_inflate_download: no inflated bytes (dg_bgzf_inflate first)"); return DG_ERR_ARG; }
-    if (cap < c->inf_bytes) { snprintf(c->err, 512, "dg_inflate_download: output capacity too small: %zu bytes of %zu", cap, c->inf_bytes); return DG_ERR_CAPACITY; }
-    if (c->inf_bytes == 0) return DG_OK;
+    if (!c->inf.valid) { snprintf(c->err, 512, "dg_inflate_download: no inflated bytes (dg_bgzf_inflate first)"); return DG_ERR_ARG; }
+    if (cap < c->inf.bytes) { snprintf(c->err, 512, "dg_inflate_download: output capacity too small: %zu bytes of %zu", cap, c->inf.bytes); return DG_ERR_CAPACITY; }
+    if (c->inf.bytes == 0) return DG_OK;
     if (!out) return DG_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(out, c->inf_out.p, c->inf_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->inf.out.p, c->inf.bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
@@ -1466,8 +1309,8 @@ extern "C" int dg_inflate_download(dg_ctx *c, void *out, size_t cap)
 extern "C" int dg_inflate_device(dg_ctx *c, void **ptr, size_t *n_out)
 {
     if (!c || !ptr || !n_out) return DG_ERR_ARG;
-    if (!c->inf_valid) { snprintf(c->err, 512, "dg_inflate_device: no inflated bytes (dg_bgzf_inflate first)"); return DG_ERR_ARG; }
-    *ptr = c->inf_bytes ? c->inf_out.p : nullptr; *n_out = c->inf_bytes;
+    if (!c->inf.valid) { snprintf(c->err, 512, "dg_inflate_device: no inflated bytes (dg_bgzf_inflate first)"); return DG_ERR_ARG; }
+    *ptr = c->inf.bytes ? c->inf.out.p : nullptr; *n_out = c->inf.bytes;
     return DG_OK;
 }
 
@@ -1485,7 +1328,7 @@ extern "C" int dg_batch_upload_fastq_bgzf(dg_ctx *c, const dg_fastq_bgzf *in, ui
     if ((in->n_head1 && !in->head1) || (in->n_blocks1 && !in->blocks1) || (in->n_head2 && !in->head2) || (in->n_blocks2 && !in->blocks2) || in->max_reads < 0) {
         snprintf(c->err, 512, "%s: a length without its pointer, or max_reads is negative", fn); return DG_ERR_ARG;
     }
-    // the members of both inputs, before anything is enqueued: text f = head f ++ its blocks' bytes, in fq_text at 0 / off2
+    // the members of both inputs, before anything is enqueued: text f = head f ++ its blocks' bytes, in fq.text at 0 / off2
     const size_t nh[2] = { in->head1 ? in->n_head1 : 0, in->head2 ? in->n_head2 : 0 }, nb[2] = { in->blocks1 ? in->n_blocks1 : 0, two && in->blocks2 ? in->n_blocks2 : 0 };
     const unsigned char *src[2] = { (const unsigned char *)in->blocks1, (const unsigned char *)in->blocks2 };
     const size_t in_off2 = (nb[0] + 255) & ~(size_t)255;
@@ -1501,33 +1344,33 @@ extern "C" int dg_batch_upload_fastq_bgzf(dg_ctx *c, const dg_fastq_bgzf *in, ui
     if (tab.size() > 0x7fffffffull) { snprintf(c->err, 512, "%s: %zu blocks are more than one call takes", fn, tab.size()); return DG_ERR_ARG; }
     FqPlan p;
     p.n[0] = nh[0] + n_inf[0]; p.n[1] = nh[1] + n_inf[1]; p.two = two; p.max_reads = (size_t)in->max_reads;
-    if (p.n[0] == 0 && p.n[1] == 0) { c->fq_valid = !check_only; c->no_batch = check_only; c->fq_tail_valid = true; return DG_OK; }       // no text: no reads, no tails
+    if (p.n[0] == 0 && p.n[1] == 0) { c->fq.valid = !check_only; c->no_batch = check_only; c->fq.tail_valid = true; return DG_OK; }       // no text: no reads, no tails
     HIPCHK(hipSetDevice(c->device));
-    { const int rc = inf_state(c); if (rc) return rc; }
+    HIPCHK(c->inf.ready());
     { const int rc = fq_reserve(c, p); if (rc) return rc; }
     for (size_t k = first2; k < tab.size(); k++) tab[k].out_off += p.off2;
-    c->fq_tail_off2 = (p.n[0] + 255) & ~(size_t)255;
-    HIPCHK(c->fq_tail.ensure(c->fq_tail_off2 + p.n[1] + 16));
+    c->fq.tail_off2 = (p.n[0] + 255) & ~(size_t)255;
+    HIPCHK(c->fq.tail.ensure(c->fq.tail_off2 + p.n[1] + 16));
     { const int rc = inf_enqueue_copies(c, tab, src[0], nb[0], src[1], nb[1], in_off2); if (rc) return rc; }
-    if (nh[0]) HIPCHK(hipMemcpyAsync(c->fq_text.p, in->head1, nh[0], hipMemcpyHostToDevice, c->stream));
-    if (nh[1]) HIPCHK(hipMemcpyAsync(c->fq_text.p + p.off2, in->head2, nh[1], hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev_fq[0], c->stream));
-    { const int rc = inf_enqueue_kernel(c, tab.size(), c->fq_text.p); if (rc) return rc; }
+    if (nh[0]) HIPCHK(hipMemcpyAsync(c->fq.text.p, in->head1, nh[0], hipMemcpyHostToDevice, c->stream));
+    if (nh[1]) HIPCHK(hipMemcpyAsync(c->fq.text.p + p.off2, in->head2, nh[1], hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->fq.ev[0], c->stream));
+    { const int rc = inf_enqueue_kernel(c, tab.size(), c->fq.text.p); if (rc) return rc; }
     { const int rc = fq_enqueue(c, p, in->rc_odd_reads, !last, true, !check_only); if (rc) return rc; }
     HIPCHK(wait_stream(c));                                       // the one wait: for the first failing block and the sizes block
-    const unsigned long long v = *c->h_inf_verdict;
+    const unsigned long long v = *c->inf.verdict.h;
     if (v != ~0ull) {                                             // (the parser ran over bytes that mean nothing: its verdict is not looked at)
         const size_t k = (size_t)(v >> 8);
         snprintf(c->err, 512, "%s: text %d block %zu: %s", fn, k >= first2 ? 2 : 1, k >= first2 ? k - first2 : k, inf_rule((uint32_t)(v & 0xffu)));
         return DG_ERR_ARG;
     }
-    const FqInfo &fi = *c->h_fq_info;
+    const FqInfo &fi = *c->fq.info.h;
     if (n_unlike) *n_unlike = fi.n_unlike;
     const int rc = fq_finish(c, fn, in->max_reads, n_reads_out, !check_only);
     if (fi.status == FQ_OK || fi.status == FQ_E_EMPTY || fi.status == FQ_E_LONG || fi.status == FQ_E_OFFSETS) {      // the lines were found: the tails are known
-        c->fq_tail_n[0] = p.n[0] - fi.tail_at[0]; c->fq_tail_n[1] = two ? p.n[1] - fi.tail_at[1] : 0;
-        c->fq_tail_valid = true;
-        if (tail) { tail[0] = c->fq_tail_n[0]; tail[1] = c->fq_tail_n[1]; }
+        c->fq.tail_n[0] = p.n[0] - fi.tail_at[0]; c->fq.tail_n[1] = two ? p.n[1] - fi.tail_at[1] : 0;
+        c->fq.tail_valid = true;
+        if (tail) { tail[0] = c->fq.tail_n[0]; tail[1] = c->fq.tail_n[1]; }
     }
     if (rc == DG_OK && check_only) c->no_batch = true;
     return rc;
@@ -1536,13 +1379,13 @@ extern "C" int dg_batch_upload_fastq_bgzf(dg_ctx *c, const dg_fastq_bgzf *in, ui
 extern "C" int dg_batch_download_fastq_tail(dg_ctx *c, char *tail1, size_t cap1, char *tail2, size_t cap2)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->fq_tail_valid) { snprintf(c->err, 512, "dg_batch_download_fastq_tail: no tails (dg_batch_upload_fastq_bgzf first)"); return DG_ERR_ARG; }
-    if (cap1 < c->fq_tail_n[0] || cap2 < c->fq_tail_n[1]) { snprintf(c->err, 512, "dg_batch_download_fastq_tail: output capacity too small (need %zu %zu)", c->fq_tail_n[0], c->fq_tail_n[1]); return DG_ERR_CAPACITY; }
-    if ((c->fq_tail_n[0] && !tail1) || (c->fq_tail_n[1] && !tail2)) return DG_ERR_ARG;
-    if (!c->fq_tail_n[0] && !c->fq_tail_n[1]) return DG_OK;
+    if (!c->fq.tail_valid) { snprintf(c->err, 512, "dg_batch_download_fastq_tail: no tails (dg_batch_upload_fastq_bgzf first)"); return DG_ERR_ARG; }
+    if (cap1 < c->fq.tail_n[0] || cap2 < c->fq.tail_n[1]) { snprintf(c->err, 512, "dg_batch_download_fastq_tail: output capacity too small (need %zu %zu)", c->fq.tail_n[0], c->fq.tail_n[1]); return DG_ERR_CAPACITY; }
+    if ((c->fq.tail_n[0] && !tail1) || (c->fq.tail_n[1] && !tail2)) return DG_ERR_ARG;
+    if (!c->fq.tail_n[0] && !c->fq.tail_n[1]) return DG_OK;
     HIPCHK(hipSetDevice(c->device));
-    if (c->fq_tail_n[0]) HIPCHK(hipMemcpyAsync(tail1, c->fq_tail.p, c->fq_tail_n[0], hipMemcpyDeviceToHost, c->stream));
-    if (c->fq_tail_n[1]) HIPCHK(hipMemcpyAsync(tail2, c->fq_tail.p + c->fq_tail_off2, c->fq_tail_n[1], hipMemcpyDeviceToHost, c->stream));
+    if (c->fq.tail_n[0]) HIPCHK(hipMemcpyAsync(tail1, c->fq.tail.p, c->fq.tail_n[0], hipMemcpyDeviceToHost, c->stream));
+    if (c->fq.tail_n[1]) HIPCHK(hipMemcpyAsync(tail2, c->fq.tail.p + c->fq.tail_off2, c->fq.tail_n[1], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
@@ -1550,7 +1393,7 @@ extern "C" int dg_batch_download_fastq_tail(dg_ctx *c, char *tail1, size_t cap1,
 extern "C" int dg_batch_fastq_device_ms(dg_ctx *c, float *ms)
 {
     if (!c || !ms) return DG_ERR_ARG;
-    *ms = c->fq_ms;
+    *ms = c->fq.ms;
     return DG_OK;
 }
 
@@ -1558,8 +1401,8 @@ extern "C" int dg_batch_download_reads(dg_ctx *c, uint32_t *seq_off, uint16_t *r
                                        const size_t caps[3], size_t used[3])
 {
     if (!c || !caps || !used) return DG_ERR_ARG;
-    if (!c->fq_valid) { snprintf(c->err, 512, "dg_batch_download_reads: the context's last upload was not dg_batch_upload_fastq"); return DG_ERR_ARG; }
-    used[0] = c->seq_bytes; used[1] = c->fq_hdr_bytes; used[2] = c->fq_qual_bytes;
+    if (!c->fq.valid) { snprintf(c->err, 512, "dg_batch_download_reads: the context's last upload was not dg_batch_upload_fastq"); return DG_ERR_ARG; }
+    used[0] = c->seq_bytes; used[1] = c->fq.hdr_bytes; used[2] = c->fq.qual_bytes;
     if (caps[0] < used[0] || caps[1] < used[1] || caps[2] < used[2]) { snprintf(c->err, 512, "dg_batch_download_reads: output capacity too small (need %zu %zu %zu)", used[0], used[1], used[2]); return DG_ERR_CAPACITY; }
     const size_t n = (size_t)c->n_reads;
     if (n == 0) { if (hdr_off) hdr_off[0] = 0; if (qual_off) qual_off[0] = 0; return DG_OK; }
@@ -1567,11 +1410,11 @@ extern "C" int dg_batch_download_reads(dg_ctx *c, uint32_t *seq_off, uint16_t *r
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(seq_off, c->seq_off.p, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(rlen, c->rlen.p, n * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(hdr_off, c->fq_hdr_off.p, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(qual_off, c->fq_qual_off.p, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(hdr_off, c->fq.hdr_off.p, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(qual_off, c->fq.qual_off.p, (n + 1) * 4, hipMemcpyDeviceToHost, c->stream));
     if (used[0]) HIPCHK(hipMemcpyAsync(seq, c->seq.p, used[0], hipMemcpyDeviceToHost, c->stream));
-    if (used[1]) HIPCHK(hipMemcpyAsync(hdr, c->fq_hdr.p, used[1], hipMemcpyDeviceToHost, c->stream));
-    if (used[2]) HIPCHK(hipMemcpyAsync(qual, c->fq_qual.p, used[2], hipMemcpyDeviceToHost, c->stream));
+    if (used[1]) HIPCHK(hipMemcpyAsync(hdr, c->fq.hdr.p, used[1], hipMemcpyDeviceToHost, c->stream));
+    if (used[2]) HIPCHK(hipMemcpyAsync(qual, c->fq.qual.p, used[2], hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
@@ -1994,12 +1837,12 @@ extern "C" int dg_batch_run(dg_ctx *c, size_t used[3])
     if (!c) return DG_ERR_ARG;
     if (c->no_batch) { snprintf(c->err, 512, "dg_batch_run: the context holds no batch (its last upload was a DG_FQ_CHECK_ONLY)"); return DG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    c->inf_valid = false;
+    c->inf.valid = false;
     c->used[0] = c->used[1] = c->used[2] = 0;
     memset(c->counters, 0, sizeof c->counters);
     if (used) used[0] = used[1] = used[2] = 0;
     c->n_t = 0;
-    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sj_batch_counted = false; c->gc_batch_counted = false; c->sam_valid = false; c->bam_valid = false; c->bam_rec_valid = false; c->bam_rec_stored = false;
+    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false;
     if (c->n_reads == 0) { c->batch_done = true; return DG_OK; }
     c->attempt_no = 0;
     int rc = enqueue_run(c);
@@ -2115,14 +1958,14 @@ extern "C" int dg_map_batch_compact(dg_ctx *c, int n_reads, const uint32_t *seq_
 static int ensure_full_records(dg_ctx *c)
 {
     if (c->full_valid || c->n_reads == 0) return DG_OK;
-    const bool keep = c->want_full, counted = c->sj_batch_counted, stored = c->bam_rec_stored, genes = c->gc_batch_counted;
+    const bool keep = c->want_full, counted = c->sj.batch_counted, stored = c->bam.rec_stored, genes = c->gc.batch_counted;
     c->want_full = true;
     size_t used[3];
     const int rc = dg_batch_run(c, used);
     c->want_full = keep;
-    c->sj_batch_counted = counted;      // (the same batch, mapped again: its tuples are in the junction table already if they were before)
-    c->bam_rec_stored = stored;         // (and its BAM records in the sorted store)
-    c->gc_batch_counted = genes;        // (and its units in the gene table)
+    c->sj.batch_counted = counted;      // (the same batch, mapped again: its tuples are in the junction table already if they were before)
+    c->bam.rec_stored = stored;         // (and its BAM records in the sorted store)
+    c->gc.batch_counted = genes;        // (and its units in the gene table)
     return rc;
 }
 
@@ -2231,8 +2074,8 @@ static int sam_batch_ready(dg_ctx *c, int n_pair_mode, size_t *n_bytes, uint64_t
     if (n_bytes) *n_bytes = 0;
     if (counters) counters[0] = counters[1] = counters[2] = 0;
     if (device_ms) *device_ms = 0.f;
-    if (bam) { c->bam_valid = false; c->bam_bytes = 0; } else { c->sam_valid = false; c->sam_bytes = 0; }
-    c->bam_rec_valid = false;           // (both formatters write the per-read offsets dg_batch_accumulate_bam walks)
+    if (bam) { c->bam.valid = false; c->bam.bytes = 0; } else { c->sam.valid = false; c->sam.bytes = 0; }
+    c->bam.rec_valid = false;           // (both formatters write the per-read offsets dg_batch_accumulate_bam walks)
     if (!c->batch_done) { snprintf(c->err, 512, "%s: the context has no finished batch (upload and run one first)", fn); return DG_ERR_ARG; }
     const int n = c->n_reads;
     if (n_pair_mode < 0 || (n_pair_mode & 1) || n_pair_mode > n) { snprintf(c->err, 512, "%s: n_pair_mode %d must be even and at most the batch's %d reads", fn, n_pair_mode, n); return DG_ERR_ARG; }
@@ -2251,18 +2094,14 @@ static int sam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr
 {
     const int n = c->n_reads;
     IndexShared *sh = c->shared_ix;
-    if (!c->d_sam_stat) {
-        HIPCHK(hipMalloc((void **)&c->d_sam_stat, 4 * 8));
-        HIPCHK(hipHostMalloc((void **)&c->h_sam_stat, 4 * 8, hipHostMallocDefault));
-        for (hipEvent_t &e : c->ev_sam) HIPCHK(hipEventCreate(&e));
-    }
+    HIPCHK(c->sam.ready());
     const uint32_t n_tiles = (uint32_t)((n + SAM_LEN_THREADS - 1) / SAM_LEN_THREADS);
-    HIPCHK(c->sam_qlen.ensure((size_t)n)); HIPCHK(c->sam_read_off.ensure((size_t)n)); HIPCHK(c->sam_tile.ensure(n_tiles));
+    HIPCHK(c->sam.qlen.ensure((size_t)n)); HIPCHK(c->sam.read_off.ensure((size_t)n)); HIPCHK(c->sam.tile.ensure(n_tiles));
     // the text's capacity is a guess the first time (one line per read); when it was too small k_sam_write alone runs again -- never the batch
     size_t want = hdr_bytes + qual_bytes + c->seq_bytes + (size_t)n * 96;
     want += want / 8;
-    if (c->env_sam_first_cap && !c->sam_text.p) want = c->env_sam_first_cap;
-    if (c->sam_text.cap < want) HIPCHK(c->sam_text.ensure(want));
+    if (c->sam.first_cap && !c->sam.text.p) want = c->sam.first_cap;
+    if (c->sam.text.cap < want) HIPCHK(c->sam.text.ensure(want));
     SamBatch b;
     b.ro = c->reads_out.p; b.po = c->reports.p; b.cig = c->cigfinal.p;
     b.seq_off = c->seq_off.p; b.rlen = c->rlen.p; b.seq = c->seq.p;
@@ -2276,38 +2115,35 @@ static int sam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr
         // arrays under the same lock, waits for the device before it frees the old ones
         std::lock_guard<std::mutex> lk(sh->mu);
         b.chr_off = sh->d_chr_name_off; b.chr = sh->d_chr_names; names_gen = sh->chr_names_gen;
-        b2 = b; b2.qlen = c->sam_qlen.p;
-        HIPCHK(hipEventRecord(c->ev_sam[0], c->stream));
-        HIPCHK(hipMemsetAsync(c->d_sam_stat, 0, 4 * 8, c->stream));
-        k_sam_len<<<n_tiles, SAM_LEN_THREADS, 0, c->stream>>>(b, c->sam_read_off.p, c->sam_qlen.p, c->sam_tile.p, c->d_sam_stat);
-        k_sam_top<<<1, 256, 0, c->stream>>>(c->sam_tile.p, n_tiles, c->d_sam_stat);
-        k_sam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam_read_off.p, c->sam_tile.p, c->d_sam_stat, (unsigned long long)c->sam_text.cap, c->sam_text.p);
+        b2 = b; b2.qlen = c->sam.qlen.p;
+        HIPCHK(hipEventRecord(c->sam.ev[0], c->stream));
+        HIPCHK(hipMemsetAsync(c->sam.stat.d, 0, 4 * 8, c->stream));
+        k_sam_len<<<n_tiles, SAM_LEN_THREADS, 0, c->stream>>>(b, c->sam.read_off.p, c->sam.qlen.p, c->sam.tile.p, c->sam.stat.d);
+        k_sam_top<<<1, 256, 0, c->stream>>>(c->sam.tile.p, n_tiles, c->sam.stat.d);
+        k_sam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam.read_off.p, c->sam.tile.p, c->sam.stat.d, (unsigned long long)c->sam.text.cap, c->sam.text.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->ev_sam[1], c->stream));
+        HIPCHK(hipEventRecord(c->sam.ev[1], c->stream));
     }
-    HIPCHK(hipMemcpyAsync(c->h_sam_stat, c->d_sam_stat, 4 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c->sam.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the one wait: for the size
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->ev_sam[0], c->ev_sam[1]);
-    const size_t total = (size_t)c->h_sam_stat[0];
-    if (total > c->sam_text.cap) {                                // the guess was too small (many lines per read): the lengths stand, the writer runs again
-        HIPCHK(c->sam_text.ensure(total));
+    float ms = c->sam.ev.ms(0, 1);
+    const size_t total = (size_t)c->sam.stat.h[0];
+    if (total > c->sam.text.cap) {                                // the guess was too small (many lines per read): the lengths stand, the writer runs again
+        HIPCHK(c->sam.text.ensure(total));
         {
             std::lock_guard<std::mutex> lk(sh->mu);
             if (names_gen != sh->chr_names_gen) { snprintf(c->err, 512, "dg_batch_format_sam: the chromosome names were replaced while the text was being formatted"); return DG_ERR_ARG; }
-            HIPCHK(hipEventRecord(c->ev_sam[0], c->stream));
-            k_sam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam_read_off.p, c->sam_tile.p, c->d_sam_stat, (unsigned long long)c->sam_text.cap, c->sam_text.p);
+            HIPCHK(hipEventRecord(c->sam.ev[0], c->stream));
+            k_sam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam.read_off.p, c->sam.tile.p, c->sam.stat.d, (unsigned long long)c->sam.text.cap, c->sam.text.p);
             HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(c->ev_sam[1], c->stream));
+            HIPCHK(hipEventRecord(c->sam.ev[1], c->stream));
         }
         HIPCHK(wait_stream(c));
-        float ms2 = 0.f;
-        (void)hipEventElapsedTime(&ms2, c->ev_sam[0], c->ev_sam[1]);
-        ms += ms2;
+        ms += c->sam.ev.ms(0, 1);
     }
-    c->sam_bytes = total; c->sam_valid = true;
+    c->sam.bytes = total; c->sam.valid = true;
     if (n_bytes) *n_bytes = total;
-    if (counters) { counters[0] = c->h_sam_stat[1]; counters[1] = c->h_sam_stat[2]; counters[2] = c->h_sam_stat[3]; }
+    if (counters) { counters[0] = c->sam.stat.h[1]; counters[1] = c->sam.stat.h[2]; counters[2] = c->sam.stat.h[3]; }
     if (device_ms) *device_ms = ms;
     return DG_OK;
 }
@@ -2319,28 +2155,28 @@ extern "C" int dg_batch_format_sam(dg_ctx *c, const dg_sam_text *in, uint32_t fl
         if (n_bytes) *n_bytes = 0;
         if (counters) counters[0] = counters[1] = counters[2] = 0;
         if (device_ms) *device_ms = 0.f;
-        c->sam_valid = false; c->sam_bytes = 0;
+        c->sam.valid = false; c->sam.bytes = 0;
         snprintf(c->err, 512, "dg_batch_format_sam: the input is NULL"); return DG_ERR_ARG;
     }
     const int rc = sam_batch_ready(c, in->n_pair_mode, n_bytes, counters, device_ms);
     if (rc) return rc;
     const int n = c->n_reads;
-    if (n == 0) { c->sam_valid = true; return DG_OK; }
+    if (n == 0) { c->sam.valid = true; return DG_OK; }
     if (!in->hdr_off || (in->qual && !in->qual_off)) { snprintf(c->err, 512, "dg_batch_format_sam: an offset array is NULL"); return DG_ERR_ARG; }
     if (sam_offsets_ok(c, "hdr_off", in->hdr_off, n) || (in->qual && sam_offsets_ok(c, "qual_off", in->qual_off, n))) return DG_ERR_ARG;
     const size_t hdr_bytes = (size_t)in->hdr_off[n] - in->hdr_off[0], qual_bytes = in->qual ? (size_t)in->qual_off[n] - in->qual_off[0] : 0;
     if (hdr_bytes && !in->hdr) { snprintf(c->err, 512, "dg_batch_format_sam: hdr is NULL"); return DG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(c->sam_hdr_off.ensure((size_t)n + 1)); HIPCHK(c->sam_hdr.ensure(hdr_bytes + 1));
-    if (in->qual) { HIPCHK(c->sam_qual_off.ensure((size_t)n + 1)); HIPCHK(c->sam_qual.ensure(qual_bytes + 1)); }
+    HIPCHK(c->sam.hdr_off.ensure((size_t)n + 1)); HIPCHK(c->sam.hdr.ensure(hdr_bytes + 1));
+    if (in->qual) { HIPCHK(c->sam.qual_off.ensure((size_t)n + 1)); HIPCHK(c->sam.qual.ensure(qual_bytes + 1)); }
     // offsets are taken relative to their first entry on the device: the kernels add them to pointers moved back by it
-    HIPCHK(hipMemcpyAsync(c->sam_hdr_off.p, in->hdr_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    if (hdr_bytes) HIPCHK(hipMemcpyAsync(c->sam_hdr.p, in->hdr + in->hdr_off[0], hdr_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->sam.hdr_off.p, in->hdr_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (hdr_bytes) HIPCHK(hipMemcpyAsync(c->sam.hdr.p, in->hdr + in->hdr_off[0], hdr_bytes, hipMemcpyHostToDevice, c->stream));
     if (in->qual) {
-        HIPCHK(hipMemcpyAsync(c->sam_qual_off.p, in->qual_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        if (qual_bytes) HIPCHK(hipMemcpyAsync(c->sam_qual.p, in->qual + in->qual_off[0], qual_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->sam.qual_off.p, in->qual_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (qual_bytes) HIPCHK(hipMemcpyAsync(c->sam.qual.p, in->qual + in->qual_off[0], qual_bytes, hipMemcpyHostToDevice, c->stream));
     }
-    return sam_format_device(c, c->sam_hdr_off.p, c->sam_hdr.p - in->hdr_off[0], in->qual ? c->sam_qual_off.p : nullptr, in->qual ? c->sam_qual.p - in->qual_off[0] : nullptr,
+    return sam_format_device(c, c->sam.hdr_off.p, c->sam.hdr.p - in->hdr_off[0], in->qual ? c->sam.qual_off.p : nullptr, in->qual ? c->sam.qual.p - in->qual_off[0] : nullptr,
                              hdr_bytes, qual_bytes, in->n_pair_mode, flags, n_bytes, counters, device_ms);
 }
 
@@ -2349,21 +2185,21 @@ extern "C" int dg_batch_format_sam_resident(dg_ctx *c, int n_pair_mode, uint32_t
     if (!c) return DG_ERR_ARG;
     const int rc = sam_batch_ready(c, n_pair_mode, n_bytes, counters, device_ms);
     if (rc) return rc;
-    if (!c->fq_valid) { snprintf(c->err, 512, "dg_batch_format_sam_resident: the context's last upload was not dg_batch_upload_fastq: no names and qualities in HBM"); return DG_ERR_ARG; }
-    if (c->n_reads == 0) { c->sam_valid = true; return DG_OK; }
+    if (!c->fq.valid) { snprintf(c->err, 512, "dg_batch_format_sam_resident: the context's last upload was not dg_batch_upload_fastq: no names and qualities in HBM"); return DG_ERR_ARG; }
+    if (c->n_reads == 0) { c->sam.valid = true; return DG_OK; }
     HIPCHK(hipSetDevice(c->device));
-    return sam_format_device(c, c->fq_hdr_off.p, c->fq_hdr.p, c->fq_qual_off.p, c->fq_qual.p, c->fq_hdr_bytes, c->fq_qual_bytes, n_pair_mode, flags, n_bytes, counters, device_ms);
+    return sam_format_device(c, c->fq.hdr_off.p, c->fq.hdr.p, c->fq.qual_off.p, c->fq.qual.p, c->fq.hdr_bytes, c->fq.qual_bytes, n_pair_mode, flags, n_bytes, counters, device_ms);
 }
 
 extern "C" int dg_batch_download_sam(dg_ctx *c, char *out, size_t cap)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->sam_valid) { snprintf(c->err, 512, "dg_batch_download_sam: no SAM text (dg_batch_format_sam first)"); return DG_ERR_ARG; }
-    if (cap < c->sam_bytes) { snprintf(c->err, 512, "dg_batch_download_sam: output capacity too small: %zu bytes of %zu", cap, c->sam_bytes); return DG_ERR_CAPACITY; }
-    if (c->sam_bytes == 0) return DG_OK;
+    if (!c->sam.valid) { snprintf(c->err, 512, "dg_batch_download_sam: no SAM text (dg_batch_format_sam first)"); return DG_ERR_ARG; }
+    if (cap < c->sam.bytes) { snprintf(c->err, 512, "dg_batch_download_sam: output capacity too small: %zu bytes of %zu", cap, c->sam.bytes); return DG_ERR_CAPACITY; }
+    if (c->sam.bytes == 0) return DG_OK;
     if (!out) return DG_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(out, c->sam_text.p, c->sam_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->sam.text.p, c->sam.bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
@@ -2371,24 +2207,15 @@ extern "C" int dg_batch_download_sam(dg_ctx *c, char *out, size_t cap)
 extern "C" int dg_batch_device_sam(dg_ctx *c, void **ptr, size_t *n_bytes)
 {
     if (!c || !ptr || !n_bytes) return DG_ERR_ARG;
-    if (!c->sam_valid) { snprintf(c->err, 512, "dg_batch_device_sam: no SAM text (dg_batch_format_sam first)"); return DG_ERR_ARG; }
-    *ptr = c->sam_bytes ? c->sam_text.p : nullptr; *n_bytes = c->sam_bytes;
+    if (!c->sam.valid) { snprintf(c->err, 512, "dg_batch_device_sam: no SAM text (dg_batch_format_sam first)"); return DG_ERR_ARG; }
+    *ptr = c->sam.bytes ? c->sam.text.p : nullptr; *n_bytes = c->sam.bytes;
     return DG_OK;
 }
 
 // ------------------------------------------------------------------------------------------
 // BAM on the device (dg_bamfmt.h, dg_bgzf.h): the records of the batch that ran last -> uncompressed BAM records -> BGZF blocks
 // ------------------------------------------------------------------------------------------
-static int bam_state(dg_ctx *c)
-{
-    if (c->d_bam_stat) return DG_OK;
-    HIPCHK(hipMalloc((void **)&c->d_bam_stat, 8 * 8));
-    HIPCHK(hipHostMalloc((void **)&c->h_bam_stat, 8 * 8, hipHostMallocDefault));
-    for (hipEvent_t &e : c->ev_bam) HIPCHK(hipEventCreate(&e));
-    return DG_OK;
-}
-
-// n bytes in HBM (4-byte aligned, readable up to the next multiple of 4) -> BGZF blocks in c->bgzf_out: three launches and one wait, for the size;
+// n bytes in HBM (4-byte aligned, readable up to the next multiple of 4) -> BGZF blocks in c->bam.bgzf_out: three launches and one wait, for the size;
 // dynamic: Huffman codes per strip (k_bgzf_deflate_dyn) in place of the fixed code
 static int bgzf_device(dg_ctx *c, const unsigned char *d_in, size_t n, bool dynamic, size_t *n_out, float *ms, unsigned long long *d_phases = nullptr)
 {
@@ -2396,19 +2223,19 @@ static int bgzf_device(dg_ctx *c, const unsigned char *d_in, size_t n, bool dyna
     const size_t blocks = (n + BGZF_BLOCK - 1) / BGZF_BLOCK;
     if (!blocks) return DG_OK;
     if (blocks > 0x7fffffffull) { snprintf(c->err, 512, "BGZF: %zu bytes are more than one call takes", n); return DG_ERR_ARG; }
-    HIPCHK(c->bgzf_slots.ensure(blocks * BGZF_SLOT)); HIPCHK(c->bgzf_size.ensure(blocks)); HIPCHK(c->bgzf_off.ensure(blocks));
-    HIPCHK(c->bgzf_out.ensure(n + (size_t)BGZF_OVERHEAD * blocks));                 // the bound of the stored form: no block is larger
-    HIPCHK(hipEventRecord(c->ev_bam[0], c->stream));
-    if (dynamic) k_bgzf_deflate_dyn<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bgzf_slots.p, c->bgzf_off.p, c->bgzf_size.p, d_phases);
-    else k_bgzf_deflate<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bgzf_slots.p, c->bgzf_off.p, c->bgzf_size.p);
-    k_sam_top<<<1, 256, 0, c->stream>>>(c->bgzf_off.p, (uint32_t)blocks, c->d_bam_stat + 6);
-    k_bgzf_copy<<<(unsigned)blocks, 256, 0, c->stream>>>(c->bgzf_slots.p, c->bgzf_off.p, c->bgzf_size.p, c->bgzf_out.p);
+    HIPCHK(c->bam.bgzf_slots.ensure(blocks * BGZF_SLOT)); HIPCHK(c->bam.bgzf_size.ensure(blocks)); HIPCHK(c->bam.bgzf_off.ensure(blocks));
+    HIPCHK(c->bam.bgzf_out.ensure(n + (size_t)BGZF_OVERHEAD * blocks));                 // the bound of the stored form: no block is larger
+    HIPCHK(hipEventRecord(c->bam.ev[0], c->stream));
+    if (dynamic) k_bgzf_deflate_dyn<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bam.bgzf_slots.p, c->bam.bgzf_off.p, c->bam.bgzf_size.p, d_phases);
+    else k_bgzf_deflate<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bam.bgzf_slots.p, c->bam.bgzf_off.p, c->bam.bgzf_size.p);
+    k_sam_top<<<1, 256, 0, c->stream>>>(c->bam.bgzf_off.p, (uint32_t)blocks, c->bam.stat.d + 6);
+    k_bgzf_copy<<<(unsigned)blocks, 256, 0, c->stream>>>(c->bam.bgzf_slots.p, c->bam.bgzf_off.p, c->bam.bgzf_size.p, c->bam.bgzf_out.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_bam[1], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_bam_stat + 6, c->d_bam_stat + 6, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->bam.ev[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->bam.stat.h + 6, c->bam.stat.d + 6, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
-    (void)hipEventElapsedTime(ms, c->ev_bam[0], c->ev_bam[1]);
-    *n_out = (size_t)c->h_bam_stat[6];
+    *ms = c->bam.ev.ms(0, 1);
+    *n_out = (size_t)c->bam.stat.h[6];
     if (*n_out > n + (size_t)BGZF_OVERHEAD * blocks) { snprintf(c->err, 512, "BGZF: %zu bytes of blocks for %zu bytes", *n_out, n); return DG_ERR_INTERNAL; }
     return DG_OK;
 }
@@ -2419,14 +2246,14 @@ static int bam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr
 {
     const int n = c->n_reads;
     IndexShared *sh = c->shared_ix;
-    { const int rc = bam_state(c); if (rc) return rc; }
+    HIPCHK(c->bam.ready());
     const uint32_t n_tiles = (uint32_t)((n + SAM_LEN_THREADS - 1) / SAM_LEN_THREADS);
-    HIPCHK(c->sam_qlen.ensure((size_t)n)); HIPCHK(c->sam_read_off.ensure((size_t)n)); HIPCHK(c->sam_tile.ensure(n_tiles));
+    HIPCHK(c->sam.qlen.ensure((size_t)n)); HIPCHK(c->sam.read_off.ensure((size_t)n)); HIPCHK(c->sam.tile.ensure(n_tiles));
     // the capacity is a guess the first time (one record per read); when it was too small k_bam_write alone runs again -- never the batch
     size_t want = hdr_bytes + qual_bytes + c->seq_bytes / 2 + (size_t)n * 64;
     want += want / 8;
-    if (c->env_bam_first_cap && !c->bam_rec.p) want = c->env_bam_first_cap;
-    if (c->bam_rec.cap < want + 8) HIPCHK(c->bam_rec.ensure(want + 8));
+    if (c->bam.first_cap && !c->bam.rec.p) want = c->bam.first_cap;
+    if (c->bam.rec.cap < want + 8) HIPCHK(c->bam.rec.ensure(want + 8));
     SamBatch b;
     b.ro = c->reads_out.p; b.po = c->reports.p; b.cig = c->cigfinal.p;
     b.seq_off = c->seq_off.p; b.rlen = c->rlen.p; b.seq = c->seq.p;
@@ -2439,46 +2266,43 @@ static int bam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr
     {   // k_bam_len takes its counters from the SAM formatter's length pass, which reads the chromosome names: enqueued under the index's lock, as there
         std::lock_guard<std::mutex> lk(sh->mu);
         b.chr_off = sh->d_chr_name_off; b.chr = sh->d_chr_names;
-        b2.qlen = c->sam_qlen.p;                                  // (the writer reads no names)
-        HIPCHK(hipEventRecord(c->ev_bam[0], c->stream));
-        HIPCHK(hipMemsetAsync(c->d_bam_stat, 0, 8 * 8, c->stream));
-        k_bam_len<<<n_tiles, SAM_LEN_THREADS, 0, c->stream>>>(b, c->sam_read_off.p, c->sam_qlen.p, c->sam_tile.p, c->d_bam_stat);
-        k_sam_top<<<1, 256, 0, c->stream>>>(c->sam_tile.p, n_tiles, c->d_bam_stat);
-        k_bam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam_read_off.p, c->sam_tile.p, c->d_bam_stat, (unsigned long long)(c->bam_rec.cap - 8), c->bam_rec.p);
+        b2.qlen = c->sam.qlen.p;                                  // (the writer reads no names)
+        HIPCHK(hipEventRecord(c->bam.ev[0], c->stream));
+        HIPCHK(hipMemsetAsync(c->bam.stat.d, 0, 8 * 8, c->stream));
+        k_bam_len<<<n_tiles, SAM_LEN_THREADS, 0, c->stream>>>(b, c->sam.read_off.p, c->sam.qlen.p, c->sam.tile.p, c->bam.stat.d);
+        k_sam_top<<<1, 256, 0, c->stream>>>(c->sam.tile.p, n_tiles, c->bam.stat.d);
+        k_bam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam.read_off.p, c->sam.tile.p, c->bam.stat.d, (unsigned long long)(c->bam.rec.cap - 8), c->bam.rec.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->ev_bam[1], c->stream));
+        HIPCHK(hipEventRecord(c->bam.ev[1], c->stream));
     }
-    HIPCHK(hipMemcpyAsync(c->h_bam_stat, c->d_bam_stat, 6 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bam.stat.h, c->bam.stat.d, 6 * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));                                       // the first wait: for the records' size
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->ev_bam[0], c->ev_bam[1]);
-    const size_t total = (size_t)c->h_bam_stat[0];
-    if (total > c->bam_rec.cap - 8) {                             // the guess was too small: the lengths stand, the writer runs again
-        HIPCHK(c->bam_rec.ensure(total + 8));
-        HIPCHK(hipEventRecord(c->ev_bam[0], c->stream));
-        k_bam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam_read_off.p, c->sam_tile.p, c->d_bam_stat, (unsigned long long)(c->bam_rec.cap - 8), c->bam_rec.p);
+    float ms = c->bam.ev.ms(0, 1);
+    const size_t total = (size_t)c->bam.stat.h[0];
+    if (total > c->bam.rec.cap - 8) {                             // the guess was too small: the lengths stand, the writer runs again
+        HIPCHK(c->bam.rec.ensure(total + 8));
+        HIPCHK(hipEventRecord(c->bam.ev[0], c->stream));
+        k_bam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam.read_off.p, c->sam.tile.p, c->bam.stat.d, (unsigned long long)(c->bam.rec.cap - 8), c->bam.rec.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->ev_bam[1], c->stream));
+        HIPCHK(hipEventRecord(c->bam.ev[1], c->stream));
         HIPCHK(wait_stream(c));
-        float ms2 = 0.f;
-        (void)hipEventElapsedTime(&ms2, c->ev_bam[0], c->ev_bam[1]);
-        ms += ms2;
+        ms += c->bam.ev.ms(0, 1);
     }
     size_t out_bytes = total;
-    c->bam_ptr = c->bam_rec.p;
-    c->bam_ms[0] = ms; c->bam_ms[1] = 0.f;
+    c->bam.ptr = c->bam.rec.p;
+    c->bam.ms[0] = ms; c->bam.ms[1] = 0.f;
     if (!(flags & DG_BAM_RAW) && total) {
         float ms_z = 0.f;
-        const int rc = bgzf_device(c, c->bam_rec.p, total, (flags & DG_BAM_DYNAMIC) != 0, &out_bytes, &ms_z);      // the second wait: for the stream's size
+        const int rc = bgzf_device(c, c->bam.rec.p, total, (flags & DG_BAM_DYNAMIC) != 0, &out_bytes, &ms_z);      // the second wait: for the stream's size
         if (rc) return rc;
-        ms += ms_z; c->bam_ms[1] = ms_z;
-        c->bam_ptr = c->bgzf_out.p;
+        ms += ms_z; c->bam.ms[1] = ms_z;
+        c->bam.ptr = c->bam.bgzf_out.p;
     }
-    c->bam_bytes = out_bytes; c->bam_valid = true;
-    c->bam_rec_valid = true; c->bam_rec_bytes = total; c->bam_rec_records = (size_t)c->h_bam_stat[4];
+    c->bam.bytes = out_bytes; c->bam.valid = true;
+    c->bam.rec_valid = true; c->bam.rec_bytes = total; c->bam.rec_records = (size_t)c->bam.stat.h[4];
     if (n_bytes) *n_bytes = out_bytes;
     if (n_raw) *n_raw = total;
-    if (counters) for (int i = 0; i < 5; i++) counters[i] = c->h_bam_stat[1 + i];
+    if (counters) for (int i = 0; i < 5; i++) counters[i] = c->bam.stat.h[1 + i];
     if (device_ms) *device_ms = ms;
     return DG_OK;
 }
@@ -2494,27 +2318,27 @@ extern "C" int dg_batch_format_bam(dg_ctx *c, const dg_sam_text *in, uint32_t fl
         if (n_bytes) *n_bytes = 0;
         if (counters) counters[0] = counters[1] = counters[2] = 0;
         if (device_ms) *device_ms = 0.f;
-        c->bam_valid = false; c->bam_bytes = 0;
+        c->bam.valid = false; c->bam.bytes = 0;
         snprintf(c->err, 512, "%s: the input is NULL", fn); return DG_ERR_ARG;
     }
     const int rc = sam_batch_ready(c, in->n_pair_mode, n_bytes, counters, device_ms, fn, true);
     if (rc) return rc;
     const int n = c->n_reads;
-    if (n == 0) { c->bam_valid = true; c->bam_ptr = nullptr; c->bam_rec_valid = true; c->bam_rec_bytes = c->bam_rec_records = 0; return DG_OK; }
+    if (n == 0) { c->bam.valid = true; c->bam.ptr = nullptr; c->bam.rec_valid = true; c->bam.rec_bytes = c->bam.rec_records = 0; return DG_OK; }
     if (!in->hdr_off || (in->qual && !in->qual_off)) { snprintf(c->err, 512, "%s: an offset array is NULL", fn); return DG_ERR_ARG; }
     if (sam_offsets_ok(c, "hdr_off", in->hdr_off, n, fn) || (in->qual && sam_offsets_ok(c, "qual_off", in->qual_off, n, fn))) return DG_ERR_ARG;
     const size_t hdr_bytes = (size_t)in->hdr_off[n] - in->hdr_off[0], qual_bytes = in->qual ? (size_t)in->qual_off[n] - in->qual_off[0] : 0;
     if (hdr_bytes && !in->hdr) { snprintf(c->err, 512, "%s: hdr is NULL", fn); return DG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(c->sam_hdr_off.ensure((size_t)n + 1)); HIPCHK(c->sam_hdr.ensure(hdr_bytes + 1));
-    if (in->qual) { HIPCHK(c->sam_qual_off.ensure((size_t)n + 1)); HIPCHK(c->sam_qual.ensure(qual_bytes + 1)); }
-    HIPCHK(hipMemcpyAsync(c->sam_hdr_off.p, in->hdr_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-    if (hdr_bytes) HIPCHK(hipMemcpyAsync(c->sam_hdr.p, in->hdr + in->hdr_off[0], hdr_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c->sam.hdr_off.ensure((size_t)n + 1)); HIPCHK(c->sam.hdr.ensure(hdr_bytes + 1));
+    if (in->qual) { HIPCHK(c->sam.qual_off.ensure((size_t)n + 1)); HIPCHK(c->sam.qual.ensure(qual_bytes + 1)); }
+    HIPCHK(hipMemcpyAsync(c->sam.hdr_off.p, in->hdr_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    if (hdr_bytes) HIPCHK(hipMemcpyAsync(c->sam.hdr.p, in->hdr + in->hdr_off[0], hdr_bytes, hipMemcpyHostToDevice, c->stream));
     if (in->qual) {
-        HIPCHK(hipMemcpyAsync(c->sam_qual_off.p, in->qual_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        if (qual_bytes) HIPCHK(hipMemcpyAsync(c->sam_qual.p, in->qual + in->qual_off[0], qual_bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->sam.qual_off.p, in->qual_off, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if (qual_bytes) HIPCHK(hipMemcpyAsync(c->sam.qual.p, in->qual + in->qual_off[0], qual_bytes, hipMemcpyHostToDevice, c->stream));
     }
-    return bam_format_device(c, c->sam_hdr_off.p, c->sam_hdr.p - in->hdr_off[0], in->qual ? c->sam_qual_off.p : nullptr, in->qual ? c->sam_qual.p - in->qual_off[0] : nullptr,
+    return bam_format_device(c, c->sam.hdr_off.p, c->sam.hdr.p - in->hdr_off[0], in->qual ? c->sam.qual_off.p : nullptr, in->qual ? c->sam.qual.p - in->qual_off[0] : nullptr,
                              hdr_bytes, qual_bytes, in->n_pair_mode, flags, n_bytes, n_raw, counters, device_ms);
 }
 
@@ -2524,21 +2348,21 @@ extern "C" int dg_batch_format_bam_resident(dg_ctx *c, int n_pair_mode, uint32_t
     bam_outputs_zero(n_raw, counters);
     const int rc = sam_batch_ready(c, n_pair_mode, n_bytes, counters, device_ms, "dg_batch_format_bam_resident", true);
     if (rc) return rc;
-    if (!c->fq_valid) { snprintf(c->err, 512, "dg_batch_format_bam_resident: the context's last upload was not dg_batch_upload_fastq: no names and qualities in HBM"); return DG_ERR_ARG; }
-    if (c->n_reads == 0) { c->bam_valid = true; c->bam_ptr = nullptr; c->bam_rec_valid = true; c->bam_rec_bytes = c->bam_rec_records = 0; return DG_OK; }
+    if (!c->fq.valid) { snprintf(c->err, 512, "dg_batch_format_bam_resident: the context's last upload was not dg_batch_upload_fastq: no names and qualities in HBM"); return DG_ERR_ARG; }
+    if (c->n_reads == 0) { c->bam.valid = true; c->bam.ptr = nullptr; c->bam.rec_valid = true; c->bam.rec_bytes = c->bam.rec_records = 0; return DG_OK; }
     HIPCHK(hipSetDevice(c->device));
-    return bam_format_device(c, c->fq_hdr_off.p, c->fq_hdr.p, c->fq_qual_off.p, c->fq_qual.p, c->fq_hdr_bytes, c->fq_qual_bytes, n_pair_mode, flags, n_bytes, n_raw, counters, device_ms);
+    return bam_format_device(c, c->fq.hdr_off.p, c->fq.hdr.p, c->fq.qual_off.p, c->fq.qual.p, c->fq.hdr_bytes, c->fq.qual_bytes, n_pair_mode, flags, n_bytes, n_raw, counters, device_ms);
 }
 
 extern "C" int dg_batch_download_bam(dg_ctx *c, void *out, size_t cap)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->bam_valid) { snprintf(c->err, 512, "dg_batch_download_bam: no BAM bytes (dg_batch_format_bam or dg_bgzf_compress first)"); return DG_ERR_ARG; }
-    if (cap < c->bam_bytes) { snprintf(c->err, 512, "dg_batch_download_bam: output capacity too small: %zu bytes of %zu", cap, c->bam_bytes); return DG_ERR_CAPACITY; }
-    if (c->bam_bytes == 0) return DG_OK;
+    if (!c->bam.valid) { snprintf(c->err, 512, "dg_batch_download_bam: no BAM bytes (dg_batch_format_bam or dg_bgzf_compress first)"); return DG_ERR_ARG; }
+    if (cap < c->bam.bytes) { snprintf(c->err, 512, "dg_batch_download_bam: output capacity too small: %zu bytes of %zu", cap, c->bam.bytes); return DG_ERR_CAPACITY; }
+    if (c->bam.bytes == 0) return DG_OK;
     if (!out) return DG_ERR_ARG;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(out, c->bam_ptr, c->bam_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->bam.ptr, c->bam.bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
@@ -2546,8 +2370,8 @@ extern "C" int dg_batch_download_bam(dg_ctx *c, void *out, size_t cap)
 extern "C" int dg_batch_device_bam(dg_ctx *c, void **ptr, size_t *n_bytes)
 {
     if (!c || !ptr || !n_bytes) return DG_ERR_ARG;
-    if (!c->bam_valid) { snprintf(c->err, 512, "dg_batch_device_bam: no BAM bytes (dg_batch_format_bam or dg_bgzf_compress first)"); return DG_ERR_ARG; }
-    *ptr = c->bam_bytes ? c->bam_ptr : nullptr; *n_bytes = c->bam_bytes;
+    if (!c->bam.valid) { snprintf(c->err, 512, "dg_batch_device_bam: no BAM bytes (dg_batch_format_bam or dg_bgzf_compress first)"); return DG_ERR_ARG; }
+    *ptr = c->bam.bytes ? c->bam.ptr : nullptr; *n_bytes = c->bam.bytes;
     return DG_OK;
 }
 
@@ -2556,19 +2380,19 @@ extern "C" int dg_bgzf_compress_flags(dg_ctx *c, const void *host_bytes, size_t 
     if (!c) return DG_ERR_ARG;
     if (n_bytes) *n_bytes = 0;
     if (device_ms) *device_ms = 0.f;
-    c->bam_valid = false; c->bam_bytes = 0; c->bam_ptr = nullptr;
+    c->bam.valid = false; c->bam.bytes = 0; c->bam.ptr = nullptr;
     if (flags & ~DG_BGZF_DYNAMIC) { snprintf(c->err, 512, "dg_bgzf_compress_flags: unknown flag bits 0x%x", flags & ~DG_BGZF_DYNAMIC); return DG_ERR_ARG; }
-    if (n == 0) { c->bam_valid = true; return DG_OK; }
+    if (n == 0) { c->bam.valid = true; return DG_OK; }
     if (!host_bytes) { snprintf(c->err, 512, "dg_bgzf_compress: the input is NULL"); return DG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    { const int rc = bam_state(c); if (rc) return rc; }
-    HIPCHK(c->bgzf_in.ensure(n + 8));
-    HIPCHK(hipMemcpyAsync(c->bgzf_in.p, host_bytes, n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c->bam.ready());
+    HIPCHK(c->bam.bgzf_in.ensure(n + 8));
+    HIPCHK(hipMemcpyAsync(c->bam.bgzf_in.p, host_bytes, n, hipMemcpyHostToDevice, c->stream));
     size_t out_bytes = 0; float ms = 0.f;
-    const int rc = bgzf_device(c, c->bgzf_in.p, n, (flags & DG_BGZF_DYNAMIC) != 0, &out_bytes, &ms);
+    const int rc = bgzf_device(c, c->bam.bgzf_in.p, n, (flags & DG_BGZF_DYNAMIC) != 0, &out_bytes, &ms);
     if (rc) return rc;
-    c->bam_ptr = c->bgzf_out.p; c->bam_bytes = out_bytes; c->bam_valid = true;
-    c->bam_ms[0] = 0.f; c->bam_ms[1] = ms;
+    c->bam.ptr = c->bam.bgzf_out.p; c->bam.bytes = out_bytes; c->bam.valid = true;
+    c->bam.ms[0] = 0.f; c->bam.ms[1] = ms;
     if (n_bytes) *n_bytes = out_bytes;
     if (device_ms) *device_ms = ms;
     return DG_OK;
@@ -2582,7 +2406,7 @@ extern "C" int dg_bgzf_compress(dg_ctx *c, const void *host_bytes, size_t n, siz
 extern "C" int dg_batch_bam_device_ms(dg_ctx *c, float ms[2])
 {
     if (!c || !ms) return DG_ERR_ARG;
-    ms[0] = c->bam_ms[0]; ms[1] = c->bam_ms[1];
+    ms[0] = c->bam.ms[0]; ms[1] = c->bam.ms[1];
     return DG_OK;
 }
 
@@ -2596,16 +2420,6 @@ extern "C" int dg_bgzf_granules(int out[2])
 // ------------------------------------------------------------------------------------------
 // the splice-junction table on the device (dg_sjtab.h): count per batch, sort and print at the end of the job
 // ------------------------------------------------------------------------------------------
-static int sj_state(dg_ctx *c)
-{
-    if (c->d_sj_stat) return DG_OK;
-    HIPCHK(hipMalloc((void **)&c->d_sj_stat, SJ_ST_WORDS * 8));
-    HIPCHK(hipMemset(c->d_sj_stat, 0, SJ_ST_WORDS * 8));
-    HIPCHK(hipHostMalloc((void **)&c->h_sj_stat, SJ_ST_WORDS * 8, hipHostMallocDefault));
-    memset(c->h_sj_stat, 0, SJ_ST_WORDS * 8);
-    for (hipEvent_t &e : c->ev_sj) HIPCHK(hipEventCreate(&e));
-    return DG_OK;
-}
 static size_t sj_round_slots(size_t slots)
 {
     size_t s = SJ_MIN_SLOTS;
@@ -2619,24 +2433,24 @@ static int sj_new_table(dg_ctx *c, size_t slots, SjSlot **old)
     HIPCHK(hipMalloc((void **)&t, slots * sizeof(SjSlot)));
     const hipError_t e = hipMemsetAsync(t, 0, slots * sizeof(SjSlot), c->stream);
     if (e != hipSuccess) { (void)hipFree(t); return fail(c, DG_ERR_HIP, "hipMemsetAsync (junction table)", e); }
-    if (old) *old = c->sj_tab;
-    else if (c->sj_tab) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->sj_tab); }
-    c->sj_tab = t; c->sj_slots = slots;
+    if (old) *old = c->sj.tab;
+    else if (c->sj.tab) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->sj.tab); }
+    c->sj.tab = t; c->sj.slots = slots;
     return DG_OK;
 }
 static int sj_ready(dg_ctx *c)
 {
     HIPCHK(hipSetDevice(c->device));
-    { const int rc = sj_state(c); if (rc) return rc; }
-    c->sj_fin_valid = false;
-    if (!c->sj_tab) return sj_new_table(c, SJ_FIRST_SLOTS, nullptr);
+    HIPCHK(c->sj.ready());
+    c->sj.fin_valid = false;
+    if (!c->sj.tab) return sj_new_table(c, SJ_FIRST_SLOTS, nullptr);
     return DG_OK;
 }
 static void sj_launch_insert(dg_ctx *c, const void *src, size_t n, int kind, DBuf<dg_sj_entry> &ovf)
 {
     if (!n) return;
-    k_sj_insert<<<(unsigned)((n + SJ_THREADS - 1) / SJ_THREADS), SJ_THREADS, 0, c->stream>>>((const unsigned char *)src, (unsigned long long)n, kind, c->sj_tab,
-                                                                                          (unsigned long long)(c->sj_slots - 1), ovf.p, (unsigned long long)ovf.cap, c->d_sj_stat);
+    k_sj_insert<<<(unsigned)((n + SJ_THREADS - 1) / SJ_THREADS), SJ_THREADS, 0, c->stream>>>((const unsigned char *)src, (unsigned long long)n, kind, c->sj.tab,
+                                                                                          (unsigned long long)(c->sj.slots - 1), ovf.p, (unsigned long long)ovf.cap, c->sj.stat.d);
 }
 // Items in device memory (on this context's stream, or ordered before it) into the table: one insert pass, one wait; then, while an item found no slot or more
 // than half the slots hold a key, a table of twice the size takes the old slots with their counts and ONLY the items of the overflow list, so every item is
@@ -2644,43 +2458,43 @@ static void sj_launch_insert(dg_ctx *c, const void *src, size_t n, int kind, DBu
 static int sj_insert(dg_ctx *c, const void *src, size_t n, int kind)
 {
     if (n >= 0xFFFFFF00ull * SJ_THREADS) { snprintf(c->err, 512, "junction table: too many items in one call"); return DG_ERR_ARG; }
-    int cur = c->sj_ovf_cur;
-    HIPCHK(c->sj_ovf[cur].ensure(n));                             // the overflow list: a bump pointer with room for every item of the pass
-    HIPCHK(hipMemsetAsync(c->d_sj_stat + SJ_ST_OVERFLOW, 0, 8, c->stream));
-    sj_launch_insert(c, src, n, kind, c->sj_ovf[cur]);
+    int cur = c->sj.ovf_cur;
+    HIPCHK(c->sj.ovf[cur].ensure(n));                             // the overflow list: a bump pointer with room for every item of the pass
+    HIPCHK(hipMemsetAsync(c->sj.stat.d + SJ_ST_OVERFLOW, 0, 8, c->stream));
+    sj_launch_insert(c, src, n, kind, c->sj.ovf[cur]);
     HIPCHK(hipGetLastError());
     for (int round = 0; ; round++) {
-        HIPCHK(hipMemcpyAsync(c->h_sj_stat, c->d_sj_stat, 3 * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->sj.stat.h, c->sj.stat.d, 3 * 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(wait_stream(c));
-        const size_t n_ovf = (size_t)c->h_sj_stat[SJ_ST_OVERFLOW];
-        c->sj_distinct = (size_t)c->h_sj_stat[SJ_ST_DISTINCT];
-        if (n_ovf > c->sj_ovf[cur].cap) { snprintf(c->err, 512, "junction table: the overflow list outgrew its capacity (%zu of %zu)", n_ovf, c->sj_ovf[cur].cap); return DG_ERR_INTERNAL; }
-        if (n_ovf == 0 && c->sj_distinct <= c->sj_slots / 2) break;
-        if (round >= 40 || c->sj_slots >= ((size_t)1 << 40)) { snprintf(c->err, 512, "junction table: growth did not converge at %zu slots", c->sj_slots); return DG_ERR_INTERNAL; }
+        const size_t n_ovf = (size_t)c->sj.stat.h[SJ_ST_OVERFLOW];
+        c->sj.distinct = (size_t)c->sj.stat.h[SJ_ST_DISTINCT];
+        if (n_ovf > c->sj.ovf[cur].cap) { snprintf(c->err, 512, "junction table: the overflow list outgrew its capacity (%zu of %zu)", n_ovf, c->sj.ovf[cur].cap); return DG_ERR_INTERNAL; }
+        if (n_ovf == 0 && c->sj.distinct <= c->sj.slots / 2) break;
+        if (round >= 40 || c->sj.slots >= ((size_t)1 << 40)) { snprintf(c->err, 512, "junction table: growth did not converge at %zu slots", c->sj.slots); return DG_ERR_INTERNAL; }
         const int nxt = cur ^ 1;
-        const size_t old_slots = c->sj_slots, old_keys = c->sj_distinct;
-        HIPCHK(c->sj_ovf[nxt].ensure(old_keys + n_ovf));
+        const size_t old_slots = c->sj.slots, old_keys = c->sj.distinct;
+        HIPCHK(c->sj.ovf[nxt].ensure(old_keys + n_ovf));
         SjSlot *old = nullptr;
         { const int rc = sj_new_table(c, old_slots * 2, &old); if (rc) return rc; }
-        hipError_t e = hipMemsetAsync(c->d_sj_stat, 0, 2 * 8, c->stream);        // the overflow and the distinct counts: the new table counts its keys itself
+        hipError_t e = hipMemsetAsync(c->sj.stat.d, 0, 2 * 8, c->stream);        // the overflow and the distinct counts: the new table counts its keys itself
         if (e == hipSuccess) {
-            sj_launch_insert(c, old, old_slots, SJ_SRC_SLOTS, c->sj_ovf[nxt]);
-            sj_launch_insert(c, c->sj_ovf[cur].p, n_ovf, SJ_SRC_ENTRIES, c->sj_ovf[nxt]);
+            sj_launch_insert(c, old, old_slots, SJ_SRC_SLOTS, c->sj.ovf[nxt]);
+            sj_launch_insert(c, c->sj.ovf[cur].p, n_ovf, SJ_SRC_ENTRIES, c->sj.ovf[nxt]);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         (void)hipFree(old);
         if (e != hipSuccess) return fail(c, DG_ERR_HIP, "junction table growth", e);
-        cur = nxt; c->sj_ovf_cur = cur;
+        cur = nxt; c->sj.ovf_cur = cur;
     }
     return DG_OK;
 }
 // an insert pass may have met a coordinate the table cannot hold (INT64_MIN): said once the pass is over, the other items are counted
 static int sj_refused(dg_ctx *c, const char *fn)
 {
-    const size_t bad = (size_t)c->h_sj_stat[SJ_ST_REFUSED];
+    const size_t bad = (size_t)c->sj.stat.h[SJ_ST_REFUSED];
     if (!bad) return DG_OK;
-    (void)hipMemsetAsync(c->d_sj_stat + SJ_ST_REFUSED, 0, 8, c->stream);
+    (void)hipMemsetAsync(c->sj.stat.d + SJ_ST_REFUSED, 0, 8, c->stream);
     snprintf(c->err, 512, "%s: %zu tuples hold the coordinate INT64_MIN, which the table does not store; the others were counted", fn, bad);
     return DG_ERR_RANGE;
 }
@@ -2695,11 +2509,11 @@ extern "C" int dg_sj_granules(int out[2])
 extern "C" int dg_sj_reserve(dg_ctx *c, size_t slots)
 {
     if (!c) return DG_ERR_ARG;
-    if (c->sj_distinct) { snprintf(c->err, 512, "dg_sj_reserve: the table holds %zu keys (dg_sj_reset first)", c->sj_distinct); return DG_ERR_ARG; }
+    if (c->sj.distinct) { snprintf(c->err, 512, "dg_sj_reserve: the table holds %zu keys (dg_sj_reset first)", c->sj.distinct); return DG_ERR_ARG; }
     if (slots > ((size_t)1 << 36)) { snprintf(c->err, 512, "dg_sj_reserve: %zu slots are more than the table takes", slots); return DG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    { const int rc = sj_state(c); if (rc) return rc; }
-    c->sj_fin_valid = false;
+    HIPCHK(c->sj.ready());
+    c->sj.fin_valid = false;
     return sj_new_table(c, sj_round_slots(slots), nullptr);
 }
 
@@ -2707,10 +2521,10 @@ extern "C" int dg_sj_reset(dg_ctx *c)
 {
     if (!c) return DG_ERR_ARG;
     { const int rc = sj_ready(c); if (rc) return rc; }
-    HIPCHK(hipMemsetAsync(c->sj_tab, 0, c->sj_slots * sizeof(SjSlot), c->stream));
-    HIPCHK(hipMemsetAsync(c->d_sj_stat, 0, SJ_ST_WORDS * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->sj.tab, 0, c->sj.slots * sizeof(SjSlot), c->stream));
+    HIPCHK(hipMemsetAsync(c->sj.stat.d, 0, SJ_ST_WORDS * 8, c->stream));
     HIPCHK(wait_stream(c));
-    c->sj_distinct = 0;
+    c->sj.distinct = 0;
     return DG_OK;
 }
 
@@ -2719,11 +2533,11 @@ extern "C" int dg_batch_accumulate_sj(dg_ctx *c, size_t *n_tuples)
     if (!c) return DG_ERR_ARG;
     if (n_tuples) *n_tuples = 0;
     if (!c->batch_done) { snprintf(c->err, 512, "dg_batch_accumulate_sj: the context has no finished batch (upload and run one first)"); return DG_ERR_ARG; }
-    if (c->sj_batch_counted) { snprintf(c->err, 512, "dg_batch_accumulate_sj: the tuples of this batch are in the table already (a batch is counted once)"); return DG_ERR_ARG; }
+    if (c->sj.batch_counted) { snprintf(c->err, 512, "dg_batch_accumulate_sj: the tuples of this batch are in the table already (a batch is counted once)"); return DG_ERR_ARG; }
     { const int rc = sj_ready(c); if (rc) return rc; }
     const size_t n = c->n_reads ? c->used[2] : 0;
     if (n) { const int rc = sj_insert(c, c->sjfinal.p, n, SJ_SRC_TUPLES); if (rc) return rc; }
-    c->sj_batch_counted = true;
+    c->sj.batch_counted = true;
     if (n_tuples) *n_tuples = n;
     return n ? sj_refused(c, "dg_batch_accumulate_sj") : DG_OK;
 }
@@ -2735,9 +2549,9 @@ extern "C" int dg_sj_add(dg_ctx *c, const dg_sj_entry *entries, size_t n)
         if (entries[i].count && !sj_key_ok(entries[i].g1, entries[i].g2)) { snprintf(c->err, 512, "dg_sj_add: entry %zu holds the coordinate INT64_MIN, which the table does not store", i); return DG_ERR_ARG; }
     { const int rc = sj_ready(c); if (rc) return rc; }
     if (!n) return DG_OK;
-    HIPCHK(c->sj_in.ensure(n));
-    HIPCHK(hipMemcpyAsync(c->sj_in.p, entries, n * sizeof(dg_sj_entry), hipMemcpyHostToDevice, c->stream));
-    return sj_insert(c, c->sj_in.p, n, SJ_SRC_ENTRIES);
+    HIPCHK(c->sj.in.ensure(n));
+    HIPCHK(hipMemcpyAsync(c->sj.in.p, entries, n * sizeof(dg_sj_entry), hipMemcpyHostToDevice, c->stream));
+    return sj_insert(c, c->sj.in.p, n, SJ_SRC_ENTRIES);
 }
 
 extern "C" int dg_sj_merge(dg_ctx *dst, dg_ctx *src)
@@ -2746,48 +2560,57 @@ extern "C" int dg_sj_merge(dg_ctx *dst, dg_ctx *src)
     if (!dst || !src) return DG_ERR_ARG;
     if (dst == src || dst->device != src->device) { snprintf(c->err, 512, "dg_sj_merge: the two contexts must differ and be on one device"); return DG_ERR_ARG; }
     { const int rc = sj_ready(dst); if (rc) return rc; }
-    src->sj_fin_valid = false;
-    if (!src->sj_tab || !src->sj_distinct) return DG_OK;
-    { const int rc = sj_state(src); if (rc) { snprintf(c->err, 512, "%s", src->err); return rc; } }
+    src->sj.fin_valid = false;
+    if (!src->sj.tab || !src->sj.distinct) return DG_OK;
+    HIPCHK(src->sj.ready());
     // behind everything the source's stream holds; the source's table is emptied on the destination's stream, which the call waits for
-    HIPCHK(hipEventRecord(src->ev_sj[2], src->stream));
-    HIPCHK(hipStreamWaitEvent(dst->stream, src->ev_sj[2], 0));
-    const int rc = sj_insert(dst, src->sj_tab, src->sj_slots, SJ_SRC_SLOTS);
+    HIPCHK(hipEventRecord(src->sj.ev[2], src->stream));
+    HIPCHK(hipStreamWaitEvent(dst->stream, src->sj.ev[2], 0));
+    const int rc = sj_insert(dst, src->sj.tab, src->sj.slots, SJ_SRC_SLOTS);
     if (rc) return rc;
-    HIPCHK(hipMemsetAsync(src->sj_tab, 0, src->sj_slots * sizeof(SjSlot), dst->stream));
-    HIPCHK(hipMemsetAsync(src->d_sj_stat, 0, SJ_ST_WORDS * 8, dst->stream));
+    HIPCHK(hipMemsetAsync(src->sj.tab, 0, src->sj.slots * sizeof(SjSlot), dst->stream));
+    HIPCHK(hipMemsetAsync(src->sj.stat.d, 0, SJ_ST_WORDS * 8, dst->stream));
     HIPCHK(wait_stream(dst));
-    src->sj_distinct = 0;
+    src->sj.distinct = 0;
     return DG_OK;
 }
 
-// The passes of the stable LSD radix sort (dg_sort.h) of n pairs by the low `bits` bits of the key, enqueued on the context's stream: the driver of the junction
-// table's sorts and of the sorted BAM store's.  keys / vals: two buffers each; which: in = the pair that holds the input, out = the one that holds the result.
-// hist holds 16 x tiles + 1 words, sums one per SCAN_TILE of them + 1: the caller's scratch.
-static int rs_sort_passes(dg_ctx *c, uint64_t *const keys[2], int64_t *const vals[2], uint32_t *hist, uint32_t *sums, uint32_t n, int bits, int &which)
+// The passes of the stable LSD radix sort (dg_sort.h) of n pairs by the low `bits` bits of the key, enqueued on stream s: the one driver of every sort the
+// library runs.  keys / vals: two buffers each; which: in = the pair that holds the input, out = the one that holds the result.
+// hist holds rs_hist_words(n) words (16 x tiles + 1), sums rs_sums_words(n) (one per SCAN_TILE of them + 1): the caller's scratch.
+static hipError_t rs_sort_passes(hipStream_t s, uint64_t *const keys[2], int64_t *const vals[2], uint32_t *hist, uint32_t *sums, uint32_t n, int bits, int &which)
 {
     const uint32_t tiles = (n + RS_TILE - 1) / RS_TILE, m = 16u * tiles, scan_tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
     for (int shift = 0; shift < bits; shift += 4) {
         const int o = which ^ 1;
-        k_rs_hist<<<tiles, 256, 0, c->stream>>>(keys[which], n, shift, tiles, hist);
-        k_scan_tiles<<<scan_tiles, 256, 0, c->stream>>>(hist, hist, sums, m);
-        k_scan_top<<<1, 256, 0, c->stream>>>(sums, scan_tiles, hist + m, nullptr, 0, nullptr, 0);
-        k_scan_add<<<(m + 255) / 256, 256, 0, c->stream>>>(hist, sums, m);
-        k_rs_scatter<<<tiles, 256, 0, c->stream>>>(keys[which], vals[which], keys[o], vals[o], n, shift, tiles, hist);
-        HIPCHK(hipGetLastError());
+        k_rs_hist<<<tiles, 256, 0, s>>>(keys[which], n, shift, tiles, hist);
+        k_scan_tiles<<<scan_tiles, 256, 0, s>>>(hist, hist, sums, m);
+        k_scan_top<<<1, 256, 0, s>>>(sums, scan_tiles, hist + m, nullptr, 0, nullptr, 0);
+        k_scan_add<<<(m + 255) / 256, 256, 0, s>>>(hist, sums, m);
+        k_rs_scatter<<<tiles, 256, 0, s>>>(keys[which], vals[which], keys[o], vals[o], n, shift, tiles, hist);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
         which = o;
     }
-    return DG_OK;
+    return hipSuccess;
 }
 static size_t rs_hist_words(uint32_t n) { return 16 * (size_t)((n + RS_TILE - 1) / RS_TILE) + 1; }
 static size_t rs_sums_words(uint32_t n) { return (rs_hist_words(n) - 1 + SCAN_TILE - 1) / SCAN_TILE + 1; }
 
-// the junction table's sort: n pairs in sj_keys / sj_vals [which]
-static int sj_sort(dg_ctx *c, uint32_t n, int bits, int &which)
+// the scratch of a sort of n pairs: the one place that sizes it
+inline hipError_t SortBufs::ensure(uint32_t n)
 {
-    HIPCHK(c->sj_hist.ensure(rs_hist_words(n))); HIPCHK(c->sj_sums.ensure(rs_sums_words(n)));
-    uint64_t *const keys[2] = {c->sj_keys[0].p, c->sj_keys[1].p}; int64_t *const vals[2] = {c->sj_vals[0].p, c->sj_vals[1].p};
-    return rs_sort_passes(c, keys, vals, c->sj_hist.p, c->sj_sums.p, n, bits, which);
+    hipError_t e = hist.ensure(rs_hist_words(n));
+    if (e != hipSuccess) { short_of = "the sorter's histograms"; short_bytes = rs_hist_words(n) * sizeof(uint32_t); return e; }
+    e = sums.ensure(rs_sums_words(n));
+    if (e != hipSuccess) { short_of = "the sorter's sums"; short_bytes = rs_sums_words(n) * sizeof(uint32_t); }
+    return e;
+}
+inline int SortBufs::sort(dg_ctx *c, uint32_t n, int bits, int &which)
+{
+    uint64_t *const keys[2] = {k[0].p, k[1].p}; int64_t *const vals[2] = {v[0].p, v[1].p};
+    const hipError_t e = rs_sort_passes(c->stream, keys, vals, hist.p, sums.p, n, bits, which);
+    return e == hipSuccess ? DG_OK : fail(c, DG_ERR_HIP, "hipGetLastError()", e);
 }
 
 extern "C" int dg_sj_finish(dg_ctx *c, uint32_t flags, size_t *n_entries, size_t *n_lines, size_t *n_bytes, float *device_ms)
@@ -2799,30 +2622,31 @@ extern "C" int dg_sj_finish(dg_ctx *c, uint32_t flags, size_t *n_entries, size_t
     if (device_ms) *device_ms = 0.f;
     const bool text = !(flags & DG_SJ_ENTRIES_ONLY);
     IndexShared *sh = c->shared_ix;
-    c->sj_fin_valid = false;
+    c->sj.fin_valid = false;
     if (text && (!sh || !sh->chr_names_set)) { snprintf(c->err, 512, "dg_sj_finish: the chromosome names are missing (dg_set_chr_names), and DG_SJ_ENTRIES_ONLY is not set"); return DG_ERR_ARG; }
     { const int rc = sj_ready(c); if (rc) return rc; }
-    c->sj_fin_entries = 0; c->sj_fin_bytes = 0;
-    if (!c->sj_distinct) { c->sj_fin_valid = true; return DG_OK; }
-    if (c->sj_distinct >= 0xFFFFF000ull) { snprintf(c->err, 512, "dg_sj_finish: %zu entries are more than the sorter takes", c->sj_distinct); return DG_ERR_ARG; }
-    const size_t cap = c->sj_distinct;
-    for (int k = 0; k < 2; k++) { HIPCHK(c->sj_keys[k].ensure(cap)); HIPCHK(c->sj_vals[k].ensure(cap)); }
-    HIPCHK(c->sj_entries.ensure(cap)); HIPCHK(c->sj_line_off.ensure(cap));
+    c->sj.fin_entries = 0; c->sj.fin_bytes = 0;
+    if (!c->sj.distinct) { c->sj.fin_valid = true; return DG_OK; }
+    if (c->sj.distinct >= 0xFFFFF000ull) { snprintf(c->err, 512, "dg_sj_finish: %zu entries are more than the sorter takes", c->sj.distinct); return DG_ERR_ARG; }
+    const size_t cap = c->sj.distinct;
+    for (int k = 0; k < 2; k++) { HIPCHK(c->sj.sort.k[k].ensure(cap)); HIPCHK(c->sj.sort.v[k].ensure(cap)); }
+    HIPCHK(c->sj.entries.ensure(cap)); HIPCHK(c->sj.line_off.ensure(cap));
     const uint32_t n_tiles = (uint32_t)((cap + SJ_THREADS - 1) / SJ_THREADS);
-    HIPCHK(c->sj_tile.ensure(n_tiles));
-    HIPCHK(hipEventRecord(c->ev_sj[0], c->stream));
-    HIPCHK(hipMemsetAsync(c->d_sj_stat + SJ_ST_ENTRIES, 0, (SJ_ST_WORDS - SJ_ST_ENTRIES) * 8, c->stream));
-    k_sj_compact<<<(unsigned)((c->sj_slots + SJ_THREADS - 1) / SJ_THREADS), SJ_THREADS, 0, c->stream>>>(c->sj_tab, (unsigned long long)c->sj_slots, (unsigned long long)cap, c->sj_keys[0].p, c->sj_vals[0].p, c->d_sj_stat);
+    HIPCHK(c->sj.tile.ensure(n_tiles));
+    HIPCHK(hipEventRecord(c->sj.ev[0], c->stream));
+    HIPCHK(hipMemsetAsync(c->sj.stat.d + SJ_ST_ENTRIES, 0, (SJ_ST_WORDS - SJ_ST_ENTRIES) * 8, c->stream));
+    k_sj_compact<<<(unsigned)((c->sj.slots + SJ_THREADS - 1) / SJ_THREADS), SJ_THREADS, 0, c->stream>>>(c->sj.tab, (unsigned long long)c->sj.slots, (unsigned long long)cap, c->sj.sort.k[0].p, c->sj.sort.v[0].p, c->sj.stat.d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->h_sj_stat, c->d_sj_stat, SJ_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c->sj.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the first wait: how many entries, and which digits their keys differ in
-    const size_t n = (size_t)c->h_sj_stat[SJ_ST_ENTRIES];
+    const size_t n = (size_t)c->sj.stat.h[SJ_ST_ENTRIES];
     if (n != cap) { snprintf(c->err, 512, "dg_sj_finish: the table holds %zu filled slots, %zu keys were counted", n, cap); return DG_ERR_INTERNAL; }
-    const int bits1 = sj_key_bits(~c->h_sj_stat[SJ_ST_NMIN1], c->h_sj_stat[SJ_ST_MAX1]), bits2 = sj_key_bits(~c->h_sj_stat[SJ_ST_NMIN2], c->h_sj_stat[SJ_ST_MAX2]);
+    const int bits1 = sj_key_bits(~c->sj.stat.h[SJ_ST_NMIN1], c->sj.stat.h[SJ_ST_MAX1]), bits2 = sj_key_bits(~c->sj.stat.h[SJ_ST_NMIN2], c->sj.stat.h[SJ_ST_MAX2]);
     int which = 0;
-    { const int rc = sj_sort(c, (uint32_t)n, bits2, which); if (rc) return rc; }
-    k_sj_gather<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->sj_tab, c->sj_vals[which].p, (uint32_t)n, c->sj_keys[which].p);
-    { const int rc = sj_sort(c, (uint32_t)n, bits1, which); if (rc) return rc; }
+    HIPCHK(c->sj.sort.ensure((uint32_t)n));
+    { const int rc = c->sj.sort.sort(c, (uint32_t)n, bits2, which); if (rc) return rc; }
+    k_sj_gather<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->sj.tab, c->sj.sort.v[which].p, (uint32_t)n, c->sj.sort.k[which].p);
+    { const int rc = c->sj.sort.sort(c, (uint32_t)n, bits1, which); if (rc) return rc; }
     SjPrint pr; pr.loc_key = c->ix.loc_key; pr.loc_chr = c->ix.loc_chr; pr.chr_off = c->ix.chr_off; pr.n2 = 2 * c->ix.n_chr; pr.name_off = nullptr; pr.names = nullptr;
     size_t text_cap = 0;
     {   // the chromosome names are read and the kernels that use them enqueued under the index's lock (as the SAM formatter does: dg_set_chr_names waits for the device before it frees them)
@@ -2831,25 +2655,24 @@ extern "C" int dg_sj_finish(dg_ctx *c, uint32_t flags, size_t *n_entries, size_t
             lk = std::unique_lock<std::mutex>(sh->mu);
             pr.name_off = sh->d_chr_name_off; pr.names = sh->d_chr_names;
             text_cap = n * ((size_t)sh->chr_name_max + 3 * 21 + 4);      // a name, three numbers of at most 20 characters and a sign, three tabs and the line end
-            HIPCHK(c->sj_text.ensure(text_cap));
+            HIPCHK(c->sj.text.ensure(text_cap));
         }
-        k_sj_entries<<<n_tiles, SJ_THREADS, 0, c->stream>>>(c->sj_tab, c->sj_vals[which].p, (uint32_t)n, pr, c->sj_entries.p, c->sj_line_off.p, c->sj_tile.p, c->d_sj_stat);
+        k_sj_entries<<<n_tiles, SJ_THREADS, 0, c->stream>>>(c->sj.tab, c->sj.sort.v[which].p, (uint32_t)n, pr, c->sj.entries.p, c->sj.line_off.p, c->sj.tile.p, c->sj.stat.d);
         if (text) {
-            k_sam_top<<<1, 256, 0, c->stream>>>(c->sj_tile.p, n_tiles, c->d_sj_stat + SJ_ST_BYTES);
-            k_sj_write<<<n_tiles, SJ_THREADS, 0, c->stream>>>(c->sj_entries.p, (uint32_t)n, pr, c->sj_line_off.p, c->sj_tile.p, c->d_sj_stat, (unsigned long long)c->sj_text.cap, c->sj_text.p);
+            k_sam_top<<<1, 256, 0, c->stream>>>(c->sj.tile.p, n_tiles, c->sj.stat.d + SJ_ST_BYTES);
+            k_sj_write<<<n_tiles, SJ_THREADS, 0, c->stream>>>(c->sj.entries.p, (uint32_t)n, pr, c->sj.line_off.p, c->sj.tile.p, c->sj.stat.d, (unsigned long long)c->sj.text.cap, c->sj.text.p);
         }
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->ev_sj[1], c->stream));
+        HIPCHK(hipEventRecord(c->sj.ev[1], c->stream));
     }
-    HIPCHK(hipMemcpyAsync(c->h_sj_stat, c->d_sj_stat, SJ_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c->sj.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the second wait: lines and bytes
-    const size_t bytes = text ? (size_t)c->h_sj_stat[SJ_ST_BYTES] : 0;
-    if (bytes > c->sj_text.cap) { snprintf(c->err, 512, "dg_sj_finish: the text needs %zu bytes, the bound was %zu", bytes, c->sj_text.cap); return DG_ERR_INTERNAL; }
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->ev_sj[0], c->ev_sj[1]);
-    c->sj_fin_entries = n; c->sj_fin_bytes = bytes; c->sj_fin_valid = true;
+    const size_t bytes = text ? (size_t)c->sj.stat.h[SJ_ST_BYTES] : 0;
+    if (bytes > c->sj.text.cap) { snprintf(c->err, 512, "dg_sj_finish: the text needs %zu bytes, the bound was %zu", bytes, c->sj.text.cap); return DG_ERR_INTERNAL; }
+    const float ms = c->sj.ev.ms(0, 1);
+    c->sj.fin_entries = n; c->sj.fin_bytes = bytes; c->sj.fin_valid = true;
     if (n_entries) *n_entries = n;
-    if (n_lines) *n_lines = (size_t)c->h_sj_stat[SJ_ST_LINES];
+    if (n_lines) *n_lines = (size_t)c->sj.stat.h[SJ_ST_LINES];
     if (n_bytes) *n_bytes = bytes;
     if (device_ms) *device_ms = ms;
     return DG_OK;
@@ -2858,14 +2681,14 @@ extern "C" int dg_sj_finish(dg_ctx *c, uint32_t flags, size_t *n_entries, size_t
 extern "C" int dg_sj_download(dg_ctx *c, dg_sj_entry *entries, size_t cap_entries, char *text, size_t cap_text)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->sj_fin_valid) { snprintf(c->err, 512, "dg_sj_download: no finished table (dg_sj_finish first)"); return DG_ERR_ARG; }
-    if ((entries && cap_entries < c->sj_fin_entries) || (text && cap_text < c->sj_fin_bytes)) {
-        snprintf(c->err, 512, "dg_sj_download: output capacity too small: %zu entries and %zu bytes of text are needed", c->sj_fin_entries, c->sj_fin_bytes);
+    if (!c->sj.fin_valid) { snprintf(c->err, 512, "dg_sj_download: no finished table (dg_sj_finish first)"); return DG_ERR_ARG; }
+    if ((entries && cap_entries < c->sj.fin_entries) || (text && cap_text < c->sj.fin_bytes)) {
+        snprintf(c->err, 512, "dg_sj_download: output capacity too small: %zu entries and %zu bytes of text are needed", c->sj.fin_entries, c->sj.fin_bytes);
         return DG_ERR_CAPACITY;
     }
     HIPCHK(hipSetDevice(c->device));
-    if (entries && c->sj_fin_entries) HIPCHK(hipMemcpyAsync(entries, c->sj_entries.p, c->sj_fin_entries * sizeof(dg_sj_entry), hipMemcpyDeviceToHost, c->stream));
-    if (text && c->sj_fin_bytes) HIPCHK(hipMemcpyAsync(text, c->sj_text.p, c->sj_fin_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (entries && c->sj.fin_entries) HIPCHK(hipMemcpyAsync(entries, c->sj.entries.p, c->sj.fin_entries * sizeof(dg_sj_entry), hipMemcpyDeviceToHost, c->stream));
+    if (text && c->sj.fin_bytes) HIPCHK(hipMemcpyAsync(text, c->sj.text.p, c->sj.fin_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
@@ -2873,30 +2696,21 @@ extern "C" int dg_sj_download(dg_ctx *c, dg_sj_entry *entries, size_t cap_entrie
 extern "C" int dg_sj_device(dg_ctx *c, void **entries, void **text)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->sj_fin_valid) { snprintf(c->err, 512, "dg_sj_device: no finished table (dg_sj_finish first)"); return DG_ERR_ARG; }
-    if (entries) *entries = c->sj_fin_entries ? c->sj_entries.p : nullptr;
-    if (text) *text = c->sj_fin_bytes ? c->sj_text.p : nullptr;
+    if (!c->sj.fin_valid) { snprintf(c->err, 512, "dg_sj_device: no finished table (dg_sj_finish first)"); return DG_ERR_ARG; }
+    if (entries) *entries = c->sj.fin_entries ? c->sj.entries.p : nullptr;
+    if (text) *text = c->sj.fin_bytes ? c->sj.text.p : nullptr;
     return DG_OK;
 }
 
 // ------------------------------------------------------------------------------------------
 // coordinate-sorted BAM on the device (dg_bamsort.h): the records of every batch stay in HBM, one sort and one gather at the end of the job
 // ------------------------------------------------------------------------------------------
-static int bs_state(dg_ctx *c)
-{
-    if (c->d_bs_stat) return DG_OK;
-    HIPCHK(hipMalloc((void **)&c->d_bs_stat, 4 * 8));
-    HIPCHK(hipMemset(c->d_bs_stat, 0, 4 * 8));
-    HIPCHK(hipHostMalloc((void **)&c->h_bs_stat, 4 * 8, hipHostMallocDefault));
-    memset(c->h_bs_stat, 0, 4 * 8);
-    for (hipEvent_t &e : c->ev_bs) HIPCHK(hipEventCreate(&e));
-    return DG_OK;
-}
 static int bs_ready(dg_ctx *c)
 {
     HIPCHK(hipSetDevice(c->device));
-    { const int rc = bs_state(c); if (rc) return rc; }
-    return bam_state(c);
+    HIPCHK(c->bs.ready());
+    HIPCHK(c->bam.ready());
+    return DG_OK;
 }
 // One array of the store with room for `need` elements (`pad` more are allocated and never counted).  DBuf::ensure frees what it holds; here the first `used`
 // elements are kept: allocate, copy device to device on the context's stream, wait, free.  hipMalloc fails: DG_ERR_CAPACITY, the array stays as it was.
@@ -2922,23 +2736,40 @@ static int bs_grow(dg_ctx *c, T *&p, size_t &cap, size_t used, size_t need, size
 // room for n_rec more records of `bytes` bytes
 static int bs_reserve(dg_ctx *c, size_t n_rec, size_t bytes, const char *fn)
 {
-    if (c->bs_n + n_rec >= 0xFFFFF000ull) { snprintf(c->err, 512, "%s: %zu records are more than the sorter takes", fn, c->bs_n + n_rec); return DG_ERR_ARG; }
-    const size_t hook = c->env_bamsort_first_cap;
+    if (c->bs.n + n_rec >= 0xFFFFF000ull) { snprintf(c->err, 512, "%s: %zu records are more than the sorter takes", fn, c->bs.n + n_rec); return DG_ERR_ARG; }
+    const size_t hook = c->bs.first_cap;
     const size_t first_bytes = hook ? std::max<size_t>(hook, BS_MIN_BYTES) : (size_t)1 << 24, first_recs = hook ? std::max<size_t>(hook / 64, 16) : (size_t)1 << 16;
-    const bool grows = (c->bs_rec && c->bs_rec_used + bytes > c->bs_rec_cap) || (c->bs_key && c->bs_n + n_rec > c->bs_key_cap);      // an array is replaced by a larger one
-    int rc = bs_grow(c, c->bs_rec, c->bs_rec_cap, c->bs_rec_used, c->bs_rec_used + bytes, first_bytes, 8, fn, "records");
-    if (!rc) rc = bs_grow(c, c->bs_key, c->bs_key_cap, c->bs_n, c->bs_n + n_rec, first_recs, 0, fn, "keys");
-    if (!rc) rc = bs_grow(c, c->bs_off, c->bs_off_cap, c->bs_n, c->bs_n + n_rec, first_recs, 0, fn, "offsets");
-    if (!rc && grows) c->bs_growths++;
+    const bool grows = (c->bs.rec && c->bs.rec_used + bytes > c->bs.rec_cap) || (c->bs.key && c->bs.n + n_rec > c->bs.key_cap);      // an array is replaced by a larger one
+    int rc = bs_grow(c, c->bs.rec, c->bs.rec_cap, c->bs.rec_used, c->bs.rec_used + bytes, first_bytes, 8, fn, "records");
+    if (!rc) rc = bs_grow(c, c->bs.key, c->bs.key_cap, c->bs.n, c->bs.n + n_rec, first_recs, 0, fn, "keys");
+    if (!rc) rc = bs_grow(c, c->bs.off, c->bs.off_cap, c->bs.n, c->bs.n + n_rec, first_recs, 0, fn, "offsets");
+    if (!rc && grows) c->bs.growths++;
     return rc;
 }
 static void bs_commit(dg_ctx *c, uint32_t ordinal, size_t n_rec, size_t bytes)
 {
-    c->bs_segs.push_back(BsSeg{ordinal, (uint64_t)c->bs_n, (uint64_t)n_rec});
-    c->bs_n += n_rec; c->bs_rec_used += bytes;
+    c->bs.segs.push_back(BsSeg{ordinal, (uint64_t)c->bs.n, (uint64_t)n_rec});
+    c->bs.n += n_rec; c->bs.rec_used += bytes;
 }
 #define BS_ENSURE(buf, n, what) do { if ((buf).ensure(n) != hipSuccess) { (void)hipGetLastError(); \
     snprintf(c->err, 512, "%s: not enough device memory: %s need %zu bytes", fn, what, (size_t)(n) * sizeof(*(buf).p)); return DG_ERR_CAPACITY; } } while (0)
+// the same for the scratch of a sort of n pairs (SortBufs::ensure names the array it could not have)
+#define BS_ENSURE_SORT(sb, n) do { if ((sb).ensure(n) != hipSuccess) { (void)hipGetLastError(); \
+    snprintf(c->err, 512, "%s: not enough device memory: %s need %zu bytes", fn, (sb).short_of, (sb).short_bytes); return DG_ERR_CAPACITY; } } while (0)
+
+// The sorted array as the stages behind dg_bam_sort_finish read it (index, coverage, duplicate marking): the records' bytes, every record's place inside its
+// tile (the sorter's other key buffer) and the tiles' sums.  bs_view is those stages' common beginning: a sorted array must be there.
+struct BsView { unsigned char *rec; const uint64_t *dst_off; uint64_t *tile; size_t n, n_raw; int n_chr; };
+static int bs_view(dg_ctx *c, const char *fn, BsView &v)
+{
+    if (!c->bs.fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
+    { const int rc = bs_ready(c); if (rc) return rc; }
+    v.rec = c->bs.sorted.p; v.dst_off = c->bs.sort.k[c->bs.fin_which ^ 1].p; v.tile = c->bs.tile.p;
+    v.n = c->bs.fin_records; v.n_raw = c->bs.fin_bytes; v.n_chr = c->ix.n_chr;
+    return DG_OK;
+}
+// the bytes of the sorted array changed (a new sort, duplicate flags written): no block of it has been compressed, and no index or track covers it
+static void bs_array_changed(dg_ctx *c) { c->bi.valid = false; c->bi.covered.clear(); c->cv.valid = false; }
 
 extern "C" int dg_bam_sort_granules(int out[3])
 {
@@ -2951,7 +2782,7 @@ extern "C" int dg_bam_sort_granules(int out[3])
 extern "C" int dg_bam_sort_info(dg_ctx *c, size_t out[4])
 {
     if (!c || !out) return DG_ERR_ARG;
-    out[0] = c->bs_n; out[1] = c->bs_rec_used; out[2] = c->bs_segs.size(); out[3] = c->bs_growths;
+    out[0] = c->bs.n; out[1] = c->bs.rec_used; out[2] = c->bs.segs.size(); out[3] = c->bs.growths;
     return DG_OK;
 }
 
@@ -2960,7 +2791,7 @@ extern "C" int dg_bam_sort_reset(dg_ctx *c)
     if (!c) return DG_ERR_ARG;
     { const int rc = bs_ready(c); if (rc) return rc; }
     HIPCHK(wait_stream(c));
-    c->bs_n = 0; c->bs_rec_used = 0; c->bs_segs.clear(); c->bs_fin_valid = false;
+    c->bs.n = 0; c->bs.rec_used = 0; c->bs.segs.clear(); c->bs.fin_valid = false;
     return DG_OK;
 }
 
@@ -2970,31 +2801,31 @@ extern "C" int dg_batch_accumulate_bam(dg_ctx *c, uint32_t ordinal, size_t *n_re
     const char *fn = "dg_batch_accumulate_bam";
     if (n_records) *n_records = 0;
     if (n_bytes) *n_bytes = 0;
-    if (!c->bam_rec_valid) { snprintf(c->err, 512, "%s: the records of the current batch are not there (dg_batch_format_bam on a finished batch first, and no dg_batch_format_sam behind it)", fn); return DG_ERR_ARG; }
-    if (c->bam_rec_stored) { snprintf(c->err, 512, "%s: the records of this batch are in the store already (a batch is added once)", fn); return DG_ERR_ARG; }
+    if (!c->bam.rec_valid) { snprintf(c->err, 512, "%s: the records of the current batch are not there (dg_batch_format_bam on a finished batch first, and no dg_batch_format_sam behind it)", fn); return DG_ERR_ARG; }
+    if (c->bam.rec_stored) { snprintf(c->err, 512, "%s: the records of this batch are in the store already (a batch is added once)", fn); return DG_ERR_ARG; }
     { const int rc = bs_ready(c); if (rc) return rc; }
-    const size_t n_rec = c->bam_rec_records, bytes = c->bam_rec_bytes;
-    if (!n_rec) { c->bam_rec_stored = true; return DG_OK; }
+    const size_t n_rec = c->bam.rec_records, bytes = c->bam.rec_bytes;
+    if (!n_rec) { c->bam.rec_stored = true; return DG_OK; }
     { const int rc = bs_reserve(c, n_rec, bytes, fn); if (rc) return rc; }
-    c->bs_fin_valid = false;
+    c->bs.fin_valid = false;
     const int n = c->n_reads;
     const uint32_t n_tiles = (uint32_t)((n + BS_THREADS - 1) / BS_THREADS);
-    BS_ENSURE(c->bs_cnt_off, (size_t)n, "the per-read counts"); BS_ENSURE(c->bs_tile_cnt, (size_t)n_tiles + 1, "the per-workgroup counts");
-    HIPCHK(hipEventRecord(c->ev_bs[0], c->stream));
-    k_bs_count<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bam_rec.p, c->sam_read_off.p, c->sam_tile.p, n, (unsigned long long)bytes, c->bs_cnt_off.p, c->bs_tile_cnt.p);
-    k_scan_top<<<1, 256, 0, c->stream>>>(c->bs_tile_cnt.p, n_tiles, (uint32_t *)(c->d_bs_stat + 1), nullptr, 0, nullptr, 0);
-    k_bs_emit<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bam_rec.p, c->sam_read_off.p, c->sam_tile.p, n, (unsigned long long)bytes, c->bs_cnt_off.p, c->bs_tile_cnt.p, c->ix.n_chr,
-                                                     (unsigned long long)c->bs_n, (unsigned long long)(c->bs_n + n_rec), (unsigned long long)c->bs_rec_used, c->bs_key, c->bs_off);
+    BS_ENSURE(c->bs.cnt_off, (size_t)n, "the per-read counts"); BS_ENSURE(c->bs.tile_cnt, (size_t)n_tiles + 1, "the per-workgroup counts");
+    HIPCHK(hipEventRecord(c->bs.ev[0], c->stream));
+    k_bs_count<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bam.rec.p, c->sam.read_off.p, c->sam.tile.p, n, (unsigned long long)bytes, c->bs.cnt_off.p, c->bs.tile_cnt.p);
+    k_scan_top<<<1, 256, 0, c->stream>>>(c->bs.tile_cnt.p, n_tiles, (uint32_t *)(c->bs.stat.d + 1), nullptr, 0, nullptr, 0);
+    k_bs_emit<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bam.rec.p, c->sam.read_off.p, c->sam.tile.p, n, (unsigned long long)bytes, c->bs.cnt_off.p, c->bs.tile_cnt.p, c->ix.n_chr,
+                                                     (unsigned long long)c->bs.n, (unsigned long long)(c->bs.n + n_rec), (unsigned long long)c->bs.rec_used, c->bs.key, c->bs.off);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(c->bs_rec + c->bs_rec_used, c->bam_rec.p, bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev_bs[1], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_bs_stat + 1, c->d_bs_stat + 1, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bs.rec + c->bs.rec_used, c->bam.rec.p, bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->bs.ev[1], c->stream));
+    HIPCHK(hipMemcpyAsync(c->bs.stat.h + 1, c->bs.stat.d + 1, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));                                       // the one wait: the walk must find the records the formatter counted
-    (void)hipEventElapsedTime(&c->bs_acc_ms, c->ev_bs[0], c->ev_bs[1]);
-    const size_t found = (size_t)(uint32_t)c->h_bs_stat[1];
+    c->bs.acc_ms = c->bs.ev.ms(0, 1);
+    const size_t found = (size_t)(uint32_t)c->bs.stat.h[1];
     if (found != n_rec) { snprintf(c->err, 512, "%s: the walk over the batch's records found %zu, the formatter wrote %zu; nothing was added", fn, found, n_rec); return DG_ERR_INTERNAL; }
     bs_commit(c, ordinal, n_rec, bytes);
-    c->bam_rec_stored = true;
+    c->bam.rec_stored = true;
     if (n_records) *n_records = n_rec;
     if (n_bytes) *n_bytes = bytes;
     return DG_OK;
@@ -3010,16 +2841,16 @@ extern "C" int dg_bam_sort_add(dg_ctx *c, const void *records, size_t n, uint32_
     if (!n) return DG_OK;
     const unsigned char *p = (const unsigned char *)records;
     const int n_chr = c->ix.n_chr;
-    const uint64_t base = c->bs_rec_used;
+    const uint64_t base = c->bs.rec_used;
     std::vector<uint64_t> keys; std::vector<int64_t> offs;
     size_t bad = 0; int why = BS_REC_OK;
     const size_t n_rec = bs_walk_checked(p, n, n_chr, &bad, &why, [&](size_t, size_t at) { keys.push_back(bs_key(p + at, n_chr)); offs.push_back((int64_t)(base + at)); });
     if (why) { snprintf(c->err, 512, "%s: record %zu: %s; nothing was added", fn, bad, bs_rec_why(why)); return DG_ERR_ARG; }
     { const int rc = bs_reserve(c, n_rec, n, fn); if (rc) return rc; }
-    c->bs_fin_valid = false;
-    HIPCHK(hipMemcpyAsync(c->bs_rec + c->bs_rec_used, p, n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bs_key + c->bs_n, keys.data(), n_rec * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(c->bs_off + c->bs_n, offs.data(), n_rec * 8, hipMemcpyHostToDevice, c->stream));
+    c->bs.fin_valid = false;
+    HIPCHK(hipMemcpyAsync(c->bs.rec + c->bs.rec_used, p, n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bs.key + c->bs.n, keys.data(), n_rec * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->bs.off + c->bs.n, offs.data(), n_rec * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(wait_stream(c));
     bs_commit(c, ordinal, n_rec, n);
     if (n_records) *n_records = n_rec;
@@ -3033,32 +2864,23 @@ extern "C" int dg_bam_sort_merge(dg_ctx *dst, dg_ctx *src)
     const char *fn = "dg_bam_sort_merge";
     if (dst == src || dst->device != src->device) { snprintf(c->err, 512, "%s: the two contexts must differ and be on one device", fn); return DG_ERR_ARG; }
     { const int rc = bs_ready(dst); if (rc) return rc; }
-    if (!src->bs_n) { src->bs_fin_valid = false; return DG_OK; }
-    { const int rc = bs_state(src); if (rc) { snprintf(c->err, 512, "%s", src->err); return rc; } }
-    const size_t n_rec = src->bs_n, bytes = src->bs_rec_used;
+    if (!src->bs.n) { src->bs.fin_valid = false; return DG_OK; }
+    HIPCHK(src->bs.ready());
+    const size_t n_rec = src->bs.n, bytes = src->bs.rec_used;
     { const int rc = bs_reserve(dst, n_rec, bytes, fn); if (rc) return rc; }
-    dst->bs_fin_valid = false; src->bs_fin_valid = false;
+    dst->bs.fin_valid = false; src->bs.fin_valid = false;
     // behind everything the source's stream holds; the call waits for the destination's stream, so the source's storage is free again when it returns
-    HIPCHK(hipEventRecord(src->ev_bs[5], src->stream));
-    HIPCHK(hipStreamWaitEvent(dst->stream, src->ev_bs[5], 0));
-    HIPCHK(hipMemcpyAsync(dst->bs_rec + dst->bs_rec_used, src->bs_rec, bytes, hipMemcpyDeviceToDevice, dst->stream));
-    HIPCHK(hipMemcpyAsync(dst->bs_key + dst->bs_n, src->bs_key, n_rec * 8, hipMemcpyDeviceToDevice, dst->stream));
-    k_bs_shift<<<(unsigned)((n_rec + 255) / 256), 256, 0, dst->stream>>>(src->bs_off, dst->bs_off + dst->bs_n, (unsigned long long)n_rec, (long long)dst->bs_rec_used);
+    HIPCHK(hipEventRecord(src->bs.ev[5], src->stream));
+    HIPCHK(hipStreamWaitEvent(dst->stream, src->bs.ev[5], 0));
+    HIPCHK(hipMemcpyAsync(dst->bs.rec + dst->bs.rec_used, src->bs.rec, bytes, hipMemcpyDeviceToDevice, dst->stream));
+    HIPCHK(hipMemcpyAsync(dst->bs.key + dst->bs.n, src->bs.key, n_rec * 8, hipMemcpyDeviceToDevice, dst->stream));
+    k_bs_shift<<<(unsigned)((n_rec + 255) / 256), 256, 0, dst->stream>>>(src->bs.off, dst->bs.off + dst->bs.n, (unsigned long long)n_rec, (long long)dst->bs.rec_used);
     HIPCHK(hipGetLastError());
     HIPCHK(wait_stream(dst));
-    for (const BsSeg &s : src->bs_segs) dst->bs_segs.push_back(BsSeg{s.ordinal, s.start + (uint64_t)dst->bs_n, s.count});      // behind dst's own: among equal ordinals dst's come first
-    dst->bs_n += n_rec; dst->bs_rec_used += bytes;
-    src->bs_n = 0; src->bs_rec_used = 0; src->bs_segs.clear();
+    for (const BsSeg &s : src->bs.segs) dst->bs.segs.push_back(BsSeg{s.ordinal, s.start + (uint64_t)dst->bs.n, s.count});      // behind dst's own: among equal ordinals dst's come first
+    dst->bs.n += n_rec; dst->bs.rec_used += bytes;
+    src->bs.n = 0; src->bs.rec_used = 0; src->bs.segs.clear();
     return DG_OK;
-}
-
-// the store's sort (rs_sort_passes): n pairs in bs_k / bs_v [which]
-static int bs_sort(dg_ctx *c, uint32_t n, int bits, int &which)
-{
-    const char *fn = "dg_bam_sort_finish";
-    BS_ENSURE(c->bs_hist, rs_hist_words(n), "the sorter's histograms"); BS_ENSURE(c->bs_sums, rs_sums_words(n), "the sorter's sums");
-    uint64_t *const keys[2] = {c->bs_k[0].p, c->bs_k[1].p}; int64_t *const vals[2] = {c->bs_v[0].p, c->bs_v[1].p};
-    return rs_sort_passes(c, keys, vals, c->bs_hist.p, c->bs_sums.p, n, bits, which);
 }
 
 extern "C" int dg_bam_sort_finish(dg_ctx *c, size_t *n_records, size_t *n_raw, float *device_ms)
@@ -3068,54 +2890,54 @@ extern "C" int dg_bam_sort_finish(dg_ctx *c, size_t *n_records, size_t *n_raw, f
     if (n_records) *n_records = 0;
     if (n_raw) *n_raw = 0;
     if (device_ms) *device_ms = 0.f;
-    c->bs_fin_valid = false; c->bs_fin_bytes = 0; c->bs_fin_records = 0; c->bs_passes = 0;
-    c->bi_valid = false; c->bi_covered.clear();             // (no block of the new array has been compressed)
-    c->cv_valid = false;
-    for (float &m : c->bs_ms) m = 0.f;
+    c->bs.fin_valid = false; c->bs.fin_bytes = 0; c->bs.fin_records = 0; c->bs.passes = 0;
+    bs_array_changed(c);
+    for (float &m : c->bs.ms) m = 0.f;
     { const int rc = bs_ready(c); if (rc) return rc; }
-    if (!c->bs_n) { c->bs_fin_valid = true; return DG_OK; }
-    const size_t n = c->bs_n, bytes = c->bs_rec_used;
+    if (!c->bs.n) { c->bs.fin_valid = true; return DG_OK; }
+    const size_t n = c->bs.n, bytes = c->bs.rec_used;
     const uint32_t n_tiles = (uint32_t)((n + BS_THREADS - 1) / BS_THREADS);
-    for (int k = 0; k < 2; k++) { BS_ENSURE(c->bs_k[k], n, "the sorter's keys"); BS_ENSURE(c->bs_v[k], n, "the sorter's values"); }
-    BS_ENSURE(c->bs_tile, (size_t)n_tiles, "the per-workgroup sums"); BS_ENSURE(c->bs_sorted, bytes + 8, "the sorted records");
+    for (int k = 0; k < 2; k++) { BS_ENSURE(c->bs.sort.k[k], n, "the sorter's keys"); BS_ENSURE(c->bs.sort.v[k], n, "the sorter's values"); }
+    BS_ENSURE(c->bs.tile, (size_t)n_tiles, "the per-workgroup sums"); BS_ENSURE(c->bs.sorted, bytes + 8, "the sorted records");
     // step one: the segments in ordinal order (neighbours in the store that stay neighbours go in one copy)
-    std::vector<uint32_t> order(c->bs_segs.size());
-    bs_order_segments(c->bs_segs.data(), c->bs_segs.size(), order.data());
-    HIPCHK(hipEventRecord(c->ev_bs[0], c->stream));
+    std::vector<uint32_t> order(c->bs.segs.size());
+    bs_order_segments(c->bs.segs.data(), c->bs.segs.size(), order.data());
+    HIPCHK(hipEventRecord(c->bs.ev[0], c->stream));
     size_t at = 0;
     for (size_t i = 0; i < order.size();) {
-        const uint64_t start = c->bs_segs[order[i]].start;
-        uint64_t count = c->bs_segs[order[i]].count;
-        for (i++; i < order.size() && c->bs_segs[order[i]].start == start + count; i++) count += c->bs_segs[order[i]].count;
+        const uint64_t start = c->bs.segs[order[i]].start;
+        uint64_t count = c->bs.segs[order[i]].count;
+        for (i++; i < order.size() && c->bs.segs[order[i]].start == start + count; i++) count += c->bs.segs[order[i]].count;
         if (!count) continue;
-        HIPCHK(hipMemcpyAsync(c->bs_k[0].p + at, c->bs_key + start, count * 8, hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(c->bs_v[0].p + at, c->bs_off + start, count * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bs.sort.k[0].p + at, c->bs.key + start, count * 8, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(c->bs.sort.v[0].p + at, c->bs.off + start, count * 8, hipMemcpyDeviceToDevice, c->stream));
         at += count;
     }
     if (at != n) { snprintf(c->err, 512, "%s: the segments hold %zu records, the store %zu", fn, at, n); return DG_ERR_INTERNAL; }
-    HIPCHK(hipEventRecord(c->ev_bs[1], c->stream));
+    HIPCHK(hipEventRecord(c->bs.ev[1], c->stream));
     // step two: one stable sort; the values are the records' offsets in the store
     int which = 0;
     const int bits = bs_key_bits(c->ix.n_chr);
-    { const int rc = bs_sort(c, (uint32_t)n, bits, which); if (rc) return rc; }
-    c->bs_passes = (bits + 3) / 4;
-    HIPCHK(hipEventRecord(c->ev_bs[2], c->stream));
+    BS_ENSURE_SORT(c->bs.sort, (uint32_t)n);
+    { const int rc = c->bs.sort.sort(c, (uint32_t)n, bits, which); if (rc) return rc; }
+    c->bs.passes = (bits + 3) / 4;
+    HIPCHK(hipEventRecord(c->bs.ev[2], c->stream));
     // step three: lengths in sorted order, their scan (the places go where the sorter's other key buffer was), the gather
-    uint64_t *dst_off = c->bs_k[which ^ 1].p;
-    k_bs_len<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bs_rec, c->bs_v[which].p, (uint32_t)n, dst_off, c->bs_tile.p);
-    k_sam_top<<<1, 256, 0, c->stream>>>(c->bs_tile.p, n_tiles, c->d_bs_stat);
+    uint64_t *dst_off = c->bs.sort.k[which ^ 1].p;
+    k_bs_len<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bs.rec, c->bs.sort.v[which].p, (uint32_t)n, dst_off, c->bs.tile.p);
+    k_sam_top<<<1, 256, 0, c->stream>>>(c->bs.tile.p, n_tiles, c->bs.stat.d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_bs[3], c->stream));
-    k_bs_gather<<<(unsigned)((n + BS_GATHER_WAVES - 1) / BS_GATHER_WAVES), 64 * BS_GATHER_WAVES, 0, c->stream>>>(c->bs_rec, c->bs_v[which].p, dst_off, c->bs_tile.p, (uint32_t)n,
-                                                                                                             (unsigned long long)bytes, c->bs_sorted.p);
+    HIPCHK(hipEventRecord(c->bs.ev[3], c->stream));
+    k_bs_gather<<<(unsigned)((n + BS_GATHER_WAVES - 1) / BS_GATHER_WAVES), 64 * BS_GATHER_WAVES, 0, c->stream>>>(c->bs.rec, c->bs.sort.v[which].p, dst_off, c->bs.tile.p, (uint32_t)n,
+                                                                                                             (unsigned long long)bytes, c->bs.sorted.p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_bs[4], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_bs_stat, c->d_bs_stat, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->bs.ev[4], c->stream));
+    HIPCHK(hipMemcpyAsync(c->bs.stat.h, c->bs.stat.d, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
-    if ((size_t)c->h_bs_stat[0] != bytes) { snprintf(c->err, 512, "%s: the sorted records' lengths add up to %zu bytes, the store holds %zu", fn, (size_t)c->h_bs_stat[0], bytes); return DG_ERR_INTERNAL; }
+    if ((size_t)c->bs.stat.h[0] != bytes) { snprintf(c->err, 512, "%s: the sorted records' lengths add up to %zu bytes, the store holds %zu", fn, (size_t)c->bs.stat.h[0], bytes); return DG_ERR_INTERNAL; }
     float total = 0.f;
-    for (int k = 0; k < 4; k++) { (void)hipEventElapsedTime(&c->bs_ms[k], c->ev_bs[k], c->ev_bs[k + 1]); total += c->bs_ms[k]; }
-    c->bs_fin_valid = true; c->bs_fin_bytes = bytes; c->bs_fin_records = n; c->bs_fin_which = which;
+    for (int k = 0; k < 4; k++) { c->bs.ms[k] = c->bs.ev.ms(k, k + 1); total += c->bs.ms[k]; }
+    c->bs.fin_valid = true; c->bs.fin_bytes = bytes; c->bs.fin_records = n; c->bs.fin_which = which;
     if (n_records) *n_records = n;
     if (n_raw) *n_raw = bytes;
     if (device_ms) *device_ms = total;
@@ -3125,17 +2947,17 @@ extern "C" int dg_bam_sort_finish(dg_ctx *c, size_t *n_records, size_t *n_raw, f
 extern "C" int dg_bam_sort_device_ms(dg_ctx *c, float ms[5], int *n_passes)
 {
     if (!c || !ms) return DG_ERR_ARG;
-    for (int k = 0; k < 4; k++) ms[k] = c->bs_ms[k];
-    ms[4] = c->bs_acc_ms;
-    if (n_passes) *n_passes = c->bs_passes;
+    for (int k = 0; k < 4; k++) ms[k] = c->bs.ms[k];
+    ms[4] = c->bs.acc_ms;
+    if (n_passes) *n_passes = c->bs.passes;
     return DG_OK;
 }
 
 extern "C" int dg_bam_sort_device(dg_ctx *c, void **ptr, size_t *n_raw)
 {
     if (!c || !ptr || !n_raw) return DG_ERR_ARG;
-    if (!c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_sort_device: no sorted array (dg_bam_sort_finish first)"); return DG_ERR_ARG; }
-    *ptr = c->bs_fin_bytes ? c->bs_sorted.p : nullptr; *n_raw = c->bs_fin_bytes;
+    if (!c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_sort_device: no sorted array (dg_bam_sort_finish first)"); return DG_ERR_ARG; }
+    *ptr = c->bs.fin_bytes ? c->bs.sorted.p : nullptr; *n_raw = c->bs.fin_bytes;
     return DG_OK;
 }
 
@@ -3145,35 +2967,35 @@ extern "C" int dg_bam_sort_compress(dg_ctx *c, size_t raw_off, size_t raw_len, u
     const char *fn = "dg_bam_sort_compress";
     if (n_bytes) *n_bytes = 0;
     if (device_ms) *device_ms = 0.f;
-    c->bam_valid = false; c->bam_bytes = 0; c->bam_ptr = nullptr;
-    if (!c->bs_fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
+    c->bam.valid = false; c->bam.bytes = 0; c->bam.ptr = nullptr;
+    if (!c->bs.fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
     if (flags != 0u && flags != DG_BGZF_DYNAMIC && flags != DG_BAM_RAW) { snprintf(c->err, 512, "%s: flags 0x%x are none of 0, DG_BGZF_DYNAMIC, DG_BAM_RAW", fn, flags); return DG_ERR_ARG; }
-    const size_t total = c->bs_fin_bytes;
+    const size_t total = c->bs.fin_bytes;
     if (raw_off % BGZF_BLOCK || raw_off > total || raw_len > total - raw_off || (raw_len % BGZF_BLOCK && raw_off + raw_len != total)) {
         snprintf(c->err, 512, "%s: the range %zu + %zu of %zu bytes must begin at a multiple of %u, and end at one or at the array's end", fn, raw_off, raw_len, total, BGZF_BLOCK);
         return DG_ERR_ARG;
     }
-    if (!raw_len) { c->bam_valid = true; return DG_OK; }
+    if (!raw_len) { c->bam.valid = true; return DG_OK; }
     { const int rc = bs_ready(c); if (rc) return rc; }
-    unsigned char *in = c->bs_sorted.p + raw_off;
+    unsigned char *in = c->bs.sorted.p + raw_off;
     size_t out_bytes = raw_len; float ms = 0.f;
-    c->bam_ptr = in;
+    c->bam.ptr = in;
     if (flags != DG_BAM_RAW) {
         const int rc = bgzf_device(c, in, raw_len, flags == DG_BGZF_DYNAMIC, &out_bytes, &ms);
         if (rc) return rc;
-        c->bam_ptr = c->bgzf_out.p;
+        c->bam.ptr = c->bam.bgzf_out.p;
         // the blocks' compressed sizes, kept for dg_bam_index_finish: device to device, at the piece's block offset
         const size_t all_blocks = (total + BGZF_BLOCK - 1) / BGZF_BLOCK, b0 = raw_off / BGZF_BLOCK, nb = (raw_len + BGZF_BLOCK - 1) / BGZF_BLOCK;
         // (no memory for that array: the compression stands, the blocks stay uncovered, and dg_bam_index_finish without block_sizes says which block it misses)
-        if (c->bi_sizes.cap < all_blocks) { c->bi_covered.clear(); if (c->bi_sizes.ensure(all_blocks) != hipSuccess) (void)hipGetLastError(); }
-        if (c->bi_sizes.cap >= all_blocks) {
-            if (c->bi_covered.size() != all_blocks) c->bi_covered.assign(all_blocks, 0);
-            HIPCHK(hipMemcpyAsync(c->bi_sizes.p + b0, c->bgzf_size.p, nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-            std::fill(c->bi_covered.begin() + (long)b0, c->bi_covered.begin() + (long)(b0 + nb), (unsigned char)1);
+        if (c->bi.sizes.cap < all_blocks) { c->bi.covered.clear(); if (c->bi.sizes.ensure(all_blocks) != hipSuccess) (void)hipGetLastError(); }
+        if (c->bi.sizes.cap >= all_blocks) {
+            if (c->bi.covered.size() != all_blocks) c->bi.covered.assign(all_blocks, 0);
+            HIPCHK(hipMemcpyAsync(c->bi.sizes.p + b0, c->bam.bgzf_size.p, nb * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+            std::fill(c->bi.covered.begin() + (long)b0, c->bi.covered.begin() + (long)(b0 + nb), (unsigned char)1);
         }
     }
-    c->bam_bytes = out_bytes; c->bam_valid = true;
-    c->bam_ms[0] = 0.f; c->bam_ms[1] = ms;
+    c->bam.bytes = out_bytes; c->bam.valid = true;
+    c->bam.ms[0] = 0.f; c->bam.ms[1] = ms;
     if (n_bytes) *n_bytes = out_bytes;
     if (device_ms) *device_ms = ms;
     return DG_OK;
@@ -3182,16 +3004,6 @@ extern "C" int dg_bam_sort_compress(dg_ctx *c, size_t raw_off, size_t raw_len, u
 // ------------------------------------------------------------------------------------------
 // the BAM index of the sorted array (dg_bamidx.h): built in HBM from the sorted records, their places and the blocks' compressed sizes
 // ------------------------------------------------------------------------------------------
-static int bi_state(dg_ctx *c)
-{
-    if (c->d_bi_stat) return DG_OK;
-    HIPCHK(hipMalloc((void **)&c->d_bi_stat, BI_ST_WORDS * 8));
-    HIPCHK(hipHostMalloc((void **)&c->h_bi_stat, BI_ST_WORDS * 8, hipHostMallocDefault));
-    memset(c->h_bi_stat, 0, BI_ST_WORDS * 8);
-    for (hipEvent_t &e : c->ev_bi) HIPCHK(hipEventCreate(&e));
-    return DG_OK;
-}
-
 extern "C" int dg_bam_index_granules(int out[2])
 {
     if (!out) return DG_ERR_ARG;
@@ -3206,12 +3018,12 @@ extern "C" int dg_bam_index_finish(dg_ctx *c, uint64_t first_block_offset, const
     if (n_bytes) *n_bytes = 0;
     if (device_ms) *device_ms = 0.f;
     if (stats) for (int k = 0; k < 6; k++) stats[k] = 0;
-    c->bi_valid = false; c->bi_bytes = 0;
-    if (!c->bs_fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
-    { const int rc = bs_ready(c); if (rc) return rc; }
-    { const int rc = bi_state(c); if (rc) return rc; }
-    const size_t n = c->bs_fin_records, n_raw = c->bs_fin_bytes, n_blocks = (n_raw + BGZF_BLOCK - 1) / BGZF_BLOCK;
-    const int n_chr = c->ix.n_chr;
+    c->bi.valid = false; c->bi.bytes = 0;
+    BsView sv;
+    { const int rc = bs_view(c, fn, sv); if (rc) return rc; }
+    HIPCHK(c->bi.ready());
+    const size_t n = sv.n, n_raw = sv.n_raw, n_blocks = (n_raw + BGZF_BLOCK - 1) / BGZF_BLOCK;
+    const int n_chr = sv.n_chr;
     if (n_chr < 1 || n_blocks > 0xFFFFFFF0ull) { snprintf(c->err, 512, "%s: %d chromosomes, %zu blocks", fn, n_chr, n_blocks); return DG_ERR_ARG; }
     if (first_block_offset >> 48) { snprintf(c->err, 512, "%s: the first block's file offset %llu does not fit a virtual offset's 48 bits", fn, (unsigned long long)first_block_offset); return DG_ERR_RANGE; }
     // the blocks' sizes: the caller's, or what the last dg_bam_sort_compress of every block left
@@ -3219,102 +3031,99 @@ extern "C" int dg_bam_index_finish(dg_ctx *c, uint64_t first_block_offset, const
     if (block_sizes) {
         if (n_blocks_given != n_blocks) { snprintf(c->err, 512, "%s: n_blocks is %zu, the sorted array of %zu bytes has %zu blocks of %u bytes", fn, n_blocks_given, n_raw, n_blocks, BGZF_BLOCK); return DG_ERR_ARG; }
         for (size_t k = 0; k < n_blocks; k++) if (!block_sizes[k]) { snprintf(c->err, 512, "%s: block %zu has the compressed size 0", fn, k); return DG_ERR_ARG; }
-        BS_ENSURE(c->bi_sizes_in, n_blocks + 1, "the blocks' compressed sizes");
-        if (n_blocks) HIPCHK(hipMemcpyAsync(c->bi_sizes_in.p, block_sizes, n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        sizes = c->bi_sizes_in.p;
+        BS_ENSURE(c->bi.sizes_in, n_blocks + 1, "the blocks' compressed sizes");
+        if (n_blocks) HIPCHK(hipMemcpyAsync(c->bi.sizes_in.p, block_sizes, n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        sizes = c->bi.sizes_in.p;
     } else {
-        for (size_t k = 0; k < n_blocks; k++) if (k >= c->bi_covered.size() || !c->bi_covered[k]) {
+        for (size_t k = 0; k < n_blocks; k++) if (k >= c->bi.covered.size() || !c->bi.covered[k]) {
             snprintf(c->err, 512, "%s: block %zu of the sorted array has not been compressed since dg_bam_sort_finish (dg_bam_sort_compress without DG_BAM_RAW), and no block_sizes are given", fn, k);
             return DG_ERR_ARG;
         }
-        sizes = c->bi_sizes.p;
+        sizes = c->bi.sizes.p;
     }
     const uint32_t tiles = (uint32_t)((n + BI_THREADS - 1) / BI_THREADS);
-    BS_ENSURE(c->bi_coff, n_blocks + 1, "the blocks' file offsets");
-    BS_ENSURE(c->bi_key, n + 1, "the records' bins"); BS_ENSURE(c->bi_voff, n + 1, "the records' virtual offsets"); BS_ENSURE(c->bi_span, n + 1, "the records' windows");
-    BS_ENSURE(c->bi_tile_cnt, (size_t)tiles + 1, "the per-workgroup chunk counts");
-    BS_ENSURE(c->bi_ref, (size_t)BI_REF_PLANES * n_chr, "the per-reference values");
-    BS_ENSURE(c->bi_ref_q, (size_t)n_chr + 1, "the per-reference chunk counts"); BS_ENSURE(c->bi_ref_b, (size_t)n_chr + 1, "the per-reference bin counts");
-    BS_ENSURE(c->bi_ref_at, (size_t)n_chr + 1, "the per-reference byte offsets"); BS_ENSURE(c->bi_lin_at, (size_t)n_chr + 1, "the per-reference window offsets");
-    c->h_bi_ref.resize((size_t)BI_REF_PLANES * n_chr); c->h_bi_lin_at.resize((size_t)n_chr + 1);
-    const uint64_t *dst_off = c->bs_k[c->bs_fin_which ^ 1].p;
-    HIPCHK(hipMemsetAsync(c->d_bi_stat, 0, BI_ST_WORDS * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_bi_stat + BI_ST_BAD, 0xff, 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->bi_ref.p, 0, (size_t)BI_REF_PLANES * n_chr * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->bi_ref.p + 3 * (size_t)n_chr, 0xff, (size_t)n_chr * 8, c->stream));
-    HIPCHK(hipEventRecord(c->ev_bi[0], c->stream));
-    k_bi_coff<<<1, BI_THREADS, 0, c->stream>>>(sizes, (uint32_t)n_blocks, (unsigned long long)first_block_offset, c->bi_coff.p, c->d_bi_stat);
+    BS_ENSURE(c->bi.coff, n_blocks + 1, "the blocks' file offsets");
+    BS_ENSURE(c->bi.key, n + 1, "the records' bins"); BS_ENSURE(c->bi.voff, n + 1, "the records' virtual offsets"); BS_ENSURE(c->bi.span, n + 1, "the records' windows");
+    BS_ENSURE(c->bi.tile_cnt, (size_t)tiles + 1, "the per-workgroup chunk counts");
+    BS_ENSURE(c->bi.ref, (size_t)BI_REF_PLANES * n_chr, "the per-reference values");
+    BS_ENSURE(c->bi.ref_q, (size_t)n_chr + 1, "the per-reference chunk counts"); BS_ENSURE(c->bi.ref_b, (size_t)n_chr + 1, "the per-reference bin counts");
+    BS_ENSURE(c->bi.ref_at, (size_t)n_chr + 1, "the per-reference byte offsets"); BS_ENSURE(c->bi.lin_at, (size_t)n_chr + 1, "the per-reference window offsets");
+    c->bi.h_ref.resize((size_t)BI_REF_PLANES * n_chr); c->bi.h_lin_at.resize((size_t)n_chr + 1);
+    HIPCHK(hipMemsetAsync(c->bi.stat.d, 0, BI_ST_WORDS * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->bi.stat.d + BI_ST_BAD, 0xff, 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->bi.ref.p, 0, (size_t)BI_REF_PLANES * n_chr * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->bi.ref.p + 3 * (size_t)n_chr, 0xff, (size_t)n_chr * 8, c->stream));
+    HIPCHK(hipEventRecord(c->bi.ev[0], c->stream));
+    k_bi_coff<<<1, BI_THREADS, 0, c->stream>>>(sizes, (uint32_t)n_blocks, (unsigned long long)first_block_offset, c->bi.coff.p, c->bi.stat.d);
     if (n) {
-        k_bi_rec<<<tiles, BI_THREADS, 0, c->stream>>>(c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, c->bi_coff.p, (uint32_t)n_blocks, n_chr,
-                                                      c->bi_key.p, c->bi_voff.p, c->bi_span.p, c->bi_ref.p, c->d_bi_stat);
-        k_bi_heads<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi_key.p, (uint32_t)n, c->bi_tile_cnt.p);
-        k_scan_top<<<1, 256, 0, c->stream>>>(c->bi_tile_cnt.p, tiles, (uint32_t *)(c->d_bi_stat + BI_ST_CHUNKS), nullptr, 0, nullptr, 0);
+        k_bi_rec<<<tiles, BI_THREADS, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, c->bi.coff.p, (uint32_t)n_blocks, n_chr,
+                                                      c->bi.key.p, c->bi.voff.p, c->bi.span.p, c->bi.ref.p, c->bi.stat.d);
+        k_bi_heads<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi.key.p, (uint32_t)n, c->bi.tile_cnt.p);
+        k_scan_top<<<1, 256, 0, c->stream>>>(c->bi.tile_cnt.p, tiles, (uint32_t *)(c->bi.stat.d + BI_ST_CHUNKS), nullptr, 0, nullptr, 0);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_bi[1], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_bi_stat, c->d_bi_stat, BI_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_bi_ref.data(), c->bi_ref.p, (size_t)BI_REF_PLANES * n_chr * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->bi.ev[1], c->stream));
+    HIPCHK(c->bi.stat.fetch(c->stream));
+    HIPCHK(hipMemcpyAsync(c->bi.h_ref.data(), c->bi.ref.p, (size_t)BI_REF_PLANES * n_chr * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));                                       // the first wait: the per-reference sizes (and the chunk count, and what was out of range)
-    if (c->h_bi_stat[BI_ST_COFF_END] >> 48) { snprintf(c->err, 512, "%s: the file offset %llu behind the last block does not fit a virtual offset's 48 bits", fn, c->h_bi_stat[BI_ST_COFF_END]); return DG_ERR_RANGE; }
-    if (c->h_bi_stat[BI_ST_BAD] != BI_NONE) {
-        snprintf(c->err, 512, "%s: record %llu of the sorted array ends behind position 2^29: a BAI cannot hold it, such a reference needs a CSI index; no index was built", fn, c->h_bi_stat[BI_ST_BAD]);
+    if (c->bi.stat.h[BI_ST_COFF_END] >> 48) { snprintf(c->err, 512, "%s: the file offset %llu behind the last block does not fit a virtual offset's 48 bits", fn, c->bi.stat.h[BI_ST_COFF_END]); return DG_ERR_RANGE; }
+    if (c->bi.stat.h[BI_ST_BAD] != BI_NONE) {
+        snprintf(c->err, 512, "%s: record %llu of the sorted array ends behind position 2^29: a BAI cannot hold it, such a reference needs a CSI index; no index was built", fn, c->bi.stat.h[BI_ST_BAD]);
         return DG_ERR_RANGE;
     }
-    const size_t n_chunks = (size_t)(uint32_t)c->h_bi_stat[BI_ST_CHUNKS];
+    const size_t n_chunks = (size_t)(uint32_t)c->bi.stat.h[BI_ST_CHUNKS];
     size_t n_placed = 0, n_lin = 0;
     for (int t = 0; t < n_chr; t++) {
-        c->h_bi_lin_at[(size_t)t] = n_lin;
-        n_lin += (size_t)c->h_bi_ref[(size_t)t];
-        n_placed += (size_t)(c->h_bi_ref[(size_t)n_chr + t] + c->h_bi_ref[2 * (size_t)n_chr + t]);
+        c->bi.h_lin_at[(size_t)t] = n_lin;
+        n_lin += (size_t)c->bi.h_ref[(size_t)t];
+        n_placed += (size_t)(c->bi.h_ref[(size_t)n_chr + t] + c->bi.h_ref[2 * (size_t)n_chr + t]);
     }
-    c->h_bi_lin_at[(size_t)n_chr] = n_lin;
+    c->bi.h_lin_at[(size_t)n_chr] = n_lin;
     if (n_placed > n || n_chunks > n_placed) { snprintf(c->err, 512, "%s: %zu placed records and %zu chunks of %zu records", fn, n_placed, n_chunks, n); return DG_ERR_INTERNAL; }
     const size_t cap = (size_t)bi_bytes_bound((uint64_t)n_chr, n_chunks, n_lin);
     const uint32_t ctiles = (uint32_t)((n_chunks + BI_THREADS - 1) / BI_THREADS);
-    BS_ENSURE(c->bi_lin, n_lin + 1, "the linear index"); BS_ENSURE(c->bi_out, cap, "the index");
-    for (int k = 0; k < 2; k++) { BS_ENSURE(c->bi_ck[k], n_chunks + 1, "the chunks' keys"); BS_ENSURE(c->bi_cv[k], n_chunks + 1, "the chunks' numbers"); }
-    BS_ENSURE(c->bi_chead, n_chunks + 1, "the chunks' first records"); BS_ENSURE(c->bi_mhead, n_chunks + 1, "the merged chunks"); BS_ENSURE(c->bi_mbin, n_chunks + 1, "the merged chunks' bins");
-    BS_ENSURE(c->bi_binq, n_chunks + 1, "the bins' first chunks"); BS_ENSURE(c->bi_flag, n_chunks + 1, "the chunks' flags"); BS_ENSURE(c->bi_excl, n_chunks + 1, "the chunks' places");
-    BS_ENSURE(c->bi_ctile, (size_t)ctiles + 1, "the per-workgroup sums");
-    BS_ENSURE(c->bi_hist, rs_hist_words((uint32_t)n_chunks), "the sorter's histograms"); BS_ENSURE(c->bi_sums, rs_sums_words((uint32_t)n_chunks), "the sorter's sums");
-    HIPCHK(hipMemcpyAsync(c->bi_lin_at.p, c->h_bi_lin_at.data(), ((size_t)n_chr + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev_bi[2], c->stream));
-    HIPCHK(hipMemsetAsync(c->bi_out.p, 0, cap, c->stream));
+    BS_ENSURE(c->bi.lin, n_lin + 1, "the linear index"); BS_ENSURE(c->bi.out, cap, "the index");
+    for (int k = 0; k < 2; k++) { BS_ENSURE(c->bi.sort.k[k], n_chunks + 1, "the chunks' keys"); BS_ENSURE(c->bi.sort.v[k], n_chunks + 1, "the chunks' numbers"); }
+    BS_ENSURE(c->bi.chead, n_chunks + 1, "the chunks' first records"); BS_ENSURE(c->bi.mhead, n_chunks + 1, "the merged chunks"); BS_ENSURE(c->bi.mbin, n_chunks + 1, "the merged chunks' bins");
+    BS_ENSURE(c->bi.binq, n_chunks + 1, "the bins' first chunks"); BS_ENSURE(c->bi.flag, n_chunks + 1, "the chunks' flags"); BS_ENSURE(c->bi.excl, n_chunks + 1, "the chunks' places");
+    BS_ENSURE(c->bi.ctile, (size_t)ctiles + 1, "the per-workgroup sums");
+    BS_ENSURE_SORT(c->bi.sort, (uint32_t)n_chunks);
+    HIPCHK(hipMemcpyAsync(c->bi.lin_at.p, c->bi.h_lin_at.data(), ((size_t)n_chr + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->bi.ev[2], c->stream));
+    HIPCHK(hipMemsetAsync(c->bi.out.p, 0, cap, c->stream));
     if (n_lin) {
-        HIPCHK(hipMemsetAsync(c->bi_lin.p, 0xff, n_lin * 8, c->stream));
-        k_bi_lin<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi_key.p, c->bi_span.p, c->bi_voff.p, (uint32_t)n, n_chr, c->bi_lin_at.p, c->bi_lin.p);
+        HIPCHK(hipMemsetAsync(c->bi.lin.p, 0xff, n_lin * 8, c->stream));
+        k_bi_lin<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi.key.p, c->bi.span.p, c->bi.voff.p, (uint32_t)n, n_chr, c->bi.lin_at.p, c->bi.lin.p);
     }
     int which = 0;
     if (n_chunks) {
-        k_bi_chunks<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi_key.p, (uint32_t)n, c->bi_tile_cnt.p, (uint32_t)n_chunks, (uint32_t)n_placed, c->bi_ck[0].p, c->bi_cv[0].p, c->bi_chead.p);
-        uint64_t *const keys[2] = {c->bi_ck[0].p, c->bi_ck[1].p}; int64_t *const vals[2] = {c->bi_cv[0].p, c->bi_cv[1].p};
-        { const int rc = rs_sort_passes(c, keys, vals, c->bi_hist.p, c->bi_sums.p, (uint32_t)n_chunks, bi_key_bits(n_chr), which); if (rc) return rc; }
-        k_bi_merge_scan<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi_ck[which].p, c->bi_cv[which].p, c->bi_chead.p, c->bi_voff.p, (uint32_t)n_chunks, c->bi_flag.p, c->bi_excl.p, c->bi_ctile.p);
-        k_sam_top<<<1, 256, 0, c->stream>>>(c->bi_ctile.p, ctiles, c->d_bi_stat + BI_ST_MERGED);
-        k_bi_merge_emit<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi_ck[which].p, c->bi_flag.p, c->bi_excl.p, c->bi_ctile.p, (uint32_t)n_chunks, n_chr, c->d_bi_stat, c->bi_mhead.p, c->bi_mbin.p,
-                                                               c->bi_binq.p, c->bi_ref_q.p, c->bi_ref_b.p);
+        k_bi_chunks<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi.key.p, (uint32_t)n, c->bi.tile_cnt.p, (uint32_t)n_chunks, (uint32_t)n_placed, c->bi.sort.k[0].p, c->bi.sort.v[0].p, c->bi.chead.p);
+        { const int rc = c->bi.sort.sort(c, (uint32_t)n_chunks, bi_key_bits(n_chr), which); if (rc) return rc; }
+        k_bi_merge_scan<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi.sort.k[which].p, c->bi.sort.v[which].p, c->bi.chead.p, c->bi.voff.p, (uint32_t)n_chunks, c->bi.flag.p, c->bi.excl.p, c->bi.ctile.p);
+        k_sam_top<<<1, 256, 0, c->stream>>>(c->bi.ctile.p, ctiles, c->bi.stat.d + BI_ST_MERGED);
+        k_bi_merge_emit<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi.sort.k[which].p, c->bi.flag.p, c->bi.excl.p, c->bi.ctile.p, (uint32_t)n_chunks, n_chr, c->bi.stat.d, c->bi.mhead.p, c->bi.mbin.p,
+                                                               c->bi.binq.p, c->bi.ref_q.p, c->bi.ref_b.p);
     } else {
-        HIPCHK(hipMemsetAsync(c->bi_ref_q.p, 0, ((size_t)n_chr + 1) * 4, c->stream));
-        HIPCHK(hipMemsetAsync(c->bi_ref_b.p, 0, ((size_t)n_chr + 1) * 4, c->stream));
+        HIPCHK(hipMemsetAsync(c->bi.ref_q.p, 0, ((size_t)n_chr + 1) * 4, c->stream));
+        HIPCHK(hipMemsetAsync(c->bi.ref_b.p, 0, ((size_t)n_chr + 1) * 4, c->stream));
     }
-    k_bi_refs<<<1, BI_THREADS, 0, c->stream>>>(n_chr, c->bi_ref.p, c->bi_ref_q.p, c->bi_ref_b.p, (unsigned long long)(n - n_placed), c->bi_ref_at.p, c->bi_out.p, (unsigned long long)cap, c->d_bi_stat);
+    k_bi_refs<<<1, BI_THREADS, 0, c->stream>>>(n_chr, c->bi.ref.p, c->bi.ref_q.p, c->bi.ref_b.p, (unsigned long long)(n - n_placed), c->bi.ref_at.p, c->bi.out.p, (unsigned long long)cap, c->bi.stat.d);
     if (n_chunks)
-        k_bi_write_chunks<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi_ck[which].p, c->bi_cv[which].p, c->bi_chead.p, c->bi_voff.p, (uint32_t)n_chunks, c->d_bi_stat, c->bi_mhead.p, c->bi_mbin.p,
-                                                                 c->bi_binq.p, c->bi_ref_q.p, c->bi_ref_b.p, c->bi_ref_at.p, n_chr, c->bi_out.p, (unsigned long long)cap);
-    k_bi_write_refs<<<(unsigned)n_chr, BI_THREADS, 0, c->stream>>>(n_chr, c->bi_ref.p, c->bi_ref_q.p, c->bi_ref_b.p, c->bi_ref_at.p, c->bi_voff.p, (uint32_t)n, c->bi_lin_at.p, c->bi_lin.p,
-                                                                   c->bi_out.p, (unsigned long long)cap);
+        k_bi_write_chunks<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi.sort.k[which].p, c->bi.sort.v[which].p, c->bi.chead.p, c->bi.voff.p, (uint32_t)n_chunks, c->bi.stat.d, c->bi.mhead.p, c->bi.mbin.p,
+                                                                 c->bi.binq.p, c->bi.ref_q.p, c->bi.ref_b.p, c->bi.ref_at.p, n_chr, c->bi.out.p, (unsigned long long)cap);
+    k_bi_write_refs<<<(unsigned)n_chr, BI_THREADS, 0, c->stream>>>(n_chr, c->bi.ref.p, c->bi.ref_q.p, c->bi.ref_b.p, c->bi.ref_at.p, c->bi.voff.p, (uint32_t)n, c->bi.lin_at.p, c->bi.lin.p,
+                                                                   c->bi.out.p, (unsigned long long)cap);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_bi[3], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_bi_stat, c->d_bi_stat, BI_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->bi.ev[3], c->stream));
+    HIPCHK(c->bi.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the second wait: the index's size
-    const size_t total = (size_t)c->h_bi_stat[BI_ST_BYTES], n_merged = (size_t)(uint32_t)c->h_bi_stat[BI_ST_MERGED], n_bins = (size_t)(c->h_bi_stat[BI_ST_MERGED] >> 32);
+    const size_t total = (size_t)c->bi.stat.h[BI_ST_BYTES], n_merged = (size_t)(uint32_t)c->bi.stat.h[BI_ST_MERGED], n_bins = (size_t)(c->bi.stat.h[BI_ST_MERGED] >> 32);
     if (total > cap || total < 16 + 8 * (size_t)n_chr || n_merged > n_chunks || n_bins > n_merged) {
         snprintf(c->err, 512, "%s: an index of %zu bytes (%zu chunks, %zu bins) where at most %zu bytes and %zu chunks can be", fn, total, n_merged, n_bins, cap, n_chunks);
         return DG_ERR_INTERNAL;
     }
-    float a = 0.f, b = 0.f;
-    (void)hipEventElapsedTime(&a, c->ev_bi[0], c->ev_bi[1]); (void)hipEventElapsedTime(&b, c->ev_bi[2], c->ev_bi[3]);
-    c->bi_valid = true; c->bi_bytes = total;
+    const float a = c->bi.ev.ms(0, 1), b = c->bi.ev.ms(2, 3);
+    c->bi.valid = true; c->bi.bytes = total;
     if (n_bytes) *n_bytes = total;
     if (device_ms) *device_ms = a + b;
     if (stats) { stats[0] = n_placed; stats[1] = n - n_placed; stats[2] = n_bins; stats[3] = n_chunks; stats[4] = n_merged; stats[5] = n_lin; }
@@ -3324,10 +3133,10 @@ extern "C" int dg_bam_index_finish(dg_ctx *c, uint64_t first_block_offset, const
 extern "C" int dg_bam_index_download(dg_ctx *c, void *out, size_t cap)
 {
     if (!c || (!out && cap)) return DG_ERR_ARG;
-    if (!c->bi_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_index_download: no index (dg_bam_index_finish first, and no store call behind it)"); return DG_ERR_ARG; }
-    if (cap < c->bi_bytes) { snprintf(c->err, 512, "dg_bam_index_download: the index has %zu bytes, the buffer %zu", c->bi_bytes, cap); return DG_ERR_CAPACITY; }
+    if (!c->bi.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_index_download: no index (dg_bam_index_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if (cap < c->bi.bytes) { snprintf(c->err, 512, "dg_bam_index_download: the index has %zu bytes, the buffer %zu", c->bi.bytes, cap); return DG_ERR_CAPACITY; }
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(out, c->bi_out.p, c->bi_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out, c->bi.out.p, c->bi.bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
@@ -3335,8 +3144,8 @@ extern "C" int dg_bam_index_download(dg_ctx *c, void *out, size_t cap)
 extern "C" int dg_bam_index_device(dg_ctx *c, void **ptr, size_t *n_bytes)
 {
     if (!c || !ptr || !n_bytes) return DG_ERR_ARG;
-    if (!c->bi_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_index_device: no index (dg_bam_index_finish first, and no store call behind it)"); return DG_ERR_ARG; }
-    *ptr = c->bi_out.p; *n_bytes = c->bi_bytes;
+    if (!c->bi.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_index_device: no index (dg_bam_index_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    *ptr = c->bi.out.p; *n_bytes = c->bi.bytes;
     return DG_OK;
 }
 
@@ -3386,20 +3195,20 @@ static int gc_ready(dg_ctx *c, const char *fn, bool fresh = false)
     if (sh) { std::lock_guard<std::mutex> lk(sh->mu); gen = sh->gc_gen; rows = 4 + (size_t)sh->gc_n_genes; }
     if (!gen) { snprintf(c->err, 512, "%s: no gene annotation (dg_gene_set_annotation first)", fn); return DG_ERR_ARG; }
     HIPCHK(hipSetDevice(c->device));
-    if (!c->ev_gc[0]) for (hipEvent_t &e : c->ev_gc) HIPCHK(hipEventCreate(&e));
-    if (c->gc_counts && c->gc_gen == gen && !fresh) return DG_OK;
-    if (c->gc_counts && c->gc_gen != gen && c->gc_nonempty && !fresh) {
-        snprintf(c->err, 512, "%s: the table holds counts of annotation generation %llu, the annotation is generation %llu now (dg_gene_reset first)", fn, (unsigned long long)c->gc_gen, (unsigned long long)gen);
+    HIPCHK(c->gc.ready());
+    if (c->gc.counts && c->gc.gen == gen && !fresh) return DG_OK;
+    if (c->gc.counts && c->gc.gen != gen && c->gc.nonempty && !fresh) {
+        snprintf(c->err, 512, "%s: the table holds counts of annotation generation %llu, the annotation is generation %llu now (dg_gene_reset first)", fn, (unsigned long long)c->gc.gen, (unsigned long long)gen);
         return DG_ERR_ARG;
     }
-    if (!c->gc_counts || c->gc_rows != rows) {
+    if (!c->gc.counts || c->gc.rows != rows) {
         unsigned long long *t = nullptr;
         HIPCHK(hipMalloc((void **)&t, rows * 3 * 8));
-        if (c->gc_counts) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->gc_counts); }
-        c->gc_counts = t; c->gc_rows = rows;
+        if (c->gc.counts) { (void)hipStreamSynchronize(c->stream); (void)hipFree(c->gc.counts); }
+        c->gc.counts = t; c->gc.rows = rows;
     }
-    HIPCHK(hipMemsetAsync(c->gc_counts, 0, c->gc_rows * 3 * 8, c->stream));
-    c->gc_gen = gen; c->gc_nonempty = false;
+    HIPCHK(hipMemsetAsync(c->gc.counts, 0, c->gc.rows * 3 * 8, c->stream));
+    c->gc.gen = gen; c->gc.nonempty = false;
     return DG_OK;
 }
 
@@ -3411,16 +3220,16 @@ static int gc_count_device(dg_ctx *c, GcBatch b, const char *fn)
     const unsigned long long n_wg = (n_units + GC_THREADS - 1) / GC_THREADS;
     if (!n_units) return DG_OK;
     if (n_wg > 0x7FFFFFFFull) { snprintf(c->err, 512, "%s: %llu units are more than one call takes", fn, n_units); return DG_ERR_ARG; }
-    HIPCHK(c->gc_wg.ensure((size_t)n_wg * 12));
+    HIPCHK(c->gc.wg.ensure((size_t)n_wg * 12));
     std::lock_guard<std::mutex> lk(sh->mu);          // (dg_gene_set_annotation replaces the table under the same lock and waits for the device before it frees the old one)
-    if (sh->gc_gen != c->gc_gen) { snprintf(c->err, 512, "%s: the annotation was replaced while the call was being prepared", fn); return DG_ERR_ARG; }
+    if (sh->gc_gen != c->gc.gen) { snprintf(c->err, 512, "%s: the annotation was replaced while the call was being prepared", fn); return DG_ERR_ARG; }
     const GcTable t{sh->d_gc_chr_first, sh->d_gc_seg_start, sh->d_gc_seg_lab, c->ix.n_chr};
-    HIPCHK(hipEventRecord(c->ev_gc[0], c->stream));
-    k_gc_count<<<(unsigned)n_wg, GC_THREADS, 0, c->stream>>>(b, t, n_units, c->gc_counts, (unsigned long long)c->gc_rows, c->gc_wg.p);
-    k_gc_top<<<1, 256, 0, c->stream>>>(c->gc_wg.p, n_wg, c->gc_counts);
+    HIPCHK(hipEventRecord(c->gc.ev[0], c->stream));
+    k_gc_count<<<(unsigned)n_wg, GC_THREADS, 0, c->stream>>>(b, t, n_units, c->gc.counts, (unsigned long long)c->gc.rows, c->gc.wg.p);
+    k_gc_top<<<1, 256, 0, c->stream>>>(c->gc.wg.p, n_wg, c->gc.counts);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_gc[1], c->stream));
-    c->gc_timed = true; c->gc_nonempty = true;
+    HIPCHK(hipEventRecord(c->gc.ev[1], c->stream));
+    c->gc.timed = true; c->gc.nonempty = true;
     return DG_OK;
 }
 
@@ -3440,14 +3249,14 @@ extern "C" int dg_batch_accumulate_genes(dg_ctx *c, int n_pair_mode, uint32_t mi
     if (!c->batch_done) { snprintf(c->err, 512, "%s: the context has no finished batch (upload and run one first)", fn); return DG_ERR_ARG; }
     { const int rc = gc_pair_mode_ok(c, fn, n_pair_mode, c->n_reads); if (rc) return rc; }
     if (c->n_reads && !c->full_valid) { snprintf(c->err, 512, "%s: the last batch has no full records (it was mapped through dg_map_batch_compact)", fn); return DG_ERR_ARG; }
-    if (c->gc_batch_counted) { snprintf(c->err, 512, "%s: the units of this batch are in the table already (a batch is counted once)", fn); return DG_ERR_ARG; }
+    if (c->gc.batch_counted) { snprintf(c->err, 512, "%s: the units of this batch are in the table already (a batch is counted once)", fn); return DG_ERR_ARG; }
     { const int rc = gc_ready(c, fn); if (rc) return rc; }
     if (c->n_reads) {
         const GcBatch b{c->reads_out.p, c->reports.p, c->cigfinal.p, (unsigned long long)c->used[0], (unsigned long long)c->used[1], c->n_reads, n_pair_mode, min_mapq};
         const int rc = gc_count_device(c, b, fn);
         if (rc) return rc;
     }
-    c->gc_batch_counted = true;
+    c->gc.batch_counted = true;
     if (n_units) *n_units = (size_t)gc_units(c->n_reads, n_pair_mode);
     return DG_OK;
 }
@@ -3464,11 +3273,11 @@ extern "C" int dg_gene_count_records(dg_ctx *c, int n_reads, int n_pair_mode, ui
     if (bad >= 0) { snprintf(c->err, 512, "%s: read %lld points outside the arrays (%zu reports, %zu CIGAR ops), or its best report is none of its own", fn, bad, n_reports, n_ops); return DG_ERR_ARG; }
     { const int rc = gc_ready(c, fn); if (rc) return rc; }
     if (!n_reads) return DG_OK;
-    HIPCHK(c->gc_in_reads.ensure((size_t)n_reads)); HIPCHK(c->gc_in_rep.ensure(n_reports + 1)); HIPCHK(c->gc_in_cig.ensure(n_ops + 1));
-    HIPCHK(hipMemcpyAsync(c->gc_in_reads.p, reads, (size_t)n_reads * sizeof(dg_read_out), hipMemcpyHostToDevice, c->stream));
-    if (n_reports) HIPCHK(hipMemcpyAsync(c->gc_in_rep.p, reports, n_reports * sizeof(dg_report_out), hipMemcpyHostToDevice, c->stream));
-    if (n_ops) HIPCHK(hipMemcpyAsync(c->gc_in_cig.p, cigar, n_ops * 4, hipMemcpyHostToDevice, c->stream));
-    const GcBatch b{c->gc_in_reads.p, c->gc_in_rep.p, c->gc_in_cig.p, (unsigned long long)n_reports, (unsigned long long)n_ops, n_reads, n_pair_mode, min_mapq};
+    HIPCHK(c->gc.in_reads.ensure((size_t)n_reads)); HIPCHK(c->gc.in_rep.ensure(n_reports + 1)); HIPCHK(c->gc.in_cig.ensure(n_ops + 1));
+    HIPCHK(hipMemcpyAsync(c->gc.in_reads.p, reads, (size_t)n_reads * sizeof(dg_read_out), hipMemcpyHostToDevice, c->stream));
+    if (n_reports) HIPCHK(hipMemcpyAsync(c->gc.in_rep.p, reports, n_reports * sizeof(dg_report_out), hipMemcpyHostToDevice, c->stream));
+    if (n_ops) HIPCHK(hipMemcpyAsync(c->gc.in_cig.p, cigar, n_ops * 4, hipMemcpyHostToDevice, c->stream));
+    const GcBatch b{c->gc.in_reads.p, c->gc.in_rep.p, c->gc.in_cig.p, (unsigned long long)n_reports, (unsigned long long)n_ops, n_reads, n_pair_mode, min_mapq};
     { const int rc = gc_count_device(c, b, fn); if (rc) return rc; }
     HIPCHK(wait_stream(c));                          // (the caller's arrays are free again, and the staging buffers may take the next call's)
     if (n_units) *n_units = (size_t)gc_units(n_reads, n_pair_mode);
@@ -3480,14 +3289,14 @@ extern "C" int dg_gene_add(dg_ctx *c, const uint64_t *counts, size_t n_rows)
     if (!c) return DG_ERR_ARG;
     const char *fn = "dg_gene_add";
     { const int rc = gc_ready(c, fn); if (rc) return rc; }
-    if (!counts || n_rows != c->gc_rows) { snprintf(c->err, 512, "%s: %zu rows, the table has %zu (4 + the annotation's genes)", fn, n_rows, c->gc_rows); return DG_ERR_ARG; }
+    if (!counts || n_rows != c->gc.rows) { snprintf(c->err, 512, "%s: %zu rows, the table has %zu (4 + the annotation's genes)", fn, n_rows, c->gc.rows); return DG_ERR_ARG; }
     const size_t n = n_rows * 3;
-    HIPCHK(c->gc_in.ensure(n));
-    HIPCHK(hipMemcpyAsync(c->gc_in.p, counts, n * 8, hipMemcpyHostToDevice, c->stream));
-    k_gc_add<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->gc_counts, c->gc_in.p, (unsigned long long)n);
+    HIPCHK(c->gc.in.ensure(n));
+    HIPCHK(hipMemcpyAsync(c->gc.in.p, counts, n * 8, hipMemcpyHostToDevice, c->stream));
+    k_gc_add<<<(unsigned)((n + 255) / 256), 256, 0, c->stream>>>(c->gc.counts, c->gc.in.p, (unsigned long long)n);
     HIPCHK(hipGetLastError());
     HIPCHK(wait_stream(c));
-    c->gc_nonempty = true;
+    c->gc.nonempty = true;
     return DG_OK;
 }
 
@@ -3497,21 +3306,21 @@ extern "C" int dg_gene_merge(dg_ctx *dst, dg_ctx *src)
     if (!dst || !src) return DG_ERR_ARG;
     const char *fn = "dg_gene_merge";
     if (dst == src || dst->device != src->device) { snprintf(c->err, 512, "%s: the two contexts must differ and be on one device", fn); return DG_ERR_ARG; }
-    if (!src->gc_counts || !src->gc_nonempty) return DG_OK;
+    if (!src->gc.counts || !src->gc.nonempty) return DG_OK;
     { const int rc = gc_ready(dst, fn); if (rc) return rc; }
-    if (dst->gc_gen != src->gc_gen || dst->gc_rows != src->gc_rows) {
-        snprintf(c->err, 512, "%s: the tables were counted under different annotation generations (%llu and %llu)", fn, (unsigned long long)dst->gc_gen, (unsigned long long)src->gc_gen);
+    if (dst->gc.gen != src->gc.gen || dst->gc.rows != src->gc.rows) {
+        snprintf(c->err, 512, "%s: the tables were counted under different annotation generations (%llu and %llu)", fn, (unsigned long long)dst->gc.gen, (unsigned long long)src->gc.gen);
         return DG_ERR_ARG;
     }
     // behind everything the source's stream holds; the source's table is emptied on the destination's stream, which the call waits for
-    HIPCHK(hipEventRecord(src->ev_gc[2], src->stream));
-    HIPCHK(hipStreamWaitEvent(dst->stream, src->ev_gc[2], 0));
-    const size_t n = dst->gc_rows * 3;
-    k_gc_add<<<(unsigned)((n + 255) / 256), 256, 0, dst->stream>>>(dst->gc_counts, src->gc_counts, (unsigned long long)n);
+    HIPCHK(hipEventRecord(src->gc.ev[2], src->stream));
+    HIPCHK(hipStreamWaitEvent(dst->stream, src->gc.ev[2], 0));
+    const size_t n = dst->gc.rows * 3;
+    k_gc_add<<<(unsigned)((n + 255) / 256), 256, 0, dst->stream>>>(dst->gc.counts, src->gc.counts, (unsigned long long)n);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemsetAsync(src->gc_counts, 0, n * 8, dst->stream));
+    HIPCHK(hipMemsetAsync(src->gc.counts, 0, n * 8, dst->stream));
     HIPCHK(wait_stream(dst));
-    dst->gc_nonempty = true; src->gc_nonempty = false;
+    dst->gc.nonempty = true; src->gc.nonempty = false;
     return DG_OK;
 }
 
@@ -3527,10 +3336,10 @@ extern "C" int dg_gene_download(dg_ctx *c, uint64_t *counts, size_t cap_rows)
 {
     if (!c) return DG_ERR_ARG;
     const char *fn = "dg_gene_download";
-    if (!c->gc_counts) { const int rc = gc_ready(c, fn); if (rc) return rc; }
-    if (!counts || cap_rows < c->gc_rows) { snprintf(c->err, 512, "%s: output capacity too small: %zu rows are needed", fn, c->gc_rows); return DG_ERR_CAPACITY; }
+    if (!c->gc.counts) { const int rc = gc_ready(c, fn); if (rc) return rc; }
+    if (!counts || cap_rows < c->gc.rows) { snprintf(c->err, 512, "%s: output capacity too small: %zu rows are needed", fn, c->gc.rows); return DG_ERR_CAPACITY; }
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(counts, c->gc_counts, c->gc_rows * 3 * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(counts, c->gc.counts, c->gc.rows * 3 * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
@@ -3538,8 +3347,8 @@ extern "C" int dg_gene_download(dg_ctx *c, uint64_t *counts, size_t cap_rows)
 extern "C" int dg_gene_device(dg_ctx *c, void **counts)
 {
     if (!c || !counts) return DG_ERR_ARG;
-    if (!c->gc_counts) { const int rc = gc_ready(c, "dg_gene_device"); if (rc) return rc; }
-    *counts = c->gc_counts;
+    if (!c->gc.counts) { const int rc = gc_ready(c, "dg_gene_device"); if (rc) return rc; }
+    *counts = c->gc.counts;
     return DG_OK;
 }
 
@@ -3547,25 +3356,15 @@ extern "C" int dg_gene_device_ms(dg_ctx *c, float *ms)
 {
     if (!c || !ms) return DG_ERR_ARG;
     *ms = 0.f;
-    if (!c->gc_timed) return DG_OK;
-    HIPCHK(hipEventSynchronize(c->ev_gc[1]));
-    HIPCHK(hipEventElapsedTime(ms, c->ev_gc[0], c->ev_gc[1]));
+    if (!c->gc.timed) return DG_OK;
+    HIPCHK(hipEventSynchronize(c->gc.ev[1]));
+    HIPCHK(hipEventElapsedTime(ms, c->gc.ev[0], c->gc.ev[1]));
     return DG_OK;
 }
 
 // ------------------------------------------------------------------------------------------
 // the coverage track of the sorted array (dg_coverage.h): built in HBM from the sorted records and their places, in buffers of its own
 // ------------------------------------------------------------------------------------------
-static int cv_state(dg_ctx *c)
-{
-    if (c->d_cv_stat) return DG_OK;
-    HIPCHK(hipMalloc((void **)&c->d_cv_stat, CV_ST_WORDS * 8));
-    HIPCHK(hipHostMalloc((void **)&c->h_cv_stat, CV_ST_WORDS * 8, hipHostMallocDefault));
-    memset(c->h_cv_stat, 0, CV_ST_WORDS * 8);
-    for (hipEvent_t &e : c->ev_cv) HIPCHK(hipEventCreate(&e));
-    return DG_OK;
-}
-
 extern "C" int dg_bam_coverage_granules(int out[2])
 {
     if (!out) return DG_ERR_ARG;
@@ -3581,45 +3380,42 @@ extern "C" int dg_bam_coverage_finish(dg_ctx *c, uint32_t flags, uint32_t exclud
     if (n_bytes) *n_bytes = 0;
     if (device_ms) *device_ms = 0.f;
     if (stats) for (int k = 0; k < 7; k++) stats[k] = 0;
-    c->cv_valid = false; c->cv_n_entries = 0; c->cv_bytes = 0; c->cv_passes = 0;
-    for (float &m : c->cv_ms) m = 0.f;
-    if (!c->bs_fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
+    c->cv.valid = false; c->cv.n_entries = 0; c->cv.bytes = 0; c->cv.passes = 0;
+    for (float &m : c->cv.ms) m = 0.f;
+    BsView sv;
+    { const int rc = bs_view(c, fn, sv); if (rc) return rc; }
     if (flags & ~(DG_COV_ENTRIES_ONLY | DG_COV_STRAND_PLUS | DG_COV_STRAND_MINUS)) { snprintf(c->err, 512, "%s: flags 0x%x hold a bit that is none of DG_COV_ENTRIES_ONLY, DG_COV_STRAND_PLUS, DG_COV_STRAND_MINUS", fn, flags); return DG_ERR_ARG; }
     const bool text = !(flags & DG_COV_ENTRIES_ONLY);
     IndexShared *sh = c->shared_ix;
     if (text && (!sh || !sh->chr_names_set)) { snprintf(c->err, 512, "%s: the chromosome names are missing (dg_set_chr_names), and DG_COV_ENTRIES_ONLY is not set", fn); return DG_ERR_ARG; }
-    { const int rc = bs_ready(c); if (rc) return rc; }
-    { const int rc = cv_state(c); if (rc) return rc; }
-    const size_t n = c->bs_fin_records, n_raw = c->bs_fin_bytes;
-    const int n_chr = c->ix.n_chr;
+    HIPCHK(c->cv.ready());
+    const size_t n = sv.n, n_raw = sv.n_raw;
+    const int n_chr = sv.n_chr;
     if (n_chr < 1) { snprintf(c->err, 512, "%s: %d chromosomes", fn, n_chr); return DG_ERR_ARG; }
-    if (!n) { c->cv_valid = true; return DG_OK; }
+    if (!n) { c->cv.valid = true; return DG_OK; }
     const CvFilter f{flags, exclude_flags, min_mapq};
     const uint32_t tiles = (uint32_t)((n + CV_THREADS - 1) / CV_THREADS);
-    BS_ENSURE(c->cv_blk_off, n, "the records' block offsets"); BS_ENSURE(c->cv_blk_tile, (size_t)tiles + 1, "the per-workgroup block counts");
-    BS_ENSURE(c->cv_part, (size_t)CV_PLANES * tiles, "the per-workgroup values");
-    const uint64_t *dst_off = c->bs_k[c->bs_fin_which ^ 1].p;
-    HIPCHK(hipMemsetAsync(c->d_cv_stat, 0, CV_ST_WORDS * 8, c->stream));
-    HIPCHK(hipEventRecord(c->ev_cv[0], c->stream));
-    k_cv_count<<<tiles, CV_THREADS, 0, c->stream>>>(c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, n_chr, f, c->cv_blk_off.p, c->cv_blk_tile.p, c->cv_part.p);
-    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv_blk_tile.p, tiles, c->d_cv_stat + CV_ST_BLOCKS, c->cv_part.p, 5, 2, c->d_cv_stat + CV_ST_COUNTED);
+    BS_ENSURE(c->cv.blk_off, n, "the records' block offsets"); BS_ENSURE(c->cv.blk_tile, (size_t)tiles + 1, "the per-workgroup block counts");
+    BS_ENSURE(c->cv.part, (size_t)CV_PLANES * tiles, "the per-workgroup values");
+    HIPCHK(hipMemsetAsync(c->cv.stat.d, 0, CV_ST_WORDS * 8, c->stream));
+    HIPCHK(hipEventRecord(c->cv.ev[0], c->stream));
+    k_cv_count<<<tiles, CV_THREADS, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, n_chr, f, c->cv.blk_off.p, c->cv.blk_tile.p, c->cv.part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv.blk_tile.p, tiles, c->cv.stat.d + CV_ST_BLOCKS, c->cv.part.p, 5, 2, c->cv.stat.d + CV_ST_COUNTED);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_cv[1], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_cv_stat, c->d_cv_stat, CV_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->cv.ev[1], c->stream));
+    HIPCHK(c->cv.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the first wait: how many events, which digits their keys differ in, and what was out of range
-    if (c->h_cv_stat[CV_ST_NBAD]) {
-        snprintf(c->err, 512, "%s: record %llu of the sorted array has a block that ends behind position 2^32 - 1: an entry cannot hold it; no track was built", fn, ~c->h_cv_stat[CV_ST_NBAD]);
+    if (c->cv.stat.h[CV_ST_NBAD]) {
+        snprintf(c->err, 512, "%s: record %llu of the sorted array has a block that ends behind position 2^32 - 1: an entry cannot hold it; no track was built", fn, ~c->cv.stat.h[CV_ST_NBAD]);
         return DG_ERR_RANGE;
     }
-    const unsigned long long n_blocks = c->h_cv_stat[CV_ST_BLOCKS], n_counted = c->h_cv_stat[CV_ST_COUNTED], aligned = c->h_cv_stat[CV_ST_ALIGNED];
+    const unsigned long long n_blocks = c->cv.stat.h[CV_ST_BLOCKS], n_counted = c->cv.stat.h[CV_ST_COUNTED], aligned = c->cv.stat.h[CV_ST_ALIGNED];
     if (2 * n_blocks >= 0xFFFFF000ull) { snprintf(c->err, 512, "%s: %llu events (two per block) are more than the sorter takes (2^32 - 1, less a tile)", fn, 2 * n_blocks); return DG_ERR_CAPACITY; }
-    float a = 0.f;
-    (void)hipEventElapsedTime(&a, c->ev_cv[0], c->ev_cv[1]);
-    c->cv_ms[0] = a;
+    c->cv.ms[0] = c->cv.ev.ms(0, 1);
     auto done = [&](size_t ne, size_t nb, unsigned long long n_bp, unsigned long long covered, unsigned long long deepest) {
         float total = 0.f;
-        for (float m : c->cv_ms) total += m;
-        c->cv_valid = true; c->cv_n_entries = ne; c->cv_bytes = nb;
+        for (float m : c->cv.ms) total += m;
+        c->cv.valid = true; c->cv.n_entries = ne; c->cv.bytes = nb;
         if (n_entries) *n_entries = ne;
         if (n_bytes) *n_bytes = nb;
         if (device_ms) *device_ms = total;
@@ -3628,86 +3424,82 @@ extern "C" int dg_bam_coverage_finish(dg_ctx *c, uint32_t flags, uint32_t exclud
     };
     if (!n_blocks) return done(0, 0, 0, 0, 0);
     const uint32_t n_ev = (uint32_t)(2 * n_blocks), etiles = (n_ev + CV_THREADS - 1) / CV_THREADS;
-    for (int k = 0; k < 2; k++) { BS_ENSURE(c->cv_k[k], (size_t)n_ev, "the events' keys"); BS_ENSURE(c->cv_v[k], (size_t)n_ev, "the events' deltas"); }
-    BS_ENSURE(c->cv_hist, rs_hist_words(n_ev), "the sorter's histograms"); BS_ENSURE(c->cv_sums, rs_sums_words(n_ev), "the sorter's sums");
-    BS_ENSURE(c->cv_incl, (size_t)n_ev, "the scanned deltas"); BS_ENSURE(c->cv_mark, (size_t)n_ev, "the events' marks");
-    BS_ENSURE(c->cv_dep_tile, (size_t)etiles + 1, "the per-workgroup depth sums"); BS_ENSURE(c->cv_tile_last, (size_t)etiles + 1, "the per-workgroup last tails");
-    BS_ENSURE(c->cv_tile_prev, (size_t)etiles + 1, "the per-workgroup previous tails"); BS_ENSURE(c->cv_cnt_tile, (size_t)etiles + 1, "the per-workgroup breakpoint counts");
-    BS_ENSURE(c->cv_part, (size_t)etiles, "the per-workgroup values");
-    const int bits = std::min(cv_key_bits(~c->h_cv_stat[CV_ST_NMIN], c->h_cv_stat[CV_ST_MAX]), cv_key_bits_max(n_chr));
+    for (int k = 0; k < 2; k++) { BS_ENSURE(c->cv.sort.k[k], (size_t)n_ev, "the events' keys"); BS_ENSURE(c->cv.sort.v[k], (size_t)n_ev, "the events' deltas"); }
+    BS_ENSURE_SORT(c->cv.sort, n_ev);
+    BS_ENSURE(c->cv.incl, (size_t)n_ev, "the scanned deltas"); BS_ENSURE(c->cv.mark, (size_t)n_ev, "the events' marks");
+    BS_ENSURE(c->cv.dep_tile, (size_t)etiles + 1, "the per-workgroup depth sums"); BS_ENSURE(c->cv.tile_last, (size_t)etiles + 1, "the per-workgroup last tails");
+    BS_ENSURE(c->cv.tile_prev, (size_t)etiles + 1, "the per-workgroup previous tails"); BS_ENSURE(c->cv.cnt_tile, (size_t)etiles + 1, "the per-workgroup breakpoint counts");
+    BS_ENSURE(c->cv.part, (size_t)etiles, "the per-workgroup values");
+    const int bits = std::min(cv_key_bits(~c->cv.stat.h[CV_ST_NMIN], c->cv.stat.h[CV_ST_MAX]), cv_key_bits_max(n_chr));
     int which = 0;
-    HIPCHK(hipEventRecord(c->ev_cv[2], c->stream));
-    k_cv_emit<<<tiles, CV_THREADS, 0, c->stream>>>(c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, n_chr, f, c->cv_blk_off.p, c->cv_blk_tile.p, n_blocks, c->cv_k[0].p, c->cv_v[0].p);
+    HIPCHK(hipEventRecord(c->cv.ev[2], c->stream));
+    k_cv_emit<<<tiles, CV_THREADS, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, n_chr, f, c->cv.blk_off.p, c->cv.blk_tile.p, n_blocks, c->cv.sort.k[0].p, c->cv.sort.v[0].p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_cv[3], c->stream));
+    HIPCHK(hipEventRecord(c->cv.ev[3], c->stream));
     {
-        uint64_t *const keys[2] = {c->cv_k[0].p, c->cv_k[1].p}; int64_t *const vals[2] = {c->cv_v[0].p, c->cv_v[1].p};
-        const int rc = rs_sort_passes(c, keys, vals, c->cv_hist.p, c->cv_sums.p, n_ev, bits, which);
+        const int rc = c->cv.sort.sort(c, n_ev, bits, which);
         if (rc) return rc;
-        c->cv_passes = (bits + 3) / 4;
+        c->cv.passes = (bits + 3) / 4;
     }
-    HIPCHK(hipEventRecord(c->ev_cv[4], c->stream));
-    const uint64_t *skey = c->cv_k[which].p;
-    k_cv_depth<<<etiles, CV_THREADS, 0, c->stream>>>(c->cv_v[which].p, n_ev, c->cv_incl.p, c->cv_dep_tile.p);
-    k_scan_top<<<1, 256, 0, c->stream>>>(c->cv_dep_tile.p, etiles, (uint32_t *)(c->d_cv_stat + CV_ST_DEPTH_END), nullptr, 0, nullptr, 0);
-    k_cv_tails<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv_incl.p, c->cv_dep_tile.p, n_ev, c->cv_tile_last.p);
-    k_cv_tails_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv_tile_last.p, etiles, c->cv_tile_prev.p);
-    k_cv_flag<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv_incl.p, c->cv_dep_tile.p, c->cv_tile_prev.p, n_ev, c->cv_mark.p, c->cv_cnt_tile.p, c->cv_part.p);
-    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv_cnt_tile.p, etiles, c->d_cv_stat + CV_ST_MARKS, c->cv_part.p, 1, 0, c->d_cv_stat + CV_ST_MAX_DEPTH);
+    HIPCHK(hipEventRecord(c->cv.ev[4], c->stream));
+    const uint64_t *skey = c->cv.sort.k[which].p;
+    k_cv_depth<<<etiles, CV_THREADS, 0, c->stream>>>(c->cv.sort.v[which].p, n_ev, c->cv.incl.p, c->cv.dep_tile.p);
+    k_scan_top<<<1, 256, 0, c->stream>>>(c->cv.dep_tile.p, etiles, (uint32_t *)(c->cv.stat.d + CV_ST_DEPTH_END), nullptr, 0, nullptr, 0);
+    k_cv_tails<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv.incl.p, c->cv.dep_tile.p, n_ev, c->cv.tile_last.p);
+    k_cv_tails_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv.tile_last.p, etiles, c->cv.tile_prev.p);
+    k_cv_flag<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv.incl.p, c->cv.dep_tile.p, c->cv.tile_prev.p, n_ev, c->cv.mark.p, c->cv.cnt_tile.p, c->cv.part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv.cnt_tile.p, etiles, c->cv.stat.d + CV_ST_MARKS, c->cv.part.p, 1, 0, c->cv.stat.d + CV_ST_MAX_DEPTH);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_cv[5], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_cv_stat, c->d_cv_stat, CV_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->cv.ev[5], c->stream));
+    HIPCHK(c->cv.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the second wait: how many breakpoints and entries
-    const size_t n_bp = (size_t)(uint32_t)c->h_cv_stat[CV_ST_MARKS], n_ent = (size_t)(c->h_cv_stat[CV_ST_MARKS] >> 32);
-    if ((uint32_t)c->h_cv_stat[CV_ST_DEPTH_END] != 0u || n_bp < 2 || n_ent < 1 || n_ent >= n_bp || n_bp > n_ev) {
-        snprintf(c->err, 512, "%s: %u events leave the depth %u behind the last, %zu breakpoints and %zu entries", fn, n_ev, (uint32_t)c->h_cv_stat[CV_ST_DEPTH_END], n_bp, n_ent);
+    const size_t n_bp = (size_t)(uint32_t)c->cv.stat.h[CV_ST_MARKS], n_ent = (size_t)(c->cv.stat.h[CV_ST_MARKS] >> 32);
+    if ((uint32_t)c->cv.stat.h[CV_ST_DEPTH_END] != 0u || n_bp < 2 || n_ent < 1 || n_ent >= n_bp || n_bp > n_ev) {
+        snprintf(c->err, 512, "%s: %u events leave the depth %u behind the last, %zu breakpoints and %zu entries", fn, n_ev, (uint32_t)c->cv.stat.h[CV_ST_DEPTH_END], n_bp, n_ent);
         return DG_ERR_INTERNAL;
     }
     const uint32_t ntiles = (uint32_t)((n_ent + CV_THREADS - 1) / CV_THREADS);
-    BS_ENSURE(c->cv_bp_key, n_bp, "the breakpoints' keys"); BS_ENSURE(c->cv_bp_depth, n_bp, "the breakpoints' depths"); BS_ENSURE(c->cv_ent_bp, n_ent, "the entries' breakpoints");
-    BS_ENSURE(c->cv_entries, n_ent, "the entries"); BS_ENSURE(c->cv_line_off, n_ent, "the lines' offsets"); BS_ENSURE(c->cv_line_tile, (size_t)ntiles + 1, "the per-workgroup line sums");
-    BS_ENSURE(c->cv_part, 2 * (size_t)ntiles, "the per-workgroup values");
+    BS_ENSURE(c->cv.bp_key, n_bp, "the breakpoints' keys"); BS_ENSURE(c->cv.bp_depth, n_bp, "the breakpoints' depths"); BS_ENSURE(c->cv.ent_bp, n_ent, "the entries' breakpoints");
+    BS_ENSURE(c->cv.entries, n_ent, "the entries"); BS_ENSURE(c->cv.line_off, n_ent, "the lines' offsets"); BS_ENSURE(c->cv.line_tile, (size_t)ntiles + 1, "the per-workgroup line sums");
+    BS_ENSURE(c->cv.part, 2 * (size_t)ntiles, "the per-workgroup values");
     {   // the chromosome names are read and the kernels that use them enqueued under the index's lock (as the SAM formatter does: dg_set_chr_names waits for the device before it frees them)
         std::unique_lock<std::mutex> lk;
         const uint32_t *name_off = nullptr; const char *names = nullptr;
         if (text) {
             lk = std::unique_lock<std::mutex>(sh->mu);
             name_off = sh->d_chr_name_off; names = sh->d_chr_names;
-            BS_ENSURE(c->cv_text, (size_t)(n_ent * cv_line_bound(sh->chr_name_max)), "the text");
+            BS_ENSURE(c->cv.text, (size_t)(n_ent * cv_line_bound(sh->chr_name_max)), "the text");
         }
-        HIPCHK(hipEventRecord(c->ev_cv[6], c->stream));
-        k_cv_compact<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv_incl.p, c->cv_dep_tile.p, c->cv_mark.p, c->cv_cnt_tile.p, n_ev, (uint32_t)n_bp, (uint32_t)n_ent, c->cv_bp_key.p, c->cv_bp_depth.p, c->cv_ent_bp.p);
-        HIPCHK(hipEventRecord(c->ev_cv[7], c->stream));
-        k_cv_entries<<<ntiles, CV_THREADS, 0, c->stream>>>(c->cv_bp_key.p, c->cv_bp_depth.p, c->cv_ent_bp.p, (uint32_t)n_bp, (uint32_t)n_ent, n_chr, name_off, c->cv_entries.p, c->cv_line_off.p, c->cv_line_tile.p, c->cv_part.p);
-        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv_line_tile.p, ntiles, c->d_cv_stat + CV_ST_BYTES, c->cv_part.p, 2, 2, c->d_cv_stat + CV_ST_COVERED);
+        HIPCHK(hipEventRecord(c->cv.ev[6], c->stream));
+        k_cv_compact<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv.incl.p, c->cv.dep_tile.p, c->cv.mark.p, c->cv.cnt_tile.p, n_ev, (uint32_t)n_bp, (uint32_t)n_ent, c->cv.bp_key.p, c->cv.bp_depth.p, c->cv.ent_bp.p);
+        HIPCHK(hipEventRecord(c->cv.ev[7], c->stream));
+        k_cv_entries<<<ntiles, CV_THREADS, 0, c->stream>>>(c->cv.bp_key.p, c->cv.bp_depth.p, c->cv.ent_bp.p, (uint32_t)n_bp, (uint32_t)n_ent, n_chr, name_off, c->cv.entries.p, c->cv.line_off.p, c->cv.line_tile.p, c->cv.part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv.line_tile.p, ntiles, c->cv.stat.d + CV_ST_BYTES, c->cv.part.p, 2, 2, c->cv.stat.d + CV_ST_COVERED);
         if (text)
-            k_cv_write<<<ntiles, CV_THREADS, 0, c->stream>>>(c->cv_entries.p, (uint32_t)n_ent, n_chr, name_off, names, c->cv_line_off.p, c->cv_line_tile.p, c->d_cv_stat, (unsigned long long)c->cv_text.cap, c->cv_text.p);
+            k_cv_write<<<ntiles, CV_THREADS, 0, c->stream>>>(c->cv.entries.p, (uint32_t)n_ent, n_chr, name_off, names, c->cv.line_off.p, c->cv.line_tile.p, c->cv.stat.d, (unsigned long long)c->cv.text.cap, c->cv.text.p);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->ev_cv[8], c->stream));
+        HIPCHK(hipEventRecord(c->cv.ev[8], c->stream));
     }
-    HIPCHK(hipMemcpyAsync(c->h_cv_stat, c->d_cv_stat, CV_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c->cv.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the third wait: the text's size, the covered bases
-    const size_t bytes = text ? (size_t)c->h_cv_stat[CV_ST_BYTES] : 0;
-    if (bytes > c->cv_text.cap) { snprintf(c->err, 512, "%s: the text needs %zu bytes, the bound was %zu", fn, bytes, c->cv_text.cap); return DG_ERR_INTERNAL; }
-    if (c->h_cv_stat[CV_ST_AREA] != aligned) { snprintf(c->err, 512, "%s: the entries hold %llu aligned bases, the blocks %llu", fn, c->h_cv_stat[CV_ST_AREA], aligned); return DG_ERR_INTERNAL; }
-    float e = 0.f, s = 0.f, d1 = 0.f, d2 = 0.f, w = 0.f;
-    (void)hipEventElapsedTime(&e, c->ev_cv[2], c->ev_cv[3]); (void)hipEventElapsedTime(&s, c->ev_cv[3], c->ev_cv[4]); (void)hipEventElapsedTime(&d1, c->ev_cv[4], c->ev_cv[5]);
-    (void)hipEventElapsedTime(&d2, c->ev_cv[6], c->ev_cv[7]); (void)hipEventElapsedTime(&w, c->ev_cv[7], c->ev_cv[8]);
-    c->cv_ms[1] = e; c->cv_ms[2] = s; c->cv_ms[3] = d1 + d2; c->cv_ms[4] = w;
-    return done(n_ent, bytes, n_bp, c->h_cv_stat[CV_ST_COVERED], c->h_cv_stat[CV_ST_MAX_DEPTH]);
+    const size_t bytes = text ? (size_t)c->cv.stat.h[CV_ST_BYTES] : 0;
+    if (bytes > c->cv.text.cap) { snprintf(c->err, 512, "%s: the text needs %zu bytes, the bound was %zu", fn, bytes, c->cv.text.cap); return DG_ERR_INTERNAL; }
+    if (c->cv.stat.h[CV_ST_AREA] != aligned) { snprintf(c->err, 512, "%s: the entries hold %llu aligned bases, the blocks %llu", fn, c->cv.stat.h[CV_ST_AREA], aligned); return DG_ERR_INTERNAL; }
+    c->cv.ms[1] = c->cv.ev.ms(2, 3); c->cv.ms[2] = c->cv.ev.ms(3, 4); c->cv.ms[3] = c->cv.ev.ms(4, 5) + c->cv.ev.ms(6, 7); c->cv.ms[4] = c->cv.ev.ms(7, 8);
+    return done(n_ent, bytes, n_bp, c->cv.stat.h[CV_ST_COVERED], c->cv.stat.h[CV_ST_MAX_DEPTH]);
 }
 
 extern "C" int dg_bam_coverage_download(dg_ctx *c, dg_cov_entry *entries, size_t cap_entries, char *text, size_t cap_text)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->cv_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_coverage_download: no track (dg_bam_coverage_finish first, and no store call behind it)"); return DG_ERR_ARG; }
-    if ((entries && cap_entries < c->cv_n_entries) || (text && cap_text < c->cv_bytes)) {
-        snprintf(c->err, 512, "dg_bam_coverage_download: output capacity too small: %zu entries and %zu bytes of text are needed", c->cv_n_entries, c->cv_bytes);
+    if (!c->cv.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_coverage_download: no track (dg_bam_coverage_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if ((entries && cap_entries < c->cv.n_entries) || (text && cap_text < c->cv.bytes)) {
+        snprintf(c->err, 512, "dg_bam_coverage_download: output capacity too small: %zu entries and %zu bytes of text are needed", c->cv.n_entries, c->cv.bytes);
         return DG_ERR_CAPACITY;
     }
     HIPCHK(hipSetDevice(c->device));
-    if (entries && c->cv_n_entries) HIPCHK(hipMemcpyAsync(entries, c->cv_entries.p, c->cv_n_entries * sizeof(dg_cov_entry), hipMemcpyDeviceToHost, c->stream));
-    if (text && c->cv_bytes) HIPCHK(hipMemcpyAsync(text, c->cv_text.p, c->cv_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (entries && c->cv.n_entries) HIPCHK(hipMemcpyAsync(entries, c->cv.entries.p, c->cv.n_entries * sizeof(dg_cov_entry), hipMemcpyDeviceToHost, c->stream));
+    if (text && c->cv.bytes) HIPCHK(hipMemcpyAsync(text, c->cv.text.p, c->cv.bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
@@ -3715,33 +3507,23 @@ extern "C" int dg_bam_coverage_download(dg_ctx *c, dg_cov_entry *entries, size_t
 extern "C" int dg_bam_coverage_device(dg_ctx *c, void **entries, void **text)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->cv_valid || !c->bs_fin_valid) { snprintf(c->err, 512, "dg_bam_coverage_device: no track (dg_bam_coverage_finish first, and no store call behind it)"); return DG_ERR_ARG; }
-    if (entries) *entries = c->cv_n_entries ? c->cv_entries.p : nullptr;
-    if (text) *text = c->cv_bytes ? c->cv_text.p : nullptr;
+    if (!c->cv.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_coverage_device: no track (dg_bam_coverage_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if (entries) *entries = c->cv.n_entries ? c->cv.entries.p : nullptr;
+    if (text) *text = c->cv.bytes ? c->cv.text.p : nullptr;
     return DG_OK;
 }
 
 extern "C" int dg_bam_coverage_device_ms(dg_ctx *c, float ms[5], int *n_passes)
 {
     if (!c || !ms) return DG_ERR_ARG;
-    for (int k = 0; k < 5; k++) ms[k] = c->cv_ms[k];
-    if (n_passes) *n_passes = c->cv_passes;
+    for (int k = 0; k < 5; k++) ms[k] = c->cv.ms[k];
+    if (n_passes) *n_passes = c->cv.passes;
     return DG_OK;
 }
 
 // ------------------------------------------------------------------------------------------
 // duplicate marking of the sorted array (dg_markdup.h): flag 0x400 written in place, in HBM, before dg_bam_sort_compress
 // ------------------------------------------------------------------------------------------
-static int md_state(dg_ctx *c)
-{
-    if (c->d_md_stat) return DG_OK;
-    HIPCHK(hipMalloc((void **)&c->d_md_stat, MD_ST_WORDS * 8));
-    HIPCHK(hipHostMalloc((void **)&c->h_md_stat, MD_ST_WORDS * 8, hipHostMallocDefault));
-    memset(c->h_md_stat, 0, MD_ST_WORDS * 8);
-    for (hipEvent_t &e : c->ev_md) HIPCHK(hipEventCreate(&e));
-    return DG_OK;
-}
-
 extern "C" int dg_bam_markdup_granules(int out[3])
 {
     if (!out) return DG_ERR_ARG;
@@ -3755,120 +3537,118 @@ extern "C" int dg_bam_markdup_finish(dg_ctx *c, uint32_t flags, uint64_t stats[8
     const char *fn = "dg_bam_markdup_finish";
     if (device_ms) *device_ms = 0.f;
     if (stats) for (int k = 0; k < 8; k++) stats[k] = 0;
-    c->md_passes = 0;
-    for (float &m : c->md_ms) m = 0.f;
-    if (!c->bs_fin_valid) { snprintf(c->err, 512, "%s: no sorted array (dg_bam_sort_finish first, and no store call behind it)", fn); return DG_ERR_ARG; }
+    c->md.passes = 0;
+    for (float &m : c->md.ms) m = 0.f;
+    BsView sv;
+    { const int rc = bs_view(c, fn, sv); if (rc) return rc; }
     if (flags & ~DG_MD_COUNT_ONLY) { snprintf(c->err, 512, "%s: flags 0x%x hold a bit that is not DG_MD_COUNT_ONLY", fn, flags); return DG_ERR_ARG; }
     const int write = (flags & DG_MD_COUNT_ONLY) ? 0 : 1;
-    { const int rc = bs_ready(c); if (rc) return rc; }
-    { const int rc = md_state(c); if (rc) return rc; }
-    const size_t n = c->bs_fin_records, n_raw = c->bs_fin_bytes;
-    const int n_chr = c->ix.n_chr, hash_bits = c->env_markdup_hash_bits;
+    HIPCHK(c->md.ready());
+    const size_t n = sv.n, n_raw = sv.n_raw;
+    const int n_chr = sv.n_chr, hash_bits = c->md.hash_bits;
     if (n_chr < 1) { snprintf(c->err, 512, "%s: %d chromosomes", fn, n_chr); return DG_ERR_ARG; }
     if (!n) return DG_OK;
     const uint32_t tiles = (uint32_t)((n + MD_THREADS - 1) / MD_THREADS);
-    BS_ENSURE(c->md_E, n, "the records' end keys"); BS_ENSURE(c->md_h, n, "the names' hashes"); BS_ENSURE(c->md_score, n, "the records' scores"); BS_ENSURE(c->md_mate, n, "the records' partners");
-    BS_ENSURE(c->md_cand_off, n, "the candidates' offsets"); BS_ENSURE(c->md_cnt_off, n, "the pairs' and ends' offsets");
-    BS_ENSURE(c->md_tile, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(c->md_junk, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(c->md_part, 2 * (size_t)tiles, "the per-workgroup values");
-    BS_ENSURE(c->md_tile_last, (size_t)tiles + 1, "the per-workgroup last heads"); BS_ENSURE(c->md_tile_prev, (size_t)tiles + 2, "the per-workgroup previous heads");
-    const uint64_t *dst_off = c->bs_k[c->bs_fin_which ^ 1].p;
-    HIPCHK(hipMemsetAsync(c->d_md_stat, 0, MD_ST_WORDS * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->md_junk.p, 0, ((size_t)tiles + 1) * 8, c->stream));
-    HIPCHK(hipEventRecord(c->ev_md[0], c->stream));
-    k_md_rec<<<tiles, MD_THREADS, 0, c->stream>>>(c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, n_chr, hash_bits, c->md_E.p, c->md_h.p, c->md_score.p, c->md_mate.p,
-                                                  c->md_cand_off.p, c->md_tile.p, c->md_part.p);
-    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_tile.p, tiles, c->d_md_stat + MD_ST_CAND, c->md_part.p, 2, 1, c->d_md_stat + MD_ST_EXAMINED);
+    BS_ENSURE(c->md.E, n, "the records' end keys"); BS_ENSURE(c->md.h, n, "the names' hashes"); BS_ENSURE(c->md.score, n, "the records' scores"); BS_ENSURE(c->md.mate, n, "the records' partners");
+    BS_ENSURE(c->md.cand_off, n, "the candidates' offsets"); BS_ENSURE(c->md.cnt_off, n, "the pairs' and ends' offsets");
+    BS_ENSURE(c->md.tile, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(c->md.junk, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(c->md.part, 2 * (size_t)tiles, "the per-workgroup values");
+    BS_ENSURE(c->md.tile_last, (size_t)tiles + 1, "the per-workgroup last heads"); BS_ENSURE(c->md.tile_prev, (size_t)tiles + 2, "the per-workgroup previous heads");
+    HIPCHK(hipMemsetAsync(c->md.stat.d, 0, MD_ST_WORDS * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->md.junk.p, 0, ((size_t)tiles + 1) * 8, c->stream));
+    HIPCHK(hipEventRecord(c->md.ev[0], c->stream));
+    k_md_rec<<<tiles, MD_THREADS, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, n_chr, hash_bits, c->md.E.p, c->md.h.p, c->md.score.p, c->md.mate.p,
+                                                  c->md.cand_off.p, c->md.tile.p, c->md.part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.tile.p, tiles, c->md.stat.d + MD_ST_CAND, c->md.part.p, 2, 1, c->md.stat.d + MD_ST_EXAMINED);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_md[1], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_md_stat, c->d_md_stat, MD_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->md.ev[1], c->stream));
+    HIPCHK(c->md.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the first wait: how many candidates, and what was out of range
-    if (c->h_md_stat[MD_ST_NBAD]) {
-        snprintf(c->err, 512, "%s: record %llu of the sorted array has an unclipped 5' end outside [-2^31, 3 * 2^31): an end key cannot hold it; nothing was written", fn, ~c->h_md_stat[MD_ST_NBAD]);
+    if (c->md.stat.h[MD_ST_NBAD]) {
+        snprintf(c->err, 512, "%s: record %llu of the sorted array has an unclipped 5' end outside [-2^31, 3 * 2^31): an end key cannot hold it; nothing was written", fn, ~c->md.stat.h[MD_ST_NBAD]);
         return DG_ERR_RANGE;
     }
-    const size_t n_cand = (size_t)c->h_md_stat[MD_ST_CAND], n_examined = (size_t)c->h_md_stat[MD_ST_EXAMINED];
+    const size_t n_cand = (size_t)c->md.stat.h[MD_ST_CAND], n_examined = (size_t)c->md.stat.h[MD_ST_EXAMINED];
     if (n_cand > n || n_examined > n) { snprintf(c->err, 512, "%s: %zu candidates and %zu examined records of %zu", fn, n_cand, n_examined, n); return DG_ERR_INTERNAL; }
     const uint32_t ctiles = (uint32_t)((n_cand + MD_THREADS - 1) / MD_THREADS);
+    SortBufs &ps = c->md.sort, &es = c->md.esort;          // candidates, then pairs / ends
     int which = 0;
     if (n_cand) {
-        for (int k = 0; k < 2; k++) { BS_ENSURE(c->md_k[k], n_cand, "the sorter's keys"); BS_ENSURE(c->md_v[k], n_cand, "the sorter's values"); }
-        BS_ENSURE(c->md_hist, rs_hist_words((uint32_t)n), "the sorter's histograms"); BS_ENSURE(c->md_sums, rs_sums_words((uint32_t)n), "the sorter's sums");
+        for (int k = 0; k < 2; k++) { BS_ENSURE(ps.k[k], n_cand, "the sorter's keys"); BS_ENSURE(ps.v[k], n_cand, "the sorter's values"); }
+        BS_ENSURE_SORT(ps, (uint32_t)n_cand);
     }
-    uint64_t *const keys[2] = {c->md_k[0].p, c->md_k[1].p}; int64_t *const vals[2] = {c->md_v[0].p, c->md_v[1].p};
-    HIPCHK(hipEventRecord(c->ev_md[2], c->stream));
+    HIPCHK(hipEventRecord(c->md.ev[2], c->stream));
     if (n_cand) {
-        k_md_compact<<<tiles, MD_THREADS, 0, c->stream>>>(c->md_cand_off.p, c->md_tile.p, c->md_h.p, (uint32_t)n, (uint32_t)n_cand, keys[0], vals[0]);
-        { const int rc = rs_sort_passes(c, keys, vals, c->md_hist.p, c->md_sums.p, (uint32_t)n_cand, hash_bits, which); if (rc) return rc; }
-        c->md_passes += (hash_bits + 3) / 4;
-        k_md_mate<<<ctiles, MD_THREADS, 0, c->stream>>>(keys[which], vals[which], (uint32_t)n_cand, (uint32_t)n, c->bs_sorted.p, dst_off, c->bs_tile.p, c->md_mate.p, c->md_part.p);
-        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_junk.p, ctiles, c->d_md_stat + MD_ST_JUNK, c->md_part.p, 1, 1, c->d_md_stat + MD_ST_CROWDED);
+        k_md_compact<<<tiles, MD_THREADS, 0, c->stream>>>(c->md.cand_off.p, c->md.tile.p, c->md.h.p, (uint32_t)n, (uint32_t)n_cand, ps.k[0].p, ps.v[0].p);
+        { const int rc = ps.sort(c, (uint32_t)n_cand, hash_bits, which); if (rc) return rc; }
+        c->md.passes += (hash_bits + 3) / 4;
+        k_md_mate<<<ctiles, MD_THREADS, 0, c->stream>>>(ps.k[which].p, ps.v[which].p, (uint32_t)n_cand, (uint32_t)n, sv.rec, sv.dst_off, sv.tile, c->md.mate.p, c->md.part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.junk.p, ctiles, c->md.stat.d + MD_ST_JUNK, c->md.part.p, 1, 1, c->md.stat.d + MD_ST_CROWDED);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(c->ev_md[3], c->stream));
-    k_md_count<<<tiles, MD_THREADS, 0, c->stream>>>(c->md_mate.p, (uint32_t)n, c->md_cnt_off.p, c->md_tile.p);
-    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_tile.p, tiles, c->d_md_stat + MD_ST_COUNTS, nullptr, 0, 0, nullptr);
+    HIPCHK(hipEventRecord(c->md.ev[3], c->stream));
+    k_md_count<<<tiles, MD_THREADS, 0, c->stream>>>(c->md.mate.p, (uint32_t)n, c->md.cnt_off.p, c->md.tile.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.tile.p, tiles, c->md.stat.d + MD_ST_COUNTS, nullptr, 0, 0, nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_md[4], c->stream));
-    HIPCHK(hipMemcpyAsync(c->h_md_stat, c->d_md_stat, MD_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipEventRecord(c->md.ev[4], c->stream));
+    HIPCHK(c->md.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the second wait: how many pairs and ends
-    const size_t n_pairs = (size_t)(c->h_md_stat[MD_ST_COUNTS] >> 32), n_ends = (size_t)(uint32_t)c->h_md_stat[MD_ST_COUNTS], n_crowded = (size_t)c->h_md_stat[MD_ST_CROWDED];
+    const size_t n_pairs = (size_t)(c->md.stat.h[MD_ST_COUNTS] >> 32), n_ends = (size_t)(uint32_t)c->md.stat.h[MD_ST_COUNTS], n_crowded = (size_t)c->md.stat.h[MD_ST_CROWDED];
     if (2 * n_pairs > n_cand || n_ends != n_examined) { snprintf(c->err, 512, "%s: %zu pairs of %zu candidates, %zu ends of %zu examined records", fn, n_pairs, n_cand, n_ends, n_examined); return DG_ERR_INTERNAL; }
     const uint32_t ptiles = (uint32_t)((n_pairs + MD_THREADS - 1) / MD_THREADS), etiles = (uint32_t)((n_ends + MD_THREADS - 1) / MD_THREADS);
     if (n_ends) {
-        for (int k = 0; k < 2; k++) { BS_ENSURE(c->md_ek[k], n_ends, "the ends' keys"); BS_ENSURE(c->md_ev[k], n_ends, "the ends' values"); }
-        BS_ENSURE(c->md_hist, rs_hist_words((uint32_t)n), "the sorter's histograms"); BS_ENSURE(c->md_sums, rs_sums_words((uint32_t)n), "the sorter's sums");
+        for (int k = 0; k < 2; k++) { BS_ENSURE(es.k[k], n_ends, "the ends' keys"); BS_ENSURE(es.v[k], n_ends, "the ends' values"); }
+        BS_ENSURE_SORT(es, (uint32_t)n_ends);
     }
-    uint64_t *const ekeys[2] = {c->md_ek[0].p, c->md_ek[1].p}; int64_t *const evals[2] = {c->md_ev[0].p, c->md_ev[1].p};
     const int e_bits = md_e_bits(n_chr);
     int pw = 0, ew = 0;
-    HIPCHK(hipEventRecord(c->ev_md[5], c->stream));
-    if (n_ends) k_md_emit<<<tiles, MD_THREADS, 0, c->stream>>>(c->md_mate.p, c->md_score.p, c->md_cnt_off.p, c->md_tile.p, (uint32_t)n, (uint32_t)n_pairs, (uint32_t)n_ends, keys[0], vals[0], ekeys[0], evals[0]);
+    HIPCHK(hipEventRecord(c->md.ev[5], c->stream));
+    if (n_ends) k_md_emit<<<tiles, MD_THREADS, 0, c->stream>>>(c->md.mate.p, c->md.score.p, c->md.cnt_off.p, c->md.tile.p, (uint32_t)n, (uint32_t)n_pairs, (uint32_t)n_ends, ps.k[0].p, ps.v[0].p, es.k[0].p, es.v[0].p);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_md[6], c->stream));
+    HIPCHK(hipEventRecord(c->md.ev[6], c->stream));
     if (n_pairs) {
-        { const int rc = rs_sort_passes(c, keys, vals, c->md_hist.p, c->md_sums.p, (uint32_t)n_pairs, MD_SCORE_BITS, pw); if (rc) return rc; }
-        k_md_rekey<<<ptiles, MD_THREADS, 0, c->stream>>>(keys[pw], vals[pw], (uint32_t)n_pairs, 0, c->md_E.p, c->md_mate.p, (uint32_t)n);
-        { const int rc = rs_sort_passes(c, keys, vals, c->md_hist.p, c->md_sums.p, (uint32_t)n_pairs, e_bits, pw); if (rc) return rc; }
-        k_md_rekey<<<ptiles, MD_THREADS, 0, c->stream>>>(keys[pw], vals[pw], (uint32_t)n_pairs, 1, c->md_E.p, c->md_mate.p, (uint32_t)n);
-        { const int rc = rs_sort_passes(c, keys, vals, c->md_hist.p, c->md_sums.p, (uint32_t)n_pairs, e_bits, pw); if (rc) return rc; }
-        c->md_passes += (MD_SCORE_BITS + 3) / 4 + 2 * ((e_bits + 3) / 4);
+        { const int rc = ps.sort(c, (uint32_t)n_pairs, MD_SCORE_BITS, pw); if (rc) return rc; }
+        k_md_rekey<<<ptiles, MD_THREADS, 0, c->stream>>>(ps.k[pw].p, ps.v[pw].p, (uint32_t)n_pairs, 0, c->md.E.p, c->md.mate.p, (uint32_t)n);
+        { const int rc = ps.sort(c, (uint32_t)n_pairs, e_bits, pw); if (rc) return rc; }
+        k_md_rekey<<<ptiles, MD_THREADS, 0, c->stream>>>(ps.k[pw].p, ps.v[pw].p, (uint32_t)n_pairs, 1, c->md.E.p, c->md.mate.p, (uint32_t)n);
+        { const int rc = ps.sort(c, (uint32_t)n_pairs, e_bits, pw); if (rc) return rc; }
+        c->md.passes += (MD_SCORE_BITS + 3) / 4 + 2 * ((e_bits + 3) / 4);
     }
-    HIPCHK(hipEventRecord(c->ev_md[7], c->stream));
+    HIPCHK(hipEventRecord(c->md.ev[7], c->stream));
     if (n_ends) {
-        { const int rc = rs_sort_passes(c, ekeys, evals, c->md_hist.p, c->md_sums.p, (uint32_t)n_ends, MD_SCORE_BITS, ew); if (rc) return rc; }
-        k_md_rekey<<<etiles, MD_THREADS, 0, c->stream>>>(ekeys[ew], evals[ew], (uint32_t)n_ends, 2, c->md_E.p, c->md_mate.p, (uint32_t)n);
-        { const int rc = rs_sort_passes(c, ekeys, evals, c->md_hist.p, c->md_sums.p, (uint32_t)n_ends, e_bits, ew); if (rc) return rc; }
-        c->md_passes += (MD_SCORE_BITS + 3) / 4 + (e_bits + 3) / 4;
+        { const int rc = es.sort(c, (uint32_t)n_ends, MD_SCORE_BITS, ew); if (rc) return rc; }
+        k_md_rekey<<<etiles, MD_THREADS, 0, c->stream>>>(es.k[ew].p, es.v[ew].p, (uint32_t)n_ends, 2, c->md.E.p, c->md.mate.p, (uint32_t)n);
+        { const int rc = es.sort(c, (uint32_t)n_ends, e_bits, ew); if (rc) return rc; }
+        c->md.passes += (MD_SCORE_BITS + 3) / 4 + (e_bits + 3) / 4;
     }
-    HIPCHK(hipEventRecord(c->ev_md[8], c->stream));
+    HIPCHK(hipEventRecord(c->md.ev[8], c->stream));
     if (n_pairs) {
-        k_md_heads<<<ptiles, MD_THREADS, 0, c->stream>>>(keys[pw], vals[pw], (uint32_t)n_pairs, c->md_E.p, c->md_mate.p, c->md_tile_last.p);
-        k_cv_tails_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_tile_last.p, ptiles, c->md_tile_prev.p);
-        k_md_flag_pairs<<<ptiles, MD_THREADS, 0, c->stream>>>(keys[pw], vals[pw], (uint32_t)n_pairs, c->md_E.p, c->md_mate.p, c->md_tile_prev.p, c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n,
-                                                               (unsigned long long)n_raw, write, c->md_part.p);
-        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_junk.p, ptiles, c->d_md_stat + MD_ST_JUNK, c->md_part.p, 2, 1, c->d_md_stat + MD_ST_DUP_PAIRS);
+        k_md_heads<<<ptiles, MD_THREADS, 0, c->stream>>>(ps.k[pw].p, ps.v[pw].p, (uint32_t)n_pairs, c->md.E.p, c->md.mate.p, c->md.tile_last.p);
+        k_cv_tails_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.tile_last.p, ptiles, c->md.tile_prev.p);
+        k_md_flag_pairs<<<ptiles, MD_THREADS, 0, c->stream>>>(ps.k[pw].p, ps.v[pw].p, (uint32_t)n_pairs, c->md.E.p, c->md.mate.p, c->md.tile_prev.p, sv.rec, sv.dst_off, sv.tile, (uint32_t)n,
+                                                               (unsigned long long)n_raw, write, c->md.part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.junk.p, ptiles, c->md.stat.d + MD_ST_JUNK, c->md.part.p, 2, 1, c->md.stat.d + MD_ST_DUP_PAIRS);
     }
     if (n_ends) {
-        k_md_flag_ends<<<etiles, MD_THREADS, 0, c->stream>>>(ekeys[ew], evals[ew], (uint32_t)n_ends, c->bs_sorted.p, dst_off, c->bs_tile.p, (uint32_t)n, (unsigned long long)n_raw, write, c->md_part.p);
-        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md_junk.p, etiles, c->d_md_stat + MD_ST_JUNK, c->md_part.p, 1, 1, c->d_md_stat + MD_ST_DUP_FRAGS);
+        k_md_flag_ends<<<etiles, MD_THREADS, 0, c->stream>>>(es.k[ew].p, es.v[ew].p, (uint32_t)n_ends, sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, write, c->md.part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.junk.p, etiles, c->md.stat.d + MD_ST_JUNK, c->md.part.p, 1, 1, c->md.stat.d + MD_ST_DUP_FRAGS);
     }
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(c->ev_md[9], c->stream));
+    HIPCHK(hipEventRecord(c->md.ev[9], c->stream));
     if (write && n_ends) {                                        // bytes of the array changed: as behind dg_bam_sort_finish, no block of it has been compressed, and no track covers it
-        c->bi_valid = false; c->bi_covered.clear(); c->cv_valid = false;
+        bs_array_changed(c);
     }
-    HIPCHK(hipMemcpyAsync(c->h_md_stat, c->d_md_stat, MD_ST_WORDS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c->md.stat.fetch(c->stream));
     HIPCHK(wait_stream(c));                                       // the third wait: the counts
     float t[9];
-    for (int k = 0; k < 9; k++) { t[k] = 0.f; (void)hipEventElapsedTime(&t[k], c->ev_md[k], c->ev_md[k + 1]); }
-    c->md_ms[0] = t[0]; c->md_ms[1] = t[2]; c->md_ms[2] = t[6]; c->md_ms[3] = t[7]; c->md_ms[4] = t[8]; c->md_ms[5] = t[3] + t[5];
+    for (int k = 0; k < 9; k++) t[k] = c->md.ev.ms(k, k + 1);
+    c->md.ms[0] = t[0]; c->md.ms[1] = t[2]; c->md.ms[2] = t[6]; c->md.ms[3] = t[7]; c->md.ms[4] = t[8]; c->md.ms[5] = t[3] + t[5];
     float total = 0.f;
-    for (float m : c->md_ms) total += m;
+    for (float m : c->md.ms) total += m;
     if (device_ms) *device_ms = total;
-    const uint64_t dup_pairs = c->h_md_stat[MD_ST_DUP_PAIRS], dup_frags = c->h_md_stat[MD_ST_DUP_FRAGS];
+    const uint64_t dup_pairs = c->md.stat.h[MD_ST_DUP_PAIRS], dup_frags = c->md.stat.h[MD_ST_DUP_FRAGS];
     if (stats) {
         stats[0] = n_examined; stats[1] = n_pairs; stats[2] = n_examined - 2 * n_pairs; stats[3] = dup_pairs; stats[4] = dup_frags; stats[5] = n_crowded;
-        stats[6] = 2 * dup_pairs + dup_frags; stats[7] = c->h_md_stat[MD_ST_FAMILY];
+        stats[6] = 2 * dup_pairs + dup_frags; stats[7] = c->md.stat.h[MD_ST_FAMILY];
     }
     return DG_OK;
 }
@@ -3876,8 +3656,8 @@ extern "C" int dg_bam_markdup_finish(dg_ctx *c, uint32_t flags, uint64_t stats[8
 extern "C" int dg_bam_markdup_device_ms(dg_ctx *c, float ms[6], int *n_passes)
 {
     if (!c || !ms) return DG_ERR_ARG;
-    for (int k = 0; k < 6; k++) ms[k] = c->md_ms[k];
-    if (n_passes) *n_passes = c->md_passes;
+    for (int k = 0; k < 6; k++) ms[k] = c->md.ms[k];
+    if (n_passes) *n_passes = c->md.passes;
     return DG_OK;
 }
 
@@ -3997,25 +3777,15 @@ extern "C" int dg_sort_pairs(int device, uint64_t *keys, int64_t *vals, uint64_t
     if (!keys || !vals || !keys_tmp || !vals_tmp || key_bits < 1 || key_bits > 64 || n >= 0xFFFFF000ull) return DG_ERR_ARG;
     HIPCHK(hipSetDevice(device));
     if (n < 2) return DG_OK;
-    const uint32_t tiles = (uint32_t)((n + RS_TILE - 1) / RS_TILE), m = 16u * tiles;
-    const uint32_t scan_tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
     uint32_t *hist = nullptr, *sums = nullptr;
-    HIPCHK(hipMalloc((void **)&hist, ((size_t)m + 1) * 4));
-    if (hipMalloc((void **)&sums, ((size_t)scan_tiles + 1) * 4) != hipSuccess) { (void)hipFree(hist); return DG_ERR_HIP; }
-    uint64_t *ka = keys, *kb = keys_tmp; int64_t *va = vals, *vb = vals_tmp;
-    hipError_t e = hipSuccess;
-    for (int shift = 0; shift < key_bits && e == hipSuccess; shift += 4) {
-        k_rs_hist<<<tiles, 256, 0, 0>>>(ka, (uint32_t)n, shift, tiles, hist);
-        k_scan_tiles<<<scan_tiles, 256, 0, 0>>>(hist, hist, sums, m);
-        k_scan_top<<<1, 256, 0, 0>>>(sums, scan_tiles, hist + m, nullptr, 0, nullptr, 0);
-        k_scan_add<<<(m + 255) / 256, 256, 0, 0>>>(hist, sums, m);
-        k_rs_scatter<<<tiles, 256, 0, 0>>>(ka, va, kb, vb, (uint32_t)n, shift, tiles, hist);
-        e = hipGetLastError();
-        std::swap(ka, kb); std::swap(va, vb);
-    }
-    if (e == hipSuccess && ka != keys) {
-        e = hipMemcpyAsync(keys, ka, n * 8, hipMemcpyDeviceToDevice, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(vals, va, n * 8, hipMemcpyDeviceToDevice, 0);
+    HIPCHK(hipMalloc((void **)&hist, rs_hist_words((uint32_t)n) * 4));
+    if (hipMalloc((void **)&sums, rs_sums_words((uint32_t)n) * 4) != hipSuccess) { (void)hipFree(hist); return DG_ERR_HIP; }
+    uint64_t *const k2[2] = {keys, keys_tmp}; int64_t *const v2[2] = {vals, vals_tmp};
+    int which = 0;
+    hipError_t e = rs_sort_passes(0, k2, v2, hist, sums, (uint32_t)n, key_bits, which);
+    if (e == hipSuccess && which) {
+        e = hipMemcpyAsync(keys, keys_tmp, n * 8, hipMemcpyDeviceToDevice, 0);
+        if (e == hipSuccess) e = hipMemcpyAsync(vals, vals_tmp, n * 8, hipMemcpyDeviceToDevice, 0);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(0);
     (void)hipFree(hist); (void)hipFree(sums);
@@ -4227,21 +3997,21 @@ extern "C" int dg_probe_bgzf_phases(dg_ctx *c, const void *host_bytes, size_t n,
 {
     if (!c || !host_bytes || !n || !cycles) return DG_ERR_ARG;
     static_assert(BGZF_PHASES == 8, "dartgpu.h says 8");
-    c->bam_valid = false; c->bam_bytes = 0; c->bam_ptr = nullptr;
+    c->bam.valid = false; c->bam.bytes = 0; c->bam.ptr = nullptr;
     HIPCHK(hipSetDevice(c->device));
-    { const int rc = bam_state(c); if (rc) return rc; }
+    HIPCHK(c->bam.ready());
     DevTmp tmp;
     unsigned long long *d_ph = nullptr;
     HIPCHK(tmp.alloc((void **)&d_ph, BGZF_PHASES * 8));
     HIPCHK(hipMemsetAsync(d_ph, 0, BGZF_PHASES * 8, c->stream));
-    HIPCHK(c->bgzf_in.ensure(n + 8));
-    HIPCHK(hipMemcpyAsync(c->bgzf_in.p, host_bytes, n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c->bam.bgzf_in.ensure(n + 8));
+    HIPCHK(hipMemcpyAsync(c->bam.bgzf_in.p, host_bytes, n, hipMemcpyHostToDevice, c->stream));
     size_t out_bytes = 0; float ms = 0.f;
-    const int rc = bgzf_device(c, c->bgzf_in.p, n, true, &out_bytes, &ms, d_ph);
+    const int rc = bgzf_device(c, c->bam.bgzf_in.p, n, true, &out_bytes, &ms, d_ph);
     if (rc) return rc;
     HIPCHK(hipMemcpy(cycles, d_ph, BGZF_PHASES * 8, hipMemcpyDeviceToHost));
-    c->bam_ptr = c->bgzf_out.p; c->bam_bytes = out_bytes; c->bam_valid = true;
-    c->bam_ms[0] = 0.f; c->bam_ms[1] = ms;
+    c->bam.ptr = c->bam.bgzf_out.p; c->bam.bytes = out_bytes; c->bam.valid = true;
+    c->bam.ms[0] = 0.f; c->bam.ms[1] = ms;
     if (n_bytes) *n_bytes = out_bytes;
     if (device_ms) *device_ms = ms;
     return DG_OK;
