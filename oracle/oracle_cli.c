@@ -224,14 +224,17 @@ int main(int argc, char **argv)
             for (k = 0; k < n; k++) bases += (size_t)ev.a[k].rlen;
             seq_off = (uint32_t *)malloc((size_t)n * 4); rl = (uint16_t *)malloc((size_t)n * 2); seq = (char *)malloc(bases + 1);
             for (k = 0, off = 0; k < n; k++) { seq_off[k] = (uint32_t)off; rl[k] = (uint16_t)ev.a[k].rlen; memcpy(seq + off, ev.a[k].seq, (size_t)ev.a[k].rlen); off += (size_t)ev.a[k].rlen; }
-            caps[0] = (size_t)n * 64 + 1024; caps[1] = (size_t)n * 256 + 4096; caps[2] = (size_t)n * 8 + 64;
-            ro = (orc_read_out *)calloc((size_t)n, sizeof *ro); po = (orc_report_out *)calloc(caps[0], sizeof *po);
-            cig = (uint32_t *)calloc(caps[1], 4); so = (orc_sj_out *)calloc(caps[2], sizeof *so);
             {
                 orc_params p2 = pr;
                 int n_even = n, rc;
+                size_t grow = 1;
                 p2.paired = pair_end;
                 n_even = n - odd;
+                /* -m on reads inside long repeats writes hundreds of reports per read: the arrays grow until the batch fits */
+            again:
+                caps[0] = ((size_t)n * 64 + 1024) * grow; caps[1] = ((size_t)n * 256 + 4096) * grow; caps[2] = ((size_t)n * 8 + 64) * grow;
+                ro = (orc_read_out *)calloc((size_t)n, sizeof *ro); po = (orc_report_out *)calloc(caps[0], sizeof *po);
+                cig = (uint32_t *)calloc(caps[1], 4); so = (orc_sj_out *)calloc(caps[2], sizeof *so);
                 gettimeofday(&tv0, 0);
                 used[0] = used[1] = used[2] = 0;
                 rc = 0;
@@ -248,6 +251,7 @@ int main(int argc, char **argv)
                 }
                 gettimeofday(&tv1, 0);
                 t_map += (double)(tv1.tv_sec - tv0.tv_sec) + 1e-6 * (double)(tv1.tv_usec - tv0.tv_usec);
+                if (rc && grow < 1024) { free(ro); free(po); free(cig); free(so); grow *= 4; goto again; }
                 if (rc) { fprintf(stderr, "oracle: output capacity exceeded\n"); return 2; }
 
                 /* ---- SAM records: OutputPairedAlignments / OutputSingledAlignments ---- */

@@ -59,10 +59,11 @@ class Oracle:
             setattr(p, k, int(v))
         return p
 
-    def map_batch(self, params: OrcParams, seq_off, rlen, flat, threads: int = 4):
+    def map_batch(self, params: OrcParams, seq_off, rlen, flat, threads: int = 4, cap_scale: int = 1):
+        """cap_scale: the report and CIGAR arrays hold that many times the usual number per read (-m on reads inside long repeats)"""
         n = len(rlen)
         a, b, c = np.ascontiguousarray(seq_off, np.uint32), np.ascontiguousarray(rlen, np.uint16), np.ascontiguousarray(flat, np.uint8)
-        caps = (C.c_size_t * 3)(n * 64 + 1024, n * 256 + 4096, n * 8 + 64)
+        caps = (C.c_size_t * 3)((n * 64 + 1024) * cap_scale, (n * 256 + 4096) * cap_scale, n * 8 + 64)
         used = (C.c_size_t * 3)()
         reads = np.zeros(n, READ_OUT); rep = np.zeros(caps[0], REPORT_OUT); cig = np.zeros(caps[1], np.uint32); sj = np.zeros(caps[2], SJ_OUT)
         ctr = (C.c_uint64 * 10)()
