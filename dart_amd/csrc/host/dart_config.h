@@ -1,0 +1,301 @@
+// dart_amd/csrc/host/dart_config.h -- what `dart` was asked to do, decided once: the command line (main.cpp:96-239 of the reference), every DART_*
+// variable of the environment, and what follows from them.  Config::parse fills it before the first HIP call and nothing reads the environment after it;
+// choose_pipelines states, in one place, which of the four host pipelines a library's files may take.  No GPU and no libdartgpu here (dartgpu.h for its
+// types only): tests/native/dart_config_checks.cpp includes this header without `main` and checks both against tables.
+#pragma once
+#include "dartgpu.h"
+#include <zlib.h>
+#include <sys/stat.h>
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <utility>
+#include <vector>
+
+static const char *VersionStr = "1.4.6";
+
+static const int RUN = -1;      // what Config::parse and the stages of main return to go on; anything else is the exit code
+
+struct Config {
+    // ---- the command line (main.cpp:136-205) ----
+    const char *index = nullptr, *out = "output.sam";
+    char sj[256] = "junctions.tab";
+    std::vector<std::string> f1, f2;
+    int threads = 4;
+    bool pair_end = false, multi = false, unique = false, silent = false, all_sj = false, bam = false;
+    dg_params p;                            // the caller's defaults with -mis, -max_dup, -max_intron, -min_intron, -m, -all_sj and `paired` applied
+    bool two_files() const { return f1.size() == f2.size(); }      // separate mate files: library k is f1[k] + f2[k]
+
+    // ---- the environment ----
+    size_t batch_reads = 500000;            // DART_BATCH: at least 4000, even
+    int inflight = 2;                       // DART_INFLIGHT: contexts per device, at least 1
+    bool has_gpus = false; int gpus = 0;    // DART_GPUS (raw: the clamp needs the device count)
+    int same_device_times = 0;              // DART_SAME_DEVICE_TIMES: 0 = unset, else 1..8
+    bool streaming = false;                 // DART_STREAMING is set (to anything): every library takes the streaming pipeline
+    bool gz_stream = false;                 // DART_GZ_STREAM is set (to anything): no .gz file is inflated whole
+    size_t gz_whole_max = 0;                // DART_GZ_WHOLE_MAX_GB (default 8) in bytes, per library
+    bool timing = false;                    // DART_TIMING is set (to anything)
+    bool sync_aids = false;                 // DART_SYNC_AIDS
+    bool has_expected_reads = false; uint64_t expected_reads = 0;      // DART_EXPECTED_READS
+    bool device_fastq = false;              // DART_DEVICE_FASTQ, unless -bo streams
+    bool device_sj = false;                 // DART_DEVICE_SJ
+    bool sort_bam = false, bam_index = false, mark_dups = false;       // DART_SORT_BAM, DART_BAM_INDEX, DART_MARK_DUPLICATES
+    int coverage = 0;                       // DART_COVERAGE: 0, 1 or 2
+    uint32_t cov_exclude = 0x704u, cov_min_mapq = 0u;                  // DART_COVERAGE_EXCLUDE, DART_COVERAGE_MIN_MAPQ
+    double sort_piece_mb = 256.0;           // DART_SORT_PIECE_MB, raw: the piece arithmetic is where the pieces are cut
+    const char *gene_gtf = nullptr;         // DART_GENE_COUNTS (empty = unset)
+    const char *gene_feature = "exon";      // DART_GENE_FEATURE (empty = unset)
+    uint32_t gene_min_mapq = 4u;            // DART_GENE_MIN_MAPQ
+    int write_threads = 1;                  // DART_WRITE_THREADS, at least 1
+    int fmt_threads = 0;                    // DART_FMT_THREADS, at least 1; 0 = unset (what -t leaves)
+    bool write_mmap = false;                // DART_WRITE=mmap
+    bool pinned = false;                    // DART_PINNED
+
+    // ---- what follows from both ----
+    bool device_bam = false;                // -bo and DART_DEVICE_BAM: records and BGZF blocks from the device
+    bool bam_streams = false;               // -bo without it: the streaming pipeline, BAM from host text
+    bool bgzf_dynamic = false;              // DART_BGZF_DYNAMIC beside device_bam (alone it does nothing)
+    bool device_sam = false;                // DART_DEVICE_SAM, which -bo switches off (BAM is built from host text, or on the device)
+    bool device_gz = false;                 // DART_DEVICE_GZ with DART_DEVICE_FASTQ, a device formatter, no -bo streaming and no DART_STREAMING
+    std::vector<std::pair<std::string, uint32_t>> cov_tracks;      // the coverage tracks: path, strand flags
+    std::string bai_path, md_path, genes_path;                     // <out>.bai, <out>.markdup.txt, <out>.genes.tab; empty = not asked for
+    const char *bam_dev_note = "";          // the `bam=` field of the DART_TIMING lines: the parallel pipeline's ...
+    const char *bam_host_note = "";         // ... and the streaming pipeline's
+
+    void usage(FILE *f, const char *prog) const      // ShowProgramUsage, main.cpp:20-40
+    {
+        fprintf(f, "\nDART v%s (Hsin-Nan Lin & Wen-Lian Hsu)\n\n", VersionStr);
+        fprintf(f, "Usage: %s -i Index_Prefix -f <ReadFile_A1 ReadFile_B1 ...> [-f2 <ReadFile_A2 ReadFile_B2 ...>] -o|-bo Alignment_Output\n\n", prog);
+        fprintf(f, "Options: -t INT        number of threads [4]\n");
+        fprintf(f, "         -f            files with #1 mates reads\n");
+        fprintf(f, "         -f2           files with #2 mates reads\n");
+        fprintf(f, "         -mis INT      maximal number of mismatches in an alignment\n");
+        fprintf(f, "         -max_dup INT  maximal number of repetitive fragments (between 100-10000) [%d]\n", p.max_dup);
+        fprintf(f, "         -o            alignment filename in SAM format\n");
+        fprintf(f, "         -bo           alignment filename in BAM format\n");
+        fprintf(f, "                       (DART_DEVICE_BAM=1 DART_SORT_BAM=1: coordinate-sorted on the device; DART_BAM_INDEX=1 beside them: its .bai too; DART_COVERAGE=1 or 2: its bedGraph, or one per strand; DART_MARK_DUPLICATES=1: flag 0x400 set on the device)\n");
+        fprintf(f, "         -j            splice junction output filename [junctions.tab]\n");
+        fprintf(f, "         -m            output multiple alignments [false]\n");
+        fprintf(f, "         -all_sj       detect all splice junction regardless of mapq score [false]\n");
+        fprintf(f, "         -p            paired-end reads are interlaced in the same file\n");
+        fprintf(f, "         -unique       output unique alignments\n");
+        fprintf(f, "         -max_intron   the maximal intron size [500000]\n");
+        fprintf(f, "         -min_intron   the minimal intron size [10]\n");
+        fprintf(f, "         -v            version\n");
+        fprintf(f, "\n");
+    }
+
+    // argv and the environment into *this.  lookup: getenv, or a test's table.  defaults: dg_params_default's, handed in so that this header links without the library.
+    // The sequence of the checks is the program's: a run that fails two of them reports the first.
+    // Returns RUN, or the exit code of a run that ends here: 0 behind -h, -v and an unreadable input (main.cpp returns 0 there), 1 behind an error.  What it
+    // has to say goes to `out` (the program's stdout) and `err` (its stderr).
+    int parse(int argc, char *argv[], const char *(*lookup)(const char *), const dg_params &defaults, FILE *out_f, FILE *err_f)
+    {
+        auto env_on = [lookup](const char *k) { const char *v = lookup(k); return v && atoi(v) != 0; };
+        p = defaults;
+        if (argc == 1 || strcmp(argv[1], "-h") == 0) { usage(out_f, argv[0]); return 0; }
+        for (int i = 1; i < argc; i++) {   // main.cpp:136-205
+            std::string a = argv[i];
+            if (a == "-i") index = argv[++i];
+            else if (a == "-f") { while (++i < argc && argv[i][0] != '-') f1.push_back(argv[i]); i--; }
+            else if (a == "-f2") { while (++i < argc && argv[i][0] != '-') f2.push_back(argv[i]); i--; }
+            else if (a == "-t") { if ((threads = atoi(argv[++i])) <= 0) { fprintf(out_f, "Warning! Thread number should be a positive number!\n"); threads = 4; } }
+            else if (a == "-o") { out = argv[++i]; bam = false; }                      // main.cpp:158-168
+            else if (a == "-bo") { out = argv[++i]; bam = true; }
+            else if (a == "-mis" && i + 1 < argc) p.max_mismatch = atoi(argv[++i]);
+            else if (a == "-max_dup" && i + 1 < argc) { p.max_dup = atoi(argv[++i]); if (p.max_dup < 100) p.max_dup = 100; else if (p.max_dup >= 10000) p.max_dup = 10000; }
+            else if (a == "-silent") silent = true;
+            else if (a == "-j") { strncpy(sj, argv[++i], 255); sj[255] = 0; }
+            else if (a == "-p") pair_end = true;
+            else if (a == "-m") multi = true;
+            else if (a == "-unique") unique = true;
+            else if (a == "-all_sj") all_sj = true;
+            else if (a == "-max_intron") { if ((p.max_intron = atoi(argv[++i])) < 100000) p.max_intron = 100000; }
+            else if (a == "-min_intron") p.min_intron = atoi(argv[++i]);
+            else if (a == "-d" || a == "-debug") {}   // debug prints are not reproduced
+            else if (a == "-v" || a == "--version") { fprintf(out_f, "DART v%s\n\n", VersionStr); return 0; }
+            else { fprintf(err_f, "Error! Unknow parameter: %s\n", argv[i]); usage(out_f, argv[0]); return 1; }
+        }
+        p.multi_hit = multi; p.all_sj = all_sj;
+        if (f1.empty()) { fprintf(err_f, "Error! Please specify a valid read input!\n"); usage(out_f, argv[0]); return 1; }
+        if (!f2.empty() && f1.size() != f2.size()) {
+            fprintf(err_f, "Error! Paired-end reads input numbers do not match!\n");
+            fprintf(err_f, "Read1:\n"); for (auto &s : f1) fprintf(err_f, "\t%s\n", s.c_str());
+            fprintf(err_f, "Read2:\n"); for (auto &s : f2) fprintf(err_f, "\t%s\n", s.c_str());
+            return 1;
+        }
+        p.paired = (pair_end || two_files()) ? 1 : 0;
+        {   // CheckInputFiles / CheckOutputFileName, main.cpp:42-94,220
+            struct stat st; bool ok = true;
+            for (auto &s : f1) if (stat(s.c_str(), &st) == -1) { ok = false; fprintf(err_f, "Cannot access file:[%s]\n", s.c_str()); }
+            for (auto &s : f2) if (stat(s.c_str(), &st) == -1) { ok = false; fprintf(err_f, "Cannot access file:[%s]\n", s.c_str()); }
+            if (strcmp(out, "output.sam") != 0 && stat(out, &st) == 0) {
+                if (st.st_mode & S_IFDIR) { ok = false; fprintf(out_f, "Warning: %s is a directory!\n", out); }
+                else if (!(st.st_mode & S_IFREG)) { ok = false; fprintf(out_f, "Warning: %s is not a regular file!\n", out); }
+            }
+            if (!ok) return 0;
+        }
+        if (const char *v = lookup("DART_BATCH")) batch_reads = (size_t)atoll(v);
+        batch_reads = std::max<size_t>(4000, batch_reads & ~(size_t)1);
+        if (const char *v = lookup("DART_INFLIGHT")) inflight = atoi(v);
+        inflight = std::max(1, inflight);
+        // DART_DEVICE_BAM=1 with -bo: plain-FASTQ libraries (and .gz ones inflated whole) take the parallel pipeline, and the BAM records and their BGZF blocks come
+        // from the device (dg_batch_format_bam); FASTA and streamed .gz keep the host writer whatever the switch says.  Without the switch -bo is what it always was.
+        device_bam = bam && env_on("DART_DEVICE_BAM");
+        bgzf_dynamic = device_bam && env_on("DART_BGZF_DYNAMIC");      // (alone it does nothing)
+        bam_streams = bam && !device_bam;         // -bo forces the streaming pipeline
+        // DART_SORT_BAM=1 beside -bo and DART_DEVICE_BAM=1: the records of every batch stay in HBM (dg_batch_accumulate_bam) and the file is written once, at the end,
+        // in coordinate order (dg_bam_sort_finish / dg_bam_sort_compress).  A user who asked for a sorted file never silently gets an unsorted one: whatever is
+        // missing ends the run before any output exists.
+        sort_bam = env_on("DART_SORT_BAM");
+        if (sort_bam && !device_bam) {
+            fprintf(err_f, "Error! DART_SORT_BAM=1 needs -bo and DART_DEVICE_BAM=1: %s missing\n", !bam ? (env_on("DART_DEVICE_BAM") ? "-bo is" : "both are") : "DART_DEVICE_BAM=1 is");
+            return 1;
+        }
+        // DART_BAM_INDEX=1 beside DART_SORT_BAM=1: the sorted file's index <out>.bai, built on the device from the sorted records and the blocks' sizes
+        // (dg_bam_index_finish) in place of the `samtools index` behind the sort.  Without the sort there is nothing to index: no output is begun.
+        bam_index = env_on("DART_BAM_INDEX");
+        if (bam_index && !sort_bam) {
+            fprintf(err_f, "Error! DART_BAM_INDEX=1 needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n");
+            return 1;
+        }
+        if (bam_index) bai_path = std::string(out) + ".bai";
+        // DART_COVERAGE=1 beside DART_SORT_BAM=1: the sorted file's coverage track <out>.bedgraph, built on the device from the sorted records (dg_bam_coverage_finish)
+        // in place of a `bedtools genomecov -bg -split` over the file; DART_COVERAGE=2: <out>.plus.bedgraph and <out>.minus.bedgraph.  DART_COVERAGE_EXCLUDE (default
+        // 0x704) and DART_COVERAGE_MIN_MAPQ (default 0) are the filter.  Without the sort there is nothing to cover: no output is begun.
+        if (const char *v = lookup("DART_COVERAGE")) coverage = atoi(v);
+        if (coverage != 0 && coverage != 1 && coverage != 2) {
+            fprintf(err_f, "Error! DART_COVERAGE=%d is neither 1 (one track) nor 2 (one track per strand)\n", coverage);
+            return 1;
+        }
+        if (coverage && !sort_bam) {
+            fprintf(err_f, "Error! DART_COVERAGE=%d needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n", coverage);
+            return 1;
+        }
+        if (const char *v = lookup("DART_COVERAGE_EXCLUDE")) cov_exclude = (uint32_t)strtoul(v, nullptr, 0);
+        if (const char *v = lookup("DART_COVERAGE_MIN_MAPQ")) cov_min_mapq = (uint32_t)strtoul(v, nullptr, 0);
+        if (coverage == 1) cov_tracks.emplace_back(std::string(out) + ".bedgraph", 0u);
+        if (coverage == 2) { cov_tracks.emplace_back(std::string(out) + ".plus.bedgraph", DG_COV_STRAND_PLUS); cov_tracks.emplace_back(std::string(out) + ".minus.bedgraph", DG_COV_STRAND_MINUS); }
+        // DART_MARK_DUPLICATES=1 beside DART_SORT_BAM=1: flag 0x400 is written into the sorted records on the device (dg_bam_markdup_finish) before the first piece
+        // is compressed, in place of a `samtools markdup` over the file; the index and the tracks see the marked records; <out>.markdup.txt holds the counts.
+        // Without the sort there is nothing to mark: no output is begun.
+        mark_dups = env_on("DART_MARK_DUPLICATES");
+        if (mark_dups && !sort_bam) {
+            fprintf(err_f, "Error! DART_MARK_DUPLICATES=1 needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n");
+            return 1;
+        }
+        if (mark_dups) md_path = std::string(out) + ".markdup.txt";
+        bam_dev_note = sort_bam ? (bgzf_dynamic ? ", bam=device+sorted+dyn" : ", bam=device+sorted") : bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "";
+        bam_host_note = !bam ? "" : ", bam=host";
+        // A library of .gz FASTQ files small enough to be inflated whole (libdeflate, ~3x zlib; DART_GZ_WHOLE_MAX_GB per file, default 8) goes through the
+        // parallel pipeline too -- if the inflated text is one the reference's gz reader and its plain reader see alike (FastqIndex::run); else, and for
+        // everything libdeflate cannot take, the streaming reader.
+        { const char *v = lookup("DART_GZ_WHOLE_MAX_GB"); gz_whole_max = (size_t)((v ? atof(v) : 8.0) * (double)(1ull << 30)); }
+        streaming = lookup("DART_STREAMING") != nullptr;
+        gz_stream = lookup("DART_GZ_STREAM") != nullptr;
+        // DART_DEVICE_SAM=1: SAM text from the device's formatter (dg_batch_format_sam) instead of the host's; -bo keeps the host's (BAM is built from host text)
+        device_sam = !bam && env_on("DART_DEVICE_SAM");
+        // DART_DEVICE_FASTQ=1: the parallel pipeline hands its batches to the GPU as FASTQ text (dg_batch_upload_fastq); the streaming pipeline and -bo ignore it
+        device_fastq = !bam_streams && env_on("DART_DEVICE_FASTQ");
+        // DART_DEVICE_GZ=1 beside DART_DEVICE_FASTQ=1 and a device formatter (DART_DEVICE_SAM=1, or DART_DEVICE_BAM=1 with -bo: the host never holds the names and
+        // qualities): a library whose files are all FASTQ .gz with a BGZF block in front is inflated on the device too (GzDevPlan, fast_fastq.h).  Anything else
+        // -- also a library its check pass turns down -- runs as without the switch.
+        device_gz = env_on("DART_DEVICE_GZ") && env_on("DART_DEVICE_FASTQ") && !bam_streams && !streaming && (device_bam || device_sam);
+        // DART_DEVICE_SJ=1: the junction table is counted, sorted and printed on the device (dg_batch_accumulate_sj per batch, dg_sj_merge / dg_sj_finish at the end);
+        // works in both pipelines, with -o and -bo alike.  Without the switch the ordered writer fills a std::map, as always.
+        device_sj = env_on("DART_DEVICE_SJ");
+        if (const char *v = lookup("DART_GPUS")) { has_gpus = true; gpus = atoi(v); }
+        // DART_SAME_DEVICE_TIMES=k (a test hook for one-GPU boxes): k "devices" that are all device 0 -- each with its own index replica, root context and clones --, so
+        // that the multi-device pool (several roots, one ordered writer: Mapping.cpp:644-664) runs where only one GPU exists
+        if (const char *v = lookup("DART_SAME_DEVICE_TIMES")) same_device_times = std::max(1, std::min(8, atoi(v)));
+        // DART_GENE_COUNTS=<annotation.gtf>: reads per gene, counted on the device batch by batch (dg_batch_accumulate_genes) from the records in HBM, written as
+        // <out>.genes.tab (STAR's ReadsPerGene.out.tab layout) after the alignments are complete.  Both pipelines, -o and -bo, beside every other switch.
+        // DART_GENE_FEATURE (default exon) picks the GTF lines, DART_GENE_MIN_MAPQ (default 4, the -unique rule mapq > 3) the units that count as unique.
+        { const char *v = lookup("DART_GENE_COUNTS"); gene_gtf = v && v[0] ? v : nullptr; }
+        if (gene_gtf) genes_path = std::string(out) + ".genes.tab";
+        { const char *v = lookup("DART_GENE_FEATURE"); if (v && v[0]) gene_feature = v; }
+        if (const char *v = lookup("DART_GENE_MIN_MAPQ")) gene_min_mapq = (uint32_t)strtoul(v, nullptr, 0);
+        if (const char *v = lookup("DART_EXPECTED_READS")) { has_expected_reads = true; expected_reads = (uint64_t)atoll(v); }
+        sync_aids = env_on("DART_SYNC_AIDS");
+        timing = lookup("DART_TIMING") != nullptr;
+        if (const char *v = lookup("DART_SORT_PIECE_MB")) sort_piece_mb = atof(v);
+        // the parallel pipeline's threads (fast_fastq.h says why ONE writer) and its arenas
+        if (const char *v = lookup("DART_WRITE_THREADS")) write_threads = std::max(1, atoi(v));
+        if (const char *v = lookup("DART_FMT_THREADS")) fmt_threads = std::max(1, atoi(v));
+        { const char *v = lookup("DART_WRITE"); write_mmap = v && strcmp(v, "mmap") == 0; }          // default pwrite (measured on tmpfs: 5.1 GB/s against 3.2 GB/s through a shared mapping)
+        pinned = env_on("DART_PINNED");
+        return RUN;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
+// which pipeline a library takes
+// ---------------------------------------------------------------------------------------------
+static bool check_read_format(const char *fn)   // CheckReadFormat, Mapping.cpp:718-726
+{
+    char b[1] = {0}; gzFile f = gzopen(fn, "rb");
+    if (!f) return false;
+    gzread(f, b, 1); gzclose(f);
+    return b[0] == '@';
+}
+
+static bool starts_with_bgzf(const char *fn)
+{
+    unsigned char h[18 + 256]; FILE *f = fopen(fn, "rb");
+    if (!f) return false;
+    const size_t got = fread(h, 1, sizeof h, f); fclose(f);
+    if (got < 18 || h[0] != 0x1f || h[1] != 0x8b || h[2] != 8 || h[3] != 4) return false;
+    const size_t xlen = (size_t)h[10] | (size_t)h[11] << 8;
+    for (size_t x = 12; x + 4 <= 12 + xlen && x + 4 <= got;) { const size_t slen = (size_t)h[x + 2] | (size_t)h[x + 3] << 8; if (h[x] == 'B' && h[x + 1] == 'C' && slen == 2) return true; x += 4 + slen; }
+    return false;
+}
+
+// What the rule below needs to know about a read file.
+struct FileProbe {
+    bool gz = false;        // the name ends in ".gz" (what follows the path's last '.' is "gz")
+    bool fastq = false;     // its first byte, inflated if need be, is '@'
+    bool bgzf = false;      // it begins with a BGZF block
+    long long size = -1;    // st_size; -1 = stat failed
+};
+static FileProbe probe(const std::string &fn)
+{
+    FileProbe f; struct stat st;
+    f.gz = fn.substr(fn.find_last_of('.') + 1) == "gz";
+    f.fastq = check_read_format(fn.c_str());
+    f.bgzf = f.gz && starts_with_bgzf(fn.c_str());
+    if (stat(fn.c_str(), &st) == 0) f.size = (long long)st.st_size;
+    return f;
+}
+
+// The pipelines a library may take; they are tried in this order: BGZF inflated on the device, .gz inflated whole, then plain FASTQ in parallel or -- for
+// whatever is left -- streaming.  The first two can still turn the library down when its turn comes (GzDevPlan::make refusing; FastqIndex::ok false after
+// the inflation) and the next one is tried.
+struct PipelineChoice {
+    bool gz_device = false, gz_whole = false;
+    bool plain = false;          // the last candidate is the parallel pipeline on plain FASTQ; false: it is the streaming pipeline
+    // the first library only, before the device is touched: the slot pool is started when mate 1 alone looks like the parallel pipeline's -- also when a .gz
+    // mate 2 makes the library stream after all
+    bool head_pool = false;
+};
+// m2 == nullptr: one file.  libdeflate: the system has it (lib_deflate().ok()).
+static PipelineChoice choose_pipelines(const Config &c, const FileProbe &m1, const FileProbe *m2, bool libdeflate)
+{
+    PipelineChoice ch;
+    const bool may_parallel = !c.bam_streams && !c.streaming;
+    // BGZF FASTQ inflated on the device: every file is FASTQ .gz with a BGZF block in front
+    ch.gz_device = c.device_gz;
+    // .gz FASTQ inflated whole: every file is FASTQ .gz of at most half of DART_GZ_WHOLE_MAX_GB
+    ch.gz_whole = may_parallel && !c.gz_stream && libdeflate && c.gz_whole_max != 0;
+    for (const FileProbe *m : {&m1, m2}) {
+        if (!m) continue;
+        if (!m->gz || !m->bgzf || !m->fastq) ch.gz_device = false;
+        if (!m->gz || !m->fastq || m->size < 0 || (size_t)m->size > c.gz_whole_max / 2) ch.gz_whole = false;
+    }
+    // plain FASTQ through the parallel pipeline: mate 1 plain FASTQ, mate 2 not .gz (its format is compared when the library is opened); all else streams
+    const bool m1_plain = may_parallel && m1.fastq && !m1.gz;
+    ch.plain = m1_plain && (!m2 || !m2->gz);
+    ch.head_pool = ch.gz_device || ch.gz_whole || m1_plain;
+    return ch;
+}

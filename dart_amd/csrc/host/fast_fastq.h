@@ -22,6 +22,7 @@
 #include <sys/mman.h>
 #include "libdeflate_dl.h"
 #include <unistd.h>
+#include "dart_config.h"
 
 // (libdeflate_dl.h: the system's libdeflate when it is there; it has no streaming interface, so a .gz file's output must fit a buffer: open_gz below)
 struct MappedFile {
@@ -54,7 +55,7 @@ struct MappedFile {
     // member's ISIZE is only a first guess (multi-member and bgzip files), and starting over doubled the work each time.
     bool open_gz(const char *fn, size_t max_out) {
         const LibDeflate &ld = lib_deflate();
-        if (!ld.ok() || getenv("DART_GZ_STREAM")) return false;          // DART_GZ_STREAM=1: always the streaming reader
+        if (!ld.ok()) return false;          // (DART_GZ_STREAM=1, always the streaming reader, is choose_pipelines' business: such a job never comes here)
         MappedFile z;
         if (!z.open(fn) || z.n < 18 || (unsigned char)z.p[0] != 0x1f || (unsigned char)z.p[1] != 0x8b) return false;
         { const size_t left = memory_left(); if (left && left / 3 < max_out) max_out = left / 3; }
@@ -329,60 +330,14 @@ static void format_views(const RView *V, int lo, int hi, int n_pair_mode, const 
 // ---------------------------------------------------------------------------------------------
 // the pipeline
 // ---------------------------------------------------------------------------------------------
-static int hdr_beg_f(const char *s, int len) { for (int i = 1; i < len; i++) if (s[i] != '>' && s[i] != '@') return i; return len - 1; }
-static int hdr_end_f(const char *s, int len) { for (int i = 1; i < len; i++) if (s[i] == ' ' || s[i] == '/' || s[i] == '\t') return i; return len - 1; }
+static int hdr_beg(const char *s, int len) { for (int i = 1; i < len; i++) if (s[i] != '>' && s[i] != '@') return i; return len - 1; }
+static int hdr_end(const char *s, int len) { for (int i = 1; i < len; i++) if (s[i] == ' ' || s[i] == '/' || s[i] == '\t') return i; return len - 1; }
 
 static inline void rev_copy(char *d, const char *s, size_t l) { if (g_avx2) rev_copy_avx2(d, s, l); else for (size_t i = 0; i < l; i++) d[i] = s[l - 1 - i]; }
 
-// DART_DEVICE_SAM=1: the SAM text of a batch is formatted on the GPU (dg_batch_format_sam) right behind its mapping, on the same context, and
-// downloaded into the slot; format_views is not run.  Set by the host program before the first library.
-static bool g_device_sam = false;
-// DART_DEVICE_FASTQ=1: a batch goes to the GPU as the bytes of its records, straight from the mapped files (dg_batch_upload_fastq): no arena, no base copy on
-// the host; with DART_DEVICE_SAM=1 as well the text is formatted from the names and qualities that upload left in HBM (dg_batch_format_sam_resident) and
-// nothing is gathered.  The index pass below still decides the batches.  A library with a record without bases keeps the host's assembly.
-static bool g_device_fastq = false;
-// DART_DEVICE_BAM=1 with -bo: the batch's BAM records are written and compressed on the GPU (dg_batch_format_bam, or its resident form with DART_DEVICE_FASTQ=1)
-// behind its mapping; the slot holds whole BGZF blocks and the ordered writer hands them to g_bam_sink (BamWriter::add_bgzf_blocks) instead of writing text to fd.
-static bool g_device_bam = false;
-// DART_BGZF_DYNAMIC=1 beside DART_DEVICE_BAM=1: the blocks are coded with dynamic Huffman codes per strip (DG_BAM_DYNAMIC): a smaller file of the same records
-static bool g_bgzf_dynamic = false;
-static std::function<bool(const char *blocks, size_t n, long long records, long long refused)> g_bam_sink;
-// DART_SORT_BAM=1 beside DART_DEVICE_BAM=1: a batch's records are left uncompressed (DG_BAM_RAW) and appended to its context's store in HBM
-// (dg_batch_accumulate_bam) under the batch's index counted across libraries; nothing is downloaded, the ordered writer only sums the counters.  The host
-// program merges the stores, sorts and writes the file at the end of the job.
-static bool g_sort_bam = false;
-static size_t g_sort_ordinal_base = 0;      // batches of the libraries before the current one
-static std::atomic<unsigned long long> g_sort_acc_ns{0};
-// DART_DEVICE_SJ=1: every mapping thread counts its batch's junction tuples in its context's table on the GPU (dg_batch_accumulate_sj) right behind the mapping;
-// the tuples are not downloaded and the ordered writer's map loop does not run.  The host program merges the tables and prints junctions.tab from the device's
-// text at the end of the job.  The three figures below feed its `[dart sj]` line: tuples seen, time in the accumulate calls, time in the writer's map loop.
-static bool g_device_sj = false;
-static std::atomic<unsigned long long> g_sj_tuples{0}, g_sj_acc_ns{0}, g_sj_map_ns{0};
-static inline unsigned long long sj_now_ns() { return (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-// the tuples of the batch that ctx has just mapped into its table
-static inline int sj_accumulate(dg_ctx *ctx)
-{
-    const unsigned long long t = sj_now_ns();
-    size_t n = 0;
-    const int rc = dg_batch_accumulate_sj(ctx, &n);
-    g_sj_acc_ns += sj_now_ns() - t; g_sj_tuples += n;
-    return rc;
-}
-
-// DART_GENE_COUNTS=<annotation.gtf>: every mapping thread counts its batch's units per gene in its context's table on the GPU (dg_batch_accumulate_genes) right
-// behind the mapping, where sj_accumulate sits: mates are still neighbours there.  The host program merges the tables and prints <out>.genes.tab at the end
-// of the job.  The figures feed its `[dart genes]` line: units counted, time in the accumulate calls.
-static bool g_gene_counts = false;
-static uint32_t g_gene_min_mapq = 4;
-static std::atomic<unsigned long long> g_gene_units{0}, g_gene_acc_ns{0};
-static inline int gene_accumulate(dg_ctx *ctx, int n_pair_mode)
-{
-    const unsigned long long t = sj_now_ns();
-    size_t n = 0;
-    const int rc = dg_batch_accumulate_genes(ctx, n_pair_mode, g_gene_min_mapq, &n);
-    g_gene_acc_ns += sj_now_ns() - t; g_gene_units += n;
-    return rc;
-}
+// the program's one clock (monotonic)
+static inline unsigned long long now_ns() { return (unsigned long long)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+static inline double now_s() { return (double)now_ns() * 1e-9; }
 
 struct FastSlot {                       // one batch travelling through the stages
     size_t first = 0; int n = 0, odd = 0; size_t seqno = 0;
@@ -402,34 +357,102 @@ struct FastStats { double t_index = 0, t_asm = 0, t_map = 0, t_fmt = 0, t_write 
 
 // Batch arenas: ordinary memory by default -- page-locking costs ~1 s per GB, more than a short job saves; DART_PINNED=1 page-locks them
 // (then the copies to and from the GPU are plain DMA transfers: worth it for long runs with several contexts in flight)
-static bool g_pinned_slots = false;
-static void *arena_alloc(size_t bytes) { return g_pinned_slots ? dg_host_alloc(bytes) : malloc(bytes ? bytes : 1); }
-static void arena_free(void *p) { if (!p) return; if (g_pinned_slots) dg_host_free(p); else free(p); }
-
-static void slot_reserve(FastSlot &s, size_t n, size_t bases, const size_t need[3])
-{
-    if (bases + 64 > s.seq_cap) { arena_free(s.seq); s.seq_cap = bases + bases / 8 + 4096; s.seq = (char *)arena_alloc(s.seq_cap); }
-    const size_t want[3] = { std::max(need[0], n * 2 + 1024), std::max(need[1], n * 6 + 4096), std::max(need[2], n + 1024) };
-    if (!s.ro || s.n_cap < n || s.caps[0] < want[0] || s.caps[1] < want[1] || s.caps[2] < want[2]) {
-        arena_free(s.ro); arena_free(s.po); arena_free(s.cig); arena_free(s.sj);
-        s.n_cap = n + 16;
-        s.ro = (dg_read_out *)arena_alloc(s.n_cap * sizeof(dg_read_out)); s.po = (dg_report_out *)arena_alloc(want[0] * sizeof(dg_report_out));
-        s.cig = (uint32_t *)arena_alloc(want[1] * 4); s.sj = (dg_sj_out *)arena_alloc(want[2] * sizeof(dg_sj_out));
-        s.caps[0] = want[0]; s.caps[1] = want[1]; s.caps[2] = want[2];
-    }
-}
-
-// the batch slots; with DART_PINNED=1 they are page-locked in the background while the index loads
+// The batch slots and their arenas; with DART_PINNED=1 they are page-locked in the background while the index loads.  (The switch counts when the pool is
+// started, which is when the first library looks like the parallel pipeline's: a pool that a later library is the first to use has ordinary memory.)
 struct SlotPool {
-    std::vector<FastSlot> slots; std::thread th;
-    void start(size_t n_slots, size_t batch_reads, size_t bytes_per_read) {
-        g_pinned_slots = getenv("DART_PINNED") && atoi(getenv("DART_PINNED")) != 0;
+    std::vector<FastSlot> slots; std::thread th; bool pinned = false;
+    void *alloc(size_t bytes) const { return pinned ? dg_host_alloc(bytes) : malloc(bytes ? bytes : 1); }
+    void release(void *p) const { if (!p) return; if (pinned) dg_host_free(p); else free(p); }
+    void reserve(FastSlot &s, size_t n, size_t bases, const size_t need[3]) const {
+        if (bases + 64 > s.seq_cap) { release(s.seq); s.seq_cap = bases + bases / 8 + 4096; s.seq = (char *)alloc(s.seq_cap); }
+        const size_t want[3] = { std::max(need[0], n * 2 + 1024), std::max(need[1], n * 6 + 4096), std::max(need[2], n + 1024) };
+        if (!s.ro || s.n_cap < n || s.caps[0] < want[0] || s.caps[1] < want[1] || s.caps[2] < want[2]) {
+            release(s.ro); release(s.po); release(s.cig); release(s.sj);
+            s.n_cap = n + 16;
+            s.ro = (dg_read_out *)alloc(s.n_cap * sizeof(dg_read_out)); s.po = (dg_report_out *)alloc(want[0] * sizeof(dg_report_out));
+            s.cig = (uint32_t *)alloc(want[1] * 4); s.sj = (dg_sj_out *)alloc(want[2] * sizeof(dg_sj_out));
+            s.caps[0] = want[0]; s.caps[1] = want[1]; s.caps[2] = want[2];
+        }
+    }
+    // text: the slot's room for the device formatter's output
+    void reserve_text(FastSlot &s, size_t nb) const { if (nb > s.text_cap) { release(s.text); s.text_cap = nb + nb / 8 + 4096; s.text = (char *)alloc(s.text_cap); } }
+    void start(size_t n_slots, size_t batch_reads, size_t bytes_per_read, bool page_locked) {
+        pinned = page_locked;
         slots.resize(n_slots);
-        if (g_pinned_slots) th = std::thread([this, batch_reads, bytes_per_read]() { const size_t z[3] = {0, 0, 0}; for (auto &s : slots) slot_reserve(s, batch_reads, batch_reads * bytes_per_read, z); });
+        if (pinned) th = std::thread([this, batch_reads, bytes_per_read]() { const size_t z[3] = {0, 0, 0}; for (auto &s : slots) reserve(s, batch_reads, batch_reads * bytes_per_read, z); });
     }
     void wait() { if (th.joinable()) th.join(); }
-    ~SlotPool() { wait(); for (auto &s : slots) { arena_free(s.seq); arena_free(s.ro); arena_free(s.po); arena_free(s.cig); arena_free(s.sj); arena_free(s.names_quals); arena_free(s.text); } }
+    ~SlotPool() { wait(); for (auto &s : slots) { release(s.seq); release(s.ro); release(s.po); release(s.cig); release(s.sj); release(s.names_quals); release(s.text); } }
 };
+
+// One run of the program: what was asked (Config), the device contexts, and everything that lives across its libraries.  main owns it and hands it to both
+// pipelines -- the parallel one below and the streaming one in dart_main.cpp -- and to the stages behind them.  What the switches mean to a batch:
+//   cfg.device_sam     the SAM text of a batch is formatted on the GPU (dg_batch_format_sam) right behind its mapping, on the same context, and downloaded into
+//                      the slot; format_views is not run
+//   cfg.device_fastq   a batch goes to the GPU as the bytes of its records, straight from the mapped files (dg_batch_upload_fastq): no arena, no base copy on the
+//                      host; with device_sam as well the text is formatted from the names and qualities that upload left in HBM (dg_batch_format_sam_resident)
+//                      and nothing is gathered.  The index pass still decides the batches.  A library with a record without bases keeps the host's assembly
+//   cfg.device_bam     the batch's BAM records are written and compressed on the GPU (dg_batch_format_bam, or its resident form with device_fastq) behind its
+//                      mapping; the slot holds whole BGZF blocks and the ordered writer hands them to bam_sink (BamWriter::add_bgzf_blocks) instead of writing
+//                      text to sam_fd.  cfg.bgzf_dynamic: the blocks are coded with dynamic Huffman codes per strip (DG_BAM_DYNAMIC): a smaller file of the same records
+//   cfg.sort_bam       a batch's records are left uncompressed (DG_BAM_RAW) and appended to its context's store in HBM (dg_batch_accumulate_bam) under the batch's
+//                      index counted across libraries; nothing is downloaded, the ordered writer only sums the counters.  The sorted-BAM stage merges the
+//                      stores, sorts and writes the file at the end of the job
+//   cfg.device_sj      every mapping thread counts its batch's junction tuples in its context's table on the GPU (sj_accumulate) right behind the mapping; the
+//                      tuples are not downloaded and the ordered writer's map loop does not run.  The junction stage merges the tables and prints junctions.tab
+//                      from the device's text at the end of the job
+//   cfg.gene_gtf       every mapping thread counts its batch's units per gene in its context's table on the GPU (gene_accumulate) right behind the mapping, where
+//                      sj_accumulate sits: mates are still neighbours there.  The gene stage merges the tables and prints <out>.genes.tab at the end of the job
+struct Job {
+    const Config &cfg;
+    std::vector<dg_ctx *> ctx, roots, clones;             // ctx: all contexts, device by device, each root followed by its clones
+    std::vector<std::string> names;                       // chromosome names
+    bool pair_end;                                        // -p, or a library of two files has been seen
+    Counters total;
+    std::map<std::pair<int64_t, int64_t>, int> sjmap;     // the host's junction table (without cfg.device_sj)
+    time_t t0 = 0;                                        // mapping began (the progress lines count from it)
+    double start_up_s = 0;                                // process start to contexts ready: the start-up field of the `[dart timing]` lines
+    SlotPool pool;                                       // batch slots of the parallel pipeline
+    std::function<bool(const char *blocks, size_t n, long long records, long long refused)> bam_sink;
+    int sam_fd = -1; uint64_t sam_off = 0;                // the parallel pipeline's place in the SAM file: descriptor and offset (advanced), set around each library
+    size_t sort_ordinal_base = 0;                         // cfg.sort_bam: batches of the libraries before the current one
+    // accounting for the `[dart timing]`, `[dart sj]` and `[dart genes]` lines: time in dg_batch_accumulate_bam; junction tuples seen, time in the accumulate
+    // calls, time in the writer's map loop; units counted per gene, time in the accumulate calls
+    std::atomic<unsigned long long> sort_acc_ns{0}, sj_tuples{0}, sj_acc_ns{0}, sj_map_ns{0}, gene_units{0}, gene_acc_ns{0};
+    explicit Job(const Config &c) : cfg(c), pair_end(c.pair_end) {}
+};
+
+// A batch is in the output: its reads into the total, its junction tuples into the host's table (UpdateLocal/GlobalSJMap, Mapping.cpp:532-577; not with
+// cfg.device_sj, where they never left the device), the progress line.  Both pipelines' ordered writers call it.
+static void batch_written(Job &job, long long n_reads, const dg_sj_out *sj, size_t n_sj)
+{
+    job.total.total += n_reads;
+    if (!job.cfg.device_sj) {
+        const unsigned long long tj = now_ns();
+        for (size_t k = 0; k < n_sj; k++) job.sjmap[std::make_pair(sj[k].g1, sj[k].g2)]++;
+        job.sj_map_ns += now_ns() - tj; job.sj_tuples += n_sj;
+    }
+    if (!job.cfg.silent) { fprintf(stdout, "\r%lld %s tags have been processed in %lld seconds...", job.total.total, job.pair_end ? "paired-end" : "singled-end", (long long)(time(NULL) - job.t0)); fflush(stdout); }
+}
+
+// the tuples of the batch that ctx has just mapped into its table
+static inline int sj_accumulate(Job &job, dg_ctx *ctx)
+{
+    const unsigned long long t = now_ns();
+    size_t n = 0;
+    const int rc = dg_batch_accumulate_sj(ctx, &n);
+    job.sj_acc_ns += now_ns() - t; job.sj_tuples += n;
+    return rc;
+}
+// likewise its units per gene
+static inline int gene_accumulate(Job &job, dg_ctx *ctx, int n_pair_mode)
+{
+    const unsigned long long t = now_ns();
+    size_t n = 0;
+    const int rc = dg_batch_accumulate_genes(ctx, n_pair_mode, job.cfg.gene_min_mapq, &n);
+    job.gene_acc_ns += now_ns() - t; job.gene_units += n;
+    return rc;
+}
 
 // The mapped read files of a library and the positions of their records.  The host program starts this for its first library before it
 // loads the genome index and calls dg_init, so the two overlap (0.2 s per 16 M reads of the 1.6 s a job of that size takes).
@@ -463,7 +486,7 @@ struct FastqIndex {
     std::string f1, f2; std::thread th;
     // gz: the files are .gz and are inflated whole first (MappedFile::open_gz); ok then also says that the plain pipeline reads them as the gz reader would
     void run(const char *a, const char *b, int T, bool gz = false, size_t max_out = 0) {
-        const double t = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+        const double t = now_s();
         f1 = a; f2 = b ? b : ""; two = b != nullptr;
         if (gz) {
             bool ok2 = true;
@@ -476,7 +499,7 @@ struct FastqIndex {
         }
         if (ok && gz) ok = !e1 && !e2 && gz_reader_sees_the_same(m1, r1, T) && (!b || gz_reader_sees_the_same(m2, r2, T));
         if (!ok && gz) { m1.close_now(); m2.close_now(); r1.clear(); r2.clear(); r1.shrink_to_fit(); r2.shrink_to_fit(); }
-        t_index = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t;
+        t_index = now_s() - t;
     }
     void start(const char *a, const char *b, int T, bool gz = false, size_t max_out = 0) { f1 = a; f2 = b ? b : ""; th = std::thread([this, a, b, T, gz, max_out]() { run(a, b, T, gz, max_out); }); }
     void wait() { if (th.joinable()) th.join(); }
@@ -535,7 +558,7 @@ struct GzDevPlan {
     }
     // false: the library is not one for this path (the caller takes the host's, silently)
     bool make(const char *f1, const char *f2, bool pair_end, size_t batch_reads, dg_ctx *c) {
-        const double t = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
+        const double t = now_s();
         two = f2 != nullptr;
         if (pair_end && !two) return false;                   // (interlaced pairs: a chunk would have to end on an even record)
         if (!m1.open(f1) || (two && !m2.open(f2))) return false;
@@ -563,29 +586,28 @@ struct GzDevPlan {
             chunks.push_back(k); total_reads += (size_t)k.n_reads;
             i1 = j1; i2 = j2;
         }
-        t_check = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t;
+        t_check = now_s() - t;
         return !chunks.empty();
     }
 };
 
 // Maps one library of plain FASTQ files.  f2 == nullptr: one file (single-end, or interlaced pairs when pair_end).
 // gzp: the library is BGZF-compressed and gzp holds its plan (DART_DEVICE_GZ): the batches are the plan's chunks, inflated and parsed on the device.
-// Returns 0, or the failing dg status (message in err).  SAM text goes to fd at *file_off (advanced).
-static int run_fast_library(const char *f1, const char *f2, bool pair_end, int threads, size_t batch_reads, const std::vector<dg_ctx *> &ctx, const dg_params &base_params,
-                            const std::vector<std::string> &names, bool unique_only, bool multi, bool silent, int fd, uint64_t *file_off,
-                            Counters &total, std::map<std::pair<int64_t, int64_t>, int> &sjmap, time_t t0, std::string &err, FastStats &st, SlotPool &pool,
-                            FastqIndex *pre = nullptr, GzDevPlan *gzp = nullptr)
+// pre: the caller's index of this library, if it made one beside dg_init (or inflated the .gz files whole).
+// Returns 0, or the failing dg status (message in err).  SAM text goes to job.sam_fd at job.sam_off (advanced).
+static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex *pre, GzDevPlan *gzp, FastStats &st, std::string &err)
 {
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const int T = std::max(1, threads);
+    const Config &c = job.cfg;
+    const bool pair_end = job.pair_end;
+    size_t batch_reads = c.batch_reads;
+    const int T = std::max(1, c.threads);
     // T is the budget of ALL stages (the GPU boxes grant a CPU quota, not cores: more runnable threads than the quota means the whole process is
     // throttled): the formatter takes what the writer (TWR threads), the assembler and the mapping threads leave.  DART_FMT_THREADS / DART_WRITE_THREADS override.
     // (ONE writer: pwrites to one file serialise on its inode lock, and two threads taking turns at it are slower than one that keeps it --
     //  write 0.78 s against 1.4-1.6 s per 16 M reads on tmpfs, profiles/r03/g_formatter_false_sharing.txt)
-    const int TWR = getenv("DART_WRITE_THREADS") ? std::max(1, atoi(getenv("DART_WRITE_THREADS"))) : 1;
-    const int TF = getenv("DART_FMT_THREADS") ? std::max(1, atoi(getenv("DART_FMT_THREADS"))) : std::max(1, T - TWR - 1);
-    const char *wm = getenv("DART_WRITE");
-    const bool use_mmap = wm && strcmp(wm, "mmap") == 0;          // default pwrite (measured on tmpfs: 5.1 GB/s against 3.2 GB/s through a shared mapping)
+    const int TWR = c.write_threads;
+    const int TF = c.fmt_threads ? c.fmt_threads : std::max(1, T - TWR - 1);
+    const bool use_mmap = c.write_mmap;
     FastqIndex own;                                   // (unless the caller has indexed this library already, beside dg_init)
     if (gzp) pre = &own;                              // (no record index: the host never sees the text)
     else {
@@ -647,9 +669,21 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
         if (f2) { mf = (k & 1) ? &m2 : &m1; return (k & 1) ? r2[k >> 1] : r1[k >> 1]; }
         mf = &m1; return r1[k];
     };
+    // read k as the formatter sees it: name, bases and qualities where they lie in the mapping, nothing copied
+    auto view_of = [&](size_t k) {
+        const MappedFile *mf; const FqRec &r = rec_of(k, mf);
+        const char *l0 = mf->p + r.off, *l1 = l0 + r.l0, *l3 = l1 + r.l1 + r.l2;
+        const int p1 = hdr_beg(l0, (int)r.l0), p2 = hdr_end(l0, (int)r.l0);
+        RView v;
+        v.h = l0 + p1; v.hl = p2 > p1 ? (uint32_t)(p2 - p1) : 0u;
+        v.s = l1; v.sl = r.l1 - 1;
+        v.q = l3; v.ql = std::min<uint32_t>(v.sl, r.l3);                 // qualities cut to the read length (GetData.cpp:118-121)
+        v.rc = pair_end && (k & 1);                                      // mate 2 is stored reverse-complemented (also in an unpaired tail)
+        return v;
+    };
     if (gzp) { n_total = gzp->total_reads; odd_from = n_total; st.gz_device = true; st.t_gz_check += gzp->t_check; }
     if (batch_reads & 1) batch_reads++;
-    const bool fq_device = gzp || (g_device_fastq && !explicit_order);      // (an entry without bases ends a chunk: the replayed order is not a byte range)
+    const bool fq_device = gzp || (c.device_fastq && !explicit_order);      // (an entry without bases ends a chunk: the replayed order is not a byte range)
     st.fq_device = fq_device;
     // the bytes of records [a, b) of a mapped file
     auto byte_range = [](const MappedFile &mf, const std::vector<FqRec> &v, size_t a, size_t b, const char *&p, size_t &n) {
@@ -657,13 +691,13 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
         p = mf.p + lo; n = hi - lo;
     };
     // slots + queues
-    pool.wait();
-    if (pool.slots.size() < ctx.size() + 2) pool.slots.resize(ctx.size() + 2);
-    std::vector<FastSlot> &slots = pool.slots;
+    job.pool.wait();
+    if (job.pool.slots.size() < job.ctx.size() + 2) job.pool.slots.resize(job.ctx.size() + 2);
+    std::vector<FastSlot> &slots = job.pool.slots;
     std::mutex mu; std::condition_variable cv;
     std::deque<FastSlot *> free_q, map_q; std::map<size_t, FastSlot *> fmt_q;
     for (auto &s : slots) free_q.push_back(&s);
-    bool asm_done = false, failed = false; size_t mappers_left = ctx.size();
+    bool asm_done = false, failed = false; size_t mappers_left = job.ctx.size();
     int fail_rc = 0;
 
     std::thread assembler([&]() {
@@ -671,11 +705,11 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
         for (size_t ci = 0; gzp && ci < gzp->chunks.size(); ci++) {      // DART_DEVICE_GZ: a batch is a chunk of the plan
             FastSlot *s;
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !free_q.empty() || failed; }); if (failed) break; s = free_q.front(); free_q.pop_front(); }
-            const double ta = now();
+            const double ta = now_s();
             const int n = gzp->chunks[ci].n_reads;
             s->first = next; s->n = n; s->odd = 0; s->seqno = seqno++; s->rc = 0; s->fq_device = true; s->gz_chunk = (int)ci;
-            { const double tl = now(); const size_t z[3] = {0, 0, 0}; slot_reserve(*s, (size_t)n, 0, z); st.t_alloc += now() - tl; }
-            st.t_asm += now() - ta;
+            { const double tl = now_s(); const size_t z[3] = {0, 0, 0}; job.pool.reserve(*s, (size_t)n, 0, z); st.t_alloc += now_s() - tl; }
+            st.t_asm += now_s() - ta;
             next += (size_t)n;
             { std::lock_guard<std::mutex> lk(mu); map_q.push_back(s); }
             cv.notify_all();
@@ -683,7 +717,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
         while (!gzp && next < n_total) {
             FastSlot *s;
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !free_q.empty() || failed; }); if (failed) break; s = free_q.front(); free_q.pop_front(); }
-            const double ta = now();
+            const double ta = now_s();
             // a batch ends at the start of the unpaired tail, which is a batch of its own
             size_t end = std::min(n_total, next + batch_reads);
             int odd = 0;
@@ -699,26 +733,17 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 else byte_range(m1, r1, next, end, s->fq1, s->fq_n1);
                 if (s->fq_n1 >= 0xFFFFFF00ull || s->fq_n2 >= 0xFFFFFF00ull) { s->rc = DG_ERR_ARG; s->err = "a batch's FASTQ text exceeds 32-bit offsets: lower DART_BATCH"; }
                 else {
-                    { const double tl = now(); const size_t z[3] = {0, 0, 0}; slot_reserve(*s, (size_t)n, 0, z); st.t_alloc += now() - tl; }
-                    if (!g_device_sam && !g_device_bam) {
+                    { const double tl = now_s(); const size_t z[3] = {0, 0, 0}; job.pool.reserve(*s, (size_t)n, 0, z); st.t_alloc += now_s() - tl; }
+                    if (!c.device_sam && !c.device_bam) {
                         s->view.resize(n);
                         const int TA = std::max(1, T / 8);
                         parallel_for(TA, [&](int tid) {
                             const int lo = (int)((long long)n * tid / TA), hi = (int)((long long)n * (tid + 1) / TA);
-                            for (int k = lo; k < hi; k++) {
-                                const MappedFile *mf; const FqRec &r = rec_of(next + k, mf);
-                                const char *l0 = mf->p + r.off, *l1 = l0 + r.l0, *l3 = l1 + r.l1 + r.l2;
-                                const int p1 = hdr_beg_f(l0, (int)r.l0), p2 = hdr_end_f(l0, (int)r.l0);
-                                RView &v = s->view[k];
-                                v.h = l0 + p1; v.hl = p2 > p1 ? (uint32_t)(p2 - p1) : 0u;
-                                v.s = l1; v.sl = r.l1 - 1;
-                                v.q = l3; v.ql = std::min<uint32_t>(v.sl, r.l3);
-                                v.rc = pair_end && ((next + k) & 1);
-                            }
+                            for (int k = lo; k < hi; k++) s->view[k] = view_of(next + k);
                         });
                     }
                 }
-                st.t_asm += now() - ta;
+                st.t_asm += now_s() - ta;
                 next = end;
                 { std::lock_guard<std::mutex> lk(mu); map_q.push_back(s); }
                 cv.notify_all();
@@ -737,26 +762,19 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             s->soff[n] = (uint32_t)bases;
             if (too_long || bases > 0xFFFFFF00ull) { s->rc = DG_ERR_ARG; s->err = "read longer than DG_MAX_RLEN"; }
             else {
-                { const double tl = now(); const size_t z[3] = {0, 0, 0}; slot_reserve(*s, (size_t)n, bases, z); st.t_alloc += now() - tl; }
+                { const double tl = now_s(); const size_t z[3] = {0, 0, 0}; job.pool.reserve(*s, (size_t)n, bases, z); st.t_alloc += now_s() - tl; }
                 const int TA = std::max(1, T / 8);              // (copying bases is a tenth of the formatter's work; T is the budget of ALL stages)
                 parallel_for(TA, [&](int tid) {
                     const int lo = (int)((long long)n * tid / TA), hi = (int)((long long)n * (tid + 1) / TA);
                     for (int k = lo; k < hi; k++) {
-                        const MappedFile *mf; const FqRec &r = rec_of(next + k, mf);
-                        const char *l0 = mf->p + r.off, *l1 = l0 + r.l0, *l3 = l1 + r.l1 + r.l2;
-                        const int p1 = hdr_beg_f(l0, (int)r.l0), p2 = hdr_end_f(l0, (int)r.l0);
-                        RView &v = s->view[k];
-                        v.h = l0 + p1; v.hl = p2 > p1 ? (uint32_t)(p2 - p1) : 0u;
-                        v.s = l1; v.sl = r.l1 - 1;
-                        v.q = l3; v.ql = std::min<uint32_t>(v.sl, r.l3);                 // qualities cut to the read length (GetData.cpp:118-121)
-                        v.rc = pair_end && ((next + k) & 1);                             // mate 2 is stored reverse-complemented (also in an unpaired tail)
+                        const RView &v = s->view[k] = view_of(next + k);
                         char *dst = s->seq + s->soff[k];
                         if (v.rc) { for (uint32_t i = 0; i < v.sl; i++) dst[i] = comp_base_f(v.s[v.sl - 1 - i]); }
                         else memcpy(dst, v.s, v.sl);
                     }
                 });
             }
-            st.t_asm += now() - ta;
+            st.t_asm += now_s() - ta;
             next = end;
             { std::lock_guard<std::mutex> lk(mu); map_q.push_back(s); }
             cv.notify_all();
@@ -766,99 +784,101 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
     });
 
     std::vector<std::thread> mappers;
-    for (size_t w = 0; w < ctx.size(); w++) mappers.emplace_back([&, w]() {
+    for (size_t w = 0; w < job.ctx.size(); w++) mappers.emplace_back([&, w]() {
         while (true) {
             FastSlot *s;
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !map_q.empty() || asm_done || failed; }); if (failed || map_q.empty()) break; s = map_q.front(); map_q.pop_front(); }
-            const double tm = now();
+            const double tm = now_s();
             double t_fq = 0, t_gz_wait = 0; float fq_ms = 0.f;
             if (!s->rc && s->fq_device) {
                 // upload the text (the device cuts it into the batch) -> run -> download
                 const int n = s->n;
-                dg_params p = base_params; p.paired = (pair_end && !s->odd) ? 1 : 0;
-                dg_set_params(ctx[w], &p);
+                dg_params p = c.p; p.paired = (pair_end && !s->odd) ? 1 : 0;
+                dg_set_params(job.ctx[w], &p);
                 dg_fastq_text ft; ft.text1 = s->fq1; ft.n1 = s->fq_n1; ft.text2 = s->fq2; ft.n2 = s->fq_n2; ft.rc_odd_reads = pair_end ? 1 : 0; ft.max_reads = n;
                 int got = 0;
-                double tu = now();
+                double tu = now_s();
                 int rc;
                 if (s->gz_chunk >= 0) {
                     // the uploads take turns: this chunk's heads are the tails of the one before
                     std::unique_lock<std::mutex> lk(gzp->mu);
                     gzp->cv.wait(lk, [&]() { return gzp->turn == (size_t)s->gz_chunk; });
-                    t_gz_wait = now() - tu; tu = now();
+                    t_gz_wait = now_s() - tu; tu = now_s();
                     uint64_t unlike = 0;
-                    rc = GzDevPlan::upload(ctx[w], *gzp, gzp->chunks[s->gz_chunk], gzp->tail1, gzp->tail2, pair_end, n, 0u, &got, &unlike);
+                    rc = GzDevPlan::upload(job.ctx[w], *gzp, gzp->chunks[s->gz_chunk], gzp->tail1, gzp->tail2, pair_end, n, 0u, &got, &unlike);
                     gzp->turn++;
                     lk.unlock(); gzp->cv.notify_all();
-                } else rc = dg_batch_upload_fastq(ctx[w], &ft, &got);
-                t_fq = now() - tu;
-                (void)dg_batch_fastq_device_ms(ctx[w], &fq_ms);
+                } else rc = dg_batch_upload_fastq(job.ctx[w], &ft, &got);
+                t_fq = now_s() - tu;
+                (void)dg_batch_fastq_device_ms(job.ctx[w], &fq_ms);
                 if (!rc && got != n) { s->rc = DG_ERR_INTERNAL; s->err = "the device parser found " + std::to_string(got) + " reads in a batch of " + std::to_string(n); }
-                else if (rc) { s->rc = rc; s->err = dg_last_error(ctx[w]); }
+                else if (rc) { s->rc = rc; s->err = dg_last_error(job.ctx[w]); }
                 else {
-                    rc = dg_batch_run(ctx[w], s->used);
+                    rc = dg_batch_run(job.ctx[w], s->used);
                     if (!rc && (s->used[0] > s->caps[0] || s->used[1] > s->caps[1] || s->used[2] > s->caps[2])) {
                         const size_t need[3] = { s->used[0] + s->used[0] / 8 + 1024, s->used[1] + s->used[1] / 8 + 1024, s->used[2] + s->used[2] / 8 + 1024 };
-                        slot_reserve(*s, (size_t)n, 0, need);
+                        job.pool.reserve(*s, (size_t)n, 0, need);
                     }
-                    if (!rc && g_device_sj) rc = sj_accumulate(ctx[w]);
-                    if (!rc && g_gene_counts) rc = gene_accumulate(ctx[w], (pair_end && !s->odd) ? n : 0);
-                    if (!rc) rc = dg_batch_download(ctx[w], s->ro, s->po, s->cig, g_device_sj ? nullptr : s->sj, s->caps);
-                    s->rc = rc; if (rc) s->err = dg_last_error(ctx[w]);
+                    if (!rc && c.device_sj) rc = sj_accumulate(job, job.ctx[w]);
+                    if (!rc && c.gene_gtf) rc = gene_accumulate(job, job.ctx[w], (pair_end && !s->odd) ? n : 0);
+                    if (!rc) rc = dg_batch_download(job.ctx[w], s->ro, s->po, s->cig, c.device_sj ? nullptr : s->sj, s->caps);
+                    s->rc = rc; if (rc) s->err = dg_last_error(job.ctx[w]);
                 }
             } else
             if (!s->rc) {
                 const int n = s->n;
                 for (int attempt = 0; attempt < 2; attempt++) {
-                    if (attempt) { const size_t need[3] = { s->used[0] * 2 + 1024, s->used[1] * 2 + 1024, s->used[2] * 2 + 1024 }; slot_reserve(*s, (size_t)n, 0, need); }
-                    dg_params p = base_params; p.paired = (pair_end && !s->odd) ? 1 : 0;
-                    dg_set_params(ctx[w], &p);
-                    int rc = dg_map_batch(ctx[w], n, s->soff.data(), s->rl.data(), s->seq, s->ro, s->po, s->cig, g_device_sj ? nullptr : s->sj, s->caps, s->used);
+                    if (attempt) { const size_t need[3] = { s->used[0] * 2 + 1024, s->used[1] * 2 + 1024, s->used[2] * 2 + 1024 }; job.pool.reserve(*s, (size_t)n, 0, need); }
+                    dg_params p = c.p; p.paired = (pair_end && !s->odd) ? 1 : 0;
+                    dg_set_params(job.ctx[w], &p);
+                    int rc = dg_map_batch(job.ctx[w], n, s->soff.data(), s->rl.data(), s->seq, s->ro, s->po, s->cig, c.device_sj ? nullptr : s->sj, s->caps, s->used);
                     if (rc == DG_ERR_CAPACITY && attempt == 0) continue;      // `used` holds the need
-                    if (!rc && g_device_sj) rc = sj_accumulate(ctx[w]);       // (a batch that ran short of capacity is mapped again as a new batch and was not counted)
-                    if (!rc && g_gene_counts) rc = gene_accumulate(ctx[w], (pair_end && !s->odd) ? n : 0);
-                    s->rc = rc; if (rc) s->err = dg_last_error(ctx[w]);
+                    if (!rc && c.device_sj) rc = sj_accumulate(job, job.ctx[w]);       // (a batch that ran short of capacity is mapped again as a new batch and was not counted)
+                    if (!rc && c.gene_gtf) rc = gene_accumulate(job, job.ctx[w], (pair_end && !s->odd) ? n : 0);
+                    s->rc = rc; if (rc) s->err = dg_last_error(job.ctx[w]);
                     break;
                 }
             }
             double t_gather = 0, t_call = 0, t_dl = 0; float dev_ms = 0.f;
-            const bool dev_out = g_device_sam || g_device_bam;
+            const bool dev_out = c.device_sam || c.device_bam;
             // the device's formatter for this job: SAM text, or with DART_DEVICE_BAM the BGZF blocks of the BAM records (in == nullptr: the resident form)
             auto dev_format = [&](const dg_sam_text *in, int npm, size_t *nb) -> int {
-                const uint32_t fl = unique_only ? DG_SAM_UNIQUE_ONLY : 0u;
-                if (!g_device_bam) return in ? dg_batch_format_sam(ctx[w], in, fl, nb, s->dev_ct, &dev_ms) : dg_batch_format_sam_resident(ctx[w], npm, fl, nb, s->dev_ct, &dev_ms);
+                const uint32_t fl = c.unique ? DG_SAM_UNIQUE_ONLY : 0u;
+                if (!c.device_bam) return in ? dg_batch_format_sam(job.ctx[w], in, fl, nb, s->dev_ct, &dev_ms) : dg_batch_format_sam_resident(job.ctx[w], npm, fl, nb, s->dev_ct, &dev_ms);
                 uint64_t ct[5] = {0, 0, 0, 0, 0}; size_t raw = 0;
-                const uint32_t bfl = fl | (g_sort_bam ? DG_BAM_RAW : g_bgzf_dynamic ? DG_BAM_DYNAMIC : 0u);
-                int rc = in ? dg_batch_format_bam(ctx[w], in, bfl, nb, &raw, ct, &dev_ms) : dg_batch_format_bam_resident(ctx[w], npm, bfl, nb, &raw, ct, &dev_ms);
+                const uint32_t bfl = fl | (c.sort_bam ? DG_BAM_RAW : c.bgzf_dynamic ? DG_BAM_DYNAMIC : 0u);
+                int rc = in ? dg_batch_format_bam(job.ctx[w], in, bfl, nb, &raw, ct, &dev_ms) : dg_batch_format_bam_resident(job.ctx[w], npm, bfl, nb, &raw, ct, &dev_ms);
                 for (int i = 0; i < 3; i++) s->dev_ct[i] = ct[i];
                 s->bam_rr[0] = ct[3]; s->bam_rr[1] = ct[4];
-                if (!rc && g_sort_bam) {
-                    const unsigned long long t = sj_now_ns();
-                    rc = dg_batch_accumulate_bam(ctx[w], (uint32_t)(g_sort_ordinal_base + s->seqno), nullptr, nullptr);
-                    g_sort_acc_ns += sj_now_ns() - t;
+                if (!rc && c.sort_bam) {
+                    const unsigned long long t = now_ns();
+                    rc = dg_batch_accumulate_bam(job.ctx[w], (uint32_t)(job.sort_ordinal_base + s->seqno), nullptr, nullptr);
+                    job.sort_acc_ns += now_ns() - t;
                     *nb = 0;                                  // the records stay in HBM: the slot carries the counters alone
                 }
                 return rc;
             };
-            auto dev_download = [&]() -> int { return g_sort_bam ? 0 : g_device_bam ? dg_batch_download_bam(ctx[w], s->text, s->text_cap) : dg_batch_download_sam(ctx[w], s->text, s->text_cap); };
-            if (!s->rc && dev_out && s->fq_device) {
-                // names and qualities are in HBM already, in stored order: nothing to gather
+            auto dev_download = [&]() -> int { return c.sort_bam ? 0 : c.device_bam ? dg_batch_download_bam(job.ctx[w], s->text, s->text_cap) : dg_batch_download_sam(job.ctx[w], s->text, s->text_cap); };
+            // format on the device, then the text (or the blocks) into the slot
+            auto dev_text = [&](const dg_sam_text *in, int npm) {
                 size_t nb = 0;
-                const double tc = now();
-                int rc = dev_format(nullptr, (pair_end && !s->odd) ? s->n : 0, &nb);
-                t_call = now() - tc;
+                const double tc = now_s();
+                int rc = dev_format(in, npm, &nb);
+                t_call = now_s() - tc;
                 if (!rc) {
-                    const double td = now();
-                    if (nb > s->text_cap) { arena_free(s->text); s->text_cap = nb + nb / 8 + 4096; s->text = (char *)arena_alloc(s->text_cap); }
+                    const double td = now_s();
+                    job.pool.reserve_text(*s, nb);
                     rc = dev_download();
                     s->text_n = nb;
-                    t_dl = now() - td;
+                    t_dl = now_s() - td;
                 }
-                if (rc) { s->rc = rc; s->err = dg_last_error(ctx[w]); }
-            } else
+                if (rc) { s->rc = rc; s->err = dg_last_error(job.ctx[w]); }
+            };
+            if (!s->rc && dev_out && s->fq_device) dev_text(nullptr, (pair_end && !s->odd) ? s->n : 0);      // names and qualities are in HBM already, in stored order: nothing to gather
+            else
             if (!s->rc && dev_out) {
                 // the batch's names and qualities, flat, mate 2's qualities in stored order (reversed); then the text from the device
-                const double tg = now();
+                const double tg = now_s();
                 const int n = s->n;
                 s->hoff.resize((size_t)n + 1); s->qoff.resize((size_t)n + 1);
                 uint32_t ho = 0, qo = 0; bool fits = true;
@@ -866,7 +886,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 s->hoff[n] = ho; s->qoff[n] = qo;
                 if (!fits) { s->rc = DG_ERR_ARG; s->err = "names and qualities of a batch exceed 32-bit offsets"; }
                 else {
-                    if ((size_t)ho + qo + 64 > s->nq_cap) { arena_free(s->names_quals); s->nq_cap = ((size_t)ho + qo) * 9 / 8 + 4096; s->names_quals = (char *)arena_alloc(s->nq_cap); }
+                    if ((size_t)ho + qo + 64 > s->nq_cap) { job.pool.release(s->names_quals); s->nq_cap = ((size_t)ho + qo) * 9 / 8 + 4096; s->names_quals = (char *)job.pool.alloc(s->nq_cap); }
                     char *hb = s->names_quals, *qb = s->names_quals + ho;
                     const int TG = std::max(1, T / 8);
                     parallel_for(TG, [&](int tid) {
@@ -877,23 +897,12 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                             if (v.rc) rev_copy(qb + s->qoff[k], v.q, v.ql); else memcpy(qb + s->qoff[k], v.q, v.ql);
                         }
                     });
-                    t_gather = now() - tg;
+                    t_gather = now_s() - tg;
                     dg_sam_text in; in.hdr_off = s->hoff.data(); in.hdr = hb; in.qual_off = s->qoff.data(); in.qual = qb; in.n_pair_mode = (pair_end && !s->odd) ? n : 0;
-                    size_t nb = 0;
-                    const double tc = now();
-                    int rc = dev_format(&in, in.n_pair_mode, &nb);
-                    t_call = now() - tc;
-                    if (!rc) {
-                        const double td = now();
-                        if (nb > s->text_cap) { arena_free(s->text); s->text_cap = nb + nb / 8 + 4096; s->text = (char *)arena_alloc(s->text_cap); }
-                        rc = dev_download();
-                        s->text_n = nb;
-                        t_dl = now() - td;
-                    }
-                    if (rc) { s->rc = rc; s->err = dg_last_error(ctx[w]); }
+                    dev_text(&in, in.n_pair_mode);
                 }
             }
-            { std::lock_guard<std::mutex> lk(mu); st.t_map += now() - tm - t_gather - t_call - t_dl - t_fq - t_gz_wait; st.t_gz_tail += t_gz_wait; st.t_fq_call += t_fq; st.t_fq_kernels += fq_ms * 1e-3; st.t_gather += t_gather; st.t_dev_call += t_call; st.t_dev_kernels += dev_ms * 1e-3; st.t_download += t_dl; st.n_batches++; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
+            { std::lock_guard<std::mutex> lk(mu); st.t_map += now_s() - tm - t_gather - t_call - t_dl - t_fq - t_gz_wait; st.t_gz_tail += t_gz_wait; st.t_fq_call += t_fq; st.t_fq_kernels += fq_ms * 1e-3; st.t_gather += t_gather; st.t_dev_call += t_call; st.t_dev_kernels += dev_ms * 1e-3; st.t_download += t_dl; st.n_batches++; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
             cv.notify_all();
         }
         { std::lock_guard<std::mutex> lk(mu); mappers_left--; }
@@ -912,20 +921,20 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
         while (true) {
             TextSet &ts = sets[cur];
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return ts.full || fmt_done || failed; }); if (!ts.full) break; }
-            const double tw = now();
+            const double tw = now_s();
             FastSlot *s = ts.slot;
             std::vector<size_t> offs(TF + 1, 0);
             for (int k = 0; k < TF; k++) offs[k + 1] = offs[k] + ts.pieces[k].second;
-            const uint64_t base = *file_off;
+            const uint64_t base = job.sam_off;
             char *win = nullptr; size_t win_len = 0; const uint64_t a0 = base & ~(uint64_t)4095;
-            if (use_mmap && !g_device_bam && offs[TF] && ftruncate(fd, (off_t)(base + offs[TF])) == 0) {      // copy into a shared mapping of the file's new part
+            if (use_mmap && !c.device_bam && offs[TF] && ftruncate(job.sam_fd, (off_t)(base + offs[TF])) == 0) {      // copy into a shared mapping of the file's new part
                 win_len = (size_t)(base + offs[TF] - a0);
-                void *m = mmap(nullptr, win_len, PROT_READ | PROT_WRITE, MAP_SHARED, fd, (off_t)a0);
+                void *m = mmap(nullptr, win_len, PROT_READ | PROT_WRITE, MAP_SHARED, job.sam_fd, (off_t)a0);
                 win = m == MAP_FAILED ? nullptr : (char *)m;
             }
             const int TW = win ? std::max(1, TF / 4) : TWR;     // writes to one file serialise in the kernel: more threads only burn the CPU share
             std::atomic<int> write_errno{0};                 // a full disk must not end as a holed SAM file and exit code 0
-            if (g_device_bam) { if (!g_bam_sink || !g_bam_sink(ts.pieces[0].first, ts.pieces[0].second, (long long)s->bam_rr[0], (long long)s->bam_rr[1])) write_errno = errno ? errno : EIO; }
+            if (c.device_bam) { if (!job.bam_sink || !job.bam_sink(ts.pieces[0].first, ts.pieces[0].second, (long long)s->bam_rr[0], (long long)s->bam_rr[1])) write_errno = errno ? errno : EIO; }
             else if (use_mmap && offs[TF] && !win) write_errno = errno ? errno : EIO;
             else parallel_for(TW, [&](int wt) {
                 for (int tid = wt; tid < TF; tid += TW) {
@@ -933,7 +942,7 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                     if (win) { memcpy(win + (base - a0) + offs[tid], piece, piece_n); continue; }
                     size_t done = 0;
                     while (done < piece_n) {
-                        const ssize_t w = pwrite(fd, piece + done, piece_n - done, (off_t)(base + offs[tid] + done));
+                        const ssize_t w = pwrite(job.sam_fd, piece + done, piece_n - done, (off_t)(base + offs[tid] + done));
                         if (w < 0 && errno == EINTR) continue;
                         if (w <= 0) { write_errno = w < 0 ? errno : ENOSPC; break; }
                         done += (size_t)w;
@@ -946,16 +955,10 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
                 cv.notify_all();
                 break;
             }
-            if (!g_device_bam) *file_off = base + offs[TF];
-            for (int k = 0; k < TF; k++) { total.unique += ts.cts[k].unique; total.unmapped += ts.cts[k].unmapped; total.paired += ts.cts[k].paired; }
-            total.total += s->n;
-            if (!g_device_sj) {
-                const unsigned long long tj = sj_now_ns();
-                for (size_t k = 0; k < s->used[2]; k++) sjmap[std::make_pair(s->sj[k].g1, s->sj[k].g2)]++;   // UpdateLocal/GlobalSJMap, Mapping.cpp:532-577
-                g_sj_map_ns += sj_now_ns() - tj; g_sj_tuples += s->used[2];
-            }
-            if (!silent) { fprintf(stdout, "\r%lld %s tags have been processed in %lld seconds...", total.total, pair_end ? "paired-end" : "singled-end", (long long)(time(NULL) - t0)); fflush(stdout); }
-            st.t_write += now() - tw;
+            if (!c.device_bam) job.sam_off = base + offs[TF];
+            for (int k = 0; k < TF; k++) { job.total.unique += ts.cts[k].unique; job.total.unmapped += ts.cts[k].unmapped; job.total.paired += ts.cts[k].paired; }
+            batch_written(job, s->n, s->sj, s->used[2]);
+            st.t_write += now_s() - tw;
             { std::lock_guard<std::mutex> lk(mu); ts.full = false; free_q.push_back(s); }
             cv.notify_all();
             cur ^= 1;
@@ -970,10 +973,10 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
           if (fmt_q.count(next_out)) { s = fmt_q[next_out]; fmt_q.erase(next_out); } else break; }
         TextSet &ts = sets[fill];
         { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !ts.full || failed; }); if (failed) break; }
-        const double tf = now();
+        const double tf = now_s();
         const int n = s->n, n_pair_mode = (pair_end && !s->odd) ? n : 0;
         ts.pieces.assign(TF, std::make_pair((const char *)nullptr, (size_t)0));
-        if (g_device_sam || g_device_bam) {                   // formatted on the device behind the mapping: the text (or the BGZF blocks) is in the slot
+        if (c.device_sam || c.device_bam) {                   // formatted on the device behind the mapping: the text (or the BGZF blocks) is in the slot
             for (int tid = 0; tid < TF; tid++) ts.cts[tid] = Counters();
             ts.pieces[0] = std::make_pair((const char *)s->text, s->text_n);
             ts.cts[0].unmapped = (long long)s->dev_ct[0]; ts.cts[0].unique = (long long)s->dev_ct[1]; ts.cts[0].paired = (long long)s->dev_ct[2];
@@ -981,10 +984,10 @@ static int run_fast_library(const char *f1, const char *f2, bool pair_end, int t
             parallel_for(TF, [&](int tid) {
                 int lo = (int)((long long)n * tid / TF) & ~1, hi = tid == TF - 1 ? n : ((int)((long long)n * (tid + 1) / TF) & ~1);
                 ts.bufs[tid].n = 0; ts.cts[tid] = Counters();
-                format_views(s->view.data(), lo, hi, n_pair_mode, s->ro, s->po, s->cig, names, unique_only, multi, true, ts.bufs[tid], ts.cts[tid]);
+                format_views(s->view.data(), lo, hi, n_pair_mode, s->ro, s->po, s->cig, job.names, c.unique, c.multi, true, ts.bufs[tid], ts.cts[tid]);
                 ts.pieces[tid] = std::make_pair((const char *)ts.bufs[tid].b, ts.bufs[tid].n);
             });
-            st.t_fmt += now() - tf;
+            st.t_fmt += now_s() - tf;
         }
         { std::lock_guard<std::mutex> lk(mu); ts.slot = s; ts.full = true; }
         cv.notify_all();
