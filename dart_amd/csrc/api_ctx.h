@@ -57,7 +57,7 @@ template <int N> struct EvSet : NoCopy {
     float ms(int i, int j) const { float v = 0.f; (void)hipEventElapsedTime(&v, e[i], e[j]); return v; }
 };
 
-// The buffers of one use of the radix sort's pass driver (rs_sort_passes, dg_api.hip): two key and two value buffers, which the stage sizes and fills itself (what they hold
+// The buffers of one use of the radix sort's pass driver (rs_sort_passes, dg_sort.h): two key and two value buffers, which the stage sizes and fills itself (what they hold
 // differs from stage to stage, and so does what the stage says when it cannot have them), and the passes' scratch, which ensure(n) sizes for n pairs.
 struct dg_ctx;
 struct SortBufs {

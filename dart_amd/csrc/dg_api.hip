@@ -206,61 +206,8 @@ static int fail(dg_ctx *c, int code, const char *what, hipError_t e)
 #define HIPCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) return fail(c, DG_ERR_HIP, #call, _e); } while (0)
 
 // ------------------------------------------------------------------------------------------
-// small utility kernels: exclusive scan in three phases (the index builder's sorter, dg_sort_pairs; the mapping path scans in single passes, dg_scan.h)
+// small utility kernels (the sums of the output stages are dg_wgscan.h, the three-launch scan and the sorter's driver dg_sort.h)
 // ------------------------------------------------------------------------------------------
-#define SCAN_TILE 2048
-__global__ void __launch_bounds__(256) k_scan_tiles(const uint32_t *in, uint32_t *out, uint32_t *tile_sums, uint32_t n)
-{
-    __shared__ uint32_t sh[256];
-    const uint32_t base = blockIdx.x * SCAN_TILE + threadIdx.x * 8;
-    uint32_t v[8], sum = 0;
-    for (int i = 0; i < 8; i++) { v[i] = base + i < n ? in[base + i] : 0; sum += v[i]; }
-    sh[threadIdx.x] = sum;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        uint32_t t = threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
-        __syncthreads();
-        sh[threadIdx.x] += t;
-        __syncthreads();
-    }
-    uint32_t run = sh[threadIdx.x] - sum;
-    for (int i = 0; i < 8; i++) { if (base + i < n) out[base + i] = run; run += v[i]; }
-    if (threadIdx.x == 255) tile_sums[blockIdx.x] = sh[255];
-}
-__global__ void __launch_bounds__(256) k_scan_top(uint32_t *tile_sums, uint32_t n_tiles, uint32_t *total_out, uint32_t *total_copy, uint32_t cap, int *err, int code)
-{
-    __shared__ uint32_t sh[256];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t b = 0; b < n_tiles; b += 256) {
-        const uint32_t i = b + threadIdx.x;
-        const uint32_t v = i < n_tiles ? tile_sums[i] : 0;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            uint32_t t = threadIdx.x >= o ? sh[threadIdx.x - o] : 0;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n_tiles) tile_sums[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += sh[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        *total_out = carry;
-        if (total_copy) *total_copy = carry;
-        if (err && carry > cap) atomicMax(err, code);          // the consumers of this scan return at once (DG_ABORT)
-    }
-}
-__global__ void __launch_bounds__(256) k_scan_add(uint32_t *out, const uint32_t *tile_sums, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] += tile_sums[i / SCAN_TILE];
-}
-
 // seeds per read -> where every read's seeds start (exclusive scan; seed_off[n] = total, flagged when it exceeds the capacity), the read
 // that owns the first seed of every 64-seed tile (k_locate's entry point) and the list of units with more seeds than a lane of k_pair
 // holds (k_chain_heavy's work list) -- ONE launch with a single-pass scan (dg_scan.h).  Round 2: three scan launches, k_tile_reads and
@@ -2119,7 +2066,7 @@ static int sam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr
         HIPCHK(hipEventRecord(c->sam.ev[0], c->stream));
         HIPCHK(hipMemsetAsync(c->sam.stat.d, 0, 4 * 8, c->stream));
         k_sam_len<<<n_tiles, SAM_LEN_THREADS, 0, c->stream>>>(b, c->sam.read_off.p, c->sam.qlen.p, c->sam.tile.p, c->sam.stat.d);
-        k_sam_top<<<1, 256, 0, c->stream>>>(c->sam.tile.p, n_tiles, c->sam.stat.d);
+        k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->sam.tile.p, n_tiles, (uint64_t *)c->sam.stat.d);
         k_sam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam.read_off.p, c->sam.tile.p, c->sam.stat.d, (unsigned long long)c->sam.text.cap, c->sam.text.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->sam.ev[1], c->stream));
@@ -2228,7 +2175,7 @@ static int bgzf_device(dg_ctx *c, const unsigned char *d_in, size_t n, bool dyna
     HIPCHK(hipEventRecord(c->bam.ev[0], c->stream));
     if (dynamic) k_bgzf_deflate_dyn<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bam.bgzf_slots.p, c->bam.bgzf_off.p, c->bam.bgzf_size.p, d_phases);
     else k_bgzf_deflate<<<(unsigned)blocks, BGZF_THREADS, 0, c->stream>>>(d_in, (unsigned long long)n, c->bam.bgzf_slots.p, c->bam.bgzf_off.p, c->bam.bgzf_size.p);
-    k_sam_top<<<1, 256, 0, c->stream>>>(c->bam.bgzf_off.p, (uint32_t)blocks, c->bam.stat.d + 6);
+    k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->bam.bgzf_off.p, (uint32_t)blocks, (uint64_t *)(c->bam.stat.d + 6));
     k_bgzf_copy<<<(unsigned)blocks, 256, 0, c->stream>>>(c->bam.bgzf_slots.p, c->bam.bgzf_off.p, c->bam.bgzf_size.p, c->bam.bgzf_out.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->bam.ev[1], c->stream));
@@ -2270,7 +2217,7 @@ static int bam_format_device(dg_ctx *c, const uint32_t *hdr_off, const char *hdr
         HIPCHK(hipEventRecord(c->bam.ev[0], c->stream));
         HIPCHK(hipMemsetAsync(c->bam.stat.d, 0, 8 * 8, c->stream));
         k_bam_len<<<n_tiles, SAM_LEN_THREADS, 0, c->stream>>>(b, c->sam.read_off.p, c->sam.qlen.p, c->sam.tile.p, c->bam.stat.d);
-        k_sam_top<<<1, 256, 0, c->stream>>>(c->sam.tile.p, n_tiles, c->bam.stat.d);
+        k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->sam.tile.p, n_tiles, (uint64_t *)c->bam.stat.d);
         k_bam_write<<<grid, 64, 0, c->stream>>>(b2, c->sam.read_off.p, c->sam.tile.p, c->bam.stat.d, (unsigned long long)(c->bam.rec.cap - 8), c->bam.rec.p);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->bam.ev[1], c->stream));
@@ -2575,28 +2522,6 @@ extern "C" int dg_sj_merge(dg_ctx *dst, dg_ctx *src)
     return DG_OK;
 }
 
-// The passes of the stable LSD radix sort (dg_sort.h) of n pairs by the low `bits` bits of the key, enqueued on stream s: the one driver of every sort the
-// library runs.  keys / vals: two buffers each; which: in = the pair that holds the input, out = the one that holds the result.
-// hist holds rs_hist_words(n) words (16 x tiles + 1), sums rs_sums_words(n) (one per SCAN_TILE of them + 1): the caller's scratch.
-static hipError_t rs_sort_passes(hipStream_t s, uint64_t *const keys[2], int64_t *const vals[2], uint32_t *hist, uint32_t *sums, uint32_t n, int bits, int &which)
-{
-    const uint32_t tiles = (n + RS_TILE - 1) / RS_TILE, m = 16u * tiles, scan_tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
-    for (int shift = 0; shift < bits; shift += 4) {
-        const int o = which ^ 1;
-        k_rs_hist<<<tiles, 256, 0, s>>>(keys[which], n, shift, tiles, hist);
-        k_scan_tiles<<<scan_tiles, 256, 0, s>>>(hist, hist, sums, m);
-        k_scan_top<<<1, 256, 0, s>>>(sums, scan_tiles, hist + m, nullptr, 0, nullptr, 0);
-        k_scan_add<<<(m + 255) / 256, 256, 0, s>>>(hist, sums, m);
-        k_rs_scatter<<<tiles, 256, 0, s>>>(keys[which], vals[which], keys[o], vals[o], n, shift, tiles, hist);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        which = o;
-    }
-    return hipSuccess;
-}
-static size_t rs_hist_words(uint32_t n) { return 16 * (size_t)((n + RS_TILE - 1) / RS_TILE) + 1; }
-static size_t rs_sums_words(uint32_t n) { return (rs_hist_words(n) - 1 + SCAN_TILE - 1) / SCAN_TILE + 1; }
-
 // the scratch of a sort of n pairs: the one place that sizes it
 inline hipError_t SortBufs::ensure(uint32_t n)
 {
@@ -2659,7 +2584,7 @@ extern "C" int dg_sj_finish(dg_ctx *c, uint32_t flags, size_t *n_entries, size_t
         }
         k_sj_entries<<<n_tiles, SJ_THREADS, 0, c->stream>>>(c->sj.tab, c->sj.sort.v[which].p, (uint32_t)n, pr, c->sj.entries.p, c->sj.line_off.p, c->sj.tile.p, c->sj.stat.d);
         if (text) {
-            k_sam_top<<<1, 256, 0, c->stream>>>(c->sj.tile.p, n_tiles, c->sj.stat.d + SJ_ST_BYTES);
+            k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->sj.tile.p, n_tiles, (uint64_t *)(c->sj.stat.d + SJ_ST_BYTES));
             k_sj_write<<<n_tiles, SJ_THREADS, 0, c->stream>>>(c->sj.entries.p, (uint32_t)n, pr, c->sj.line_off.p, c->sj.tile.p, c->sj.stat.d, (unsigned long long)c->sj.text.cap, c->sj.text.p);
         }
         HIPCHK(hipGetLastError());
@@ -2813,7 +2738,7 @@ extern "C" int dg_batch_accumulate_bam(dg_ctx *c, uint32_t ordinal, size_t *n_re
     BS_ENSURE(c->bs.cnt_off, (size_t)n, "the per-read counts"); BS_ENSURE(c->bs.tile_cnt, (size_t)n_tiles + 1, "the per-workgroup counts");
     HIPCHK(hipEventRecord(c->bs.ev[0], c->stream));
     k_bs_count<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bam.rec.p, c->sam.read_off.p, c->sam.tile.p, n, (unsigned long long)bytes, c->bs.cnt_off.p, c->bs.tile_cnt.p);
-    k_scan_top<<<1, 256, 0, c->stream>>>(c->bs.tile_cnt.p, n_tiles, (uint32_t *)(c->bs.stat.d + 1), nullptr, 0, nullptr, 0);
+    k_tiles_top<uint32_t><<<1, 256, 0, c->stream>>>(c->bs.tile_cnt.p, n_tiles, (uint32_t *)(c->bs.stat.d + 1));
     k_bs_emit<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bam.rec.p, c->sam.read_off.p, c->sam.tile.p, n, (unsigned long long)bytes, c->bs.cnt_off.p, c->bs.tile_cnt.p, c->ix.n_chr,
                                                      (unsigned long long)c->bs.n, (unsigned long long)(c->bs.n + n_rec), (unsigned long long)c->bs.rec_used, c->bs.key, c->bs.off);
     HIPCHK(hipGetLastError());
@@ -2925,7 +2850,7 @@ extern "C" int dg_bam_sort_finish(dg_ctx *c, size_t *n_records, size_t *n_raw, f
     // step three: lengths in sorted order, their scan (the places go where the sorter's other key buffer was), the gather
     uint64_t *dst_off = c->bs.sort.k[which ^ 1].p;
     k_bs_len<<<n_tiles, BS_THREADS, 0, c->stream>>>(c->bs.rec, c->bs.sort.v[which].p, (uint32_t)n, dst_off, c->bs.tile.p);
-    k_sam_top<<<1, 256, 0, c->stream>>>(c->bs.tile.p, n_tiles, c->bs.stat.d);
+    k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->bs.tile.p, n_tiles, (uint64_t *)c->bs.stat.d);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->bs.ev[3], c->stream));
     k_bs_gather<<<(unsigned)((n + BS_GATHER_WAVES - 1) / BS_GATHER_WAVES), 64 * BS_GATHER_WAVES, 0, c->stream>>>(c->bs.rec, c->bs.sort.v[which].p, dst_off, c->bs.tile.p, (uint32_t)n,
@@ -3059,7 +2984,7 @@ extern "C" int dg_bam_index_finish(dg_ctx *c, uint64_t first_block_offset, const
         k_bi_rec<<<tiles, BI_THREADS, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, c->bi.coff.p, (uint32_t)n_blocks, n_chr,
                                                       c->bi.key.p, c->bi.voff.p, c->bi.span.p, c->bi.ref.p, c->bi.stat.d);
         k_bi_heads<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi.key.p, (uint32_t)n, c->bi.tile_cnt.p);
-        k_scan_top<<<1, 256, 0, c->stream>>>(c->bi.tile_cnt.p, tiles, (uint32_t *)(c->bi.stat.d + BI_ST_CHUNKS), nullptr, 0, nullptr, 0);
+        k_tiles_top<uint32_t><<<1, 256, 0, c->stream>>>(c->bi.tile_cnt.p, tiles, (uint32_t *)(c->bi.stat.d + BI_ST_CHUNKS));
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->bi.ev[1], c->stream));
@@ -3100,7 +3025,7 @@ extern "C" int dg_bam_index_finish(dg_ctx *c, uint64_t first_block_offset, const
         k_bi_chunks<<<tiles, BI_THREADS, 0, c->stream>>>(c->bi.key.p, (uint32_t)n, c->bi.tile_cnt.p, (uint32_t)n_chunks, (uint32_t)n_placed, c->bi.sort.k[0].p, c->bi.sort.v[0].p, c->bi.chead.p);
         { const int rc = c->bi.sort.sort(c, (uint32_t)n_chunks, bi_key_bits(n_chr), which); if (rc) return rc; }
         k_bi_merge_scan<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi.sort.k[which].p, c->bi.sort.v[which].p, c->bi.chead.p, c->bi.voff.p, (uint32_t)n_chunks, c->bi.flag.p, c->bi.excl.p, c->bi.ctile.p);
-        k_sam_top<<<1, 256, 0, c->stream>>>(c->bi.ctile.p, ctiles, c->bi.stat.d + BI_ST_MERGED);
+        k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->bi.ctile.p, ctiles, (uint64_t *)(c->bi.stat.d + BI_ST_MERGED));
         k_bi_merge_emit<<<ctiles, BI_THREADS, 0, c->stream>>>(c->bi.sort.k[which].p, c->bi.flag.p, c->bi.excl.p, c->bi.ctile.p, (uint32_t)n_chunks, n_chr, c->bi.stat.d, c->bi.mhead.p, c->bi.mbin.p,
                                                                c->bi.binq.p, c->bi.ref_q.p, c->bi.ref_b.p);
     } else {
@@ -3444,7 +3369,7 @@ extern "C" int dg_bam_coverage_finish(dg_ctx *c, uint32_t flags, uint32_t exclud
     HIPCHK(hipEventRecord(c->cv.ev[4], c->stream));
     const uint64_t *skey = c->cv.sort.k[which].p;
     k_cv_depth<<<etiles, CV_THREADS, 0, c->stream>>>(c->cv.sort.v[which].p, n_ev, c->cv.incl.p, c->cv.dep_tile.p);
-    k_scan_top<<<1, 256, 0, c->stream>>>(c->cv.dep_tile.p, etiles, (uint32_t *)(c->cv.stat.d + CV_ST_DEPTH_END), nullptr, 0, nullptr, 0);
+    k_tiles_top<uint32_t><<<1, 256, 0, c->stream>>>(c->cv.dep_tile.p, etiles, (uint32_t *)(c->cv.stat.d + CV_ST_DEPTH_END));
     k_cv_tails<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv.incl.p, c->cv.dep_tile.p, n_ev, c->cv.tile_last.p);
     k_cv_tails_top<<<1, CV_THREADS, 0, c->stream>>>(c->cv.tile_last.p, etiles, c->cv.tile_prev.p);
     k_cv_flag<<<etiles, CV_THREADS, 0, c->stream>>>(skey, c->cv.incl.p, c->cv.dep_tile.p, c->cv.tile_prev.p, n_ev, c->cv.mark.p, c->cv.cnt_tile.p, c->cv.part.p);

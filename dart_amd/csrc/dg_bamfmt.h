@@ -5,7 +5,7 @@
 // (names without tab or newline and the index's chromosome names -- distinct, not empty, neither "*" nor "=" -- as this program prints them):
 //   k_bam_len     lane = read: the bytes of all its records, the SAM formatter's three counters, records written and lines refused; every
 //                 workgroup leaves the exclusive scan of its 256 lengths and their sum
-//   k_sam_top     (dg_samfmt.h) one workgroup: the scan of the workgroup sums, the total
+//   k_tiles_top   (dg_wgscan.h) one workgroup: the scan of the workgroup sums, the total
 //   k_bam_write   wave = read: lane i on byte i of the name, the packed bases and the qualities, lane c on CIGAR op c; lane 0 composes the 36
 //                 fixed bytes and the tags in LDS, the wave stores them
 // Every byte's place follows from the scanned lengths alone, so the array is the same whatever the grid.
@@ -151,32 +151,26 @@ SAM_HD uint64_t bam_read_records(const SamBatch &b, int k, unsigned char *out)
 // ------------------------------------------------------------------------------------------
 // the kernels
 // ------------------------------------------------------------------------------------------
-// stat[0] total bytes (k_sam_top), stat[1..3] the SAM formatter's counters, stat[4] records written, stat[5] lines refused
+// stat[0] total bytes (k_tiles_top), stat[1..3] the SAM formatter's counters, stat[4] records written, stat[5] lines refused
 __global__ void __launch_bounds__(SAM_LEN_THREADS)
 k_bam_len(const SamBatch b, uint64_t *__restrict__ read_off, uint32_t *__restrict__ qlen_out, uint64_t *__restrict__ tile_sum, unsigned long long *__restrict__ stat)
 {
-    __shared__ uint64_t s_scan[SAM_LEN_THREADS];
+    __shared__ uint64_t s_wave[SAM_LEN_THREADS / 64];
     __shared__ uint32_t s_ct[5];
     const int k = (int)(blockIdx.x * SAM_LEN_THREADS + threadIdx.x);
     if (threadIdx.x < 5) s_ct[threadIdx.x] = 0;
     uint32_t ct[3] = {0, 0, 0}, rr[2] = {0, 0};
     uint32_t ql = 0;
     const uint64_t len = k < b.n_reads ? bam_read_len(b, k, ct, rr, &ql) : 0ull;
-    s_scan[threadIdx.x] = len;
-    __syncthreads();
-    for (int o = 1; o < SAM_LEN_THREADS; o <<= 1) {
-        const uint64_t t = (int)threadIdx.x >= o ? s_scan[threadIdx.x - o] : 0ull;
-        __syncthreads();
-        s_scan[threadIdx.x] += t;
-        __syncthreads();
-    }
-    if (k < b.n_reads) { read_off[k] = s_scan[threadIdx.x] - len; qlen_out[k] = ql; }
+    uint64_t all;
+    const uint64_t ex = d_wg_exclusive<uint64_t>(len, all, s_wave);
+    if (k < b.n_reads) { read_off[k] = ex; qlen_out[k] = ql; }
 #pragma unroll
     for (int i = 0; i < 3; i++) if (ct[i]) atomicAdd(&s_ct[i], ct[i]);
 #pragma unroll
     for (int i = 0; i < 2; i++) if (rr[i]) atomicAdd(&s_ct[3 + i], rr[i]);
     __syncthreads();
-    if (threadIdx.x == SAM_LEN_THREADS - 1) tile_sum[blockIdx.x] = s_scan[SAM_LEN_THREADS - 1];
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
     if (threadIdx.x < 5 && s_ct[threadIdx.x]) atomicAdd(&stat[1 + threadIdx.x], (unsigned long long)s_ct[threadIdx.x]);
 }
 

@@ -43,13 +43,13 @@
 //   k_bi_rec         lane = sorted record: the field reads and the CIGAR walk (never past the record's block_size); leaves the key refID << 16 | bin (all ones
 //                    for an unplaced record), voff of the record's start, its window span and mapped bit; per reference (wave reduction, then one global
 //                    atomic per wave): the number of windows, the mapped and unmapped counts, the first and last record; the first record that is out of range
-//   k_bi_heads       lane = record: head flag where (refID, bin) differs from the previous placed record; the workgroup's count        (k_scan_top)
+//   k_bi_heads       lane = record: head flag where (refID, bin) differs from the previous placed record; the workgroup's count        (k_tiles_top)
 //   -- the one mid-way wait: the per-reference values, the chunk count and the error word go to the host, which sizes the linear index and the output --
 //   k_bi_lin         lane = record: 64-bit atomicMin of voff(start) into its windows (an array of all ones; the minimum makes the order of the atomics irrelevant),
 //                    but not into a window the mapped record in front covers too: that one, or one further in front, holds the smaller offset
 //   k_bi_chunks      lane = record: the heads compacted, in file order: (key, chunk number) pairs and each chunk's first record
 //   (sort)           one stable radix sort of the chunks by refID << 16 | bin (rs_sort_passes of dg_sort.h; 16 + bs_chr_bits(n_chr) key bits)
-//   k_bi_merge_scan  lane = sorted chunk: the neighbour merge test and the bin head test; workgroup scan of both counts in one 64-bit word    (k_sam_top)
+//   k_bi_merge_scan  lane = sorted chunk: the neighbour merge test and the bin head test; workgroup scan of both counts in one 64-bit word    (k_tiles_top)
 //   k_bi_merge_emit  lane = sorted chunk: merged chunk q -> its first sorted chunk and its bin; bin b -> its first merged chunk; reference t -> its first bin and chunk
 //   k_bi_refs        one workgroup: every reference's bytes, their scan = its byte offset; magic, n_ref, n_no_coor, the total
 //   k_bi_write_chunks lane = merged chunk: its 16 bytes; a bin's first chunk writes the bin's 8 bytes too
@@ -59,9 +59,11 @@
 #ifndef DG_BAMIDX_H
 #define DG_BAMIDX_H
 #include "dg_bamsort.h"
+#include "dg_wgscan.h"
 
 #define BI_HD __host__ __device__ __forceinline__
 #define BI_THREADS 256               // records per workgroup of k_bi_rec (dg_bam_index_granules [0])
+static_assert(BI_THREADS == WG_THREADS, "the kernels here scan with d_wg_exclusive");
 #define BI_BLOCK 0xff00ull           // input bytes per BGZF block (dg_bgzf.h: BGZF_BLOCK)
 #define BI_MAX_END (1ll << 29)       // the largest end a BAI holds
 #define BI_PSEUDO_BIN 37450u
@@ -168,10 +170,9 @@ k_bi_coff(const uint32_t *__restrict__ sizes, uint32_t n_blocks, unsigned long l
         const uint32_t k = b0 + threadIdx.x;
         const uint64_t mine = k < n_blocks ? (uint64_t)sizes[k] : 0ull;
         uint64_t all;
-        const uint64_t ex = bs_block_exclusive(mine, &all, s_wave);
+        const uint64_t ex = d_wg_exclusive(mine, all, s_wave);
         if (k < n_blocks) coff[k] = carry + ex;
         carry += all;
-        __syncthreads();
     }
     if (threadIdx.x == 0) { coff[n_blocks] = carry; stat[BI_ST_COFF_END] = carry; }
 }
@@ -237,7 +238,7 @@ k_bi_heads(const uint64_t *__restrict__ key, uint32_t n, uint32_t *__restrict__ 
 {
     __shared__ uint32_t s_wave[BI_THREADS / 64];
     uint32_t all;
-    (void)bs_block_exclusive(bi_head_flag(key, blockIdx.x * BI_THREADS + threadIdx.x, n), &all, s_wave);
+    (void)d_wg_exclusive(bi_head_flag(key, blockIdx.x * BI_THREADS + threadIdx.x, n), all, s_wave);
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = all;
 }
 
@@ -272,7 +273,7 @@ k_bi_chunks(const uint64_t *__restrict__ key, uint32_t n, const uint32_t *__rest
     __shared__ uint32_t s_wave[BI_THREADS / 64];
     const uint32_t i = blockIdx.x * BI_THREADS + threadIdx.x, h = bi_head_flag(key, i, n);
     uint32_t all;
-    const uint32_t c = tile_base[blockIdx.x] + bs_block_exclusive(h, &all, s_wave);
+    const uint32_t c = tile_base[blockIdx.x] + d_wg_exclusive(h, all, s_wave);
     if (h && c < n_chunks) { ckey[c] = key[i]; cval[c] = (int64_t)c; chead[c] = i; }
     if (i == 0) chead[n_chunks] = n_placed;
 }
@@ -295,7 +296,7 @@ k_bi_merge_scan(const uint64_t *__restrict__ skey, const int64_t *__restrict__ s
         f = (merged ? 0u : 1u) | (bin_head ? 2u : 0u);
     }
     uint64_t all;
-    const uint64_t ex = bs_block_exclusive((uint64_t)(f & 1u) | (uint64_t)(f >> 1) << 32, &all, s_wave);
+    const uint64_t ex = d_wg_exclusive((uint64_t)(f & 1u) | (uint64_t)(f >> 1) << 32, all, s_wave);
     if (j < n_chunks) { flag[j] = (unsigned char)f; excl[j] = ex; }
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
 }
@@ -333,10 +334,9 @@ k_bi_refs(int n_chr, const unsigned long long *__restrict__ ref, const uint32_t 
         uint64_t mine = 0;
         if (t < n_chr) mine = bi_ref_bytes(ref_b[t + 1] - ref_b[t], ref_q[t + 1] - ref_q[t], ref[n_chr + t] + ref[2 * (size_t)n_chr + t] > 0, ref[t]);
         uint64_t all;
-        const uint64_t ex = bs_block_exclusive(mine, &all, s_wave);
+        const uint64_t ex = d_wg_exclusive(mine, all, s_wave);
         if (t < n_chr) ref_at[t] = carry + ex;
         carry += all;
-        __syncthreads();
     }
     if (threadIdx.x == 0) {
         ref_at[n_chr] = carry;

@@ -12,7 +12,7 @@
 //
 //   k_bs_count   lane = read: walks the block_size fields inside the read's byte range of the batch's record array (k_bam_len's scanned offsets) and counts
 //                its records (0 to several: a refused line left none); every workgroup leaves the exclusive scan of its 256 counts and their sum
-//   (scan)       k_scan_top over the workgroup sums
+//   (scan)       k_tiles_top over the workgroup sums
 //   k_bs_emit    lane = read: the same walk; record i of the batch gets its key and its offset in the store
 //   k_bs_shift   lane = record: offsets of another context's store, moved behind this one's bytes (dg_bam_sort_merge)
 //   k_bs_len     lane = sorted record: its bytes (block_size + 4); the workgroup's exclusive scan and sum (64 bit)
@@ -25,6 +25,7 @@
 #define DG_BAMSORT_H
 #include "dg_bamfmt.h"
 #include "dg_sort.h"
+#include "dg_wgscan.h"
 #include <algorithm>
 
 #define BS_HD __host__ __device__ __forceinline__
@@ -32,6 +33,7 @@
 #define BS_MIN_BYTES 4096        // the smallest store (dg_bam_sort_granules [2])
 #define BS_GATHER_WAVES 4        // records per workgroup of k_bs_gather
 static_assert(BS_THREADS == SAM_LEN_THREADS, "k_bs_count reads k_bam_len's per-workgroup offsets");
+static_assert(BS_THREADS == WG_THREADS, "k_bs_count and k_bs_len scan with d_wg_exclusive");
 
 BS_HD uint32_t bs_le32(const unsigned char *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 // bits that hold tid' (0 .. n_chr)
@@ -131,21 +133,6 @@ inline void bs_order_segments(const BsSeg *segs, size_t n, uint32_t *order)
 // ------------------------------------------------------------------------------------------
 // the kernels
 // ------------------------------------------------------------------------------------------
-// exclusive scan over the workgroup's 256 lanes (wave scans, the four wave sums through LDS); *total = the workgroup's sum in every lane
-template <class T>
-__device__ __forceinline__ T bs_block_exclusive(T mine, T *total, T *s_wave)
-{
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    T incl = mine;
-    for (int o = 1; o < 64; o <<= 1) { const T up = __shfl_up(incl, o, 64); if (lane >= (uint32_t)o) incl += up; }
-    if (lane == 63u) s_wave[wv] = incl;
-    __syncthreads();
-    T before = 0, all = 0;
-    for (uint32_t w = 0; w < BS_THREADS / 64; w++) { const T s = s_wave[w]; if (w < wv) before += s; all += s; }
-    *total = all;
-    return before + incl - mine;
-}
-
 __global__ void __launch_bounds__(BS_THREADS)
 k_bs_count(const unsigned char *__restrict__ rec, const uint64_t *__restrict__ read_off, const uint64_t *__restrict__ tile_base, int n_reads, unsigned long long total,
            uint32_t *__restrict__ cnt_off, uint32_t *__restrict__ tile_cnt)
@@ -155,7 +142,7 @@ k_bs_count(const unsigned char *__restrict__ rec, const uint64_t *__restrict__ r
     uint32_t mine = 0;
     if (k < n_reads) mine = bs_range_walk(rec, bs_read_begin(read_off, tile_base, k, n_reads, total), bs_read_begin(read_off, tile_base, k + 1, n_reads, total), BsNoop());
     uint32_t all;
-    const uint32_t ex = bs_block_exclusive(mine, &all, s_wave);
+    const uint32_t ex = d_wg_exclusive(mine, all, s_wave);
     if (k < n_reads) cnt_off[k] = ex;
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = all;
 }
@@ -186,7 +173,7 @@ k_bs_len(const unsigned char *__restrict__ store, const int64_t *__restrict__ of
     const uint32_t i = blockIdx.x * BS_THREADS + threadIdx.x;
     const uint64_t mine = i < n ? 4ull + (uint64_t)bs_le32(store + offs[i]) : 0ull;
     uint64_t all;
-    const uint64_t ex = bs_block_exclusive(mine, &all, s_wave);
+    const uint64_t ex = d_wg_exclusive(mine, all, s_wave);
     if (i < n) dst_off[i] = ex;
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
 }

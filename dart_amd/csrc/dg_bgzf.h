@@ -2,7 +2,7 @@
 // The array is cut into blocks of BGZF_BLOCK (0xff00) input bytes; one workgroup compresses one block into a 64 KB slot of its own:
 //   k_bgzf_deflate  the 18-byte gzip / 'BC' header, ONE raw deflate block (fixed Huffman codes, LZ77 with distances up to 32768), CRC32, ISIZE;
 //                   a block whose coded form is not smaller than its input is written as a stored deflate block (input + 31 bytes)
-//   k_sam_top       (dg_samfmt.h) the exclusive scan of the block sizes, the total
+//   k_tiles_top     (dg_wgscan.h) the exclusive scan of the block sizes, the total
 //   k_bgzf_copy     slot -> its place in the contiguous stream
 // The match search is made so that the bytes never depend on timing: the block is walked in strips of BGZF_STRIP bytes, a strip is cut into
 // BGZF_SEG-byte segments (lane = segment).  A lane takes its segment greedily, serially; its candidates are

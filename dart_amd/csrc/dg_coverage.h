@@ -36,7 +36,7 @@
 //   -- the first wait: the number of events sizes the sorter's buffers; a record out of range ends the call --
 //   k_cv_emit       lane = sorted record: the same walk; block b of the array leaves the pairs (start key, +1) and (end key, -1) at 2 b and 2 b + 1
 //   (sort)          one stable radix sort of the events (rs_sort_passes of dg_sort.h): only the low digits in which the smallest and largest key differ
-//   k_cv_depth      lane = sorted event: the workgroup's inclusive scan of the deltas and its sum (k_scan_top of dg_api.hip).  32 bit: a record's blocks do not overlap,
+//   k_cv_depth      lane = sorted event: the workgroup's inclusive scan of the deltas and its sum (k_tiles_top of dg_wgscan.h).  32 bit: a record's blocks do not overlap,
 //                   so no prefix of the sorted deltas exceeds the number of records (< 2^32), and none is negative (an end's start lies in front of it)
 //   k_cv_tails      lane = event: the last event of a run of equal keys (a tail) carries the depth behind its position; per workgroup its last tail's depth
 //   k_cv_tails_top  one workgroup: a last-valid scan over those, so every workgroup knows the depth of the last tail in front of it, however far back it lies
@@ -48,12 +48,13 @@
 //                   has a successor on its reference), its line's length, the workgroup's scan (k_cv_top); covered bases and the sum of depth x length
 //   k_cv_write      lane = entry: the line's bytes at the scanned place
 // A run of equal keys may straddle workgroups and sorter tiles, and the previous tail may lie any number of workgroups back: both scans carry what they need
-// across workgroups (k_scan_top, k_cv_tails_top); no lane reads a neighbour's result, and no kernel here uses an atomic.
+// across workgroups (k_tiles_top, k_cv_tails_top); no lane reads a neighbour's result, and no kernel here uses an atomic.
 // Memory: 4 bytes per record; 40 bytes per event (two key and two value buffers of the sorter, the scanned delta, the marks) and the sorter's histograms; 12
 // per breakpoint; 24 per entry and its line; up to 40 per workgroup.  Everything a lane computes is host-callable: tests/native/coverage_checks.hip runs the same code on the CPU.
 #ifndef DG_COVERAGE_H
 #define DG_COVERAGE_H
 #include "dg_bamsort.h"
+#include "dg_wgscan.h"
 
 #define CV_HD __host__ __device__ __forceinline__
 #define CV_THREADS 256               // records / events / entries per workgroup of every kernel here (dg_bam_coverage_granules [0])
@@ -61,6 +62,7 @@
 #define CV_NONE (~0ull)              // no tail yet (the last-valid scans)
 #define CV_PLANES 5                  // the most per-workgroup values a kernel leaves for k_cv_top
 static_assert(CV_THREADS == BS_THREADS, "k_cv_count reads k_bs_len's per-workgroup offsets");
+static_assert(CV_THREADS == WG_THREADS, "the kernels here and of dg_markdup.h scan with d_wg_exclusive");
 // the call's small device state, 64-bit words.  k_cv_top's outputs lie side by side: sums first, then maxima
 enum { CV_ST_BLOCKS = 0, CV_ST_COUNTED, CV_ST_ALIGNED, CV_ST_NMIN /* max of ~key = ~min */, CV_ST_MAX, CV_ST_NBAD /* max of ~index of a record out of range; 0: none */,
        CV_ST_DEPTH_END /* the scanned deltas' total: 0 */, CV_ST_MARKS /* entries << 32 | breakpoints */, CV_ST_MAX_DEPTH, CV_ST_BYTES, CV_ST_COVERED, CV_ST_AREA /* sum of depth x length */,
@@ -161,8 +163,6 @@ CV_HD uint64_t cv_line_bound(uint32_t name_max) { return (uint64_t)name_max + 3 
 // ------------------------------------------------------------------------------------------
 // the kernels
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long cv_wave_sum(unsigned long long v) { for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64); return v; }
-__device__ __forceinline__ unsigned long long cv_wave_max(unsigned long long v) { for (int o = 32; o > 0; o >>= 1) { const unsigned long long u = __shfl_xor(v, o, 64); v = u > v ? u : v; } return v; }
 // the workgroup's values -- v[p] summed for p < n_sum, else the maximum -- into plane p of `part` (planes x workgroups): every wave leaves its own in LDS, the first N
 // threads combine the four.  s_part holds 4 N words.
 template <int N>
@@ -171,7 +171,7 @@ __device__ __forceinline__ void cv_block_partials(const unsigned long long (&v)[
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
 #pragma unroll
     for (int p = 0; p < N; p++) {
-        const unsigned long long w = p < n_sum ? cv_wave_sum(v[p]) : cv_wave_max(v[p]);
+        const unsigned long long w = p < n_sum ? d_wave_sum(v[p]) : d_wave_max(v[p]);
         if (lane == 0u) s_part[p * (CV_THREADS / 64) + wv] = w;
     }
     __syncthreads();
@@ -190,25 +190,19 @@ k_cv_top(uint64_t *__restrict__ tile_sum, uint32_t n_tiles, unsigned long long *
     __shared__ uint64_t s_wave[CV_THREADS / 64];
     __shared__ unsigned long long s_part[CV_PLANES * (CV_THREADS / 64)];
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint64_t carry = 0;
+    const uint64_t all = d_tiles_exclusive<uint64_t>(tile_sum, n_tiles, 1, s_wave);
+    if (threadIdx.x == 0) *total = all;
     unsigned long long acc[CV_PLANES];
 #pragma unroll
     for (int p = 0; p < CV_PLANES; p++) acc[p] = 0ull;
-    for (uint32_t t0 = 0; t0 < n_tiles; t0 += CV_THREADS) {
-        const uint32_t t = t0 + threadIdx.x;
-        uint64_t all;
-        const uint64_t ex = bs_block_exclusive(t < n_tiles ? tile_sum[t] : (uint64_t)0, &all, s_wave);
-        if (t < n_tiles) tile_sum[t] = carry + ex;
-        carry += all;
+    for (uint32_t t = threadIdx.x; t < n_tiles; t += CV_THREADS) {
 #pragma unroll
         for (int p = 0; p < CV_PLANES; p++)
-            if (p < n_planes && t < n_tiles) { const unsigned long long v = part[(size_t)p * n_tiles + t]; acc[p] = p < n_sum ? acc[p] + v : (v > acc[p] ? v : acc[p]); }
-        __syncthreads();
+            if (p < n_planes) { const unsigned long long v = part[(size_t)p * n_tiles + t]; acc[p] = p < n_sum ? acc[p] + v : (v > acc[p] ? v : acc[p]); }
     }
-    if (threadIdx.x == 0) *total = carry;
 #pragma unroll
     for (int p = 0; p < CV_PLANES; p++) {
-        const unsigned long long w = p < n_sum ? cv_wave_sum(acc[p]) : cv_wave_max(acc[p]);
+        const unsigned long long w = p < n_sum ? d_wave_sum(acc[p]) : d_wave_max(acc[p]);
         if (lane == 0u) s_part[p * (CV_THREADS / 64) + wv] = w;
     }
     __syncthreads();
@@ -245,7 +239,7 @@ k_cv_count(const unsigned char *__restrict__ sorted, const uint64_t *__restrict_
         }
     }
     uint64_t all;
-    const uint64_t ex = bs_block_exclusive(mine, &all, s_wave);
+    const uint64_t ex = d_wg_exclusive(mine, all, s_wave);
     if (i < n) blk_off[i] = (uint32_t)ex;                      // (at most 255 records of at most 65535 blocks in front)
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
     const unsigned long long v[5] = {counted, t.bad ? 0ull : t.aligned, nmin, kmax, nbad};
@@ -274,7 +268,7 @@ k_cv_depth(const int64_t *__restrict__ vals, uint32_t n_ev, uint32_t *__restrict
     const uint32_t i = blockIdx.x * CV_THREADS + threadIdx.x;
     const uint32_t mine = i < n_ev ? (uint32_t)vals[i] : 0u;
     uint32_t all;
-    const uint32_t ex = bs_block_exclusive(mine, &all, s_wave);
+    const uint32_t ex = d_wg_exclusive(mine, all, s_wave);
     if (i < n_ev) incl[i] = ex + mine;
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
 }
@@ -348,7 +342,7 @@ k_cv_flag(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ incl, 
     const uint32_t prev = (uint32_t)cv_fill(before, left);
     const bool tail = own != CV_NONE, bp = cv_is_breakpoint(tail, (uint32_t)own, prev), ent = bp && (uint32_t)own > 0u;
     uint32_t all;
-    const uint32_t ex = bs_block_exclusive((bp ? 1u : 0u) | (ent ? 1u << 16 : 0u), &all, s_wave);
+    const uint32_t ex = d_wg_exclusive((bp ? 1u : 0u) | (ent ? 1u << 16 : 0u), all, s_wave);
     if (i < n_ev) mark[i] = cv_mark(ex, bp, ent);
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = (uint64_t)(all >> 16) << 32 | (uint64_t)(all & 0xffffu);
     const unsigned long long v[1] = {tail ? (unsigned long long)(uint32_t)own : 0ull};
@@ -390,7 +384,7 @@ k_cv_entries(const uint64_t *__restrict__ bp_key, const uint32_t *__restrict__ b
         if (name_off && e.chr < (uint32_t)n_chr) mine = cv_line_len(name_off, e);
     }
     uint64_t all;
-    const uint64_t ex = bs_block_exclusive(mine, &all, s_wave);
+    const uint64_t ex = d_wg_exclusive(mine, all, s_wave);
     if (j < n_ent) line_off[j] = (uint32_t)ex;
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
     const unsigned long long v[2] = {covered, area};

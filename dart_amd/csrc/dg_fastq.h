@@ -19,12 +19,12 @@
 #ifndef DG_FASTQ_H
 #define DG_FASTQ_H
 #include "../../include/dartgpu.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "dg_wgscan.h"
 
 #define FQ_HD __host__ __device__ __forceinline__
 
 #define FQ_THREADS 256
+static_assert(FQ_THREADS == WG_THREADS, "the kernels here scan with d_wg_exclusive");
 #define FQ_ROUNDS 4
 #define FQ_TILE DG_FASTQ_TILE                 // bytes of text per workgroup of k_fq_count / k_fq_lines: FQ_ROUNDS rounds of 256 threads x 16 bytes
 static_assert(FQ_TILE == FQ_THREADS * 16 * FQ_ROUNDS, "a tile is FQ_ROUNDS rounds of 16 bytes per thread");
@@ -112,23 +112,6 @@ struct FqText {
     int two;
 };
 
-// exclusive scan of one value per thread over a workgroup of 256 (4 waves): shuffles inside a wave, the four wave sums through LDS
-template <typename T>
-__device__ __forceinline__ T fq_block_scan(T v, T *s_w, T &total)
-{
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const T t = __shfl_up(inc, o, 64); if ((int)lane >= o) inc += t; }
-    __syncthreads();                       // the previous scan's wave sums have been read
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    T base = 0; total = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < FQ_THREADS / 64; i++) { const T s = s_w[i]; if (i < w) base += s; total += s; }
-    return base + inc - v;
-}
-
 __device__ __forceinline__ uint32_t fq_load_mask(const unsigned char *t, uint64_t pos, uint64_t n)
 {
     if (pos >= n) return 0u;
@@ -147,7 +130,7 @@ k_fq_count(const FqText x, uint32_t *__restrict__ tile_cnt, uint32_t tile_stride
 #pragma unroll
     for (int j = 0; j < FQ_ROUNDS; j++) cnt += (uint32_t)__popc(fq_load_mask(x.t[f], base + ((uint64_t)j * FQ_THREADS + threadIdx.x) * 16u, n));
     uint32_t total;
-    (void)fq_block_scan<uint32_t>(cnt, s_w, total);
+    (void)d_wg_exclusive<uint32_t>(cnt, total, s_w);
     if (threadIdx.x == 0) tile_cnt[(size_t)f * tile_stride + blockIdx.x] = total;
 }
 
@@ -160,16 +143,7 @@ k_fq_top(const FqText x, uint32_t *__restrict__ tile_cnt, uint32_t tile_stride, 
     __shared__ uint32_t s_lines[2];
     for (int f = 0; f < (x.two ? 2 : 1); f++) {
         const uint32_t n_tiles = (uint32_t)(((uint64_t)x.n[f] + FQ_TILE - 1) / FQ_TILE);
-        uint32_t *tc = tile_cnt + (size_t)f * tile_stride;
-        uint32_t carry = 0;
-        for (uint32_t t0 = 0; t0 < n_tiles; t0 += FQ_THREADS) {
-            const uint32_t i = t0 + threadIdx.x;
-            const uint32_t v = i < n_tiles ? tc[i] : 0u;
-            uint32_t total;
-            const uint32_t ex = fq_block_scan<uint32_t>(v, s_w, total);
-            if (i < n_tiles) tc[i] = carry + ex;
-            carry += total;
-        }
+        const uint32_t carry = d_tiles_exclusive<uint32_t>(tile_cnt + (size_t)f * tile_stride, n_tiles, 1, s_w);
         if (threadIdx.x == 0) {
             const uint32_t lines = carry + ((x.n[f] && x.t[f][x.n[f] - 1] != '\n') ? 1u : 0u);
             info->n_nl[f] = carry; info->n_lines[f] = lines; s_lines[f] = lines;
@@ -211,7 +185,7 @@ k_fq_lines(const FqText x, const uint32_t *__restrict__ tile_off, uint32_t tile_
         const uint64_t pos = base + ((uint64_t)j * FQ_THREADS + threadIdx.x) * 16u;
         uint32_t m = fq_load_mask(x.t[f], pos, n);
         uint32_t total;
-        uint32_t at = line + fq_block_scan<uint32_t>((uint32_t)__popc(m), s_w, total);
+        uint32_t at = line + d_wg_exclusive<uint32_t>((uint32_t)__popc(m), total, s_w);
         while (m) {
             const uint32_t b = (uint32_t)__ffs((int)m) - 1u;
             m &= m - 1u;
@@ -292,13 +266,11 @@ k_fq_len(const FqText x, FqInfo *info, uint16_t *__restrict__ rlen_out, uint32_t
 #pragma unroll
     for (int i = 0; i < 3; i++) {
         uint32_t total;
-        const uint32_t ex = fq_block_scan<uint32_t>(len[i], s_w, total);
+        const uint32_t ex = d_wg_exclusive<uint32_t>(len[i], total, s_w);
         if (k < n_reads) loc[(size_t)i * stride + k] = ex;
         if (threadIdx.x == 0) tile_sum[(size_t)i * n_tiles + blockIdx.x] = total;
     }
-    uint32_t mx = len[0];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(mx, o, 64); mx = t > mx ? t : mx; }
+    const uint32_t mx = d_wave_max(len[0]);
     if ((threadIdx.x & 63u) == 0 && mx) atomicMax(&info->max_rlen, mx);
 }
 
@@ -310,17 +282,8 @@ k_fq_top3(unsigned long long *__restrict__ tile_sum, uint32_t n_tiles, FqInfo *_
     const uint32_t used = (info->n_reads + FQ_THREADS - 1) / FQ_THREADS;
     const uint32_t nt = used < n_tiles ? used : n_tiles;
     for (int r = 0; r < 3; r++) {
-        unsigned long long *ts = tile_sum + (size_t)r * n_tiles;
-        unsigned long long carry = 0;
-        for (uint32_t t0 = 0; t0 < nt; t0 += FQ_THREADS) {
-            const uint32_t i = t0 + threadIdx.x;
-            const unsigned long long v = i < nt ? ts[i] : 0ull;
-            unsigned long long total;
-            const unsigned long long ex = fq_block_scan<unsigned long long>(v, s_w, total);
-            if (i < nt) ts[i] = carry + ex;
-            carry += total;
-        }
-        if (threadIdx.x == 0) info->total[r] = carry;
+        const unsigned long long total = d_tiles_exclusive<unsigned long long>(tile_sum + (size_t)r * n_tiles, nt, 1, s_w);
+        if (threadIdx.x == 0) info->total[r] = total;
     }
     __syncthreads();
     if (threadIdx.x == 0) {

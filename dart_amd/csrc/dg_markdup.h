@@ -193,7 +193,7 @@ k_md_rec(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__ 
         E[i] = r.E; h[i] = r.h; score[i] = r.score; mate[i] = r.examined ? MD_FRAGMENT : MD_NOT_EXAMINED;
     }
     uint64_t all;
-    const uint64_t ex = bs_block_exclusive(mine, &all, s_wave);
+    const uint64_t ex = d_wg_exclusive(mine, all, s_wave);
     if (i < n) cand_off[i] = (uint32_t)ex | (mine ? 1u << 31 : 0u);
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
     const unsigned long long v[2] = {examined, nbad};
@@ -235,7 +235,7 @@ k_md_count(const uint32_t *__restrict__ mate, uint32_t n, uint32_t *__restrict__
     const uint32_t i = blockIdx.x * MD_THREADS + threadIdx.x;
     const uint64_t mine = i < n ? md_counts(i, mate[i]) : 0ull;
     uint64_t all;
-    const uint64_t ex = bs_block_exclusive(mine, &all, s_wave);
+    const uint64_t ex = d_wg_exclusive(mine, all, s_wave);
     if (i < n) cnt_off[i] = (uint32_t)(ex >> 32) << 16 | ((uint32_t)ex & 0xFFFFu);          // (at most 255 pairs and 510 ends in front)
     if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
 }

@@ -3,15 +3,14 @@
 // in __host__ __device__ functions that the two kernels below and the CPU suite (tests/native/sam_checks.hip) share:
 //   k_sam_len     lane = read: the byte length of the read's text and the three counters; every workgroup leaves the exclusive scan of its
 //                 256 lengths and their sum
-//   k_sam_top     one workgroup: exclusive scan of the workgroup sums (64 bit), the total
+//   k_tiles_top   (dg_wgscan.h) one workgroup: exclusive scan of the workgroup sums (64 bit), the total
 //   k_sam_write   wave = read: name, bases and qualities are copied (or reverse-complemented / reversed) lane beside lane; the numeric
 //                 fields of a line are composed by lane 0 into LDS and stored from there by the wave
 // Every byte's place follows from the scanned lengths alone, so the text is the same whatever the grid.
 #ifndef DG_SAMFMT_H
 #define DG_SAMFMT_H
 #include "../../include/dartgpu.h"
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "dg_wgscan.h"
 
 #define SAM_HD __host__ __device__ __forceinline__
 
@@ -194,61 +193,30 @@ SAM_HD uint64_t sam_read_text(const SamBatch &b, int k, char *out)
 // the kernels
 // ------------------------------------------------------------------------------------------
 #define SAM_LEN_THREADS 256
+static_assert(SAM_LEN_THREADS == WG_THREADS, "k_sam_len and k_bam_len scan with d_wg_exclusive");
 #define SAM_MID_STAGE 192        // bytes of LDS for a line's FLAG .. TLEN (a line with more -- hundreds of CIGAR ops, a long chromosome name -- is written by lane 0 alone)
 #define SAM_TAIL_STAGE 64        // the tags never exceed 59 bytes
 static_assert(3 * 11 + 3 * 6 + 7 + 1 <= SAM_TAIL_STAGE, "the tags fit their staging area");
 
-// stat[0] total bytes (k_sam_top), stat[1..3] the counters
+// stat[0] total bytes (k_tiles_top), stat[1..3] the counters
 __global__ void __launch_bounds__(SAM_LEN_THREADS)
 k_sam_len(const SamBatch b, uint64_t *__restrict__ read_off, uint32_t *__restrict__ qlen_out, uint64_t *__restrict__ tile_sum, unsigned long long *__restrict__ stat)
 {
-    __shared__ uint64_t s_scan[SAM_LEN_THREADS];
+    __shared__ uint64_t s_wave[SAM_LEN_THREADS / 64];
     __shared__ uint32_t s_ct[3];
     const int k = (int)(blockIdx.x * SAM_LEN_THREADS + threadIdx.x);
     if (threadIdx.x < 3) s_ct[threadIdx.x] = 0;
     uint32_t ct[3] = {0, 0, 0};
     uint32_t ql = 0;
     const uint64_t len = k < b.n_reads ? sam_read_len(b, k, ct, &ql) : 0ull;
-    s_scan[threadIdx.x] = len;
-    __syncthreads();
-    for (int o = 1; o < SAM_LEN_THREADS; o <<= 1) {
-        const uint64_t t = (int)threadIdx.x >= o ? s_scan[threadIdx.x - o] : 0ull;
-        __syncthreads();
-        s_scan[threadIdx.x] += t;
-        __syncthreads();
-    }
-    if (k < b.n_reads) { read_off[k] = s_scan[threadIdx.x] - len; qlen_out[k] = ql; }
+    uint64_t all;
+    const uint64_t ex = d_wg_exclusive<uint64_t>(len, all, s_wave);
+    if (k < b.n_reads) { read_off[k] = ex; qlen_out[k] = ql; }
 #pragma unroll
     for (int i = 0; i < 3; i++) if (ct[i]) atomicAdd(&s_ct[i], ct[i]);
     __syncthreads();
-    if (threadIdx.x == SAM_LEN_THREADS - 1) tile_sum[blockIdx.x] = s_scan[SAM_LEN_THREADS - 1];
+    if (threadIdx.x == 0) tile_sum[blockIdx.x] = all;
     if (threadIdx.x < 3 && s_ct[threadIdx.x]) atomicAdd(&stat[1 + threadIdx.x], (unsigned long long)s_ct[threadIdx.x]);
-}
-
-__global__ void __launch_bounds__(256)
-k_sam_top(uint64_t *__restrict__ tile_sum, uint32_t n_tiles, unsigned long long *__restrict__ stat)
-{
-    __shared__ uint64_t sh[256];
-    __shared__ uint64_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t t0 = 0; t0 < n_tiles; t0 += 256) {
-        const uint32_t i = t0 + threadIdx.x;
-        const uint64_t v = i < n_tiles ? tile_sum[i] : 0ull;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            const uint64_t t = (int)threadIdx.x >= o ? sh[threadIdx.x - o] : 0ull;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n_tiles) tile_sum[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += sh[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) stat[0] = carry;
 }
 
 // One wave per workgroup, one workgroup per read (no loop over reads: what is fixed per read then lives in scalar registers for that read only, and

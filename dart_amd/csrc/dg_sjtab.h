@@ -25,6 +25,7 @@
 #define DG_SJTAB_H
 #include "dg_samfmt.h"
 #include "dg_scan.h"
+#include "dg_wgscan.h"
 
 #define SJ_HD __host__ __device__ __forceinline__
 #define SJ_THREADS 256           // items per workgroup of k_sj_insert (dg_sj_granules [0])
@@ -144,12 +145,6 @@ k_sj_insert(const unsigned char *__restrict__ src, unsigned long long n, int kin
     if (at < ovf_cap) { dg_sj_entry e; e.g1 = g1; e.g2 = g2; e.count = (uint32_t)cnt; e.chr = 0; ovf[at] = e; }
 }
 
-__device__ __forceinline__ unsigned long long sj_wave_max(unsigned long long v)
-{
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long u = __shfl_xor(v, o, 64); v = u > v ? u : v; }
-    return v;
-}
-
 __global__ void __launch_bounds__(SJ_THREADS)
 k_sj_compact(const SjSlot *__restrict__ tab, unsigned long long n_slots, unsigned long long cap, uint64_t *__restrict__ keys, int64_t *__restrict__ vals, unsigned long long *stat)
 {
@@ -166,7 +161,7 @@ k_sj_compact(const SjSlot *__restrict__ tab, unsigned long long n_slots, unsigne
     base = __shfl(base, leader, 64);
     const unsigned long long at = base + (unsigned long long)__popcll(m & ((1ull << lane) - 1ull));
     if (filled && at < cap) { keys[at] = k2; vals[at] = (int64_t)i; }
-    const unsigned long long a = sj_wave_max(filled ? ~k1 : 0ull), b = sj_wave_max(filled ? k1 : 0ull), c = sj_wave_max(filled ? ~k2 : 0ull), d = sj_wave_max(filled ? k2 : 0ull);
+    const unsigned long long a = d_wave_max(filled ? ~k1 : 0ull), b = d_wave_max(filled ? k1 : 0ull), c = d_wave_max(filled ? ~k2 : 0ull), d = d_wave_max(filled ? k2 : 0ull);
     if (lane == leader) { atomicMax(stat + SJ_ST_NMIN1, a); atomicMax(stat + SJ_ST_MAX1, b); atomicMax(stat + SJ_ST_NMIN2, c); atomicMax(stat + SJ_ST_MAX2, d); }
 }
 

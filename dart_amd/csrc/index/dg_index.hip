@@ -332,7 +332,7 @@ extern "C" DI_API int di_bwt_blocks(int device, const int64_t *sa, const uint64_
 
 // ==========================================================================================
 // The whole build, natively: di_build_files (what `dart index` and dart_amd/index_build.py call).  Host orchestration of the
-// kernels above plus the radix sorter's kernels (../dg_sort.h, the same ones dg_sort_pairs launches) and three small scans.
+// kernels above plus the radix sorter and the u32 scan of ../dg_sort.h (the kernels and the pass driver dg_sort_pairs runs).
 // ==========================================================================================
 #include "../dg_sort.h"
 #include <algorithm>
@@ -340,80 +340,6 @@ extern "C" DI_API int di_bwt_blocks(int device, const int64_t *sa, const uint64_
 #include <cstdlib>
 #include <string>
 #include <vector>
-
-// ---- exclusive scan of n u32 (three phases; tiles of 2048)
-#define S32_TILE 2048u
-__global__ void __launch_bounds__(256) k_s32_a(const uint32_t *__restrict__ in, uint32_t *__restrict__ out, uint32_t *__restrict__ sums, uint32_t n)
-{
-    __shared__ uint32_t ws[4];
-    const uint32_t base = blockIdx.x * S32_TILE + threadIdx.x * 8u, lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint32_t v[8], sum = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) { v[i] = base + i < n ? in[base + i] : 0u; sum += v[i]; }
-    uint32_t incl = sum;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64); if (lane >= (uint32_t)o) incl += up; }
-    if (lane == 63) ws[wv] = incl;
-    __syncthreads();
-    uint32_t run = incl - sum;
-    for (uint32_t w = 0; w < wv; w++) run += ws[w];
-#pragma unroll
-    for (int i = 0; i < 8; i++) { if (base + i < n) out[base + i] = run; run += v[i]; }
-    if (threadIdx.x == 255) sums[blockIdx.x] = run;
-}
-__global__ void __launch_bounds__(256) k_s32_b(uint32_t *__restrict__ sums, uint32_t n_tiles, uint32_t *__restrict__ total)
-{
-    __shared__ uint32_t sh[256];
-    __shared__ uint32_t carry;
-    if (threadIdx.x == 0) carry = 0;
-    __syncthreads();
-    for (uint32_t b = 0; b < n_tiles; b += 256u) {
-        const uint32_t i = b + threadIdx.x, v = i < n_tiles ? sums[i] : 0u;
-        sh[threadIdx.x] = v;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {
-            const uint32_t t = threadIdx.x >= (uint32_t)o ? sh[threadIdx.x - o] : 0u;
-            __syncthreads();
-            sh[threadIdx.x] += t;
-            __syncthreads();
-        }
-        if (i < n_tiles) sums[i] = carry + sh[threadIdx.x] - v;
-        __syncthreads();
-        if (threadIdx.x == 255) carry += sh[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-__global__ void __launch_bounds__(256) k_s32_c(uint32_t *__restrict__ out, const uint32_t *__restrict__ sums, uint32_t n)
-{
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) out[i] += sums[i / S32_TILE];
-}
-// scratch: ceil(n / 2048) + 1 u32; the total lands in scratch[ceil(n / 2048)]
-static void scan_u32(const uint32_t *in, uint32_t *out, uint32_t n, uint32_t *scratch)
-{
-    const uint32_t tiles = (n + S32_TILE - 1) / S32_TILE;
-    k_s32_a<<<tiles, 256, 0, 0>>>(in, out, scratch, n);
-    k_s32_b<<<1, 256, 0, 0>>>(scratch, tiles, scratch + tiles);
-    k_s32_c<<<(n + 255u) / 256u, 256, 0, 0>>>(out, scratch, n);
-}
-
-// ---- the sorter: the kernels of ../dg_sort.h under the same driver as dg_sort_pairs (dg_api.hip), with caller-owned scratch
-static void sort_pairs(uint64_t *keys, int64_t *vals, uint64_t *tk, int64_t *tv, uint32_t m, int key_bits, uint32_t *hist, uint32_t *scan_scratch)
-{
-    if (m < 2) return;
-    const uint32_t tiles = (m + RS_TILE - 1) / RS_TILE, cells = 16u * tiles;
-    uint64_t *ka = keys, *kb = tk; int64_t *va = vals, *vb = tv;
-    for (int shift = 0; shift < key_bits; shift += 4) {
-        k_rs_hist<<<tiles, 256, 0, 0>>>(ka, m, shift, tiles, hist);
-        scan_u32(hist, hist, cells, scan_scratch);
-        k_rs_scatter<<<tiles, 256, 0, 0>>>(ka, va, kb, vb, m, shift, tiles, hist);
-        std::swap(ka, kb); std::swap(va, vb);
-    }
-    if (ka != keys) {
-        (void)hipMemcpyAsync(keys, ka, (size_t)m * 8, hipMemcpyDeviceToDevice, 0);
-        (void)hipMemcpyAsync(vals, va, (size_t)m * 8, hipMemcpyDeviceToDevice, 0);
-    }
-}
 
 // ---- .pac bytes, sampled rows, the Occ counters in front of each block
 __global__ void __launch_bounds__(256) k_pac(const uint8_t *__restrict__ fwd, uint64_t L, uint8_t *__restrict__ pac, uint64_t n_bytes)
@@ -448,57 +374,29 @@ __global__ void __launch_bounds__(256) k_occ_a(const uint32_t *__restrict__ coun
     uint32_t c[4][4], sum[4];
     d_occ_lane(counts, nblk, (uint64_t)blockIdx.x * OCC_TILE + threadIdx.x * 4u, c, sum);
 #pragma unroll
-    for (int f = 0; f < 4; f++) for (int o = 32; o; o >>= 1) sum[f] += (uint32_t)__shfl_xor((int)sum[f], o, 64);
+    for (int f = 0; f < 4; f++) sum[f] = d_wave_sum(sum[f]);
     if ((threadIdx.x & 63u) == 0) for (int f = 0; f < 4; f++) ws[threadIdx.x >> 6][f] = sum[f];
     __syncthreads();
     if (threadIdx.x < 4) tsum[(size_t)blockIdx.x * 4u + threadIdx.x] = (uint64_t)ws[0][threadIdx.x] + ws[1][threadIdx.x] + ws[2][threadIdx.x] + ws[3][threadIdx.x];
 }
 __global__ void __launch_bounds__(256) k_occ_b(uint64_t *__restrict__ tsum, uint32_t tiles, uint64_t *__restrict__ total)
 {
-    __shared__ uint64_t sh[256];
-    __shared__ uint64_t carry;
+    __shared__ uint64_t s_wave[4];
     for (int f = 0; f < 4; f++) {
-        if (threadIdx.x == 0) carry = 0;
-        __syncthreads();
-        for (uint32_t b = 0; b < tiles; b += 256u) {
-            const uint32_t i = b + threadIdx.x;
-            const uint64_t v = i < tiles ? tsum[(size_t)i * 4u + f] : 0ull;
-            sh[threadIdx.x] = v;
-            __syncthreads();
-            for (int o = 1; o < 256; o <<= 1) {
-                const uint64_t t = threadIdx.x >= (uint32_t)o ? sh[threadIdx.x - o] : 0ull;
-                __syncthreads();
-                sh[threadIdx.x] += t;
-                __syncthreads();
-            }
-            if (i < tiles) tsum[(size_t)i * 4u + f] = carry + sh[threadIdx.x] - v;
-            __syncthreads();
-            if (threadIdx.x == 255) carry += sh[255];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) total[f] = carry;
-        __syncthreads();
+        const uint64_t all = d_tiles_exclusive<uint64_t>(tsum + f, tiles, 4, s_wave);
+        if (threadIdx.x == 0) total[f] = all;
     }
 }
 __global__ void __launch_bounds__(256) k_occ_c(const uint32_t *__restrict__ counts, uint64_t nblk, const uint64_t *__restrict__ tsum, uint64_t *__restrict__ blocks64)
 {
-    __shared__ uint32_t ws[4][4];
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    __shared__ uint32_t s_wave[4];
     const uint64_t b0 = (uint64_t)blockIdx.x * OCC_TILE + threadIdx.x * 4u;
-    uint32_t c[4][4], sum[4], ex[4];
+    uint32_t c[4][4], sum[4];
     d_occ_lane(counts, nblk, b0, c, sum);
 #pragma unroll
     for (int f = 0; f < 4; f++) {
-        uint32_t incl = sum[f];
-        for (int o = 1; o < 64; o <<= 1) { const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64); if (lane >= (uint32_t)o) incl += up; }
-        if (lane == 63) ws[wv][f] = incl;
-        ex[f] = incl - sum[f];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int f = 0; f < 4; f++) {
-        uint64_t run = tsum[(size_t)blockIdx.x * 4u + f] + ex[f];
-        for (uint32_t w = 0; w < wv; w++) run += ws[w][f];
+        uint32_t all;
+        uint64_t run = tsum[(size_t)blockIdx.x * 4u + f] + d_wg_exclusive<uint32_t>(sum[f], all, s_wave);
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             if (b0 + (uint64_t)q < nblk) blocks64[(b0 + (uint64_t)q) * 8u + (uint64_t)f] = run;     // a block = 16 u32 = 8 u64: the first four are the counts
@@ -606,11 +504,12 @@ extern "C" DI_API int di_build_files(int device, const uint8_t *fwd, uint64_t l_
     uint64_t counts[16], lows[16], m_max = 0;
     {
         uint32_t *scr = nullptr;
-        DI_CHK(d.get(&scr, (size_t)(tiles / S32_TILE + 2)));
+        const uint32_t scan_tiles = (tiles + SCAN_TILE - 1) / SCAN_TILE;
+        DI_CHK(d.get(&scr, (size_t)scan_tiles + 1));
         for (int p = 0; p < 16; p++) {
-            scan_u32(table + (size_t)p * tiles, bases + (size_t)p * tiles, tiles, scr);
+            rs_scan_u32(0, table + (size_t)p * tiles, bases + (size_t)p * tiles, tiles, scr, scr + scan_tiles);
             uint32_t tot = 0;
-            DI_CHK(hipMemcpy(&tot, scr + (tiles + S32_TILE - 1) / S32_TILE, 4, hipMemcpyDeviceToHost));
+            DI_CHK(hipMemcpy(&tot, scr + scan_tiles, 4, hipMemcpyDeviceToHost));
             counts[p] = tot; if (tot > m_max) m_max = tot;
         }
         d.drop(scr); d.drop(table);
@@ -626,8 +525,8 @@ extern "C" DI_API int di_build_files(int device, const uint8_t *fwd, uint64_t l_
     DI_CHK(d.get(&new_pos, m_max));
     const uint32_t m_tiles = (uint32_t)((m_max + DI_TILE - 1) / DI_TILE);
     DI_CHK(d.get(&grp_scr, (size_t)2 * m_tiles + 4));
-    DI_CHK(d.get(&hist, (size_t)16 * m_tiles + 16));
-    DI_CHK(d.get(&scan_scr, (size_t)(16 * (size_t)m_tiles / S32_TILE + 4)));
+    DI_CHK(d.get(&hist, rs_hist_words((uint32_t)m_max)));
+    DI_CHK(d.get(&scan_scr, rs_sums_words((uint32_t)m_max)));
     say("bucket sizes known, buffers allocated");
     // rows: '$' first, then per first symbol c0 the suffix "c0 $" (if the text ends in c0), then the buckets c0 A, c0 C, c0 G, c0 T
     {
@@ -646,12 +545,19 @@ extern "C" DI_API int di_build_files(int device, const uint8_t *fwd, uint64_t l_
         }
         if (row != N) { snprintf(g_err, sizeof g_err, "di_build_files: bucket counts do not add up"); return -2; }
     }
-    auto sorted = [&](uint32_t m, int bits) {
+    auto sorted = [&](uint32_t m, int bits) -> int {                           // keys / vals by the low `bits` bits of the keys: the driver dg_sort_pairs runs
         (void)hipStreamSynchronize(0);
         Clock c;
-        sort_pairs(keys, vals, tk, tv, m, bits, hist, scan_scr);
-        (void)hipStreamSynchronize(0);
+        uint64_t *const k2[2] = {keys, tk}; int64_t *const v2[2] = {vals, tv};
+        int which = 0;
+        if (m >= 2) DI_CHK(rs_sort_passes(0, k2, v2, hist, scan_scr, m, bits, which));
+        if (which) {
+            DI_CHK(hipMemcpyAsync(keys, tk, (size_t)m * 8, hipMemcpyDeviceToDevice, 0));
+            DI_CHK(hipMemcpyAsync(vals, tv, (size_t)m * 8, hipMemcpyDeviceToDevice, 0));
+        }
+        DI_CHK(hipStreamSynchronize(0));
         sort_s += c.s();
+        return 0;
     };
     auto regroup = [&](const uint32_t *pos, uint32_t m, uint64_t lo, uint32_t *n_tied) -> int {
         const uint32_t t = (m + DI_TILE - 1) / DI_TILE;
@@ -677,9 +583,9 @@ extern "C" DI_API int di_build_files(int device, const uint8_t *fwd, uint64_t l_
         if (m == 0) continue;
         k_bucket_keys<<<tiles, 256, 0, 0>>>(T, n, (uint32_t)p, bases + (size_t)p * tiles, keys, vals);
         DI_LAUNCHED("k_bucket_keys");
-        sorted(m, 63);
         uint32_t t = 0;
-        int rc = regroup(nullptr, m, lows[p], &t); if (rc) return rc;
+        int rc = sorted(m, 63); if (rc) return rc;
+        rc = regroup(nullptr, m, lows[p], &t); if (rc) return rc;
         rc = keep_tied(p, t); if (rc) return rc;
         tied_total += t;
         if (getenv("DART_INDEX_VERBOSE")) {
@@ -698,9 +604,9 @@ extern "C" DI_API int di_build_files(int device, const uint8_t *fwd, uint64_t l_
             k_doubling_keys<<<(m + 255u) / 256u, 256, 0, 0>>>(sa, rank, lows[p], pending[p], m, k, N, r2_bits, keys, vals);
             DI_LAUNCHED("k_doubling_keys");
             int bits = 0; while ((counts[p] >> bits) != 0) bits++;
-            sorted(m, std::min(64, r2_bits + bits));
             uint32_t t = 0;
-            int rc = regroup(pending[p], m, lows[p], &t); if (rc) return rc;
+            int rc = sorted(m, std::min(64, r2_bits + bits)); if (rc) return rc;
+            rc = regroup(pending[p], m, lows[p], &t); if (rc) return rc;
             rc = keep_tied(p, t); if (rc) return rc;
             tied_total += t;
         }

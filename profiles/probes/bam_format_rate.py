@@ -1,4 +1,4 @@
-"""Device time of the BAM writer (dg_batch_format_bam: k_bam_len + k_sam_top + k_bam_write, then k_bgzf_deflate + k_sam_top + k_bgzf_copy) on the headline
+"""Device time of the BAM writer (dg_batch_format_bam: k_bam_len + k_tiles_top + k_bam_write, then k_bgzf_deflate + k_tiles_top + k_bgzf_copy) on the headline
 workload's shape: 1 M pairs of 2x101 on the chr20-sized planted genome at -mis 5, the batch of sam_format_rate.py.  A tool, not a test.  Prints the device time
 split into record kernels and BGZF kernels, bytes read and written, raw and compressed sizes, and the share of the HBM peak.
 --dynamic adds a second arm in the same process, its runs alternating with the first arm's: DG_BAM_DYNAMIC (k_bgzf_deflate_dyn in place of k_bgzf_deflate).  The

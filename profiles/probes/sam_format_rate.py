@@ -1,4 +1,4 @@
-"""Device time of the SAM formatter (dg_batch_format_sam: k_sam_len + k_sam_top + k_sam_write) on the headline workload's shape: 1 M pairs of 2x101 on the
+"""Device time of the SAM formatter (dg_batch_format_sam: k_sam_len + k_tiles_top + k_sam_write) on the headline workload's shape: 1 M pairs of 2x101 on the
 chr20-sized planted genome at -mis 5.  A tool, not a test.  Prints reads/s and the achieved fraction of the HBM peak for bytes in + bytes out.
 
     python profiles/probes/sam_format_rate.py [--runs 20] [--warmup 3] [--pairs 1000000] [--cache DIR] [--out FILE]

@@ -6,6 +6,9 @@ import numpy as np
 import pytest
 import common, bam_decode
 import bamsort_inputs as bsi
+import bamidx_inputs as bii
+import coverage_inputs as cvi
+import markdup_inputs as mdi
 from dart_amd import host
 
 pytestmark = pytest.mark.gpu
@@ -195,6 +198,38 @@ def test_seams_of_the_sorter_through_records_from_the_host(env):
         assert e.gpu.bam_sort_add(b"".join(recs[:cut]), 0) == cut
         want = sorted(recs, key=lambda r: bsi.key(r, e.n_chr))
         assert sorted_array(e.gpu) == b"".join(want), n
+
+
+def _descending_aligned(n, n_chr):
+    """_descending's keys and ties, every record placed with one CIGAR op and qualities: the index, the coverage track and the duplicate marker all take it"""
+    n_keys = (n + 7) // 8
+    recs = [bii.record(k * n_chr // n_keys, k // 2, 16 if k & 1 else 0, b"q%d" % i, [(20, bii.M)], l_seq=20, mapq=30, fill=30)
+            for i, k in ((i, (n - 1 - i) // 8) for i in range(n))]
+    assert len({struct.unpack_from("<i", r, 4)[0] for r in recs[::max(n // 64, 1)]}) >= 2
+    return recs
+
+
+@pytest.mark.parametrize("n", [65535, 65536, 65537, 131073])
+def test_more_than_256_workgroup_sums_carry_through_the_tile_sum_scans(env, n):
+    """One record per lane: 65 536 records are 256 workgroup sums, the last size that k_tiles_top (both widths) and k_cv_top scan without a carry; 65 537 and
+    131 073 give 257 and 513.  Store, index, coverage track (entries only) and duplicate counts of the same array, each against its Python twin."""
+    e, g = env, env.gpu
+    assert e.n_chr >= 2
+    recs = _descending_aligned(n, e.n_chr)
+    cut = n // 3
+    g.bam_sort_reset()
+    assert g.bam_sort_add(b"".join(recs[cut:]), 1) == n - cut
+    assert g.bam_sort_add(b"".join(recs[:cut]), 0) == cut
+    raw = sorted_array(g)
+    assert raw == b"".join(sorted(recs, key=lambda r: bsi.key(r, e.n_chr)))
+    sizes = bii.stored_sizes(raw)
+    assert g.bam_index_finish(1 << 40, sizes) == bii.build_bai(raw, sizes, 1 << 40, e.n_chr)
+    ent, text = g.bam_coverage_finish(entries_only=True)
+    t_ent, t_stats = cvi.twin(raw, e.n_chr)
+    assert ent.tolist() == t_ent and text == b"" and g.bam_coverage_stats == t_stats and t_stats[0] == n and len(t_ent) > 2 * e.n_chr
+    stats = mdi.twin(raw, e.n_chr)[1]
+    assert g.bam_markdup_finish(count_only=True) == stats and stats[0] == stats[2] == n and stats[4] == n - (n + 7) // 8
+    assert g.bam_sort_compress(0, len(raw), raw=True) == raw
 
 
 def test_seams_of_the_key_kernels_through_batches(env):

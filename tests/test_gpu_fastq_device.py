@@ -108,6 +108,24 @@ def test_fastq_upload_with_line_ends_on_tile_seams(ctxs):
         _same_reads(_batch(gpu), want2)
 
 
+def test_fastq_upload_of_more_reads_than_one_scan_of_the_workgroup_sums_holds(ctxs):
+    """65 537 single reads: 257 workgroups of k_fq_len, so k_fq_top3's scan of their sums takes a second trip with a carry, for all three lengths"""
+    gpu = ctxs["pe101_spliced"][2]
+    n = 65537
+    seqs = [bytes(r) for r in fdi.random_reads(n, rlen=20, seed=9)]
+    names = [b"r%d" % (k * 7919 % n) + b"x" * (k % 5) for k in range(n)]
+    quals = [bytes(33 + (k + j) % 41 for j in range(20 - k % 4)) for k in range(n)]
+    text = b"".join(b"@%s\n%s\n+\n%s\n" % (names[k], seqs[k], quals[k]) for k in range(n))
+    so, rl, flat = host.pack_reads(seqs)
+    assert gpu.upload_fastq(text) == n
+    gso, grl, gflat, gnames, gquals = gpu.download_reads()
+    assert np.array_equal(gso, so) and np.array_equal(grl, rl) and np.array_equal(gflat, flat)
+    want = fdi.reference_reads(text, None, False)           # (a quality shorter than its read is stored with its line end, as the reference's reader keeps it)
+    assert [h for h, s, q in want] == names and [s for h, s, q in want] == seqs
+    assert gnames == names and gquals == [q for h, s, q in want]
+    assert len({len(x) for x in names}) > 4 and {len(q) for q in quals} == {17, 18, 19, 20}
+
+
 def test_fastq_upload_does_not_depend_on_how_the_text_is_split(ctxs):
     c, ix, gpu, t1, t2 = ctxs["pe101_spliced"]
     n = len(c["reads"])
