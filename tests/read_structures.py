@@ -493,12 +493,13 @@ def _plain_pair(kind):
             _, b = _pos(rng, G, 10, rlen + 10, cj)
             m1, m2, _ = _orient(rng, L, G.seq(b, b + rlen), True)
         elif kind == "far":
-            want = (2000, 20000, 600000)[k % 3]      # (600 kb is beyond max_intron's default of 500 kb, the limit of a pair's distance)
+            want = (2000, 20000, 600000)[k % 3]      # (600 kb is beyond max_intron's default of 500 kb, but max_intron does not limit a pair's distance: mates pair while mate 2's
+                                                     # candidate lies less than 2 000 000 bases downstream of mate 1's, Mapping.cpp:420-429 -- so all three distances pair)
             ci = int(np.argmax(G.hi - G.lo))
             room = int(G.hi[ci] - G.lo[ci]) - 2 * rlen - 40
             dist = min(want, room)                   # a genome whose longest chromosome is shorter than the distance: as far as it goes.  The golden genomes' longest chromosomes
-                                                     # are 300 kb and 250 kb, so the committed sets hold 2 kb, 20 kb and about 299.8 kb / 249.5 kb -- all within the limit; a pair
-                                                     # beyond it is made only on a larger genome (the fuzz rounds'), and pair_other_chromosome is the committed sets' unpairable case
+                                                     # are 300 kb and 250 kb, so the committed sets hold 2 kb, 20 kb and about 299.8 kb / 249.5 kb.  A pair beyond the reach of
+                                                     # 2 000 000 needs a chromosome longer than that (tests/threshold_inputs.py, ladder E); pair_other_chromosome is these sets' unpairable case
             a = int(rng.integers(G.lo[ci] + 10, G.hi[ci] - dist - 2 * rlen - 10 + 1))
             m1, m2, _ = _orient(rng, G.seq(a, a + rlen), G.seq(a + rlen + dist, a + 2 * rlen + dist), True)
             info = dict(distance=dist)
