@@ -173,6 +173,16 @@ struct MdState {
     int hash_bits = MD_HASH_BITS;   // DG_MARKDUP_HASH_BITS: test hook, the bits of a name's hash that are kept (makes collisions and crowded runs reachable)
     hipError_t ready() { const hipError_t e = stat.ready(); return e != hipSuccess ? e : ev.ready(); }
 };
+// the allele counts of the sorted array (dg_pileup.h): buffers of its own: per record the event offsets, per event the sorter's pairs, the two scanned planes,
+// the previous tail and the mark, per distinct allele key its key, sum and depth, per site its first key, its mark and its line's place, per kept site the entry
+struct PuState {
+    DBuf<uint64_t> ev_off, ev_tile, junk, part, part2, incl_d, incl_a, tile_d, tile_a, tile_last, cnt_tile, ak_key, ak_n, ak_depth, kept_tile, line_tile; SortBufs sort;
+    DBuf<uint32_t> tile_prev, prev_tail, mark, site_key, site_mark, line_off; DBuf<dg_site_entry> entries; DBuf<char> text;
+    DevStat<unsigned long long, PU_ST_WORDS> stat;      // PU_ST_* words
+    EvSet<11> ev;                                       // around the kernels between the waits
+    bool valid = false; size_t n_entries = 0, bytes = 0; float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f}; int passes = 0;
+    hipError_t ready() { const hipError_t e = stat.ready(); return e != hipSuccess ? e : ev.ready(); }
+};
 // the gene table (dg_genecount.h): resident across batches, (4 + n_genes) x 3 words, counted under annotation generation gen; the per-workgroup lines of
 // the N_* rows; host counts and host records on their way in
 struct GcState {

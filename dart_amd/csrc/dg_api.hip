@@ -20,6 +20,7 @@
 #include "dg_bamidx.h"
 #include "dg_coverage.h"
 #include "dg_markdup.h"
+#include "dg_pileup.h"
 #include "dg_genecount.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -151,7 +152,7 @@ struct dg_ctx {
     bool batch_done = false;       // the batch on the context has been run and waited for
     bool no_batch = false;         // the last upload was a DG_FQ_CHECK_ONLY: there is nothing to run
     // the library stages' state, one struct each (api_ctx.h); every stage's section of this file drives its own
-    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; GcState gc;
+    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; GcState gc;
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
@@ -2694,7 +2695,7 @@ static int bs_view(dg_ctx *c, const char *fn, BsView &v)
     return DG_OK;
 }
 // the bytes of the sorted array changed (a new sort, duplicate flags written): no block of it has been compressed, and no index or track covers it
-static void bs_array_changed(dg_ctx *c) { c->bi.valid = false; c->bi.covered.clear(); c->cv.valid = false; }
+static void bs_array_changed(dg_ctx *c) { c->bi.valid = false; c->bi.covered.clear(); c->cv.valid = false; c->pu.valid = false; }
 
 extern "C" int dg_bam_sort_granules(int out[3])
 {
@@ -3443,6 +3444,187 @@ extern "C" int dg_bam_coverage_device_ms(dg_ctx *c, float ms[5], int *n_passes)
     if (!c || !ms) return DG_ERR_ARG;
     for (int k = 0; k < 5; k++) ms[k] = c->cv.ms[k];
     if (n_passes) *n_passes = c->cv.passes;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the allele counts of the sorted array (dg_pileup.h): the records' bases against the index's 2-bit text, in buffers of its own
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_bam_pileup_granules(int out[3])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = PU_WG; out[1] = RS_TILE; out[2] = PU_STEP;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_pileup_finish(dg_ctx *c, uint32_t flags, uint32_t exclude_flags, uint32_t min_mapq, uint32_t min_alt, size_t *n_sites, size_t *n_bytes, uint64_t stats[10], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_pileup_finish";
+    if (n_sites) *n_sites = 0;
+    if (n_bytes) *n_bytes = 0;
+    if (device_ms) *device_ms = 0.f;
+    if (stats) for (int k = 0; k < 10; k++) stats[k] = 0;
+    c->pu.valid = false; c->pu.n_entries = 0; c->pu.bytes = 0; c->pu.passes = 0;
+    for (float &m : c->pu.ms) m = 0.f;
+    BsView sv;
+    { const int rc = bs_view(c, fn, sv); if (rc) return rc; }
+    if (flags & ~DG_PU_ENTRIES_ONLY) { snprintf(c->err, 512, "%s: flags 0x%x hold a bit that is not DG_PU_ENTRIES_ONLY", fn, flags); return DG_ERR_ARG; }
+    if (min_alt == 0u) { snprintf(c->err, 512, "%s: min_alt is 0: a site has at least one observation of its top allele", fn); return DG_ERR_ARG; }
+    const bool text = !(flags & DG_PU_ENTRIES_ONLY);
+    IndexShared *sh = c->shared_ix;
+    if (text && (!sh || !sh->chr_names_set)) { snprintf(c->err, 512, "%s: the chromosome names are missing (dg_set_chr_names), and DG_PU_ENTRIES_ONLY is not set", fn); return DG_ERR_ARG; }
+    HIPCHK(c->pu.ready());
+    const size_t n = sv.n, n_raw = sv.n_raw;
+    const int n_chr = sv.n_chr;
+    if (n_chr < 1) { snprintf(c->err, 512, "%s: %d chromosomes", fn, n_chr); return DG_ERR_ARG; }
+    if (!n) { c->pu.valid = true; return DG_OK; }
+    const PuFilter f{exclude_flags, min_mapq};
+    const DIndex ix = c->ix;
+    const uint32_t tiles = (uint32_t)((n + PU_WG - 1) / PU_WG);
+    BS_ENSURE(c->pu.ev_off, n, "the records' event offsets"); BS_ENSURE(c->pu.ev_tile, (size_t)tiles + 1, "the per-workgroup event counts");
+    BS_ENSURE(c->pu.junk, (size_t)tiles + 1, "the per-workgroup scratch"); BS_ENSURE(c->pu.part, (size_t)CV_PLANES * tiles, "the per-workgroup values");
+    BS_ENSURE(c->pu.part2, 2 * (size_t)tiles, "the per-workgroup key bounds");
+    HIPCHK(hipMemsetAsync(c->pu.stat.d, 0, PU_ST_WORDS * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->pu.junk.p, 0, ((size_t)tiles + 1) * 8, c->stream));
+    HIPCHK(hipEventRecord(c->pu.ev[0], c->stream));
+    k_pu_count<<<tiles, PU_WG, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, ix, f, c->pu.ev_off.p, c->pu.ev_tile.p, c->pu.part.p, c->pu.part2.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->pu.ev_tile.p, tiles, c->pu.stat.d + PU_ST_EVENTS, c->pu.part.p, 5, 4, c->pu.stat.d + PU_ST_RECS);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->pu.junk.p, tiles, c->pu.stat.d + PU_ST_JUNK, c->pu.part2.p, 2, 0, c->pu.stat.d + PU_ST_NMIN);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->pu.ev[1], c->stream));
+    HIPCHK(c->pu.stat.fetch(c->stream));
+    HIPCHK(wait_stream(c));                                       // the first wait: how many events, the bounds of their keys, and what was out of range
+    const unsigned long long *st = c->pu.stat.h;
+    if (st[PU_ST_NBAD]) {
+        snprintf(c->err, 512, "%s: record %llu of the sorted array has a block that ends behind position 2^32 - 1: an entry cannot hold it; no table was built", fn, ~st[PU_ST_NBAD]);
+        return DG_ERR_RANGE;
+    }
+    const unsigned long long n_events = st[PU_ST_EVENTS];
+    if (n_events >= 0xFFFFF000ull) { snprintf(c->err, 512, "%s: %llu events are more than the sorter takes (2^32 - 1, less a tile)", fn, n_events); return DG_ERR_CAPACITY; }
+    // (fewer than 2^32 events: every counter below is below 2^32, and the packed sums did not run into each other)
+    const unsigned long long n_counted = (uint32_t)st[PU_ST_RECS], n_left_out = st[PU_ST_RECS] >> 32, aligned = st[PU_ST_ALIGNED], n_blocks = (uint32_t)st[PU_ST_BLK_INS], n_ins = st[PU_ST_BLK_INS] >> 32,
+                             n_mis = (uint32_t)st[PU_ST_MIS_DEL], n_del = st[PU_ST_MIS_DEL] >> 32;
+    c->pu.ms[0] = c->pu.ev.ms(0, 1);
+    auto done = [&](size_t n_before, size_t n_kept, size_t nb, unsigned long long deepest) {
+        float total = 0.f;
+        for (float m : c->pu.ms) total += m;
+        c->pu.valid = true; c->pu.n_entries = n_kept; c->pu.bytes = nb;
+        if (n_sites) *n_sites = n_kept;
+        if (n_bytes) *n_bytes = nb;
+        if (device_ms) *device_ms = total;
+        if (stats) { stats[0] = n_counted; stats[1] = n_blocks; stats[2] = aligned; stats[3] = n_mis; stats[4] = n_del; stats[5] = n_ins; stats[6] = n_before; stats[7] = n_kept; stats[8] = n_left_out; stats[9] = deepest; }
+        return DG_OK;
+    };
+    if (n_events != 2 * n_blocks + n_mis + n_del + n_ins) { snprintf(c->err, 512, "%s: %llu events, but %llu blocks, %llu mismatches, %llu deleted bases and %llu insertions", fn, n_events, n_blocks, n_mis, n_del, n_ins); return DG_ERR_INTERNAL; }
+    if (n_events == 2 * n_blocks) return done(0, 0, 0, 0);        // (no allele event: no site; this covers no event at all)
+    const uint32_t n_ev = (uint32_t)n_events, etiles = (n_ev + PU_WG - 1) / PU_WG;
+    for (int k = 0; k < 2; k++) { BS_ENSURE(c->pu.sort.k[k], (size_t)n_ev, "the events' keys"); BS_ENSURE(c->pu.sort.v[k], (size_t)n_ev, "the events' values"); }
+    BS_ENSURE_SORT(c->pu.sort, n_ev);
+    BS_ENSURE(c->pu.incl_d, (size_t)n_ev, "the scanned depth plane"); BS_ENSURE(c->pu.incl_a, (size_t)n_ev, "the scanned allele plane");
+    BS_ENSURE(c->pu.prev_tail, (size_t)n_ev, "the events' previous tails"); BS_ENSURE(c->pu.mark, (size_t)n_ev, "the events' marks");
+    BS_ENSURE(c->pu.tile_d, (size_t)etiles + 1, "the per-workgroup depth sums"); BS_ENSURE(c->pu.tile_a, (size_t)etiles + 1, "the per-workgroup allele sums");
+    BS_ENSURE(c->pu.tile_last, (size_t)etiles + 1, "the per-workgroup last tails"); BS_ENSURE(c->pu.tile_prev, (size_t)etiles + 1, "the per-workgroup previous tails");
+    BS_ENSURE(c->pu.cnt_tile, (size_t)etiles + 1, "the per-workgroup key counts");
+    const int bits = std::min(cv_key_bits(~st[PU_ST_NMIN], st[PU_ST_MAX]), pu_key_bits_max(n_chr));
+    int which = 0;
+    HIPCHK(hipEventRecord(c->pu.ev[2], c->stream));
+    k_pu_emit<<<tiles, PU_WG, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, ix, f, c->pu.ev_off.p, c->pu.ev_tile.p, n_events, c->pu.sort.k[0].p, c->pu.sort.v[0].p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->pu.ev[3], c->stream));
+    {
+        const int rc = c->pu.sort.sort(c, n_ev, bits, which);
+        if (rc) return rc;
+        c->pu.passes = (bits + 3) / 4;
+    }
+    HIPCHK(hipEventRecord(c->pu.ev[4], c->stream));
+    const uint64_t *skey = c->pu.sort.k[which].p;
+    k_pu_scan<<<etiles, PU_WG, 0, c->stream>>>(skey, c->pu.sort.v[which].p, n_ev, c->pu.incl_d.p, c->pu.incl_a.p, c->pu.tile_d.p, c->pu.tile_a.p);
+    k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->pu.tile_d.p, etiles, (uint64_t *)(c->pu.stat.d + PU_ST_DEPTH_END));
+    k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->pu.tile_a.p, etiles, (uint64_t *)(c->pu.stat.d + PU_ST_ALLELES));
+    k_pu_tails<<<etiles, PU_WG, 0, c->stream>>>(skey, n_ev, c->pu.tile_last.p);
+    k_cv_tails_top<<<1, CV_THREADS, 0, c->stream>>>(c->pu.tile_last.p, etiles, c->pu.tile_prev.p);
+    k_pu_flag<<<etiles, PU_WG, 0, c->stream>>>(skey, c->pu.tile_prev.p, n_ev, c->pu.prev_tail.p, c->pu.mark.p, c->pu.cnt_tile.p);
+    k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->pu.cnt_tile.p, etiles, (uint64_t *)(c->pu.stat.d + PU_ST_MARKS));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->pu.ev[5], c->stream));
+    HIPCHK(c->pu.stat.fetch(c->stream));
+    HIPCHK(wait_stream(c));                                       // the second wait: how many distinct allele keys and sites
+    const size_t n_keys = (size_t)(uint32_t)st[PU_ST_MARKS], n_before = (size_t)(st[PU_ST_MARKS] >> 32);
+    const unsigned long long alleles = st[PU_ST_ALLELES];
+    if (st[PU_ST_DEPTH_END] != 0ull || (unsigned long long)(uint32_t)alleles != n_mis + n_del + n_ins || n_before < 1 || n_before > n_keys || n_keys > n_mis + n_del + n_ins) {
+        snprintf(c->err, 512, "%s: %u events leave the depth 0x%llx behind the last and %llu allele events of %llu, %zu distinct allele keys and %zu sites", fn, n_ev, st[PU_ST_DEPTH_END],
+                 (unsigned long long)(uint32_t)alleles, n_mis + n_del + n_ins, n_keys, n_before);
+        return DG_ERR_INTERNAL;
+    }
+    const uint32_t stiles = (uint32_t)((n_before + PU_WG - 1) / PU_WG);
+    BS_ENSURE(c->pu.ak_key, n_keys, "the allele keys"); BS_ENSURE(c->pu.ak_n, n_keys, "the allele keys' counts"); BS_ENSURE(c->pu.ak_depth, n_keys, "the allele keys' depths");
+    BS_ENSURE(c->pu.site_key, n_before, "the sites' first keys"); BS_ENSURE(c->pu.site_mark, n_before, "the sites' marks"); BS_ENSURE(c->pu.line_off, n_before, "the lines' offsets");
+    BS_ENSURE(c->pu.kept_tile, (size_t)stiles + 1, "the per-workgroup site counts"); BS_ENSURE(c->pu.line_tile, (size_t)stiles + 1, "the per-workgroup line sums");
+    BS_ENSURE(c->pu.part, (size_t)stiles, "the per-workgroup values");
+    // the chromosome names are read and the kernels that use them enqueued under the index's lock, as the coverage track does; the lock is held across the third wait,
+    // whose sizes the writing kernel needs
+    std::unique_lock<std::mutex> lk;
+    const uint32_t *name_off = nullptr; const char *names = nullptr;
+    if (text) { lk = std::unique_lock<std::mutex>(sh->mu); name_off = sh->d_chr_name_off; names = sh->d_chr_names; }
+    HIPCHK(hipEventRecord(c->pu.ev[6], c->stream));
+    k_pu_compact<<<etiles, PU_WG, 0, c->stream>>>(skey, c->pu.incl_d.p, c->pu.incl_a.p, c->pu.tile_d.p, c->pu.tile_a.p, c->pu.prev_tail.p, c->pu.mark.p, c->pu.cnt_tile.p, n_ev, (uint32_t)n_keys,
+                                                   (uint32_t)n_before, c->pu.ak_key.p, c->pu.ak_n.p, c->pu.ak_depth.p, c->pu.site_key.p);
+    HIPCHK(hipEventRecord(c->pu.ev[7], c->stream));
+    k_pu_sites<<<stiles, PU_WG, 0, c->stream>>>(c->pu.ak_key.p, c->pu.ak_n.p, c->pu.ak_depth.p, c->pu.site_key.p, (uint32_t)n_keys, (uint32_t)n_before, ix, min_alt, name_off, c->pu.site_mark.p,
+                                                 c->pu.line_off.p, c->pu.kept_tile.p, c->pu.line_tile.p, c->pu.part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->pu.kept_tile.p, stiles, c->pu.stat.d + PU_ST_KEPT, c->pu.part.p, 1, 0, c->pu.stat.d + PU_ST_MAX_DEPTH);
+    k_tiles_top<uint64_t><<<1, 256, 0, c->stream>>>(c->pu.line_tile.p, stiles, (uint64_t *)(c->pu.stat.d + PU_ST_BYTES));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->pu.ev[8], c->stream));
+    HIPCHK(c->pu.stat.fetch(c->stream));
+    HIPCHK(wait_stream(c));                                       // the third wait: the kept sites and the text's size
+    const size_t n_kept = (size_t)st[PU_ST_KEPT], bytes = text ? (size_t)st[PU_ST_BYTES] : 0;
+    if (n_kept > n_before) { snprintf(c->err, 512, "%s: %zu sites kept of %zu", fn, n_kept, n_before); return DG_ERR_INTERNAL; }
+    HIPCHK(hipEventRecord(c->pu.ev[9], c->stream));
+    if (n_kept) {
+        BS_ENSURE(c->pu.entries, n_kept, "the entries");
+        if (bytes) BS_ENSURE(c->pu.text, bytes, "the text");
+        k_pu_write<<<stiles, PU_WG, 0, c->stream>>>(c->pu.ak_key.p, c->pu.ak_n.p, c->pu.ak_depth.p, c->pu.site_key.p, (uint32_t)n_keys, (uint32_t)n_before, ix, min_alt, name_off, bytes ? names : nullptr,
+                                                     c->pu.site_mark.p, c->pu.line_off.p, c->pu.kept_tile.p, c->pu.line_tile.p, (unsigned long long)n_kept, (unsigned long long)bytes, c->pu.entries.p,
+                                                     c->pu.text.p);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(c->pu.ev[10], c->stream));
+    HIPCHK(wait_stream(c));
+    c->pu.ms[1] = c->pu.ev.ms(2, 3); c->pu.ms[2] = c->pu.ev.ms(3, 4); c->pu.ms[3] = c->pu.ev.ms(4, 5) + c->pu.ev.ms(6, 7); c->pu.ms[4] = c->pu.ev.ms(7, 8) + c->pu.ev.ms(9, 10);
+    return done(n_before, n_kept, bytes, st[PU_ST_MAX_DEPTH]);
+}
+
+extern "C" int dg_bam_pileup_download(dg_ctx *c, dg_site_entry *entries, size_t cap_entries, char *text, size_t cap_text)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->pu.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_pileup_download: no table (dg_bam_pileup_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if ((entries && cap_entries < c->pu.n_entries) || (text && cap_text < c->pu.bytes)) {
+        snprintf(c->err, 512, "dg_bam_pileup_download: output capacity too small: %zu entries and %zu bytes of text are needed", c->pu.n_entries, c->pu.bytes);
+        return DG_ERR_CAPACITY;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (entries && c->pu.n_entries) HIPCHK(hipMemcpyAsync(entries, c->pu.entries.p, c->pu.n_entries * sizeof(dg_site_entry), hipMemcpyDeviceToHost, c->stream));
+    if (text && c->pu.bytes) HIPCHK(hipMemcpyAsync(text, c->pu.text.p, c->pu.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_bam_pileup_device(dg_ctx *c, void **entries, void **text)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->pu.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_pileup_device: no table (dg_bam_pileup_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if (entries) *entries = c->pu.n_entries ? c->pu.entries.p : nullptr;
+    if (text) *text = c->pu.bytes ? c->pu.text.p : nullptr;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_pileup_device_ms(dg_ctx *c, float ms[5], int *n_passes)
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    for (int k = 0; k < 5; k++) ms[k] = c->pu.ms[k];
+    if (n_passes) *n_passes = c->pu.passes;
     return DG_OK;
 }
 

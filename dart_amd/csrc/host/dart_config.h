@@ -44,6 +44,8 @@ struct Config {
     bool sort_bam = false, bam_index = false, mark_dups = false;       // DART_SORT_BAM, DART_BAM_INDEX, DART_MARK_DUPLICATES
     int coverage = 0;                       // DART_COVERAGE: 0, 1 or 2
     uint32_t cov_exclude = 0x704u, cov_min_mapq = 0u;                  // DART_COVERAGE_EXCLUDE, DART_COVERAGE_MIN_MAPQ
+    bool pileup = false;                    // DART_PILEUP
+    uint32_t pu_min_alt = 2u, pu_exclude = 0x704u, pu_min_mapq = 0u;   // DART_PILEUP_MIN_ALT, DART_PILEUP_EXCLUDE, DART_PILEUP_MIN_MAPQ
     double sort_piece_mb = 256.0;           // DART_SORT_PIECE_MB, raw: the piece arithmetic is where the pieces are cut
     const char *gene_gtf = nullptr;         // DART_GENE_COUNTS (empty = unset)
     const char *gene_feature = "exon";      // DART_GENE_FEATURE (empty = unset)
@@ -60,7 +62,7 @@ struct Config {
     bool device_sam = false;                // DART_DEVICE_SAM, which -bo switches off (BAM is built from host text, or on the device)
     bool device_gz = false;                 // DART_DEVICE_GZ with DART_DEVICE_FASTQ, a device formatter, no -bo streaming and no DART_STREAMING
     std::vector<std::pair<std::string, uint32_t>> cov_tracks;      // the coverage tracks: path, strand flags
-    std::string bai_path, md_path, genes_path;                     // <out>.bai, <out>.markdup.txt, <out>.genes.tab; empty = not asked for
+    std::string bai_path, md_path, genes_path, sites_path;         // <out>.bai, <out>.markdup.txt, <out>.genes.tab, <out>.sites.tsv; empty = not asked for
     const char *bam_dev_note = "";          // the `bam=` field of the DART_TIMING lines: the parallel pipeline's ...
     const char *bam_host_note = "";         // ... and the streaming pipeline's
 
@@ -187,6 +189,23 @@ struct Config {
             return 1;
         }
         if (mark_dups) md_path = std::string(out) + ".markdup.txt";
+        // DART_PILEUP=1 beside DART_SORT_BAM=1: the sorted file's variant-site table <out>.sites.tsv, allele counts built on the device from the sorted records and
+        // the index's text (dg_bam_pileup_finish) in place of a `samtools mpileup` over the file; behind the duplicate marking when that is on.  DART_PILEUP_MIN_ALT
+        // (default 2), DART_PILEUP_EXCLUDE (default 0x704) and DART_PILEUP_MIN_MAPQ (default 0) are the filter.  Without the sort there is nothing to pile up: no
+        // output is begun.
+        pileup = env_on("DART_PILEUP");
+        if (pileup && !sort_bam) {
+            fprintf(err_f, "Error! DART_PILEUP=1 needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n");
+            return 1;
+        }
+        if (const char *v = lookup("DART_PILEUP_MIN_ALT")) pu_min_alt = (uint32_t)strtoul(v, nullptr, 0);
+        if (const char *v = lookup("DART_PILEUP_EXCLUDE")) pu_exclude = (uint32_t)strtoul(v, nullptr, 0);
+        if (const char *v = lookup("DART_PILEUP_MIN_MAPQ")) pu_min_mapq = (uint32_t)strtoul(v, nullptr, 0);
+        if (pileup && pu_min_alt == 0u) {
+            fprintf(err_f, "Error! DART_PILEUP_MIN_ALT=0: a site has at least one observation of its top allele\n");
+            return 1;
+        }
+        if (pileup) sites_path = std::string(out) + ".sites.tsv";
         bam_dev_note = sort_bam ? (bgzf_dynamic ? ", bam=device+sorted+dyn" : ", bam=device+sorted") : bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "";
         bam_host_note = !bam ? "" : ", bam=host";
         // A library of .gz FASTQ files small enough to be inflated whole (libdeflate, ~3x zlib; DART_GZ_WHOLE_MAX_GB per file, default 8) goes through the

@@ -357,7 +357,8 @@ struct Output { FILE *sam = nullptr; BamWriter bam; };      // -o: the SAM file 
 //     streams / merge, sort, markdup, a piece, the .bai     BEFORE_CLOSE  yes               yes     yes         yes      (DART_SORT_BAM only:
 //   the same without DART_SORT_BAM                          BEFORE_CLOSE  no                stays   -           -         an unsorted run keeps
 //   bam.close() itself fails                                CLOSE_FAILED  no (not twice)    yes*    yes         yes       its partial file)
-//   a coverage track fails (BAM and .bai are complete)      AFTER_CLOSE   no                stays   stays       yes
+//   a coverage track or the site table fails (BAM and
+//     .bai are complete)                                    AFTER_CLOSE   no                stays   stays       yes      (<out>.sites.tsv goes with the tracks)
 //
 //   * with DART_SORT_BAM; without it the file stays, and none of the others can exist.  (<out>.genes.tab is the gene stage's own.)
 enum AbandonAt { BEFORE_CLOSE, CLOSE_FAILED, AFTER_CLOSE };
@@ -371,6 +372,7 @@ static void abandon_outputs(const Config &c, Output &o, AbandonAt at)
     }
     for (const auto &t : c.cov_tracks) remove(t.first.c_str());      // (no failed run leaves a track or the duplicates' counts, stale ones included)
     if (c.mark_dups) remove(c.md_path.c_str());
+    if (c.pileup) remove(c.sites_path.c_str());
 }
 
 // The contexts: one root per device (the index files go to its HBM inside dg_init_files, main.cpp:231-235 / bwt_index.cpp:147-159), clones
@@ -832,6 +834,28 @@ static int write_coverage(Job &job, Output &o)
     return RUN;
 }
 
+// DART_PILEUP: the variant-site table of the sorted (and, with DART_MARK_DUPLICATES, marked) array, which still lies in HBM; the BAM and its index are complete and
+// closed, and a failure here leaves them as they are
+static int write_pileup(Job &job, Output &o)
+{
+    dg_ctx *root = job.roots[0];
+    const double tp0 = now_s();
+    size_t ns = 0, nb = 0; float ms = 0.f; uint64_t st[10] = {0};
+    int rc = dg_bam_pileup_finish(root, 0, job.cfg.pu_exclude, job.cfg.pu_min_mapq, job.cfg.pu_min_alt, &ns, &nb, st, &ms);
+    std::vector<char> text(nb ? nb : 1);
+    if (!rc) rc = dg_bam_pileup_download(root, nullptr, 0, text.data(), nb);
+    if (rc) { abandon_outputs(job.cfg, o, AFTER_CLOSE); fprintf(stderr, "\nError! DART_PILEUP=1: %s\n", dg_last_error(root)); return 1; }
+    static const char header[] = "#chr\tpos\tref\tdepth\tdepth_rev\tA\tC\tG\tT\tN\tDEL\tINS\tA_rev\tC_rev\tG_rev\tT_rev\tN_rev\tDEL_rev\tINS_rev\n";
+    FILE *pf = fopen(job.cfg.sites_path.c_str(), "wb");
+    const bool ok = pf && fwrite(header, 1, sizeof header - 1, pf) == sizeof header - 1 && fwrite(text.data(), 1, nb, pf) == nb;
+    if (!(pf && fclose(pf) == 0 && ok)) { abandon_outputs(job.cfg, o, AFTER_CLOSE); fprintf(stderr, "Error while writing %s\n", job.cfg.sites_path.c_str()); return 1; }
+    if (job.cfg.timing)
+        fprintf(stderr, "[dart timing] pileup: %llu records, %llu mismatching and %llu deleted bases, %llu insertions; %llu sites, %zu kept, %zu bytes; %.3f s (kernels %.3f s; min alt %u, exclude 0x%x, min mapq %u)\n",
+                (unsigned long long)st[0], (unsigned long long)st[3], (unsigned long long)st[4], (unsigned long long)st[5], (unsigned long long)st[6], ns, nb, now_s() - tp0, ms * 1e-3,
+                job.cfg.pu_min_alt, job.cfg.pu_exclude, job.cfg.pu_min_mapq);
+    return RUN;
+}
+
 // DART_DEVICE_SJ: the clones' tables into their root's, further roots' into the first (downloaded entries, counted again there), then the table is sorted,
 // mapped to chromosomes and printed on the device: the text is junctions.tab
 struct SjTable { std::string text; size_t entries = 0, lines = 0; float finish_ms = 0.f; };
@@ -989,6 +1013,7 @@ int main(int argc, char *argv[])
     if (cfg.bam) { if (!out.bam.close()) { abandon_outputs(cfg, out, CLOSE_FAILED); fprintf(stderr, "Error while writing %s\n", cfg.out); return 1; } }
     else fclose(out.sam);
     if (cfg.coverage && (rc = write_coverage(job, out)) != RUN) return rc;
+    if (cfg.pileup && (rc = write_pileup(job, out)) != RUN) return rc;
     SjTable sj;
     if (cfg.device_sj && (rc = finish_junctions(job, sj)) != RUN) return rc;
     unsigned long long gene_counted = 0;

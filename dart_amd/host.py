@@ -40,6 +40,8 @@ SJ_ENTRY = np.dtype([("g1", "<i8"), ("g2", "<i8"), ("count", "<u4"), ("chr", "<u
 SJ_ENTRIES_ONLY = 1
 COV_ENTRY = np.dtype([("chr", "<u4"), ("start", "<u4"), ("end", "<u4"), ("depth", "<u4")])      # dg_cov_entry
 COV_ENTRIES_ONLY, COV_STRAND_PLUS, COV_STRAND_MINUS = 1, 2, 4
+SITE_ENTRY = np.dtype([("chr", "<u4"), ("pos", "<u4"), ("depth", "<u4"), ("depth_rev", "<u4"), ("ref", "<u4"), ("top", "<u4"), ("n", "<u4", (7,)), ("n_rev", "<u4", (7,))])      # dg_site_entry
+PU_ENTRIES_ONLY = 1
 MD_COUNT_ONLY = 1                                                                                 # DG_MD_COUNT_ONLY
 SJ_NO_CHR = 0xFFFFFFFF
 GENE_EXON = np.dtype([("chr", "<i4"), ("start", "<u4"), ("end", "<u4"), ("strand", "<u4"), ("gene", "<u4")])      # dg_gene_exon
@@ -321,6 +323,12 @@ def _load_lib():
         lib.dg_bam_coverage_device.argtypes = [vp, vp, vp]
         lib.dg_bam_coverage_device_ms.argtypes = [vp, vp, vp]
         lib.dg_bam_coverage_granules.argtypes = [vp]
+    if hasattr(lib, "dg_bam_pileup_finish"):                 # (likewise: the allele counts of the sorted array)
+        lib.dg_bam_pileup_finish.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]
+        lib.dg_bam_pileup_download.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t]
+        lib.dg_bam_pileup_device.argtypes = [vp, vp, vp]
+        lib.dg_bam_pileup_device_ms.argtypes = [vp, vp, vp]
+        lib.dg_bam_pileup_granules.argtypes = [vp]
     if hasattr(lib, "dg_bam_markdup_finish"):                # (likewise: duplicate marking of the sorted array)
         lib.dg_bam_markdup_finish.argtypes = [vp, C.c_uint32, vp, vp]
         lib.dg_bam_markdup_device_ms.argtypes = [vp, vp, vp]
@@ -846,6 +854,29 @@ class DartGPU:
         self.bam_coverage_device_ms_split, self.bam_coverage_passes = tuple(float(x) for x in split), int(passes.value)
         ent = np.zeros(max(int(ne.value), 1), COV_ENTRY); text = np.zeros(max(int(nb.value), 1), np.uint8)
         self._chk(self.lib.dg_bam_coverage_download(self.ctx, ent.ctypes.data, int(ne.value), text.ctypes.data, int(nb.value)), "dg_bam_coverage_download")
+        return ent[:int(ne.value)], text[:int(nb.value)].tobytes()
+
+    # ---- the allele counts of the sorted array (dg_bam_pileup_*): the variant-site table, built in HBM behind bam_sort_finish ----
+    def bam_pileup_granules(self):
+        """(records / events / sites per workgroup, events per tile of the sorter, reference bases per packed compare step) (dg_bam_pileup_granules)"""
+        g = (C.c_int * 3)()
+        self._chk(self.lib.dg_bam_pileup_granules(g), "dg_bam_pileup_granules")
+        return int(g[0]), int(g[1]), int(g[2])
+
+    def bam_pileup_finish(self, exclude: int = 0x704, min_mapq: int = 0, min_alt: int = 2, entries_only: bool = False):
+        """the allele counts of the sorted array (dg_bam_pileup_finish + dg_bam_pileup_download) -> (SITE_ENTRY array, the table's bytes).
+        self.bam_pileup_stats = (records counted, blocks, aligned bases, mismatching bases, deleted bases, insertions, sites before the min_alt filter, sites kept,
+        records left out, largest depth at a kept site), self.bam_pileup_device_ms = the kernels' device time, self.bam_pileup_device_ms_split = (counting walk,
+        emitting walk, event sort, scans and compaction, sites and text), self.bam_pileup_passes = the sorter's passes"""
+        ne = C.c_size_t(0); nb = C.c_size_t(0); ms = C.c_float(0); st = (C.c_uint64 * 10)()
+        self._chk(self.lib.dg_bam_pileup_finish(self.ctx, PU_ENTRIES_ONLY if entries_only else 0, int(exclude), int(min_mapq), int(min_alt), C.byref(ne), C.byref(nb), st, C.byref(ms)),
+                  "dg_bam_pileup_finish")
+        self.bam_pileup_stats, self.bam_pileup_device_ms = tuple(int(x) for x in st), float(ms.value)
+        split = (C.c_float * 5)(); passes = C.c_int(0)
+        self._chk(self.lib.dg_bam_pileup_device_ms(self.ctx, split, C.byref(passes)), "dg_bam_pileup_device_ms")
+        self.bam_pileup_device_ms_split, self.bam_pileup_passes = tuple(float(x) for x in split), int(passes.value)
+        ent = np.zeros(max(int(ne.value), 1), SITE_ENTRY); text = np.zeros(max(int(nb.value), 1), np.uint8)
+        self._chk(self.lib.dg_bam_pileup_download(self.ctx, ent.ctypes.data, int(ne.value), text.ctypes.data, int(nb.value)), "dg_bam_pileup_download")
         return ent[:int(ne.value)], text[:int(nb.value)].tobytes()
 
     # ---- duplicate marking of the sorted array (dg_bam_markdup_*): flag 0x400 written in HBM behind bam_sort_finish, before bam_sort_compress ----

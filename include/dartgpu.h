@@ -580,6 +580,64 @@ int dg_bam_markdup_finish(dg_ctx *, uint32_t flags, uint64_t stats[8], float *de
 int dg_bam_markdup_device_ms(dg_ctx *, float ms[6], int *n_passes);
 int dg_bam_markdup_granules(int out[3]);
 
+/* ---- allele counts of the sorted array, on the device (dart_amd/csrc/dg_pileup.h): a table of the positions at which a read shows something else than the
+ * reference.  The reference program has no such output: an opt-in extension (what `samtools mpileup`, `bam-readcount` or `pysamstats` would compute from the
+ * file).  THE DEFINITION -- no pileup tool exists where this library is built and tested, so this text, not a run of one, is what the tests pin
+ * (tests/pileup_inputs.py is its sequential twin).
+ * Input: the sorted array of dg_bam_sort_finish with no store call behind it.  The call may come before, between or after dg_bam_sort_compress,
+ * dg_bam_index_finish and dg_bam_coverage_finish and disturbs none of them; after dg_bam_markdup_finish it sees the marks.
+ * Per record, fields read byte by byte as the coverage track reads them, and l_seq, u32 at byte 20, and the bases: base i is the high nibble of byte
+ * 36 + l_read_name + 4 n_cigar_op + i / 2 for even i, the low nibble for odd i.
+ *     counted  everything the coverage track asks without a strand selection (placed, pos >= 0, mapped, n_cigar_op > 0, (flag & exclude_flags) == 0,
+ *              mapq >= min_mapq, the CIGAR inside the record and the array), and: the packed bases inside the record and the array; l_seq > 0; the CIGAR's
+ *              read length (the sum of M, I, S, =, X) == l_seq; pos + rlen <= chr_len[refID] (rlen: the sum of M, D, N, =, X).  A record that fails only one
+ *              or both of the last two is not counted and tallied in stats[8].
+ *     range    a block end above 2^32 - 1 on a record that passes the coverage track's conditions: DG_ERR_RANGE, the text names the record's index, as in the
+ *              coverage call.  Tested before the four further conditions: on a chromosome shorter than 2^32 - 1 a block that ends at 2^32 - 1 is a stats[8]
+ *              tally, one that ends past it the error.
+ *     strand   s = flag >> 4 & 1: the read's orientation, which is what strand-bias filters use -- not the coverage track's transcript strand.
+ *     walk     p = pos, q = 0.  M, = or X of length L: read base q + k is observed at reference position p + k for each k < L, then p += L, q += L; a length
+ *              above 0 is also a block [p, p + L).  D: every position p .. p + L - 1 gets one DEL observation, p += L.  N: p += L.  I of length L > 0: one INS
+ *              observation at the anchor max(p, pos + 1) - 1 (the reference base in front of the insertion, or the read's first position when nothing
+ *              precedes it), then q += L.  S: q += L.  H, P: nothing.
+ *     alleles  A C G T N DEL INS = 1 .. 7 in the key, 0 .. 6 in the entry.  The reference base at (chr, p) is the base the index's 2-bit text holds at
+ *              chr_off[chr] + p, so an N of the FASTA is whatever base the indexer stored.  A read nibble 1, 2, 4, 8 is A, C, G, T; nibble 0 ('=') is the
+ *              reference base; every other nibble is N.  A base observation is an event only when its allele differs from the reference base; the CIGAR op
+ *              (M, = or X) plays no part in that.
+ * Events are ordered by chr << 35 | position << 3 | code with a 64-bit value.  Code 0 is a depth event: every block gives (start, +(1 + (s << 32))) and
+ * (end, -(1 + (s << 32))); two 32-bit counters travel in one word.  Codes 1 .. 7 carry 1 + (s << 32).  Depth events sort in front of the allele events of their
+ * position, so the running sum of the code-0 values at an allele event is depth | depth_rev << 32 there (starts at the position included, ends excluded); the
+ * sum of the values of a run of equal keys is that allele's n | n_rev << 32.
+ * Sites: a position with at least one allele event.  n[0..4] count the A, C, G, T and N observed there, the reference allele's own count filled in as depth -
+ * (the other four), n_rev likewise: n[0] + .. + n[4] == depth on both strands.  n[5], n[6]: deleted bases and insertions, outside the depth.  top: the
+ * non-reference allele, DEL and INS included, with the largest n, ties to the smallest code.  A site is kept when n[top] >= min_alt.  Kept sites ascend in
+ * (chr, pos).  The result is a function of the record set: not of order, grid, batch split, ordinals, contexts or growth history.
+ * Text: per kept site "name\tpos+1\tR\tdepth\tdepth_rev\tA\tC\tG\tT\tN\tDEL\tINS\tA_rev\t..\tINS_rev\n", decimal, no header line, names of dg_set_chr_names.
+ *   dg_bam_pileup_finish      flags: DG_PU_ENTRIES_ONLY (no text; the chromosome names are not needed); any other bit, min_alt == 0, no valid sorted array (the
+ *                             text names dg_bam_sort_finish), or text without chromosome names: DG_ERR_ARG.  exclude_flags: 0x704 is the usual filter;
+ *                             min_mapq: 0 counts every record.  stats (may be NULL): [0] records counted, [1] blocks, [2] aligned bases, [3] mismatching
+ *                             bases, [4] deleted bases, [5] insertions, [6] sites before the min_alt filter, [7] sites kept, [8] records left out for l_seq /
+ *                             CIGAR disagreement or for passing their chromosome's end, [9] the largest depth at a kept site.  *device_ms (may be NULL): device
+ *                             time of the kernels, a measurement.  More events than the sorter takes (2^32 - 1, less a tile): DG_ERR_CAPACITY, the count in the
+ *                             text.  The call enqueues on the context's stream and waits three times: for the number of events, for the numbers of distinct
+ *                             allele keys and sites, and for the kept sites and the text's size.  Buffers of its own, never the sorter's or the coverage
+ *                             track's: 8 bytes per record, 56 per event and the sorter's histograms, 24 per distinct allele key, 12 per site, 80 per kept site
+ *                             and its line; a failed allocation gives DG_ERR_CAPACITY, the text names the need.  An empty store gives 0 sites and 0 bytes.
+ *                             Every failure leaves the context, the store, the sorted array, the recorded block sizes, a finished index and a finished track
+ *                             usable; the call may be repeated with other filters.  dg_destroy frees the buffers.
+ *   dg_bam_pileup_download    copies entries and / or text out (either pointer may be NULL); DG_ERR_CAPACITY, nothing written, when a capacity is too small
+ *   dg_bam_pileup_device      entries and text in HBM (NULL when there are none), valid until the next store or pileup call on the context
+ *   dg_bam_pileup_device_ms   the last finish's device time by stage: [0] the counting walk, [1] the emitting walk, [2] the event sort, [3] the scans and the
+ *                             compaction, [4] sites, entries and text; *n_passes (may be NULL): the sorter's passes
+ *   dg_bam_pileup_granules    [0] records / events / sites per workgroup, [1] the sorter's tile (events), [2] reference bases per packed compare step        */
+#define DG_PU_ENTRIES_ONLY 1u
+typedef struct { uint32_t chr, pos, depth, depth_rev, ref /* 0..3 */, top; uint32_t n[7], n_rev[7]; } dg_site_entry;   /* 80 bytes */
+int dg_bam_pileup_finish(dg_ctx *, uint32_t flags, uint32_t exclude_flags, uint32_t min_mapq, uint32_t min_alt, size_t *n_sites, size_t *n_bytes, uint64_t stats[10], float *device_ms);
+int dg_bam_pileup_download(dg_ctx *, dg_site_entry *entries, size_t cap_entries, char *text, size_t cap_text);
+int dg_bam_pileup_device(dg_ctx *, void **entries, void **text);
+int dg_bam_pileup_device_ms(dg_ctx *, float ms[5], int *n_passes);
+int dg_bam_pileup_granules(int out[3]);
+
 /* ---- gene-level read counts on the device (dart_amd/csrc/dg_genecount.h): a ReadsPerGene table per job ----
  * Counted per batch, from the records the batch left in HBM (mates 2i and 2i + 1 are still neighbours), in a per-context table that stays in HBM across
  * batches and is merged at the end of the job, as the junction table is.  Modelled on `htseq-count --mode union` with the layout of STAR's ReadsPerGene.out.tab;
