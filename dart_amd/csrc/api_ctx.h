@@ -183,6 +183,14 @@ struct PuState {
     bool valid = false; size_t n_entries = 0, bytes = 0; float ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f}; int passes = 0;
     hipError_t ready() { const hipError_t e = stat.ready(); return e != hipSuccess ? e : ev.ready(); }
 };
+// the QC tables of the sorted array (dg_qc.h): the words, and nothing else: both kernels add into them
+struct QcState {
+    DBuf<unsigned long long> words;
+    EvSet<3> ev;                                        // around the two kernels
+    bool valid = false; size_t n_words = 0; float ms[2] = {0.f, 0.f};
+    int max_groups = QC_GROUPS;     // DG_QC_MAX_GROUPS: test hook, caps the kernels' grid (a few thousand records drive a workgroup through several trips and flushes)
+    hipError_t ready() { return ev.ready(); }
+};
 // the gene table (dg_genecount.h): resident across batches, (4 + n_genes) x 3 words, counted under annotation generation gen; the per-workgroup lines of
 // the N_* rows; host counts and host records on their way in
 struct GcState {

@@ -21,6 +21,7 @@
 #include "dg_coverage.h"
 #include "dg_markdup.h"
 #include "dg_pileup.h"
+#include "dg_qc.h"
 #include "dg_genecount.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -152,7 +153,7 @@ struct dg_ctx {
     bool batch_done = false;       // the batch on the context has been run and waited for
     bool no_batch = false;         // the last upload was a DG_FQ_CHECK_ONLY: there is nothing to run
     // the library stages' state, one struct each (api_ctx.h); every stage's section of this file drives its own
-    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; GcState gc;
+    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; GcState gc;
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
@@ -189,6 +190,7 @@ static void read_env(dg_ctx *c)
     c->bam.first_cap = (size_t)std::max(0, geti("DG_BAM_FIRST_CAP", 0));
     c->bs.first_cap = (size_t)std::max(0, geti("DG_BAMSORT_FIRST_CAP", 0));
     c->md.hash_bits = geti("DG_MARKDUP_HASH_BITS", MD_HASH_BITS); if (c->md.hash_bits < 1 || c->md.hash_bits > MD_HASH_BITS) c->md.hash_bits = MD_HASH_BITS;
+    c->qc.max_groups = geti("DG_QC_MAX_GROUPS", QC_GROUPS); if (c->qc.max_groups < 1 || c->qc.max_groups > QC_GROUPS) c->qc.max_groups = QC_GROUPS;
     c->env_seed_multi = geti("DG_SEED_MULTI", 4); if (c->env_seed_multi < 0 || c->env_seed_multi > SQF_MULTI_MAX) c->env_seed_multi = SQF_MULTI_MAX;   // rows of an interval that are located and compared with the text at once (0: single rows only)
 }
 
@@ -2695,7 +2697,7 @@ static int bs_view(dg_ctx *c, const char *fn, BsView &v)
     return DG_OK;
 }
 // the bytes of the sorted array changed (a new sort, duplicate flags written): no block of it has been compressed, and no index or track covers it
-static void bs_array_changed(dg_ctx *c) { c->bi.valid = false; c->bi.covered.clear(); c->cv.valid = false; c->pu.valid = false; }
+static void bs_array_changed(dg_ctx *c) { c->bi.valid = false; c->bi.covered.clear(); c->cv.valid = false; c->pu.valid = false; c->qc.valid = false; }
 
 extern "C" int dg_bam_sort_granules(int out[3])
 {
@@ -3625,6 +3627,99 @@ extern "C" int dg_bam_pileup_device_ms(dg_ctx *c, float ms[5], int *n_passes)
     if (!c || !ms) return DG_ERR_ARG;
     for (int k = 0; k < 5; k++) ms[k] = c->pu.ms[k];
     if (n_passes) *n_passes = c->pu.passes;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the QC tables of the sorted array (dg_qc.h): one flat array of counters, both kernels add into it; read-only on the sorted array
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_bam_qc_granules(int out[5])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = QC_WG; out[1] = QC_LANE_BASES; out[2] = QC_STEP; out[3] = QC_FLUSH_TRIPS; out[4] = (int)QC_BIG;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_qc_offsets(int n_chr, size_t out[9])
+{
+    if (!out || n_chr < 1) return DG_ERR_ARG;
+    out[0] = qc_off_fs(); out[1] = qc_off_ch(); out[2] = qc_off_mq(n_chr); out[3] = qc_off_is(n_chr); out[4] = qc_off_rl(n_chr); out[5] = qc_off_pc(n_chr); out[6] = qc_off_id(n_chr);
+    out[7] = qc_off_sn(n_chr); out[8] = qc_words(n_chr);
+    return DG_OK;
+}
+
+extern "C" int dg_bam_qc_format(const uint64_t *words, size_t n_words, int n_chr, const char *const *names, const int64_t *lengths, char *out, size_t cap, size_t *n_bytes)
+{
+    if (n_bytes) *n_bytes = 0;
+    if (!words || !names || !lengths || n_chr < 1 || n_words != qc_words(n_chr) || (!out && cap)) return DG_ERR_ARG;
+    std::string text;
+    qc_format(words, n_chr, names, lengths, text);
+    if (n_bytes) *n_bytes = text.size();
+    if (cap < text.size()) return DG_ERR_CAPACITY;
+    if (!text.empty()) memcpy(out, text.data(), text.size());
+    return DG_OK;
+}
+
+extern "C" int dg_bam_qc_finish(dg_ctx *c, uint32_t flags, uint32_t exclude_flags, uint32_t min_mapq, size_t *n_words, float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_qc_finish";
+    if (n_words) *n_words = 0;
+    if (device_ms) *device_ms = 0.f;
+    c->qc.valid = false; c->qc.n_words = 0; c->qc.ms[0] = c->qc.ms[1] = 0.f;
+    BsView sv;
+    { const int rc = bs_view(c, fn, sv); if (rc) return rc; }
+    if (flags) { snprintf(c->err, 512, "%s: flags 0x%x hold a bit that is not defined", fn, flags); return DG_ERR_ARG; }
+    HIPCHK(c->qc.ready());
+    const size_t n = sv.n, n_raw = sv.n_raw;
+    const int n_chr = sv.n_chr;
+    if (n_chr < 1) { snprintf(c->err, 512, "%s: %d chromosomes", fn, n_chr); return DG_ERR_ARG; }
+    const size_t nw = qc_words(n_chr);
+    BS_ENSURE(c->qc.words, nw, "the tables");
+    HIPCHK(hipMemsetAsync(c->qc.words.p, 0, nw * 8, c->stream));
+    if (n) {
+        const PuFilter f{exclude_flags, min_mapq};
+        const DIndex ix = c->ix;
+        const uint32_t cap = (uint32_t)c->qc.max_groups;
+        const uint32_t g_flag = (uint32_t)std::min<size_t>(cap, (n + QC_WG - 1) / QC_WG), g_cycle = (uint32_t)std::min<size_t>(cap, (n + QC_WG / QC_GROUP - 1) / (QC_WG / QC_GROUP));
+        HIPCHK(hipEventRecord(c->qc.ev[0], c->stream));
+        k_qc_flag<<<g_flag, QC_WG, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, n_chr, c->qc.words.p);
+        HIPCHK(hipEventRecord(c->qc.ev[1], c->stream));
+        k_qc_cycle<<<g_cycle, QC_WG, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, ix, f, c->qc.words.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->qc.ev[2], c->stream));
+    }
+    HIPCHK(wait_stream(c));
+    if (n) { c->qc.ms[0] = c->qc.ev.ms(0, 1); c->qc.ms[1] = c->qc.ev.ms(1, 2); }
+    c->qc.valid = true; c->qc.n_words = nw;
+    if (n_words) *n_words = nw;
+    if (device_ms) *device_ms = c->qc.ms[0] + c->qc.ms[1];
+    return DG_OK;
+}
+
+extern "C" int dg_bam_qc_download(dg_ctx *c, uint64_t *words, size_t cap_words)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->qc.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_qc_download: no tables (dg_bam_qc_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if (!words || cap_words < c->qc.n_words) { snprintf(c->err, 512, "dg_bam_qc_download: output capacity too small: %zu words are needed", c->qc.n_words); return DG_ERR_CAPACITY; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(words, c->qc.words.p, c->qc.n_words * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_bam_qc_device(dg_ctx *c, void **words)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->qc.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_qc_device: no tables (dg_bam_qc_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if (words) *words = c->qc.words.p;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_qc_device_ms(dg_ctx *c, float ms[2])
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    ms[0] = c->qc.ms[0]; ms[1] = c->qc.ms[1];
     return DG_OK;
 }
 

@@ -46,6 +46,8 @@ struct Config {
     uint32_t cov_exclude = 0x704u, cov_min_mapq = 0u;                  // DART_COVERAGE_EXCLUDE, DART_COVERAGE_MIN_MAPQ
     bool pileup = false;                    // DART_PILEUP
     uint32_t pu_min_alt = 2u, pu_exclude = 0x704u, pu_min_mapq = 0u;   // DART_PILEUP_MIN_ALT, DART_PILEUP_EXCLUDE, DART_PILEUP_MIN_MAPQ
+    bool qc = false;                        // DART_QC
+    uint32_t qc_exclude = 0x904u, qc_min_mapq = 0u;                    // DART_QC_EXCLUDE, DART_QC_MIN_MAPQ
     double sort_piece_mb = 256.0;           // DART_SORT_PIECE_MB, raw: the piece arithmetic is where the pieces are cut
     const char *gene_gtf = nullptr;         // DART_GENE_COUNTS (empty = unset)
     const char *gene_feature = "exon";      // DART_GENE_FEATURE (empty = unset)
@@ -63,6 +65,7 @@ struct Config {
     bool device_gz = false;                 // DART_DEVICE_GZ with DART_DEVICE_FASTQ, a device formatter, no -bo streaming and no DART_STREAMING
     std::vector<std::pair<std::string, uint32_t>> cov_tracks;      // the coverage tracks: path, strand flags
     std::string bai_path, md_path, genes_path, sites_path;         // <out>.bai, <out>.markdup.txt, <out>.genes.tab, <out>.sites.tsv; empty = not asked for
+    std::string qc_path;                                           // <out>.qc.txt; empty = not asked for
     const char *bam_dev_note = "";          // the `bam=` field of the DART_TIMING lines: the parallel pipeline's ...
     const char *bam_host_note = "";         // ... and the streaming pipeline's
 
@@ -206,6 +209,18 @@ struct Config {
             return 1;
         }
         if (pileup) sites_path = std::string(out) + ".sites.tsv";
+        // DART_QC=1 beside DART_SORT_BAM=1: the sorted file's QC tables <out>.qc.txt -- flag summary, per-chromosome counts, MAPQ, insert-size and read-length
+        // histograms, per-cycle base / quality / error tables -- built on the device from the sorted records and the index's text (dg_bam_qc_finish) in place of
+        // `samtools flagstat`, `idxstats` and `stats` over the file; behind the duplicate marking when that is on.  DART_QC_EXCLUDE (default 0x904) and
+        // DART_QC_MIN_MAPQ (default 0) pick the records the per-cycle tables profile.  Without the sort there is nothing to look at: no output is begun.
+        qc = env_on("DART_QC");
+        if (qc && !sort_bam) {
+            fprintf(err_f, "Error! DART_QC=1 needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n");
+            return 1;
+        }
+        if (const char *v = lookup("DART_QC_EXCLUDE")) qc_exclude = (uint32_t)strtoul(v, nullptr, 0);
+        if (const char *v = lookup("DART_QC_MIN_MAPQ")) qc_min_mapq = (uint32_t)strtoul(v, nullptr, 0);
+        if (qc) qc_path = std::string(out) + ".qc.txt";
         bam_dev_note = sort_bam ? (bgzf_dynamic ? ", bam=device+sorted+dyn" : ", bam=device+sorted") : bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "";
         bam_host_note = !bam ? "" : ", bam=host";
         // A library of .gz FASTQ files small enough to be inflated whole (libdeflate, ~3x zlib; DART_GZ_WHOLE_MAX_GB per file, default 8) goes through the

@@ -357,8 +357,8 @@ struct Output { FILE *sam = nullptr; BamWriter bam; };      // -o: the SAM file 
 //     streams / merge, sort, markdup, a piece, the .bai     BEFORE_CLOSE  yes               yes     yes         yes      (DART_SORT_BAM only:
 //   the same without DART_SORT_BAM                          BEFORE_CLOSE  no                stays   -           -         an unsorted run keeps
 //   bam.close() itself fails                                CLOSE_FAILED  no (not twice)    yes*    yes         yes       its partial file)
-//   a coverage track or the site table fails (BAM and
-//     .bai are complete)                                    AFTER_CLOSE   no                stays   stays       yes      (<out>.sites.tsv goes with the tracks)
+//   a coverage track, the site table or the QC fails (BAM and
+//     .bai are complete)                                    AFTER_CLOSE   no                stays   stays       yes      (<out>.sites.tsv and <out>.qc.txt go with the tracks)
 //
 //   * with DART_SORT_BAM; without it the file stays, and none of the others can exist.  (<out>.genes.tab is the gene stage's own.)
 enum AbandonAt { BEFORE_CLOSE, CLOSE_FAILED, AFTER_CLOSE };
@@ -373,6 +373,7 @@ static void abandon_outputs(const Config &c, Output &o, AbandonAt at)
     for (const auto &t : c.cov_tracks) remove(t.first.c_str());      // (no failed run leaves a track or the duplicates' counts, stale ones included)
     if (c.mark_dups) remove(c.md_path.c_str());
     if (c.pileup) remove(c.sites_path.c_str());
+    if (c.qc) remove(c.qc_path.c_str());
 }
 
 // The contexts: one root per device (the index files go to its HBM inside dg_init_files, main.cpp:231-235 / bwt_index.cpp:147-159), clones
@@ -856,6 +857,31 @@ static int write_pileup(Job &job, Output &o)
     return RUN;
 }
 
+// DART_QC: the QC tables of the sorted (and, with DART_MARK_DUPLICATES, marked) array, which still lies in HBM; the text is made on the host from the downloaded words.
+// The BAM and its index are complete and closed, and a failure here leaves them as they are
+static int write_qc(Job &job, const HostIndex &ix, Output &o)
+{
+    dg_ctx *root = job.roots[0];
+    const double tq0 = now_s();
+    size_t nw = 0, nb = 0; float ms = 0.f;
+    int rc = dg_bam_qc_finish(root, 0, job.cfg.qc_exclude, job.cfg.qc_min_mapq, &nw, &ms);
+    std::vector<uint64_t> words(nw ? nw : 1);
+    if (!rc) rc = dg_bam_qc_download(root, words.data(), nw);
+    if (rc) { abandon_outputs(job.cfg, o, AFTER_CLOSE); fprintf(stderr, "\nError! DART_QC=1: %s\n", dg_last_error(root)); return 1; }
+    std::vector<const char *> names; std::vector<int64_t> lens;
+    for (size_t k = 0; k < ix.names.size(); k++) { names.push_back(ix.names[k].c_str()); lens.push_back((int64_t)ix.len[k]); }
+    std::vector<char> text(1);
+    rc = dg_bam_qc_format(words.data(), nw, (int)names.size(), names.data(), lens.data(), nullptr, 0, &nb);
+    if (rc == DG_ERR_CAPACITY) { text.resize(nb ? nb : 1); rc = dg_bam_qc_format(words.data(), nw, (int)names.size(), names.data(), lens.data(), text.data(), nb, &nb); }
+    if (rc) { abandon_outputs(job.cfg, o, AFTER_CLOSE); fprintf(stderr, "\nError! DART_QC=1: the tables' text could not be made (%d)\n", rc); return 1; }
+    FILE *qf = fopen(job.cfg.qc_path.c_str(), "wb");
+    const bool ok = qf && fwrite(text.data(), 1, nb, qf) == nb;
+    if (!(qf && fclose(qf) == 0 && ok)) { abandon_outputs(job.cfg, o, AFTER_CLOSE); fprintf(stderr, "Error while writing %s\n", job.cfg.qc_path.c_str()); return 1; }
+    if (job.cfg.timing)
+        fprintf(stderr, "[dart timing] qc: %zu words, %zu bytes; %.3f s (kernels %.3f s; exclude 0x%x, min mapq %u)\n", nw, nb, now_s() - tq0, ms * 1e-3, job.cfg.qc_exclude, job.cfg.qc_min_mapq);
+    return RUN;
+}
+
 // DART_DEVICE_SJ: the clones' tables into their root's, further roots' into the first (downloaded entries, counted again there), then the table is sorted,
 // mapped to chromosomes and printed on the device: the text is junctions.tab
 struct SjTable { std::string text; size_t entries = 0, lines = 0; float finish_ms = 0.f; };
@@ -1014,6 +1040,7 @@ int main(int argc, char *argv[])
     else fclose(out.sam);
     if (cfg.coverage && (rc = write_coverage(job, out)) != RUN) return rc;
     if (cfg.pileup && (rc = write_pileup(job, out)) != RUN) return rc;
+    if (cfg.qc && (rc = write_qc(job, ix, out)) != RUN) return rc;
     SjTable sj;
     if (cfg.device_sj && (rc = finish_junctions(job, sj)) != RUN) return rc;
     unsigned long long gene_counted = 0;

@@ -329,6 +329,14 @@ def _load_lib():
         lib.dg_bam_pileup_device.argtypes = [vp, vp, vp]
         lib.dg_bam_pileup_device_ms.argtypes = [vp, vp, vp]
         lib.dg_bam_pileup_granules.argtypes = [vp]
+    if hasattr(lib, "dg_bam_qc_finish"):                     # (likewise: the QC tables of the sorted array)
+        lib.dg_bam_qc_finish.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp]
+        lib.dg_bam_qc_download.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_bam_qc_device.argtypes = [vp, vp]
+        lib.dg_bam_qc_device_ms.argtypes = [vp, vp]
+        lib.dg_bam_qc_granules.argtypes = [vp]
+        lib.dg_bam_qc_offsets.argtypes = [C.c_int, vp]
+        lib.dg_bam_qc_format.argtypes = [vp, C.c_size_t, C.c_int, vp, vp, vp, C.c_size_t, vp]
     if hasattr(lib, "dg_bam_markdup_finish"):                # (likewise: duplicate marking of the sorted array)
         lib.dg_bam_markdup_finish.argtypes = [vp, C.c_uint32, vp, vp]
         lib.dg_bam_markdup_device_ms.argtypes = [vp, vp, vp]
@@ -407,6 +415,37 @@ class BatchResult:
         r = self.reports[rep_index]
         ops = self.cigar[r["cigar_off"]: r["cigar_off"] + r["n_cigar"]]
         return "".join("%d%s" % (o >> 4, "MIDNS"[o & 15]) for o in ops)
+
+
+QC_SECTIONS = (("FS", (2, 16)), ("CH", None), ("MQ", (256,)), ("IS", (3, 8001)), ("RL", (2, 512)), ("PC", (2, 12, 512)), ("ID", (2, 65)), ("SN", (32,)))
+
+
+def qc_views(lib, words, n_chr: int):
+    """the flat QC words (dg_bam_qc_download) sliced into named views by dg_bam_qc_offsets"""
+    off = (C.c_size_t * 9)()
+    if lib.dg_bam_qc_offsets(int(n_chr), off) != 0 or int(off[8]) != len(words):
+        raise RuntimeError("dg_bam_qc_offsets: %d words do not fit %d chromosomes" % (len(words), n_chr))
+    out = {"words": words}
+    for k, (name, shape) in enumerate(QC_SECTIONS):
+        out[name] = words[int(off[k]):int(off[k + 1])].reshape(shape if shape else (n_chr + 1, 2))
+    return out
+
+
+def qc_text(lib, words, names, lengths) -> bytes:
+    """dg_bam_qc_format: the text of the flat QC words; needs no device"""
+    w = np.ascontiguousarray(words, np.uint64)
+    nm = [n if isinstance(n, bytes) else n.encode() for n in names]
+    arr = (C.c_char_p * len(nm))(*nm)
+    ln = np.ascontiguousarray(lengths, np.int64)
+    nb = C.c_size_t(0)
+    rc = lib.dg_bam_qc_format(w.ctypes.data, len(w), len(nm), arr, ln.ctypes.data, None, 0, C.byref(nb))
+    if rc not in (0, -4):
+        raise RuntimeError("dg_bam_qc_format failed (%d)" % rc)
+    buf = np.zeros(max(int(nb.value), 1), np.uint8)
+    rc = lib.dg_bam_qc_format(w.ctypes.data, len(w), len(nm), arr, ln.ctypes.data, buf.ctypes.data, int(nb.value), C.byref(nb))
+    if rc != 0:
+        raise RuntimeError("dg_bam_qc_format failed (%d)" % rc)
+    return buf[:int(nb.value)].tobytes()
 
 
 class DartGPU:
@@ -878,6 +917,33 @@ class DartGPU:
         ent = np.zeros(max(int(ne.value), 1), SITE_ENTRY); text = np.zeros(max(int(nb.value), 1), np.uint8)
         self._chk(self.lib.dg_bam_pileup_download(self.ctx, ent.ctypes.data, int(ne.value), text.ctypes.data, int(nb.value)), "dg_bam_pileup_download")
         return ent[:int(ne.value)], text[:int(nb.value)].tobytes()
+
+    # ---- the QC tables of the sorted array (dg_bam_qc_*): flag summary, histograms and per-cycle tables, built in HBM behind bam_sort_finish ----
+    def bam_qc_granules(self):
+        """(threads per workgroup, bases per lane, bases per step of the lanes that share a record, trips between two flushes, the record length above which per-base terms go straight
+        to the global words) (dg_bam_qc_granules)"""
+        g = (C.c_int * 5)()
+        self._chk(self.lib.dg_bam_qc_granules(g), "dg_bam_qc_granules")
+        return tuple(int(x) for x in g)
+
+    def bam_qc_finish(self, exclude: int = 0x904, min_mapq: int = 0):
+        """the QC tables of the sorted array (dg_bam_qc_finish + dg_bam_qc_download) -> dict of numpy views into one uint64 array: "words" (all of them), "FS"
+        [2, 16], "CH" [n_chr + 1, 2], "MQ" [256], "IS" [3, 8001], "RL" [2, 512], "PC" [2, 12, 512], "ID" [2, 65], "SN" [32].  self.bam_qc_device_ms = the
+        kernels' device time, self.bam_qc_device_ms_split = (per-record tables, per-cycle pass)"""
+        nw = C.c_size_t(0); ms = C.c_float(0)
+        self._chk(self.lib.dg_bam_qc_finish(self.ctx, 0, int(exclude), int(min_mapq), C.byref(nw), C.byref(ms)), "dg_bam_qc_finish")
+        self.bam_qc_device_ms = float(ms.value)
+        split = (C.c_float * 2)()
+        self._chk(self.lib.dg_bam_qc_device_ms(self.ctx, split), "dg_bam_qc_device_ms")
+        self.bam_qc_device_ms_split = tuple(float(x) for x in split)
+        words = np.zeros(int(nw.value), np.uint64)
+        self._chk(self.lib.dg_bam_qc_download(self.ctx, words.ctypes.data, len(words)), "dg_bam_qc_download")
+        return qc_views(self.lib, words, len(self.index.names))
+
+    def bam_qc_text(self, words) -> bytes:
+        """the text of QC words (a dict of bam_qc_finish, or the flat array) with the index's chromosome names and lengths (dg_bam_qc_format, on the host)"""
+        w = words["words"] if isinstance(words, dict) else words
+        return qc_text(self.lib, w, self.index.names, self.index.chr_len)
 
     # ---- duplicate marking of the sorted array (dg_bam_markdup_*): flag 0x400 written in HBM behind bam_sort_finish, before bam_sort_compress ----
     def bam_markdup_granules(self):

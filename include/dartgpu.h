@@ -638,6 +638,71 @@ int dg_bam_pileup_device(dg_ctx *, void **entries, void **text);
 int dg_bam_pileup_device_ms(dg_ctx *, float ms[5], int *n_passes);
 int dg_bam_pileup_granules(int out[3]);
 
+/* ---- alignment QC of the sorted array, on the device (dart_amd/csrc/dg_qc.h): the flag summary, per-chromosome counts, MAPQ, insert-size and read-length
+ * histograms and the per-cycle base / quality / error tables.  The reference program has no such output: an opt-in extension (what `samtools flagstat`,
+ * `idxstats` and `stats` and Picard CollectInsertSizeMetrics would compute from the file).  THE DEFINITION -- no samtools exists where this library is built and
+ * tested, so this text, not a run of a tool, is what the tests pin (tests/qc_inputs.py is its sequential twin).
+ * Input: the sorted array of dg_bam_sort_finish with no store call behind it; read-only on it.  The call may come before, between or after the other stages and
+ * disturbs none of them; after dg_bam_markdup_finish it sees the marks.
+ * Per record, fields read byte by byte, little endian, as the duplicate marking and the allele counts read them: block_size u32 at byte 0, refID i32 at 4, pos i32
+ * at 8, l_read_name u8 at 12, mapq u8 at 13, n_cigar_op u16 at 16, flag u16 at 18, l_seq u32 at 20, next_refID i32 at 24, next_pos i32 at 28, tlen i32 at 32.
+ * All counters are u64 words in one flat array, the sections in the order below (dg_bam_qc_offsets gives their first words for a given n_chr).
+ *     whole    36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <= 4 + block_size, and that size <= the bytes the array holds from the record's start.
+ *              A record that is not whole adds 1 to SN.malformed and takes part in nothing else.  primary: flag & 0x900 == 0.  mapped: flag & 4 clear.
+ *     FS[2][16]  the flag summary, first index flag >> 9 & 1 (QC fail), every whole record: 0 total, 1 primary, 2 secondary (0x100), 3 supplementary (0x800 without
+ *              0x100), 4 duplicates (0x400), 5 primary duplicates, 6 mapped, 7 primary mapped; rows 8 .. 15 count primary records with flag & 1 only: 8 paired,
+ *              9 read1 (0x40), 10 read2 (0x80), 11 properly paired (0x2 and mapped), 12 mapped with the mate mapped (0x8 clear), 13 singletons (mapped, 0x8 set),
+ *              14 a row-12 record with next_refID != refID, 15 a row-14 record with mapq >= 5.
+ *     CH[n_chr + 1][2]  t = refID when 0 <= refID < n_chr, else n_chr: column 0 mapped, column 1 unmapped whole records.
+ *     MQ[256]  primary mapped records by mapq.
+ *     IS[3][DG_QC_ISIZE]  each pair once: a primary mapped record with flag & 1 set, flag & 8 clear, flag & 0x40 set, next_refID == refID and tlen != 0; bin
+ *              min(|tlen|, 8000), |tlen| in 64 bits.  a = flag >> 4 & 1, b = flag >> 5 & 1: a == b is row 2 (other); else f, r = the forward and the reverse
+ *              mate's position ((pos, next_pos) when a is 0, (next_pos, pos) when a is 1): f <= r row 0 (inward), f > r row 1 (outward).
+ *     RL[2][DG_QC_CYCLES]  primary whole records, mapped or not, by k = flag >> 7 & 1; bin min(l_seq, 511).
+ *     profiled a whole record that the allele counts would count (dg_bam_pileup_finish's `counted`) under exclude_flags and min_mapq (0x904 and 0 are the usual
+ *              filter); one that passes that filter but is left out there or out of range adds 1 to SN.left_out, and no error is raised for it.
+ *     PC[2][12][DG_QC_CYCLES]  every stored base i of a profiled record: class k = flag >> 7 & 1, cycle c = min(s ? l_seq - 1 - i : i, 511), s = flag >> 4 & 1.
+ *              Columns 0 .. 4 the base as sequenced, A C G T other: nibbles 1, 2, 4, 8 are A, C, G, T, complemented when s is set; an '=' nibble inside M / = / X is
+ *              the reference base, complemented when s is set; everything else ('=' inside I or S too) is other.  5 the quality byte (0xff adds 0); 6 aligned (the
+ *              base lies in an M / = / X op); 7 mismatch: aligned, and the allele by the allele counts' rule differs from the reference base at its position;
+ *              8 inserted; 9 soft-clipped; 10 insertions: + 1 at the cycle of the first stored base of every I op with len > 0; 11 deletions: + 1 for every D
+ *              op with len > 0 at the cycle of stored base max(q, 1) - 1, q the read offset at the op.  Word (k * 12 + column) * 512 + c.
+ *     ID[2][DG_QC_INDEL]  profiled records: an I op of length L > 0 in [0][min(L, 64)], a D op in [1][min(L, 64)]; index 0 stays 0.
+ *     SN[32]   0 records, 1 malformed, 2 profiled, 3 left_out, 4 bases (the l_seq of primary whole records), 5 profiled bases, 6 aligned, 7 mismatches,
+ *              8 inserted bases, 9 deleted bases, 10 clipped, 11 N ops (len > 0), 12 skipped bases, 13 bases without quality (0xff), 14 quality sum, 15 pairs
+ *              counted in IS, 16 .. 31 zero.
+ * The tables are a function of the record set: not of order, grid, batch split, ordinals, contexts or growth history (integer sums do not depend on order).
+ *   dg_bam_qc_finish      flags: none is defined, any bit is DG_ERR_ARG; no valid sorted array: DG_ERR_ARG, the text names dg_bam_sort_finish.  *n_words: the size
+ *                         of the array, dg_bam_qc_offsets' [8] for the index's n_chr.  *device_ms (may be NULL): device time of
+ *                         the kernels, a measurement.  One wait.  A buffer of its own (the words); a failed allocation gives DG_ERR_CAPACITY.  An empty store
+ *                         gives all-zero words.  Every failure leaves the context, the store, the sorted array and every finished stage usable; the call may be
+ *                         repeated with another filter.  DG_QC_MAX_GROUPS (read at dg_init) caps the kernels' grid: a test hook, the words do not depend on it.
+ *   dg_bam_qc_download    copies the words out; DG_ERR_CAPACITY, nothing written, when cap_words is too small
+ *   dg_bam_qc_device      the words in HBM, valid until the next store or QC call on the context
+ *   dg_bam_qc_device_ms   the last finish's device time by stage: [0] the per-record tables (lane = record), [1] the per-cycle pass (a quarter wave = record)
+ *   dg_bam_qc_granules    [0] threads per workgroup, [1] bases per lane, [2] bases per step of the lanes that share a record, [3] trips between two flushes of the workgroup's table, [4] the
+ *                         record length above which per-base terms go straight to the global words
+ *   dg_bam_qc_offsets     the first words of FS, CH, MQ, IS, RL, PC, ID, SN for n_chr chromosomes, and [8] the number of words
+ *   dg_bam_qc_format      the text of downloaded words, on the host (no context, no device; integers only): "SN\tname\tvalue", "FS\tname\tpassed\tfailed",
+ *                         "CH\tname\tlength\tmapped\tunmapped" (the last row `*`, length 0), "MQ\tq\tn", "IS\tsize\tinward\toutward\tother", "RL\tlen\tfirst\tlast",
+ *                         "PC\tclass\tcycle+1\tA\tC\tG\tT\tother\tquality\taligned\tmismatch\tinserted\tclipped\tinsertions\tdeletions" (class: first, last),
+ *                         "ID\tlen\tins\tdel".  MQ, IS, RL, ID: the rows with a non-zero count; PC: per class the rows up to the last with a non-zero count.  Behind
+ *                         the sixteen SN words four derived values, floored, 0 when the denominator is 0: error_ppm = mismatches 10^6 / aligned,
+ *                         mean_quality_milli = quality sum 1000 / (profiled bases - bases without quality), insert_mean_milli over the IS bins below 8000,
+ *                         insert_median = the smallest size whose cumulative count over all three rows reaches (pairs + 1) / 2; products in 128 bits.
+ *                         *n_bytes: the text's size; DG_ERR_CAPACITY, nothing written, when cap is smaller (out may be NULL with cap 0 to ask for the size);
+ *                         n_words != the size for n_chr, n_chr < 1 or a missing pointer: DG_ERR_ARG                                                        */
+#define DG_QC_CYCLES 512
+#define DG_QC_ISIZE 8001
+#define DG_QC_INDEL 65
+int dg_bam_qc_finish(dg_ctx *, uint32_t flags, uint32_t exclude_flags, uint32_t min_mapq, size_t *n_words, float *device_ms);
+int dg_bam_qc_download(dg_ctx *, uint64_t *words, size_t cap_words);
+int dg_bam_qc_device(dg_ctx *, void **words);
+int dg_bam_qc_device_ms(dg_ctx *, float ms[2]);
+int dg_bam_qc_granules(int out[5]);
+int dg_bam_qc_offsets(int n_chr, size_t out[9]);
+int dg_bam_qc_format(const uint64_t *words, size_t n_words, int n_chr, const char *const *names, const int64_t *lengths, char *out, size_t cap, size_t *n_bytes);
+
 /* ---- gene-level read counts on the device (dart_amd/csrc/dg_genecount.h): a ReadsPerGene table per job ----
  * Counted per batch, from the records the batch left in HBM (mates 2i and 2i + 1 are still neighbours), in a per-context table that stays in HBM across
  * batches and is merged at the end of the job, as the junction table is.  Modelled on `htseq-count --mode union` with the layout of STAR's ReadsPerGene.out.tab;
