@@ -191,6 +191,15 @@ struct QcState {
     int max_groups = QC_GROUPS;     // DG_QC_MAX_GROUPS: test hook, caps the kernels' grid (a few thousand records drive a workgroup through several trips and flushes)
     hipError_t ready() { return ev.ready(); }
 };
+// MD / NM / ts on the sorted array (dg_tags.h): the second array with its records' places and tile sums -- after a call they ARE the store's sorted array
+// (dg_bam_tags_finish swaps them with bs.sorted, the sorter's other key buffer and bs.tile), and what lies here is the old one, kept for the next call
+struct TgState {
+    DBuf<unsigned char> sorted; DBuf<uint64_t> off, tile, junk, part, part2;
+    DevStat<unsigned long long, TG_ST_WORDS> stat;      // TG_ST_* words
+    EvSet<5> ev;                                        // around the kernels in front of and behind the wait; [4] between the write pass's two
+    float ms[2] = {0.f, 0.f}, write_ms[2] = {0.f, 0.f};
+    hipError_t ready() { const hipError_t e = stat.ready(); return e != hipSuccess ? e : ev.ready(); }
+};
 // the gene table (dg_genecount.h): resident across batches, (4 + n_genes) x 3 words, counted under annotation generation gen; the per-workgroup lines of
 // the N_* rows; host counts and host records on their way in
 struct GcState {

@@ -22,6 +22,7 @@
 #include "dg_markdup.h"
 #include "dg_pileup.h"
 #include "dg_qc.h"
+#include "dg_tags.h"
 #include "dg_genecount.h"
 #include <stdio.h>
 #include <stdlib.h>
@@ -153,7 +154,7 @@ struct dg_ctx {
     bool batch_done = false;       // the batch on the context has been run and waited for
     bool no_batch = false;         // the last upload was a DG_FQ_CHECK_ONLY: there is nothing to run
     // the library stages' state, one struct each (api_ctx.h); every stage's section of this file drives its own
-    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; GcState gc;
+    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; TgState tg; GcState gc;
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
@@ -3860,6 +3861,91 @@ extern "C" int dg_bam_markdup_device_ms(dg_ctx *c, float ms[6], int *n_passes)
     if (!c || !ms) return DG_ERR_ARG;
     for (int k = 0; k < 6; k++) ms[k] = c->md.ms[k];
     if (n_passes) *n_passes = c->md.passes;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// MD / NM / ts on the sorted array (dg_tags.h): the one stage that changes the records' sizes: new lengths, a scan, a rewrite into a second array, which then
+// takes the sorted array's place in everything bs_view hands out
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_bam_tags_granules(int out[3])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = TG_WG; out[1] = TG_LANES; out[2] = PU_STEP;
+    return DG_OK;
+}
+
+template <typename T> static void tg_swap(DBuf<T> &a, DBuf<T> &b) { std::swap(a.p, b.p); std::swap(a.cap, b.cap); }
+
+extern "C" int dg_bam_tags_finish(dg_ctx *c, uint32_t flags, size_t *n_raw_out, uint64_t stats[8], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_tags_finish";
+    if (n_raw_out) *n_raw_out = 0;
+    if (device_ms) *device_ms = 0.f;
+    if (stats) for (int k = 0; k < 8; k++) stats[k] = 0;
+    c->tg.ms[0] = c->tg.ms[1] = c->tg.write_ms[0] = c->tg.write_ms[1] = 0.f;
+    if (flags == 0u || (flags & ~TG_ALL)) { snprintf(c->err, 512, "%s: flags 0x%x are not a non-empty set of DG_TAG_MD, DG_TAG_NM, DG_TAG_TS", fn, flags); return DG_ERR_ARG; }
+    BsView sv;
+    { const int rc = bs_view(c, fn, sv); if (rc) return rc; }
+    HIPCHK(c->tg.ready());
+    const size_t n = sv.n, n_raw = sv.n_raw;
+    if (sv.n_chr < 1) { snprintf(c->err, 512, "%s: %d chromosomes", fn, sv.n_chr); return DG_ERR_ARG; }
+    if (!n) return DG_OK;
+    const DIndex ix = c->ix;
+    const uint32_t tiles = (uint32_t)((n + TG_WG - 1) / TG_WG);
+    BS_ENSURE(c->tg.off, n, "the records' new places"); BS_ENSURE(c->tg.tile, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(c->tg.junk, (size_t)tiles + 1, "the per-workgroup scratch");
+    BS_ENSURE(c->tg.part, (size_t)CV_PLANES * tiles, "the per-workgroup values"); BS_ENSURE(c->tg.part2, (size_t)tiles, "the per-workgroup values");
+    HIPCHK(hipMemsetAsync(c->tg.stat.d, 0, TG_ST_WORDS * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->tg.junk.p, 0, ((size_t)tiles + 1) * 8, c->stream));
+    HIPCHK(hipEventRecord(c->tg.ev[0], c->stream));
+    k_tg_len<<<tiles, TG_WG, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, ix, flags, c->tg.off.p, c->tg.tile.p, c->tg.part.p, c->tg.part2.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->tg.tile.p, tiles, c->tg.stat.d + TG_ST_BYTES, c->tg.part.p, 5, 5, c->tg.stat.d + TG_ST_RECS);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->tg.junk.p, tiles, c->tg.stat.d + TG_ST_JUNK, c->tg.part2.p, 1, 1, c->tg.stat.d + TG_ST_NO_TS);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->tg.ev[1], c->stream));
+    HIPCHK(c->tg.stat.fetch(c->stream));
+    HIPCHK(wait_stream(c));                                       // the one wait in front of the rewrite: the new array's size
+    const unsigned long long *st = c->tg.stat.h;
+    const size_t bytes = (size_t)st[TG_ST_BYTES];
+    const unsigned long long rewritten = (uint32_t)st[TG_ST_RECS], not_eligible = st[TG_ST_RECS] >> 32, aux_bad = (uint32_t)st[TG_ST_AUX_TS];
+    if (rewritten + not_eligible + aux_bad != n) { snprintf(c->err, 512, "%s: %llu records rewritten and %llu + %llu copied of %zu", fn, rewritten, not_eligible, aux_bad, n); return DG_ERR_INTERNAL; }
+    BS_ENSURE(c->tg.sorted, bytes + 8, "the tagged records");
+    HIPCHK(hipEventRecord(c->tg.ev[2], c->stream));
+    k_tg_tail<<<tiles, TG_WG, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, ix, flags, c->tg.off.p, c->tg.tile.p, (unsigned long long)bytes, c->tg.sorted.p);
+    HIPCHK(hipEventRecord(c->tg.ev[4], c->stream));
+    k_tg_copy<<<(unsigned)((n + TG_WG / TG_LANES - 1) / (TG_WG / TG_LANES)), TG_WG, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, ix, flags, c->tg.off.p,
+                                                                                                    c->tg.tile.p, (unsigned long long)bytes, c->tg.sorted.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->tg.ev[3], c->stream));
+    HIPCHK(wait_stream(c));
+    // the new array takes the old one's place: its bytes, every record's place inside its tile, the tiles' sums, the size
+    tg_swap(c->bs.sorted, c->tg.sorted); tg_swap(c->bs.sort.k[c->bs.fin_which ^ 1], c->tg.off); tg_swap(c->bs.tile, c->tg.tile);
+    c->bs.fin_bytes = bytes;
+    bs_array_changed(c);
+    c->tg.ms[0] = c->tg.ev.ms(0, 1); c->tg.ms[1] = c->tg.ev.ms(2, 3);
+    c->tg.write_ms[0] = c->tg.ev.ms(2, 4); c->tg.write_ms[1] = c->tg.ev.ms(4, 3);
+    if (n_raw_out) *n_raw_out = bytes;
+    if (device_ms) *device_ms = c->tg.ms[0] + c->tg.ms[1];
+    if (stats) {
+        stats[0] = rewritten; stats[1] = not_eligible; stats[2] = aux_bad; stats[3] = st[TG_ST_REMOVED]; stats[4] = st[TG_ST_MISM]; stats[5] = st[TG_ST_INDEL];
+        stats[6] = st[TG_ST_AUX_TS] >> 32; stats[7] = st[TG_ST_NO_TS];
+    }
+    return DG_OK;
+}
+
+extern "C" int dg_bam_tags_device_ms(dg_ctx *c, float ms[2])
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    ms[0] = c->tg.ms[0]; ms[1] = c->tg.ms[1];
+    return DG_OK;
+}
+
+// a probe's hook (not in the public header): the write pass by kernel: [0] k_tg_tail, [1] k_tg_copy
+extern "C" int dg_bam_tags_write_ms(dg_ctx *c, float ms[2])
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    ms[0] = c->tg.write_ms[0]; ms[1] = c->tg.write_ms[1];
     return DG_OK;
 }
 

@@ -48,6 +48,7 @@ struct Config {
     uint32_t pu_min_alt = 2u, pu_exclude = 0x704u, pu_min_mapq = 0u;   // DART_PILEUP_MIN_ALT, DART_PILEUP_EXCLUDE, DART_PILEUP_MIN_MAPQ
     bool qc = false;                        // DART_QC
     uint32_t qc_exclude = 0x904u, qc_min_mapq = 0u;                    // DART_QC_EXCLUDE, DART_QC_MIN_MAPQ
+    uint32_t bam_tags = 0u;                 // DART_BAM_TAGS: DG_TAG_* bits, 0 = not asked for
     double sort_piece_mb = 256.0;           // DART_SORT_PIECE_MB, raw: the piece arithmetic is where the pieces are cut
     const char *gene_gtf = nullptr;         // DART_GENE_COUNTS (empty = unset)
     const char *gene_feature = "exon";      // DART_GENE_FEATURE (empty = unset)
@@ -90,6 +91,23 @@ struct Config {
         fprintf(f, "         -min_intron   the minimal intron size [10]\n");
         fprintf(f, "         -v            version\n");
         fprintf(f, "\n");
+    }
+
+    // DART_BAM_TAGS' value -> DG_TAG_* bits; 0: `bad` holds the first word that is none of MD, NM, ts (the whole value for 1 / all misspelt; "" for an empty word)
+    static uint32_t parse_bam_tags(const char *v, std::string &bad)
+    {
+        const std::string s = v;
+        if (s == "1" || s == "all") return DG_TAG_MD | DG_TAG_NM | DG_TAG_TS;
+        uint32_t bits = 0;
+        for (size_t at = 0;;) {
+            const size_t e = s.find(',', at);
+            const std::string w = s.substr(at, e == std::string::npos ? std::string::npos : e - at);
+            if (w == "MD") bits |= DG_TAG_MD; else if (w == "NM") bits |= DG_TAG_NM; else if (w == "ts") bits |= DG_TAG_TS;
+            else { bad = w; return 0; }
+            if (e == std::string::npos) break;
+            at = e + 1;
+        }
+        return bits;
     }
 
     // argv and the environment into *this.  lookup: getenv, or a test's table.  defaults: dg_params_default's, handed in so that this header links without the library.
@@ -221,6 +239,21 @@ struct Config {
         if (const char *v = lookup("DART_QC_EXCLUDE")) qc_exclude = (uint32_t)strtoul(v, nullptr, 0);
         if (const char *v = lookup("DART_QC_MIN_MAPQ")) qc_min_mapq = (uint32_t)strtoul(v, nullptr, 0);
         if (qc) qc_path = std::string(out) + ".qc.txt";
+        // DART_BAM_TAGS beside DART_SORT_BAM=1: a comma list of MD, NM, ts (1 or all: all three): the sorted records get MD:Z, NM as edit distance and ts:A on the
+        // device (dg_bam_tags_finish) behind the duplicate marking and before the first piece is compressed, in place of a `samtools calmd` over the file.  A word
+        // that is none of them ends the run before any output exists; so does a missing sort: there is nothing to tag.
+        if (const char *v = lookup("DART_BAM_TAGS")) {
+            std::string bad;
+            bam_tags = parse_bam_tags(v, bad);
+            if (!bam_tags) {
+                fprintf(err_f, "Error! DART_BAM_TAGS=%s: \"%s\" is none of MD, NM, ts (a comma list of them; 1 or all: all three)\n", v, bad.c_str());
+                return 1;
+            }
+            if (!sort_bam) {
+                fprintf(err_f, "Error! DART_BAM_TAGS=%s needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n", v);
+                return 1;
+            }
+        }
         bam_dev_note = sort_bam ? (bgzf_dynamic ? ", bam=device+sorted+dyn" : ", bam=device+sorted") : bgzf_dynamic ? ", bam=device+dyn" : device_bam ? ", bam=device" : "";
         bam_host_note = !bam ? "" : ", bam=host";
         // A library of .gz FASTQ files small enough to be inflated whole (libdeflate, ~3x zlib; DART_GZ_WHOLE_MAX_GB per file, default 8) goes through the

@@ -743,7 +743,7 @@ static int run_library(Job &job, Output &o, size_t lib, LibPlan &plan)
 }
 
 // DART_SORT_BAM: the clones' stores into their root's, one sort, and the sorted array out in pieces of whole BGZF blocks: compress -> download -> write;
-// DART_MARK_DUPLICATES before the first piece, DART_BAM_INDEX behind the last
+// DART_MARK_DUPLICATES, then DART_BAM_TAGS, before the first piece, DART_BAM_INDEX behind the last
 static int finish_sorted_bam(Job &job, Output &o)
 {
     dg_ctx *root = job.roots[0];
@@ -765,6 +765,14 @@ static int finish_sorted_bam(Job &job, Output &o)
         for (int k = 0; k < 8 && ok; k++) ok = fprintf(mf, "%s\t%llu\n", md_names[k], (unsigned long long)md_stats[k]) > 0;
         if (!(mf && fclose(mf) == 0 && ok)) return fail("Error while writing ", job.cfg.md_path.c_str());
         t_md = now_s() - tm0;
+    }
+    // DART_BAM_TAGS: MD, NM, ts onto the (marked) records, also before any piece is compressed; the array the pieces are cut from is the new one
+    uint64_t tg_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; float tg_ms[2] = {0.f, 0.f}; double t_tg = 0.0;
+    if (job.cfg.bam_tags) {
+        const double tt0 = now_s();
+        if ((rc = dg_bam_tags_finish(root, job.cfg.bam_tags, &n_raw, tg_stats, nullptr))) return fail(rc == DG_ERR_CAPACITY ? "\nError! DART_BAM_TAGS: the tagged records do not fit in device memory: " : "\nError! DART_BAM_TAGS: ", dg_last_error(root));
+        (void)dg_bam_tags_device_ms(root, tg_ms);
+        t_tg = now_s() - tt0;
     }
     const double ts1 = now_s();
     const size_t block = 0xff00;
@@ -803,11 +811,16 @@ static int finish_sorted_bam(Job &job, Output &o)
         char idx_note[128] = "";
         if (job.cfg.bam_index) snprintf(idx_note, sizeof idx_note, "; index %.3f s (kernels %.3f s, %zu bytes)", now_s() - ts2, bai_ms * 1e-3, bai_bytes);
         fprintf(stderr, "[dart timing]%s: %zu records, %zu raw bytes; accumulate (sum over workers) %.3f s; merge + finish %.3f s (kernels %.3f s); compress + download + write %.3f s (BGZF kernels %.3f s, %zu pieces of %zu bytes, %zu bytes out)%s\n",
-                job.cfg.bam_dev_note + 1, n_sorted, n_raw, job.sort_acc_ns.load() * 1e-9, ts1 - ts0 - t_md, fin_ms * 1e-3, ts2 - ts1, z_ms * 1e-3, n_pieces, piece, n_out, idx_note);
+                job.cfg.bam_dev_note + 1, n_sorted, n_raw, job.sort_acc_ns.load() * 1e-9, ts1 - ts0 - t_md - t_tg, fin_ms * 1e-3, ts2 - ts1, z_ms * 1e-3, n_pieces, piece, n_out, idx_note);
         if (job.cfg.mark_dups)
             fprintf(stderr, "[dart timing] markdup: %llu examined records, %llu pairs, %llu fragments; %llu records marked (%llu pairs, %llu fragments); %.3f s (kernels %.3f s)\n",
                     (unsigned long long)md_stats[0], (unsigned long long)md_stats[1], (unsigned long long)md_stats[2], (unsigned long long)md_stats[6], (unsigned long long)md_stats[3],
                     (unsigned long long)md_stats[4], t_md, md_ms * 1e-3);
+        if (job.cfg.bam_tags)
+            fprintf(stderr, "[dart timing] tags: %llu records rewritten, %llu + %llu copied (not eligible, aux unreadable), %llu old tags removed, %llu mismatches, %llu inserted + deleted bases, %llu ts written, %llu + %llu introns without (no motif, conflict); %zu raw bytes; %.3f s (length pass %.3f s, write pass %.3f s)\n",
+                    (unsigned long long)tg_stats[0], (unsigned long long)tg_stats[1], (unsigned long long)tg_stats[2], (unsigned long long)tg_stats[3], (unsigned long long)tg_stats[4],
+                    (unsigned long long)tg_stats[5], (unsigned long long)tg_stats[6], (unsigned long long)(tg_stats[7] & 0xFFFFFFFFull), (unsigned long long)(tg_stats[7] >> 32), n_raw, t_tg,
+                    tg_ms[0] * 1e-3, tg_ms[1] * 1e-3);
     }
     return RUN;
 }

@@ -43,6 +43,7 @@ COV_ENTRIES_ONLY, COV_STRAND_PLUS, COV_STRAND_MINUS = 1, 2, 4
 SITE_ENTRY = np.dtype([("chr", "<u4"), ("pos", "<u4"), ("depth", "<u4"), ("depth_rev", "<u4"), ("ref", "<u4"), ("top", "<u4"), ("n", "<u4", (7,)), ("n_rev", "<u4", (7,))])      # dg_site_entry
 PU_ENTRIES_ONLY = 1
 MD_COUNT_ONLY = 1                                                                                 # DG_MD_COUNT_ONLY
+TAG_MD, TAG_NM, TAG_TS = 1, 2, 4                                                                  # DG_TAG_*
 SJ_NO_CHR = 0xFFFFFFFF
 GENE_EXON = np.dtype([("chr", "<i4"), ("start", "<u4"), ("end", "<u4"), ("strand", "<u4"), ("gene", "<u4")])      # dg_gene_exon
 GENE_NONE, GENE_AMBIG = 0xFFFFFFFF, 0xFFFFFFFE
@@ -341,6 +342,11 @@ def _load_lib():
         lib.dg_bam_markdup_finish.argtypes = [vp, C.c_uint32, vp, vp]
         lib.dg_bam_markdup_device_ms.argtypes = [vp, vp, vp]
         lib.dg_bam_markdup_granules.argtypes = [vp]
+    if hasattr(lib, "dg_bam_tags_finish"):                   # (likewise: MD / NM / ts on the sorted array)
+        lib.dg_bam_tags_finish.argtypes = [vp, C.c_uint32, vp, vp, vp]
+        lib.dg_bam_tags_device_ms.argtypes = [vp, vp]
+        lib.dg_bam_tags_granules.argtypes = [vp]
+        lib.dg_bam_tags_write_ms.argtypes = [vp, vp]                # (a probe's hook, not in include/dartgpu.h)
     if hasattr(lib, "dg_gene_set_annotation"):               # (likewise: gene-level read counts)
         lib.dg_gene_set_annotation.argtypes = [vp, vp, vp]
         lib.dg_batch_accumulate_genes.argtypes = [vp, C.c_int, C.c_uint32, vp]
@@ -965,6 +971,28 @@ class DartGPU:
         self._chk(self.lib.dg_bam_markdup_device_ms(self.ctx, split, C.byref(passes)), "dg_bam_markdup_device_ms")
         self.bam_markdup_device_ms_split, self.bam_markdup_passes = tuple(float(x) for x in split), int(passes.value)
         return self.bam_markdup_stats
+
+    # ---- MD / NM / ts on the sorted array (dg_bam_tags_*): behind bam_sort_finish (and bam_markdup_finish), before bam_sort_compress ----
+    def bam_tags_granules(self):
+        """(records per workgroup of the length pass, lanes per record of the write pass's copy, bases per compare step) (dg_bam_tags_granules)"""
+        g = (C.c_int * 3)()
+        self._chk(self.lib.dg_bam_tags_granules(g), "dg_bam_tags_granules")
+        return int(g[0]), int(g[1]), int(g[2])
+
+    def bam_tags_finish(self, md: bool = True, nm: bool = True, ts: bool = True, flags=None):
+        """rewrites the sorted array with MD:Z, NM (edit distance) and ts:A (dg_bam_tags_finish; flags: the DG_TAG_* bits instead of the three switches) ->
+        (raw bytes of the new array, stats); the stats, also kept as self.bam_tags_stats = (records rewritten, copied verbatim: not eligible, copied verbatim:
+        aux unreadable, old tags removed, mismatches, inserted + deleted bases, ts written, introns without ts: no motif | conflict << 32);
+        self.bam_tags_device_ms = the kernels' device time, self.bam_tags_device_ms_split = (length pass, write pass)"""
+        if flags is None:
+            flags = (TAG_MD if md else 0) | (TAG_NM if nm else 0) | (TAG_TS if ts else 0)
+        nb = C.c_size_t(0); ms = C.c_float(0); st = (C.c_uint64 * 8)()
+        self._chk(self.lib.dg_bam_tags_finish(self.ctx, int(flags), C.byref(nb), st, C.byref(ms)), "dg_bam_tags_finish")
+        self.bam_tags_stats, self.bam_tags_device_ms = tuple(int(x) for x in st), float(ms.value)
+        split = (C.c_float * 2)()
+        self._chk(self.lib.dg_bam_tags_device_ms(self.ctx, split), "dg_bam_tags_device_ms")
+        self.bam_tags_device_ms_split = tuple(float(x) for x in split)
+        return int(nb.value), self.bam_tags_stats
 
     def wait_index(self):
         self._chk(self.lib.dg_index_wait(self.ctx), "dg_index_wait")

@@ -703,6 +703,37 @@ int dg_bam_qc_granules(int out[5]);
 int dg_bam_qc_offsets(int n_chr, size_t out[9]);
 int dg_bam_qc_format(const uint64_t *words, size_t n_words, int n_chr, const char *const *names, const int64_t *lengths, char *out, size_t cap, size_t *n_bytes);
 
+/* ---- MD, NM and ts on the records of the sorted array, on the device (dart_amd/csrc/dg_tags.h): what `samtools calmd` would add to the finished file, written in
+ * HBM in front of the first dg_bam_sort_compress.  The reference program has no such output: an opt-in extension.  THE DEFINITION is the comment at the head of
+ * dg_tags.h -- no samtools exists where this library is built and tested, so that text, not a run of a tool, is what the tests pin (tests/tags_inputs.py is its
+ * sequential twin).  In short: a record the allele counts would count with no filter, whose aux area can be walked, is rewritten: the tags named MD, NM, ts whose
+ * flag bit is set are removed, then NM:C/S/I (edit distance: mismatches + inserted + deleted bases, NOT the mapper's mismatch count), MD:Z (as htslib prints it) and
+ * ts:A (from the intron motifs GT..AG GC..AG / CT..AC CT..GC of every N op of 4 or more bases; the sign is flipped for a reverse read, minimap2's convention;
+ * XS:A is not used because XS:i holds that name) are appended in that order, each when selected; block_size follows.  Every other record is copied verbatim.
+ *   dg_bam_tags_finish      needs the sorted array of dg_bam_sort_finish with no store call behind it (else DG_ERR_ARG, the text names dg_bam_sort_finish).
+ *                           flags: DG_TAG_MD | DG_TAG_NM | DG_TAG_TS; 0, or any other bit: DG_ERR_ARG, nothing enqueued.  Writes a second array with the same
+ *                           records in the same order; afterwards dg_bam_sort_device, dg_bam_sort_compress, dg_bam_markdup_finish, dg_bam_index_finish, the coverage
+ *                           track, the allele counts and the QC tables all work on the new array (*n_raw: its size); what they had built over the old bytes
+ *                           (compressed sizes, an index, a track, a table) is void, as behind dg_bam_sort_finish.  The store is untouched: another
+ *                           dg_bam_sort_finish gives the untagged array again.  A second call with the same flags gives the same bytes as one.  stats (may be NULL):
+ *                           [0] records rewritten, [1] copied verbatim: not eligible, [2] copied verbatim: aux area unreadable, [3] old tags removed, [4] mismatches
+ *                           and [5] inserted + deleted bases of the rewritten records, [6] ts written, [7] records with an intron and no ts: no motif | conflict
+ *                           << 32.  *device_ms (may be NULL): both kernels' device time.  Two waits.  Memory: the new array and 8 bytes per record; the old array's
+ *                           buffer is kept for the next call.  A failed allocation: DG_ERR_CAPACITY, the text names the array and its size.  Every failure leaves
+ *                           the context, the store and the OLD sorted array valid.  An empty store gives 0 bytes.  The bytes do not depend on the grid, the batch
+ *                           split, the contexts or the store's growth history.
+ *                           Measured (profiles/tags/tags_rate.json, one MI355X, 2.0 M records of 2x101, 432 MB): 2.42 ms of kernels -- length pass 0.61 ms, write pass
+ *                           1.81 ms (2.45 times k_bs_gather's 0.74 ms over the same records) -- beside 17.9 ms of BGZF kernels over the tagged array.
+ *   dg_bam_tags_device_ms   the last finish's device time: [0] the length pass (lane = record), [1] the write pass (the new tags, lane = record; the bytes that
+ *                           stay, sixteen lanes = record)
+ *   dg_bam_tags_granules    [0] records per workgroup of the length pass, [1] lanes per record of the write pass's copy, [2] bases per compare step       */
+#define DG_TAG_MD 1u
+#define DG_TAG_NM 2u
+#define DG_TAG_TS 4u
+int dg_bam_tags_finish(dg_ctx *, uint32_t flags, size_t *n_raw, uint64_t stats[8], float *device_ms);
+int dg_bam_tags_device_ms(dg_ctx *, float ms[2]);
+int dg_bam_tags_granules(int out[3]);
+
 /* ---- gene-level read counts on the device (dart_amd/csrc/dg_genecount.h): a ReadsPerGene table per job ----
  * Counted per batch, from the records the batch left in HBM (mates 2i and 2i + 1 are still neighbours), in a per-context table that stays in HBM across
  * batches and is merged at the end of the job, as the junction table is.  Modelled on `htseq-count --mode union` with the layout of STAR's ReadsPerGene.out.tab;
