@@ -3418,37 +3418,46 @@ extern "C" int dg_bam_coverage_finish(dg_ctx *c, uint32_t flags, uint32_t exclud
     return done(n_ent, bytes, n_bp, c->cv.stat.h[CV_ST_COVERED], c->cv.stat.h[CV_ST_MAX_DEPTH]);
 }
 
-extern "C" int dg_bam_coverage_download(dg_ctx *c, dg_cov_entry *entries, size_t cap_entries, char *text, size_t cap_text)
+// ---- the accessors of the two table stages (the coverage track, the allele counts): S = CvState / PuState; the function is dg_bam_<stage>_<call>, `noun` what
+// its texts call the result ----
+template <class S, class E>
+static int table_download(dg_ctx *c, S dg_ctx::*m, const char *stage, const char *noun, E *entries, size_t cap_entries, char *text, size_t cap_text)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->cv.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_coverage_download: no track (dg_bam_coverage_finish first, and no store call behind it)"); return DG_ERR_ARG; }
-    if ((entries && cap_entries < c->cv.n_entries) || (text && cap_text < c->cv.bytes)) {
-        snprintf(c->err, 512, "dg_bam_coverage_download: output capacity too small: %zu entries and %zu bytes of text are needed", c->cv.n_entries, c->cv.bytes);
+    S &st = c->*m;
+    if (!st.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_%s_download: no %s (dg_bam_%s_finish first, and no store call behind it)", stage, noun, stage); return DG_ERR_ARG; }
+    if ((entries && cap_entries < st.n_entries) || (text && cap_text < st.bytes)) {
+        snprintf(c->err, 512, "dg_bam_%s_download: output capacity too small: %zu entries and %zu bytes of text are needed", stage, st.n_entries, st.bytes);
         return DG_ERR_CAPACITY;
     }
     HIPCHK(hipSetDevice(c->device));
-    if (entries && c->cv.n_entries) HIPCHK(hipMemcpyAsync(entries, c->cv.entries.p, c->cv.n_entries * sizeof(dg_cov_entry), hipMemcpyDeviceToHost, c->stream));
-    if (text && c->cv.bytes) HIPCHK(hipMemcpyAsync(text, c->cv.text.p, c->cv.bytes, hipMemcpyDeviceToHost, c->stream));
+    if (entries && st.n_entries) HIPCHK(hipMemcpyAsync(entries, st.entries.p, st.n_entries * sizeof(E), hipMemcpyDeviceToHost, c->stream));
+    if (text && st.bytes) HIPCHK(hipMemcpyAsync(text, st.text.p, st.bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(wait_stream(c));
     return DG_OK;
 }
-
-extern "C" int dg_bam_coverage_device(dg_ctx *c, void **entries, void **text)
+template <class S>
+static int table_device(dg_ctx *c, S dg_ctx::*m, const char *stage, const char *noun, void **entries, void **text)
 {
     if (!c) return DG_ERR_ARG;
-    if (!c->cv.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_coverage_device: no track (dg_bam_coverage_finish first, and no store call behind it)"); return DG_ERR_ARG; }
-    if (entries) *entries = c->cv.n_entries ? c->cv.entries.p : nullptr;
-    if (text) *text = c->cv.bytes ? c->cv.text.p : nullptr;
+    S &st = c->*m;
+    if (!st.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_%s_device: no %s (dg_bam_%s_finish first, and no store call behind it)", stage, noun, stage); return DG_ERR_ARG; }
+    if (entries) *entries = st.n_entries ? st.entries.p : nullptr;
+    if (text) *text = st.bytes ? st.text.p : nullptr;
+    return DG_OK;
+}
+template <class S>
+static int table_device_ms(dg_ctx *c, S dg_ctx::*m, float ms[5], int *n_passes)
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    for (int k = 0; k < 5; k++) ms[k] = (c->*m).ms[k];
+    if (n_passes) *n_passes = (c->*m).passes;
     return DG_OK;
 }
 
-extern "C" int dg_bam_coverage_device_ms(dg_ctx *c, float ms[5], int *n_passes)
-{
-    if (!c || !ms) return DG_ERR_ARG;
-    for (int k = 0; k < 5; k++) ms[k] = c->cv.ms[k];
-    if (n_passes) *n_passes = c->cv.passes;
-    return DG_OK;
-}
+extern "C" int dg_bam_coverage_download(dg_ctx *c, dg_cov_entry *entries, size_t cap_entries, char *text, size_t cap_text) { return table_download(c, &dg_ctx::cv, "coverage", "track", entries, cap_entries, text, cap_text); }
+extern "C" int dg_bam_coverage_device(dg_ctx *c, void **entries, void **text) { return table_device(c, &dg_ctx::cv, "coverage", "track", entries, text); }
+extern "C" int dg_bam_coverage_device_ms(dg_ctx *c, float ms[5], int *n_passes) { return table_device_ms(c, &dg_ctx::cv, ms, n_passes); }
 
 // ------------------------------------------------------------------------------------------
 // the allele counts of the sorted array (dg_pileup.h): the records' bases against the index's 2-bit text, in buffers of its own
@@ -3599,37 +3608,9 @@ extern "C" int dg_bam_pileup_finish(dg_ctx *c, uint32_t flags, uint32_t exclude_
     return done(n_before, n_kept, bytes, st[PU_ST_MAX_DEPTH]);
 }
 
-extern "C" int dg_bam_pileup_download(dg_ctx *c, dg_site_entry *entries, size_t cap_entries, char *text, size_t cap_text)
-{
-    if (!c) return DG_ERR_ARG;
-    if (!c->pu.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_pileup_download: no table (dg_bam_pileup_finish first, and no store call behind it)"); return DG_ERR_ARG; }
-    if ((entries && cap_entries < c->pu.n_entries) || (text && cap_text < c->pu.bytes)) {
-        snprintf(c->err, 512, "dg_bam_pileup_download: output capacity too small: %zu entries and %zu bytes of text are needed", c->pu.n_entries, c->pu.bytes);
-        return DG_ERR_CAPACITY;
-    }
-    HIPCHK(hipSetDevice(c->device));
-    if (entries && c->pu.n_entries) HIPCHK(hipMemcpyAsync(entries, c->pu.entries.p, c->pu.n_entries * sizeof(dg_site_entry), hipMemcpyDeviceToHost, c->stream));
-    if (text && c->pu.bytes) HIPCHK(hipMemcpyAsync(text, c->pu.text.p, c->pu.bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(wait_stream(c));
-    return DG_OK;
-}
-
-extern "C" int dg_bam_pileup_device(dg_ctx *c, void **entries, void **text)
-{
-    if (!c) return DG_ERR_ARG;
-    if (!c->pu.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_pileup_device: no table (dg_bam_pileup_finish first, and no store call behind it)"); return DG_ERR_ARG; }
-    if (entries) *entries = c->pu.n_entries ? c->pu.entries.p : nullptr;
-    if (text) *text = c->pu.bytes ? c->pu.text.p : nullptr;
-    return DG_OK;
-}
-
-extern "C" int dg_bam_pileup_device_ms(dg_ctx *c, float ms[5], int *n_passes)
-{
-    if (!c || !ms) return DG_ERR_ARG;
-    for (int k = 0; k < 5; k++) ms[k] = c->pu.ms[k];
-    if (n_passes) *n_passes = c->pu.passes;
-    return DG_OK;
-}
+extern "C" int dg_bam_pileup_download(dg_ctx *c, dg_site_entry *entries, size_t cap_entries, char *text, size_t cap_text) { return table_download(c, &dg_ctx::pu, "pileup", "table", entries, cap_entries, text, cap_text); }
+extern "C" int dg_bam_pileup_device(dg_ctx *c, void **entries, void **text) { return table_device(c, &dg_ctx::pu, "pileup", "table", entries, text); }
+extern "C" int dg_bam_pileup_device_ms(dg_ctx *c, float ms[5], int *n_passes) { return table_device_ms(c, &dg_ctx::pu, ms, n_passes); }
 
 // ------------------------------------------------------------------------------------------
 // the QC tables of the sorted array (dg_qc.h): one flat array of counters, both kernels add into it; read-only on the sorted array

@@ -7,9 +7,7 @@
 // record, with two deliberate differences (named below).  No samtools or htslib binary exists where this project is built and tested: this definition -- not
 // a run of samtools -- is what the tests pin (tests/bamidx_inputs.py is its sequential twin).
 //
-// Per sorted record (fields are read byte by byte: records are unaligned; block_size is at byte 0):
-//   refID int32 at byte 4, pos int32 at byte 8, l_read_name u8 at byte 12, n_cigar_op u16 at byte 16, flag u16 at byte 18;
-//   the CIGAR ops are u32 little endian (len << 4 | op) and start at byte 36 + l_read_name
+// Per sorted record (its fields and CIGAR as bam_head and bam_cigar_walk of dg_bamrec.h read them):
 //   placed   0 <= refID < n_chr.  All other records come last in the sorted array; they are only counted, in n_no_coor
 //   mapped   flag & 4 is clear
 //   rlen     the sum of len over ops 0, 2, 3, 7, 8 (M, D, N, =, X) when the record is mapped and n_cigar_op > 0, else 0
@@ -77,21 +75,15 @@ struct BiRec { int32_t refid, pos; long long beg, end, rlen; uint32_t bin; bool 
 BI_HD BiRec bi_record(const unsigned char *rec, uint64_t avail, int n_chr)
 {
     BiRec r; r.refid = -1; r.pos = -1; r.beg = 0; r.end = 1; r.rlen = 0; r.bin = 4680u; r.placed = false; r.mapped = false;
-    if (avail < BAM_FIXED) return r;
-    r.refid = (int32_t)bs_le32(rec + 4); r.pos = (int32_t)bs_le32(rec + 8);
-    const uint32_t l_name = rec[12], n_cigar = (uint32_t)rec[16] | (uint32_t)rec[17] << 8, flag = (uint32_t)rec[18] | (uint32_t)rec[19] << 8;
+    const BamHead h = bam_head(rec, avail);
+    if (!h.ok) return r;
+    r.refid = h.refid; r.pos = h.pos;
     r.placed = r.refid >= 0 && r.refid < n_chr;
-    r.mapped = !(flag & 4u);
-    if (r.mapped && n_cigar) {
-        uint64_t size = 4ull + (uint64_t)bs_le32(rec);
-        if (size > avail) size = avail;
-        const uint64_t at = (uint64_t)BAM_FIXED + l_name;
-        uint64_t n_ops = at <= size ? (size - at) / 4 : 0;
-        if (n_ops > n_cigar) n_ops = n_cigar;
-        for (uint64_t k = 0; k < n_ops; k++) {
-            const uint32_t c = bs_le32(rec + at + 4 * k), op = c & 15u;
-            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) r.rlen += (long long)(c >> 4);
-        }
+    r.mapped = !(h.flag & 4u);
+    if (r.mapped && h.n_cigar) {                               // the ops are cut to what fits in the record and the array; nothing is refused
+        uint64_t n_ops = h.cigar_at <= h.size ? (h.size - h.cigar_at) / 4 : 0;
+        if (n_ops > h.n_cigar) n_ops = h.n_cigar;
+        r.rlen = (long long)bam_cigar_walk(rec, h.cigar_at, n_ops, 0, BamNoOp()).p;
     }
     const long long end_raw = (long long)r.pos + (r.rlen ? r.rlen : 1);
     r.beg = r.pos > 0 ? (long long)r.pos : 0;
@@ -177,12 +169,6 @@ k_bi_coff(const uint32_t *__restrict__ sizes, uint32_t n_blocks, unsigned long l
     if (threadIdx.x == 0) { coff[n_blocks] = carry; stat[BI_ST_COFF_END] = carry; }
 }
 
-// where sorted record i starts in the array (k_bs_len's offsets and the scanned per-tile sums); i == n: the array's end
-__device__ __forceinline__ uint64_t bi_rec_start(const uint64_t *dst_off, const uint64_t *tile_base, uint32_t i, uint32_t n, uint64_t n_raw)
-{
-    return i < n ? tile_base[i / BS_THREADS] + dst_off[i] : n_raw;
-}
-
 __global__ void __launch_bounds__(BI_THREADS)
 k_bi_rec(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__ dst_off, const uint64_t *__restrict__ tile_base, uint32_t n, unsigned long long n_raw,
          const uint64_t *__restrict__ coff, uint32_t n_blocks, int n_chr, uint64_t *__restrict__ key, uint64_t *__restrict__ voff, uint32_t *__restrict__ span,
@@ -193,7 +179,7 @@ k_bi_rec(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__ 
     int32_t refid = -1;
     unsigned long long windows = 0, mapped = 0, unmapped = 0, lo = BI_NONE, hi = 0;
     if (i < n) {
-        const uint64_t at = bi_rec_start(dst_off, tile_base, i, n, n_raw);
+        const uint64_t at = bam_rec_start(dst_off, tile_base, i);
         BiRec r; r.placed = false;
         if (at < n_raw) r = bi_record(sorted + at, n_raw - at, n_chr);
         key[i] = r.placed ? bi_key(r) : BI_NONE;

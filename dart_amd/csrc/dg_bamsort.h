@@ -2,8 +2,7 @@
 // record one 64-bit key and its byte offset in the store), and at the end of the job one stable radix sort (dg_sort.h) and one gather leave all records in
 // one contiguous array in coordinate order, which dg_bgzf.h then compresses piece by piece.  The reference has no such output: an opt-in extension.
 //
-// The order is defined by a record's own bytes (SAM specification 4.2; records are not 4-byte aligned, so every field is read byte by byte):
-//   refID  int32 at byte 4, pos int32 at byte 8, flag uint16 at byte 18, little endian (byte 0 is block_size)
+// The order is defined by a record's own fields (bam_head of dg_bamrec.h reads them):
 //   tid' = refID when 0 <= refID < n_chr, else n_chr: unplaced records come last
 //   key  = tid' << 33 | (uint32)(pos + 1) << 1 | (flag >> 4 & 1)
 //   ascending key; equal keys keep their input order: ascending batch ordinal, then the record's place in its batch
@@ -23,29 +22,27 @@
 // or the growth history of the store.  The key, the two walks with their checks and the segment order are host-callable (tests/native/bamsort_checks.hip).
 #ifndef DG_BAMSORT_H
 #define DG_BAMSORT_H
-#include "dg_bamfmt.h"
+#include "dg_bamrec.h"
 #include "dg_sort.h"
 #include "dg_wgscan.h"
 #include <algorithm>
 
 #define BS_HD __host__ __device__ __forceinline__
-#define BS_THREADS 256           // reads per workgroup of k_bs_count / k_bs_emit (dg_bam_sort_granules [0])
+// BS_THREADS (dg_bamrec.h) is also the reads per workgroup of k_bs_count / k_bs_emit
 #define BS_MIN_BYTES 4096        // the smallest store (dg_bam_sort_granules [2])
 #define BS_GATHER_WAVES 4        // records per workgroup of k_bs_gather
 static_assert(BS_THREADS == SAM_LEN_THREADS, "k_bs_count reads k_bam_len's per-workgroup offsets");
 static_assert(BS_THREADS == WG_THREADS, "k_bs_count and k_bs_len scan with d_wg_exclusive");
 
-BS_HD uint32_t bs_le32(const unsigned char *p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
 // bits that hold tid' (0 .. n_chr)
 BS_HD int bs_chr_bits(int n_chr) { int b = 0; for (uint32_t x = (uint32_t)n_chr; x; x >>= 1) b++; return b; }
 BS_HD int bs_key_bits(int n_chr) { return 33 + bs_chr_bits(n_chr); }
-// the sort key of the record that starts (with its block_size) at rec
+// the sort key of the record that starts (with its block_size) at rec.  Nothing is checked: the caller's walk has seen the fixed part inside its range
 BS_HD uint64_t bs_key(const unsigned char *rec, int n_chr)
 {
-    const int32_t refid = (int32_t)bs_le32(rec + 4);
-    const uint32_t pos1 = bs_le32(rec + 8) + 1u, flag = (uint32_t)rec[18] | (uint32_t)rec[19] << 8;
-    const uint64_t tid = refid >= 0 && refid < n_chr ? (uint64_t)refid : (uint64_t)n_chr;
-    return tid << 33 | (uint64_t)pos1 << 1 | (uint64_t)(flag >> 4 & 1u);
+    const BamHead h = bam_head(rec, BAM_FIXED);
+    const uint64_t tid = h.refid >= 0 && h.refid < n_chr ? (uint64_t)h.refid : (uint64_t)n_chr;
+    return tid << 33 | (uint64_t)((uint32_t)h.pos + 1u) << 1 | (uint64_t)(h.flag >> 4 & 1u);
 }
 
 // ---- records from outside (dg_bam_sort_add): every field the store relies on is checked ----
@@ -68,11 +65,11 @@ BS_HD int bs_record_check(const unsigned char *p, size_t left, int n_chr, size_t
     const uint64_t bs = bs_le32(p);
     if (bs < 32) return BS_REC_SIZE;
     if (bs > left - 4) return BS_REC_TRUNCATED;
-    const uint64_t l_name = p[12], n_cigar = (uint64_t)p[16] | (uint64_t)p[17] << 8, l_seq = bs_le32(p + 20);
-    if (bs < 32 + l_name + 4 * n_cigar + (l_seq + 1) / 2 + l_seq) return BS_REC_SIZE;
-    if (l_name == 0) return BS_REC_NAME;
-    if ((int32_t)bs_le32(p + 4) >= n_chr) return BS_REC_REFID;
-    if ((int32_t)bs_le32(p + 8) < -1) return BS_REC_POS;
+    const BamHead h = bam_head(p, left);                      // (bs >= 32 lies inside left: the fixed part does)
+    if (h.block < h.aux_at) return BS_REC_SIZE;
+    if (h.l_name == 0) return BS_REC_NAME;
+    if (h.refid >= n_chr) return BS_REC_REFID;
+    if (h.pos < -1) return BS_REC_POS;
     *size = (size_t)bs + 4;
     return BS_REC_OK;
 }
@@ -187,7 +184,7 @@ k_bs_gather(const unsigned char *__restrict__ store, const int64_t *__restrict__
     const uint64_t i = (uint64_t)blockIdx.x * BS_GATHER_WAVES + (threadIdx.x >> 6);
     if (i >= n) return;
     const unsigned char *s = store + offs[i];
-    const uint64_t at = tile_base[i / BS_THREADS] + dst_off[i];
+    const uint64_t at = bam_rec_start(dst_off, tile_base, (uint32_t)i);
     unsigned char *d = out + at;
     const uint32_t len = 4u + bs_le32(s);
     if (at + len > out_bytes) return;                          // (the lengths add up to the store's bytes; a record that would not fit is never written)

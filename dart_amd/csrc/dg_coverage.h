@@ -7,9 +7,7 @@
 // (blocks, 0-based half-open intervals, zero depth not printed) with the default filter of `samtools depth` (FLAG 0x704 skipped) -- is what the tests pin
 // (tests/coverage_inputs.py is its sequential twin).
 //
-// Per sorted record (fields are read byte by byte: records are unaligned; block_size is at byte 0):
-//   refID int32 at byte 4, pos int32 at byte 8, l_read_name u8 at byte 12, mapq u8 at byte 13, n_cigar_op u16 at byte 16, flag u16 at byte 18;
-//   the CIGAR ops are u32 little endian (len << 4 | op) and start at byte 36 + l_read_name.  No read ever passes the record's block_size or the array's end.
+// Per sorted record (its fields and CIGAR as bam_head and bam_cigar_walk of dg_bamrec.h read them; no read ever passes the record's block_size or the array's end):
 //   counted  all of: 0 <= refID < n_chr; pos >= 0; flag & 4 clear; n_cigar_op > 0; (flag & exclude_flags) == 0; mapq >= min_mapq; the strand selection, if
 //            any, passes; and the CIGAR lies inside the record and the array: 36 + l_read_name + 4 n_cigar_op <= 4 + block_size (dg_bam_sort_add refuses a
 //            record that breaks the last rule, so it is reachable only by the lane code's tests)
@@ -79,20 +77,16 @@ CV_HD bool cv_strand_passes(uint32_t flags, uint32_t flag)
     if (want == 0u || want == (DG_COV_STRAND_PLUS | DG_COV_STRAND_MINUS)) return true;
     return want == DG_COV_STRAND_PLUS ? s == 0u : s == 1u;
 }
-// the record that starts (with its block_size) at rec, `avail` bytes of the array behind rec
-CV_HD CvRec cv_record(const unsigned char *rec, uint64_t avail, int n_chr, const CvFilter &f)
+// the record with the fixed fields h: counted only when its whole CIGAR lies inside the record and the array
+CV_HD CvRec cv_record(const BamHead &h, int n_chr, const CvFilter &f)
 {
-    CvRec r; r.counted = false; r.refid = -1; r.pos = -1; r.cigar_at = 0; r.n_ops = 0;
-    if (avail < BAM_FIXED) return r;
-    r.refid = (int32_t)bs_le32(rec + 4); r.pos = (int32_t)bs_le32(rec + 8);
-    const uint32_t l_name = rec[12], mapq = rec[13], n_cigar = (uint32_t)rec[16] | (uint32_t)rec[17] << 8, flag = (uint32_t)rec[18] | (uint32_t)rec[19] << 8;
-    uint64_t size = 4ull + (uint64_t)bs_le32(rec);
-    if (size > avail) size = avail;
-    r.cigar_at = (uint64_t)BAM_FIXED + l_name; r.n_ops = n_cigar;
-    r.counted = r.refid >= 0 && r.refid < n_chr && r.pos >= 0 && !(flag & 4u) && n_cigar > 0u && !(flag & f.exclude) && mapq >= f.min_mapq && cv_strand_passes(f.flags, flag) &&
-                r.cigar_at + 4ull * n_cigar <= size;
+    CvRec r; r.refid = h.refid; r.pos = h.pos; r.cigar_at = h.cigar_at; r.n_ops = h.n_cigar;
+    r.counted = h.ok && h.refid >= 0 && h.refid < n_chr && h.pos >= 0 && !(h.flag & 4u) && h.n_cigar > 0u && !(h.flag & f.exclude) && h.mapq >= f.min_mapq &&
+                cv_strand_passes(f.flags, h.flag) && h.seq_at <= h.size;
     return r;
 }
+// the record that starts (with its block_size) at rec, `avail` bytes of the array behind rec
+CV_HD CvRec cv_record(const unsigned char *rec, uint64_t avail, int n_chr, const CvFilter &f) { return cv_record(bam_head(rec, avail), n_chr, f); }
 CV_HD uint64_t cv_key(int32_t refid, uint64_t position) { return (uint64_t)(uint32_t)refid << 32 | position; }
 CV_HD int cv_key_bits_max(int n_chr) { return 32 + bs_chr_bits(n_chr); }
 // how many low bits the smallest and the largest key differ in: every key between them shares the digits above
@@ -101,13 +95,8 @@ CV_HD int cv_key_bits(uint64_t lo, uint64_t hi) { int b = 0; for (uint64_t x = l
 template <class F>
 CV_HD uint32_t cv_blocks(const unsigned char *rec, const CvRec &r, F &f)
 {
-    uint64_t p = (uint64_t)r.pos;
     uint32_t k = 0;
-    for (uint32_t j = 0; j < r.n_ops; j++) {
-        const uint32_t c = bs_le32(rec + r.cigar_at + 4ull * j), op = c & 15u, len = c >> 4;
-        if (op == 0u || op == 7u || op == 8u) { if (len) { f(k, p, p + len); k++; } p += len; }
-        else if (op == 2u || op == 3u) p += len;
-    }
+    bam_cigar_walk(rec, r.cigar_at, r.n_ops, (uint64_t)r.pos, [&](uint32_t op, uint32_t len, uint64_t p, uint64_t) { if (bam_op_aligned(op) && len) { f(k, p, p + len); k++; } });
     return k;
 }
 struct CvTally {                    // k_cv_count's walk
@@ -214,9 +203,6 @@ k_cv_top(uint64_t *__restrict__ tile_sum, uint32_t n_tiles, unsigned long long *
     }
 }
 
-// where sorted record i starts in the array (k_bs_len's offsets and the scanned per-tile sums)
-__device__ __forceinline__ uint64_t cv_rec_start(const uint64_t *dst_off, const uint64_t *tile_base, uint32_t i) { return tile_base[i / BS_THREADS] + dst_off[i]; }
-
 __global__ void __launch_bounds__(CV_THREADS)
 k_cv_count(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__ dst_off, const uint64_t *__restrict__ tile_base, uint32_t n, unsigned long long n_raw, int n_chr,
            const CvFilter f, uint32_t *__restrict__ blk_off, uint64_t *__restrict__ tile_sum, uint64_t *__restrict__ part /* 5 planes: counted, aligned | ~min key, max key, ~bad */)
@@ -227,7 +213,7 @@ k_cv_count(const unsigned char *__restrict__ sorted, const uint64_t *__restrict_
     uint64_t mine = 0, counted = 0, nmin = 0, kmax = 0, nbad = 0;
     CvTally t; t.aligned = 0; t.lo = CV_NONE; t.hi = 0; t.bad = false;
     if (i < n) {
-        const uint64_t at = cv_rec_start(dst_off, tile_base, i);
+        const uint64_t at = bam_rec_start(dst_off, tile_base, i);
         if (at < n_raw) {
             const CvRec r = cv_record(sorted + at, n_raw - at, n_chr, f);
             if (r.counted) {
@@ -253,7 +239,7 @@ k_cv_emit(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__
 {
     const uint32_t i = blockIdx.x * CV_THREADS + threadIdx.x;
     if (i >= n) return;
-    const uint64_t at = cv_rec_start(dst_off, tile_base, i);
+    const uint64_t at = bam_rec_start(dst_off, tile_base, i);
     if (at >= n_raw) return;
     const CvRec r = cv_record(sorted + at, n_raw - at, n_chr, f);
     if (!r.counted) return;

@@ -6,9 +6,7 @@
 // THE DEFINITION.  No samtools or Picard exists where this project is built and tested: this definition -- modelled on Picard's rules (unclipped 5' ends, sum
 // of base qualities, a fragment loses to any pair that shares its end) -- is what the tests pin (tests/markdup_inputs.py is its sequential twin).
 //
-// Per sorted record (fields are read byte by byte, little endian: records are unaligned; block_size is at byte 0):
-//   refID int32 at byte 4, pos int32 at byte 8, l_read_name u8 at byte 12, n_cigar_op u16 at byte 16, flag u16 at byte 18, l_seq u32 at byte 20; the name
-//   starts at byte 36, the CIGAR ops (u32: len << 4 | op) behind it, then (l_seq + 1) / 2 bytes of packed bases, then l_seq quality bytes.
+// Per sorted record (its fields, CIGAR and the places of its parts as bam_head and bam_cigar_walk of dg_bamrec.h give them):
 //   examined  all of: 0 <= refID < n_chr; pos >= 0; flag & 4 clear; flag & 0x900 clear; n_cigar_op > 0; and name, CIGAR, bases and qualities lie inside the
 //             record and the array: 36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <= 4 + block_size, and <= the bytes the array holds from the
 //             record's start.  Every other record plays no part and leaves with its bytes unchanged.
@@ -88,42 +86,39 @@ MD_HD uint64_t md_hash(const unsigned char *name, uint32_t len, int hash_bits)
     h ^= h >> 48;
     return hash_bits >= 64 ? h : h & ((1ull << hash_bits) - 1ull);
 }
-MD_HD uint32_t md_name_len(const unsigned char *rec) { return rec[12] ? (uint32_t)rec[12] - 1u : 0u; }
+MD_HD uint32_t md_name_len(const BamHead &h) { return h.l_name ? h.l_name - 1u : 0u; }
+MD_HD uint32_t md_name_len(const unsigned char *rec) { return md_name_len(bam_head(rec, BAM_FIXED)); }      // (of an examined record: its fixed part lies inside the array)
 MD_HD int md_e_bits(int n_chr) { return 34 + bs_chr_bits(n_chr); }
 // the record that starts (with its block_size) at rec, `avail` bytes of the array behind rec
 MD_HD MdRec md_record(const unsigned char *rec, uint64_t avail, int n_chr, int hash_bits)
 {
     MdRec r; r.examined = false; r.candidate = false; r.bad = false; r.E = 0; r.h = 0; r.score = 0;
-    if (avail < BAM_FIXED) return r;
-    const int32_t refid = (int32_t)bs_le32(rec + 4), pos = (int32_t)bs_le32(rec + 8);
-    const uint32_t l_name = rec[12], n_cigar = (uint32_t)rec[16] | (uint32_t)rec[17] << 8, flag = (uint32_t)rec[18] | (uint32_t)rec[19] << 8;
-    const uint64_t l_seq = bs_le32(rec + 20);
-    uint64_t size = 4ull + (uint64_t)bs_le32(rec);
-    if (size > avail) size = avail;
-    const uint64_t cigar_at = (uint64_t)BAM_FIXED + l_name, qual_at = cigar_at + 4ull * n_cigar + (l_seq + 1) / 2;
-    r.examined = refid >= 0 && refid < n_chr && pos >= 0 && !(flag & 4u) && !(flag & 0x900u) && n_cigar > 0u && qual_at + l_seq <= size;
+    const BamHead h = bam_head(rec, avail);
+    const int32_t refid = h.refid, pos = h.pos;
+    const uint32_t flag = h.flag;
+    // examined only when the qualities end inside the record and the array; secondary and supplementary records are left out
+    r.examined = h.ok && refid >= 0 && refid < n_chr && pos >= 0 && !(flag & 4u) && !(flag & 0x900u) && h.n_cigar > 0u && h.aux_at <= h.size;
     if (!r.examined) return r;
     const uint32_t s = flag >> 4 & 1u;
-    uint64_t rlen = 0, lead = 0, trail = 0;
+    uint64_t lead = 0, trail = 0;
     bool seen = false;
-    for (uint32_t j = 0; j < n_cigar; j++) {
-        const uint32_t c = bs_le32(rec + cigar_at + 4ull * j), op = c & 15u, len = c >> 4;
+    const uint64_t rlen = bam_cigar_walk(rec, h.cigar_at, h.n_cigar, 0, [&](uint32_t op, uint32_t len, uint64_t, uint64_t) {
         if (op == 4u || op == 5u) { if (seen) trail += len; else lead += len; }
-        else { seen = true; trail = 0; if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) rlen += len; }
-    }
+        else { seen = true; trail = 0; }
+    }).p;
     const int64_t u5 = s ? (int64_t)pos + (int64_t)rlen - 1 + (int64_t)trail : (int64_t)pos - (int64_t)lead;
     const int64_t biased = u5 + (1ll << 31);
     if (biased < 0 || biased >= (1ll << 33)) { r.bad = true; return r; }
     r.E = (uint64_t)(uint32_t)refid << 34 | (uint64_t)biased << 1 | (uint64_t)s;
     uint32_t score = 0;
-    for (uint64_t k = 0; k < l_seq; k++) { const uint32_t q = rec[qual_at + k]; if (q >= 15u && q <= 93u && score < MD_SCORE_MAX) score += q; }
+    for (uint64_t k = 0; k < (uint64_t)h.l_seq; k++) { const uint32_t q = rec[h.qual_at + k]; if (q >= 15u && q <= 93u && score < MD_SCORE_MAX) score += q; }
     r.score = score > MD_SCORE_MAX ? MD_SCORE_MAX : score;
     r.candidate = (flag & 1u) && !(flag & 8u) && ((flag >> 6 & 1u) ^ (flag >> 7 & 1u));
-    if (r.candidate) r.h = md_hash(rec + BAM_FIXED, md_name_len(rec), hash_bits);
+    if (r.candidate) r.h = md_hash(rec + BAM_FIXED, md_name_len(h), hash_bits);
     return r;
 }
-// where sorted record i starts in the array (k_bs_len's offsets and the scanned per-tile sums)
-MD_HD uint64_t md_rec_start(const uint64_t *dst_off, const uint64_t *tile_base, uint32_t i) { return tile_base[i / BS_THREADS] + dst_off[i]; }
+// bam_rec_start under the name tests/native/markdup_checks.hip calls it by
+MD_HD uint64_t md_rec_start(const uint64_t *dst_off, const uint64_t *tile_base, uint32_t i) { return bam_rec_start(dst_off, tile_base, i); }
 MD_HD bool md_same_name(const unsigned char *a, const unsigned char *b)
 {
     const uint32_t la = md_name_len(a);
@@ -141,15 +136,15 @@ MD_HD uint32_t md_mate(const uint64_t *keys, const int64_t *vals, uint32_t n_can
     while (right < MD_CROWD && j + right + 1u < n_cand && keys[j + right + 1u] == k) right++;
     *crowded = left + right + 1u > MD_CROWD;
     if (*crowded) return MD_FRAGMENT;
-    const unsigned char *mine = sorted + md_rec_start(dst_off, tile_base, (uint32_t)vals[j]);
+    const unsigned char *mine = sorted + bam_rec_start(dst_off, tile_base, (uint32_t)vals[j]);
     uint32_t same = 0, other = 0;
     for (uint32_t t = j - left; t <= j + right; t++) {
         if (t == j) continue;
-        if (md_same_name(mine, sorted + md_rec_start(dst_off, tile_base, (uint32_t)vals[t]))) { same++; other = (uint32_t)vals[t]; }
+        if (md_same_name(mine, sorted + bam_rec_start(dst_off, tile_base, (uint32_t)vals[t]))) { same++; other = (uint32_t)vals[t]; }
     }
     if (same != 1u) return MD_FRAGMENT;
-    const unsigned char *theirs = sorted + md_rec_start(dst_off, tile_base, other);
-    return ((mine[18] ^ theirs[18]) & 0x40u) ? other : MD_FRAGMENT;          // (a candidate has exactly one of 0x40 and 0x80)
+    const unsigned char *theirs = sorted + bam_rec_start(dst_off, tile_base, other);
+    return ((bam_head(mine, BAM_FIXED).flag ^ bam_head(theirs, BAM_FIXED).flag) & 0x40u) ? other : MD_FRAGMENT;         // (a candidate has exactly one of 0x40 and 0x80)
 }
 MD_HD bool md_is_rep(uint32_t i, uint32_t mate) { return mate < MD_FRAGMENT && i < mate; }
 // what record i adds to the lists: pairs << 32 | ends
@@ -186,7 +181,7 @@ k_md_rec(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__ 
     uint64_t mine = 0, examined = 0, nbad = 0;
     if (i < n) {
         MdRec r; r.examined = false; r.candidate = false; r.bad = false; r.E = 0; r.h = 0; r.score = 0;
-        const uint64_t at = md_rec_start(dst_off, tile_base, i);
+        const uint64_t at = bam_rec_start(dst_off, tile_base, i);
         if (at < n_raw) r = md_record(sorted + at, n_raw - at, n_chr, hash_bits);
         if (r.bad) nbad = ~(uint64_t)i;
         examined = r.examined ? 1 : 0; mine = r.candidate ? 1 : 0;
@@ -290,7 +285,7 @@ k_md_heads(const uint64_t *__restrict__ keys, const int64_t *__restrict__ vals, 
 __device__ __forceinline__ void md_write(unsigned char *sorted, const uint64_t *dst_off, const uint64_t *tile_base, uint32_t i, uint32_t n, unsigned long long n_raw, bool dup)
 {
     if (i >= n) return;
-    const uint64_t at = md_rec_start(dst_off, tile_base, i) + 19ull;
+    const uint64_t at = bam_rec_start(dst_off, tile_base, i) + 19ull;
     if (at < n_raw) sorted[at] = md_verdict(sorted[at], dup);
 }
 

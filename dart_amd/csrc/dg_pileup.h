@@ -5,8 +5,7 @@
 //
 // THE DEFINITION.  No pileup tool exists where this project is built and tested: this text is what the tests pin (tests/pileup_inputs.py is its sequential twin).
 //
-// Per sorted record (fields are read byte by byte, exactly as cv_record of dg_coverage.h reads them): in addition l_seq, u32 at byte 20, and the bases: base i is
-//   the high nibble of byte 36 + l_read_name + 4 n_cigar_op + i / 2 for even i, the low nibble for odd i.
+// Per sorted record (its fields, CIGAR and packed bases as bam_head and bam_cigar_walk of dg_bamrec.h give them):
 //   counted  everything the coverage track asks (0 <= refID < n_chr; pos >= 0; flag & 4 clear; n_cigar_op > 0; (flag & exclude_flags) == 0; mapq >= min_mapq;
 //            the CIGAR inside the record and the array), and: the packed bases inside the record and the array; l_seq > 0; the CIGAR's read length (the sum
 //            of M, I, S, =, X) == l_seq; the record ends on its chromosome, pos + rlen <= chr_len[refID] (rlen: the sum of M, D, N, =, X).  A record that fails
@@ -83,31 +82,27 @@ PU_HD int pu_key_bits_max(int n_chr) { return 35 + bs_chr_bits(n_chr); }
 PU_HD int64_t pu_chr_len(const DIndex &ix, int32_t refid) { return ix.loc_key[refid] + 1 - ix.chr_off[refid]; }     // (ChrLocMap's forward keys are the chromosomes' last bases)
 PU_HD uint64_t pu_value(uint32_t s) { return 1ull + ((uint64_t)s << 32); }
 
-// the record that starts (with its block_size) at rec, `avail` bytes of the array behind rec
-PU_HD PuRec pu_record(const unsigned char *rec, uint64_t avail, const DIndex &ix, const PuFilter &f)
+// the record at rec with the fixed fields h: what the coverage track counts, with the packed bases inside the record and the array and l_seq != 0; PU_RANGE comes
+// before those two, PU_LEFT_OUT behind them
+PU_HD PuRec pu_record(const unsigned char *rec, const BamHead &h, const DIndex &ix, const PuFilter &f)
 {
     const CvFilter cf{0u, f.exclude, f.min_mapq};
-    const CvRec c = cv_record(rec, avail, ix.n_chr, cf);
+    const CvRec c = cv_record(h, ix.n_chr, cf);
     PuRec r; r.state = PU_SKIP; r.refid = c.refid; r.pos = c.pos; r.n_ops = c.n_ops; r.cigar_at = c.cigar_at; r.l_seq = 0; r.s = 0; r.seq_at = 0; r.rlen = 0;
     if (!c.counted) return r;
-    uint64_t size = 4ull + (uint64_t)bs_le32(rec);
-    if (size > avail) size = avail;
-    r.l_seq = bs_le32(rec + 20); r.s = ((uint32_t)rec[18] >> 4) & 1u;
-    r.seq_at = c.cigar_at + 4ull * c.n_ops;
-    uint64_t p = (uint64_t)c.pos, qlen = 0;
+    r.l_seq = h.l_seq; r.s = h.flag >> 4 & 1u; r.seq_at = h.seq_at;
     bool bad = false;
-    for (uint32_t j = 0; j < c.n_ops; j++) {
-        const uint32_t w = bs_le32(rec + c.cigar_at + 4ull * j), op = w & 15u, len = w >> 4;
-        if (op == 0u || op == 7u || op == 8u) { p += len; qlen += len; if (len && p > CV_MAX_POS) bad = true; }
-        else if (op == 2u || op == 3u) p += len;
-        else if (op == 1u || op == 4u) qlen += len;
-    }
-    r.rlen = p - (uint64_t)c.pos;
+    const BamAt end = bam_cigar_walk(rec, c.cigar_at, c.n_ops, (uint64_t)c.pos, [&](uint32_t op, uint32_t len, uint64_t p, uint64_t) {
+        if (bam_op_aligned(op) && len && p + len > CV_MAX_POS) bad = true;
+    });
+    r.rlen = end.p - (uint64_t)c.pos;
     if (bad) { r.state = PU_RANGE; return r; }
-    if (r.seq_at + ((uint64_t)r.l_seq + 1) / 2 > size || r.l_seq == 0u) return r;
-    r.state = qlen == (uint64_t)r.l_seq && (int64_t)p <= pu_chr_len(ix, c.refid) ? PU_COUNTED : PU_LEFT_OUT;
+    if (h.qual_at > h.size || r.l_seq == 0u) return r;
+    r.state = end.q == (uint64_t)r.l_seq && (int64_t)end.p <= pu_chr_len(ix, c.refid) ? PU_COUNTED : PU_LEFT_OUT;
     return r;
 }
+// the record that starts (with its block_size) at rec, `avail` bytes of the array behind rec
+PU_HD PuRec pu_record(const unsigned char *rec, uint64_t avail, const DIndex &ix, const PuFilter &f) { return pu_record(rec, bam_head(rec, avail), ix, f); }
 
 // sixteen symbols of the forward text from g on as 2-bit codes, the first in the top bits.  One unaligned fetch of pac at the right shift; a window that
 // reaches the last bytes of the array goes base by base (on the device pac holds both strands and a pad: the forward text never gets there)
@@ -175,26 +170,17 @@ PU_HD PuTally pu_walk(const unsigned char *rec, const PuRec &r, const DIndex &ix
     PuTally t; t.events = 0; t.aligned = 0; t.blocks = 0; t.mism = 0; t.del = 0; t.ins = 0;
     const unsigned char *seq = rec + r.seq_at;
     const int64_t g0 = ix.chr_off[r.refid];
-    uint64_t p = (uint64_t)r.pos;
-    uint32_t q = 0;
-    for (uint32_t j = 0; j < r.n_ops; j++) {
-        const uint32_t w = bs_le32(rec + r.cigar_at + 4ull * j), op = w & 15u, len = w >> 4;
-        if (op == 0u || op == 7u || op == 8u) {
-            if (len) { f.depth(t.events, p, p + len); t.events += 2; t.blocks++; t.aligned += len; }
+    bam_cigar_walk(rec, r.cigar_at, r.n_ops, (uint64_t)r.pos, [&](uint32_t op, uint32_t len, uint64_t p, uint64_t q) {
+        if (!len) return;
+        if (bam_op_aligned(op)) {
+            f.depth(t.events, p, p + len); t.events += 2; t.blocks++; t.aligned += len;
             for (uint32_t k = 0; k < len; k += PU_STEP) {
-                const PuStep st = pu_compare16(pu_nibbles16(seq, r.l_seq, q + k), pu_ref16(ix, g0 + (int64_t)(p + k)), len - k);
+                const PuStep st = pu_compare16(pu_nibbles16(seq, r.l_seq, (uint32_t)q + k), pu_ref16(ix, g0 + (int64_t)(p + k)), len - k);
                 if (st.mis) { f.bases(t.events, p + k, st); const uint32_t m = pu_popc(st.mis); t.events += m; t.mism += m; }
             }
-            p += len; q += len;
-        } else if (op == 2u) {
-            if (len) { f.del(t.events, p, len); t.events += len; t.del += len; }
-            p += len;
-        } else if (op == 3u) p += len;
-        else if (op == 1u) {
-            if (len) { f.ins(t.events, (p > (uint64_t)r.pos + 1 ? p : (uint64_t)r.pos + 1) - 1); t.events++; t.ins++; }
-            q += len;
-        } else if (op == 4u) q += len;
-    }
+        } else if (op == 2u) { f.del(t.events, p, len); t.events += len; t.del += len; }
+        else if (op == 1u) { f.ins(t.events, (p > (uint64_t)r.pos + 1 ? p : (uint64_t)r.pos + 1) - 1); t.events++; t.ins++; }
+    });
     return t;
 }
 struct PuNoSink {                   // k_pu_count's walk: the tally is all it wants
@@ -315,7 +301,7 @@ k_pu_count(const unsigned char *__restrict__ sorted, const uint64_t *__restrict_
     const uint32_t i = blockIdx.x * PU_WG + threadIdx.x;
     uint64_t mine = 0, recs = 0, aligned = 0, blk_ins = 0, mis_del = 0, nbad = 0, nmin = 0, kmax = 0;
     if (i < n) {
-        const uint64_t at = cv_rec_start(dst_off, tile_base, i);
+        const uint64_t at = bam_rec_start(dst_off, tile_base, i);
         if (at < n_raw) {
             const PuRec r = pu_record(sorted + at, n_raw - at, ix, f);
             if (r.state == PU_RANGE) nbad = ~(uint64_t)i;
@@ -345,7 +331,7 @@ k_pu_emit(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__
 {
     const uint32_t i = blockIdx.x * PU_WG + threadIdx.x;
     if (i >= n) return;
-    const uint64_t at = cv_rec_start(dst_off, tile_base, i);
+    const uint64_t at = bam_rec_start(dst_off, tile_base, i);
     if (at >= n_raw) return;
     const PuRec r = pu_record(sorted + at, n_raw - at, ix, f);
     if (r.state != PU_COUNTED) return;

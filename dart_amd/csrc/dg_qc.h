@@ -6,9 +6,7 @@
 //
 // THE DEFINITION.  No samtools exists where this project is built and tested: this text is what the tests pin (tests/qc_inputs.py is its sequential twin).
 //
-// Per sorted record (fields are read byte by byte, little endian, exactly as md_record of dg_markdup.h and pu_record of dg_pileup.h read them): block_size u32 at
-//   byte 0, refID i32 at 4, pos i32 at 8, l_read_name u8 at 12, mapq u8 at 13, n_cigar_op u16 at 16, flag u16 at 18, l_seq u32 at 20, next_refID i32 at 24,
-//   next_pos i32 at 28, tlen i32 at 32; CIGAR, bases (base i: the high nibble of its byte for even i) and qualities behind the name as in every BAM record.
+// Per sorted record its fields, CIGAR, bases and qualities as bam_head of dg_bamrec.h gives them.
 // All counters are u64 words in one flat array, the sections in this order; DG_QC_CYCLES = 512, DG_QC_ISIZE = 8001, DG_QC_INDEL = 65.
 //   whole    36 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 + l_seq <= 4 + block_size, and that size <= the bytes the array holds from the record's start.
 //            A record that is not whole adds 1 to SN.malformed and takes part in nothing else.  primary: flag & 0x900 == 0.  mapped: flag & 4 clear.
@@ -105,14 +103,9 @@ enum { QC_SN_RECORDS = 0, QC_SN_MALFORMED, QC_SN_PROFILED, QC_SN_LEFT_OUT, QC_SN
 struct QcHead { bool whole; uint32_t flag, mapq, l_seq; int32_t refid, pos, next_refid, next_pos, tlen; };
 QC_HD QcHead qc_head(const unsigned char *rec, uint64_t avail)
 {
-    QcHead h; h.whole = false; h.flag = 0; h.mapq = 0; h.l_seq = 0; h.refid = -1; h.pos = -1; h.next_refid = -1; h.next_pos = -1; h.tlen = 0;
-    if (avail < BAM_FIXED) return h;
-    h.refid = (int32_t)bs_le32(rec + 4); h.pos = (int32_t)bs_le32(rec + 8);
-    const uint64_t l_name = rec[12], n_cigar = (uint64_t)rec[16] | (uint64_t)rec[17] << 8;
-    h.mapq = rec[13]; h.flag = (uint32_t)rec[18] | (uint32_t)rec[19] << 8; h.l_seq = bs_le32(rec + 20);
-    h.next_refid = (int32_t)bs_le32(rec + 24); h.next_pos = (int32_t)bs_le32(rec + 28); h.tlen = (int32_t)bs_le32(rec + 32);
-    const uint64_t size = (uint64_t)BAM_FIXED + l_name + 4ull * n_cigar + ((uint64_t)h.l_seq + 1) / 2 + (uint64_t)h.l_seq;
-    h.whole = size <= 4ull + (uint64_t)bs_le32(rec) && size <= avail;
+    const BamHead b = bam_head(rec, avail);
+    QcHead h; h.flag = b.flag; h.mapq = b.mapq; h.l_seq = b.l_seq; h.refid = b.refid; h.pos = b.pos; h.next_refid = b.next_refid; h.next_pos = b.next_pos; h.tlen = b.tlen;
+    h.whole = b.ok && b.aux_at <= b.block && b.aux_at <= avail;          // the computed length against the stored size and against the array
     return h;
 }
 QC_HD uint32_t qc_is_bin(int32_t tlen) { const int64_t t = (int64_t)tlen; const uint64_t a = (uint64_t)(t < 0 ? -t : t); return (uint32_t)(a < (uint64_t)DG_QC_ISIZE - 1 ? a : (uint64_t)DG_QC_ISIZE - 1); }
@@ -152,8 +145,7 @@ QC_HD void qc_tables(const QcHead &h, int n_chr, S &s)
 
 // ---- a profiled record: the per-op terms, then base by base ----
 QC_HD uint32_t qc_cycle(uint32_t i, uint32_t l_seq, uint32_t s) { const uint32_t c = s ? l_seq - 1u - i : i; return c < (uint32_t)DG_QC_CYCLES - 1 ? c : (uint32_t)DG_QC_CYCLES - 1; }
-QC_HD bool qc_op_takes_read(uint32_t op) { return op == 0u || op == 1u || op == 4u || op == 7u || op == 8u; }
-QC_HD bool qc_op_takes_ref(uint32_t op) { return op == 0u || op == 2u || op == 3u || op == 7u || op == 8u; }
+QC_HD bool qc_op_takes_read(uint32_t op) { return bam_op_takes_read(op); }      // (the name tests/native/qc_checks.hip calls it by)
 // op (with len) at read offset q of a profiled record of class k: s.pc(k, column, cycle, 1), s.id(row, bin), s.sn(word, value)
 template <class S>
 QC_HD void qc_op_event(uint32_t op, uint32_t len, uint64_t q, uint32_t l_seq, uint32_t strand, uint32_t k, S &s)
@@ -170,9 +162,9 @@ QC_HD void qc_seek(const unsigned char *rec, const PuRec &r, QcCursor &c, uint64
 {
     while (c.j < r.n_ops) {
         const uint32_t w = bs_le32(rec + r.cigar_at + 4ull * c.j), op = w & 15u, len = w >> 4;
-        if (qc_op_takes_read(op) && c.q + len > from) break;
-        if (qc_op_takes_read(op)) c.q += len;
-        if (qc_op_takes_ref(op)) c.p += len;
+        if (bam_op_takes_read(op) && c.q + len > from) break;
+        if (bam_op_takes_read(op)) c.q += len;
+        if (bam_op_takes_ref(op)) c.p += len;
         c.j++;
     }
 }
@@ -186,7 +178,7 @@ QC_HD void qc_quad(const unsigned char *rec, const PuRec &r, const QcCursor &c, 
     uint64_t q = c.q, p = c.p;
     for (uint32_t j = c.j; j < r.n_ops && q < end; j++) {
         const uint32_t w = bs_le32(rec + r.cigar_at + 4ull * j), op = w & 15u, len = w >> 4;
-        if (qc_op_takes_read(op)) {
+        if (bam_op_takes_read(op)) {
             const uint32_t cls = op == 1u ? 2u : op == 4u ? 3u : 1u;
 #pragma unroll
             for (int k = 0; k < QC_LANE_BASES; k++) {
@@ -195,7 +187,7 @@ QC_HD void qc_quad(const unsigned char *rec, const PuRec &r, const QcCursor &c, 
             }
             q += len;
         }
-        if (qc_op_takes_ref(op)) p += len;
+        if (bam_op_takes_ref(op)) p += len;
     }
 }
 // four bytes from p on, low byte first.  On the device two aligned dwords, funnel-shifted (k_bs_gather's way): up to 7 bytes behind p + 3 are read, which lie in
@@ -343,7 +335,7 @@ k_qc_flag(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__
         const uint64_t i = base + threadIdx.x;
         QcFlagSink s{s_fs, s_mq, s_rl, s_sn, words + qc_off_is(n_chr), 0xFFFFFFFFu};
         if (i < n) {
-            const uint64_t at = cv_rec_start(dst_off, tile_base, (uint32_t)i);
+            const uint64_t at = bam_rec_start(dst_off, tile_base, (uint32_t)i);
             QcHead h = qc_head(sorted + (at < n_raw ? at : 0), at < n_raw ? n_raw - at : 0);
             qc_tables(h, n_chr, s);
         }
@@ -388,7 +380,7 @@ k_qc_cycle(const unsigned char *__restrict__ sorted, const uint64_t *__restrict_
     uint32_t trips = 0;
     for (uint64_t base = (uint64_t)blockIdx.x * (QC_WG / QC_GROUP); base < n; base += (uint64_t)gridDim.x * (QC_WG / QC_GROUP)) {
         const uint64_t i = base + grp;
-        const uint64_t at = i < n ? cv_rec_start(dst_off, tile_base, (uint32_t)i) : n_raw;
+        const uint64_t at = i < n ? bam_rec_start(dst_off, tile_base, (uint32_t)i) : n_raw;
         if (at < n_raw) {
             const unsigned char *rec = sorted + at;
             const QcHead h = qc_head(rec, n_raw - at);
@@ -399,12 +391,10 @@ k_qc_cycle(const unsigned char *__restrict__ sorted, const uint64_t *__restrict_
                 if (r.state == PU_COUNTED) {
                     const uint32_t k = h.flag >> 7 & 1u;
                     if (lane == 0u) s.sn(QC_SN_PROFILED, 1);
-                    uint64_t q = 0;
-                    for (uint32_t j = 0; j < r.n_ops; j++) {
-                        const uint32_t w = bs_le32(rec + r.cigar_at + 4ull * j), op = w & 15u, len = w >> 4;
-                        if ((j & (QC_GROUP - 1u)) == lane) qc_op_event(op, len, q, r.l_seq, r.s, k, s);
-                        if (qc_op_takes_read(op)) q += len;
-                    }
+                    uint32_t j = 0;                                   // op j's terms are lane j & 15's
+                    bam_cigar_walk(rec, r.cigar_at, r.n_ops, 0, [&](uint32_t op, uint32_t len, uint64_t, uint64_t q) {
+                        if ((j++ & (QC_GROUP - 1u)) == lane) qc_op_event(op, len, q, r.l_seq, r.s, k, s);
+                    });
                     QcCursor c{0u, 0ull, (uint64_t)r.pos};
                     for (uint64_t b = 0; b < (uint64_t)r.l_seq; b += QC_STEP) {
                         qc_seek(rec, r, c, b);

@@ -115,12 +115,13 @@ struct TgPlan { int kind; PuRec r; uint64_t size /* the record's bytes inside th
 TG_HD TgPlan tg_plan(const unsigned char *rec, uint64_t avail, const DIndex &ix, uint32_t flags)
 {
     TgPlan p; p.kind = TG_NOT_ELIGIBLE; p.aux_at = 0; p.kept = 0; p.removed = 0;
-    const uint64_t whole = avail >= 4 ? 4ull + (uint64_t)bs_le32(rec) : ~0ull;
+    const BamHead h = bam_head(rec, avail);
+    const uint64_t whole = avail >= 4 ? 4ull + (uint64_t)bs_le32(rec) : ~0ull;      // (of a record whose fixed part is cut short too: it is copied as far as it goes)
     p.size = whole <= avail ? whole : avail;
     const PuFilter all{0u, 0u};
-    p.r = pu_record(rec, avail, ix, all);
-    if (whole > avail || p.r.state != PU_COUNTED) return p;
-    p.aux_at = p.r.seq_at + ((uint64_t)p.r.l_seq + 1) / 2 + (uint64_t)p.r.l_seq;
+    p.r = pu_record(rec, h, ix, all);
+    if (whole > avail || p.r.state != PU_COUNTED) return p;                        // refused when block_size passes the array's end, not clamped
+    p.aux_at = h.aux_at;
     if (p.aux_at > p.size) return p;
     TgAuxCount c{0, 0};
     if (!tg_aux_walk(rec, p.aux_at, p.size, flags, c)) { p.kind = TG_AUX_BAD; return p; }
@@ -157,15 +158,12 @@ TG_HD TgTally tg_walk(const unsigned char *rec, const PuRec &r, const DIndex &ix
     TgTally t; t.mism = 0; t.ins = 0; t.del = 0; t.votes = 0; t.introns = 0;
     const unsigned char *seq = rec + r.seq_at;
     const int64_t g0 = ix.chr_off[r.refid];
-    uint64_t p = (uint64_t)r.pos;
     uint32_t u = 0;
-    uint32_t q = 0;
-    for (uint32_t j = 0; j < r.n_ops; j++) {
-        const uint32_t w = bs_le32(rec + r.cigar_at + 4ull * j), op = w & 15u, len = w >> 4;
-        if (op == 0u || op == 7u || op == 8u) {
+    bam_cigar_walk(rec, r.cigar_at, r.n_ops, (uint64_t)r.pos, [&](uint32_t op, uint32_t len, uint64_t p, uint64_t q) {
+        if (bam_op_aligned(op)) {
             for (uint32_t k = 0; k < len; k += PU_STEP) {
                 const uint32_t n = len - k < PU_STEP ? len - k : PU_STEP, ref = pu_ref16(ix, g0 + (int64_t)(p + k));
-                const PuStep st = pu_compare16(pu_nibbles16(seq, r.l_seq, q + k), ref, n);
+                const PuStep st = pu_compare16(pu_nibbles16(seq, r.l_seq, (uint32_t)q + k), ref, n);
                 uint32_t prev = 0;
                 for (uint32_t m = st.mis; m;) {
                     const uint32_t z = pu_clz(m), b = z >> 1;                    // base b of the step: bit 30 - 2 b
@@ -175,24 +173,16 @@ TG_HD TgTally tg_walk(const unsigned char *rec, const PuRec &r, const DIndex &ix
                 }
                 u += n - prev;
             }
-            p += len; q += len;
-        } else if (op == 2u) {
-            if (len) {
-                tg_num(o, u); o.ch('^');
-                for (uint32_t i = 0; i < len; i++) o.ch(tg_letter(tg_text(ix, g0 + (int64_t)(p + i))));
-                u = 0; t.del += len;
-            }
-            p += len;
-        } else if (op == 3u) {
-            if (len >= 4u) {
-                const int64_t g = g0 + (int64_t)p;
-                const uint32_t v = tg_motif(tg_text(ix, g), tg_text(ix, g + 1), tg_text(ix, g + (int64_t)len - 2), tg_text(ix, g + (int64_t)len - 1));
-                t.votes |= v; t.introns++;
-            }
-            p += len;
-        } else if (op == 1u) { t.ins += len; q += len; }
-        else if (op == 4u) q += len;
-    }
+        } else if (op == 2u && len) {
+            tg_num(o, u); o.ch('^');
+            for (uint32_t i = 0; i < len; i++) o.ch(tg_letter(tg_text(ix, g0 + (int64_t)(p + i))));
+            u = 0; t.del += len;
+        } else if (op == 3u && len >= 4u) {
+            const int64_t g = g0 + (int64_t)p;
+            const uint32_t v = tg_motif(tg_text(ix, g), tg_text(ix, g + 1), tg_text(ix, g + (int64_t)len - 2), tg_text(ix, g + (int64_t)len - 1));
+            t.votes |= v; t.introns++;
+        } else if (op == 1u) t.ins += len;
+    });
     tg_num(o, u);
     return t;
 }
@@ -312,7 +302,7 @@ k_tg_len(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__ 
     const uint32_t i = blockIdx.x * TG_WG + threadIdx.x;
     uint64_t mine = 0, recs = 0, aux_ts = 0, removed = 0, mism = 0, indel = 0, no_ts = 0;
     if (i < n) {
-        const uint64_t at = cv_rec_start(dst_off, tile_base, i);
+        const uint64_t at = bam_rec_start(dst_off, tile_base, i);
         if (at < n_raw) {
             const TgLen l = tg_len_record(sorted + at, n_raw - at, ix, flags);
             mine = l.size;
@@ -342,7 +332,7 @@ k_tg_tail(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__
 {
     const uint32_t i = blockIdx.x * TG_WG + threadIdx.x;
     if (i >= n) return;
-    const uint64_t at = cv_rec_start(dst_off, tile_base, i), to = new_base[blockIdx.x] + new_off[i];
+    const uint64_t at = bam_rec_start(dst_off, tile_base, i), to = new_base[blockIdx.x] + new_off[i];
     if (at >= n_raw || to >= out_bytes) return;
     const TgPlan p = tg_plan(sorted + at, n_raw - at, ix, flags);
     (void)tg_write_new(sorted + at, p, ix, flags, out + to, out_bytes - to);
@@ -356,7 +346,7 @@ k_tg_copy(const unsigned char *__restrict__ sorted, const uint64_t *__restrict__
     const uint32_t lane = threadIdx.x & (TG_LANES - 1u);
     const uint64_t i = (uint64_t)blockIdx.x * (TG_WG / TG_LANES) + threadIdx.x / TG_LANES;
     if (i >= n) return;
-    const uint64_t at = cv_rec_start(dst_off, tile_base, (uint32_t)i), to = new_base[i / TG_WG] + new_off[i];
+    const uint64_t at = bam_rec_start(dst_off, tile_base, (uint32_t)i), to = new_base[i / TG_WG] + new_off[i];
     if (at >= n_raw || to >= out_bytes) return;
     const TgPlan p = tg_plan(sorted + at, n_raw - at, ix, flags);
     tg_write_stay(sorted + at, p, flags, out + to, out_bytes - to, lane);
