@@ -191,6 +191,16 @@ struct QcState {
     int max_groups = QC_GROUPS;     // DG_QC_MAX_GROUPS: test hook, caps the kernels' grid (a few thousand records drive a workgroup through several trips and flushes)
     hipError_t ready() { return ev.ready(); }
 };
+// the RNA-seq metrics of the sorted array (dg_rnametrics.h): the words; the per-workgroup lines of both passes; for the depth an event path of its own under
+// the stage's filter (per record the block offsets, per event the sorter's pairs and the scanned deltas), so the coverage track's buffers stay what they were
+struct RmState {
+    DBuf<unsigned long long> words, body; DBuf<uint64_t> line, blk_tile, part; DBuf<uint32_t> blk_off, incl, dep_tile; SortBufs sort;
+    DevStat<unsigned long long, CV_ST_WORDS> stat;      // CV_ST_* words: k_cv_count's, and the scanned deltas' total
+    EvSet<6> ev;                                        // around the class pass, the counting walk, the event path and the body pass
+    bool valid = false; size_t n_words = 0; float ms[3] = {0.f, 0.f, 0.f};
+    int max_groups = RM_GROUPS;     // DG_RNA_MAX_GROUPS: test hook, caps the grids of k_rm_class and k_rm_body
+    hipError_t ready() { const hipError_t e = stat.ready(); return e != hipSuccess ? e : ev.ready(); }
+};
 // MD / NM / ts on the sorted array (dg_tags.h): the second array with its records' places and tile sums -- after a call they ARE the store's sorted array
 // (dg_bam_tags_finish swaps them with bs.sorted, the sorter's other key buffer and bs.tile), and what lies here is the old one, kept for the next call
 struct TgState {

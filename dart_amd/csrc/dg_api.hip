@@ -24,6 +24,7 @@
 #include "dg_qc.h"
 #include "dg_tags.h"
 #include "dg_genecount.h"
+#include "dg_rnametrics.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -103,6 +104,9 @@ struct IndexShared {
     uint32_t *d_chr_name_off = nullptr; char *d_chr_names = nullptr; bool chr_names_set = false; uint64_t chr_names_gen = 0; uint32_t chr_name_max = 0;
     // the gene annotation's segment table (dg_gene_set_annotation, dg_genecount.h): with the index, so every clone counts with it; gc_gen: 0 = none
     uint32_t *d_gc_chr_first = nullptr, *d_gc_seg_start = nullptr, *d_gc_seg_lab = nullptr; uint32_t gc_n_genes = 0; size_t gc_n_seg = 0; uint64_t gc_gen = 0;
+    // the transcript annotation's tables (dg_rna_set_annotation, dg_rnametrics.h): the segment table, the eligible transcripts and their merged exons; rm_gen: 0 = none
+    uint32_t *d_rm_chr_first = nullptr, *d_rm_seg_start = nullptr, *d_rm_seg_cs = nullptr; RmTx *d_rm_tx = nullptr; RmExon *d_rm_ex = nullptr;
+    size_t rm_n_seg = 0, rm_n_tx = 0, rm_n_elig = 0; uint64_t rm_gen = 0;
 };
 
 struct dg_ctx {
@@ -154,7 +158,7 @@ struct dg_ctx {
     bool batch_done = false;       // the batch on the context has been run and waited for
     bool no_batch = false;         // the last upload was a DG_FQ_CHECK_ONLY: there is nothing to run
     // the library stages' state, one struct each (api_ctx.h); every stage's section of this file drives its own
-    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; TgState tg; GcState gc;
+    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; TgState tg; GcState gc; RmState rm;
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
@@ -192,6 +196,7 @@ static void read_env(dg_ctx *c)
     c->bs.first_cap = (size_t)std::max(0, geti("DG_BAMSORT_FIRST_CAP", 0));
     c->md.hash_bits = geti("DG_MARKDUP_HASH_BITS", MD_HASH_BITS); if (c->md.hash_bits < 1 || c->md.hash_bits > MD_HASH_BITS) c->md.hash_bits = MD_HASH_BITS;
     c->qc.max_groups = geti("DG_QC_MAX_GROUPS", QC_GROUPS); if (c->qc.max_groups < 1 || c->qc.max_groups > QC_GROUPS) c->qc.max_groups = QC_GROUPS;
+    c->rm.max_groups = geti("DG_RNA_MAX_GROUPS", RM_GROUPS); if (c->rm.max_groups < 1 || c->rm.max_groups > RM_GROUPS) c->rm.max_groups = RM_GROUPS;
     c->env_seed_multi = geti("DG_SEED_MULTI", 4); if (c->env_seed_multi < 0 || c->env_seed_multi > SQF_MULTI_MAX) c->env_seed_multi = SQF_MULTI_MAX;   // rows of an interval that are located and compared with the text at once (0: single rows only)
 }
 
@@ -549,6 +554,7 @@ extern "C" void dg_destroy(dg_ctx *c)
         if (sh->d_chr_name_off) (void)hipFree(sh->d_chr_name_off);
         if (sh->d_chr_names) (void)hipFree(sh->d_chr_names);
         for (void *p : {(void *)sh->d_gc_chr_first, (void *)sh->d_gc_seg_start, (void *)sh->d_gc_seg_lab}) if (p) (void)hipFree(p);
+        for (void *p : {(void *)sh->d_rm_chr_first, (void *)sh->d_rm_seg_start, (void *)sh->d_rm_seg_cs, (void *)sh->d_rm_tx, (void *)sh->d_rm_ex}) if (p) (void)hipFree(p);
         delete sh; c->shared_ix = nullptr;
     }
     void *ptrs[] = { c->d_bwt, c->d_sa, c->d_pac, c->d_lockey, c->d_locchr, c->d_chroff };
@@ -2698,7 +2704,7 @@ static int bs_view(dg_ctx *c, const char *fn, BsView &v)
     return DG_OK;
 }
 // the bytes of the sorted array changed (a new sort, duplicate flags written): no block of it has been compressed, and no index or track covers it
-static void bs_array_changed(dg_ctx *c) { c->bi.valid = false; c->bi.covered.clear(); c->cv.valid = false; c->pu.valid = false; c->qc.valid = false; }
+static void bs_array_changed(dg_ctx *c) { c->bi.valid = false; c->bi.covered.clear(); c->cv.valid = false; c->pu.valid = false; c->qc.valid = false; c->rm.valid = false; }
 
 extern "C" int dg_bam_sort_granules(int out[3])
 {
@@ -3702,6 +3708,184 @@ extern "C" int dg_bam_qc_device_ms(dg_ctx *c, float ms[2])
 {
     if (!c || !ms) return DG_ERR_ARG;
     ms[0] = c->qc.ms[0]; ms[1] = c->qc.ms[1];
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// the RNA-seq metrics of the sorted array (dg_rnametrics.h): the annotation's tables live with the index, the words and the event path's buffers with the
+// context; read-only on the sorted array
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_bam_rna_granules(int out[2])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = RM_THREADS; out[1] = RM_TX_PER_WG;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_rna_offsets(size_t out[6])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = rm_off_ba(); out[1] = rm_off_rc(); out[2] = rm_off_st(); out[3] = rm_off_bc(); out[4] = rm_off_sn(); out[5] = rm_words();
+    return DG_OK;
+}
+
+extern "C" int dg_bam_rna_format(const uint64_t *words, size_t n_words, char *out, size_t cap, size_t *n_bytes)
+{
+    if (n_bytes) *n_bytes = 0;
+    if (!words || n_words != rm_words() || (!out && cap)) return DG_ERR_ARG;
+    std::string text;
+    rm_format(words, text);
+    if (n_bytes) *n_bytes = text.size();
+    if (cap < text.size()) return DG_ERR_CAPACITY;
+    if (!text.empty()) memcpy(out, text.data(), text.size());
+    return DG_OK;
+}
+
+extern "C" int dg_rna_set_annotation(dg_ctx *c, const dg_rna_annot *a, size_t *n_segments, size_t *n_eligible)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_segments) *n_segments = 0;
+    if (n_eligible) *n_eligible = 0;
+    IndexShared *sh = c->shared_ix;
+    if (!sh || !a) { snprintf(c->err, 512, "dg_rna_set_annotation: no annotation (or a context without an index)"); return DG_ERR_ARG; }
+    RmFlat fl;
+    char why[400];
+    if (!rm_flatten(c->ix.n_chr, a, fl, why, sizeof why)) { snprintf(c->err, 512, "dg_rna_set_annotation: %s", why); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(sh->mu);
+    void *d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const void *src[5] = {fl.chr_first.data(), fl.seg_start.data(), fl.seg_cs.data(), fl.tx.data(), fl.ex.data()};
+    const size_t bytes[5] = {fl.chr_first.size() * 4, fl.seg_start.size() * 4, fl.seg_cs.size() * 4, fl.tx.size() * sizeof(RmTx), fl.ex.size() * sizeof(RmExon)};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 5 && e == hipSuccess; k++) {
+        e = hipMalloc(&d[k], bytes[k] + 64);
+        if (e == hipSuccess && bytes[k]) e = hipMemcpy(d[k], src[k], bytes[k], hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { for (void *p : d) if (p) (void)hipFree(p); return fail(c, DG_ERR_HIP, "the transcript annotation's tables", e); }
+    // dg_bam_rna_finish reads the pointers and enqueues the kernels that use them under sh->mu: under the lock every kernel that may read the old tables is
+    // already in a stream, so the device is waited for, then they are freed (as dg_gene_set_annotation does)
+    if (sh->rm_gen) { (void)hipDeviceSynchronize(); for (void *p : {(void *)sh->d_rm_chr_first, (void *)sh->d_rm_seg_start, (void *)sh->d_rm_seg_cs, (void *)sh->d_rm_tx, (void *)sh->d_rm_ex}) (void)hipFree(p); }
+    sh->d_rm_chr_first = (uint32_t *)d[0]; sh->d_rm_seg_start = (uint32_t *)d[1]; sh->d_rm_seg_cs = (uint32_t *)d[2]; sh->d_rm_tx = (RmTx *)d[3]; sh->d_rm_ex = (RmExon *)d[4];
+    sh->rm_n_seg = fl.seg_start.size(); sh->rm_n_tx = a->n_tx; sh->rm_n_elig = fl.tx.size(); sh->rm_gen++;
+    if (n_segments) *n_segments = fl.seg_start.size();
+    if (n_eligible) *n_eligible = fl.tx.size();
+    return DG_OK;
+}
+
+extern "C" int dg_bam_rna_finish(dg_ctx *c, uint32_t flags, uint32_t exclude_flags, uint32_t min_mapq, uint64_t min_cov, size_t *n_words, float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_rna_finish";
+    if (n_words) *n_words = 0;
+    if (device_ms) *device_ms = 0.f;
+    c->rm.valid = false; c->rm.n_words = 0;
+    for (float &m : c->rm.ms) m = 0.f;
+    BsView sv;
+    { const int rc = bs_view(c, fn, sv); if (rc) return rc; }
+    if (flags) { snprintf(c->err, 512, "%s: flags 0x%x hold a bit that is not defined", fn, flags); return DG_ERR_ARG; }
+    IndexShared *sh = c->shared_ix;
+    uint64_t gen = 0;
+    if (sh) { std::lock_guard<std::mutex> lk(sh->mu); gen = sh->rm_gen; }
+    if (!gen) { snprintf(c->err, 512, "%s: no transcript annotation (dg_rna_set_annotation first)", fn); return DG_ERR_ARG; }
+    HIPCHK(c->rm.ready());
+    const size_t n = sv.n, n_raw = sv.n_raw;
+    const int n_chr = sv.n_chr;
+    if (n_chr < 1) { snprintf(c->err, 512, "%s: %d chromosomes", fn, n_chr); return DG_ERR_ARG; }
+    const size_t nw = rm_words();
+    const CvFilter f{0u, exclude_flags, min_mapq};
+    const uint32_t tiles = (uint32_t)((n + CV_THREADS - 1) / CV_THREADS), cap = (uint32_t)c->rm.max_groups, g_class = std::min(cap, tiles);
+    BS_ENSURE(c->rm.words, nw, "the words");
+    BS_ENSURE(c->rm.line, (size_t)RM_PLANES * g_class + 1, "the per-workgroup lines");
+    BS_ENSURE(c->rm.blk_off, n + 1, "the records' block offsets"); BS_ENSURE(c->rm.blk_tile, (size_t)tiles + 1, "the per-workgroup block counts");
+    BS_ENSURE(c->rm.part, (size_t)CV_PLANES * tiles + 1, "the per-workgroup values");
+    size_t n_elig = 0;
+    HIPCHK(hipMemsetAsync(c->rm.words.p, 0, nw * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->rm.stat.d, 0, CV_ST_WORDS * 8, c->stream));
+    {   // the tables are read and the kernels that use them enqueued under the index's lock (dg_rna_set_annotation waits for the device before it frees them)
+        std::lock_guard<std::mutex> lk(sh->mu);
+        if (sh->rm_gen != gen) { snprintf(c->err, 512, "%s: the annotation was replaced while the call was being prepared", fn); return DG_ERR_ARG; }
+        const RmTable t{sh->d_rm_chr_first, sh->d_rm_seg_start, sh->d_rm_seg_cs, n_chr};
+        n_elig = sh->rm_n_elig;
+        HIPCHK(hipEventRecord(c->rm.ev[0], c->stream));
+        if (n) k_rm_class<<<g_class, RM_THREADS, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, t, f, c->rm.line.p);
+        k_rm_top<<<1, RM_THREADS, 0, c->stream>>>(c->rm.line.p, n ? g_class : 0u, (unsigned long long)n, (unsigned long long)sh->rm_n_tx, (unsigned long long)n_elig, (unsigned long long)sh->rm_n_seg, c->rm.words.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->rm.ev[1], c->stream));
+    }
+    if (n) {
+        k_cv_count<<<tiles, CV_THREADS, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, n_chr, f, c->rm.blk_off.p, c->rm.blk_tile.p, c->rm.part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->rm.blk_tile.p, tiles, c->rm.stat.d + CV_ST_BLOCKS, c->rm.part.p, 5, 2, c->rm.stat.d + CV_ST_COUNTED);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(c->rm.ev[2], c->stream));
+    HIPCHK(c->rm.stat.fetch(c->stream));
+    HIPCHK(wait_stream(c));                                       // the first wait: how many events, which digits their keys differ in, and what was out of range
+    if (c->rm.stat.h[CV_ST_NBAD]) {
+        snprintf(c->err, 512, "%s: record %llu of the sorted array has a block that ends behind position 2^32 - 1; no words were built", fn, ~c->rm.stat.h[CV_ST_NBAD]);
+        return DG_ERR_RANGE;
+    }
+    const unsigned long long n_blocks = c->rm.stat.h[CV_ST_BLOCKS];
+    if (2 * n_blocks >= 0xFFFFF000ull) { snprintf(c->err, 512, "%s: %llu events (two per block) are more than the sorter takes (2^32 - 1, less a tile)", fn, 2 * n_blocks); return DG_ERR_CAPACITY; }
+    c->rm.ms[0] = c->rm.ev.ms(0, 1); c->rm.ms[1] = c->rm.ev.ms(1, 2);
+    if (n_blocks && n_elig) {
+        const uint32_t n_ev = (uint32_t)(2 * n_blocks), etiles = (n_ev + CV_THREADS - 1) / CV_THREADS;
+        const uint32_t g_body = (uint32_t)std::min<size_t>(cap, (n_elig + RM_TX_PER_WG - 1) / RM_TX_PER_WG);
+        for (int k = 0; k < 2; k++) { BS_ENSURE(c->rm.sort.k[k], (size_t)n_ev, "the events' keys"); BS_ENSURE(c->rm.sort.v[k], (size_t)n_ev, "the events' deltas"); }
+        BS_ENSURE_SORT(c->rm.sort, n_ev);
+        BS_ENSURE(c->rm.incl, (size_t)n_ev, "the scanned deltas"); BS_ENSURE(c->rm.dep_tile, (size_t)etiles + 1, "the per-workgroup depth sums");
+        BS_ENSURE(c->rm.body, (size_t)RM_BODY_LINE * g_body, "the body pass's per-workgroup lines");
+        const int bits = std::min(cv_key_bits(~c->rm.stat.h[CV_ST_NMIN], c->rm.stat.h[CV_ST_MAX]), cv_key_bits_max(n_chr));
+        int which = 0;
+        HIPCHK(hipEventRecord(c->rm.ev[3], c->stream));
+        k_cv_emit<<<tiles, CV_THREADS, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, n_chr, f, c->rm.blk_off.p, c->rm.blk_tile.p, n_blocks, c->rm.sort.k[0].p, c->rm.sort.v[0].p);
+        HIPCHK(hipGetLastError());
+        { const int rc = c->rm.sort.sort(c, n_ev, bits, which); if (rc) return rc; }
+        k_cv_depth<<<etiles, CV_THREADS, 0, c->stream>>>(c->rm.sort.v[which].p, n_ev, c->rm.incl.p, c->rm.dep_tile.p);
+        k_tiles_top<uint32_t><<<1, 256, 0, c->stream>>>(c->rm.dep_tile.p, etiles, (uint32_t *)(c->rm.stat.d + CV_ST_DEPTH_END));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(c->rm.ev[4], c->stream));
+        {
+            std::lock_guard<std::mutex> lk(sh->mu);
+            if (sh->rm_gen != gen) { snprintf(c->err, 512, "%s: the annotation was replaced while the call was running", fn); return DG_ERR_ARG; }
+            k_rm_body<<<g_body, RM_THREADS, 0, c->stream>>>(sh->d_rm_tx, sh->d_rm_ex, (uint32_t)n_elig, c->rm.sort.k[which].p, c->rm.incl.p, c->rm.dep_tile.p, n_ev, (unsigned long long)min_cov, c->rm.body.p);
+            k_rm_body_top<<<RM_BODY_LINE / RM_TX_PER_WG, RM_THREADS, 0, c->stream>>>(c->rm.body.p, g_body, c->rm.words.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(c->rm.ev[5], c->stream));
+        }
+        HIPCHK(c->rm.stat.fetch(c->stream));
+        HIPCHK(wait_stream(c));                                   // the second wait
+        if ((uint32_t)c->rm.stat.h[CV_ST_DEPTH_END] != 0u) { snprintf(c->err, 512, "%s: %u events leave the depth %u behind the last", fn, n_ev, (uint32_t)c->rm.stat.h[CV_ST_DEPTH_END]); return DG_ERR_INTERNAL; }
+        c->rm.ms[1] += c->rm.ev.ms(3, 4); c->rm.ms[2] = c->rm.ev.ms(4, 5);
+    }
+    c->rm.valid = true; c->rm.n_words = nw;
+    if (n_words) *n_words = nw;
+    if (device_ms) *device_ms = c->rm.ms[0] + c->rm.ms[1] + c->rm.ms[2];
+    return DG_OK;
+}
+
+extern "C" int dg_bam_rna_download(dg_ctx *c, uint64_t *words, size_t cap_words)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->rm.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_rna_download: no words (dg_bam_rna_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if (!words || cap_words < c->rm.n_words) { snprintf(c->err, 512, "dg_bam_rna_download: output capacity too small: %zu words are needed", c->rm.n_words); return DG_ERR_CAPACITY; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(words, c->rm.words.p, c->rm.n_words * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_bam_rna_device(dg_ctx *c, void **words)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!c->rm.valid || !c->bs.fin_valid) { snprintf(c->err, 512, "dg_bam_rna_device: no words (dg_bam_rna_finish first, and no store call behind it)"); return DG_ERR_ARG; }
+    if (words) *words = c->rm.words.p;
+    return DG_OK;
+}
+
+extern "C" int dg_bam_rna_device_ms(dg_ctx *c, float ms[3])
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    for (int k = 0; k < 3; k++) ms[k] = c->rm.ms[k];
     return DG_OK;
 }
 

@@ -48,6 +48,9 @@ struct Config {
     uint32_t pu_min_alt = 2u, pu_exclude = 0x704u, pu_min_mapq = 0u;   // DART_PILEUP_MIN_ALT, DART_PILEUP_EXCLUDE, DART_PILEUP_MIN_MAPQ
     bool qc = false;                        // DART_QC
     uint32_t qc_exclude = 0x904u, qc_min_mapq = 0u;                    // DART_QC_EXCLUDE, DART_QC_MIN_MAPQ
+    const char *rna_gtf = nullptr;          // DART_RNA_METRICS (empty = unset)
+    uint32_t rna_exclude = 0x904u, rna_min_mapq = 0u;                  // DART_RNA_EXCLUDE, DART_RNA_MIN_MAPQ
+    uint64_t rna_min_cov = 100u;            // DART_RNA_MIN_COV
     uint32_t bam_tags = 0u;                 // DART_BAM_TAGS: DG_TAG_* bits, 0 = not asked for
     double sort_piece_mb = 256.0;           // DART_SORT_PIECE_MB, raw: the piece arithmetic is where the pieces are cut
     const char *gene_gtf = nullptr;         // DART_GENE_COUNTS (empty = unset)
@@ -67,6 +70,7 @@ struct Config {
     std::vector<std::pair<std::string, uint32_t>> cov_tracks;      // the coverage tracks: path, strand flags
     std::string bai_path, md_path, genes_path, sites_path;         // <out>.bai, <out>.markdup.txt, <out>.genes.tab, <out>.sites.tsv; empty = not asked for
     std::string qc_path;                                           // <out>.qc.txt; empty = not asked for
+    std::string rna_path;                                          // <out>.rna_metrics.txt; empty = not asked for
     const char *bam_dev_note = "";          // the `bam=` field of the DART_TIMING lines: the parallel pipeline's ...
     const char *bam_host_note = "";         // ... and the streaming pipeline's
 
@@ -239,6 +243,20 @@ struct Config {
         if (const char *v = lookup("DART_QC_EXCLUDE")) qc_exclude = (uint32_t)strtoul(v, nullptr, 0);
         if (const char *v = lookup("DART_QC_MIN_MAPQ")) qc_min_mapq = (uint32_t)strtoul(v, nullptr, 0);
         if (qc) qc_path = std::string(out) + ".qc.txt";
+        // DART_RNA_METRICS=<annotation.gtf> beside DART_SORT_BAM=1: the sorted file's RNA-seq metrics <out>.rna_metrics.txt -- aligned bases by class (coding, UTR,
+        // intronic, intergenic, ribosomal), records by class and by strand against the annotation, the gene-body coverage profile -- built on the device from the
+        // sorted records and the annotation's transcripts (dg_bam_rna_finish) in place of Picard CollectRnaSeqMetrics over the file; behind the duplicate marking
+        // and the tagging when they are on.  DART_RNA_EXCLUDE (default 0x904) and DART_RNA_MIN_MAPQ (default 0) pick the records, DART_RNA_MIN_COV (default 100)
+        // the transcripts whose profile counts.  Without the sort there is nothing to look at: no output is begun.
+        { const char *v = lookup("DART_RNA_METRICS"); rna_gtf = v && v[0] ? v : nullptr; }
+        if (rna_gtf && !sort_bam) {
+            fprintf(err_f, "Error! DART_RNA_METRICS=%s needs DART_SORT_BAM=1 (and with it -bo and DART_DEVICE_BAM=1): DART_SORT_BAM=1 is missing\n", rna_gtf);
+            return 1;
+        }
+        if (const char *v = lookup("DART_RNA_EXCLUDE")) rna_exclude = (uint32_t)strtoul(v, nullptr, 0);
+        if (const char *v = lookup("DART_RNA_MIN_MAPQ")) rna_min_mapq = (uint32_t)strtoul(v, nullptr, 0);
+        if (const char *v = lookup("DART_RNA_MIN_COV")) rna_min_cov = (uint64_t)strtoull(v, nullptr, 0);
+        if (rna_gtf) rna_path = std::string(out) + ".rna_metrics.txt";
         // DART_BAM_TAGS beside DART_SORT_BAM=1: a comma list of MD, NM, ts (1 or all: all three): the sorted records get MD:Z, NM as edit distance and ts:A on the
         // device (dg_bam_tags_finish) behind the duplicate marking and before the first piece is compressed, in place of a `samtools calmd` over the file.  A word
         // that is none of them ends the run before any output exists; so does a missing sort: there is nothing to tag.

@@ -358,7 +358,7 @@ struct Output { FILE *sam = nullptr; BamWriter bam; };      // -o: the SAM file 
 //   the same without DART_SORT_BAM                          BEFORE_CLOSE  no                stays   -           -         an unsorted run keeps
 //   bam.close() itself fails                                CLOSE_FAILED  no (not twice)    yes*    yes         yes       its partial file)
 //   a coverage track, the site table or the QC fails (BAM and
-//     .bai are complete)                                    AFTER_CLOSE   no                stays   stays       yes      (<out>.sites.tsv and <out>.qc.txt go with the tracks)
+//     .bai are complete)                                    AFTER_CLOSE   no                stays   stays       yes      (<out>.sites.tsv, <out>.qc.txt and <out>.rna_metrics.txt go with the tracks)
 //
 //   * with DART_SORT_BAM; without it the file stays, and none of the others can exist.  (<out>.genes.tab is the gene stage's own.)
 enum AbandonAt { BEFORE_CLOSE, CLOSE_FAILED, AFTER_CLOSE };
@@ -374,12 +374,13 @@ static void abandon_outputs(const Config &c, Output &o, AbandonAt at)
     if (c.mark_dups) remove(c.md_path.c_str());
     if (c.pileup) remove(c.sites_path.c_str());
     if (c.qc) remove(c.qc_path.c_str());
+    if (c.rna_gtf) remove(c.rna_path.c_str());
 }
 
 // The contexts: one root per device (the index files go to its HBM inside dg_init_files, main.cpp:231-235 / bwt_index.cpp:147-159), clones
 // for the batches in flight.  The look-up aids are built in the background while the first batches are mapped (DART_SYNC_AIDS=1: before).
 // Then the gene annotation and the chromosome names to every root.
-static int make_contexts(Job &job, const HostIndex &ix, const GtfAnnotation &gtf, int n_gpu)
+static int make_contexts(Job &job, const HostIndex &ix, const GtfAnnotation &gtf, const GtfTranscripts &rna, int n_gpu)
 {
     {
         const std::string pb = std::string(job.cfg.index) + ".bwt", ps = std::string(job.cfg.index) + ".sa", pp = std::string(job.cfg.index) + ".pac";
@@ -422,6 +423,15 @@ static int make_contexts(Job &job, const HostIndex &ix, const GtfAnnotation &gtf
         dg_gene_annot ann; ann.n_genes = (uint32_t)gtf.genes.size(); ann.pad = 0; ann.n_exons = gtf.exons.size(); ann.exons = gtf.exons.data();
         for (dg_ctx *r : job.roots) if (dg_gene_set_annotation(r, &ann, nullptr)) {
             fprintf(stderr, "Error! DART_GENE_COUNTS=%s: %s\n", job.cfg.gene_gtf, dg_last_error(r));
+            for (auto x : job.clones) dg_destroy(x);
+            for (auto x : job.roots) dg_destroy(x);
+            return 1;
+        }
+    }
+    if (job.cfg.rna_gtf) {       // the transcripts go to every root too
+        dg_rna_annot ann; ann.n_tx = (uint32_t)rna.tx.size(); ann.pad = 0; ann.n_exons = rna.exons.size(); ann.tx = rna.tx.data(); ann.exons = rna.exons.data();
+        for (dg_ctx *r : job.roots) if (dg_rna_set_annotation(r, &ann, nullptr, nullptr)) {
+            fprintf(stderr, "Error! DART_RNA_METRICS=%s: %s\n", job.cfg.rna_gtf, dg_last_error(r));
             for (auto x : job.clones) dg_destroy(x);
             for (auto x : job.roots) dg_destroy(x);
             return 1;
@@ -895,6 +905,31 @@ static int write_qc(Job &job, const HostIndex &ix, Output &o)
     return RUN;
 }
 
+// DART_RNA_METRICS: the RNA-seq metrics of the sorted (and, with DART_MARK_DUPLICATES and DART_BAM_TAGS, marked and tagged) array, which still lies in HBM, against
+// the annotation's transcripts; the text is made on the host from the downloaded words.  The BAM and its index are complete and closed, and a failure here
+// leaves them as they are
+static int write_rna_metrics(Job &job, Output &o)
+{
+    dg_ctx *root = job.roots[0];
+    const double tr0 = now_s();
+    size_t nw = 0, nb = 0; float ms = 0.f;
+    int rc = dg_bam_rna_finish(root, 0, job.cfg.rna_exclude, job.cfg.rna_min_mapq, job.cfg.rna_min_cov, &nw, &ms);
+    std::vector<uint64_t> words(nw ? nw : 1);
+    if (!rc) rc = dg_bam_rna_download(root, words.data(), nw);
+    if (rc) { abandon_outputs(job.cfg, o, AFTER_CLOSE); fprintf(stderr, "\nError! DART_RNA_METRICS=%s: %s\n", job.cfg.rna_gtf, dg_last_error(root)); return 1; }
+    std::vector<char> text(1);
+    rc = dg_bam_rna_format(words.data(), nw, nullptr, 0, &nb);
+    if (rc == DG_ERR_CAPACITY) { text.resize(nb ? nb : 1); rc = dg_bam_rna_format(words.data(), nw, text.data(), nb, &nb); }
+    if (rc) { abandon_outputs(job.cfg, o, AFTER_CLOSE); fprintf(stderr, "\nError! DART_RNA_METRICS=%s: the metrics' text could not be made (%d)\n", job.cfg.rna_gtf, rc); return 1; }
+    FILE *rf = fopen(job.cfg.rna_path.c_str(), "wb");
+    const bool ok = rf && fwrite(text.data(), 1, nb, rf) == nb;
+    if (!(rf && fclose(rf) == 0 && ok)) { abandon_outputs(job.cfg, o, AFTER_CLOSE); fprintf(stderr, "Error while writing %s\n", job.cfg.rna_path.c_str()); return 1; }
+    if (job.cfg.timing)
+        fprintf(stderr, "[dart timing] rna metrics: %zu words, %zu bytes; %.3f s (kernels %.3f s; exclude 0x%x, min mapq %u, min cov %llu)\n", nw, nb, now_s() - tr0, ms * 1e-3, job.cfg.rna_exclude,
+                job.cfg.rna_min_mapq, (unsigned long long)job.cfg.rna_min_cov);
+    return RUN;
+}
+
 // DART_DEVICE_SJ: the clones' tables into their root's, further roots' into the first (downloaded entries, counted again there), then the table is sorted,
 // mapped to chromosomes and printed on the device: the text is junctions.tab
 struct SjTable { std::string text; size_t entries = 0, lines = 0; float finish_ms = 0.f; };
@@ -1035,7 +1070,16 @@ int main(int argc, char *argv[])
         if (gtf.skipped_seq || gtf.skipped_strand)
             fprintf(stderr, "DART_GENE_COUNTS: skipped %zu '%s' lines on sequences the index lacks and %zu with a strand other than + or -\n", gtf.skipped_seq, cfg.gene_feature, gtf.skipped_strand);
     }
-    if ((rc = make_contexts(job, ix, gtf, n_gpu)) != RUN) return rc;
+    // DART_RNA_METRICS: the same for its GTF
+    GtfTranscripts rna;
+    if (cfg.rna_gtf) {
+        remove(cfg.rna_path.c_str());
+        const std::string rerr = gtf_parse_transcripts(cfg.rna_gtf, ix.names, rna);
+        if (!rerr.empty()) { fprintf(stderr, "\nError! DART_RNA_METRICS=%s: %s\n", cfg.rna_gtf, rerr.c_str()); return 1; }
+        if (rna.skipped_seq || rna.skipped_strand)
+            fprintf(stderr, "DART_RNA_METRICS: skipped %zu lines on sequences the index lacks and %zu with a strand other than + or -\n", rna.skipped_seq, rna.skipped_strand);
+    }
+    if ((rc = make_contexts(job, ix, gtf, rna, n_gpu)) != RUN) return rc;
     job.start_up_s = now_s() - t_proc0;
     fprintf(stdout, "\nLoad the reference sequences...\n");
     if ((rc = open_output(job, ix, out)) != RUN) return rc;
@@ -1054,6 +1098,7 @@ int main(int argc, char *argv[])
     if (cfg.coverage && (rc = write_coverage(job, out)) != RUN) return rc;
     if (cfg.pileup && (rc = write_pileup(job, out)) != RUN) return rc;
     if (cfg.qc && (rc = write_qc(job, ix, out)) != RUN) return rc;
+    if (cfg.rna_gtf && (rc = write_rna_metrics(job, out)) != RUN) return rc;
     SjTable sj;
     if (cfg.device_sj && (rc = finish_junctions(job, sj)) != RUN) return rc;
     unsigned long long gene_counted = 0;

@@ -51,6 +51,15 @@ GENE_NONE, GENE_AMBIG = 0xFFFFFFFF, 0xFFFFFFFE
 
 class GeneAnnot(C.Structure):
     _fields_ = [("n_genes", C.c_uint32), ("pad", C.c_uint32), ("n_exons", C.c_size_t), ("exons", C.c_void_p)]
+
+
+RNA_TX = np.dtype([("chr", "<i4"), ("strand", "<u4"), ("flags", "<u4"), ("cds_start", "<u4"), ("cds_end", "<u4"), ("n_exons", "<u4"), ("first_exon", "<u8")])      # dg_rna_tx
+RNA_EXON = np.dtype([("start", "<u4"), ("end", "<u4")])                                           # dg_rna_exon
+RNA_TX_RIBOSOMAL = 1                                                                              # DG_RNA_TX_RIBOSOMAL
+
+
+class RnaAnnot(C.Structure):
+    _fields_ = [("n_tx", C.c_uint32), ("pad", C.c_uint32), ("n_exons", C.c_size_t), ("tx", C.c_void_p), ("exons", C.c_void_p)]
 assert READ_OUT.itemsize == 36 and REPORT_OUT.itemsize == 40 and SJ_OUT.itemsize == 24 and READ_C.itemsize == 12 and REPORT_C.itemsize == 16
 
 
@@ -347,6 +356,15 @@ def _load_lib():
         lib.dg_bam_tags_device_ms.argtypes = [vp, vp]
         lib.dg_bam_tags_granules.argtypes = [vp]
         lib.dg_bam_tags_write_ms.argtypes = [vp, vp]                # (a probe's hook, not in include/dartgpu.h)
+    if hasattr(lib, "dg_bam_rna_finish"):                    # (likewise: the RNA-seq metrics of the sorted array)
+        lib.dg_rna_set_annotation.argtypes = [vp, vp, vp, vp]
+        lib.dg_bam_rna_finish.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, vp, vp]
+        lib.dg_bam_rna_download.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_bam_rna_device.argtypes = [vp, vp]
+        lib.dg_bam_rna_device_ms.argtypes = [vp, vp]
+        lib.dg_bam_rna_granules.argtypes = [vp]
+        lib.dg_bam_rna_offsets.argtypes = [vp]
+        lib.dg_bam_rna_format.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp]
     if hasattr(lib, "dg_gene_set_annotation"):               # (likewise: gene-level read counts)
         lib.dg_gene_set_annotation.argtypes = [vp, vp, vp]
         lib.dg_batch_accumulate_genes.argtypes = [vp, C.c_int, C.c_uint32, vp]
@@ -451,6 +469,34 @@ def qc_text(lib, words, names, lengths) -> bytes:
     rc = lib.dg_bam_qc_format(w.ctypes.data, len(w), len(nm), arr, ln.ctypes.data, buf.ctypes.data, int(nb.value), C.byref(nb))
     if rc != 0:
         raise RuntimeError("dg_bam_qc_format failed (%d)" % rc)
+    return buf[:int(nb.value)].tobytes()
+
+
+RNA_SECTIONS = (("BA", (5,)), ("RC", (5,)), ("ST", (4,)), ("BC", (3, 100)), ("SN", (16,)))
+
+
+def rna_views(lib, words):
+    """the flat RNA-metrics words (dg_bam_rna_download) sliced into named views by dg_bam_rna_offsets"""
+    off = (C.c_size_t * 6)()
+    if lib.dg_bam_rna_offsets(off) != 0 or int(off[5]) != len(words):
+        raise RuntimeError("dg_bam_rna_offsets: %d words where %d are expected" % (len(words), int(off[5])))
+    out = {"words": words}
+    for k, (name, shape) in enumerate(RNA_SECTIONS):
+        out[name] = words[int(off[k]):int(off[k + 1])].reshape(shape)
+    return out
+
+
+def rna_text(lib, words) -> bytes:
+    """dg_bam_rna_format: the text of the flat RNA-metrics words (or of a dict of rna_views); needs no device"""
+    w = np.ascontiguousarray(words["words"] if isinstance(words, dict) else words, np.uint64)
+    nb = C.c_size_t(0)
+    rc = lib.dg_bam_rna_format(w.ctypes.data, len(w), None, 0, C.byref(nb))
+    if rc not in (0, -4):
+        raise RuntimeError("dg_bam_rna_format failed (%d)" % rc)
+    buf = np.zeros(max(int(nb.value), 1), np.uint8)
+    rc = lib.dg_bam_rna_format(w.ctypes.data, len(w), buf.ctypes.data, int(nb.value), C.byref(nb))
+    if rc != 0:
+        raise RuntimeError("dg_bam_rna_format failed (%d)" % rc)
     return buf[:int(nb.value)].tobytes()
 
 
@@ -945,6 +991,41 @@ class DartGPU:
         words = np.zeros(int(nw.value), np.uint64)
         self._chk(self.lib.dg_bam_qc_download(self.ctx, words.ctypes.data, len(words)), "dg_bam_qc_download")
         return qc_views(self.lib, words, len(self.index.names))
+
+    # ---- the RNA-seq metrics of the sorted array (dg_rna_set_annotation, dg_bam_rna_*): base classes, strand and gene-body coverage, built in HBM ----
+    def rna_set_annotation(self, tx, exons):
+        """flattens and uploads the transcript annotation, kept with the index and shared by clones (dg_rna_set_annotation) -> (segments, eligible
+        transcripts); tx: an RNA_TX array, exons: an RNA_EXON array, 0-based half-open coordinates"""
+        t = np.ascontiguousarray(tx, RNA_TX); e = np.ascontiguousarray(exons, RNA_EXON)
+        keep_t = t if len(t) else np.zeros(1, RNA_TX); keep_e = e if len(e) else np.zeros(1, RNA_EXON)
+        ann = RnaAnnot(len(t), 0, len(e), keep_t.ctypes.data, keep_e.ctypes.data)
+        ns, ne = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self.lib.dg_rna_set_annotation(self.ctx, C.byref(ann), C.byref(ns), C.byref(ne)), "dg_rna_set_annotation")
+        return int(ns.value), int(ne.value)
+
+    def bam_rna_granules(self):
+        """(records per workgroup trip of the class pass, transcripts per workgroup trip of the body pass) (dg_bam_rna_granules)"""
+        g = (C.c_int * 2)()
+        self._chk(self.lib.dg_bam_rna_granules(g), "dg_bam_rna_granules")
+        return int(g[0]), int(g[1])
+
+    def bam_rna_finish(self, exclude: int = 0x904, min_mapq: int = 0, min_cov: int = 100):
+        """the RNA-seq metrics of the sorted array (dg_bam_rna_finish + dg_bam_rna_download) -> dict of numpy views into one uint64 array: "words" (all of
+        them), "BA" [5], "RC" [5], "ST" [4], "BC" [3, 100], "SN" [16].  self.bam_rna_device_ms = the kernels' device time, self.bam_rna_device_ms_split =
+        (class pass, events and sort, body pass)"""
+        nw, ms = C.c_size_t(0), C.c_float(0)
+        self._chk(self.lib.dg_bam_rna_finish(self.ctx, 0, int(exclude), int(min_mapq), int(min_cov), C.byref(nw), C.byref(ms)), "dg_bam_rna_finish")
+        self.bam_rna_device_ms = float(ms.value)
+        split = (C.c_float * 3)()
+        self._chk(self.lib.dg_bam_rna_device_ms(self.ctx, split), "dg_bam_rna_device_ms")
+        self.bam_rna_device_ms_split = tuple(float(x) for x in split)
+        words = np.zeros(int(nw.value), np.uint64)
+        self._chk(self.lib.dg_bam_rna_download(self.ctx, words.ctypes.data, len(words)), "dg_bam_rna_download")
+        return rna_views(self.lib, words)
+
+    def bam_rna_text(self, words) -> bytes:
+        """the text of RNA-metrics words (a dict of bam_rna_finish, or the flat array) (dg_bam_rna_format, on the host)"""
+        return rna_text(self.lib, words)
 
     def bam_qc_text(self, words) -> bytes:
         """the text of QC words (a dict of bam_qc_finish, or the flat array) with the index's chromosome names and lengths (dg_bam_qc_format, on the host)"""

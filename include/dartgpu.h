@@ -796,6 +796,71 @@ int dg_gene_device(dg_ctx *, void **counts);
 int dg_gene_device_ms(dg_ctx *, float *ms);
 int dg_gene_granules(int out[2]);
 
+/* ---- RNA-seq metrics of the sorted array, on the device (dart_amd/csrc/dg_rnametrics.h): the share of the aligned bases on coding sequence, UTR, introns,
+ * intergenic sequence and rRNA, the library's strandedness and the gene-body coverage profile: what Picard CollectRnaSeqMetrics (RSeQC read_distribution.py,
+ * infer_experiment.py, geneBody_coverage.py) computes from the finished file.  An opt-in extension, read-only on the sorted array; the reference has no such
+ * output.  THE DEFINITION -- no Picard or RSeQC exists where this project is built and tested, so this text is what the tests pin (tests/rnametrics_inputs.py is
+ * its sequential twin).
+ *   Annotation.  n_tx >= 1 transcripts and their exons, 0-based half-open on the chromosome.  Valid: 0 <= chr < n_chr; strand 0 or 1; no flag bit other than
+ *     DG_RNA_TX_RIBOSOMAL; n_exons >= 1 and the exon range inside the exon array; every exon start < end <= 2^32 - 1; cds_start <= cds_end (equal: no CDS).
+ *     Anything else is DG_ERR_ARG, the text names the first bad transcript.  Exons of a transcript may come in any order, may overlap and may touch: the library
+ *     sorts each transcript's exons and merges those that overlap or touch.  The transcript's span is [first start, last end), its length L the sum of the merged
+ *     exons; it is eligible when L >= 100.  Flattened on the host, once, and uploaded; kept with the index and shared by its clones, independent of the gene-count
+ *     annotation; a second call replaces the tables after waiting for the device.
+ *     class(p) of base p of chromosome c: the maximum over every transcript on c whose span holds p of 4 RIBOSOMAL (p in an exon of a flagged transcript), 3 CODING
+ *     (p in an exon and cds_start <= p < cds_end), 2 UTR (p in an exon otherwise; a transcript without CDS is all UTR, as Picard counts it), 1 INTRONIC (p in the
+ *     span but in no exon of that transcript); 0 INTERGENIC when no span holds p.  strands(p): the OR of 1 << strand over the transcripts whose span holds p.
+ *     The segment table: per chromosome ascending breakpoints, per segment (class, strands), neighbouring segments with equal pairs merged, the segment behind the
+ *     last span (0, 0).  *n_segments: its size; *n_eligible: the number of eligible transcripts (either may be NULL).
+ *   Records.  A record of the sorted array is counted exactly as the coverage track counts it, under exclude_flags and min_mapq (refID, pos, flag 4 clear,
+ *     n_cigar_op > 0, the filter, the CIGAR inside record and array); its blocks are the coverage track's (M, =, X ops with L > 0; D and N move the position).  A
+ *     block end above 2^32 - 1 on a counted record: DG_ERR_RANGE, the text names the record's index, no words are left behind.  s = (flag >> 4 & 1) ^ (flag >> 7 & 1).
+ *   Words, u64 in one flat array (dg_bam_rna_offsets gives the sections' first words):
+ *     BA[5]      every base of every block of every counted record: + 1 at class(p); a block on a chromosome without segments, or outside them, is class 0.
+ *     RC[5]      per counted record + 1 at the highest class any of its blocks touches.
+ *     ST[4]      per counted record, b = the OR of strands over every segment its blocks touch: b == 0 ST[3] (intergenic); b == 3 ST[2] (ambiguous); otherwise
+ *                ST[0] (sense) when s == (b == 2), else ST[1] (antisense).  A second mate already counts for the opposite strand through s.
+ *     BC[3][100] the gene-body profile.  depth(c, g): the number of (counted record, block) pairs on c with start <= g < end; it ignores strand.  For an eligible
+ *                transcript sample b (0 .. 99) sits at transcript offset o_b = floor((2 b + 1) L / 200); offsets run 5' to 3': over the merged exons from the
+ *                left for strand 0, from the right (L - 1 - o_b from the left) for strand 1; mapped through the exons' prefix lengths to a genomic g,
+ *                d_b = depth(chr, g).  S = the sum of d_b; the transcript contributes when S >= max(min_cov, 1): BC[0][b] += d_b, BC[1][b] += (d_b > 0),
+ *                BC[2][b] += floor(d_b * 100000 / S), its profile in per mille of its own mean (Picard's normalization), in integers.
+ *     SN[16]     0 records, 1 counted, 2 blocks, 3 aligned bases (= the sum of BA), 4 transcripts, 5 eligible, 6 contributing, 7 segments, 8 .. 15 zero.
+ *   The words are a function of the record set and the annotation: not of order, grid, batch split, ordinals, contexts or growth history.
+ *   dg_rna_set_annotation  as above; DG_ERR_ARG leaves the tables of an earlier call in place, and so does a failed allocation or copy of the new tables, which
+ *                          gives DG_ERR_HIP with the HIP error's text (as dg_gene_set_annotation does)
+ *   dg_bam_rna_finish      flags: none is defined, any bit is DG_ERR_ARG; no valid sorted array: DG_ERR_ARG, the text names dg_bam_sort_finish; no annotation:
+ *                          DG_ERR_ARG, the text names dg_rna_set_annotation.  Read-only on the array: it may come before, between or after the other stages and
+ *                          disturbs none of them; behind the duplicate marking and the tagging it sees their array.  *n_words: the size of the array
+ *                          (dg_bam_rna_offsets' [5]).  *device_ms (may be NULL): device time of the kernels, a measurement.  Buffers of its own; a failed
+ *                          allocation gives DG_ERR_CAPACITY.  Every failure leaves the context, the store, the array and every finished stage usable.  Repeatable
+ *                          with another filter.  An empty store gives zero BA, RC, ST and BC.  DG_RNA_MAX_GROUPS (read at dg_init) caps the grids: a test
+ *                          hook, the words do not depend on it.  A dg_rna_set_annotation of another thread that replaces the tables while the call is being
+ *                          prepared or between its two passes: DG_ERR_ARG, the text says so, no words are left; call again.
+ *   dg_bam_rna_download    copies the words out; DG_ERR_CAPACITY, nothing written, when cap_words is too small
+ *   dg_bam_rna_device      the words in HBM, valid until the next store or RNA-metrics call on the context
+ *   dg_bam_rna_device_ms   the last finish's device time by part: [0] the class pass, [1] events, sort and depth, [2] the body pass
+ *   dg_bam_rna_granules    [0] records per workgroup trip of the class pass, [1] transcripts per workgroup trip of the body pass
+ *   dg_bam_rna_offsets     the first words of BA, RC, ST, BC, SN, and [5] the number of words
+ *   dg_bam_rna_format      the text of downloaded words, on the host (no context, no device; integers only, products in 128 bits): "SN\tname\tvalue",
+ *                          "BA\tclass\tbases\tppm" (ppm = bases 10^6 / aligned), "RC\tclass\trecords", "ST\tname\trecords", "BC\tbin\tdepth\tcovered\tnormalized".
+ *                          Behind the eight SN words four derived ones, floored, 0 when the denominator is 0: sense_ppm = ST[0] 10^6 / (ST[0] + ST[1]),
+ *                          five_prime_milli = the sum of BC[2][0 .. 9] / (10 contributing), three_prime_milli the same over bins 90 .. 99, five_to_three_milli =
+ *                          1000 x the sum of BC[2][0 .. 9] / the sum of BC[2][90 .. 99].  *n_bytes: the text's size; DG_ERR_CAPACITY, nothing written, when cap is
+ *                          smaller (out may be NULL with cap 0 to ask for the size); n_words != the size or a missing pointer: DG_ERR_ARG                     */
+#define DG_RNA_TX_RIBOSOMAL 1u
+typedef struct { int32_t chr; uint32_t strand /* 0 +, 1 - */, flags /* DG_RNA_TX_RIBOSOMAL */, cds_start, cds_end /* 0-based half-open on the chromosome; equal: no CDS */; uint32_t n_exons; uint64_t first_exon; } dg_rna_tx;      /* 32 bytes */
+typedef struct { uint32_t start, end; } dg_rna_exon;   /* 0-based half-open */
+typedef struct { uint32_t n_tx; uint32_t pad; size_t n_exons; const dg_rna_tx *tx; const dg_rna_exon *exons; } dg_rna_annot;
+int dg_rna_set_annotation(dg_ctx *, const dg_rna_annot *, size_t *n_segments, size_t *n_eligible);
+int dg_bam_rna_finish(dg_ctx *, uint32_t flags, uint32_t exclude_flags, uint32_t min_mapq, uint64_t min_cov, size_t *n_words, float *device_ms);
+int dg_bam_rna_download(dg_ctx *, uint64_t *words, size_t cap_words);
+int dg_bam_rna_device(dg_ctx *, void **words);
+int dg_bam_rna_device_ms(dg_ctx *, float ms[3]);
+int dg_bam_rna_granules(int out[2]);
+int dg_bam_rna_offsets(size_t out[6]);
+int dg_bam_rna_format(const uint64_t *words, size_t n_words, char *out, size_t cap, size_t *n_bytes);
+
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
 int dg_last_timings(dg_ctx *, const char **names, float *ms, int cap);
