@@ -219,3 +219,21 @@ struct GcState {
     hipError_t ready() { return ev.ready(); }
     ~GcState() { if (counts) (void)hipFree(counts); }
 };
+// the class table (dg_txquant.h): resident across batches, CSR, built under annotation generation gen; tab[cur] holds it, a build writes tab[cur ^ 1] and the
+// two change places when it has succeeded.  words: the table's eight words; bw: a batch's, added when its classes are in.  Per batch: the units' sizes and
+// hashes, the workgroups' lines and sums, the pool (one item per counted unit); per build: the sorter's pairs, the heads, sizes and their sums; a
+// downloaded table or host records on their way in; the EM's arrays and the result words of the last dg_tx_finish
+struct TxTab { DBuf<uint64_t> off, cnt; DBuf<uint32_t> ids; size_t n_classes = 0, n_members = 0; };
+struct TxState {
+    TxTab tab[2]; int cur = 0; uint64_t gen = 0; bool made = false, nonempty = false, batch_counted = false, timed = false, fin_valid = false;
+    DBuf<unsigned long long> words, bw, wg, tile_sz, tile_items, in_words, S, S2, res;
+    DBuf<uint32_t> size, pool_ids, head, sz, sz_ex, scan_sums, in_ids, active, eff, conv; DBuf<uint64_t> hash, pool_off, in_off, in_cnt; DBuf<double> theta;
+    DBuf<dg_read_out> in_reads; DBuf<dg_report_out> in_rep; DBuf<uint32_t> in_cig; SortBufs sort;
+    DevStat<unsigned long long, 4> pst;       // [0] the pool's ids, [1] its items (k_tx_top); the EM: [0] M, [1] N, [2] workgroups that saw a transcript move
+    DevStat<uint32_t, 4> bst;                 // a build: [0] classes, [1] members, [2] a hash collision was seen
+    DevStat<unsigned long long, 8> wst;       // the table's words, fetched
+    EvSet<7> ev;                              // [0..1] a compatibility pass, [2..3] a part of a build, [4..5] the EM; [6]: the source stream's place for dg_tx_merge
+    float ms[3] = {0.f, 0.f, 0.f}; size_t n_words = 0; uint32_t n_tx = 0; unsigned long long strand_mode = 0;      // strand_mode: of the last count (a merge into an empty table brings its own)
+    int hash_bits = 64;        // DG_TX_HASH_BITS: test hook, the bits of a list's hash that are kept (forces the collision path); the tables do not depend on it
+    hipError_t ready() { hipError_t e = pst.ready(); if (e == hipSuccess) e = bst.ready(); if (e == hipSuccess) e = wst.ready(); return e != hipSuccess ? e : ev.ready(); }
+};

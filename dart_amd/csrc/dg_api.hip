@@ -25,6 +25,7 @@
 #include "dg_tags.h"
 #include "dg_genecount.h"
 #include "dg_rnametrics.h"
+#include "dg_txquant.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -107,6 +108,9 @@ struct IndexShared {
     // the transcript annotation's tables (dg_rna_set_annotation, dg_rnametrics.h): the segment table, the eligible transcripts and their merged exons; rm_gen: 0 = none
     uint32_t *d_rm_chr_first = nullptr, *d_rm_seg_start = nullptr, *d_rm_seg_cs = nullptr; RmTx *d_rm_tx = nullptr; RmExon *d_rm_ex = nullptr;
     size_t rm_n_seg = 0, rm_n_tx = 0, rm_n_elig = 0; uint64_t rm_gen = 0;
+    // the expression stage's tables (dg_tx_set_annotation, dg_txquant.h): the segment table with its transcript lists, the transcripts and their merged exons; tx_gen: 0 = none
+    uint32_t *d_tx_chr_first = nullptr, *d_tx_seg_start = nullptr, *d_tx_seg_ids = nullptr; uint64_t *d_tx_seg_off = nullptr; TxTx *d_tx_tx = nullptr; TxExon *d_tx_ex = nullptr;
+    size_t tx_n_seg = 0; uint32_t tx_n_tx = 0; uint64_t tx_gen = 0;
 };
 
 struct dg_ctx {
@@ -158,7 +162,7 @@ struct dg_ctx {
     bool batch_done = false;       // the batch on the context has been run and waited for
     bool no_batch = false;         // the last upload was a DG_FQ_CHECK_ONLY: there is nothing to run
     // the library stages' state, one struct each (api_ctx.h); every stage's section of this file drives its own
-    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; TgState tg; GcState gc; RmState rm;
+    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; TgState tg; GcState gc; RmState rm; TxState tx;
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
@@ -197,6 +201,7 @@ static void read_env(dg_ctx *c)
     c->md.hash_bits = geti("DG_MARKDUP_HASH_BITS", MD_HASH_BITS); if (c->md.hash_bits < 1 || c->md.hash_bits > MD_HASH_BITS) c->md.hash_bits = MD_HASH_BITS;
     c->qc.max_groups = geti("DG_QC_MAX_GROUPS", QC_GROUPS); if (c->qc.max_groups < 1 || c->qc.max_groups > QC_GROUPS) c->qc.max_groups = QC_GROUPS;
     c->rm.max_groups = geti("DG_RNA_MAX_GROUPS", RM_GROUPS); if (c->rm.max_groups < 1 || c->rm.max_groups > RM_GROUPS) c->rm.max_groups = RM_GROUPS;
+    c->tx.hash_bits = geti("DG_TX_HASH_BITS", 64); if (c->tx.hash_bits < 1 || c->tx.hash_bits > 64) c->tx.hash_bits = 64;
     c->env_seed_multi = geti("DG_SEED_MULTI", 4); if (c->env_seed_multi < 0 || c->env_seed_multi > SQF_MULTI_MAX) c->env_seed_multi = SQF_MULTI_MAX;   // rows of an interval that are located and compared with the text at once (0: single rows only)
 }
 
@@ -555,6 +560,7 @@ extern "C" void dg_destroy(dg_ctx *c)
         if (sh->d_chr_names) (void)hipFree(sh->d_chr_names);
         for (void *p : {(void *)sh->d_gc_chr_first, (void *)sh->d_gc_seg_start, (void *)sh->d_gc_seg_lab}) if (p) (void)hipFree(p);
         for (void *p : {(void *)sh->d_rm_chr_first, (void *)sh->d_rm_seg_start, (void *)sh->d_rm_seg_cs, (void *)sh->d_rm_tx, (void *)sh->d_rm_ex}) if (p) (void)hipFree(p);
+        for (void *p : {(void *)sh->d_tx_chr_first, (void *)sh->d_tx_seg_start, (void *)sh->d_tx_seg_ids, (void *)sh->d_tx_seg_off, (void *)sh->d_tx_tx, (void *)sh->d_tx_ex}) if (p) (void)hipFree(p);
         delete sh; c->shared_ix = nullptr;
     }
     void *ptrs[] = { c->d_bwt, c->d_sa, c->d_pac, c->d_lockey, c->d_locchr, c->d_chroff };
@@ -986,7 +992,7 @@ static int enqueue_upload(dg_ctx *c, int n_reads, const uint32_t *seq_off, const
         mx = rlen[i] > mx ? rlen[i] : mx;
     }
     if (mx > DG_MAX_RLEN) { snprintf(c->err, 512, "a read is longer than DG_MAX_RLEN (%d)", DG_MAX_RLEN); return DG_ERR_ARG; }
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->tx.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
     c->no_batch = false; c->inf.valid = false;
     HIPCHK(c->seq.ensure(bytes + 64));     /* the kernels read up to 24 bytes at a read position in one go */
     HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
@@ -1049,7 +1055,7 @@ static int enqueue_upload_packed(dg_ctx *c, int n_reads, int rlen_all, const uin
     if (mx > DG_MAX_RLEN || mx > 16 * W2 || (size_t)n_reads * 16 * W2 > 0xFFFFFFF0ull) { snprintf(c->err, 512, "packed batch: read length %d does not fit %d words (or exceeds DG_MAX_RLEN / 2^32 bases)", mx, W2); return DG_ERR_ARG; }
     if (n_reads && (mx + 15) / 16 != W2) { snprintf(c->err, 512, "packed batch: words_per_read must be ceil(longest read / 16) = %d", (mx + 15) / 16); return DG_ERR_ARG; }
     const size_t nw = (size_t)n_reads * W2, bytes = nw * 16;
-    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
+    c->n_reads = n_reads; c->max_rlen = mx; c->seq_bytes = bytes; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->tx.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
     c->no_batch = false; c->inf.valid = false;
     HIPCHK(c->seq.ensure(bytes + 64)); HIPCHK(c->seq_off.ensure((size_t)n_reads + 1)); HIPCHK(c->rlen.ensure((size_t)n_reads + 1));
     HIPCHK(c->enc.ensure(2 * nw + 16)); HIPCHK(c->packed_in.ensure(nw + 1)); HIPCHK(c->nlist_in.ensure(n_n + 1));
@@ -1163,7 +1169,7 @@ static int fq_finish(dg_ctx *c, const char *fn, int max_reads, int *n_reads_out,
 // whatever happens in an upload of FASTQ text, the context holds no batch until the call has succeeded
 static void fq_forget_batch(dg_ctx *c)
 {
-    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
+    c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->tx.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
     c->fq.hdr_bytes = c->fq.qual_bytes = 0; c->fq.ms = 0.f;
     c->no_batch = false; c->inf.valid = false; c->fq.tail_valid = false; c->fq.tail_n[0] = c->fq.tail_n[1] = 0;
 }
@@ -1799,7 +1805,7 @@ extern "C" int dg_batch_run(dg_ctx *c, size_t used[3])
     memset(c->counters, 0, sizeof c->counters);
     if (used) used[0] = used[1] = used[2] = 0;
     c->n_t = 0;
-    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false;
+    c->packed_valid = false; c->full_valid = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->tx.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false;
     if (c->n_reads == 0) { c->batch_done = true; return DG_OK; }
     c->attempt_no = 0;
     int rc = enqueue_run(c);
@@ -1915,7 +1921,7 @@ extern "C" int dg_map_batch_compact(dg_ctx *c, int n_reads, const uint32_t *seq_
 static int ensure_full_records(dg_ctx *c)
 {
     if (c->full_valid || c->n_reads == 0) return DG_OK;
-    const bool keep = c->want_full, counted = c->sj.batch_counted, stored = c->bam.rec_stored, genes = c->gc.batch_counted;
+    const bool keep = c->want_full, counted = c->sj.batch_counted, stored = c->bam.rec_stored, genes = c->gc.batch_counted, txs = c->tx.batch_counted;
     c->want_full = true;
     size_t used[3];
     const int rc = dg_batch_run(c, used);
@@ -1923,6 +1929,7 @@ static int ensure_full_records(dg_ctx *c)
     c->sj.batch_counted = counted;      // (the same batch, mapped again: its tuples are in the junction table already if they were before)
     c->bam.rec_stored = stored;         // (and its BAM records in the sorted store)
     c->gc.batch_counted = genes;        // (and its units in the gene table)
+    c->tx.batch_counted = txs;          // (and in the class table)
     return rc;
 }
 
@@ -3298,6 +3305,448 @@ extern "C" int dg_gene_device_ms(dg_ctx *c, float *ms)
 }
 
 // ------------------------------------------------------------------------------------------
+// transcript-level expression (dg_txquant.h): the annotation's tables live with the index, a class table with every context
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_tx_granules(int out[2])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = TX_THREADS; out[1] = TX_WAVE;
+    return DG_OK;
+}
+extern "C" const char *dg_tx_word_name(int i) { return i >= 0 && i < 16 ? TX_WORD_NAMES[i] : nullptr; }
+
+extern "C" int dg_tx_set_annotation(dg_ctx *c, const dg_rna_annot *a, size_t *n_exons_merged, size_t *n_segments)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_exons_merged) *n_exons_merged = 0;
+    if (n_segments) *n_segments = 0;
+    IndexShared *sh = c->shared_ix;
+    if (!sh || !a) { snprintf(c->err, 512, "dg_tx_set_annotation: no annotation (or a context without an index)"); return DG_ERR_ARG; }
+    TxFlat fl;
+    char why[400];
+    if (!tx_flatten(c->ix.n_chr, a, fl, why, sizeof why)) { snprintf(c->err, 512, "dg_tx_set_annotation: %s", why); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lk(sh->mu);
+    void *d[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const void *src[6] = {fl.chr_first.data(), fl.seg_start.data(), fl.seg_ids.data(), fl.seg_off.data(), fl.tx.data(), fl.ex.data()};
+    const size_t bytes[6] = {fl.chr_first.size() * 4, fl.seg_start.size() * 4, fl.seg_ids.size() * 4, fl.seg_off.size() * 8, fl.tx.size() * sizeof(TxTx), fl.ex.size() * sizeof(TxExon)};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 6 && e == hipSuccess; k++) {
+        e = hipMalloc(&d[k], bytes[k] + 64);
+        if (e == hipSuccess && bytes[k]) e = hipMemcpy(d[k], src[k], bytes[k], hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { for (void *p : d) if (p) (void)hipFree(p); return fail(c, DG_ERR_HIP, "the expression stage's annotation tables", e); }
+    // every call that reads the tables enqueues its kernels under sh->mu and waits for them there: the device is waited for, then the old ones are freed
+    if (sh->tx_gen) { (void)hipDeviceSynchronize(); for (void *p : {(void *)sh->d_tx_chr_first, (void *)sh->d_tx_seg_start, (void *)sh->d_tx_seg_ids, (void *)sh->d_tx_seg_off, (void *)sh->d_tx_tx, (void *)sh->d_tx_ex}) (void)hipFree(p); }
+    sh->d_tx_chr_first = (uint32_t *)d[0]; sh->d_tx_seg_start = (uint32_t *)d[1]; sh->d_tx_seg_ids = (uint32_t *)d[2]; sh->d_tx_seg_off = (uint64_t *)d[3]; sh->d_tx_tx = (TxTx *)d[4]; sh->d_tx_ex = (TxExon *)d[5];
+    sh->tx_n_seg = fl.seg_start.size(); sh->tx_n_tx = a->n_tx; sh->tx_gen++;
+    if (n_exons_merged) *n_exons_merged = fl.ex.size();
+    if (n_segments) *n_segments = fl.seg_start.size();
+    return DG_OK;
+}
+
+// the context's class table for the current annotation: made on first use; an empty one of another generation is replaced, a filled one is the caller's to reset
+static int tx_ready(dg_ctx *c, const char *fn, bool fresh = false)
+{
+    IndexShared *sh = c->shared_ix;
+    uint64_t gen = 0; uint32_t n_tx = 0;
+    if (sh) { std::lock_guard<std::mutex> lk(sh->mu); gen = sh->tx_gen; n_tx = sh->tx_n_tx; }
+    if (!gen) { snprintf(c->err, 512, "%s: no transcript annotation (dg_tx_set_annotation first)", fn); return DG_ERR_ARG; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(c->tx.ready());
+    HIPCHK(c->tx.words.ensure(8)); HIPCHK(c->tx.bw.ensure(8));
+    if (c->tx.made && c->tx.gen == gen && !fresh) return DG_OK;
+    if (c->tx.made && c->tx.gen != gen && c->tx.nonempty && !fresh) {
+        snprintf(c->err, 512, "%s: the table holds classes of annotation generation %llu, the annotation is generation %llu now (dg_tx_reset first)", fn, (unsigned long long)c->tx.gen, (unsigned long long)gen);
+        return DG_ERR_ARG;
+    }
+    HIPCHK(hipMemsetAsync(c->tx.words.p, 0, 64, c->stream));
+    c->tx.tab[c->tx.cur].n_classes = 0; c->tx.tab[c->tx.cur].n_members = 0;
+    c->tx.gen = gen; c->tx.n_tx = n_tx; c->tx.made = true; c->tx.nonempty = false; c->tx.fin_valid = false;
+    return DG_OK;
+}
+
+#define TX_ENSURE(buf, n, what) do { if ((buf).ensure(n) != hipSuccess) { (void)hipGetLastError(); \
+    snprintf(c->err, 512, "%s: not enough device memory: %s need %zu bytes", fn, what, (size_t)(n) * sizeof(*(buf).p)); return DG_ERR_CAPACITY; } } while (0)
+
+// everything a build of n items sorts and scans in
+static int tx_build_bufs(dg_ctx *c, const char *fn, size_t n)
+{
+    TxState &x = c->tx;
+    for (int k = 0; k < 2; k++) { TX_ENSURE(x.sort.k[k], n, "the sorter's keys"); TX_ENSURE(x.sort.v[k], n, "the sorter's values"); }
+    if (x.sort.ensure((uint32_t)n) != hipSuccess) { (void)hipGetLastError(); snprintf(c->err, 512, "%s: not enough device memory: %s need %zu bytes", fn, x.sort.short_of, x.sort.short_bytes); return DG_ERR_CAPACITY; }
+    TX_ENSURE(x.head, n, "the heads"); TX_ENSURE(x.sz, n, "the heads' sizes"); TX_ENSURE(x.sz_ex, n, "the heads' offsets");
+    TX_ENSURE(x.scan_sums, (n + SCAN_TILE - 1) / SCAN_TILE + 1, "the scan's sums");
+    return DG_OK;
+}
+
+// The class building: the table's classes and the items b (a batch's pool, another table, a downloaded table) sorted by their lists' hashes, equal lists
+// made one class, into the context's other table; on success the two change places.  b_members: the ids b holds; b_keys_ready: the sorter's first key
+// buffer holds b's keys already, behind the table's.  The call waits for the stream.
+static int tx_build(dg_ctx *c, const char *fn, TxItems b, uint64_t b_members, bool b_keys_ready)
+{
+    TxState &x = c->tx;
+    TxTab &A = x.tab[x.cur], &O = x.tab[x.cur ^ 1];
+    if (!b.n) return DG_OK;
+    const TxTwo s{TxItems{A.off.p, A.ids.p, A.cnt.p, (uint64_t)A.n_classes}, b};
+    const uint64_t n = (uint64_t)A.n_classes + b.n, members_in = (uint64_t)A.n_members + b_members;
+    if (n >= 0xFFFFFFF0ull || members_in >= 0xFFFFFFF0ull) { snprintf(c->err, 512, "%s: %llu items with %llu ids are more than one class table takes", fn, (unsigned long long)n, (unsigned long long)members_in); return DG_ERR_RANGE; }
+    { const int rc = tx_build_bufs(c, fn, (size_t)n); if (rc) return rc; }
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    HIPCHK(hipEventRecord(x.ev[2], c->stream));
+    k_tx_hash<<<grid, 256, 0, c->stream>>>(s, n, b_keys_ready ? (unsigned long long)A.n_classes : n, tx_hash_mask(x.hash_bits), x.sort.k[0].p, x.sort.v[0].p);
+    int which = 0;
+    { const int rc = x.sort.sort(c, (uint32_t)n, (x.hash_bits + 3) / 4 * 4, which); if (rc) return rc; }
+    HIPCHK(hipMemsetAsync(x.bst.d, 0, 4 * sizeof(uint32_t), c->stream));
+    k_tx_heads<<<grid, 256, 0, c->stream>>>(s, n, x.sort.k[which].p, x.sort.v[which].p, x.head.p, x.sz.p, x.bst.d);
+    rs_scan_u32(c->stream, x.head.p, x.head.p, (uint32_t)n, x.scan_sums.p, x.bst.d);
+    rs_scan_u32(c->stream, x.sz.p, x.sz_ex.p, (uint32_t)n, x.scan_sums.p, x.bst.d + 1);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(x.ev[3], c->stream));
+    HIPCHK(x.bst.fetch(c->stream));
+    HIPCHK(wait_stream(c));
+    x.ms[1] += x.ev.ms(2, 3);
+    if (x.bst.h[2]) {
+        // two lists under one hash: their items may interleave in the sorted order, so runs are not classes.  This build is finished on the host, exactly.
+        std::vector<uint64_t> off[2], cnt[2]; std::vector<uint32_t> ids[2];
+        const TxItems *src[2] = {&s.a, &s.b};
+        TxTwo hs;
+        TxItems *dst[2] = {&hs.a, &hs.b};
+        for (int k = 0; k < 2; k++) {
+            const TxItems &q = *src[k];
+            off[k].assign((size_t)q.n + 1, 0ull);
+            if (q.n) HIPCHK(hipMemcpy(off[k].data(), q.off, ((size_t)q.n + 1) * 8, hipMemcpyDeviceToHost));
+            const uint64_t base = off[k][0], m = off[k][(size_t)q.n] - base;
+            for (uint64_t &o : off[k]) o -= base;
+            ids[k].resize((size_t)m);
+            if (m) HIPCHK(hipMemcpy(ids[k].data(), q.ids + base, (size_t)m * 4, hipMemcpyDeviceToHost));
+            if (q.cnt && q.n) { cnt[k].resize((size_t)q.n); HIPCHK(hipMemcpy(cnt[k].data(), q.cnt, (size_t)q.n * 8, hipMemcpyDeviceToHost)); }
+            *dst[k] = TxItems{off[k].data(), ids[k].data(), q.cnt && q.n ? cnt[k].data() : nullptr, q.n};
+        }
+        TxHostTab t;
+        tx_build_host(hs, t);
+        TX_ENSURE(O.off, t.off.size(), "the class table's offsets"); TX_ENSURE(O.ids, t.ids.size(), "the class table's ids"); TX_ENSURE(O.cnt, t.cnt.size(), "the class table's counts");
+        HIPCHK(hipMemcpy(O.off.p, t.off.data(), t.off.size() * 8, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(O.ids.p, t.ids.data(), t.ids.size() * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(O.cnt.p, t.cnt.data(), t.cnt.size() * 8, hipMemcpyHostToDevice));
+        O.n_classes = t.cnt.size(); O.n_members = t.ids.size();
+    } else {
+        const size_t nc = x.bst.h[0], nm = x.bst.h[1];
+        TX_ENSURE(O.off, nc + 1, "the class table's offsets"); TX_ENSURE(O.ids, nm, "the class table's ids"); TX_ENSURE(O.cnt, nc, "the class table's counts");
+        HIPCHK(hipMemsetAsync(O.cnt.p, 0, nc * 8, c->stream));
+        HIPCHK(hipEventRecord(x.ev[2], c->stream));
+        k_tx_csr<<<grid, 256, 0, c->stream>>>(s, n, x.sort.v[which].p, x.sz.p, x.head.p, x.sz_ex.p, (unsigned long long)nc, (unsigned long long)nm, O.off.p, O.ids.p, (unsigned long long *)O.cnt.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(x.ev[3], c->stream));
+        HIPCHK(wait_stream(c));
+        x.ms[1] += x.ev.ms(2, 3);
+        O.n_classes = nc; O.n_members = nm;
+    }
+    x.cur ^= 1;
+    return DG_OK;
+}
+
+// the compatibility passes over the records b holds in HBM and the build that folds the batch's classes in
+static int tx_count_device(dg_ctx *c, GcBatch b, uint32_t strand_mode, const char *fn)
+{
+    IndexShared *sh = c->shared_ix;
+    TxState &x = c->tx;
+    const unsigned long long n_units = gc_units(b.n_reads, b.n_pair_mode);
+    const unsigned long long n_wg = (n_units + TX_THREADS - 1) / TX_THREADS;
+    if (!n_units) return DG_OK;
+    if (n_wg > 0x7FFFFFFFull) { snprintf(c->err, 512, "%s: %llu units are more than one call takes", fn, n_units); return DG_ERR_ARG; }
+    TX_ENSURE(x.size, (size_t)n_units, "the units' sizes"); TX_ENSURE(x.hash, (size_t)n_units, "the units' hashes");
+    TX_ENSURE(x.wg, (size_t)n_wg * 8, "the workgroups' lines"); TX_ENSURE(x.tile_sz, (size_t)n_wg, "the workgroups' sums"); TX_ENSURE(x.tile_items, (size_t)n_wg, "the workgroups' sums");
+    const uint64_t mask = tx_hash_mask(x.hash_bits);
+    x.ms[0] = x.ms[1] = 0.f;
+    {   // the tables are read and the kernels that use them enqueued under the index's lock: dg_tx_set_annotation replaces them under the same lock and waits
+        // for the device before it frees the old ones.  The lock is not held across the waits below, so the clones of an index count side by side
+        std::lock_guard<std::mutex> lk(sh->mu);
+        if (sh->tx_gen != x.gen) { snprintf(c->err, 512, "%s: the annotation was replaced while the call was being prepared", fn); return DG_ERR_ARG; }
+        const TxTable T{sh->d_tx_chr_first, sh->d_tx_seg_start, sh->d_tx_seg_off, sh->d_tx_seg_ids, sh->d_tx_tx, sh->d_tx_ex, c->ix.n_chr, sh->tx_n_tx};
+        HIPCHK(hipEventRecord(x.ev[0], c->stream));
+        k_tx_count<<<(unsigned)n_wg, TX_THREADS, 0, c->stream>>>(b, T, n_units, strand_mode, mask, x.size.p, x.hash.p, x.wg.p, x.tile_sz.p, x.tile_items.p);
+        k_tx_top<<<1, WG_THREADS, 0, c->stream>>>(x.wg.p, (uint32_t)n_wg, x.bw.p, x.tile_sz.p, x.tile_items.p, x.pst.d);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(x.ev[1], c->stream));
+    }
+    HIPCHK(x.pst.fetch(c->stream));
+    HIPCHK(wait_stream(c));
+    x.ms[0] += x.ev.ms(0, 1);
+    const unsigned long long n_ids = x.pst.h[0], n_items = x.pst.h[1];
+    if (n_items) {
+        const size_t n_tab = x.tab[x.cur].n_classes;
+        if (n_tab + n_items >= 0xFFFFFFF0ull || n_ids >= 0xFFFFFFF0ull) { snprintf(c->err, 512, "%s: %llu items with %llu ids are more than one class table takes", fn, n_tab + n_items, n_ids); return DG_ERR_RANGE; }
+        { const int rc = tx_build_bufs(c, fn, n_tab + (size_t)n_items); if (rc) return rc; }
+        TX_ENSURE(x.pool_off, (size_t)n_items + 1, "the pool's offsets"); TX_ENSURE(x.pool_ids, (size_t)n_ids, "the pool's ids");
+        {
+            std::lock_guard<std::mutex> lk(sh->mu);
+            if (sh->tx_gen != x.gen) { snprintf(c->err, 512, "%s: the annotation was replaced while the call was running", fn); return DG_ERR_ARG; }
+            const TxTable T{sh->d_tx_chr_first, sh->d_tx_seg_start, sh->d_tx_seg_off, sh->d_tx_seg_ids, sh->d_tx_tx, sh->d_tx_ex, c->ix.n_chr, sh->tx_n_tx};
+            HIPCHK(hipEventRecord(x.ev[0], c->stream));
+            k_tx_write<<<(unsigned)n_wg, TX_THREADS, 0, c->stream>>>(b, T, n_units, strand_mode, x.size.p, x.hash.p, x.tile_sz.p, x.tile_items.p, n_items, n_ids, x.pool_off.p, x.pool_ids.p, x.sort.k[0].p + n_tab);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(x.ev[1], c->stream));
+        }
+        HIPCHK(wait_stream(c));
+        x.ms[0] += x.ev.ms(0, 1);
+        const int rc = tx_build(c, fn, TxItems{x.pool_off.p, x.pool_ids.p, nullptr, n_items}, n_ids, true);
+        if (rc) return rc;
+    }
+    k_gc_add<<<1, 256, 0, c->stream>>>(x.words.p, x.bw.p, 8ull);
+    HIPCHK(hipGetLastError());
+    HIPCHK(wait_stream(c));
+    x.timed = true; x.nonempty = true; x.fin_valid = false; x.strand_mode = strand_mode;
+    return DG_OK;
+}
+
+extern "C" int dg_batch_accumulate_tx(dg_ctx *c, int n_pair_mode, uint32_t min_mapq, uint32_t strand_mode, size_t *n_units)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_batch_accumulate_tx";
+    if (n_units) *n_units = 0;
+    { IndexShared *sh = c->shared_ix; uint64_t gen = 0; if (sh) { std::lock_guard<std::mutex> lk(sh->mu); gen = sh->tx_gen; }
+      if (!gen) { snprintf(c->err, 512, "%s: no transcript annotation (dg_tx_set_annotation first)", fn); return DG_ERR_ARG; } }
+    if (!c->batch_done) { snprintf(c->err, 512, "%s: the context has no finished batch (upload and run one first)", fn); return DG_ERR_ARG; }
+    { const int rc = gc_pair_mode_ok(c, fn, n_pair_mode, c->n_reads); if (rc) return rc; }
+    if (strand_mode > 2u) { snprintf(c->err, 512, "%s: strand_mode %u is none of 0, 1, 2", fn, strand_mode); return DG_ERR_ARG; }
+    if (c->n_reads && !c->full_valid) { snprintf(c->err, 512, "%s: the last batch has no full records (it was mapped through dg_map_batch_compact)", fn); return DG_ERR_ARG; }
+    if (c->tx.batch_counted) { snprintf(c->err, 512, "%s: the units of this batch are in the table already (a batch is counted once)", fn); return DG_ERR_ARG; }
+    { const int rc = tx_ready(c, fn); if (rc) return rc; }
+    if (c->n_reads) {
+        const GcBatch b{c->reads_out.p, c->reports.p, c->cigfinal.p, (unsigned long long)c->used[0], (unsigned long long)c->used[1], c->n_reads, n_pair_mode, min_mapq};
+        const int rc = tx_count_device(c, b, strand_mode, fn);
+        if (rc) return rc;
+    }
+    c->tx.batch_counted = true;
+    if (n_units) *n_units = (size_t)gc_units(c->n_reads, n_pair_mode);
+    return DG_OK;
+}
+
+extern "C" int dg_tx_count_records(dg_ctx *c, int n_reads, int n_pair_mode, uint32_t min_mapq, uint32_t strand_mode, const dg_read_out *reads, const dg_report_out *reports, size_t n_reports,
+                                   const uint32_t *cigar, size_t n_ops, size_t *n_units)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_tx_count_records";
+    if (n_units) *n_units = 0;
+    if (n_reads < 0 || (n_reads && !reads) || (n_reports && !reports) || (n_ops && !cigar)) { snprintf(c->err, 512, "%s: %d reads, %zu reports and %zu CIGAR ops need their arrays", fn, n_reads, n_reports, n_ops); return DG_ERR_ARG; }
+    { const int rc = gc_pair_mode_ok(c, fn, n_pair_mode, n_reads); if (rc) return rc; }
+    if (strand_mode > 2u) { snprintf(c->err, 512, "%s: strand_mode %u is none of 0, 1, 2", fn, strand_mode); return DG_ERR_ARG; }
+    const long long bad = gc_first_bad_read(reads, n_reads, reports, n_reports, n_ops);
+    if (bad >= 0) { snprintf(c->err, 512, "%s: read %lld points outside the arrays (%zu reports, %zu CIGAR ops), or its best report is none of its own", fn, bad, n_reports, n_ops); return DG_ERR_ARG; }
+    { const int rc = tx_ready(c, fn); if (rc) return rc; }
+    if (!n_reads) return DG_OK;
+    HIPCHK(c->tx.in_reads.ensure((size_t)n_reads)); HIPCHK(c->tx.in_rep.ensure(n_reports + 1)); HIPCHK(c->tx.in_cig.ensure(n_ops + 1));
+    HIPCHK(hipMemcpyAsync(c->tx.in_reads.p, reads, (size_t)n_reads * sizeof(dg_read_out), hipMemcpyHostToDevice, c->stream));
+    if (n_reports) HIPCHK(hipMemcpyAsync(c->tx.in_rep.p, reports, n_reports * sizeof(dg_report_out), hipMemcpyHostToDevice, c->stream));
+    if (n_ops) HIPCHK(hipMemcpyAsync(c->tx.in_cig.p, cigar, n_ops * 4, hipMemcpyHostToDevice, c->stream));
+    const GcBatch b{c->tx.in_reads.p, c->tx.in_rep.p, c->tx.in_cig.p, (unsigned long long)n_reports, (unsigned long long)n_ops, n_reads, n_pair_mode, min_mapq};
+    { const int rc = tx_count_device(c, b, strand_mode, fn); if (rc) return rc; }
+    if (n_units) *n_units = (size_t)gc_units(n_reads, n_pair_mode);
+    return DG_OK;
+}
+
+extern "C" int dg_tx_add(dg_ctx *c, const uint64_t *off, const uint32_t *ids, const uint64_t *count, size_t n_classes, const uint64_t *words8)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_tx_add";
+    { const int rc = tx_ready(c, fn); if (rc) return rc; }
+    TxState &x = c->tx;
+    if (!words8) { snprintf(c->err, 512, "%s: the table's eight words are missing", fn); return DG_ERR_ARG; }
+    size_t where = 0;
+    const char *what = tx_bad_table(off, ids, count, n_classes, x.n_tx, where);
+    if (what) { snprintf(c->err, 512, "%s: class %zu: %s (%u transcripts)", fn, where, what, x.n_tx); return DG_ERR_ARG; }
+    const size_t n_members = n_classes ? (size_t)off[n_classes] : 0;
+    TX_ENSURE(x.in_words, 8, "the words");
+    if (n_classes) {
+        TX_ENSURE(x.in_off, n_classes + 1, "the added table's offsets"); TX_ENSURE(x.in_ids, n_members, "the added table's ids"); TX_ENSURE(x.in_cnt, n_classes, "the added table's counts");
+        HIPCHK(hipMemcpyAsync(x.in_off.p, off, (n_classes + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(x.in_ids.p, ids, n_members * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(x.in_cnt.p, count, n_classes * 8, hipMemcpyHostToDevice, c->stream));
+        x.ms[1] = 0.f;
+        const int rc = tx_build(c, fn, TxItems{x.in_off.p, x.in_ids.p, x.in_cnt.p, (uint64_t)n_classes}, n_members, false);
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(x.in_words.p, words8, 64, hipMemcpyHostToDevice, c->stream));
+    k_gc_add<<<1, 256, 0, c->stream>>>(x.words.p, x.in_words.p, 8ull);
+    HIPCHK(hipGetLastError());
+    HIPCHK(wait_stream(c));
+    x.nonempty = true; x.fin_valid = false;
+    return DG_OK;
+}
+
+extern "C" int dg_tx_merge(dg_ctx *dst, dg_ctx *src)
+{
+    dg_ctx *c = dst;
+    if (!dst || !src) return DG_ERR_ARG;
+    const char *fn = "dg_tx_merge";
+    if (dst == src || dst->device != src->device) { snprintf(c->err, 512, "%s: the two contexts must differ and be on one device", fn); return DG_ERR_ARG; }
+    if (!src->tx.made || !src->tx.nonempty) return DG_OK;
+    { const int rc = tx_ready(dst, fn); if (rc) return rc; }
+    if (dst->tx.gen != src->tx.gen) {
+        snprintf(c->err, 512, "%s: the tables were built under different annotation generations (%llu and %llu)", fn, (unsigned long long)dst->tx.gen, (unsigned long long)src->tx.gen);
+        return DG_ERR_ARG;
+    }
+    // behind everything the source's stream holds; the source's table is emptied on the destination's stream, which the call waits for
+    HIPCHK(hipEventRecord(src->tx.ev[6], src->stream));
+    HIPCHK(hipStreamWaitEvent(dst->stream, src->tx.ev[6], 0));
+    const TxTab &S = src->tx.tab[src->tx.cur];
+    dst->tx.ms[1] = 0.f;
+    { const int rc = tx_build(dst, fn, TxItems{S.off.p, S.ids.p, S.cnt.p, (uint64_t)S.n_classes}, S.n_members, false); if (rc) return rc; }
+    k_gc_add<<<1, 256, 0, dst->stream>>>(dst->tx.words.p, src->tx.words.p, 8ull);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemsetAsync(src->tx.words.p, 0, 64, dst->stream));
+    HIPCHK(wait_stream(dst));
+    src->tx.tab[src->tx.cur].n_classes = 0; src->tx.tab[src->tx.cur].n_members = 0;
+    if (!dst->tx.nonempty) dst->tx.strand_mode = src->tx.strand_mode;
+    dst->tx.nonempty = true; dst->tx.fin_valid = false; src->tx.nonempty = false; src->tx.fin_valid = false;
+    return DG_OK;
+}
+
+extern "C" int dg_tx_reset(dg_ctx *c)
+{
+    if (!c) return DG_ERR_ARG;
+    { const int rc = tx_ready(c, "dg_tx_reset", true); if (rc) return rc; }
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_tx_classes_size(dg_ctx *c, size_t *n_classes, size_t *n_members)
+{
+    if (!c) return DG_ERR_ARG;
+    if (n_classes) *n_classes = 0;
+    if (n_members) *n_members = 0;
+    if (!c->tx.made) { const int rc = tx_ready(c, "dg_tx_classes_size"); if (rc) return rc; }
+    if (n_classes) *n_classes = c->tx.tab[c->tx.cur].n_classes;
+    if (n_members) *n_members = c->tx.tab[c->tx.cur].n_members;
+    return DG_OK;
+}
+
+extern "C" int dg_tx_classes_download(dg_ctx *c, uint64_t *off, uint32_t *ids, uint64_t *count, size_t cap_classes, size_t cap_members, uint64_t *words8)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_tx_classes_download";
+    if (!c->tx.made) { const int rc = tx_ready(c, fn); if (rc) return rc; }
+    const TxTab &A = c->tx.tab[c->tx.cur];
+    if (!off || !words8 || cap_classes < A.n_classes || cap_members < A.n_members || (A.n_classes && (!ids || !count))) {
+        snprintf(c->err, 512, "%s: output capacity too small: %zu classes and %zu ids are needed", fn, A.n_classes, A.n_members); return DG_ERR_CAPACITY;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    off[0] = 0;
+    if (A.n_classes) {
+        HIPCHK(hipMemcpyAsync(off, A.off.p, (A.n_classes + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(ids, A.ids.p, A.n_members * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(count, A.cnt.p, A.n_classes * 8, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(hipMemcpyAsync(words8, c->tx.words.p, 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_tx_finish(dg_ctx *c, uint32_t flags, uint64_t frag_mean, uint32_t max_rounds, size_t *n_words, float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_tx_finish";
+    if (n_words) *n_words = 0;
+    if (device_ms) *device_ms = 0.f;
+    if (flags) { snprintf(c->err, 512, "%s: flags 0x%x: no flag is defined", fn, flags); return DG_ERR_ARG; }
+    { const int rc = tx_ready(c, fn); if (rc) return rc; }
+    TxState &x = c->tx;
+    IndexShared *sh = c->shared_ix;
+    const TxTab &A = x.tab[x.cur];
+    const uint32_t n_tx = x.n_tx, n_wg = (n_tx + 255u) / 256u;
+    const unsigned long long nc = A.n_classes, nm = A.n_members;
+    x.fin_valid = false;
+    TX_ENSURE(x.S, n_tx, "S"); TX_ENSURE(x.S2, n_tx, "S'"); TX_ENSURE(x.theta, n_tx, "theta"); TX_ENSURE(x.active, n_tx, "the active marks"); TX_ENSURE(x.eff, n_tx, "the effective lengths");
+    TX_ENSURE(x.conv, n_wg, "the convergence words"); TX_ENSURE(x.res, (size_t)n_tx + 16, "the result words");
+    HIPCHK(hipEventRecord(x.ev[4], c->stream));
+    HIPCHK(hipMemsetAsync(x.active.p, 0, (size_t)n_tx * 4, c->stream));
+    if (nm) k_tx_active<<<(unsigned)((nm + 255) / 256), 256, 0, c->stream>>>(A.ids.p, nm, n_tx, x.active.p);
+    k_tx_em_prep<<<1, WG_THREADS, 0, c->stream>>>(x.active.p, n_tx, (const unsigned long long *)A.cnt.p, nc, x.pst.d);
+    HIPCHK(hipGetLastError());
+    HIPCHK(x.pst.fetch(c->stream));
+    HIPCHK(hipMemcpyAsync(x.wst.h, x.words.p, 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    const unsigned long long M = x.pst.h[0], N = x.pst.h[1];
+    if (N >= TX_MAX_N) { snprintf(c->err, 512, "%s: the counts sum to %llu, the EM takes less than 2^33", fn, N); return DG_ERR_RANGE; }
+    const unsigned long long *w = x.wst.h;
+    const unsigned long long mean = w[TXW_FL_N] ? w[TXW_FL_SUM] / w[TXW_FL_N] : (unsigned long long)frag_mean;
+    {   // the transcripts' lengths are read under the index's lock (dg_tx_set_annotation waits for the device before it frees them)
+        std::lock_guard<std::mutex> lk(sh->mu);
+        if (sh->tx_gen != x.gen) { snprintf(c->err, 512, "%s: the annotation was replaced while the call was being prepared", fn); return DG_ERR_ARG; }
+        k_tx_start<<<n_wg, 256, 0, c->stream>>>(sh->d_tx_tx, n_tx, x.active.p, M ? N * TX_F / M : 0ull, mean, x.S.p, x.S2.p, x.eff.p, x.theta.p);
+        HIPCHK(hipGetLastError());
+    }
+    unsigned long long rounds = 0, converged = M ? 0ull : 1ull;
+    while (M && rounds < max_rounds) {
+        if (nc) k_tx_em<<<(unsigned)((nc + 255) / 256), 256, 0, c->stream>>>(A.off.p, A.ids.p, (const unsigned long long *)A.cnt.p, nc, x.theta.p, x.S2.p);
+        k_tx_theta<<<n_wg, 256, 0, c->stream>>>(n_tx, x.eff.p, x.S.p, x.S2.p, x.theta.p, x.conv.p);
+        rounds++;
+        if (rounds == max_rounds || rounds % TX_CHECK_EVERY == 0) {       // (the rounds between two looks are enqueued without a wait)
+            k_tx_conv<<<1, WG_THREADS, 0, c->stream>>>(x.conv.p, n_wg, x.pst.d);
+            HIPCHK(hipGetLastError());
+            HIPCHK(x.pst.fetch(c->stream));
+            HIPCHK(wait_stream(c));
+            converged = x.pst.h[2] ? 0ull : 1ull;
+            if (converged && rounds % TX_CHECK_EVERY == 0) break;
+        }
+    }
+    const unsigned long long tail[16] = {w[0], w[1], w[2], w[3], w[4], nc, nm, M, rounds, converged, w[TXW_FL_SUM], w[TXW_FL_N], mean, x.strand_mode, 0ull, 0ull};
+    HIPCHK(hipMemcpyAsync(x.res.p, x.S.p, (size_t)n_tx * 8, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(x.res.p + n_tx, tail, sizeof tail, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(x.ev[5], c->stream));
+    HIPCHK(wait_stream(c));
+    x.ms[2] = x.ev.ms(4, 5);
+    x.n_words = (size_t)n_tx + 16; x.fin_valid = true;
+    if (n_words) *n_words = x.n_words;
+    if (device_ms) *device_ms = x.ms[2];
+    return DG_OK;
+}
+
+extern "C" int dg_tx_download(dg_ctx *c, uint64_t *words, size_t cap_words)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_tx_download";
+    if (!c->tx.fin_valid) { snprintf(c->err, 512, "%s: no result (dg_tx_finish first, and no table call behind it)", fn); return DG_ERR_ARG; }
+    if (!words || cap_words < c->tx.n_words) { snprintf(c->err, 512, "%s: output capacity too small: %zu words are needed", fn, c->tx.n_words); return DG_ERR_CAPACITY; }
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(words, c->tx.res.p, c->tx.n_words * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(wait_stream(c));
+    return DG_OK;
+}
+
+extern "C" int dg_tx_device(dg_ctx *c, void **words, size_t *n_words)
+{
+    if (!c || !words || !n_words) return DG_ERR_ARG;
+    if (!c->tx.fin_valid) { snprintf(c->err, 512, "dg_tx_device: no result (dg_tx_finish first, and no table call behind it)"); return DG_ERR_ARG; }
+    *words = c->tx.res.p; *n_words = c->tx.n_words;
+    return DG_OK;
+}
+
+extern "C" int dg_tx_device_ms(dg_ctx *c, float ms[3])
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    for (int k = 0; k < 3; k++) ms[k] = c->tx.ms[k];
+    return DG_OK;
+}
+
+extern "C" int dg_tx_format(const uint64_t *words, size_t n_words, const dg_rna_annot *a, const char *const *names, char *out, size_t cap, size_t *n_bytes)
+{
+    if (n_bytes) *n_bytes = 0;
+    if (!words || !a || !a->tx || !names || n_words != (size_t)a->n_tx + 16 || (!out && cap)) return DG_ERR_ARG;
+    char why[400];
+    if (!rm_validate(1 << 30, a, why, sizeof why)) return DG_ERR_ARG;
+    std::vector<uint32_t> len(a->n_tx);
+    std::vector<dg_rna_exon> m;
+    for (uint32_t t = 0; t < a->n_tx; t++) { tx_merge_exons(a, a->tx[t], m); uint32_t L = 0; for (const dg_rna_exon &e : m) L += e.end - e.start; len[t] = L; }
+    const std::string text = tx_format(words, a->n_tx, len.data(), names);
+    if (n_bytes) *n_bytes = text.size();
+    if (cap < text.size()) return DG_ERR_CAPACITY;
+    if (!text.empty()) memcpy(out, text.data(), text.size());
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
 // the coverage track of the sorted array (dg_coverage.h): built in HBM from the sorted records and their places, in buffers of its own
 // ------------------------------------------------------------------------------------------
 extern "C" int dg_bam_coverage_granules(int out[2])
@@ -4247,6 +4696,32 @@ extern "C" int dg_sort_pairs(int device, uint64_t *keys, int64_t *vals, uint64_t
 }
 
 // ---- stage probes ----
+extern "C" int dg_probe_sort_passes(int device, uint64_t *keys, int64_t *vals, uint64_t *keys_tmp, int64_t *vals_tmp, size_t n, int key_bits, float *ms, int *in_tmp)
+{
+    dg_ctx *c = nullptr;                                   // (HIPCHK reports through the init error string)
+    if (!keys || !vals || !keys_tmp || !vals_tmp || !ms || key_bits < 1 || key_bits > 64 || n < 2 || n >= 0xFFFFF000ull) return DG_ERR_ARG;
+    HIPCHK(hipSetDevice(device));
+    uint32_t *hist = nullptr, *sums = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t e = hipMalloc((void **)&hist, rs_hist_words((uint32_t)n) * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&sums, rs_sums_words((uint32_t)n) * 4);
+    if (e == hipSuccess) e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    uint64_t *const k2[2] = {keys, keys_tmp}; int64_t *const v2[2] = {vals, vals_tmp};
+    int which = 0;
+    if (e == hipSuccess) e = hipEventRecord(e0, 0);
+    if (e == hipSuccess) e = rs_sort_passes(0, k2, v2, hist, sums, (uint32_t)n, key_bits, which);
+    if (e == hipSuccess) e = hipEventRecord(e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(ms, e0, e1);
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipFree(hist); (void)hipFree(sums);
+    if (in_tmp) *in_tmp = which;
+    if (e != hipSuccess) return fail(nullptr, DG_ERR_HIP, "dg_probe_sort_passes", e);
+    return DG_OK;
+}
+
 extern "C" int dg_probe_seeds(dg_ctx *c, int n_reads, const uint32_t *seq_off, const uint16_t *rlen, const char *seq,
                               uint32_t *seed_off, int32_t *rpos, int32_t *slen, int64_t *gpos, size_t cap, size_t *used)
 {

@@ -169,10 +169,9 @@ RM_HD uint64_t rm_norm(uint32_t d, uint64_t S) { return (uint64_t)d * 100000ull 
 struct RmFlat {
     std::vector<uint32_t> chr_first, seg_start, seg_cs; std::vector<RmTx> tx; std::vector<RmExon> ex;      // tx: the eligible ones
 };
-// false with a text that names the first bad transcript
-static inline bool rm_flatten(int n_chr, const dg_rna_annot *a, RmFlat &o, char *err, size_t err_len)
+// the annotation's validity rules (dg_rna_set_annotation's and dg_tx_set_annotation's): false with a text that names the first bad transcript
+static inline bool rm_validate(int n_chr, const dg_rna_annot *a, char *err, size_t err_len)
 {
-    o.chr_first.assign((size_t)(n_chr > 0 ? n_chr : 0) + 1, 0u); o.seg_start.clear(); o.seg_cs.clear(); o.tx.clear(); o.ex.clear();
     if (n_chr < 1 || !a || a->n_tx < 1u || !a->tx || (a->n_exons && !a->exons)) { snprintf(err, err_len, "the annotation needs at least one chromosome and one transcript (%d chromosomes, %u transcripts)", n_chr, a ? a->n_tx : 0u); return false; }
     for (uint32_t i = 0; i < a->n_tx; i++) {
         const dg_rna_tx &t = a->tx[i];
@@ -184,6 +183,13 @@ static inline bool rm_flatten(int n_chr, const dg_rna_annot *a, RmFlat &o, char 
             for (uint32_t k = 0; k < t.n_exons && !what; k++) if (!(a->exons[t.first_exon + k].start < a->exons[t.first_exon + k].end)) what = "an exon's start < end does not hold";
         if (what) { snprintf(err, err_len, "transcript %u (chr %d, strand %u, flags 0x%x, CDS [%u, %u), %u exons from %llu): %s", i, t.chr, t.strand, t.flags, t.cds_start, t.cds_end, t.n_exons, (unsigned long long)t.first_exon, what); return false; }
     }
+    return true;
+}
+// false with a text that names the first bad transcript
+static inline bool rm_flatten(int n_chr, const dg_rna_annot *a, RmFlat &o, char *err, size_t err_len)
+{
+    o.chr_first.assign((size_t)(n_chr > 0 ? n_chr : 0) + 1, 0u); o.seg_start.clear(); o.seg_cs.clear(); o.tx.clear(); o.ex.clear();
+    if (!rm_validate(n_chr, a, err, err_len)) return false;
     // events (chromosome, position): which 0 the span (class 1 and the strand), 2 .. 4 an exon piece of that class
     struct Ev { uint64_t key; int32_t which, delta; uint32_t strand; };
     std::vector<Ev> ev;

@@ -7,6 +7,7 @@
 #include <zlib.h>
 #include <sys/stat.h>
 #include <algorithm>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -56,6 +57,11 @@ struct Config {
     const char *gene_gtf = nullptr;         // DART_GENE_COUNTS (empty = unset)
     const char *gene_feature = "exon";      // DART_GENE_FEATURE (empty = unset)
     uint32_t gene_min_mapq = 4u;            // DART_GENE_MIN_MAPQ
+    const char *tx_gtf = nullptr;           // DART_TX_QUANT (empty = unset)
+    uint32_t tx_strand = 0u, tx_max_rounds = 1000u;                    // DART_TX_STRAND (0, 1, 2), DART_TX_MAX_ROUNDS
+    uint64_t tx_frag_mean = 200u;           // DART_TX_FRAG_MEAN
+    static constexpr uint32_t tx_min_mapq = 4u;                        // the units that count as unique: the -unique rule, mapq > 3 (no switch)
+    std::string tx_path;                    // <out>.transcripts.tab; empty = not asked for
     int write_threads = 1;                  // DART_WRITE_THREADS, at least 1
     int fmt_threads = 0;                    // DART_FMT_THREADS, at least 1; 0 = unset (what -t leaves)
     bool write_mmap = false;                // DART_WRITE=mmap
@@ -302,6 +308,28 @@ struct Config {
         if (gene_gtf) genes_path = std::string(out) + ".genes.tab";
         { const char *v = lookup("DART_GENE_FEATURE"); if (v && v[0]) gene_feature = v; }
         if (const char *v = lookup("DART_GENE_MIN_MAPQ")) gene_min_mapq = (uint32_t)strtoul(v, nullptr, 0);
+        // DART_TX_QUANT=<annotation.gtf>: abundance per transcript: every batch's units are folded into equivalence classes on the device (dg_batch_accumulate_tx)
+        // where the gene counts count, an EM over the merged classes runs there at the end of the job (dg_tx_finish), and <out>.transcripts.tab is written after the
+        // alignments are complete.  Both pipelines, -o and -bo, beside every other switch; it does not need the sort.  DART_TX_STRAND (0 unstranded, 1 forward,
+        // 2 reverse; default 0), DART_TX_FRAG_MEAN (the mean fragment length of a library without pairs, default 200) and DART_TX_MAX_ROUNDS (default 1000): a
+        // value that is no such number ends the run before any output exists.
+        { const char *v = lookup("DART_TX_QUANT"); tx_gtf = v && v[0] ? v : nullptr; }
+        if (tx_gtf) tx_path = std::string(out) + ".transcripts.tab";
+        {
+            const struct { const char *name; unsigned long long lo, hi; } num[3] = {{"DART_TX_STRAND", 0ull, 2ull}, {"DART_TX_FRAG_MEAN", 1ull, 0xFFFFFFFFull}, {"DART_TX_MAX_ROUNDS", 0ull, 0xFFFFFFFFull}};
+            unsigned long long val[3] = {tx_strand, tx_frag_mean, tx_max_rounds};
+            for (int k = 0; k < 3; k++) if (const char *v = lookup(num[k].name)) {
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long x = strtoull(v, &end, 0);
+                if (!(v[0] >= '0' && v[0] <= '9') || *end || errno || x < num[k].lo || x > num[k].hi) {
+                    fprintf(err_f, "Error! %s=%s: a whole number from %llu to %llu is expected\n", num[k].name, v, num[k].lo, num[k].hi);
+                    return 1;
+                }
+                val[k] = x;
+            }
+            tx_strand = (uint32_t)val[0]; tx_frag_mean = val[1]; tx_max_rounds = (uint32_t)val[2];
+        }
         if (const char *v = lookup("DART_EXPECTED_READS")) { has_expected_reads = true; expected_reads = (uint64_t)atoll(v); }
         sync_aids = env_on("DART_SYNC_AIDS");
         timing = lookup("DART_TIMING") != nullptr;

@@ -380,7 +380,7 @@ static void abandon_outputs(const Config &c, Output &o, AbandonAt at)
 // The contexts: one root per device (the index files go to its HBM inside dg_init_files, main.cpp:231-235 / bwt_index.cpp:147-159), clones
 // for the batches in flight.  The look-up aids are built in the background while the first batches are mapped (DART_SYNC_AIDS=1: before).
 // Then the gene annotation and the chromosome names to every root.
-static int make_contexts(Job &job, const HostIndex &ix, const GtfAnnotation &gtf, const GtfTranscripts &rna, int n_gpu)
+static int make_contexts(Job &job, const HostIndex &ix, const GtfAnnotation &gtf, const GtfTranscripts &rna, const GtfTranscripts &txq, int n_gpu)
 {
     {
         const std::string pb = std::string(job.cfg.index) + ".bwt", ps = std::string(job.cfg.index) + ".sa", pp = std::string(job.cfg.index) + ".pac";
@@ -432,6 +432,15 @@ static int make_contexts(Job &job, const HostIndex &ix, const GtfAnnotation &gtf
         dg_rna_annot ann; ann.n_tx = (uint32_t)rna.tx.size(); ann.pad = 0; ann.n_exons = rna.exons.size(); ann.tx = rna.tx.data(); ann.exons = rna.exons.data();
         for (dg_ctx *r : job.roots) if (dg_rna_set_annotation(r, &ann, nullptr, nullptr)) {
             fprintf(stderr, "Error! DART_RNA_METRICS=%s: %s\n", job.cfg.rna_gtf, dg_last_error(r));
+            for (auto x : job.clones) dg_destroy(x);
+            for (auto x : job.roots) dg_destroy(x);
+            return 1;
+        }
+    }
+    if (job.cfg.tx_gtf) {        // and the expression stage's transcripts
+        dg_rna_annot ann; ann.n_tx = (uint32_t)txq.tx.size(); ann.pad = 0; ann.n_exons = txq.exons.size(); ann.tx = txq.tx.data(); ann.exons = txq.exons.data();
+        for (dg_ctx *r : job.roots) if (dg_tx_set_annotation(r, &ann, nullptr, nullptr)) {
+            fprintf(stderr, "Error! DART_TX_QUANT=%s: %s\n", job.cfg.tx_gtf, dg_last_error(r));
             for (auto x : job.clones) dg_destroy(x);
             for (auto x : job.roots) dg_destroy(x);
             return 1;
@@ -594,6 +603,7 @@ struct Streaming {
         b.ro.reset(new dg_read_out[n]); b.n_reads = (size_t)n;
         size_t caps[3] = { (size_t)n * 4 + 1024, (size_t)n * 16 + 4096, (size_t)n + 1024 };
         bool gene_even_counted = false;    // DART_GENE_COUNTS: likewise, the first part's units
+        bool tx_even_counted = false;      // DART_TX_QUANT: likewise
         bool sj_even_counted = false;      // DART_DEVICE_SJ: a batch runs in two parts (pairs, then an odd tail); the first part's tuples are counted once, also when the second part makes the batch run again
         for (int attempt = 0; attempt < 2; attempt++) {
             b.po.reset(new dg_report_out[caps[0]]); b.cig.reset(new uint32_t[caps[1]]); if (!c.device_sj) b.sj.reset(new dg_sj_out[caps[2]]);
@@ -604,6 +614,7 @@ struct Streaming {
             int rc = n_even ? dg_map_batch(x, n_even, off.data(), rl.data(), flat.data(), b.ro.get(), b.po.get(), b.cig.get(), b.sj.get(), caps, used1) : 0;
             if (rc == 0 && n_even && c.device_sj && !sj_even_counted) { rc = sj_accumulate(job, x); sj_even_counted = rc == 0; }
             if (rc == 0 && n_even && c.gene_gtf && !gene_even_counted) { rc = gene_accumulate(job, x, job.pair_end ? n_even : 0); gene_even_counted = rc == 0; }
+            if (rc == 0 && n_even && c.tx_gtf && !tx_even_counted) { rc = tx_accumulate(job, x, job.pair_end ? n_even : 0); tx_even_counted = rc == 0; }
             if (rc == 0 && n_even && c.device_sam) rc = device_text(b, x, 0, job.pair_end ? n_even : 0);
             if (rc == 0 && b.odd) {
                 p.paired = 0; dg_set_params(x, &p);
@@ -612,6 +623,7 @@ struct Streaming {
                                   b.cig.get() + used1[1], c.device_sj ? nullptr : b.sj.get() + used1[2], caps2, used2);
                 if (rc == 0 && c.device_sj) rc = sj_accumulate(job, x);
                 if (rc == 0 && c.gene_gtf) rc = gene_accumulate(job, x, 0);
+                if (rc == 0 && c.tx_gtf) rc = tx_accumulate(job, x, 0);
                 if (rc == 0 && c.device_sam) rc = device_text(b, x, n_even, 0);      // (before the offsets below are rebased: the device holds the batch's own)
                 if (rc == DG_ERR_CAPACITY) for (int q = 0; q < 3; q++) used2[q] += used1[q];
                 else {
@@ -980,6 +992,39 @@ static int write_gene_table(Job &job, const GtfAnnotation &gtf, unsigned long lo
     return RUN;
 }
 
+// DART_TX_QUANT: the clones' class tables into their root's (dg_tx_merge), further roots' into the first (downloaded, folded in with dg_tx_add), the EM on the
+// first root (dg_tx_finish); the host prints <out>.transcripts.tab from the words (dg_tx_format).  summary: the 16 summary words, ms: the device times by part
+static int write_tx_table(Job &job, const GtfTranscripts &txq, uint64_t summary[16], float ms[3])
+{
+    auto tx_fail = [&](dg_ctx *x) { fprintf(stderr, "\nError! DART_TX_QUANT=%s: %s\n", job.cfg.tx_gtf, dg_last_error(x)); return 1; };
+    for (size_t d = 0; d < job.roots.size(); d++)
+        for (int k = 1; k < job.cfg.inflight; k++) if (dg_tx_merge(job.roots[d], job.ctx[d * (size_t)job.cfg.inflight + k])) return tx_fail(job.roots[d]);
+    for (size_t d = 1; d < job.roots.size(); d++) {
+        size_t nc = 0, nm = 0;
+        if (dg_tx_classes_size(job.roots[d], &nc, &nm)) return tx_fail(job.roots[d]);
+        std::vector<uint64_t> off(nc + 1), cnt(nc + 1); std::vector<uint32_t> ids(nm + 1); uint64_t w8[8];
+        if (dg_tx_classes_download(job.roots[d], off.data(), ids.data(), cnt.data(), nc, nm, w8)) return tx_fail(job.roots[d]);
+        if (dg_tx_add(job.roots[0], off.data(), ids.data(), cnt.data(), nc, w8)) return tx_fail(job.roots[0]);
+    }
+    dg_ctx *root = job.roots[0];
+    size_t nw = 0;
+    if (dg_tx_finish(root, 0, job.cfg.tx_frag_mean, job.cfg.tx_max_rounds, &nw, nullptr)) return tx_fail(root);
+    std::vector<uint64_t> words(nw);
+    if (dg_tx_download(root, words.data(), nw) || dg_tx_device_ms(root, ms)) return tx_fail(root);
+    memcpy(summary, words.data() + nw - 16, 16 * sizeof(uint64_t));
+    dg_rna_annot ann; ann.n_tx = (uint32_t)txq.tx.size(); ann.pad = 0; ann.n_exons = txq.exons.size(); ann.tx = txq.tx.data(); ann.exons = txq.exons.data();
+    std::vector<const char *> names;
+    for (const std::string &n : txq.names) names.push_back(n.c_str());
+    std::vector<char> text; size_t nb = 0;
+    int rc = dg_tx_format(words.data(), nw, &ann, names.data(), nullptr, 0, &nb);
+    if (rc == DG_ERR_CAPACITY) { text.resize(nb ? nb : 1); rc = dg_tx_format(words.data(), nw, &ann, names.data(), text.data(), nb, &nb); }
+    if (rc) { fprintf(stderr, "\nError! DART_TX_QUANT=%s: the table's text could not be made (%d)\n", job.cfg.tx_gtf, rc); return 1; }
+    FILE *tf = fopen(job.cfg.tx_path.c_str(), "wb");
+    const bool ok = tf && fwrite(text.data(), 1, nb, tf) == nb;
+    if (!(tf && fclose(tf) == 0 && ok)) { remove(job.cfg.tx_path.c_str()); fprintf(stderr, "Error while writing %s\n", job.cfg.tx_path.c_str()); return 1; }
+    return RUN;
+}
+
 // Mapping.cpp:812-822 and OutputSpliceJunctions, Mapping.cpp:683-716
 static void print_summary(const Job &job, const HostIndex &ix, const SjTable &sj)
 {
@@ -1079,7 +1124,16 @@ int main(int argc, char *argv[])
         if (rna.skipped_seq || rna.skipped_strand)
             fprintf(stderr, "DART_RNA_METRICS: skipped %zu lines on sequences the index lacks and %zu with a strand other than + or -\n", rna.skipped_seq, rna.skipped_strand);
     }
-    if ((rc = make_contexts(job, ix, gtf, rna, n_gpu)) != RUN) return rc;
+    // DART_TX_QUANT: and for its GTF; no failed run leaves a table, a stale one included
+    GtfTranscripts txq;
+    if (cfg.tx_gtf) {
+        remove(cfg.tx_path.c_str());
+        const std::string terr = gtf_parse_transcripts(cfg.tx_gtf, ix.names, txq);
+        if (!terr.empty()) { fprintf(stderr, "\nError! DART_TX_QUANT=%s: %s\n", cfg.tx_gtf, terr.c_str()); return 1; }
+        if (txq.skipped_seq || txq.skipped_strand)
+            fprintf(stderr, "DART_TX_QUANT: skipped %zu lines on sequences the index lacks and %zu with a strand other than + or -\n", txq.skipped_seq, txq.skipped_strand);
+    }
+    if ((rc = make_contexts(job, ix, gtf, rna, txq, n_gpu)) != RUN) return rc;
     job.start_up_s = now_s() - t_proc0;
     fprintf(stdout, "\nLoad the reference sequences...\n");
     if ((rc = open_output(job, ix, out)) != RUN) return rc;
@@ -1103,9 +1157,16 @@ int main(int argc, char *argv[])
     if (cfg.device_sj && (rc = finish_junctions(job, sj)) != RUN) return rc;
     unsigned long long gene_counted = 0;
     if (cfg.gene_gtf && (rc = write_gene_table(job, gtf, gene_counted)) != RUN) return rc;
+    uint64_t tx_summary[16] = {0}; float tx_ms[3] = {0.f, 0.f, 0.f};
+    if (cfg.tx_gtf && (rc = write_tx_table(job, txq, tx_summary, tx_ms)) != RUN) return rc;
     for (auto x : job.clones) dg_destroy(x);
     for (auto x : job.roots) dg_destroy(x);
     if (job.total.total > 0) print_summary(job, ix, sj);
+    if (cfg.timing && cfg.tx_gtf) {
+        fprintf(stderr, "[dart timing] tx:");
+        for (int k = 0; k < 16; k++) fprintf(stderr, " %s=%llu", dg_tx_word_name(k), (unsigned long long)tx_summary[k]);
+        fprintf(stderr, " acc_ms=%.3f compat_ms=%.3f classes_ms=%.3f em_ms=%.3f\n", job.tx_acc_ns.load() * 1e-6, (double)tx_ms[0], (double)tx_ms[1], (double)tx_ms[2]);
+    }
     if (cfg.timing && cfg.gene_gtf)
         fprintf(stderr, "[dart genes] table=device units=%llu counted=%llu genes=%zu acc_ms=%.3f min_mapq=%u\n", (unsigned long long)job.gene_units.load(), gene_counted, gtf.genes.size(), job.gene_acc_ns.load() * 1e-6, cfg.gene_min_mapq);
     if (cfg.timing) {

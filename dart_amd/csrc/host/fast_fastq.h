@@ -403,6 +403,8 @@ struct SlotPool {
 //                      from the device's text at the end of the job
 //   cfg.gene_gtf       every mapping thread counts its batch's units per gene in its context's table on the GPU (gene_accumulate) right behind the mapping, where
 //                      sj_accumulate sits: mates are still neighbours there.  The gene stage merges the tables and prints <out>.genes.tab at the end of the job
+//   cfg.tx_gtf         likewise its units into its context's class table (tx_accumulate); the expression stage merges the tables, runs the EM and prints
+//                      <out>.transcripts.tab at the end of the job
 struct Job {
     const Config &cfg;
     std::vector<dg_ctx *> ctx, roots, clones;             // ctx: all contexts, device by device, each root followed by its clones
@@ -418,7 +420,7 @@ struct Job {
     size_t sort_ordinal_base = 0;                         // cfg.sort_bam: batches of the libraries before the current one
     // accounting for the `[dart timing]`, `[dart sj]` and `[dart genes]` lines: time in dg_batch_accumulate_bam; junction tuples seen, time in the accumulate
     // calls, time in the writer's map loop; units counted per gene, time in the accumulate calls
-    std::atomic<unsigned long long> sort_acc_ns{0}, sj_tuples{0}, sj_acc_ns{0}, sj_map_ns{0}, gene_units{0}, gene_acc_ns{0};
+    std::atomic<unsigned long long> sort_acc_ns{0}, sj_tuples{0}, sj_acc_ns{0}, sj_map_ns{0}, gene_units{0}, gene_acc_ns{0}, tx_units{0}, tx_acc_ns{0};
     explicit Job(const Config &c) : cfg(c), pair_end(c.pair_end) {}
 };
 
@@ -451,6 +453,16 @@ static inline int gene_accumulate(Job &job, dg_ctx *ctx, int n_pair_mode)
     size_t n = 0;
     const int rc = dg_batch_accumulate_genes(ctx, n_pair_mode, job.cfg.gene_min_mapq, &n);
     job.gene_acc_ns += now_ns() - t; job.gene_units += n;
+    return rc;
+}
+
+// and its units into its class table (DART_TX_QUANT)
+static inline int tx_accumulate(Job &job, dg_ctx *ctx, int n_pair_mode)
+{
+    const unsigned long long t = now_ns();
+    size_t n = 0;
+    const int rc = dg_batch_accumulate_tx(ctx, n_pair_mode, Config::tx_min_mapq, job.cfg.tx_strand, &n);
+    job.tx_acc_ns += now_ns() - t; job.tx_units += n;
     return rc;
 }
 
@@ -821,6 +833,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
                     }
                     if (!rc && c.device_sj) rc = sj_accumulate(job, job.ctx[w]);
                     if (!rc && c.gene_gtf) rc = gene_accumulate(job, job.ctx[w], (pair_end && !s->odd) ? n : 0);
+                    if (!rc && c.tx_gtf) rc = tx_accumulate(job, job.ctx[w], (pair_end && !s->odd) ? n : 0);
                     if (!rc) rc = dg_batch_download(job.ctx[w], s->ro, s->po, s->cig, c.device_sj ? nullptr : s->sj, s->caps);
                     s->rc = rc; if (rc) s->err = dg_last_error(job.ctx[w]);
                 }
@@ -835,6 +848,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
                     if (rc == DG_ERR_CAPACITY && attempt == 0) continue;      // `used` holds the need
                     if (!rc && c.device_sj) rc = sj_accumulate(job, job.ctx[w]);       // (a batch that ran short of capacity is mapped again as a new batch and was not counted)
                     if (!rc && c.gene_gtf) rc = gene_accumulate(job, job.ctx[w], (pair_end && !s->odd) ? n : 0);
+                    if (!rc && c.tx_gtf) rc = tx_accumulate(job, job.ctx[w], (pair_end && !s->odd) ? n : 0);
                     s->rc = rc; if (rc) s->err = dg_last_error(job.ctx[w]);
                     break;
                 }

@@ -63,6 +63,22 @@ class RnaAnnot(C.Structure):
 assert READ_OUT.itemsize == 36 and REPORT_OUT.itemsize == 40 and SJ_OUT.itemsize == 24 and READ_C.itemsize == 12 and REPORT_C.itemsize == 16
 
 
+def tx_text(lib, words, tx, exons, names) -> bytes:
+    """the text of the expression stage's result words under the annotation they were made with (dg_tx_format: on the host, no context)"""
+    w = np.ascontiguousarray(words, np.uint64); t = np.ascontiguousarray(tx, RNA_TX); e = np.ascontiguousarray(exons, RNA_EXON)
+    ann = RnaAnnot(len(t), 0, len(e), t.ctypes.data if len(t) else None, e.ctypes.data if len(e) else None)
+    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() if isinstance(n, str) else n for n in names])
+    nb = C.c_size_t(0)
+    rc = lib.dg_tx_format(w.ctypes.data, len(w), C.byref(ann), arr, None, 0, C.byref(nb))
+    if rc not in (0, -4):
+        raise RuntimeError("dg_tx_format failed (%d)" % rc)
+    out = C.create_string_buffer(max(nb.value, 1))
+    rc = lib.dg_tx_format(w.ctypes.data, len(w), C.byref(ann), arr, out, nb.value, C.byref(nb))
+    if rc != 0:
+        raise RuntimeError("dg_tx_format failed (%d)" % rc)
+    return out.raw[:nb.value]
+
+
 def expand_compact(reads_c, reports_c, cigar_c, rlen):
     """dg_read_c / dg_report_c arrays + the stored CIGAR ops + the read lengths -> (reads, reports, cigar ops) in the full record
     dtypes: rep_off / sj_off as running sums; a report marked DG_CIGAR_FULL_MATCH gets its "<length of its read>M" back; the stored ops
@@ -376,6 +392,21 @@ def _load_lib():
         lib.dg_gene_device.argtypes = [vp, vp]
         lib.dg_gene_device_ms.argtypes = [vp, vp]
         lib.dg_gene_granules.argtypes = [vp]
+    if hasattr(lib, "dg_tx_set_annotation"):                 # (likewise: transcript-level expression)
+        lib.dg_tx_set_annotation.argtypes = [vp, vp, vp, vp]
+        lib.dg_batch_accumulate_tx.argtypes = [vp, C.c_int, C.c_uint32, C.c_uint32, vp]
+        lib.dg_tx_count_records.argtypes = [vp, C.c_int, C.c_int, C.c_uint32, C.c_uint32, vp, vp, C.c_size_t, vp, C.c_size_t, vp]
+        lib.dg_tx_merge.argtypes = [vp, vp]
+        lib.dg_tx_add.argtypes = [vp, vp, vp, vp, C.c_size_t, vp]
+        lib.dg_tx_reset.argtypes = [vp]
+        lib.dg_tx_classes_size.argtypes = [vp, vp, vp]
+        lib.dg_tx_classes_download.argtypes = [vp, vp, vp, vp, C.c_size_t, C.c_size_t, vp]
+        lib.dg_tx_finish.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_uint32, vp, vp]
+        lib.dg_tx_download.argtypes = [vp, vp, C.c_size_t]
+        lib.dg_tx_device.argtypes = [vp, vp, vp]
+        lib.dg_tx_device_ms.argtypes = [vp, vp]
+        lib.dg_tx_granules.argtypes = [vp]
+        lib.dg_tx_format.argtypes = [vp, C.c_size_t, vp, vp, vp, C.c_size_t, vp]
     lib.dg_last_counters.argtypes = [vp, vp, C.c_int]
     lib.dg_probe_seeds.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, C.c_size_t, vp]
     lib.dg_probe_nw.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_size_t]
@@ -991,6 +1022,75 @@ class DartGPU:
         words = np.zeros(int(nw.value), np.uint64)
         self._chk(self.lib.dg_bam_qc_download(self.ctx, words.ctypes.data, len(words)), "dg_bam_qc_download")
         return qc_views(self.lib, words, len(self.index.names))
+
+    # ---- transcript-level expression on the device (dg_tx_*): equivalence classes per batch in a table in HBM, an EM over them at the end of the job ----
+    def tx_granules(self):
+        """(units per workgroup of the compatibility passes, the wave width) (dg_tx_granules)"""
+        g = (C.c_int * 2)()
+        self._chk(self.lib.dg_tx_granules(g), "dg_tx_granules")
+        return int(g[0]), int(g[1])
+
+    def tx_set_annotation(self, tx, exons):
+        """flattens and uploads the transcript annotation, kept with the index and shared by clones (dg_tx_set_annotation) -> (merged exons, segments);
+        tx: an RNA_TX array, exons: an RNA_EXON array, 0-based half-open coordinates"""
+        t = np.ascontiguousarray(tx, RNA_TX); e = np.ascontiguousarray(exons, RNA_EXON)
+        keep_t = t if len(t) else np.zeros(1, RNA_TX); keep_e = e if len(e) else np.zeros(1, RNA_EXON)
+        ann = RnaAnnot(len(t), 0, len(e), keep_t.ctypes.data, keep_e.ctypes.data)
+        nm, ns = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self.lib.dg_tx_set_annotation(self.ctx, C.byref(ann), C.byref(nm), C.byref(ns)), "dg_tx_set_annotation")
+        return int(nm.value), int(ns.value)
+
+    def accumulate_tx(self, n_pair_mode: int, min_mapq: int = 4, strand_mode: int = 0) -> int:
+        """folds the units of the batch that ran last into the context's class table (dg_batch_accumulate_tx) -> the number of units"""
+        n = C.c_size_t(0)
+        self._chk(self.lib.dg_batch_accumulate_tx(self.ctx, int(n_pair_mode), int(min_mapq), int(strand_mode), C.byref(n)), "dg_batch_accumulate_tx")
+        return int(n.value)
+
+    def tx_count_records(self, reads, reports, cigar, n_pair_mode: int, min_mapq: int = 4, strand_mode: int = 0) -> int:
+        """host records (READ_OUT, REPORT_OUT, CIGAR words) through the same kernels (dg_tx_count_records) -> the number of units"""
+        rd = np.ascontiguousarray(reads, READ_OUT); rp = np.ascontiguousarray(reports, REPORT_OUT); cg = np.ascontiguousarray(cigar, np.uint32)
+        n = C.c_size_t(0)
+        self._chk(self.lib.dg_tx_count_records(self.ctx, len(rd), int(n_pair_mode), int(min_mapq), int(strand_mode), rd.ctypes.data if len(rd) else None,
+                                               rp.ctypes.data if len(rp) else None, len(rp), cg.ctypes.data if len(cg) else None, len(cg), C.byref(n)), "dg_tx_count_records")
+        return int(n.value)
+
+    def tx_merge(self, src: "DartGPU"):
+        """folds src's class table into this context's and leaves src's empty (dg_tx_merge)"""
+        self._chk(self.lib.dg_tx_merge(self.ctx, src.ctx), "dg_tx_merge")
+
+    def tx_add(self, off, ids, count, words8):
+        """a downloaded class table folded in (dg_tx_add): uint64 off [n + 1], uint32 ids, uint64 count [n], uint64 words [8]"""
+        o = np.ascontiguousarray(off, np.uint64); i = np.ascontiguousarray(ids, np.uint32); k = np.ascontiguousarray(count, np.uint64); w = np.ascontiguousarray(words8, np.uint64)
+        assert len(w) == 8 and (len(k) == 0 or len(o) == len(k) + 1)
+        self._chk(self.lib.dg_tx_add(self.ctx, o.ctypes.data if len(k) else None, i.ctypes.data if len(i) else None, k.ctypes.data if len(k) else None, len(k), w.ctypes.data), "dg_tx_add")
+
+    def tx_reset(self):
+        self._chk(self.lib.dg_tx_reset(self.ctx), "dg_tx_reset")
+
+    def tx_classes(self):
+        """the context's class table (dg_tx_classes_size + dg_tx_classes_download) -> (off uint64 [n + 1], ids uint32, count uint64 [n], words uint64 [8])"""
+        nc, nm = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self.lib.dg_tx_classes_size(self.ctx, C.byref(nc), C.byref(nm)), "dg_tx_classes_size")
+        off = np.zeros(nc.value + 1, np.uint64); ids = np.zeros(max(nm.value, 1), np.uint32); cnt = np.zeros(max(nc.value, 1), np.uint64); words = np.zeros(8, np.uint64)
+        self._chk(self.lib.dg_tx_classes_download(self.ctx, off.ctypes.data, ids.ctypes.data, cnt.ctypes.data, nc.value, nm.value, words.ctypes.data), "dg_tx_classes_download")
+        split = (C.c_float * 3)()
+        self._chk(self.lib.dg_tx_device_ms(self.ctx, split), "dg_tx_device_ms")
+        self.tx_device_ms_split = tuple(float(x) for x in split)
+        return off, ids[:nm.value], cnt[:nc.value], words
+
+    def tx_finish(self, frag_mean: int = 200, max_rounds: int = 1000) -> np.ndarray:
+        """the EM over the context's class table (dg_tx_finish + dg_tx_download) -> uint64 [n_tx + 16]: S and the 16 summary words; self.tx_em_device_ms =
+        its device time"""
+        nw, ms = C.c_size_t(0), C.c_float(0)
+        self._chk(self.lib.dg_tx_finish(self.ctx, 0, int(frag_mean), int(max_rounds), C.byref(nw), C.byref(ms)), "dg_tx_finish")
+        self.tx_em_device_ms = float(ms.value)
+        words = np.zeros(int(nw.value), np.uint64)
+        self._chk(self.lib.dg_tx_download(self.ctx, words.ctypes.data, len(words)), "dg_tx_download")
+        return words
+
+    def tx_text(self, words, tx, exons, names) -> bytes:
+        """the text of result words (dg_tx_format, on the host)"""
+        return tx_text(self.lib, words, tx, exons, names)
 
     # ---- the RNA-seq metrics of the sorted array (dg_rna_set_annotation, dg_bam_rna_*): base classes, strand and gene-body coverage, built in HBM ----
     def rna_set_annotation(self, tx, exons):

@@ -861,6 +861,83 @@ int dg_bam_rna_granules(int out[2]);
 int dg_bam_rna_offsets(size_t out[6]);
 int dg_bam_rna_format(const uint64_t *words, size_t n_words, char *out, size_t cap, size_t *n_bytes);
 
+/* ---- transcript-level expression on the device (dart_amd/csrc/dg_txquant.h): per batch every unit's set of compatible transcripts, reduced to equivalence
+ * classes (ascending transcript list, count) in a class table that stays in HBM across batches; at the end of the job the tables are merged and an EM over the
+ * classes gives every transcript its share: what RSEM, or Salmon and kallisto in alignment mode, compute from the finished file.  An opt-in extension; the
+ * reference has no such output.  THE DEFINITION -- none of those tools exists where this project is built and tested, so this text is what the tests pin
+ * (tests/txquant_inputs.py is its sequential twin).
+ *   Annotation.  dg_rna_set_annotation's structs, validity rules and error texts (the first bad transcript is named, a bad call leaves the old tables in
+ *     place); cds_* and flags are validated and not used.  Each transcript's exons are sorted, exons that overlap or touch are merged; L_t = the sum of the
+ *     merged exons.  The tables (per transcript the merged exons with their prefix lengths; per chromosome a segment table: ascending breakpoints, per segment
+ *     the ascending ids of the transcripts with a merged exon over it, neighbouring segments with equal lists merged, the segment behind the last exon empty) are
+ *     built on the host once, kept with the index, shared by its clones, independent of the gene-count and RNA-metrics annotations, and carry a generation.
+ *   A read's alignment, strand s and blocks: the gene counts' rules, word for word (above).
+ *   A read's pieces.  Blocks with L > 0 are joined into one piece across I and D ops (a D's bases belong to the piece); an N op of any length ends a piece, the
+ *     next block begins a new one; ops that change nothing change nothing.  A read without blocks has no pieces.
+ *   Read r is compatible with transcript t when: it has at least one piece and t is on the read's chromosome; every piece lies wholly inside one merged exon of
+ *     t; for consecutive pieces j, j + 1 piece j ends exactly at the end of merged exon e and piece j + 1 starts exactly at the start of merged exon e + 1;
+ *     under strand_mode 1 (forward) t's strand == s, under strand_mode 2 (reverse) t's strand != s, strand_mode 0 ignores the strand.
+ *   A unit (the gene counts' units), in this order: 1. no read aligned: unmapped; 2. an aligned read has mapq < min_mapq: multimapping; 3. the unit's set is the
+ *     intersection of its aligned reads' compatible sets, each read under its own s; empty: incompatible; 4. otherwise counted: + 1 for the class whose list is
+ *     the set in ascending id order.
+ *   Fragment length, for a counted unit with two aligned reads, on t0 = the set's smallest id: toff(g) = the prefix length of the merged exon that holds g + g -
+ *     that exon's start; fl = toff(largest block end - 1) + 1 - toff(smallest block start) over both reads; FL_SUM += fl, FL_N += 1.
+ *   Class table, CSR: uint64 off[n_classes + 1], uint32 ids[], uint64 count[], with eight words: units, unmapped, multimapping, incompatible, counted, FL_SUM,
+ *     FL_N, 0; units = the sum of the next four.  As a multiset of (list, count) it is a function of the multiset of units: not of their order, the batch split,
+ *     the grid, the contexts or the merges.  The order of the classes is not defined.
+ *   Effective length.  mean = floor(FL_SUM / FL_N) when FL_N > 0, else frag_mean; eff_t = L_t - mean + 1 when L_t >= mean, else L_t (kallisto's fallback).
+ *   EM.  F = 2^20; N = the sum of the counts, N >= 2^33: DG_ERR_RANGE; t is active when a class lists it, M = the number of active transcripts.  M = 0: every
+ *     S_t = 0, 0 rounds, converged.  Start: S_t = floor(N F / M) for active t, 0 otherwise.  One round, every floating-point operation one IEEE double operation
+ *     without contraction: alpha_t = (double)S_t / F (exact); theta_t = alpha_t / (double)eff_t; per class D = the members' theta added one after the other in
+ *     ascending id order from 0.0; D == 0.0: the class gives nothing; otherwise per member q = theta_t / D, x = (double)n_c q, add = (uint64)floor(x 1048576.0),
+ *     S'_t += add, an integer sum: S' does not depend on the order of the classes, the grid or the atomics.  conv_r: every t with S'_t >= F has
+ *     100 |S'_t - S_t| <= S'_t.  The EM stops after round r when r == max_rounds, or when r is a multiple of 16 and conv_r holds; max_rounds 0 gives the start
+ *     values.  `converged` is conv_r of the last round (1 for M = 0; 0 when M > 0 and no round ran).
+ *     Result words: S[n_tx], then 16: units, unmapped, multimapping, incompatible, counted, classes, members (the sum of the list lengths), active, rounds,
+ *     converged, FL_SUM, FL_N, the mean used, strand_mode (of the context's last count), 0, 0.
+ *   dg_tx_set_annotation     as above; *n_exons_merged, *n_segments (either may be NULL): the tables' sizes
+ *   dg_batch_accumulate_tx   the units of the batch that ran last, folded into the context's table; *n_units (may be NULL).  DG_ERR_ARG, the table as it was:
+ *                            no annotation, no finished batch, a batch counted already, n_pair_mode odd or above the batch, compact records, strand_mode > 2, a
+ *                            table of another annotation generation (dg_tx_reset first)
+ *   dg_tx_count_records      the same record layout from host memory through the same kernels; the first read whose ranges leave the arrays is named and
+ *                            nothing is counted
+ *   dg_tx_merge              folds src's table into dst's and leaves src's empty; DG_ERR_ARG for dst == src, two devices or different generations
+ *   dg_tx_add                a downloaded table folded in (further roots); lists that are empty or not ascending, ids outside the annotation: DG_ERR_ARG, nothing
+ *                            changes, the text names the class
+ *   dg_tx_reset              an empty table of the current annotation's generation
+ *   dg_tx_classes_size       the table's classes and members
+ *   dg_tx_classes_download   off [n_classes + 1], ids, count and the eight words; DG_ERR_CAPACITY, nothing written, the text names the need, when a cap is smaller
+ *   dg_tx_finish             the EM over the context's table; flags: none is defined, any bit is DG_ERR_ARG.  Repeatable, leaves the class table as it was.
+ *                            *n_words = n_tx + 16; *device_ms (may be NULL): a measurement
+ *   dg_tx_download           the result words of the last finish; DG_ERR_CAPACITY, nothing written, when cap_words is too small
+ *   dg_tx_device             the same words in HBM, valid until the next dg_tx_* call on the context
+ *   dg_tx_device_ms          device time by part: [0] the compatibility passes and [1] the class building of the last count, merge or add, [2] the last EM
+ *   dg_tx_granules           [0] units per workgroup of the compatibility passes, [1] the wave width
+ *   dg_tx_word_name          the name of summary word i (0 .. 15) as dg_tx_format prints it; NULL for any other i
+ *   dg_tx_format             the text of downloaded result words, on the host (no context, no device; integers only, products in 128 bits): "# name\tvalue"
+ *                            per summary word, "transcript_id\tlength\teff_length\test_counts\ttpm", then one line per transcript in the caller's order:
+ *                            est_counts = floor(S_t 1000 / F) printed as %llu.%03llu; rate_t = floor(S_t 1024 / eff_t), R = the sum of the rates; tpm in
+ *                            thousandths = floor(rate_t 10^9 / R), 0 when R = 0, printed the same way.  a: the annotation the words were made under (for L_t);
+ *                            names: n_tx strings.  *n_bytes: the text's size; DG_ERR_CAPACITY, nothing written, when cap is smaller (out may be NULL with cap 0)
+ * Every failure leaves the context, the batch, the table and the other stages usable.  DG_TX_HASH_BITS (read at dg_init) truncates the lists' hashes: a test
+ * hook that forces the path for colliding hashes, the tables do not depend on it.                                                                       */
+int dg_tx_set_annotation(dg_ctx *, const dg_rna_annot *, size_t *n_exons_merged, size_t *n_segments);
+int dg_batch_accumulate_tx(dg_ctx *, int n_pair_mode, uint32_t min_mapq, uint32_t strand_mode, size_t *n_units);
+int dg_tx_count_records(dg_ctx *, int n_reads, int n_pair_mode, uint32_t min_mapq, uint32_t strand_mode, const dg_read_out *reads, const dg_report_out *reports, size_t n_reports,
+                        const uint32_t *cigar, size_t n_ops, size_t *n_units);
+int dg_tx_merge(dg_ctx *dst, dg_ctx *src);
+int dg_tx_add(dg_ctx *, const uint64_t *off, const uint32_t *ids, const uint64_t *count, size_t n_classes, const uint64_t *words8);
+int dg_tx_reset(dg_ctx *);
+int dg_tx_classes_size(dg_ctx *, size_t *n_classes, size_t *n_members);
+int dg_tx_classes_download(dg_ctx *, uint64_t *off, uint32_t *ids, uint64_t *count, size_t cap_classes, size_t cap_members, uint64_t *words8);
+int dg_tx_finish(dg_ctx *, uint32_t flags, uint64_t frag_mean, uint32_t max_rounds, size_t *n_words, float *device_ms);
+int dg_tx_download(dg_ctx *, uint64_t *words, size_t cap_words);
+int dg_tx_device(dg_ctx *, void **words, size_t *n_words);
+int dg_tx_device_ms(dg_ctx *, float ms[3]);
+int dg_tx_granules(int out[2]);
+const char *dg_tx_word_name(int i);
+int dg_tx_format(const uint64_t *words, size_t n_words, const dg_rna_annot *a, const char *const *names, char *out, size_t cap, size_t *n_bytes);
+
 /* per-kernel device time of the last dg_batch_run, measured with HIP events on the library's
  * stream: names[i] -> ms[i]; returns the number of entries written (<= cap)                   */
 int dg_last_timings(dg_ctx *, const char **names, float *ms, int cap);
@@ -888,6 +965,9 @@ int dg_debug_scan_trace(dg_ctx *, int which, uint64_t *out, size_t cap_tiles, si
  * input and the result, *_tmp are scratch of the same size.  Runs on the device's NULL stream and returns when done.
  * dart_amd/index_build.py drives it (prefix doubling: one sort of (rank pair, suffix) per round).                              */
 int dg_sort_pairs(int device, uint64_t *keys, int64_t *vals, uint64_t *keys_tmp, int64_t *vals_tmp, size_t n, int key_bits);
+/* The same passes alone, timed: the histograms are allocated before the first event and freed after the second, and nothing is copied back, so the sorted
+ * pairs may end in keys_tmp / vals_tmp (*in_tmp = 1).  *ms: the device time of the passes.  A yardstick for profiles/probes, n >= 2.               */
+int dg_probe_sort_passes(int device, uint64_t *keys, int64_t *vals, uint64_t *keys_tmp, int64_t *vals_tmp, size_t n, int key_bits, float *ms, int *in_tmp);
 
 /* ---- stage probes (parity tests of single kernels; mirror oracle/dart_oracle.h) ----
  * seeds of every read after the (gPos,rPos) sort (IdentifySeedPairs, AlignmentCandidates.cpp:181-215):
