@@ -91,6 +91,16 @@ struct FqState {
     bool tail_valid = false; size_t tail_n[2] = {0, 0}, tail_off2 = 0;
     hipError_t ready() { const hipError_t e = info.ready(); return e != hipSuccess ? e : ev.ready(); }
 };
+// trimming inside the FASTQ upload (dg_set_trim, dg_trim.h): the switches as the kernels take them, a TrimRead per read of the input, the statistics block;
+// stats / ms: of the last upload (zeros when it did not trim)
+struct TrimState {
+    bool on = false; TrimPar par = {};
+    DBuf<TrimRead> win;
+    DevStat<TrimInfo, 1> info;
+    EvSet<2> ev;                               // around the trimming kernels
+    uint64_t stats[16] = {}; float ms = 0.f; bool enqueued = false;      // enqueued: the upload under way took the trimmed path
+    hipError_t ready() { const hipError_t e = info.ready(); return e != hipSuccess ? e : ev.ready(); }
+};
 // BGZF inflated on the device (dg_bgzf_inflate, dg_batch_upload_fastq_bgzf; dg_inflate.h): the compressed bytes, the member table, a status word per member,
 // the first failing member; out holds the bytes of a dg_bgzf_inflate (the FASTQ path inflates straight into fq.text)
 struct InfState {

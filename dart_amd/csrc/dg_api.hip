@@ -14,6 +14,7 @@
 #include "dg_bgzf.h"
 #include "dg_bgzf_dyn.h"
 #include "dg_fastq.h"
+#include "dg_trim.h"
 #include "dg_inflate.h"
 #include "dg_sjtab.h"
 #include "dg_bamsort.h"
@@ -162,7 +163,7 @@ struct dg_ctx {
     bool batch_done = false;       // the batch on the context has been run and waited for
     bool no_batch = false;         // the last upload was a DG_FQ_CHECK_ONLY: there is nothing to run
     // the library stages' state, one struct each (api_ctx.h); every stage's section of this file drives its own
-    SamState sam; FqState fq; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; TgState tg; GcState gc; RmState rm; TxState tx;
+    SamState sam; FqState fq; TrimState tr; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; TgState tg; GcState gc; RmState rm; TxState tx;
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
@@ -1093,6 +1094,7 @@ struct FqPlan { size_t n[2], off2, line_cap[2], tile_stride, reads_bound, len_ti
 static int fq_reserve(dg_ctx *c, FqPlan &p)
 {
     HIPCHK(c->fq.ready());
+    if (c->tr.on) HIPCHK(c->tr.ready());
     // a record has at least one byte per existing line, so a text of n bytes holds at most n + 1 line starts; the three outputs together are never larger
     // than the texts
     const size_t max_reads = p.max_reads, n1 = p.n[0], n2 = p.n[1];
@@ -1105,9 +1107,33 @@ static int fq_reserve(dg_ctx *c, FqPlan &p)
     p.len_tiles = std::max<size_t>(1, (p.reads_bound + FQ_THREADS - 1) / FQ_THREADS);
     const size_t reads_bound = p.reads_bound, text_bytes = p.text_bytes;
     HIPCHK(c->fq.text.ensure(p.off2 + n2 + 32)); HIPCHK(c->fq.lines.ensure(p.line_cap[0] + p.line_cap[1] + 2)); HIPCHK(c->fq.tile_cnt.ensure(2 * p.tile_stride + 1));
-    HIPCHK(c->fq.name_at.ensure(reads_bound + 1)); HIPCHK(c->fq.name_len.ensure(reads_bound + 1)); HIPCHK(c->fq.loc.ensure(3 * (reads_bound + 1))); HIPCHK(c->fq.tile_sum.ensure(3 * p.len_tiles));
+    HIPCHK(c->fq.name_at.ensure(reads_bound + 1)); HIPCHK(c->fq.name_len.ensure(reads_bound + 1)); HIPCHK(c->fq.loc.ensure(4 * (reads_bound + 1))); HIPCHK(c->fq.tile_sum.ensure(4 * p.len_tiles));      // (the fourth row: the trimmed path's keep flags)
+    if (c->tr.on) HIPCHK(c->tr.win.ensure(reads_bound + 1));
     HIPCHK(c->fq.hdr_off.ensure(reads_bound + 1)); HIPCHK(c->fq.qual_off.ensure(reads_bound + 1)); HIPCHK(c->fq.hdr.ensure(text_bytes + 1)); HIPCHK(c->fq.qual.ensure(text_bytes + 1));
     HIPCHK(c->seq.ensure(text_bytes + 64)); HIPCHK(c->seq_off.ensure(reads_bound + 1)); HIPCHK(c->rlen.ensure(reads_bound + 1));
+    return DG_OK;
+}
+
+// the context trims (dg_set_trim): behind the line kernels the windows are cut, and the length, sum and writing kernels are the ones of dg_trim.h
+static int fq_enqueue_trimmed(dg_ctx *c, const FqPlan &p, const FqText &x, int rc_odd_reads, bool write)
+{
+    const uint32_t stride = (uint32_t)(p.reads_bound + 1);
+    HIPCHK(hipMemsetAsync(c->tr.info.d, 0, sizeof(TrimInfo), c->stream));
+    HIPCHK(hipEventRecord(c->tr.ev[0], c->stream));
+    if (p.reads_bound) k_trim_cut<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d, c->tr.par, c->tr.win.p);
+    k_trim_len<<<(unsigned)p.len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->fq.info.d, c->tr.par, c->tr.win.p, c->tr.info.d, c->fq.name_at.p, c->fq.name_len.p, c->fq.loc.p, stride, c->fq.tile_sum.p,
+                                                                     (uint32_t)p.len_tiles);
+    k_trim_top3<<<1, FQ_THREADS, 0, c->stream>>>(c->fq.tile_sum.p, (uint32_t)p.len_tiles, c->fq.info.d, c->tr.info.d);
+    if (p.reads_bound && write)
+        k_trim_write<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d, c->tr.info.d, rc_odd_reads ? 1 : 0, c->tr.win.p, c->fq.name_at.p, c->fq.name_len.p, c->fq.loc.p, stride,
+                                                                     c->fq.tile_sum.p, (uint32_t)p.len_tiles, c->rlen.p, c->seq_off.p, c->seq.p, c->fq.hdr_off.p, c->fq.hdr.p, c->fq.qual_off.p,
+                                                                     c->fq.qual.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(c->tr.ev[1], c->stream));
+    HIPCHK(hipEventRecord(c->fq.ev[1], c->stream));
+    HIPCHK(c->fq.info.fetch(c->stream));
+    HIPCHK(c->tr.info.fetch(c->stream));
+    c->tr.enqueued = true;
     return DG_OK;
 }
 
@@ -1125,6 +1151,7 @@ static int fq_enqueue(dg_ctx *c, const FqPlan &p, int rc_odd_reads, bool whole, 
     k_fq_lines<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq.tile_cnt.p, (uint32_t)p.tile_stride, c->fq.info.d);
     if (whole) k_fq_tail<<<dim3(64, p.two ? 2u : 1u), FQ_THREADS, 0, c->stream>>>(x, c->fq.info.d, c->fq.tail.p, (uint32_t)c->fq.tail_off2);
     if (pieces && p.reads_bound) k_fq_unlike<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d);
+    if (c->tr.on) return fq_enqueue_trimmed(c, p, x, rc_odd_reads, write);
     k_fq_len<<<(unsigned)p.len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->fq.info.d, c->rlen.p, c->fq.name_at.p, c->fq.name_len.p, c->fq.loc.p, stride, c->fq.tile_sum.p, (uint32_t)p.len_tiles);
     k_fq_top3<<<1, FQ_THREADS, 0, c->stream>>>(c->fq.tile_sum.p, (uint32_t)p.len_tiles, c->fq.info.d);
     if (p.reads_bound && write)
@@ -1141,6 +1168,8 @@ static int fq_finish(dg_ctx *c, const char *fn, int max_reads, int *n_reads_out,
 {
     c->fq.ms = c->fq.ev.ms(0, 1);
     const FqInfo &fi = *c->fq.info.h;
+    const bool trimmed = c->tr.enqueued;
+    c->tr.enqueued = false;
     if (n_reads_out) *n_reads_out = (int)std::min<uint32_t>(fi.n_reads, 0x7FFFFFFFu);
     switch (fi.status) {
     case FQ_OK: break;
@@ -1160,8 +1189,15 @@ static int fq_finish(dg_ctx *c, const char *fn, int max_reads, int *n_reads_out,
         snprintf(c->err, 512, "%s: the bases, names or qualities of the batch exceed 32-bit offsets", fn);
         return DG_ERR_ARG;
     }
+    uint32_t n_reads = fi.n_reads;
+    if (trimmed) {                                               // the batch is the kept reads
+        const TrimInfo &ti = *c->tr.info.h;
+        memcpy(c->tr.stats, ti.stats, sizeof c->tr.stats); c->tr.ms = c->tr.ev.ms(0, 1);
+        n_reads = ti.n_kept;
+        if (n_reads_out) *n_reads_out = (int)n_reads;
+    }
     if (!keep) return DG_OK;
-    c->n_reads = (int)fi.n_reads; c->max_rlen = (int)fi.max_rlen; c->seq_bytes = (size_t)fi.total[0];
+    c->n_reads = (int)n_reads; c->max_rlen = (int)fi.max_rlen; c->seq_bytes = (size_t)fi.total[0];
     c->fq.hdr_bytes = (size_t)fi.total[1]; c->fq.qual_bytes = (size_t)fi.total[2]; c->fq.valid = true;
     return DG_OK;
 }
@@ -1171,6 +1207,7 @@ static void fq_forget_batch(dg_ctx *c)
 {
     c->n_reads = 0; c->max_rlen = 0; c->seq_bytes = 0; c->enc_ready = false; c->enqueued = false; c->batch_done = false; c->sj.batch_counted = false; c->gc.batch_counted = false; c->tx.batch_counted = false; c->sam.valid = false; c->bam.valid = false; c->bam.rec_valid = false; c->bam.rec_stored = false; c->fq.valid = false;
     c->fq.hdr_bytes = c->fq.qual_bytes = 0; c->fq.ms = 0.f;
+    memset(c->tr.stats, 0, sizeof c->tr.stats); c->tr.ms = 0.f; c->tr.enqueued = false;
     c->no_batch = false; c->inf.valid = false; c->fq.tail_valid = false; c->fq.tail_n[0] = c->fq.tail_n[1] = 0;
 }
 
@@ -1357,6 +1394,49 @@ extern "C" int dg_batch_fastq_device_ms(dg_ctx *c, float *ms)
 {
     if (!c || !ms) return DG_ERR_ARG;
     *ms = c->fq.ms;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// trimming inside the FASTQ upload (dg_trim.h)
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_set_trim(dg_ctx *c, const dg_trim *t)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!t) { c->tr.on = false; return DG_OK; }
+    if (t->flags & ~DG_TRIM_PAIRS) { snprintf(c->err, 512, "dg_set_trim: unknown flag bits 0x%x", t->flags & ~DG_TRIM_PAIRS); return DG_ERR_ARG; }
+    if (t->min_len == 0 || t->min_overlap == 0) { snprintf(c->err, 512, "dg_set_trim: min_len and min_overlap must be at least 1"); return DG_ERR_ARG; }
+    if (t->max_err_permille > 1000u) { snprintf(c->err, 512, "dg_set_trim: max_err_permille is %u, above 1000", t->max_err_permille); return DG_ERR_ARG; }
+    if (t->poly_mask & ~15u) { snprintf(c->err, 512, "dg_set_trim: poly_mask 0x%x has a bit above 3", t->poly_mask); return DG_ERR_ARG; }
+    if (t->qual3 > TR_QUAL_MAX || t->qual5 > TR_QUAL_MAX || t->qual_base > TR_QUAL_MAX) { snprintf(c->err, 512, "dg_set_trim: qual3, qual5 and qual_base must not exceed %u", TR_QUAL_MAX); return DG_ERR_ARG; }
+    TrimPar par = {};
+    for (int i = 0; i < 2; i++) {
+        if (t->n_adapter[i] > 64u) { snprintf(c->err, 512, "dg_set_trim: adapter %d has %u bases, more than 64", i, t->n_adapter[i]); return DG_ERR_ARG; }
+        for (uint32_t j = 0; j < t->n_adapter[i]; j++) {
+            const char b = t->adapter[i][j];
+            if (b != 'A' && b != 'C' && b != 'G' && b != 'T') { snprintf(c->err, 512, "dg_set_trim: adapter %d has a byte outside ACGT at %u", i, j); return DG_ERR_ARG; }
+            par.acode[i][j >> 5] |= (uint64_t)trim_code(b) << (2u * (j & 31u));
+        }
+        par.alen[i] = t->n_adapter[i];
+    }
+    par.flags = t->flags; par.qual3 = t->qual3; par.qual5 = t->qual5; par.qual_base = t->qual_base; par.min_overlap = t->min_overlap; par.max_err_permille = t->max_err_permille;
+    par.poly_mask = t->poly_mask; par.poly_min = t->poly_min; par.min_len = t->min_len;
+    c->tr.par = par; c->tr.on = true;
+    return DG_OK;
+}
+
+extern "C" int dg_batch_trim_stats(dg_ctx *c, uint64_t stats[16], float *device_ms)
+{
+    if (!c || !stats) return DG_ERR_ARG;
+    memcpy(stats, c->tr.stats, sizeof c->tr.stats);
+    if (device_ms) *device_ms = c->tr.ms;
+    return DG_OK;
+}
+
+extern "C" int dg_trim_granules(int out[2])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = FQ_THREADS; out[1] = 64;
     return DG_OK;
 }
 

@@ -62,6 +62,9 @@ struct Config {
     uint64_t tx_frag_mean = 200u;           // DART_TX_FRAG_MEAN
     static constexpr uint32_t tx_min_mapq = 4u;                        // the units that count as unique: the -unique rule, mapq > 3 (no switch)
     std::string tx_path;                    // <out>.transcripts.tab; empty = not asked for
+    bool trim = false;                      // any of DART_TRIM_ADAPTER, DART_TRIM_QUAL, DART_TRIM_QUAL5, DART_TRIM_POLY
+    dg_trim trim_par;                       // the DART_TRIM_* switches as dg_set_trim takes them (flags: the library's pairing decides DG_TRIM_PAIRS)
+    std::string trim_path;                  // <out>.trim.txt; empty = not asked for
     int write_threads = 1;                  // DART_WRITE_THREADS, at least 1
     int fmt_threads = 0;                    // DART_FMT_THREADS, at least 1; 0 = unset (what -t leaves)
     bool write_mmap = false;                // DART_WRITE=mmap
@@ -118,6 +121,49 @@ struct Config {
             at = e + 1;
         }
         return bits;
+    }
+
+    // the DART_TRIM_* switches into trim / trim_par; RUN, or 1 behind a value that cannot be used (said on err_f)
+    int parse_trim(const char *(*lookup)(const char *), FILE *err_f)
+    {
+        memset(&trim_par, 0, sizeof trim_par);
+        trim_par.qual_base = 33; trim_par.min_overlap = 3; trim_par.max_err_permille = 100; trim_par.poly_min = 10; trim_par.min_len = 20;
+        auto adapter = [&](const char *key, int which) -> bool {      // false: said why
+            const char *v = lookup(key);
+            if (!v || !v[0]) return true;
+            std::string a = v;
+            if (a == "illumina") a = "AGATCGGAAGAGC"; else if (a == "nextera") a = "CTGTCTCTTATA"; else if (a == "smallrna") a = "TGGAATTCTCGG";
+            if (a.size() > 64 || a.find_first_not_of("ACGT") != std::string::npos) {
+                fprintf(err_f, "Error! %s=%s: an adapter is at most 64 letters of ACGT, or one of illumina, nextera, smallrna\n", key, v);
+                return false;
+            }
+            trim_par.n_adapter[which] = (uint32_t)a.size(); memcpy(trim_par.adapter[which], a.data(), a.size());
+            return true;
+        };
+        if (!adapter("DART_TRIM_ADAPTER", 0)) return 1;
+        trim_par.n_adapter[1] = trim_par.n_adapter[0]; memcpy(trim_par.adapter[1], trim_par.adapter[0], 64);
+        if (!adapter("DART_TRIM_ADAPTER2", 1)) return 1;
+        const struct { const char *name; uint32_t *to; unsigned long long lo, hi; } num[7] = {
+            {"DART_TRIM_QUAL", &trim_par.qual3, 0ull, 93ull}, {"DART_TRIM_QUAL5", &trim_par.qual5, 0ull, 93ull}, {"DART_TRIM_POLY_MIN", &trim_par.poly_min, 1ull, 1000ull},
+            {"DART_TRIM_MIN_OVERLAP", &trim_par.min_overlap, 1ull, 64ull}, {"DART_TRIM_ERR", &trim_par.max_err_permille, 0ull, 1000ull}, {"DART_TRIM_MIN_LEN", &trim_par.min_len, 1ull, 1000ull},
+            {nullptr, nullptr, 0ull, 0ull}};
+        for (int k = 0; num[k].name; k++) if (const char *v = lookup(num[k].name)) {
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long x = strtoull(v, &end, 10);
+            if (!(v[0] >= '0' && v[0] <= '9') || *end || errno || x < num[k].lo || x > num[k].hi) {
+                fprintf(err_f, "Error! %s=%s: a whole number from %llu to %llu is expected\n", num[k].name, v, num[k].lo, num[k].hi);
+                return 1;
+            }
+            *num[k].to = (uint32_t)x;
+        }
+        if (const char *v = lookup("DART_TRIM_POLY")) for (const char *q = v; *q; q++) {
+            const char *at = strchr("ACGT", *q >= 'a' && *q <= 'z' ? *q - 32 : *q);
+            if (!at) { fprintf(err_f, "Error! DART_TRIM_POLY=%s: letters of ACGT are expected\n", v); return 1; }
+            trim_par.poly_mask |= 1u << (at - "ACGT");
+        }
+        trim = trim_par.n_adapter[0] || trim_par.n_adapter[1] || trim_par.qual3 || trim_par.qual5 || trim_par.poly_mask;
+        return RUN;
     }
 
     // argv and the environment into *this.  lookup: getenv, or a test's table.  defaults: dg_params_default's, handed in so that this header links without the library.
@@ -294,6 +340,22 @@ struct Config {
         // qualities): a library whose files are all FASTQ .gz with a BGZF block in front is inflated on the device too (GzDevPlan, fast_fastq.h).  Anything else
         // -- also a library its check pass turns down -- runs as without the switch.
         device_gz = env_on("DART_DEVICE_GZ") && env_on("DART_DEVICE_FASTQ") && !bam_streams && !streaming && (device_bam || device_sam);
+        // DART_TRIM_*: adapters, poly tails and low-quality ends are cut on the device inside the FASTQ upload (dg_set_trim), in place of a cutadapt / fastp pass over
+        // the files in front of the mapper; pairs that became too short are dropped; <out>.trim.txt holds the sums.  Any of DART_TRIM_ADAPTER (ACGT letters, or
+        // illumina / nextera / smallrna), DART_TRIM_QUAL (3' end), DART_TRIM_QUAL5 or DART_TRIM_POLY (letters of ACGT) turns the stage on; DART_TRIM_ADAPTER2 (mate
+        // 2's, default the first), DART_TRIM_POLY_MIN (10), DART_TRIM_MIN_OVERLAP (3), DART_TRIM_ERR (permille, 100) and DART_TRIM_MIN_LEN (20) tune it.  The host no
+        // longer knows names, qualities or even the read count of a batch, so the stage needs the device parser and a device formatter: without them the job is
+        // refused -- untrimmed reads are never mapped silently.
+        {
+            int trc = parse_trim(lookup, err_f);
+            if (trc != RUN) return trc;
+            if (trim && !(device_fastq && (device_sam || device_bam) && !streaming)) {
+                fprintf(err_f, "Error! DART_TRIM_* needs the device parser and a device formatter (DART_DEVICE_FASTQ=1 with DART_DEVICE_SAM=1, or with DART_DEVICE_BAM=1 and -bo): %s\n",
+                        streaming ? "DART_STREAMING is set" : bam && !device_bam ? "DART_DEVICE_BAM=1 is missing" : !device_fastq ? "DART_DEVICE_FASTQ=1 is missing" : "DART_DEVICE_SAM=1 is missing");
+                return 1;
+            }
+            if (trim) trim_path = std::string(out) + ".trim.txt";
+        }
         // DART_DEVICE_SJ=1: the junction table is counted, sorted and printed on the device (dg_batch_accumulate_sj per batch, dg_sj_merge / dg_sj_finish at the end);
         // works in both pipelines, with -o and -bo alike.  Without the switch the ordered writer fills a std::map, as always.
         device_sj = env_on("DART_DEVICE_SJ");

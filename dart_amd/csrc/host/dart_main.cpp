@@ -753,6 +753,11 @@ static int run_library(Job &job, Output &o, size_t lib, LibPlan &plan)
         abandon_outputs(job.cfg, o, BEFORE_CLOSE);
         return 1;
     }
+    if (job.cfg.trim && !L.fast_host) {      // (untrimmed reads are never mapped silently)
+        fprintf(stderr, "\nError! DART_TRIM_*: %s takes the streaming pipeline (FASTA, a streamed .gz), where nothing is trimmed\n", f1);
+        abandon_outputs(job.cfg, o, BEFORE_CLOSE);
+        return 1;
+    }
     if (L.sep) job.pair_end = true;
     const int rc = L.fast_host ? run_fast_stage(job, o, lib, &plan.pre, nullptr, false) : run_streaming_stage(job, o, L);
     if (rc != RUN) return rc;
@@ -1025,6 +1030,19 @@ static int write_tx_table(Job &job, const GtfTranscripts &txq, uint64_t summary[
     return RUN;
 }
 
+// DART_TRIM_*: the statistics of every upload, summed over batches and libraries, as key<TAB>value lines in the order of dg_batch_trim_stats
+static int write_trim_stats(const Job &job)
+{
+    static const char *const key[14] = {"reads_in", "reads_kept", "bases_in", "bases_kept", "qual5_bases", "qual3_bases", "adapter0_reads", "adapter1_reads", "adapter_bases", "poly_reads",
+                                        "poly_bases", "too_short_reads", "mate_dropped_reads", "qual_skipped_reads"};
+    std::string text;
+    for (int k = 0; k < 14; k++) { text += key[k]; text += '\t'; text += std::to_string(job.trim_stats[k].load()); text += '\n'; }
+    FILE *tf = fopen(job.cfg.trim_path.c_str(), "wb");
+    const bool ok = tf && fwrite(text.data(), 1, text.size(), tf) == text.size();
+    if (!(tf && fclose(tf) == 0 && ok)) { remove(job.cfg.trim_path.c_str()); fprintf(stderr, "Error while writing %s\n", job.cfg.trim_path.c_str()); return 1; }
+    return RUN;
+}
+
 // Mapping.cpp:812-822 and OutputSpliceJunctions, Mapping.cpp:683-716
 static void print_summary(const Job &job, const HostIndex &ix, const SjTable &sj)
 {
@@ -1133,6 +1151,7 @@ int main(int argc, char *argv[])
         if (txq.skipped_seq || txq.skipped_strand)
             fprintf(stderr, "DART_TX_QUANT: skipped %zu lines on sequences the index lacks and %zu with a strand other than + or -\n", txq.skipped_seq, txq.skipped_strand);
     }
+    if (cfg.trim) remove(cfg.trim_path.c_str());      // (no failed run leaves a table, a stale one included)
     if ((rc = make_contexts(job, ix, gtf, rna, txq, n_gpu)) != RUN) return rc;
     job.start_up_s = now_s() - t_proc0;
     fprintf(stdout, "\nLoad the reference sequences...\n");
@@ -1159,6 +1178,7 @@ int main(int argc, char *argv[])
     if (cfg.gene_gtf && (rc = write_gene_table(job, gtf, gene_counted)) != RUN) return rc;
     uint64_t tx_summary[16] = {0}; float tx_ms[3] = {0.f, 0.f, 0.f};
     if (cfg.tx_gtf && (rc = write_tx_table(job, txq, tx_summary, tx_ms)) != RUN) return rc;
+    if (cfg.trim && (rc = write_trim_stats(job)) != RUN) return rc;
     for (auto x : job.clones) dg_destroy(x);
     for (auto x : job.roots) dg_destroy(x);
     if (job.total.total > 0) print_summary(job, ix, sj);
@@ -1167,6 +1187,9 @@ int main(int argc, char *argv[])
         for (int k = 0; k < 16; k++) fprintf(stderr, " %s=%llu", dg_tx_word_name(k), (unsigned long long)tx_summary[k]);
         fprintf(stderr, " acc_ms=%.3f compat_ms=%.3f classes_ms=%.3f em_ms=%.3f\n", job.tx_acc_ns.load() * 1e-6, (double)tx_ms[0], (double)tx_ms[1], (double)tx_ms[2]);
     }
+    if (cfg.timing && cfg.trim)
+        fprintf(stderr, "[dart trim] reads_in=%llu reads_kept=%llu bases_in=%llu bases_kept=%llu kernels_ms=%.3f\n", job.trim_stats[0].load(), job.trim_stats[1].load(), job.trim_stats[2].load(),
+                job.trim_stats[3].load(), job.trim_kernel_us.load() * 1e-3);
     if (cfg.timing && cfg.gene_gtf)
         fprintf(stderr, "[dart genes] table=device units=%llu counted=%llu genes=%zu acc_ms=%.3f min_mapq=%u\n", (unsigned long long)job.gene_units.load(), gene_counted, gtf.genes.size(), job.gene_acc_ns.load() * 1e-6, cfg.gene_min_mapq);
     if (cfg.timing) {

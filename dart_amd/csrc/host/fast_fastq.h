@@ -392,6 +392,10 @@ struct SlotPool {
 //   cfg.device_fastq   a batch goes to the GPU as the bytes of its records, straight from the mapped files (dg_batch_upload_fastq): no arena, no base copy on the
 //                      host; with device_sam as well the text is formatted from the names and qualities that upload left in HBM (dg_batch_format_sam_resident)
 //                      and nothing is gathered.  The index pass still decides the batches.  A library with a record without bases keeps the host's assembly
+//   cfg.trim           every mapping thread sets the DART_TRIM_* switches on its context (dg_set_trim) for the library, and the upload cuts adapters, poly tails and
+//                      low-quality ends and drops what became too short: the batch's read count is from then on what the upload returned, not what the index
+//                      pass planned, and the statistics of every upload are summed into trim_stats.  Needs device_fastq and a device formatter (Config refuses the
+//                      job otherwise); a library that falls back to the host's assembly is refused here
 //   cfg.device_bam     the batch's BAM records are written and compressed on the GPU (dg_batch_format_bam, or its resident form with device_fastq) behind its
 //                      mapping; the slot holds whole BGZF blocks and the ordered writer hands them to bam_sink (BamWriter::add_bgzf_blocks) instead of writing
 //                      text to sam_fd.  cfg.bgzf_dynamic: the blocks are coded with dynamic Huffman codes per strip (DG_BAM_DYNAMIC): a smaller file of the same records
@@ -421,6 +425,7 @@ struct Job {
     // accounting for the `[dart timing]`, `[dart sj]` and `[dart genes]` lines: time in dg_batch_accumulate_bam; junction tuples seen, time in the accumulate
     // calls, time in the writer's map loop; units counted per gene, time in the accumulate calls
     std::atomic<unsigned long long> sort_acc_ns{0}, sj_tuples{0}, sj_acc_ns{0}, sj_map_ns{0}, gene_units{0}, gene_acc_ns{0}, tx_units{0}, tx_acc_ns{0};
+    std::atomic<unsigned long long> trim_stats[16] = {}, trim_kernel_us{0};      // cfg.trim: dg_batch_trim_stats summed over batches and libraries; the trimming kernels' device time
     explicit Job(const Config &c) : cfg(c), pair_end(c.pair_end) {}
 };
 
@@ -697,6 +702,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
     if (batch_reads & 1) batch_reads++;
     const bool fq_device = gzp || (c.device_fastq && !explicit_order);      // (an entry without bases ends a chunk: the replayed order is not a byte range)
     st.fq_device = fq_device;
+    if (c.trim && !fq_device) { err = "DART_TRIM_*: this library falls back to the host's assembly (a record without bases), where nothing is trimmed"; return DG_ERR_ARG; }
     // the bytes of records [a, b) of a mapped file
     auto byte_range = [](const MappedFile &mf, const std::vector<FqRec> &v, size_t a, size_t b, const char *&p, size_t &n) {
         const size_t lo = a < v.size() ? (size_t)v[a].off : mf.n, hi = b < v.size() ? (size_t)v[b].off : mf.n;
@@ -797,6 +803,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
 
     std::vector<std::thread> mappers;
     for (size_t w = 0; w < job.ctx.size(); w++) mappers.emplace_back([&, w]() {
+        if (c.trim) { dg_trim t = c.trim_par; t.flags = pair_end ? DG_TRIM_PAIRS : 0u; if (dg_set_trim(job.ctx[w], &t)) { std::lock_guard<std::mutex> lk(mu); failed = true; fail_rc = DG_ERR_ARG; err = dg_last_error(job.ctx[w]); } }
         while (true) {
             FastSlot *s;
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&]() { return !map_q.empty() || asm_done || failed; }); if (failed || map_q.empty()) break; s = map_q.front(); map_q.pop_front(); }
@@ -804,7 +811,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
             double t_fq = 0, t_gz_wait = 0; float fq_ms = 0.f;
             if (!s->rc && s->fq_device) {
                 // upload the text (the device cuts it into the batch) -> run -> download
-                const int n = s->n;
+                int n = s->n;
                 dg_params p = c.p; p.paired = (pair_end && !s->odd) ? 1 : 0;
                 dg_set_params(job.ctx[w], &p);
                 dg_fastq_text ft; ft.text1 = s->fq1; ft.n1 = s->fq_n1; ft.text2 = s->fq2; ft.n2 = s->fq_n2; ft.rc_odd_reads = pair_end ? 1 : 0; ft.max_reads = n;
@@ -823,6 +830,13 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
                 } else rc = dg_batch_upload_fastq(job.ctx[w], &ft, &got);
                 t_fq = now_s() - tu;
                 (void)dg_batch_fastq_device_ms(job.ctx[w], &fq_ms);
+                if (!rc && c.trim) {             // the batch is what the upload kept: every count behind it is the returned one
+                    uint64_t ts[16]; float tms = 0.f;
+                    (void)dg_batch_trim_stats(job.ctx[w], ts, &tms);
+                    for (int k = 0; k < 16; k++) job.trim_stats[k] += ts[k];
+                    job.trim_kernel_us += (unsigned long long)(tms * 1e3f);
+                    s->n = n = got;
+                }
                 if (!rc && got != n) { s->rc = DG_ERR_INTERNAL; s->err = "the device parser found " + std::to_string(got) + " reads in a batch of " + std::to_string(n); }
                 else if (rc) { s->rc = rc; s->err = dg_last_error(job.ctx[w]); }
                 else {
@@ -919,6 +933,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
             { std::lock_guard<std::mutex> lk(mu); st.t_map += now_s() - tm - t_gather - t_call - t_dl - t_fq - t_gz_wait; st.t_gz_tail += t_gz_wait; st.t_fq_call += t_fq; st.t_fq_kernels += fq_ms * 1e-3; st.t_gather += t_gather; st.t_dev_call += t_call; st.t_dev_kernels += dev_ms * 1e-3; st.t_download += t_dl; st.n_batches++; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
             cv.notify_all();
         }
+        if (c.trim) (void)dg_set_trim(job.ctx[w], nullptr);      // (the next library's check pass, and its pairing, start from an untrimmed context)
         { std::lock_guard<std::mutex> lk(mu); mappers_left--; }
         cv.notify_all();
     });

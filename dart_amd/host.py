@@ -151,6 +151,17 @@ class FastqBgzf(C.Structure):
 FQ_CHECK_ONLY = 1           # DG_FQ_CHECK_ONLY: inflate, count and check; no batch is written
 
 
+class Trim(C.Structure):
+    """dg_trim (include/dartgpu.h)"""
+    _fields_ = [("flags", C.c_uint32), ("qual3", C.c_uint32), ("qual5", C.c_uint32), ("qual_base", C.c_uint32), ("min_overlap", C.c_uint32), ("max_err_permille", C.c_uint32),
+                ("poly_mask", C.c_uint32), ("poly_min", C.c_uint32), ("min_len", C.c_uint32), ("n_adapter", C.c_uint32 * 2), ("adapter", (C.c_char * 64) * 2)]
+
+
+TRIM_PAIRS = 1              # DG_TRIM_PAIRS: reads 2k and 2k+1 are mates
+TRIM_STAT_KEYS = ("reads_in", "reads_kept", "bases_in", "bases_kept", "qual5_bases", "qual3_bases", "adapter0_reads", "adapter1_reads", "adapter_bases", "poly_reads",
+                  "poly_bases", "too_short_reads", "mate_dropped_reads", "qual_skipped_reads")
+
+
 def flatten_strings(items):
     """list of bytes / str -> (u32 offsets [n + 1], u8 array): the form dg_set_chr_names and dg_batch_format_sam take names and qualities in"""
     bs = [x if isinstance(x, (bytes, bytearray)) else x.encode("latin1") for x in items]
@@ -298,6 +309,10 @@ def _load_lib():
         lib.dg_batch_download_reads.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         lib.dg_batch_fastq_device_ms.argtypes = [vp, vp]
         lib.dg_fastq_tile.restype = C.c_int
+    if hasattr(lib, "dg_set_trim"):                          # (likewise: trimming inside the FASTQ upload)
+        lib.dg_set_trim.argtypes = [vp, vp]
+        lib.dg_batch_trim_stats.argtypes = [vp, vp, vp]
+        lib.dg_trim_granules.argtypes = [vp]
     if hasattr(lib, "dg_batch_format_bam"):                  # (likewise: BAM records and BGZF blocks on the device)
         lib.dg_batch_format_bam.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp]
         lib.dg_batch_format_bam_resident.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, vp, vp]
@@ -604,6 +619,39 @@ class DartGPU:
         self.lib.dg_batch_fastq_device_ms(self.ctx, C.byref(ms))
         self.fastq_device_ms = float(ms.value)
         return self._n
+
+    def set_trim(self, adapter=b"", adapter2=None, qual3: int = 0, qual5: int = 0, qual_base: int = 33, min_overlap: int = 3, max_err_permille: int = 100,
+                 poly: str = "", poly_min: int = 10, min_len: int = 20, pairs: bool = False, off: bool = False, flags: int | None = None, poly_mask: int | None = None):
+        """cut adapters, poly tails and low-quality ends inside every following FASTQ upload of this context (dg_set_trim; the definition is in
+        include/dartgpu.h).  adapter2 None: the first adapter; poly: letters of ACGT; off=True: no trimming.  flags / poly_mask: the raw words, for the error tests."""
+        if not hasattr(self.lib, "dg_set_trim"):
+            raise RuntimeError("this build of libdartgpu.so has no dg_set_trim")
+        if off:
+            self._chk(self.lib.dg_set_trim(self.ctx, None), "dg_set_trim")
+            return
+        a = [bytes(adapter), bytes(adapter if adapter2 is None else adapter2)]
+        t = Trim()
+        t.flags = (TRIM_PAIRS if pairs else 0) if flags is None else flags
+        t.qual3, t.qual5, t.qual_base, t.min_overlap, t.max_err_permille = qual3, qual5, qual_base, min_overlap, max_err_permille
+        t.poly_mask = sum(1 << "ACGT".index(c) for c in poly.upper()) if poly_mask is None else poly_mask
+        t.poly_min, t.min_len = poly_min, min_len
+        for i in range(2):
+            t.n_adapter[i] = len(a[i])
+            C.memmove(t.adapter[i], a[i][:64], min(len(a[i]), 64))
+        self._chk(self.lib.dg_set_trim(self.ctx, C.byref(t)), "dg_set_trim")
+
+    def trim_stats(self):
+        """the last upload's trimming statistics (dg_batch_trim_stats) -> [16] ints; self.trim_device_ms holds the trimming kernels' device time"""
+        st = (C.c_uint64 * 16)(); ms = C.c_float(0)
+        self._chk(self.lib.dg_batch_trim_stats(self.ctx, st, C.byref(ms)), "dg_batch_trim_stats")
+        self.trim_device_ms = float(ms.value)
+        return [int(x) for x in st]
+
+    def trim_granules(self):
+        """(reads per workgroup of the length kernel, start positions per round of the cutting kernel) (dg_trim_granules)"""
+        g = (C.c_int * 2)()
+        self._chk(self.lib.dg_trim_granules(g), "dg_trim_granules")
+        return int(g[0]), int(g[1])
 
     def download_reads(self):
         """the batch a FASTQ upload parsed (dg_batch_download_reads) -> (seq_off u32 [n], rlen u16 [n], flat u8, names [n] bytes, stored qualities [n] bytes)"""

@@ -345,6 +345,53 @@ int dg_batch_upload_fastq_bgzf(dg_ctx *, const dg_fastq_bgzf *, uint32_t flags, 
 int dg_batch_download_fastq_tail(dg_ctx *, char *tail1, size_t cap1, char *tail2, size_t cap2);
 int dg_inflate_granules(int out[2]);
 
+/* ---- adapters, poly tails and low-quality ends cut on the device, inside the FASTQ upload (an extension: the reference has no such stage; opt-in per
+ * context, unset nothing changes) ----
+ * The rules follow cutadapt where that is simple to say (its quality rule, its poly-A rule, its order of steps); this text is the definition, and
+ * tests/trim_inputs.py is its sequential twin.  A read is its line 1 as sequenced (L bases s[0..L)) and its quality line cut to the read (ql <= L bytes
+ * q[0..ql)), as dg_batch_upload_fastq takes them.  All steps work in file orientation; the reverse complement of a stored mate 2 is applied afterwards to the
+ * kept window.  A base compares by its upper case; anything outside ACGT equals nothing.  All arithmetic is integer.
+ *   1. quality ends   only when ql == L; else the step is skipped for the read and the read is counted (stats [13]).  v(i) = q[i] - qual_base.
+ *                     3' end, qual3 > 0: walk i = L-1 down to 0 with sum += qual3 - v(i); stop at the first sum < 0; b = the i at which sum first reached its
+ *                     strict maximum > 0, or L when it never did.  5' end, qual5 > 0: the mirror walk from i = 0; a = i + 1 at the first strict maximum, or 0.
+ *                     Both walks see the whole read.  a >= b: the window is empty (a = b = 0; its bases count as cut by the 5' rule up to a, the rest by the 3').
+ *   2. adapter        of the read's mate: adapter 0 for reads of text 1, adapter 1 for reads of text 2; in one text, adapter 1 for the odd reads when
+ *                     DG_TRIM_PAIRS is set (an interleaved pair text), adapter 0 otherwise.  A length of 0: none.  For p = a .. b - min_overlap ascending:
+ *                     n = min(b - p, alen), m = the number of i < n with s[p+i] != A[i]; the first p with m * 1000 <= n * max_err_permille sets b = p.
+ *                     Hamming distance only, no indels: a stated limit.
+ *   3. poly tails     for each base c in poly_mask the suffix scores S(i) = sum over j = i .. b-1 of (s[j] == c ? +1 : -2), a <= i < b; i* = the smallest i
+ *                     with the maximal S; the tail counts when S(i*) > 0 and b - i* >= poly_min; b becomes the smallest counting i* over the enabled bases.
+ *   4. length         a read fails when b - a < min_len.  With DG_TRIM_PAIRS reads 2k and 2k+1 are kept or dropped together (a last read without partner
+ *                     stands alone).  Kept reads keep their order; the batch is the kept reads, compacted.
+ * The stored read is s[a..b), the stored quality q[a..min(b, ql)) (empty when a >= ql), the name unchanged.  Errors of the plain upload keep their meaning on
+ * the untrimmed record (a record without bases, a read longer than DG_MAX_RLEN, the count rules of two texts, max_reads against the input count).  A batch of
+ * which nothing is left is DG_OK with 0 reads.
+ *   dg_set_trim           NULL: off.  Per context, not inherited by dg_clone.  From then on dg_batch_upload_fastq and dg_batch_upload_fastq_bgzf trim (tails,
+ *                         n_unlike and DG_FQ_CHECK_ONLY of the latter stay as they are); *n_reads is the kept count; dg_batch_download_reads, the resident
+ *                         formatters and every later stage see the trimmed, compacted batch.  The upload still waits once; the trimmed path has kernels of its
+ *                         own (dg_trim.h), the plain path keeps its launches.  DG_ERR_ARG with a text, the context usable and its setting as it was: any flag
+ *                         bit but DG_TRIM_PAIRS, an adapter longer than 64 bases or with a byte outside ACGT, min_len == 0, min_overlap == 0,
+ *                         max_err_permille > 1000, a poly_mask bit above 3, qual3 / qual5 / qual_base above 255.
+ *   dg_batch_trim_stats   of the last upload (zeros when it did not trim): [0] reads in, [1] reads kept, [2] bases in, [3] bases kept, [4] bases cut by the 5'
+ *                         quality rule, [5] by the 3' quality rule, [6] reads with adapter 0 found, [7] with adapter 1, [8] adapter bases cut, [9] reads with a
+ *                         poly tail, [10] poly bases cut, [11] reads that failed the length on their own, [12] reads dropped because the mate failed, [13] reads
+ *                         not quality-trimmed because ql < L, [14], [15] zero.  Integer sums: the same whatever the grid.  *device_ms (may be NULL): the
+ *                         trimming kernels' device time alone (dg_batch_fastq_device_ms includes them), a measurement.
+ *   dg_trim_granules      [0] reads per workgroup of the length kernel, [1] start positions (and walk steps) per round of the cutting kernel: tests place
+ *                         drops and read lengths on these seams                                                                                        */
+#define DG_TRIM_PAIRS 1u      /* reads 2k and 2k+1 are mates: kept or dropped together; in one text the odd reads take adapter 1 */
+typedef struct {
+    uint32_t flags;                         /* DG_TRIM_PAIRS */
+    uint32_t qual3, qual5, qual_base;       /* 0 = off; base 33 */
+    uint32_t min_overlap, max_err_permille; /* 3, 100 */
+    uint32_t poly_mask, poly_min;           /* bit 0..3 = A C G T; 10 */
+    uint32_t min_len;                       /* >= 1 */
+    uint32_t n_adapter[2]; char adapter[2][64];  /* ACGT only */
+} dg_trim;
+int dg_set_trim(dg_ctx *, const dg_trim *);
+int dg_batch_trim_stats(dg_ctx *, uint64_t stats[16], float *device_ms);
+int dg_trim_granules(int out[2]);
+
 /* ---- the splice-junction table on the device: count, sort and print in HBM (replaces UpdateLocalSJMap / UpdateGlobalSJMap, Mapping.cpp:532-577, and
  * OutputSpliceJunctions, Mapping.cpp:683-716) ----
  * Every context owns a table (g1, g2) -> count that stays in HBM across batches: an open-addressing hash table keyed by the full 128 bits, grown by the
