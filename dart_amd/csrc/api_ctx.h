@@ -95,6 +95,14 @@ struct FqState {
 // stats / ms: of the last upload (zeros when it did not trim)
 struct TrimState {
     bool on = false; TrimPar par = {};
+    bool umi_on = false; dg_umi umi = {};      // dg_set_umi: alone it takes the trimmed path with every step off and min_len 1
+    bool any() const { return on || umi_on; }
+    TrimPar effective() const {
+        TrimPar p = par;
+        if (!on) { p = TrimPar{}; p.qual_base = 33; p.min_overlap = 1; p.min_len = 1; }
+        if (umi_on) { p.umi_on = 1; p.umi_flags = umi.flags; p.umi_sep = (unsigned char)umi.sep; for (int i = 0; i < 2; i++) { p.umi_len[i] = umi.len[i]; p.umi_skip[i] = umi.skip[i]; } }
+        return p;
+    }
     DBuf<TrimRead> win;
     DevStat<TrimInfo, 1> info;
     EvSet<2> ev;                               // around the trimming kernels
@@ -181,6 +189,16 @@ struct MdState {
     EvSet<10> ev;
     float ms[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; int passes = 0;
     int hash_bits = MD_HASH_BITS;   // DG_MARKDUP_HASH_BITS: test hook, the bits of a name's hash that are kept (makes collisions and crowded runs reachable)
+    hipError_t ready() { const hipError_t e = stat.ready(); return e != hipSuccess ? e : ev.ready(); }
+};
+// UMI-aware duplicate marking (dg_umidup.h): works in MdState's buffers (the two calls never run at once on a context) and holds what it needs beside them:
+// per record U; per item of the list in hand (pairs, then ends) its mark, group, the groups' places, the families' first groups, the winners, the work list
+struct UdState {
+    DBuf<uint64_t> U, part, tile_h, tile_w;
+    DBuf<uint32_t> mark, grp_of, gpos, ffirst, woff, wl; DBuf<unsigned char> win;
+    DevStat<unsigned long long, UD_ST_WORDS> stat;      // UD_ST_* words
+    EvSet<15> ev;
+    float ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; int passes = 0;
     hipError_t ready() { const hipError_t e = stat.ready(); return e != hipSuccess ? e : ev.ready(); }
 };
 // the allele counts of the sorted array (dg_pileup.h): buffers of its own: per record the event offsets, per event the sorter's pairs, the two scanned planes,

@@ -21,6 +21,7 @@
 #include "dg_bamidx.h"
 #include "dg_coverage.h"
 #include "dg_markdup.h"
+#include "dg_umidup.h"
 #include "dg_pileup.h"
 #include "dg_qc.h"
 #include "dg_tags.h"
@@ -163,7 +164,7 @@ struct dg_ctx {
     bool batch_done = false;       // the batch on the context has been run and waited for
     bool no_batch = false;         // the last upload was a DG_FQ_CHECK_ONLY: there is nothing to run
     // the library stages' state, one struct each (api_ctx.h); every stage's section of this file drives its own
-    SamState sam; FqState fq; TrimState tr; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; PuState pu; QcState qc; TgState tg; GcState gc; RmState rm; TxState tx;
+    SamState sam; FqState fq; TrimState tr; InfState inf; BamState bam; SjState sj; BsState bs; BiState bi; CvState cv; MdState md; UdState ud; PuState pu; QcState qc; TgState tg; GcState gc; RmState rm; TxState tx;
     bool want_full = true, full_valid = false;          // the full record types of the units k_pair finishes: written by this run (dg_map_batch_compact does not want them) / present for the batch that ran last
     int n_cu = 256, runs_of_last_batch = 0, attempt_no = 0;
     // environment switches, read once per context (not per batch)
@@ -1094,7 +1095,7 @@ struct FqPlan { size_t n[2], off2, line_cap[2], tile_stride, reads_bound, len_ti
 static int fq_reserve(dg_ctx *c, FqPlan &p)
 {
     HIPCHK(c->fq.ready());
-    if (c->tr.on) HIPCHK(c->tr.ready());
+    if (c->tr.any()) HIPCHK(c->tr.ready());
     // a record has at least one byte per existing line, so a text of n bytes holds at most n + 1 line starts; the three outputs together are never larger
     // than the texts
     const size_t max_reads = p.max_reads, n1 = p.n[0], n2 = p.n[1];
@@ -1108,8 +1109,9 @@ static int fq_reserve(dg_ctx *c, FqPlan &p)
     const size_t reads_bound = p.reads_bound, text_bytes = p.text_bytes;
     HIPCHK(c->fq.text.ensure(p.off2 + n2 + 32)); HIPCHK(c->fq.lines.ensure(p.line_cap[0] + p.line_cap[1] + 2)); HIPCHK(c->fq.tile_cnt.ensure(2 * p.tile_stride + 1));
     HIPCHK(c->fq.name_at.ensure(reads_bound + 1)); HIPCHK(c->fq.name_len.ensure(reads_bound + 1)); HIPCHK(c->fq.loc.ensure(4 * (reads_bound + 1))); HIPCHK(c->fq.tile_sum.ensure(4 * p.len_tiles));      // (the fourth row: the trimmed path's keep flags)
-    if (c->tr.on) HIPCHK(c->tr.win.ensure(reads_bound + 1));
-    HIPCHK(c->fq.hdr_off.ensure(reads_bound + 1)); HIPCHK(c->fq.qual_off.ensure(reads_bound + 1)); HIPCHK(c->fq.hdr.ensure(text_bytes + 1)); HIPCHK(c->fq.qual.ensure(text_bytes + 1));
+    if (c->tr.any()) HIPCHK(c->tr.win.ensure(reads_bound + 1));
+    HIPCHK(c->fq.hdr_off.ensure(reads_bound + 1)); HIPCHK(c->fq.qual_off.ensure(reads_bound + 1)); HIPCHK(c->fq.qual.ensure(text_bytes + 1));
+    HIPCHK(c->fq.hdr.ensure(text_bytes + 1 + (c->tr.umi_on ? 22 * (reads_bound + 1) : 0)));      // (dg_set_umi: a name gains the separator and at most 21 letters)
     HIPCHK(c->seq.ensure(text_bytes + 64)); HIPCHK(c->seq_off.ensure(reads_bound + 1)); HIPCHK(c->rlen.ensure(reads_bound + 1));
     return DG_OK;
 }
@@ -1118,16 +1120,20 @@ static int fq_reserve(dg_ctx *c, FqPlan &p)
 static int fq_enqueue_trimmed(dg_ctx *c, const FqPlan &p, const FqText &x, int rc_odd_reads, bool write)
 {
     const uint32_t stride = (uint32_t)(p.reads_bound + 1);
+    const TrimPar par = c->tr.effective();
     HIPCHK(hipMemsetAsync(c->tr.info.d, 0, sizeof(TrimInfo), c->stream));
     HIPCHK(hipEventRecord(c->tr.ev[0], c->stream));
-    if (p.reads_bound) k_trim_cut<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d, c->tr.par, c->tr.win.p);
-    k_trim_len<<<(unsigned)p.len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->fq.info.d, c->tr.par, c->tr.win.p, c->tr.info.d, c->fq.name_at.p, c->fq.name_len.p, c->fq.loc.p, stride, c->fq.tile_sum.p,
+    if (p.reads_bound) k_trim_cut<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d, par, c->tr.win.p);
+    k_trim_len<<<(unsigned)p.len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->fq.info.d, par, c->tr.win.p, c->tr.info.d, c->fq.name_at.p, c->fq.name_len.p, c->fq.loc.p, stride, c->fq.tile_sum.p,
                                                                      (uint32_t)p.len_tiles);
     k_trim_top3<<<1, FQ_THREADS, 0, c->stream>>>(c->fq.tile_sum.p, (uint32_t)p.len_tiles, c->fq.info.d, c->tr.info.d);
     if (p.reads_bound && write)
         k_trim_write<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d, c->tr.info.d, rc_odd_reads ? 1 : 0, c->tr.win.p, c->fq.name_at.p, c->fq.name_len.p, c->fq.loc.p, stride,
                                                                      c->fq.tile_sum.p, (uint32_t)p.len_tiles, c->rlen.p, c->seq_off.p, c->seq.p, c->fq.hdr_off.p, c->fq.hdr.p, c->fq.qual_off.p,
                                                                      c->fq.qual.p);
+    if (p.reads_bound && write && par.umi_on)
+        k_trim_umi_name<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d, TrimUmi{par.umi_on, par.umi_flags, {par.umi_len[0], par.umi_len[1]}, par.umi_sep}, c->tr.win.p, c->fq.name_len.p,
+                                                                        c->fq.loc.p, stride, c->fq.tile_sum.p, (uint32_t)p.len_tiles, c->fq.hdr.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(c->tr.ev[1], c->stream));
     HIPCHK(hipEventRecord(c->fq.ev[1], c->stream));
@@ -1151,7 +1157,7 @@ static int fq_enqueue(dg_ctx *c, const FqPlan &p, int rc_odd_reads, bool whole, 
     k_fq_lines<<<text_grid, FQ_THREADS, 0, c->stream>>>(x, c->fq.tile_cnt.p, (uint32_t)p.tile_stride, c->fq.info.d);
     if (whole) k_fq_tail<<<dim3(64, p.two ? 2u : 1u), FQ_THREADS, 0, c->stream>>>(x, c->fq.info.d, c->fq.tail.p, (uint32_t)c->fq.tail_off2);
     if (pieces && p.reads_bound) k_fq_unlike<<<(unsigned)p.reads_bound, 64, 0, c->stream>>>(x, c->fq.info.d);
-    if (c->tr.on) return fq_enqueue_trimmed(c, p, x, rc_odd_reads, write);
+    if (c->tr.any()) return fq_enqueue_trimmed(c, p, x, rc_odd_reads, write);
     k_fq_len<<<(unsigned)p.len_tiles, FQ_THREADS, 0, c->stream>>>(x, c->fq.info.d, c->rlen.p, c->fq.name_at.p, c->fq.name_len.p, c->fq.loc.p, stride, c->fq.tile_sum.p, (uint32_t)p.len_tiles);
     k_fq_top3<<<1, FQ_THREADS, 0, c->stream>>>(c->fq.tile_sum.p, (uint32_t)p.len_tiles, c->fq.info.d);
     if (p.reads_bound && write)
@@ -1422,6 +1428,19 @@ extern "C" int dg_set_trim(dg_ctx *c, const dg_trim *t)
     par.flags = t->flags; par.qual3 = t->qual3; par.qual5 = t->qual5; par.qual_base = t->qual_base; par.min_overlap = t->min_overlap; par.max_err_permille = t->max_err_permille;
     par.poly_mask = t->poly_mask; par.poly_min = t->poly_min; par.min_len = t->min_len;
     c->tr.par = par; c->tr.on = true;
+    return DG_OK;
+}
+
+extern "C" int dg_set_umi(dg_ctx *c, const dg_umi *u)
+{
+    if (!c) return DG_ERR_ARG;
+    if (!u) { c->tr.umi_on = false; return DG_OK; }
+    if (u->flags & ~DG_UMI_PAIRS) { snprintf(c->err, 512, "dg_set_umi: unknown flag bits 0x%x", u->flags & ~DG_UMI_PAIRS); return DG_ERR_ARG; }
+    if ((uint64_t)u->len[0] + u->len[1] == 0 || (uint64_t)u->len[0] + u->len[1] > UD_MAX_LEN) { snprintf(c->err, 512, "dg_set_umi: the two lengths together are %llu, not 1..%d", (unsigned long long)u->len[0] + u->len[1], UD_MAX_LEN); return DG_ERR_ARG; }
+    for (int m = 0; m < 2; m++)
+        if ((uint64_t)u->len[m] + u->skip[m] > (uint64_t)DG_MAX_RLEN) { snprintf(c->err, 512, "dg_set_umi: len[%d] + skip[%d] is %llu, above %d", m, m, (unsigned long long)u->len[m] + u->skip[m], DG_MAX_RLEN); return DG_ERR_ARG; }
+    if (u->sep == 0 || u->sep == ' ' || u->sep == '\t' || u->sep == '/' || ud_code((unsigned char)u->sep)) { snprintf(c->err, 512, "dg_set_umi: the separator 0x%02x is NUL, a blank, a tab, '/' or one of ACGTN+-", (unsigned char)u->sep); return DG_ERR_ARG; }
+    c->tr.umi = *u; c->tr.umi_on = true;
     return DG_OK;
 }
 
@@ -4555,6 +4574,186 @@ extern "C" int dg_bam_markdup_device_ms(dg_ctx *c, float ms[6], int *n_passes)
     if (!c || !ms) return DG_ERR_ARG;
     for (int k = 0; k < 6; k++) ms[k] = c->md.ms[k];
     if (n_passes) *n_passes = c->md.passes;
+    return DG_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// UMI-aware duplicate marking of the sorted array (dg_umidup.h): dg_markdup.h's record rules, mate search and lists; U as one more sort key; groups, families,
+// clusters and the flag writes are this stage's own kernels
+// ------------------------------------------------------------------------------------------
+extern "C" int dg_bam_markdup_umi_granules(int out[4])
+{
+    if (!out) return DG_ERR_ARG;
+    out[0] = MD_THREADS; out[1] = RS_TILE; out[2] = MD_CROWD; out[3] = UD_FAMILY;
+    return DG_OK;
+}
+
+// One sorted list (pairs: ends = 0, keys = lo; ends: ends = 1, keys = E) from its heads to its flags.  st: the list's UD_L_* words on the device; ev0: the first
+// of its three events, which follow the event behind whatever ran in front of it
+static int ud_verdicts(dg_ctx *c, const char *fn, const BsView &sv, const uint64_t *keys, const int64_t *vals, uint32_t n_items, int ends, uint32_t max_edit, int write,
+                       unsigned long long *st, int ev0)
+{
+    UdState &u = c->ud;
+    const uint32_t n = (uint32_t)sv.n, tiles = (n_items + MD_THREADS - 1) / MD_THREADS, wtiles = std::min<uint32_t>(tiles, 4u * (uint32_t)std::max(c->n_cu, 1));      // k_ud_cluster: 4 waves per workgroup, a few workgroups per CU at the most; a wave strides over the work list
+    BS_ENSURE(u.mark, n_items, "the items' marks"); BS_ENSURE(u.grp_of, n_items, "the items' groups"); BS_ENSURE(u.gpos, (size_t)n_items + 1, "the groups' places");
+    BS_ENSURE(u.ffirst, (size_t)n_items + 1, "the families' first groups"); BS_ENSURE(u.win, n_items, "the groups' winners"); BS_ENSURE(u.woff, n_items, "the families' offsets");
+    BS_ENSURE(u.wl, (size_t)n_items / 2 + 1, "the work list"); BS_ENSURE(u.tile_h, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(u.tile_w, (size_t)tiles + 1, "the per-workgroup sums");
+    k_ud_heads<<<tiles, MD_THREADS, 0, c->stream>>>(keys, vals, n_items, ends, c->md.E.p, c->md.mate.p, u.U.p, u.mark.p, u.tile_h.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(u.tile_h.p, tiles, st + UD_L_HEADS, nullptr, 0, 0, nullptr);
+    k_ud_groups<<<tiles, MD_THREADS, 0, c->stream>>>(u.mark.p, u.tile_h.p, n_items, u.grp_of.p, u.gpos.p, u.ffirst.p, u.win.p);
+    k_ud_fams<<<tiles, MD_THREADS, 0, c->stream>>>(u.ffirst.p, st + UD_L_HEADS, n_items, max_edit, u.woff.p, u.tile_w.p, u.part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(u.tile_w.p, tiles, st + UD_L_WORK, u.part.p, 2, 2, st + UD_L_MULTI);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(u.ev[ev0 + 0], c->stream));
+    if (max_edit) {
+        k_ud_worklist<<<tiles, MD_THREADS, 0, c->stream>>>(u.woff.p, u.tile_w.p, n_items, u.wl.p);
+        k_ud_cluster<<<wtiles, MD_THREADS, 0, c->stream>>>(u.wl.p, st + UD_L_WORK, u.ffirst.p, u.gpos.p, vals, n_items, ends, u.U.p, c->md.score.p, c->md.mate.p, n, u.win.p, u.part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.junk.p, wtiles, c->ud.stat.d + UD_ST_JUNK, u.part.p, 2, 1, st + UD_L_ABSORBED);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(u.ev[ev0 + 1], c->stream));
+    k_ud_flag<<<tiles, MD_THREADS, 0, c->stream>>>(vals, n_items, ends, u.grp_of.p, u.gpos.p, u.win.p, c->md.mate.p, sv.rec, sv.dst_off, sv.tile, n, (unsigned long long)sv.n_raw, write, u.part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.junk.p, tiles, c->ud.stat.d + UD_ST_JUNK, u.part.p, 2, 1, st + UD_L_DUP);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(u.ev[ev0 + 2], c->stream));
+    return DG_OK;
+}
+
+extern "C" int dg_bam_markdup_umi_finish(dg_ctx *c, const dg_umi_rules *rules, uint32_t flags, uint64_t stats[12], float *device_ms)
+{
+    if (!c) return DG_ERR_ARG;
+    const char *fn = "dg_bam_markdup_umi_finish";
+    if (device_ms) *device_ms = 0.f;
+    if (stats) for (int k = 0; k < 12; k++) stats[k] = 0;
+    UdState &u = c->ud;
+    u.passes = 0;
+    for (float &m : u.ms) m = 0.f;
+    BsView sv;
+    { const int rc = bs_view(c, fn, sv); if (rc) return rc; }
+    if (flags & ~DG_MD_COUNT_ONLY) { snprintf(c->err, 512, "%s: flags 0x%x hold a bit that is not DG_MD_COUNT_ONLY", fn, flags); return DG_ERR_ARG; }
+    if (!rules) { snprintf(c->err, 512, "%s: no rules", fn); return DG_ERR_ARG; }
+    if (rules->flags) { snprintf(c->err, 512, "%s: rules->flags 0x%x: no bit is defined", fn, rules->flags); return DG_ERR_ARG; }
+    if (rules->max_edit > 1u) { snprintf(c->err, 512, "%s: max_edit %u: 0 (exact) or 1", fn, rules->max_edit); return DG_ERR_ARG; }
+    if (rules->sep == 0) { snprintf(c->err, 512, "%s: the separator is the NUL byte", fn); return DG_ERR_ARG; }
+    const int write = (flags & DG_MD_COUNT_ONLY) ? 0 : 1;
+    const uint32_t max_edit = rules->max_edit;
+    HIPCHK(c->md.ready()); HIPCHK(u.ready());
+    const size_t n = sv.n, n_raw = sv.n_raw;
+    const int n_chr = sv.n_chr, hash_bits = c->md.hash_bits;
+    if (n_chr < 1) { snprintf(c->err, 512, "%s: %d chromosomes", fn, n_chr); return DG_ERR_ARG; }
+    if (!n) return DG_OK;
+    const uint32_t tiles = (uint32_t)((n + MD_THREADS - 1) / MD_THREADS);
+    BS_ENSURE(c->md.E, n, "the records' end keys"); BS_ENSURE(c->md.h, n, "the names' hashes"); BS_ENSURE(c->md.score, n, "the records' scores"); BS_ENSURE(c->md.mate, n, "the records' partners");
+    BS_ENSURE(c->md.cand_off, n, "the candidates' offsets"); BS_ENSURE(c->md.cnt_off, n, "the pairs' and ends' offsets"); BS_ENSURE(u.U, n, "the records' UMIs");
+    BS_ENSURE(c->md.tile, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(c->md.junk, (size_t)tiles + 1, "the per-workgroup sums"); BS_ENSURE(c->md.part, 2 * (size_t)tiles, "the per-workgroup values");
+    BS_ENSURE(u.part, 4 * (size_t)tiles + 4, "the per-workgroup values");
+    HIPCHK(hipMemsetAsync(u.stat.d, 0, UD_ST_WORDS * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->md.junk.p, 0, ((size_t)tiles + 1) * 8, c->stream));
+    HIPCHK(hipEventRecord(u.ev[0], c->stream));
+    k_ud_rec<<<tiles, MD_THREADS, 0, c->stream>>>(sv.rec, sv.dst_off, sv.tile, (uint32_t)n, (unsigned long long)n_raw, n_chr, hash_bits, (unsigned char)rules->sep, c->md.E.p, c->md.h.p, u.U.p,
+                                                  c->md.score.p, c->md.mate.p, c->md.cand_off.p, c->md.tile.p, u.part.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.tile.p, tiles, u.stat.d + UD_ST_CAND, u.part.p, 4, 2, u.stat.d + UD_ST_EXAMINED);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(u.ev[1], c->stream));
+    HIPCHK(u.stat.fetch(c->stream));
+    HIPCHK(wait_stream(c));                                       // the first wait: how many candidates, what was out of range, and the largest U
+    if (u.stat.h[UD_ST_NBAD]) {
+        snprintf(c->err, 512, "%s: record %llu of the sorted array has an unclipped 5' end outside [-2^31, 3 * 2^31): an end key cannot hold it; nothing was written", fn, ~u.stat.h[UD_ST_NBAD]);
+        return DG_ERR_RANGE;
+    }
+    const size_t n_cand = (size_t)u.stat.h[UD_ST_CAND], n_examined = (size_t)u.stat.h[UD_ST_EXAMINED], n_umi = (size_t)u.stat.h[UD_ST_WITH_UMI];
+    const int umi_bits = ud_umi_bits(u.stat.h[UD_ST_UMAX]);
+    if (n_cand > n || n_examined > n || n_umi > n_examined) { snprintf(c->err, 512, "%s: %zu candidates, %zu examined records and %zu with a UMI of %zu", fn, n_cand, n_examined, n_umi, n); return DG_ERR_INTERNAL; }
+    const uint32_t ctiles = (uint32_t)((n_cand + MD_THREADS - 1) / MD_THREADS);
+    SortBufs &ps = c->md.sort, &es = c->md.esort;          // candidates, then pairs / ends
+    int which = 0;
+    if (n_cand) {
+        for (int k = 0; k < 2; k++) { BS_ENSURE(ps.k[k], n_cand, "the sorter's keys"); BS_ENSURE(ps.v[k], n_cand, "the sorter's values"); }
+        BS_ENSURE_SORT(ps, (uint32_t)n_cand);
+    }
+    HIPCHK(hipEventRecord(u.ev[2], c->stream));
+    if (n_cand) {
+        k_md_compact<<<tiles, MD_THREADS, 0, c->stream>>>(c->md.cand_off.p, c->md.tile.p, c->md.h.p, (uint32_t)n, (uint32_t)n_cand, ps.k[0].p, ps.v[0].p);
+        { const int rc = ps.sort(c, (uint32_t)n_cand, hash_bits, which); if (rc) return rc; }
+        u.passes += (hash_bits + 3) / 4;
+        k_md_mate<<<ctiles, MD_THREADS, 0, c->stream>>>(ps.k[which].p, ps.v[which].p, (uint32_t)n_cand, (uint32_t)n, sv.rec, sv.dst_off, sv.tile, c->md.mate.p, c->md.part.p);
+        k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.junk.p, ctiles, u.stat.d + UD_ST_JUNK, c->md.part.p, 1, 1, u.stat.d + UD_ST_CROWDED);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(u.ev[3], c->stream));
+    k_md_count<<<tiles, MD_THREADS, 0, c->stream>>>(c->md.mate.p, (uint32_t)n, c->md.cnt_off.p, c->md.tile.p);
+    k_cv_top<<<1, CV_THREADS, 0, c->stream>>>(c->md.tile.p, tiles, u.stat.d + UD_ST_COUNTS, nullptr, 0, 0, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(u.ev[4], c->stream));
+    HIPCHK(u.stat.fetch(c->stream));
+    HIPCHK(wait_stream(c));                                       // the second wait: how many pairs and ends
+    const size_t n_pairs = (size_t)(u.stat.h[UD_ST_COUNTS] >> 32), n_ends = (size_t)(uint32_t)u.stat.h[UD_ST_COUNTS], n_crowded = (size_t)u.stat.h[UD_ST_CROWDED];
+    if (2 * n_pairs > n_cand || n_ends != n_examined) { snprintf(c->err, 512, "%s: %zu pairs of %zu candidates, %zu ends of %zu examined records", fn, n_pairs, n_cand, n_ends, n_examined); return DG_ERR_INTERNAL; }
+    const uint32_t ptiles = (uint32_t)((n_pairs + MD_THREADS - 1) / MD_THREADS), etiles = (uint32_t)((n_ends + MD_THREADS - 1) / MD_THREADS);
+    if (n_ends) {
+        for (int k = 0; k < 2; k++) { BS_ENSURE(es.k[k], n_ends, "the ends' keys"); BS_ENSURE(es.v[k], n_ends, "the ends' values"); }
+        BS_ENSURE_SORT(es, (uint32_t)n_ends);
+    }
+    const int e_bits = md_e_bits(n_chr);
+    int pw = 0, ew = 0;
+    HIPCHK(hipEventRecord(u.ev[5], c->stream));
+    if (n_ends) k_md_emit<<<tiles, MD_THREADS, 0, c->stream>>>(c->md.mate.p, c->md.score.p, c->md.cnt_off.p, c->md.tile.p, (uint32_t)n, (uint32_t)n_pairs, (uint32_t)n_ends, ps.k[0].p, ps.v[0].p, es.k[0].p, es.v[0].p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(u.ev[6], c->stream));
+    if (n_pairs) {                                                // (lo, hi, U, score descending, rep)
+        { const int rc = ps.sort(c, (uint32_t)n_pairs, MD_SCORE_BITS, pw); if (rc) return rc; }
+        if (umi_bits) {
+            k_ud_rekey_u<<<ptiles, MD_THREADS, 0, c->stream>>>(ps.k[pw].p, ps.v[pw].p, (uint32_t)n_pairs, u.U.p, (uint32_t)n);
+            { const int rc = ps.sort(c, (uint32_t)n_pairs, umi_bits, pw); if (rc) return rc; }
+        }
+        k_md_rekey<<<ptiles, MD_THREADS, 0, c->stream>>>(ps.k[pw].p, ps.v[pw].p, (uint32_t)n_pairs, 0, c->md.E.p, c->md.mate.p, (uint32_t)n);
+        { const int rc = ps.sort(c, (uint32_t)n_pairs, e_bits, pw); if (rc) return rc; }
+        k_md_rekey<<<ptiles, MD_THREADS, 0, c->stream>>>(ps.k[pw].p, ps.v[pw].p, (uint32_t)n_pairs, 1, c->md.E.p, c->md.mate.p, (uint32_t)n);
+        { const int rc = ps.sort(c, (uint32_t)n_pairs, e_bits, pw); if (rc) return rc; }
+        u.passes += (MD_SCORE_BITS + 3) / 4 + (umi_bits + 3) / 4 + 2 * ((e_bits + 3) / 4);
+    }
+    HIPCHK(hipEventRecord(u.ev[7], c->stream));
+    if (n_ends) {                                                 // (E, U, paired first, score descending, index)
+        { const int rc = es.sort(c, (uint32_t)n_ends, MD_SCORE_BITS, ew); if (rc) return rc; }
+        if (umi_bits) {
+            k_ud_rekey_u<<<etiles, MD_THREADS, 0, c->stream>>>(es.k[ew].p, es.v[ew].p, (uint32_t)n_ends, u.U.p, (uint32_t)n);
+            { const int rc = es.sort(c, (uint32_t)n_ends, umi_bits, ew); if (rc) return rc; }
+        }
+        k_md_rekey<<<etiles, MD_THREADS, 0, c->stream>>>(es.k[ew].p, es.v[ew].p, (uint32_t)n_ends, 2, c->md.E.p, c->md.mate.p, (uint32_t)n);
+        { const int rc = es.sort(c, (uint32_t)n_ends, e_bits, ew); if (rc) return rc; }
+        u.passes += (MD_SCORE_BITS + 3) / 4 + (umi_bits + 3) / 4 + (e_bits + 3) / 4;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(u.ev[8], c->stream));
+    // (the events of a list that is empty are recorded all the same: the stages' times stay defined)
+    if (n_pairs) { const int rc = ud_verdicts(c, fn, sv, ps.k[pw].p, ps.v[pw].p, (uint32_t)n_pairs, 0, max_edit, write, u.stat.d + UD_ST_PAIRS, 9); if (rc) return rc; }
+    else for (int k = 9; k < 12; k++) HIPCHK(hipEventRecord(u.ev[k], c->stream));
+    if (n_ends) { const int rc = ud_verdicts(c, fn, sv, es.k[ew].p, es.v[ew].p, (uint32_t)n_ends, 1, max_edit, write, u.stat.d + UD_ST_ENDS, 12); if (rc) return rc; }
+    else for (int k = 12; k < 15; k++) HIPCHK(hipEventRecord(u.ev[k], c->stream));
+    if (write && n_ends) bs_array_changed(c);                     // bytes of the array changed: as behind dg_bam_markdup_finish
+    HIPCHK(u.stat.fetch(c->stream));
+    HIPCHK(wait_stream(c));                                       // the third wait: the counts
+    float t[14];
+    for (int k = 0; k < 14; k++) t[k] = u.ev.ms(k, k + 1);
+    u.ms[0] = t[0]; u.ms[1] = t[2]; u.ms[2] = t[6]; u.ms[3] = t[7]; u.ms[4] = t[8] + t[11]; u.ms[5] = t[9] + t[12]; u.ms[6] = t[10] + t[13]; u.ms[7] = t[3] + t[5];
+    float total = 0.f;
+    for (float m : u.ms) total += m;
+    if (device_ms) *device_ms = total;
+    const unsigned long long *P = u.stat.h + UD_ST_PAIRS, *Q = u.stat.h + UD_ST_ENDS;
+    const uint64_t dup_pairs = P[UD_L_DUP], dup_frags = Q[UD_L_DUP];
+    if (stats) {
+        stats[0] = n_examined; stats[1] = n_pairs; stats[2] = n_examined - 2 * n_pairs; stats[3] = dup_pairs; stats[4] = dup_frags; stats[5] = n_crowded;
+        stats[6] = 2 * dup_pairs + dup_frags; stats[7] = P[UD_L_CLUSTER_MAX] > P[UD_L_GROUP_MAX] ? P[UD_L_CLUSTER_MAX] : P[UD_L_GROUP_MAX];
+        stats[8] = n_umi; stats[9] = P[UD_L_MULTI]; stats[10] = P[UD_L_ABSORBED] + Q[UD_L_ABSORBED]; stats[11] = P[UD_L_CROWDED] + Q[UD_L_CROWDED];
+    }
+    return DG_OK;
+}
+
+extern "C" int dg_bam_markdup_umi_device_ms(dg_ctx *c, float ms[8], int *n_passes)
+{
+    if (!c || !ms) return DG_ERR_ARG;
+    for (int k = 0; k < 8; k++) ms[k] = c->ud.ms[k];
+    if (n_passes) *n_passes = c->ud.passes;
     return DG_OK;
 }
 

@@ -28,7 +28,8 @@
 //   with equal (lo, hi) the one with the largest score survives, on equal scores the one with the smallest rep; both records of every other pair get 0x400.
 // Fragments.  A fragment with end key E is a duplicate when any pair has lo == E or hi == E, or when another fragment with the same E has a larger score, or
 //   an equal score and a smaller index.
-// Optical duplicates, UMIs and the propagation to secondary or supplementary records are not done.
+// Optical duplicates and the propagation to secondary or supplementary records are not done; UMIs are dg_umidup.h's (dg_bam_markdup_umi_finish), which reuses
+// every function below.
 // The verdict is a function of the sorted array alone, and that array is a function of the record set and the ordinals (dg_bamsort.h).
 //
 //   k_md_rec         lane = sorted record: the filter, the CIGAR walk, the quality sum, the name's hash: E, score, h, the class (in `mate`: not examined /
@@ -89,11 +90,12 @@ MD_HD uint64_t md_hash(const unsigned char *name, uint32_t len, int hash_bits)
 MD_HD uint32_t md_name_len(const BamHead &h) { return h.l_name ? h.l_name - 1u : 0u; }
 MD_HD uint32_t md_name_len(const unsigned char *rec) { return md_name_len(bam_head(rec, BAM_FIXED)); }      // (of an examined record: its fixed part lies inside the array)
 MD_HD int md_e_bits(int n_chr) { return 34 + bs_chr_bits(n_chr); }
-// the record that starts (with its block_size) at rec, `avail` bytes of the array behind rec
-MD_HD MdRec md_record(const unsigned char *rec, uint64_t avail, int n_chr, int hash_bits)
+// the record that starts (with its block_size) at rec, `avail` bytes of the array behind rec: everything but the name's hash (h stays 0); hd: its fixed fields
+MD_HD MdRec md_record_fields(const unsigned char *rec, uint64_t avail, int n_chr, BamHead &hd)
 {
     MdRec r; r.examined = false; r.candidate = false; r.bad = false; r.E = 0; r.h = 0; r.score = 0;
-    const BamHead h = bam_head(rec, avail);
+    hd = bam_head(rec, avail);
+    const BamHead &h = hd;
     const int32_t refid = h.refid, pos = h.pos;
     const uint32_t flag = h.flag;
     // examined only when the qualities end inside the record and the array; secondary and supplementary records are left out
@@ -114,6 +116,12 @@ MD_HD MdRec md_record(const unsigned char *rec, uint64_t avail, int n_chr, int h
     for (uint64_t k = 0; k < (uint64_t)h.l_seq; k++) { const uint32_t q = rec[h.qual_at + k]; if (q >= 15u && q <= 93u && score < MD_SCORE_MAX) score += q; }
     r.score = score > MD_SCORE_MAX ? MD_SCORE_MAX : score;
     r.candidate = (flag & 1u) && !(flag & 8u) && ((flag >> 6 & 1u) ^ (flag >> 7 & 1u));
+    return r;
+}
+MD_HD MdRec md_record(const unsigned char *rec, uint64_t avail, int n_chr, int hash_bits)
+{
+    BamHead h;
+    MdRec r = md_record_fields(rec, avail, n_chr, h);
     if (r.candidate) r.h = md_hash(rec + BAM_FIXED, md_name_len(h), hash_bits);
     return r;
 }

@@ -8,6 +8,8 @@
 //   k_trim_len    k_fq_len with the windows: the mate's verdict, a fourth scanned row (the keep flags), the sums of the statistics
 //   k_trim_top3   k_fq_top3 with four rows; the kept count
 //   k_trim_write  k_fq_write with the window and the compacted index; it also writes rlen[] (k_fq_len writes it at the input index)
+// dg_set_umi puts one more cut in front: k_trim_cut starts u bases in, k_trim_len gives the pairwise verdict, the longer name and two sums, and k_trim_umi_name, a
+// launch of its own behind k_trim_write when the rule is set, writes the suffix (inside k_trim_write it cost that kernel 14 spilled SGPRs and a wave of occupancy).
 // The statistics are integer sums, so they -- like the batch -- are the same whatever the grid.
 #ifndef DG_TRIM_H
 #define DG_TRIM_H
@@ -22,10 +24,13 @@ static_assert(DG_MAX_RLEN <= 1024 && (DG_MAX_RLEN * 2 + 64) / 64 + 2 <= TR_WORDS
 struct TrimPar {
     uint32_t flags, qual3, qual5, qual_base, min_overlap, max_err_permille, poly_mask, poly_min, min_len, alen[2];
     uint64_t acode[2][2];
+    uint32_t umi_on, umi_flags, umi_len[2], umi_skip[2], umi_sep;      // dg_set_umi: the inline UMI cut in front of the four steps
 };
+// what of them k_trim_write needs: the name's suffix
+struct TrimUmi { uint32_t on, flags, len[2], sep; };
 // what k_trim_cut leaves per read
 enum { TR_F_ADAPTER = 1, TR_F_ADAPTER1 = 2, TR_F_POLY = 4, TR_F_QSKIP = 8, TR_F_KEEP = 16 };
-struct TrimRead { uint16_t a, b, cut5, cut3, ad_cut, poly_cut, flags, pad; };
+struct TrimRead { uint16_t a, b, cut5, cut3, ad_cut, poly_cut, flags, umi_fail /* the read is too short for its UMI and linker (k_trim_len never writes it: the partner's lane reads it) */; };
 static_assert(sizeof(TrimRead) == 16, "one 16-byte store per read");
 struct TrimInfo { unsigned long long stats[16]; uint32_t n_kept, pad[3]; };
 
@@ -103,6 +108,15 @@ FQ_HD bool trim_long_enough(uint32_t a, uint32_t b, uint32_t min_len) { return b
 // the stored quality's length: q[a .. min(b, ql))
 FQ_HD uint32_t trim_stored_ql(uint32_t a, uint32_t b, uint32_t ql) { const uint32_t e = b < ql ? b : ql; return e > a ? e - a : 0u; }
 
+// ---- the inline UMI (dg_set_umi): cut in front of the four steps, which then work on s[u .. L) ----
+// the slot of a read (as trim_adapter_of picks the adapter); whether reads 2k and 2k + 1 are partners; the bases cut in front; the rule; a stored letter; what a name gains
+FQ_HD int trim_umi_slot(uint32_t k, bool two, int file, uint32_t umi_flags) { return two ? file : ((umi_flags & DG_UMI_PAIRS) ? (int)(k & 1u) : 0); }
+FQ_HD bool trim_umi_partnered(uint32_t k, bool two, uint32_t umi_flags, uint32_t n_reads) { return (two || (umi_flags & DG_UMI_PAIRS)) && (k ^ 1u) < n_reads; }
+FQ_HD uint32_t trim_umi_cut(const TrimPar &p, int slot) { return p.umi_on ? p.umi_len[slot] + p.umi_skip[slot] : 0u; }
+FQ_HD bool trim_umi_ok(uint32_t L, uint32_t u) { return L >= u + 1u; }
+FQ_HD char trim_umi_letter(char ch) { const uint32_t c = trim_code(ch); return c == 0u ? 'A' : c == 1u ? 'C' : c == 2u ? 'G' : c == 3u ? 'T' : 'N'; }
+FQ_HD uint32_t trim_umi_suffix(const TrimPar &p, int slot, bool partnered) { return p.umi_on ? 1u + (partnered ? p.umi_len[0] + p.umi_len[1] : p.umi_len[slot]) : 0u; }
+
 #ifdef __HIPCC__
 // ------------------------------------------------------------------------------------------
 // the kernels
@@ -164,8 +178,11 @@ k_trim_cut(const FqText x, const FqInfo *__restrict__ info, const TrimPar par, T
     const uint32_t l1 = fq_dev_line(x, info, f, 4ull * rec + 1, s1), l3 = fq_dev_line(x, info, f, 4ull * rec + 3, s3);
     TrimRead r = {0, 0, 0, 0, 0, 0, 0, 0};
     if (l1 < 2u || l1 - 1u > (uint32_t)DG_MAX_RLEN) { if (lane == 0) out[k] = r; return; }
-    const uint32_t L = l1 - 1u, ql = L < l3 ? L : l3;
-    const char *line1 = (const char *)x.t[f] + s1, *line3 = (const char *)x.t[f] + s3;
+    // the UMI and its linker leave first: everything below sees s[u .. L) and q[u .. ql); step 1's condition is that of the untouched lengths
+    const uint32_t L0 = l1 - 1u, ql0 = L0 < l3 ? L0 : l3, u = trim_umi_cut(par, trim_umi_slot(k, x.two != 0, f, par.umi_flags));
+    if (!trim_umi_ok(L0, u)) { r.umi_fail = 1; if (lane == 0) out[k] = r; return; }
+    const uint32_t L = L0 - u, ql = ql0 == L0 ? L : (ql0 > u ? ql0 - u : 0u);
+    const char *line1 = (const char *)x.t[f] + s1 + u, *line3 = (const char *)x.t[f] + s3 + u;
     // the read as 2-bit codes and the not-ACGT mask
     for (uint32_t i0 = 0; i0 < L; i0 += 64) {
         const uint32_t c = i0 + lane < L ? trim_code(line1[i0 + lane]) : 4u;
@@ -210,7 +227,7 @@ k_trim_cut(const FqText x, const FqInfo *__restrict__ info, const TrimPar par, T
         if (nb < b) { poly_cut = b - nb; b = nb; flags |= TR_F_POLY; }
     }
     if (lane == 0) {
-        r.a = (uint16_t)a; r.b = (uint16_t)b; r.cut5 = (uint16_t)cut5; r.cut3 = (uint16_t)cut3; r.ad_cut = (uint16_t)ad_cut; r.poly_cut = (uint16_t)poly_cut; r.flags = (uint16_t)flags;
+        r.a = (uint16_t)(a + u); r.b = (uint16_t)(b + u); r.cut5 = (uint16_t)cut5; r.cut3 = (uint16_t)cut3; r.ad_cut = (uint16_t)ad_cut; r.poly_cut = (uint16_t)poly_cut; r.flags = (uint16_t)flags;
         out[k] = r;
     }
 }
@@ -240,14 +257,18 @@ k_trim_len(const FqText x, FqInfo *info, const TrimPar par, TrimRead *__restrict
         name_at[k] = r.name_at; name_len[k] = r.hl;
         if (good) {
             const TrimRead w = win[k];
-            const bool own = trim_long_enough(w.a, w.b, par.min_len);
+            const int slot = trim_umi_slot(k, x.two != 0, f, par.umi_flags);
+            const bool partnered = par.umi_on && trim_umi_partnered(k, x.two != 0, par.umi_flags, n_reads);
+            const bool umi_fail = w.umi_fail != 0, umi_drop = umi_fail || (partnered && win[k ^ 1u].umi_fail != 0);      // the UMI rule is pairwise whatever DG_TRIM_PAIRS says
+            const bool own = trim_long_enough(w.a, w.b, par.min_len) && !umi_fail;
             bool mate = true;
             if ((par.flags & DG_TRIM_PAIRS) && (k ^ 1u) < n_reads) { const TrimRead m = win[k ^ 1u]; mate = trim_long_enough(m.a, m.b, par.min_len); }
-            const bool keep = own && mate;
-            if (keep) { len[0] = (uint32_t)w.b - w.a; len[1] = r.hl; len[2] = trim_stored_ql(w.a, w.b, r.ql); len[3] = 1u; }
+            const bool keep = own && mate && !umi_drop;
+            if (keep) { len[0] = (uint32_t)w.b - w.a; len[1] = r.hl + trim_umi_suffix(par, slot, partnered); len[2] = trim_stored_ql(w.a, w.b, r.ql); len[3] = 1u; }
             st[0] = 1; st[1] = keep; st[2] = (unsigned long long)r.rlen; st[3] = len[0]; st[4] = w.cut5; st[5] = w.cut3;
             st[6] = (w.flags & TR_F_ADAPTER) && !(w.flags & TR_F_ADAPTER1); st[7] = (w.flags & TR_F_ADAPTER) && (w.flags & TR_F_ADAPTER1); st[8] = w.ad_cut;
-            st[9] = (w.flags & TR_F_POLY) != 0; st[10] = w.poly_cut; st[11] = !own; st[12] = own && !mate; st[13] = (w.flags & TR_F_QSKIP) != 0;
+            st[9] = (w.flags & TR_F_POLY) != 0; st[10] = w.poly_cut; st[11] = !umi_drop && !own; st[12] = !umi_drop && own && !mate; st[13] = (w.flags & TR_F_QSKIP) != 0;
+            st[14] = par.umi_on && !umi_fail ? trim_umi_cut(par, slot) : 0u; st[15] = umi_drop;
             if (keep) win[k].flags = (uint16_t)(w.flags | TR_F_KEEP);          // (the mate's lane reads a, b alone)
         }
     }
@@ -261,7 +282,7 @@ k_trim_len(const FqText x, FqInfo *info, const TrimPar par, TrimRead *__restrict
     const uint32_t mx = d_wave_max(len[0]);
     if ((threadIdx.x & 63u) == 0 && mx) atomicMax(&info->max_rlen, mx);
 #pragma unroll
-    for (int i = 0; i < 14; i++) {
+    for (int i = 0; i < 16; i++) {
         const unsigned long long v = d_wave_sum<unsigned long long>(st[i]);
         if ((threadIdx.x & 63u) == 0 && v) atomicAdd(&ti->stats[i], v);
     }
@@ -316,6 +337,32 @@ k_trim_write(const FqText x, const FqInfo *__restrict__ info, const TrimInfo *__
     for (uint32_t i = lane; i < hl; i += 64) hdr[ho + i] = name[i];
     for (uint32_t i = lane; i < ql; i += 64) qual[qo + i] = fq_stored_qual(line3, ql, i, rc);
     if (lane == 0) { seq_off[at] = so; hdr_off[at] = ho; qual_off[at] = qo; rlen[at] = (uint16_t)rl; }
+}
+// dg_set_umi only, behind k_trim_write (whose registers stay what they were): one wave per read of the input; a kept read's name gains sep, then the letters of
+// read 2k and of read 2k + 1, or the read's own when it stands alone.  The partner's line 1 is found through fq_read_place(k ^ 1).
+__global__ void __launch_bounds__(64)
+k_trim_umi_name(const FqText x, const FqInfo *__restrict__ info, const TrimUmi um, const TrimRead *__restrict__ win, const uint32_t *__restrict__ name_len, const uint32_t *__restrict__ loc,
+                uint32_t stride, const unsigned long long *__restrict__ tile_base, uint32_t n_tiles, char *__restrict__ hdr)
+{
+    if (info->status != FQ_OK) return;
+    const uint32_t n_reads = info->n_reads, k = blockIdx.x, lane = threadIdx.x;
+    if (k >= n_reads || !(win[k].flags & TR_F_KEEP)) return;
+    const uint32_t ho = (uint32_t)tile_base[(size_t)n_tiles + k / FQ_THREADS] + loc[(size_t)stride + k], hl = name_len[k];
+    if (um.on) {                                                    // the name's suffix: sep, then the letters of read 2k and of read 2k + 1, or the read's own when it stands alone
+        const bool two = x.two != 0, partnered = trim_umi_partnered(k, two, um.flags, n_reads);
+        if (lane == 0) hdr[ho + hl] = (char)um.sep;
+        uint32_t o = ho + hl + 1u;
+#pragma unroll 1
+        for (uint32_t j = 0; j < (partnered ? 2u : 1u); j++) {
+            const uint32_t kk = partnered ? (k & ~1u) + j : k;
+            int ff; uint32_t rr, ss;
+            fq_read_place(kk, two, ff, rr);
+            const uint32_t ll = fq_dev_line(x, info, ff, 4ull * rr + 1, ss), n = um.len[trim_umi_slot(kk, two, ff, um.flags)];
+            const char *from = (const char *)x.t[ff] + ss;
+            for (uint32_t i = lane; i < n && i < ll; i += 64) hdr[o + i] = trim_umi_letter(from[i]);      // (a kept read's partner passed the rule: its line holds them)
+            o += n;
+        }
+    }
 }
 #endif
 #endif

@@ -43,6 +43,7 @@ struct Config {
     bool device_fastq = false;              // DART_DEVICE_FASTQ, unless -bo streams
     bool device_sj = false;                 // DART_DEVICE_SJ
     bool sort_bam = false, bam_index = false, mark_dups = false;       // DART_SORT_BAM, DART_BAM_INDEX, DART_MARK_DUPLICATES
+    int md_umi = 0; char md_umi_sep = '_';  // DART_MARKDUP_UMI: 0 = unset, 1 = exact, 2 = edit1; DART_MARKDUP_UMI_SEP (default: DART_UMI_SEP)
     int coverage = 0;                       // DART_COVERAGE: 0, 1 or 2
     uint32_t cov_exclude = 0x704u, cov_min_mapq = 0u;                  // DART_COVERAGE_EXCLUDE, DART_COVERAGE_MIN_MAPQ
     bool pileup = false;                    // DART_PILEUP
@@ -65,6 +66,9 @@ struct Config {
     bool trim = false;                      // any of DART_TRIM_ADAPTER, DART_TRIM_QUAL, DART_TRIM_QUAL5, DART_TRIM_POLY
     dg_trim trim_par;                       // the DART_TRIM_* switches as dg_set_trim takes them (flags: the library's pairing decides DG_TRIM_PAIRS)
     std::string trim_path;                  // <out>.trim.txt; empty = not asked for
+    bool umi = false;                       // DART_UMI
+    dg_umi umi_par;                         // DART_UMI, DART_UMI_SKIP, DART_UMI_SEP as dg_set_umi takes them (flags: the library's pairing decides DG_UMI_PAIRS)
+    bool cuts() const { return trim || umi; }      // the upload takes the trimmed path: what holds for DART_TRIM_* holds for DART_UMI
     int write_threads = 1;                  // DART_WRITE_THREADS, at least 1
     int fmt_threads = 0;                    // DART_FMT_THREADS, at least 1; 0 = unset (what -t leaves)
     bool write_mmap = false;                // DART_WRITE=mmap
@@ -163,6 +167,38 @@ struct Config {
             trim_par.poly_mask |= 1u << (at - "ACGT");
         }
         trim = trim_par.n_adapter[0] || trim_par.n_adapter[1] || trim_par.qual3 || trim_par.qual5 || trim_par.poly_mask;
+        return RUN;
+    }
+
+    // DART_UMI=<n1>[,<n2>] (the UMI's letters at the start of mate 1 / mate 2), DART_UMI_SKIP=<n1>[,<n2>] (linker bases behind them), DART_UMI_SEP (one byte, default _)
+    // into umi / umi_par; RUN, or 1 behind a value that cannot be used (said on err_f)
+    int parse_umi(const char *(*lookup)(const char *), FILE *err_f)
+    {
+        memset(&umi_par, 0, sizeof umi_par);
+        umi_par.sep = '_';
+        auto two = [&](const char *key, uint32_t to[2]) -> bool {
+            const char *v = lookup(key);
+            if (!v) return true;
+            const char *q = v;
+            for (int m = 0; m < 2; m++) {
+                char *end = nullptr;
+                errno = 0;
+                const unsigned long long x = strtoull(q, &end, 10);
+                if (!(q[0] >= '0' && q[0] <= '9') || errno || x > 1000ull || (*end && !(*end == ',' && m == 0))) { fprintf(err_f, "Error! %s=%s: one or two whole numbers from 0 to 1000, <n1>[,<n2>], are expected\n", key, v); return false; }
+                to[m] = (uint32_t)x;
+                if (!*end) break;
+                q = end + 1;
+            }
+            return true;
+        };
+        if (!two("DART_UMI", umi_par.len) || !two("DART_UMI_SKIP", umi_par.skip)) return 1;
+        if (const char *v = lookup("DART_UMI_SEP")) {
+            if (strlen(v) != 1 || strchr(" \t/ACGTN+-", v[0])) { fprintf(err_f, "Error! DART_UMI_SEP=%s: one byte that is no blank, tab, / or one of ACGTN+-\n", v); return 1; }
+            umi_par.sep = v[0];
+        }
+        umi = lookup("DART_UMI") != nullptr;
+        if (umi && (umi_par.len[0] + umi_par.len[1] == 0 || umi_par.len[0] + umi_par.len[1] > 21u)) { fprintf(err_f, "Error! DART_UMI=%s: the two lengths together are 1 to 21 letters\n", lookup("DART_UMI")); return 1; }
+        if (!umi && lookup("DART_UMI_SKIP")) { fprintf(err_f, "Error! DART_UMI_SKIP=%s needs DART_UMI: DART_UMI is missing\n", lookup("DART_UMI_SKIP")); return 1; }
         return RUN;
     }
 
@@ -266,6 +302,19 @@ struct Config {
             return 1;
         }
         if (mark_dups) md_path = std::string(out) + ".markdup.txt";
+        // DART_MARKDUP_UMI=exact|edit1 beside DART_MARK_DUPLICATES=1: the UMI behind the last DART_MARKDUP_UMI_SEP (default _; ':' for names that carry the UMI as their
+        // last field) of a read's name is part of a duplicate's signature (dg_bam_markdup_umi_finish); edit1 also joins UMIs one letter apart.  <out>.markdup.txt
+        // gains four counts.  Alone it would mark nothing: no output is begun.
+        if (const char *v = lookup("DART_MARKDUP_UMI")) {
+            md_umi = strcmp(v, "exact") == 0 ? 1 : strcmp(v, "edit1") == 0 ? 2 : 0;
+            if (!md_umi) { fprintf(err_f, "Error! DART_MARKDUP_UMI=%s: exact or edit1\n", v); return 1; }
+            if (!mark_dups) { fprintf(err_f, "Error! DART_MARKDUP_UMI=%s needs DART_MARK_DUPLICATES=1 (and with it DART_SORT_BAM=1): DART_MARK_DUPLICATES=1 is missing\n", v); return 1; }
+        }
+        if (const char *v = lookup("DART_UMI_SEP")) if (strlen(v) == 1) md_umi_sep = v[0];      // (the default: what DART_UMI appends; a value that cannot be used is refused further down)
+        if (const char *v = lookup("DART_MARKDUP_UMI_SEP")) {
+            if (strlen(v) != 1) { fprintf(err_f, "Error! DART_MARKDUP_UMI_SEP=%s: one byte\n", v); return 1; }
+            md_umi_sep = v[0];
+        }
         // DART_PILEUP=1 beside DART_SORT_BAM=1: the sorted file's variant-site table <out>.sites.tsv, allele counts built on the device from the sorted records and
         // the index's text (dg_bam_pileup_finish) in place of a `samtools mpileup` over the file; behind the duplicate marking when that is on.  DART_PILEUP_MIN_ALT
         // (default 2), DART_PILEUP_EXCLUDE (default 0x704) and DART_PILEUP_MIN_MAPQ (default 0) are the filter.  Without the sort there is nothing to pile up: no
@@ -354,7 +403,15 @@ struct Config {
                         streaming ? "DART_STREAMING is set" : bam && !device_bam ? "DART_DEVICE_BAM=1 is missing" : !device_fastq ? "DART_DEVICE_FASTQ=1 is missing" : "DART_DEVICE_SAM=1 is missing");
                 return 1;
             }
-            if (trim) trim_path = std::string(out) + ".trim.txt";
+            // DART_UMI: the inline UMI is cut inside the same upload and goes to the end of the read's name, where DART_MARKDUP_UMI reads it; the same needs, the same refusal
+            trc = parse_umi(lookup, err_f);
+            if (trc != RUN) return trc;
+            if (umi && !(device_fastq && (device_sam || device_bam) && !streaming)) {
+                fprintf(err_f, "Error! DART_UMI needs the device parser and a device formatter (DART_DEVICE_FASTQ=1 with DART_DEVICE_SAM=1, or with DART_DEVICE_BAM=1 and -bo): %s\n",
+                        streaming ? "DART_STREAMING is set" : bam && !device_bam ? "DART_DEVICE_BAM=1 is missing" : !device_fastq ? "DART_DEVICE_FASTQ=1 is missing" : "DART_DEVICE_SAM=1 is missing");
+                return 1;
+            }
+            if (cuts()) trim_path = std::string(out) + ".trim.txt";
         }
         // DART_DEVICE_SJ=1: the junction table is counted, sorted and printed on the device (dg_batch_accumulate_sj per batch, dg_sj_merge / dg_sj_finish at the end);
         // works in both pipelines, with -o and -bo alike.  Without the switch the ordered writer fills a std::map, as always.

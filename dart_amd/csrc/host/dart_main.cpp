@@ -753,8 +753,8 @@ static int run_library(Job &job, Output &o, size_t lib, LibPlan &plan)
         abandon_outputs(job.cfg, o, BEFORE_CLOSE);
         return 1;
     }
-    if (job.cfg.trim && !L.fast_host) {      // (untrimmed reads are never mapped silently)
-        fprintf(stderr, "\nError! DART_TRIM_*: %s takes the streaming pipeline (FASTA, a streamed .gz), where nothing is trimmed\n", f1);
+    if (job.cfg.cuts() && !L.fast_host) {      // (untrimmed reads are never mapped silently)
+        fprintf(stderr, "\nError! DART_TRIM_* / DART_UMI: %s takes the streaming pipeline (FASTA, a streamed .gz), where nothing is trimmed\n", f1);
         abandon_outputs(job.cfg, o, BEFORE_CLOSE);
         return 1;
     }
@@ -782,14 +782,21 @@ static int finish_sorted_bam(Job &job, Output &o)
     size_t n_sorted = 0, n_raw = 0; float fin_ms = 0.f;
     if ((rc = dg_bam_sort_finish(root, &n_sorted, &n_raw, &fin_ms))) return sort_fail(rc);
     // DART_MARK_DUPLICATES: the verdicts go into the sorted records before any piece is compressed
-    uint64_t md_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; float md_ms = 0.f; double t_md = 0.0;
+    // (DART_MARKDUP_UMI: with the UMI at the end of the name in the signature, and four more counts)
+    uint64_t md_stats[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; float md_ms = 0.f; double t_md = 0.0;
     if (job.cfg.mark_dups) {
         const double tm0 = now_s();
-        if ((rc = dg_bam_markdup_finish(root, 0u, md_stats, &md_ms))) return fail("\nError! DART_MARK_DUPLICATES=1: ", dg_last_error(root));
-        static const char *const md_names[8] = {"examined_records", "pairs", "fragments", "duplicate_pairs", "duplicate_fragments", "candidates_in_crowded_runs", "records_marked_duplicate", "largest_family"};
+        const int n_md = job.cfg.md_umi ? 12 : 8;
+        if (job.cfg.md_umi) {
+            dg_umi_rules rules; memset(&rules, 0, sizeof rules);
+            rules.max_edit = job.cfg.md_umi == 2 ? 1u : 0u; rules.sep = job.cfg.md_umi_sep;
+            if ((rc = dg_bam_markdup_umi_finish(root, &rules, 0u, md_stats, &md_ms))) return fail("\nError! DART_MARKDUP_UMI: ", dg_last_error(root));
+        } else if ((rc = dg_bam_markdup_finish(root, 0u, md_stats, &md_ms))) return fail("\nError! DART_MARK_DUPLICATES=1: ", dg_last_error(root));
+        static const char *const md_names[12] = {"examined_records", "pairs", "fragments", "duplicate_pairs", "duplicate_fragments", "candidates_in_crowded_runs", "records_marked_duplicate", "largest_family",
+                                                 "records_with_umi", "pair_families_of_several_umis", "umi_groups_absorbed", "crowded_umi_families"};
         FILE *mf = fopen(job.cfg.md_path.c_str(), "wb");
         bool ok = mf != nullptr;
-        for (int k = 0; k < 8 && ok; k++) ok = fprintf(mf, "%s\t%llu\n", md_names[k], (unsigned long long)md_stats[k]) > 0;
+        for (int k = 0; k < n_md && ok; k++) ok = fprintf(mf, "%s\t%llu\n", md_names[k], (unsigned long long)md_stats[k]) > 0;
         if (!(mf && fclose(mf) == 0 && ok)) return fail("Error while writing ", job.cfg.md_path.c_str());
         t_md = now_s() - tm0;
     }
@@ -1037,6 +1044,7 @@ static int write_trim_stats(const Job &job)
                                         "poly_bases", "too_short_reads", "mate_dropped_reads", "qual_skipped_reads"};
     std::string text;
     for (int k = 0; k < 14; k++) { text += key[k]; text += '\t'; text += std::to_string(job.trim_stats[k].load()); text += '\n'; }
+    if (job.cfg.umi) { text += "umi_bases\t" + std::to_string(job.trim_stats[14].load()) + "\numi_dropped_reads\t" + std::to_string(job.trim_stats[15].load()) + "\n"; }      // DART_UMI: the two sums of the cut
     FILE *tf = fopen(job.cfg.trim_path.c_str(), "wb");
     const bool ok = tf && fwrite(text.data(), 1, text.size(), tf) == text.size();
     if (!(tf && fclose(tf) == 0 && ok)) { remove(job.cfg.trim_path.c_str()); fprintf(stderr, "Error while writing %s\n", job.cfg.trim_path.c_str()); return 1; }
@@ -1151,7 +1159,7 @@ int main(int argc, char *argv[])
         if (txq.skipped_seq || txq.skipped_strand)
             fprintf(stderr, "DART_TX_QUANT: skipped %zu lines on sequences the index lacks and %zu with a strand other than + or -\n", txq.skipped_seq, txq.skipped_strand);
     }
-    if (cfg.trim) remove(cfg.trim_path.c_str());      // (no failed run leaves a table, a stale one included)
+    if (cfg.cuts()) remove(cfg.trim_path.c_str());      // (no failed run leaves a table, a stale one included)
     if ((rc = make_contexts(job, ix, gtf, rna, txq, n_gpu)) != RUN) return rc;
     job.start_up_s = now_s() - t_proc0;
     fprintf(stdout, "\nLoad the reference sequences...\n");
@@ -1178,7 +1186,7 @@ int main(int argc, char *argv[])
     if (cfg.gene_gtf && (rc = write_gene_table(job, gtf, gene_counted)) != RUN) return rc;
     uint64_t tx_summary[16] = {0}; float tx_ms[3] = {0.f, 0.f, 0.f};
     if (cfg.tx_gtf && (rc = write_tx_table(job, txq, tx_summary, tx_ms)) != RUN) return rc;
-    if (cfg.trim && (rc = write_trim_stats(job)) != RUN) return rc;
+    if (cfg.cuts() && (rc = write_trim_stats(job)) != RUN) return rc;
     for (auto x : job.clones) dg_destroy(x);
     for (auto x : job.roots) dg_destroy(x);
     if (job.total.total > 0) print_summary(job, ix, sj);
@@ -1187,7 +1195,7 @@ int main(int argc, char *argv[])
         for (int k = 0; k < 16; k++) fprintf(stderr, " %s=%llu", dg_tx_word_name(k), (unsigned long long)tx_summary[k]);
         fprintf(stderr, " acc_ms=%.3f compat_ms=%.3f classes_ms=%.3f em_ms=%.3f\n", job.tx_acc_ns.load() * 1e-6, (double)tx_ms[0], (double)tx_ms[1], (double)tx_ms[2]);
     }
-    if (cfg.timing && cfg.trim)
+    if (cfg.timing && cfg.cuts())
         fprintf(stderr, "[dart trim] reads_in=%llu reads_kept=%llu bases_in=%llu bases_kept=%llu kernels_ms=%.3f\n", job.trim_stats[0].load(), job.trim_stats[1].load(), job.trim_stats[2].load(),
                 job.trim_stats[3].load(), job.trim_kernel_us.load() * 1e-3);
     if (cfg.timing && cfg.gene_gtf)

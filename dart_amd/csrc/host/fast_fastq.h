@@ -702,7 +702,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
     if (batch_reads & 1) batch_reads++;
     const bool fq_device = gzp || (c.device_fastq && !explicit_order);      // (an entry without bases ends a chunk: the replayed order is not a byte range)
     st.fq_device = fq_device;
-    if (c.trim && !fq_device) { err = "DART_TRIM_*: this library falls back to the host's assembly (a record without bases), where nothing is trimmed"; return DG_ERR_ARG; }
+    if (c.cuts() && !fq_device) { err = "DART_TRIM_* / DART_UMI: this library falls back to the host's assembly (a record without bases), where nothing is trimmed"; return DG_ERR_ARG; }
     // the bytes of records [a, b) of a mapped file
     auto byte_range = [](const MappedFile &mf, const std::vector<FqRec> &v, size_t a, size_t b, const char *&p, size_t &n) {
         const size_t lo = a < v.size() ? (size_t)v[a].off : mf.n, hi = b < v.size() ? (size_t)v[b].off : mf.n;
@@ -803,6 +803,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
 
     std::vector<std::thread> mappers;
     for (size_t w = 0; w < job.ctx.size(); w++) mappers.emplace_back([&, w]() {
+        if (c.umi) { dg_umi u = c.umi_par; u.flags = pair_end ? DG_UMI_PAIRS : 0u; if (dg_set_umi(job.ctx[w], &u)) { std::lock_guard<std::mutex> lk(mu); failed = true; fail_rc = DG_ERR_ARG; err = dg_last_error(job.ctx[w]); } }
         if (c.trim) { dg_trim t = c.trim_par; t.flags = pair_end ? DG_TRIM_PAIRS : 0u; if (dg_set_trim(job.ctx[w], &t)) { std::lock_guard<std::mutex> lk(mu); failed = true; fail_rc = DG_ERR_ARG; err = dg_last_error(job.ctx[w]); } }
         while (true) {
             FastSlot *s;
@@ -830,7 +831,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
                 } else rc = dg_batch_upload_fastq(job.ctx[w], &ft, &got);
                 t_fq = now_s() - tu;
                 (void)dg_batch_fastq_device_ms(job.ctx[w], &fq_ms);
-                if (!rc && c.trim) {             // the batch is what the upload kept: every count behind it is the returned one
+                if (!rc && c.cuts()) {             // the batch is what the upload kept: every count behind it is the returned one
                     uint64_t ts[16]; float tms = 0.f;
                     (void)dg_batch_trim_stats(job.ctx[w], ts, &tms);
                     for (int k = 0; k < 16; k++) job.trim_stats[k] += ts[k];
@@ -933,6 +934,7 @@ static int run_fast_library(Job &job, const char *f1, const char *f2, FastqIndex
             { std::lock_guard<std::mutex> lk(mu); st.t_map += now_s() - tm - t_gather - t_call - t_dl - t_fq - t_gz_wait; st.t_gz_tail += t_gz_wait; st.t_fq_call += t_fq; st.t_fq_kernels += fq_ms * 1e-3; st.t_gather += t_gather; st.t_dev_call += t_call; st.t_dev_kernels += dev_ms * 1e-3; st.t_download += t_dl; st.n_batches++; if (s->rc) { failed = true; fail_rc = s->rc; err = s->err; } fmt_q[s->seqno] = s; }
             cv.notify_all();
         }
+        if (c.umi) (void)dg_set_umi(job.ctx[w], nullptr);
         if (c.trim) (void)dg_set_trim(job.ctx[w], nullptr);      // (the next library's check pass, and its pairing, start from an untrimmed context)
         { std::lock_guard<std::mutex> lk(mu); mappers_left--; }
         cv.notify_all();

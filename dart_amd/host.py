@@ -49,6 +49,14 @@ GENE_EXON = np.dtype([("chr", "<i4"), ("start", "<u4"), ("end", "<u4"), ("strand
 GENE_NONE, GENE_AMBIG = 0xFFFFFFFF, 0xFFFFFFFE
 
 
+class DgUmi(C.Structure):                                                                         # dg_umi
+    _fields_ = [("flags", C.c_uint32), ("len", C.c_uint32 * 2), ("skip", C.c_uint32 * 2), ("sep", C.c_char), ("pad", C.c_char * 3)]
+
+
+class DgUmiRules(C.Structure):                                                                    # dg_umi_rules
+    _fields_ = [("flags", C.c_uint32), ("max_edit", C.c_uint32), ("sep", C.c_char), ("pad", C.c_char * 3)]
+
+
 class GeneAnnot(C.Structure):
     _fields_ = [("n_genes", C.c_uint32), ("pad", C.c_uint32), ("n_exons", C.c_size_t), ("exons", C.c_void_p)]
 
@@ -313,6 +321,8 @@ def _load_lib():
         lib.dg_set_trim.argtypes = [vp, vp]
         lib.dg_batch_trim_stats.argtypes = [vp, vp, vp]
         lib.dg_trim_granules.argtypes = [vp]
+    if hasattr(lib, "dg_set_umi"):                           # (likewise: inline UMIs cut inside the FASTQ upload)
+        lib.dg_set_umi.argtypes = [vp, vp]
     if hasattr(lib, "dg_batch_format_bam"):                  # (likewise: BAM records and BGZF blocks on the device)
         lib.dg_batch_format_bam.argtypes = [vp, vp, C.c_uint32, vp, vp, vp, vp]
         lib.dg_batch_format_bam_resident.argtypes = [vp, C.c_int, C.c_uint32, vp, vp, vp, vp]
@@ -382,6 +392,10 @@ def _load_lib():
         lib.dg_bam_markdup_finish.argtypes = [vp, C.c_uint32, vp, vp]
         lib.dg_bam_markdup_device_ms.argtypes = [vp, vp, vp]
         lib.dg_bam_markdup_granules.argtypes = [vp]
+    if hasattr(lib, "dg_bam_markdup_umi_finish"):            # (likewise: UMI-aware duplicate marking)
+        lib.dg_bam_markdup_umi_finish.argtypes = [vp, vp, C.c_uint32, vp, vp]
+        lib.dg_bam_markdup_umi_device_ms.argtypes = [vp, vp, vp]
+        lib.dg_bam_markdup_umi_granules.argtypes = [vp]
     if hasattr(lib, "dg_bam_tags_finish"):                   # (likewise: MD / NM / ts on the sorted array)
         lib.dg_bam_tags_finish.argtypes = [vp, C.c_uint32, vp, vp, vp]
         lib.dg_bam_tags_device_ms.argtypes = [vp, vp]
@@ -639,6 +653,19 @@ class DartGPU:
             t.n_adapter[i] = len(a[i])
             C.memmove(t.adapter[i], a[i][:64], min(len(a[i]), 64))
         self._chk(self.lib.dg_set_trim(self.ctx, C.byref(t)), "dg_set_trim")
+
+    def set_umi(self, len1: int = 0, len2: int = 0, skip1: int = 0, skip2: int = 0, sep: bytes = b"_", pairs: bool = False, off: bool = False, flags: int | None = None):
+        """cut inline UMIs (the first len bases of a read, then skip bases of linker; slot 1: text 2's reads, or the odd reads of one text with pairs) inside every
+        following FASTQ upload of this context and append them to the stored names behind sep (dg_set_umi; the definition is in include/dartgpu.h).  off=True:
+        no cut.  flags: the raw word, for the error tests."""
+        if off:
+            self._chk(self.lib.dg_set_umi(self.ctx, None), "dg_set_umi")
+            return
+        u = DgUmi()
+        u.flags = (1 if pairs else 0) if flags is None else flags
+        u.len[0], u.len[1], u.skip[0], u.skip[1] = len1, len2, skip1, skip2
+        u.sep = sep if isinstance(sep, bytes) else sep.encode()
+        self._chk(self.lib.dg_set_umi(self.ctx, C.byref(u)), "dg_set_umi")
 
     def trim_stats(self):
         """the last upload's trimming statistics (dg_batch_trim_stats) -> [16] ints; self.trim_device_ms holds the trimming kernels' device time"""
@@ -1200,6 +1227,31 @@ class DartGPU:
         self._chk(self.lib.dg_bam_markdup_device_ms(self.ctx, split, C.byref(passes)), "dg_bam_markdup_device_ms")
         self.bam_markdup_device_ms_split, self.bam_markdup_passes = tuple(float(x) for x in split), int(passes.value)
         return self.bam_markdup_stats
+
+    # ---- UMI-aware duplicate marking of the sorted array (dg_bam_markdup_umi_*): bam_markdup_finish with the UMI at the end of the name in the signature ----
+    def bam_markdup_umi_granules(self):
+        """bam_markdup_granules and the largest family (groups of one position) that is clustered (dg_bam_markdup_umi_granules)"""
+        g = (C.c_int * 4)()
+        self._chk(self.lib.dg_bam_markdup_umi_granules(g), "dg_bam_markdup_umi_granules")
+        return tuple(int(x) for x in g)
+
+    def bam_markdup_umi_finish(self, max_edit: int = 0, sep: bytes = b"_", count_only: bool = False):
+        """marks the duplicates of the sorted array in place with the UMI behind the last `sep` of a name as part of the signature (dg_bam_markdup_umi_finish;
+        max_edit 1: UMIs one letter apart are clustered; count_only: decides and counts, writes no flag) -> the stats, also kept as self.bam_markdup_umi_stats =
+        bam_markdup_stats' first seven, the largest cluster, examined records with a UMI, pair families of several groups, absorbed groups, crowded families;
+        self.bam_markdup_umi_device_ms = the kernels' device time, self.bam_markdup_umi_device_ms_split = (record pass, mate sort and search, pair sorts, end
+        sorts, heads groups and families, clustering, flag writes, counting and emitting), self.bam_markdup_umi_passes = the sorter's passes"""
+        sep = sep.encode() if isinstance(sep, str) else bytes(sep)
+        if len(sep) != 1:
+            raise ValueError("sep is one byte")
+        rules = DgUmiRules(0, int(max_edit), sep, b"")
+        ms = C.c_float(0); st = (C.c_uint64 * 12)()
+        self._chk(self.lib.dg_bam_markdup_umi_finish(self.ctx, C.byref(rules), MD_COUNT_ONLY if count_only else 0, st, C.byref(ms)), "dg_bam_markdup_umi_finish")
+        self.bam_markdup_umi_stats, self.bam_markdup_umi_device_ms = tuple(int(x) for x in st), float(ms.value)
+        split = (C.c_float * 8)(); passes = C.c_int(0)
+        self._chk(self.lib.dg_bam_markdup_umi_device_ms(self.ctx, split, C.byref(passes)), "dg_bam_markdup_umi_device_ms")
+        self.bam_markdup_umi_device_ms_split, self.bam_markdup_umi_passes = tuple(float(x) for x in split), int(passes.value)
+        return self.bam_markdup_umi_stats
 
     # ---- MD / NM / ts on the sorted array (dg_bam_tags_*): behind bam_sort_finish (and bam_markdup_finish), before bam_sort_compress ----
     def bam_tags_granules(self):

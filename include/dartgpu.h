@@ -389,6 +389,28 @@ typedef struct {
     uint32_t n_adapter[2]; char adapter[2][64];  /* ACGT only */
 } dg_trim;
 int dg_set_trim(dg_ctx *, const dg_trim *);
+
+/* ---- inline UMIs cut inside the FASTQ upload (dart_amd/csrc/dg_trim.h): what `umi_tools extract` or `fastp --umi` do over the files in front of the mapper.  The
+ * first len[m] bases of a read are its UMI, the next skip[m] a linker; both leave the read, and the UMI's letters go to the end of the stored name, where
+ * dg_bam_markdup_umi_finish reads them.
+ *     slot       of a read: what picks its adapter in dg_set_trim: reads of text 2 take slot 1; the odd reads of one text take slot 1 under DG_UMI_PAIRS; every
+ *                other read slot 0
+ *     partners   reads 2k and 2k+1 when there are two texts or DG_UMI_PAIRS is set; a last read without a partner stands alone
+ *     cut        a read with line 1 = s[0..L) and slot m: u = len[m] + skip[m]; its UMI letters are s[0..len[m]) in upper case, anything outside ACGT as N; the
+ *                next skip[m] bases are dropped.  A read with L < u + 1 fails the rule: it and its partner are both dropped -- the rule is pairwise
+ *                whatever DG_TRIM_PAIRS says
+ *     name       the stored name gains sep, then the read's own letters when it stands alone, else the letters of read 2k followed by those of read 2k+1:
+ *                mates keep equal names.  (dg_batch_format_bam's refusal of names above 254 bytes applies to the longer name.)
+ *     order      the cut comes first: steps 1-4 of dg_set_trim work on s[u..L) and q[u..ql), "the whole read" meaning that remainder; step 1's condition
+ *                compares the untouched ql and L; the stored read is the final window.  dg_set_umi alone takes the trimmed upload path with every step off
+ *                and min_len 1; with no UMI set the trimmed path gives the bytes it gave, and the plain path keeps its six launches
+ *     stats      dg_batch_trim_stats [14]: the UMI and linker bases removed from reads that passed the rule; [15]: reads dropped by the rule, their own or
+ *                their partner's (such a read counts in neither [11] nor [12]).  Both are 0 when the rule is off
+ *   dg_set_umi   NULL: off.  Per context, not inherited by dg_clone.  DG_ERR_ARG with a text, the setting left as it was: a flag bit but DG_UMI_PAIRS;
+ *                len[0] + len[1] == 0 or > 21; len[m] + skip[m] > DG_MAX_RLEN; sep 0, a blank, a tab, '/' or one of ACGTN+-                          */
+#define DG_UMI_PAIRS 1u    /* one text holds pairs: reads 2k, 2k+1 are partners, odd reads take slot 1 */
+typedef struct { uint32_t flags; uint32_t len[2], skip[2]; char sep; char pad[3]; } dg_umi;
+int dg_set_umi(dg_ctx *, const dg_umi *);
 int dg_batch_trim_stats(dg_ctx *, uint64_t stats[16], float *device_ms);
 int dg_trim_granules(int out[2]);
 
@@ -605,8 +627,8 @@ int dg_bam_coverage_granules(int out[2]);
  *                with equal (lo, hi) the largest score survives, on equal scores the smallest rep; both records of every other pair get 0x400.
  *     fragments  a fragment with end key E is a duplicate when any pair has lo == E or hi == E, or another fragment with the same E has a larger score, or
  *                an equal score and a smaller index.
- * Optical duplicates, UMIs and the propagation to secondary or supplementary records are not done.
- *   dg_bam_markdup_finish     works in place on the array of the last dg_bam_sort_finish.  flags: DG_MD_COUNT_ONLY decides and counts but writes no flag; any
+ * Optical duplicates and the propagation to secondary or supplementary records are not done; UMIs are dg_bam_markdup_umi_finish's (below).
+ *   dg_bam_markdup_finish    works in place on the array of the last dg_bam_sort_finish.  flags: DG_MD_COUNT_ONLY decides and counts but writes no flag; any
  *                             other bit, or no valid sorted array (none finished, or a store call behind the finish; the text names dg_bam_sort_finish):
  *                             DG_ERR_ARG.  stats (may be NULL): [0] examined records, [1] pairs, [2] fragments, [3] duplicate pairs, [4] duplicate fragments,
  *                             [5] candidates in crowded runs, [6] records that leave with 0x400 = 2 [3] + [4], [7] the largest family: pairs sharing one
@@ -626,6 +648,43 @@ int dg_bam_coverage_granules(int out[2]);
 int dg_bam_markdup_finish(dg_ctx *, uint32_t flags, uint64_t stats[8], float *device_ms);
 int dg_bam_markdup_device_ms(dg_ctx *, float ms[6], int *n_passes);
 int dg_bam_markdup_granules(int out[3]);
+
+/* ---- UMI-aware duplicate marking of the sorted array, on the device (dart_amd/csrc/dg_umidup.h): dg_bam_markdup_finish with the unique molecular identifier
+ * at the end of a record's name as one more part of a duplicate's signature.  Highly expressed transcripts put many independent fragments on the same
+ * coordinates; marking by position alone flags real molecules as copies.  What `umi_tools dedup` would compute from the finished file, here before
+ * dg_bam_sort_compress; no umi_tools exists where this library is built and tested, so this text is what the tests pin (tests/umidup_inputs.py is its twin).
+ * THE DEFINITION.  Examined records, end key E, score, candidates, hash, runs, crowded runs, pairs, fragments, DG_ERR_RANGE and the treatment of the input's
+ * 0x400 bit are exactly those of dg_bam_markdup_finish.  Beyond them:
+ *     U          of an examined record: the name bytes behind the last `sep` of the l_read_name - 1 name bytes.  Valid when 1..21 bytes long and every byte one
+ *                of A C G T N + -; those take the codes 1..7, the first letter in the most significant 3-bit field: U = sum of code_i 8^(len - 1 - i), at most 63
+ *                bits and never 0.  Every other record has U = 0: no sep, an empty suffix, more than 21 bytes, any other byte (lower case too).  Mates share
+ *                their name, so a pair has one U.
+ *     pair families   the pairs with equal (lo, hi); a group: those with equal (lo, hi, U); its count: its pairs
+ *     end families    every pair gives two ends, (lo, U) and (hi, U), every fragment one, (E, U).  A family: the ends with equal E; a group: those with equal
+ *                (E, U), pair ends and fragments alike; its count: its ends
+ *     clustering one family's groups each get a root.  max_edit 0: every group is its own root.  A family of more than 64 groups is CROWDED: every group is
+ *                its own root (the family is counted for either max_edit).  Else the groups are walked by count descending, then U ascending, and a group g joins
+ *                the FIRST earlier group r for which all hold: r is a root; U_r != 0 and U_g != 0; both UMIs have the same length; their letters differ in at most
+ *                one place; count_r >= 2 count_g - 1.  Without such an r, g is a root.  One hop only: a group whose only neighbour has itself been absorbed
+ *                stays a root (a stated limit against the chains of umi_tools' directional method).
+ *     verdicts   among the pairs of a family with equal root the largest score survives, on equal scores the smallest rep; both records of every other such
+ *                pair get 0x400.  A fragment is a duplicate when the groups of its end family that share its root hold a pair end, or another fragment with a
+ *                larger score, or an equal score and a smaller index.
+ * Consequence: when no examined record has a UMI, the bytes and stats[0..7] are those of dg_bam_markdup_finish on the same array, for either max_edit.
+ * Limits: Hamming distance 1 only, one hop, 21 letters, and no RX tag is written.
+ *   dg_bam_markdup_umi_finish      rules: NULL, max_edit > 1, sep == 0 or any rules->flags bit: DG_ERR_ARG.  flags, the sorted array, the failure texts, what a writing
+ *                             call forgets, the three waits and idempotence: as dg_bam_markdup_finish.  stats (may be NULL): [0..6] as there; [7] the largest
+ *                             set of pairs sharing one (lo, hi, root); [8] examined records with U != 0; [9] pair families that hold more than one group; [10]
+ *                             groups absorbed by another group, pair and end families together; [11] crowded families, both kinds together.  The buffers are
+ *                             dg_bam_markdup_finish's and 8 bytes per record, 13 per end and 4 per two ends beside them.
+ *   dg_bam_markdup_umi_device_ms   the last finish's device time by stage: [0] the record pass, [1] the mate sort and search, [2] the pair sorts, [3] the end sorts,
+ *                             [4] heads, groups and families, [5] the clustering, [6] the flag writes, [7] counting and emitting; *n_passes (may be NULL): the
+ *                             sorter's passes (the UMI sorts take only the bits of the largest U, 4 per pass)
+ *   dg_bam_markdup_umi_granules    [0..2] as dg_bam_markdup_granules, [3] the largest family that is clustered (64)                                      */
+typedef struct { uint32_t flags; uint32_t max_edit /* 0 or 1 */; char sep /* '_' */; char pad[3]; } dg_umi_rules;
+int dg_bam_markdup_umi_finish(dg_ctx *, const dg_umi_rules *, uint32_t flags /* DG_MD_COUNT_ONLY */, uint64_t stats[12], float *device_ms);
+int dg_bam_markdup_umi_device_ms(dg_ctx *, float ms[8], int *n_passes);
+int dg_bam_markdup_umi_granules(int out[4]);
 
 /* ---- allele counts of the sorted array, on the device (dart_amd/csrc/dg_pileup.h): a table of the positions at which a read shows something else than the
  * reference.  The reference program has no such output: an opt-in extension (what `samtools mpileup`, `bam-readcount` or `pysamstats` would compute from the
